@@ -34,6 +34,29 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_IMAGE_BYTES = 48 << 20     # --dump-outputs: larger images are written as a fixed, seeded pixel sample (64 MB in all at most)
+DUMP_SAMPLE_SEED = 20261015
+DUMP_LOCKSTEP_EVERY = 4         # --dump-outputs on the fly path: the lock-step worker's stride (what the N > 1 calibration picks at c3)
+
+
+def dump_outputs(out_dir: str, image: np.ndarray, counts: dict) -> dict:
+    """Writes the last timed frame: `image` (H x W x 4 float32) whole, or a seeded sample of its pixels with their flat indices when it
+    exceeds DUMP_IMAGE_BYTES, and the frame's counts (float64, in `counts` order).  Returns {name: shape} of what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    arrays = {}
+    if img.nbytes <= DUMP_IMAGE_BYTES:
+        arrays["image"] = img
+    else:
+        px = img.reshape(-1, img.shape[-1])
+        n = DUMP_IMAGE_BYTES // (px[0].nbytes + 8)         # each sampled pixel + its float64 index
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], size=n, replace=False))
+        arrays["image_sample"] = px[idx]
+        arrays["image_sample_pixel"] = idx.astype(np.float64)
+    arrays["frame_counts"] = np.array([float(v) for v in counts.values()], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def build_workload(name: str, lod0_override: int | None = None):
@@ -297,7 +320,15 @@ def main():
     ap.add_argument("--item-order", type=int, default=-1, help="GSWT_OPT_ITEM_ORDER: 0 the compositor's work items in tile order, 1 heaviest first")
     ap.add_argument("--no-chunk-cull", action="store_true", help="GSWT_OPT_NO_CHUNK_CULL: project every chunk of the draws that survive the tile cull (A/B of the per-chunk frustum cull)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0, help="CPU baseline: fly-path frames are rendered by the oracle until this much time has gone (at most 24 frames)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                    "(float32 image, float64 frame counts; a seeded pixel sample when the image exceeds 48 MB).  On the fly path the worker then runs in "
+                    f"lock-step (every {DUMP_LOCKSTEP_EVERY}-th camera in order, swapped in 3 frames later) so that the same arguments give the same frame")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    # --dump-outputs on the fly path: the newest-camera-wins worker makes the last frame's draw list depend on thread timing; the
+    # lock-step worker (as N > 1 uses it) with a fixed stride makes it a function of the arguments alone
+    deterministic = bool(args.dump_outputs) and args.mode == "flypath" and not args.freeze_sort
     if args.timing_every <= 0:
         # 0 = auto.  Every third frame of a long run carries hipEvents (3 is coprime with the five frame slots: every slot is sampled).  A short
         # fly-path run on one GPU (the driver's --steps 20) carries NONE inside its timed region: ten samples, two per slot, were never a
@@ -551,7 +582,7 @@ def main():
             collect()
         stream.synchronize()
 
-    lockstep = world > 1            # (also with GSWT_BENCH_FAKE_WORLD)
+    lockstep = world > 1 or deterministic            # (also with GSWT_BENCH_FAKE_WORLD)
     first_tag = [0]
 
     def timed_run(n, worker, warm):
@@ -584,13 +615,13 @@ def main():
     if args.mode == "static" and args.static_at >= 0:
         swap_in(res_k)
     dev_worker = None
-    defer_swap = args.mode == "flypath" and world == 1 and not args.no_defer_swap
+    defer_swap = args.mode == "flypath" and not lockstep and not args.no_defer_swap
     if defer_swap:
         # a swap-in takes effect with the first frame submitted after its device-side list build has finished; frames submitted
         # meanwhile keep the previous SortData (the reference's swap-in also lands one frame after the worker's message)
         r.set_option(L.GSWT_OPT_DEFER_SWAP, 1)
-    elif args.mode == "flypath" and world > 1 and not args.no_defer_swap:
-        # N > 1: every rank must switch at the same frame, and "finished" is a per-GPU event: the swap-in lands with the third
+    elif args.mode == "flypath" and lockstep and not args.no_defer_swap:
+        # N > 1 (and --dump-outputs): every rank must switch at the same frame, and "finished" is a per-GPU event: the swap-in lands with the third
         # frame submitted after it on every rank (the build has two frames' time; a late one is waited for on the device)
         r.set_option(L.GSWT_OPT_DEFER_SWAP, 3)
     if args.mode == "flypath":
@@ -603,7 +634,9 @@ def main():
             swap_in(res)
     if args.freeze_sort and worker is not None:
         worker.close()
-    if lockstep and worker is not None and not args.freeze_sort:
+    if deterministic:
+        state["every"] = DUMP_LOCKSTEP_EVERY
+    elif lockstep and worker is not None and not args.freeze_sort:
         # The reference's worker takes the newest camera whenever it is free (state.rs:323-334); the lock-step stand-in for it hands over every
         # E-th camera, and E has to leave the worker the time of one event or the render thread waits for it: with E = 4, a 0.28-0.56 ms event
         # (sort_tiles, at times + build_tiles, at c3) holds a rank of eight, whose frames take ~75 us, at ~120 us per frame.  E = the event time over the
@@ -625,6 +658,12 @@ def main():
             e = int(et.item())
         state["every"] = int(os.environ.get("GSWT_BENCH_LOCKSTEP_EVERY", e))
     dt = timed_run(args.steps, None if args.freeze_sort else worker, args.warmup)
+    dump_image = None
+    if args.dump_outputs:
+        # the last timed step's frame, before the loops below reuse the output buffers: the gathered frame with N > 1, else its slot's buffer
+        last_out = frame if use_dist else outs[(args.warmup + args.steps - 1) % state["slots"]]
+        dump_image = last_out.cpu().numpy()
+        dump_counts = {k: stats["last"][k] for k in ("n_draws", "n_instanced", "n_visible", "n_pairs")}
     main_stats = {k: (list(v) if isinstance(v, list) else v) for k, v in stats.items()}
     if trace is not None:
         tb = trace[0][2]
@@ -801,7 +840,7 @@ def main():
                             "merged_groups_sorted": mg_built, "merged_groups_copied": mg_reused, "merged_groups_copied_from_older_than_previous_event": mg_deep,
                             "merged_groups_sorted_share": (mg_built / float(mg_built + mg_reused)) if (mg_built + mg_reused) else None,
                             "lockstep_every": (state["every"] if lockstep else None),
-                            "takes_effect": "first frame submitted after the event's device-side list build has finished (GSWT_OPT_DEFER_SWAP = 1)" if defer_swap else ("third frame submitted after the swap-in, on every rank (GSWT_OPT_DEFER_SWAP = 3)" if (world > 1 and args.mode == "flypath" and not args.no_defer_swap) else "next frame (which waits for the build on the device)"),
+                            "takes_effect": "first frame submitted after the event's device-side list build has finished (GSWT_OPT_DEFER_SWAP = 1)" if defer_swap else ("third frame submitted after the swap-in, on every rank (GSWT_OPT_DEFER_SWAP = 3)" if (lockstep and args.mode == "flypath" and not args.no_defer_swap) else "next frame (which waits for the build on the device)"),
                             "note": "SortData swap-ins inside the timed region (gswt_set_draws_merge_groups: draw-list upload into the spare draw set + merged lists built on the device, on a stream of their own)"},
             "worker_ms": worker_ms,
             "host_submit_ms_mean": float(np.mean(st["submit_ms"])) if st["submit_ms"] else None,
@@ -856,6 +895,7 @@ def main():
             # (its image is compared with the GPU's frame of the same draw list), then further cameras spread over the path until
             # --cpu-baseline-seconds have gone (at most 24 frames): a bounded sample of the same workload, not one frame.
             wang.set_device_merge(False)
+            r.set_option(L.GSWT_OPT_DEFER_SWAP, 0)          # the comparison frame below must use the draw list set right before it
             cam_ids = [last_i] + [int(k * len(cams) / 23.0) % len(cams) for k in range(23)] if len(cams) > 1 else [last_i]
             times, cmp_diff, nthr = [], None, None
             t_budget = time.perf_counter() + max(0.0, args.cpu_baseline_seconds)
@@ -886,6 +926,10 @@ def main():
                                              f"order = {args.order}): oracle/gswt_oracle.c, OpenMP over 16-row bands; the reference itself (Rust + wgpu) cannot run here",
                                    "frames_per_s_min_max": [1.0 / max(times), 1.0 / min(times)],
                                    "max_abs_diff_vs_gpu": cmp_diff}
+        if dump_image is not None:
+            res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dump_image, dump_counts),
+                                   "frame": args.warmup + args.steps - 1, "frame_counts": list(dump_counts),
+                                   "worker": (f"lock-step, every {state['every']}-th camera" if deterministic else None)}
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(res) + "\n").encode())
     if abi_comm:

@@ -10,7 +10,7 @@ def test_bench_help_lists_the_contract_options():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
     for opt in ("--gpus", "--steps", "--warmup", "--workload", "--mode", "--graph", "--no-graph", "--segment", "--in-flight", "--device-worker",
-                "--timing-every", "--static-steps", "--no-cpu-baseline"):
+                "--timing-every", "--static-steps", "--no-cpu-baseline", "--dump-outputs"):
         assert opt in r.stdout, opt
 
 
@@ -44,3 +44,35 @@ def test_auto_segment_fills_the_chip_and_keeps_dense_frames_long():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     for opt in ("--order", "--depth-sort", "--item-order", "--no-chunk-cull", "--vertex-stage", "--composite"):
         assert opt in r.stdout, opt
+
+
+def test_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: a small image is written whole, a large one as a fixed seeded pixel sample (with the flat pixel indices),
+    both with the frame counts, all float32 / float64 and 64 MB at most."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    counts = {"n_draws": 3, "n_instanced": 70, "n_visible": 50, "n_pairs": 900}
+    small = np.random.default_rng(1).random((24, 32, 4), dtype=np.float32)
+    shapes = bench.dump_outputs(str(tmp_path / "small"), small, counts)
+    assert shapes == {"image": [24, 32, 4], "frame_counts": [4]}
+    assert np.array_equal(np.load(tmp_path / "small" / "image.npy"), small)
+    fc = np.load(tmp_path / "small" / "frame_counts.npy")
+    assert fc.dtype == np.float64 and fc.tolist() == [3.0, 70.0, 50.0, 900.0]
+
+    big = np.zeros((2160, 3840, 4), dtype=np.float32)                # c5's frame: 133 MB
+    big[..., 0] = np.arange(2160 * 3840, dtype=np.float32).reshape(2160, 3840)
+    written = []
+    for k in range(2):
+        d = tmp_path / f"big{k}"
+        bench.dump_outputs(str(d), big, counts)
+        files = sorted(os.listdir(d))
+        assert files == ["frame_counts.npy", "image_sample.npy", "image_sample_pixel.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        written.append({f: np.load(d / f) for f in files})
+    smp, pix = written[0]["image_sample.npy"], written[0]["image_sample_pixel.npy"]
+    assert smp.dtype == np.float32 and pix.dtype == np.float64 and smp.shape == (pix.shape[0], 4)
+    assert np.all(np.diff(pix) > 0) and smp.shape[0] > 1_000_000
+    assert np.array_equal(smp[:, 0], pix.astype(np.float32))       # the sample holds the pixels its indices name
+    for f in written[0]:
+        assert np.array_equal(written[0][f], written[1][f]), f       # the same sample every run

@@ -3,7 +3,7 @@ of three LDS buffers with ready / consumed counters instead of two workgroup bar
 the image has to be the default compositor's BIT FOR BIT when nothing is cut (transmittance_eps = 0); with the early-out on, a wave stops
 accumulating weights below eps at a 128-pair boundary instead of a 256-pair one, so the two images may differ by less than eps (the
 per-wave exits are the delicate part of the protocol: a saturated wave keeps staging for the others).  Checked with a background colour
-+ depth buffer, debug colours, shards, short and long work items, at c3 and on the dense c3d.  Per-pixel math: /root/reference/src/gswt.wgsl:425-435; blend state renderer.rs:118-129."""
++ depth buffer, debug colours, shards, short and long work items, at c3 and on the dense c3d.  Per-pixel math: the reference's src/gswt.wgsl:425-435; blend state renderer.rs:118-129."""
 import numpy as np
 import pytest
 

@@ -11,7 +11,7 @@ reference's default HeightMap surface (c3h), with bench.py's early-out threshold
 Round 4: the product's DEFAULT vertex stage is the strict one (k_project<., ., STRICT>: +1 us of 71 at c3); the second test below shows
 that the default image then meets 1e-4 (+ the early-out cut) against the strict image on every pixel that holds no flipped coverage
 decision, at c3, c3h and c5.  The first test keeps the numbers of the v2 option (GSWT_OPT_STRICT_VS = 0), whose thin-ellipse term the
-table above lists.  /root/reference/src/gswt.wgsl:152-258,402-435."""
+table above lists.  The reference's src/gswt.wgsl:152-258,402-435."""
 import numpy as np
 import pytest
 

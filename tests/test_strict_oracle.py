@@ -8,7 +8,7 @@ tests pin is HOW FAR APART two legal evaluations are, at the sizes of BASELINE.j
   * everywhere else the images differ by the continuous part of the arithmetic: a few 1e-4 at a handful of pixels (thin
     ellipses: lambda2 = mid - radius cancels), below 1e-4 elsewhere.
 The 1e-4 contract of the product is against v2 (tests/test_baseline_configs_gpu.py); tests/test_strict_gpu.py repeats these
-bounds for the GPU image against the strict image.  Reference: /root/reference/src/gswt.wgsl:152-258,402-435."""
+bounds for the GPU image against the strict image.  Reference: src/gswt.wgsl:152-258,402-435."""
 import numpy as np
 import pytest
 

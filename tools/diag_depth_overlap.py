@@ -3,7 +3,7 @@
 after frames that leave the slots in other shapes (a dense scene, a small framebuffer with lists beyond the LDS buffer): prints every frame
 that differs and where.  usage: tools/diag_depth_overlap.py [first workload]   (GSWT_DIAG_REPS: repetitions, default 3)"""
 import os, sys, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from gswt_renderer_amd.renderer import GSWTRenderer
 from gswt_renderer_amd import _lib as L, host, workloads

@@ -4,7 +4,7 @@ path (two laps of 240 cameras, every `every`-th one a sort event), keys every me
 reference's cache key, wangtile.rs:575-593: (view, ordered member (lod, tile, other lod)) -- and counts the groups NOT found in (a) the
 last K events (what the retained draw sets give: K <= 9), (b) an LRU of N groups (the reference keeps 1 024).
 Usage: python tools/merge_cache_sim.py [workload] [every]      numbers quoted in DESIGN.md section 7"""
-import sys, time; sys.path.insert(0,'/root/repo')
+import os, sys, time; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import bench
 from collections import OrderedDict
@@ -15,7 +15,7 @@ w, wang, cu0, vp0, sort0 = bench.build_workload(name)
 W,H=w["width"],w["height"]; cam0=workloads.camera_for(name)
 wang.set_device_merge(True)
 cams=[]
-for pos,tgt in flypath.sample(flypath.load("c3" if name!="c5" else ("c5" if __import__('os').path.exists('/root/repo/gswt_renderer_amd/flypaths/c5.json') else "c3")), 240):
+for pos,tgt in flypath.sample(flypath.load("c3" if name!="c5" else ("c5" if os.path.exists(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gswt_renderer_amd', 'flypaths', 'c5.json')) else "c3")), 240):
     cams.append((tuple(float(x) for x in pos),)+host.camera_uniforms(pos,tgt,cam0["up"],cam0["fovy"],cam0["near"],cam0["far"],W,H))
 events=[]
 prev_vp=None

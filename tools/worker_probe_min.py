@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gswt_renderer_amd import host, synth, workloads, flypath
 from gswt_renderer_amd.pipeline import GSWTPipeline
 from gswt_renderer_amd.worker import DeviceWorker
