@@ -350,7 +350,6 @@ struct gswt_ctx {
     // -- 17.8 k positions for 10.7 k live chunks -- and c5's is 80 k of 366 k: 736-742 against 723-728 frames/s.  The cut is only taken where it
     // removes at least half of the grid.)
     uint32_t live_hint = 0;                // longest live list (per XCD) of the last finished frame; 0: none yet
-    int opt_no_grid_hint = 0;              // GSWT_NO_GRID_HINT=1 (environment): always the full grid
     uint32_t depth_max_tile_len = 0;       // longest tile list of the last finished depth-ordered frame (0: none yet -- try tile-local)
     unsigned long long stat_depth_local = 0, stat_depth_global = 0;     // depth-ordered frames enqueued on either path (re-runs included)
     int last_slot = 0;
@@ -360,7 +359,6 @@ struct gswt_ctx {
     // options
     int opt_no_prefilter = 0;
     int opt_debug_varyings = 0;
-    int opt_dbg_flags = 0;
     int opt_timing = 2;      // 0: no events, 1: frame + k_composite, 2: every stage
     // pairs per compositor work item (multiple of 256).  A tile's list is cut into segments that are composited in parallel and folded
     // by k_combine; a segment cannot know that the segments in front of it already saturated its pixels, so with the early-out on
@@ -559,7 +557,6 @@ try {
     // streams that share a queue run one behind the other.  The layout string names the order: c = ctx stream, 0-4 = frame slot
     // streams, s = the stream of the sort-event builds, p = a placeholder that is never used; a slot stream the string leaves out is
     // created when that slot is first used.  (GSWT_STREAM_LAYOUT overrides it: tuning only.)
-    c->opt_no_grid_hint = getenv("GSWT_NO_GRID_HINT") && atoi(getenv("GSWT_NO_GRID_HINT")) != 0;
     const char* layout = getenv("GSWT_STREAM_LAYOUT");
     if (!layout || !*layout) layout = kStreamLayout;
     for (const char* q = layout; *q; q++) {
@@ -644,12 +641,9 @@ try {
     switch (key) {
     case GSWT_OPT_NO_LOD_PREFILTER: c->opt_no_prefilter = value; c->draws_ready = false; return GSWT_OK;
     case GSWT_OPT_DEBUG_VARYINGS: c->opt_debug_varyings = value; return GSWT_OK;
-    case GSWT_OPT_DEBUG_FLAGS:
-#ifndef GSWT_EXPERIMENTS
-        // the ablation branches (wrong images by design) exist only in the measurement build: the product cannot be switched into them
-        if (value != 0) return fail(c, GSWT_ERR_BAD_ARG, "GSWT_OPT_DEBUG_FLAGS: this library was built without -DGSWT_EXPERIMENTS (make variants)");
-#endif
-        c->opt_dbg_flags = value; return GSWT_OK;
+    case GSWT_OPT_DEBUG_FLAGS:          // reserved
+        if (value != 0) return fail(c, GSWT_ERR_BAD_ARG, "GSWT_OPT_DEBUG_FLAGS is reserved: only 0 is accepted");
+        return GSWT_OK;
     case GSWT_OPT_TIMING: c->opt_timing = value; return GSWT_OK;
     case GSWT_OPT_NO_MERGE_REUSE: c->opt_no_merge_reuse = value; return GSWT_OK;
     case GSWT_OPT_DEFER_SWAP: c->opt_defer_swap = value; return GSWT_OK;
@@ -1417,7 +1411,6 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
     // (0 = "divide": a one-row map, map_wh_y == 1, would wrap the magic to 0 and the multiply-high quotient to 0 -- ADVICE r3)
     f.map_wh_y_magic = f.map_wh_y >= 2u && f.map_wh_y < 65536u ? 0xFFFFFFFFu / f.map_wh_y + 1u : 0u;
     f.tiles_x_magic = f.tiles_x > 0 && f.tiles_x < 65536 ? 0xFFFFFFFFu / (uint32_t)f.tiles_x + 1u : 0u;
-    f.dbg_flags = c->opt_dbg_flags;
 
     const int rsc = f.shard_count;                                  // row-shard count (1 in column mode)
     const int tiles_y_local = rsc > 1 ? (f.tiles_y - f.shard_index + rsc - 1) / rsc : f.tiles_y;
@@ -1508,7 +1501,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
                 d_radix_depth, (uint32_t)rz_depth, D.chunk_tab.p, D.n_chunks, c->static_boxes.p, c->opt_no_chunk_cull == 0 && !dbg, sl.live_cid.p);
     {
         uint64_t eff = D.n_launch;
-        if (!dbg && !sl.full_grid && !c->opt_no_grid_hint && c->live_hint) {
+        if (!dbg && !sl.full_grid && c->live_hint) {
             const uint64_t cut = 8ull * ((uint64_t)c->live_hint + c->live_hint / 2 + 256);
             if (cut * 2 <= eff) eff = cut;                     // (only where it removes most of the grid: a re-run costs a frame)
         }

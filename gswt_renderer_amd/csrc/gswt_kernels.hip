@@ -567,7 +567,7 @@ __global__ __launch_bounds__(256) void k_cull(const Frame f, const DrawDev* __re
 // overlap with the live ones: project stage 461 -> 433 us at c5, 87 -> 87 us at c3, frame rates unchanged.
 // -DGSWT_TRACE (tools/composite_trace.py): per work item, 100 MHz wall-clock stamps of the compositor's phases, left by lane 0 of wave 0:
 // [0] entry, [1] item known, [2] first batch staged (gathers have arrived), [3] last walk done, [4] pairs of the item,
-// [5] walk steps of wave 0 / of the wave, [6] ticks wave 0 spent in bin + walk, [7] hardware id (HW_ID | XCC_ID << 32)
+// [5] unused, [6] ticks wave 0 spent in bin + walk, [7] hardware id (HW_ID | XCC_ID << 32)
 #ifdef GSWT_TRACE
 constexpr uint32_t kTraceItems = 1u << 17;
 __device__ unsigned long long g_trace[kTraceItems * 8];
@@ -580,35 +580,15 @@ __device__ unsigned long long g_trace[kTraceItems * 8];
 // k_project's stamps (tools/project_trace.py), rows 8192 + launch position: [0] entry, [1] launch-table entry known, [2] list word arrived (lane 0),
 // [3] record arrived (lane 0, when it gets that far), [4] wave 0 through the projection, [5] behind the workgroup barrier, [6] end,
 // [7] hardware id (HW_ID | XCC_ID << 32) | chunk has pairs << 63
-// The quotients and roots of the projection are IEEE operations (correctly rounded: what the CPU checker reproduces).  -DGSWT_AB_FASTMATH
-// (measurement only, WRONG bits) swaps them for the 1-ulp hardware approximations: the upper bound of what a cheaper exact sequence could gain.
-// Ablation bits of GSWT_OPT_DEBUG_FLAGS (profiling: they cut a kernel short and the image is WRONG): compiled only into the measurement
-// build (-DGSWT_EXPERIMENTS, `make variants`); the product library has no such branches and refuses a nonzero flag word.
-#ifdef GSWT_EXPERIMENTS
-#define GSWT_ABL(F, BITS) (((F).dbg_flags & (BITS)) != 0)
-#else
-#define GSWT_ABL(F, BITS) false
-#endif
-#ifdef GSWT_AB_FASTMATH
-#define GSWT_RCP(X) __builtin_amdgcn_rcpf(X)
-#define GSWT_SQRT(X) __builtin_amdgcn_sqrtf(X)
-#else
-#define GSWT_RCP(X) (1.0f / (X))
-#define GSWT_SQRT(X) sqrtf(X)
-#endif
+// The quotients and roots of the projection are IEEE operations (correctly rounded: what the CPU checker reproduces).
 // STRICT (GSWT_OPT_STRICT_VS): A6..A10 as the shader text writes them (gswt.wgsl:152-258, 260-265, 402-419) -- every `*`, `+`, `-`, `/` its own
 // correctly rounded binary32 operation, matrix x vector as the left-to-right sum of column products, the full `scene_scale_mat * Vrk *
 // transpose(..)` and `transpose(T) * Vrk * T` matrix products, length = sqrt(x*x + y*y), normalize = v / length(v), no fused multiply-add:
 // the same operations, in the same order, as the CPU checker's strict mode, per splat bit for bit.  The default (sequence v2, DESIGN.md
 // section 4) evaluates the same expressions with fma chains and one reciprocal per quotient -- also legal WGSL, ~25 % fewer instructions,
 // and up to 5e-4 away from this one on thin ellipses (lambda2 = mid - radius cancels).
-// HALVES = 2 (round 4, measured and NOT the default: see launch_project): a 512-thread workgroup takes TWO consecutive entries of its XCD's
-// launch list, one per half (waves 0-3 / 4-7), side by side: the same body at the same 64 VGPRs, half the workgroups for the dispatcher
-// to hand out (the trace reads as dispatch-bound: 13.7 k workgroups of ~5 us started at ~260 per us keep ~1 300 of the chip's 2 048
-// workgroup slots filled; chunks IN SEQUENCE in one workgroup were slower: more registers, longer lifetime).  The halves meet only at
-// the barrier in front of the per-chunk sums.
-template <bool DEBUG, bool FULL, bool STRICT, int HALVES = 1>
-__global__ __launch_bounds__(256 * HALVES) void k_project(
+template <bool DEBUG, bool FULL, bool STRICT>
+__global__ __launch_bounds__(256) void k_project(
     const Frame f, const DrawDev* __restrict__ draws, const uint2* __restrict__ chunk_tab,
     const uint32_t* __restrict__ static_list, const uint32_t* __restrict__ merged_list,
     const uint32_t* __restrict__ merged_map, const uint4* __restrict__ tex,
@@ -617,8 +597,7 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
     Rec* __restrict__ recs, float* __restrict__ depths, uint32_t* __restrict__ block_sums, uint32_t* __restrict__ super_sums, uint32_t n_super,
     Varyings* __restrict__ dbg, float4* __restrict__ col_f)
 {
-    static_assert(HALVES == 1 || !DEBUG, "the debug-varyings build visits the static chunk table one entry per workgroup");
-    __shared__ uint32_t s_wsum[4 * HALVES], s_wvis[4 * HALVES];
+    __shared__ uint32_t s_wsum[4], s_wvis[4];
     // chunk_tab is in LAUNCH order, which is not slot order: workgroup b runs on XCD b % 8, and the table is laid out so
     // that all chunks of a draw land on one XCD (DrawDev::xcd) -- a draw's gathers stay inside one tile type's 313 KB of the
     // record table, so an XCD's 4 MB L2 then holds the few tile types it is working on instead of all 48 (6.6 MB).
@@ -626,8 +605,6 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
     // live count exit after one cached scalar load); the debug-varyings build visits every chunk through the static table.
     uint2 ct;
     uint32_t list_top = 0, list_cnt = 0;      // non-DEBUG: list index of this chunk's lane 0, list length | merged << 31 (from k_cull)
-    const uint32_t half = HALVES == 2 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0u;
-    bool active = true;                        // HALVES == 2: the upper half of the last workgroup of an odd list has no entry
 #ifdef GSWT_TRACE
     const bool tr_on = threadIdx.x == 0 && blockIdx.x < 49152u;
     const uint32_t tr_item = 8192u + blockIdx.x;
@@ -637,27 +614,24 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
         ct = chunk_tab[blockIdx.x];
         if (ct.y == 0xFFFFFFFFu) return;    // padding of a short per-XCD list
     } else {
-        const uint32_t x = blockIdx.x & 7u, k0 = (blockIdx.x >> 3) * (uint32_t)HALVES;
-        const uint32_t n_live = live_cnt[x * kSuperStride];
-        if (k0 >= n_live) return;
-        active = k0 + half < n_live;
-        const uint4 lt = live_tab[(size_t)min(k0 + half, n_live - 1u) * 8u + x];
+        const uint32_t x = blockIdx.x & 7u, k = blockIdx.x >> 3;
+        if (k >= live_cnt[x * kSuperStride]) return;
+        const uint4 lt = live_tab[(size_t)k * 8u + x];
         ct = make_uint2(lt.x, lt.y);
         list_top = lt.z; list_cnt = lt.w;
-        if (GSWT_ABL(f, 256)) return;      // ablation: nothing behind the launch-table entry
 #ifdef GSWT_TRACE
         { unsigned long long sink = lt.x + lt.w; asm volatile("" :: "s"(sink)); }
         GSWT_TR(1, GSWT_NOW())
 #endif
     }
     const DrawDev& d = draws[ct.x];
-    const uint32_t tid = HALVES == 2 ? (threadIdx.x & 255u) : threadIdx.x;
+    const uint32_t tid = threadIdx.x;
     const uint32_t cid = (d.slot_base + ct.y) >> 8;      // chunk id in slot space
     const bool s_culled = DEBUG ? draw_culled[ct.x] != 0u : false;
 
     const uint32_t r = ct.y + tid;
     const uint32_t slot = d.slot_base + r;
-    const bool in_list = DEBUG ? r < d.count : (active && r < (list_cnt & 0x7FFFFFFFu));
+    const bool in_list = DEBUG ? r < d.count : r < (list_cnt & 0x7FFFFFFFu);
     uint32_t count = 0;
     bool visible = false;
     uint2 my_rect = make_uint2(1u, 0u);     // empty: tx0 = 1 > tx1 = 0
@@ -684,7 +658,6 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
             if (f.band_cull && d.single_draw == 1u && cell_culled[map_id_m] != 0u) break;
             // A1 gswt.wgsl:38-42
             if (d.valid_lod_id >= 0 && d.valid_lod_id != (int32_t)lod_id) break;
-            if (GSWT_ABL(f, 128)) break;       // ablation: stop behind the list word, in front of the record gather
             // A2 :45-49
             const uint4 w0 = tex[2 * (size_t)gs_index];
             const uint4 w1 = tex[2 * (size_t)gs_index + 1];
@@ -910,7 +883,6 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
                     q[rr] = fmaf(f.GP[12 + rr], cv[3], fmaf(f.GP[8 + rr], cv[2], fmaf(f.GP[4 + rr], cv[1], f.GP[rr] * cv[0])));
                 float clip = 1.2f * q[3];
                 if (q[2] < -clip || q[0] < -clip || q[0] > clip || q[1] < -clip || q[1] > clip) break;
-                if (GSWT_ABL(f, 16)) break;               // ablation: stop after the frustum cull
                 // A7 :169-205
                 float K[9];
                 {
@@ -943,7 +915,7 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
                 float d0 = c0 - f.cam_pos[0], d1 = c1 - f.cam_pos[1], d2 = c2 - f.cam_pos[2];
                 float t[3];
                 for (int rr = 0; rr < 3; rr++) t[rr] = fmaf(f.V[8 + rr], d2, fmaf(f.V[4 + rr], d1, f.V[rr] * d0));
-                const float rz = GSWT_RCP(t[2]);
+                const float rz = 1.0f / t[2];
                 float txtz = t[0] * rz, tytz = t[1] * rz;
                 float limx = 1.3f * f.htan[0], limy = 1.3f * f.htan[1];
                 t[0] = clampf(txtz, -limx, limx) * t[2];
@@ -966,15 +938,15 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
                 float c11 = fmaf(A1[2], T1[2], fmaf(A1[1], T1[1], A1[0] * T1[0]));
                 float mid = 0.5f * (c00 + c11);
                 float hxx = 0.5f * (c00 - c11);
-                float radius = GSWT_SQRT(fmaf(hxx, hxx, c01 * c01));
+                float radius = sqrtf(fmaf(hxx, hxx, c01 * c01));
                 float l1 = mid + radius, l2 = mid - radius;
                 if (l2 < 0.0f) break;
                 float vx = c01, vy = l1 - c00;
-                float vlen = GSWT_SQRT(fmaf(vx, vx, vy * vy));
-                const float rv = GSWT_RCP(vlen);
+                float vlen = sqrtf(fmaf(vx, vx, vy * vy));
+                const float rv = 1.0f / vlen;
                 float ex = vx * rv, ey = vy * rv;
-                float smaj = fminf(GSWT_SQRT(2.0f * l1), 1024.0f);
-                float smin = fminf(GSWT_SQRT(2.0f * l2), 1024.0f);
+                float smaj = fminf(sqrtf(2.0f * l1), 1024.0f);
+                float smin = fminf(sqrtf(2.0f * l2), 1024.0f);
                 majx = smaj * ex; majy = smaj * ey;
                 minx = smin * ey; miny = smin * -ex;
                 // A9 :260-265, 402-410 (byte / 255 as byte * fl(1 / 255))
@@ -990,7 +962,7 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
                 }
                 // rgba *= clamp(z/w + 1, 0, 1): identically 1 for 0 <= z/w, kept for the debug output only
                 // A10 :415-419
-                const float rq = GSWT_RCP(q[3]);
+                const float rq = 1.0f / q[3];
                 ndcx = q[0] * rq; ndcy = q[1] * rq; depth = q[2] * rq;
                 if (DEBUG) {
                     float fade = clampf(fmaf(q[2], rq, 1.0f), 0.0f, 1.0f);
@@ -1013,11 +985,11 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
             visible = true;
             // depth_compare Less against the 1.0 clear when no proxy depth is bound (renderer.rs:182,436)
             if (!f.has_depth && !(depth < 1.0f)) { visible = false; break; }
-            const float ruu = GSWT_RCP(uu), rww = GSWT_RCP(ww);
+            const float ruu = 1.0f / uu, rww = 1.0f / ww;
             const float r_iux = ux * ruu, r_iuy = uy * ruu, r_ivx = wx * rww, r_ivy = wy * rww;
             // half extents of |p| <= 2, inflated by 1e-5 relative + 1e-3 px (conservative under f32 rounding)
-            float hx = fmaf(2.0f * GSWT_SQRT(fmaf(wx, wx, ux * ux)), 1.00001f, 0.001f);
-            float hy = fmaf(2.0f * GSWT_SQRT(fmaf(wy, wy, uy * uy)), 1.00001f, 0.001f);
+            float hx = fmaf(2.0f * sqrtf(fmaf(wx, wx, ux * ux)), 1.00001f, 0.001f);
+            float hy = fmaf(2.0f * sqrtf(fmaf(wy, wy, uy * uy)), 1.00001f, 0.001f);
             // pixels whose CENTRE lies inside the box: x in [ceil(c - h - 0.5), floor(c + h - 0.5)]
             float fx0 = ceilf(cxp - hx - 0.5f), fx1 = floorf(cxp + hx - 0.5f);
             float fy0 = ceilf(cyp - hy - 0.5f), fy1 = floorf(cyp + hy - 0.5f);
@@ -1028,7 +1000,6 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
                 tx0 = max(tx0, f.col0); tx1 = min(tx1, f.col1 - 1);          // column band of this ctx (the whole frame when off)
                 int rows = owned_rows(ty0, ty1, f.shard_index, f.shard_count);
                 count = tx1 >= tx0 ? (uint32_t)((tx1 - tx0 + 1) * rows) : 0u;
-                if (GSWT_ABL(f, 8)) count = 0;        // ablation: no record / rect stores, no pairs
                 if (count) {
                     my_rect = make_uint2((uint32_t)tx0 | ((uint32_t)tx1 << 16), (uint32_t)ty0 | ((uint32_t)ty1 << 16));
                     // 32-byte record: the inverse map, the centre, alpha and the packed colour (unpacked by the compositor's blend);
@@ -1052,12 +1023,10 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
     // (Round 4, measured and reverted: no barrier here -- every wave adding its own sums with fire-and-forget atomics (12 per workgroup
     // instead of 2 + a store, the rects stored whether or not the chunk emits pairs): k_project 57 -> 183 us at c3, 379 -> 561 at c5.  The
     // device-scope atomics of a kernel retire at ~1 per ns chip-wide whatever their addresses: 107 k more of them cost 125 us.)
-    const uint32_t w0 = 4u * half;             // first wave of this half in the workgroup's tables
-    if ((tid & 63u) == 0) { s_wsum[w0 + (tid >> 6)] = wsum; s_wvis[w0 + (tid >> 6)] = wvis; }
+    if ((tid & 63u) == 0) { s_wsum[tid >> 6] = wsum; s_wvis[tid >> 6] = wvis; }
     __syncthreads();
     GSWT_TR(5, GSWT_NOW())
-    if (!active) return;
-    const uint32_t bsum = s_wsum[w0] + s_wsum[w0 + 1u] + s_wsum[w0 + 2u] + s_wsum[w0 + 3u];
+    const uint32_t bsum = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
 #ifdef GSWT_TRACE
     { unsigned hwid, xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid)); asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
       GSWT_TR(7, (unsigned long long)hwid | ((unsigned long long)(xcc & 0xFFu) << 32) | ((unsigned long long)(bsum ? 1u : 0u) << 63)) }
@@ -1069,7 +1038,7 @@ __global__ __launch_bounds__(256 * HALVES) void k_project(
         // two-level sums, spread over n_chunks / 256 addresses (a single hot counter serialises the whole grid);
         // k_totals folds them into counters[0] (visible splats) and counters[1] (pairs)
         if (bsum) atomicAdd(&super_sums[(cid >> 8) * kSuperStride], bsum);
-        uint32_t v = s_wvis[w0] + s_wvis[w0 + 1u] + s_wvis[w0 + 2u] + s_wvis[w0 + 3u];
+        uint32_t v = s_wvis[0] + s_wvis[1] + s_wvis[2] + s_wvis[3];
         if (v) atomicAdd(&super_sums[(n_super + (cid >> 8)) * kSuperStride], v);
     }
     GSWT_TR(6, GSWT_NOW())
@@ -1205,7 +1174,7 @@ __device__ __forceinline__ uint32_t block_scan_and_sum(uint32_t v, uint32_t r, u
 // depths in composite order.  Round 4's first version sorted the emitting SPLATS by depth and emitted the pairs in that order (compaction,
 // three passes with the tile rect as payload, per-group pair counts, a scan, the emission: five more kernels and 111 us per c3 frame);
 // keying the PAIRS costs one more 4-byte word per pair in k_emit and in the depth passes and needs none of that.
-// TAB (the default since the end of round 4; GSWT_EMIT_TAB=0: four consecutive chunks of the frame): the workgroup takes four entries of k_cull's table of live chunks (k_project's launch table: one XCD's list, so the chunks are not
+// TAB (every frame with a live-chunk table; without one, in the debug-varyings frame: four consecutive chunks of the frame): the workgroup takes four entries of k_cull's table of live chunks (k_project's launch table: one XCD's list, so the chunks are not
 // neighbours in slot order -- they need not be: a chunk's first pair comes from the prefix arrays) instead of four consecutive chunks of
 // the frame.  At c3 73 % of the chunks are not live, and 39 % of this kernel's workgroup-time was workgroups that loaded four zeros and left
 // (tools/emit_trace.py); the price is one more dependent load in front of everything.  One frame at a time the kernel takes what it took (c3 18.9
@@ -2259,15 +2228,7 @@ struct CompLane {
     uint32_t lane, grp;
 };
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ v2f pk_splat(float s) { v2f r; r.x = s; r.y = s; return r; }
-
-#ifdef GSWT_EXPERIMENTS
-constexpr uint32_t kListStride = 288u;     // (the register-broadcast walk pads a list to whole rounds of 16 + one round of prefetch overrun)
-#else
 constexpr uint32_t kListStride = 264u;     // u16 entries per sub-block list: 256 hits + padding to an even count + 2 of prefetch overrun
-#endif
 constexpr uint32_t kNullRec = 256u;        // LDS record no pixel is ever inside (list padding)
 
 // bin + walk of one staged batch (n pairs in LDS) for one wave; updates the lane's (T, colour) state.
@@ -2277,7 +2238,7 @@ constexpr uint32_t kNullRec = 256u;        // LDS record no pixel is ever inside
 // List entries are LDS byte offsets of the records (u16), padded to an even length with the offset of a null record
 // whose r^2 is +inf: the walk needs neither a shift nor an `i < n` test nor a mid-pair exit.
 // BATCH: pairs per staged batch (256 in k_composite, 128 in k_composite_dw); the list stride and the null record's index follow it.
-template <bool EARLY, bool DEPTH, bool COLF, bool PK, bool DPPW, uint32_t BATCH = 256u>
+template <bool EARLY, bool DEPTH, bool COLF, uint32_t BATCH = 256u>
 __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLane& g, uint32_t n, const float4* s_q0, const float4* s_q1,
                                                    const float4* s_q2, const uint32_t* s_bb, const float* s_dep, uint16_t* wlist,
                                                    float dbuf, float t_eps, float& T, float& ar, float& ag, float& ab, bool& wave_live)
@@ -2310,74 +2271,7 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
     const uint32_t n_mine = grp == 0u ? cnt0 : grp == 1u ? cnt1 : grp == 2u ? cnt2 : cnt3;
     const uint32_t n_max = max(max(cnt0, cnt1), max(cnt2, cnt3));
     GSWT_STAT_BATCH(n_max, cnt0, cnt1, cnt2, cnt3)
-    if (GSWT_ABL(f, 1) || n_max == 0u) return;
-    if (DPPW && !DEPTH && !COLF && !PK) {
-        // ---- register-broadcast walk (measurement variant, -DGSWT_EXPERIMENTS only: 123-128 us against 95 us at c3, 312 against 242 at c3d) ----
-        // In rounds of 16 steps: lane j of a 16-lane group loads the record of its list's entry 16 r + j ONCE (one list read + two
-        // ds_read_b128 per lane and round, the next round's in flight during this one), and step j takes the record's dwords from lane j
-        // through DPP row_newbcast:j, folded into the consuming instructions (v_fmac_f32_dpp, v_cvt_f32_ubyteN_dpp; three v_mov_b32_dpp
-        // for the addends).  No LDS access and no LDS latency inside the steps: with the records fetched per step (a list entry, then two
-        // ds_read_b128 that depend on it) a step lasted as long as that round trip under load, ~200 cycles for ~19 VALU instructions.
-        // Same F4 sequence (v_fmac is the fused multiply-add of the scalar code), same blend order: the image is bit-identical.
-        const uint32_t gi = lane & 15u;
-        const uint32_t n_steps = (n_max + 1u) & ~1u;
-        const uint32_t n_pad = ((n_max + 15u) & ~15u) + 16u;                 // whole rounds + the prefetched one
-        for (uint32_t p = n_mine + gi; p < n_pad; p += 16u) my_list[p] = (uint16_t)(kNull * 16u);
-        const char* const q0b = reinterpret_cast<const char*>(s_q0);
-        const char* const q1b = reinterpret_cast<const char*>(s_q1);
-        uint32_t e = my_list[gi];
-        float4 c0 = *reinterpret_cast<const float4*>(q0b + e), c1 = *reinterpret_cast<const float4*>(q1b + e);
-        const float nl2e = -1.4426950408889634f;
-        float t0, t1, t2, t3;
-#define GSWT_DSTEP(J)                                                                                          \
-        asm volatile(                                                                                          \
-            "v_mov_b32_dpp %[t0], %[r2] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"                       \
-            "v_mov_b32_dpp %[t1], %[r6] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"                       \
-            "v_fmac_f32_dpp %[t0], %[r1], %[ly] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"               \
-            "v_fmac_f32_dpp %[t1], %[r5], %[ly] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"               \
-            "v_fmac_f32_dpp %[t0], %[r0], %[lx] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"               \
-            "v_fmac_f32_dpp %[t1], %[r4], %[lx] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"               \
-            "v_mul_f32 %[t2], %[t0], %[t0]\n"                                                                  \
-            "v_fmac_f32 %[t2], %[t1], %[t1]\n"                                                                 \
-            "v_cmp_ge_f32 vcc, 4.0, %[t2]\n"                                                                   \
-            "s_cbranch_vccz 1f\n"                                                                              \
-            "v_mov_b32_dpp %[t3], %[r3] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"                       \
-            "v_fmac_f32 %[t3], %[k], %[t2]\n"                                                                  \
-            "v_exp_f32 %[t3], %[t3]\n"                                                                         \
-            "v_cvt_f32_ubyte0_dpp %[t0], %[r7] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"                \
-            "v_cvt_f32_ubyte1_dpp %[t1], %[r7] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"                \
-            "v_cvt_f32_ubyte2_dpp %[t2], %[r7] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n"                \
-            "v_cndmask_b32 %[t3], 0, %[t3], vcc\n"                                                             \
-            "v_mul_f32 %[t3], %[T], %[t3]\n"                                                                   \
-            "v_fmac_f32 %[ar], %[t3], %[t0]\n"                                                                 \
-            "v_fmac_f32 %[ag], %[t3], %[t1]\n"                                                                 \
-            "v_fmac_f32 %[ab], %[t3], %[t2]\n"                                                                 \
-            "v_sub_f32 %[T], %[T], %[t3]\n"                                                                    \
-            "1:\n"                                                                                             \
-            : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [T] "+v"(T), [ar] "+v"(ar), [ag] "+v"(ag), [ab] "+v"(ab) \
-            : [r0] "v"(c0.x), [r1] "v"(c0.y), [r2] "v"(c0.z), [r3] "v"(c0.w), [r4] "v"(c1.x), [r5] "v"(c1.y), [r6] "v"(c1.z), [r7] "v"(c1.w), \
-              [lx] "v"(lx), [ly] "v"(ly), [k] "s"(nl2e)                                                        \
-            : "vcc");
-        for (uint32_t base = 0; base < n_steps; base += 16u) {
-            e = my_list[base + 16u + gi];                                   // the next round's entry and record
-            const float4 n0 = *reinterpret_cast<const float4*>(q0b + e), n1 = *reinterpret_cast<const float4*>(q1b + e);
-            const uint32_t left = n_steps - base;                           // even, >= 2
-            do {
-                GSWT_DSTEP(0) GSWT_DSTEP(1) if (left <= 2u) break;
-                GSWT_DSTEP(2) GSWT_DSTEP(3) if (left <= 4u) break;
-                GSWT_DSTEP(4) GSWT_DSTEP(5) if (left <= 6u) break;
-                GSWT_DSTEP(6) GSWT_DSTEP(7) if (left <= 8u) break;
-                GSWT_DSTEP(8) GSWT_DSTEP(9) if (left <= 10u) break;
-                GSWT_DSTEP(10) GSWT_DSTEP(11) if (left <= 12u) break;
-                GSWT_DSTEP(12) GSWT_DSTEP(13) if (left <= 14u) break;
-                GSWT_DSTEP(14) GSWT_DSTEP(15)
-            } while (0);
-            c0 = n0; c1 = n1;
-        }
-#undef GSWT_DSTEP
-        if (EARLY && ballot64(T >= t_eps) == 0ull) wave_live = false;
-        return;
-    }
+    if (n_max == 0u) return;
     // pad this group's list with the null record up to the wave's even step count (+2: the walk reads two entries ahead)
     const uint32_t n_steps = (n_max + 1u) & ~1u;
     for (uint32_t p = n_mine + (lane & 15u); p < n_steps + 2u; p += 16u) my_list[p] = (uint16_t)(kNull * 16u);
@@ -2391,34 +2285,7 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
 #define GSWT_REC1(O) (*reinterpret_cast<const float4*>(q1b + (O)))
 #define GSWT_REC2(O) (*reinterpret_cast<const float4*>(q2b + (O)))
 #define GSWT_RECD(O) (*reinterpret_cast<const float*>(dpb + ((O) >> 2)))
-// PK (measurement variant, -DGSWT_EXPERIMENTS only): the staged record is q0 = (iu.x, iv.x, iu.y, iv.y), q1 = (-ku, -kv, log2 alpha, rgba8),
-// so that F4's two coordinates are the two halves of packed operations -- (pu_y, pv_y) = v_pk_fma_f32((iu.y, iv.y), ly, (-ku, -kv)),
-// (p.x, p.y) = v_pk_fma_f32((iu.x, iv.x), lx, (pu_y, pv_y)) -- and the blend pairs (red, green) and (T, blue): (T, ab) += wgt * (-1, cb).
-// IEEE per component: the same image bit for bit, 15 VALU instructions per step instead of 19 -- and 5-7 % SLOWER (c3 104.6 against
-// 98.9 us, c3d 259.8 against 243.8): four v_pk_fma_f32 cost more than the eight scalar instructions they replace.
 #define GSWT_STEP(Q0, Q1, Q2, DV)                                                                   \
-    if (PK && !DPPW) {                                                                              \
-        v2f iy_, k_, ix_;                                                                           \
-        iy_.x = Q0.z; iy_.y = Q0.w; k_.x = Q1.x; k_.y = Q1.y; ix_.x = Q0.x; ix_.y = Q0.y;           \
-        const v2f pyv = pk_fma(iy_, pk_splat(ly), k_);                                              \
-        const v2f pp = pk_fma(ix_, pk_splat(lx), pyv);                                              \
-        const float r2 = fmaf(pp.y, pp.y, pp.x * pp.x);                                             \
-        bool cover = r2 <= 4.0f;                                                                    \
-        if (DEPTH) cover = cover && DV < dbuf;                                                      \
-        if (ballot64(cover) != 0ull) {                                                              \
-            const float e = __builtin_amdgcn_exp2f(fmaf(r2, -1.4426950408889634f, Q1.z));           \
-            const float Bv = cover ? e : 0.0f;                                                      \
-            const float wgt = T * Bv;                                                               \
-            const uint32_t cw = __float_as_uint(Q1.w);                                              \
-            v2f c01, acc01, acc23;                                                                  \
-            c01.x = COLF ? Q2.x : (float)(cw & 0xFFu); c01.y = COLF ? Q2.y : (float)((cw >> 8) & 0xFFu); \
-            mtb.y = COLF ? Q2.z : (float)((cw >> 16) & 0xFFu);                                      \
-            acc01.x = ar; acc01.y = ag; acc23.x = T; acc23.y = ab;                                  \
-            acc01 = pk_fma(pk_splat(wgt), c01, acc01);                                              \
-            acc23 = pk_fma(pk_splat(wgt), mtb, acc23);                                              \
-            ar = acc01.x; ag = acc01.y; T = acc23.x; ab = acc23.y;                                  \
-        }                                                                                           \
-    } else                                                                                          \
     {                                                                                               \
         const float pu_y = fmaf(Q0.y, ly, Q0.z);                                                    \
         const float pv_y = fmaf(Q1.y, ly, Q1.z);                                                    \
@@ -2429,12 +2296,10 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
         if (DEPTH) cover = cover && DV < dbuf;                                                      \
         GSWT_STAT_STEP(cover)                                                                       \
         /* the blend runs under EXEC masking (s_and_saveexec on the coverage mask, skipped when no lane is covered): round 2 predicated it   \
-           with a v_cndmask behind a wave-uniform ballot test; one VALU instruction less per step, 95.8 -> 93.0 us at c3 (round 3).           \
-           (DPPW && PK: that older form, kept as a measurement variant of the -DGSWT_EXPERIMENTS build) */                                   \
-        if ((DPPW && PK) ? ballot64(cover) != 0ull : cover) {                                       \
+           with a v_cndmask behind a wave-uniform ballot test; one VALU instruction less per step, 95.8 -> 93.0 us at c3 (round 3) */        \
+        if (cover) {                                                                                \
             const float e = __builtin_amdgcn_exp2f(fmaf(r2, -1.4426950408889634f, Q0.w));           \
-            const float Bv = (DPPW && PK) ? (cover ? e : 0.0f) : e;                                 \
-            const float wgt = T * Bv;                                                               \
+            const float wgt = T * e;                                                                \
             const uint32_t cw = __float_as_uint(Q1.w);                                              \
             ar = fmaf(wgt, COLF ? Q2.x : (float)(cw & 0xFFu), ar);                                  \
             ag = fmaf(wgt, COLF ? Q2.y : (float)((cw >> 8) & 0xFFu), ag);                           \
@@ -2442,7 +2307,6 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
             T = T - wgt;                                                                            \
         }                                                                                           \
     }
-    v2f mtb; mtb.x = -1.0f; mtb.y = 0.0f;        // (-1, blue): T - wgt = fma(wgt, -1, T) exactly
     {
         // (every list entry goes through an empty asm as soon as it is loaded: carried around the loop as a 16-bit value, the compiler
         // masks each one again before using it as an LDS address -- one VALU instruction per step; a 32-bit register it cannot look
@@ -2511,7 +2375,7 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
 // k_combine does: the image is bit-identical whichever workgroup that is.  (c) Workgroup 0 publishes the frame's counters to the host.
 // One ticket per multi-segment work item on ITS tile's word: ~700 atomics per c3 frame on ~250 addresses (a single frame-wide ticket
 // word would serialise at ~8 ns per atomic on the memory side).
-template <bool EARLY, bool DEPTH, bool COLF, bool PK, bool DPPW, bool FOLD = false>
+template <bool EARLY, bool DEPTH, bool COLF, bool FOLD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || COLF) ? 7 : 8, 8))) void k_composite(const Frame f, const uint2* __restrict__ ranges,
                                                    const uint32_t* __restrict__ item_base, const uint4* __restrict__ item_tab,
                                                    uint32_t seg, const uint32_t* __restrict__ vals, const Rec* __restrict__ recs,
@@ -2583,8 +2447,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     // the null record: p.x = +inf for every pixel (0 * l + inf), so r^2 = +inf and no pixel is ever inside
     if (tid == 0) {
         if (EARLY) s_dead = make_uint4(0u, 0u, 0u, 0u);
-        s_q0[kNullRec] = (PK && !DPPW) ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(0.f, 0.f, __builtin_inff(), 0.f);
-        s_q1[kNullRec] = (PK && !DPPW) ? make_float4(__builtin_inff(), 0.f, 0.f, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+        s_q0[kNullRec] = make_float4(0.f, 0.f, __builtin_inff(), 0.f);
+        s_q1[kNullRec] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (DEPTH) s_dep[DEPTH ? kNullRec : 0u] = 0.0f;
         if (COLF) s_q2[COLF ? kNullRec : 0u] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -2605,28 +2469,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
         }
     uint32_t slot_nxt = 0;
     const uint32_t last_pair = rg.y - 1u;
-    // profiling ablations of the gather chain (output is wrong): 32 = no `vals` level (the pair index stands in for the slot),
-    // 64 = no record gather (every pair reads record 0)
-    const bool abl_vals = GSWT_ABL(f, 32), abl_recs = GSWT_ABL(f, 64);
-#define GSWT_VAL(I) (abl_vals ? (I) : vals[(I)])
-    if (rg.x < rg.y && !GSWT_ABL(f, 4)) {
-        uint32_t slot0 = GSWT_VAL(min(rg.x + tid, last_pair));
-        if (abl_recs) slot0 = 0u;
+    if (rg.x < rg.y) {
+        const uint32_t slot0 = vals[min(rg.x + tid, last_pair)];
         GSWT_LOAD_REC(slot0)
         if (COLF) rd = col_f[slot0];
-        slot_nxt = GSWT_VAL(min(rg.x + 256u + tid, last_pair));
+        slot_nxt = vals[min(rg.x + 256u + tid, last_pair)];
     }
     for (uint32_t base = rg.x; base < rg.y; base += 256u) {
         const uint32_t n = min(256u, rg.y - base);
-        if (GSWT_ABL(f, 4)) break;                       // ablation: no staging at all
         if (tid < n) {
             // F3: per-(splat, tile) constants
             const float ox = fmaf(hW, rb.x, c0x), oy = fmaf(hHn, rb.y, c0y);
             const float nku = -fmaf(ra.x, ox, ra.y * oy);
             const float nkv = -fmaf(ra.z, ox, ra.w * oy);
             const float l2a = __builtin_amdgcn_logf(rb.z);                           // v_log_f32 = log2; log2(0) = -inf -> B = 0
-            s_q0[tid] = (PK && !DPPW) ? make_float4(ra.x, ra.z, ra.y, ra.w) : make_float4(ra.x, ra.y, nku, l2a);
-            s_q1[tid] = (PK && !DPPW) ? make_float4(nku, nkv, l2a, rb.w) : make_float4(ra.z, ra.w, nkv, rb.w);
+            s_q0[tid] = make_float4(ra.x, ra.y, nku, l2a);
+            s_q1[tid] = make_float4(ra.z, ra.w, nkv, rb.w);
             // Pixel half extents of |p| <= 2 from the inverse map: the quad axes are u = iu / |iu|^2, w = iv / |iv|^2 and the
             // box is 2 sqrt(u.x^2 + w.x^2) by 2 sqrt(u.y^2 + w.y^2).  Approximate reciprocals / roots (1 ulp) under a 1e-4
             // relative + 2e-3 px margin: the box only has to CONTAIN every pixel centre with r^2 <= 4 (it decides which
@@ -2661,13 +2519,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
         const unsigned long long tr_t0 = GSWT_NOW();
 #endif
         {
-            if (abl_recs) slot_nxt = 0u;
             GSWT_LOAD_REC(slot_nxt)
             if (COLF) rd = col_f[slot_nxt];
-            slot_nxt = GSWT_VAL(min(base + 512u + tid, last_pair));
+            slot_nxt = vals[min(base + 512u + tid, last_pair)];
         }
-        if (wave_live && !GSWT_ABL(f, 2))               // ablation bit 2: stage only
-            composite_bin_walk<EARLY, DEPTH, COLF, PK, DPPW>(f, cl, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, wave_live);
+        if (wave_live)
+            composite_bin_walk<EARLY, DEPTH, COLF>(f, cl, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, wave_live);
 #ifdef GSWT_TRACE
         tr_walk += GSWT_NOW() - tr_t0;
 #endif
@@ -2773,9 +2630,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
 // LDS 18.4 KB (k_composite: 17.9 KB): 8 workgroups per CU.
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t lds_peek(const uint32_t* p) { return *reinterpret_cast<const volatile uint32_t*>(p); }
-#ifndef GSWT_DW_SLEEP
-#define GSWT_DW_SLEEP 1        // s_sleep units (64 clocks) between two polls of a counter
-#endif
+constexpr int kDwSleep = 1;            // s_sleep units (64 clocks) between two polls of a counter
 
 template <bool EARLY, bool DEPTH, bool COLF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : DEPTH ? 7 : 8, 8))) void k_composite_dw(const Frame f,
@@ -2865,7 +2720,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
                 if (ks > k) break;                      // not needed yet: try again after the next walk
                 while (lds_peek(&s_done[sb]) < need) {
                     if (EARLY && lds_peek(&s_dead) == 4u) { all_dead = true; break; }
-                    __builtin_amdgcn_s_sleep(GSWT_DW_SLEEP);
+                    __builtin_amdgcn_s_sleep(kDwSleep);
                 }
                 if (all_dead) break;
             }
@@ -2905,14 +2760,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
             const uint32_t target = 2u * (ku + 1u);
             while (lds_peek(&s_staged[kb]) < target) {
                 if (EARLY && lds_peek(&s_dead) == 4u) { all_dead = true; break; }
-                __builtin_amdgcn_s_sleep(GSWT_DW_SLEEP);
+                __builtin_amdgcn_s_sleep(kDwSleep);
             }
             if (all_dead) break;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
         const uint32_t n = min(B, n_pairs - k * B);
         if (wave_live)
-            composite_bin_walk<EARLY, DEPTH, COLF, false, false, B>(f, cl, n, s_q0 + kb * BS, s_q1 + kb * BS, s_q2 + (COLF ? kb * BS : 0u), s_bb + kb * B,
+            composite_bin_walk<EARLY, DEPTH, COLF, B>(f, cl, n, s_q0 + kb * BS, s_q1 + kb * BS, s_q2 + (COLF ? kb * BS : 0u), s_bb + kb * B,
                                                                     s_dep + (DEPTH ? kb * BS : 0u), wlist, dbuf, t_eps, T, ar, ag, ab, wave_live);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if (lane == 0u) {
@@ -2947,10 +2802,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
         if (orow < out_rows) out[(size_t)orow * f.out_w + (px2 - f.out_x0)] = o;
     }
 }
-
-#ifdef GSWT_EXPERIMENTS
-#include "gswt_composite_exp.hip"      // compositor variants of round 3 (measured, not shipped)
-#endif
 
 // Folds the per-segment partials of multi-segment tiles: (C1,T1) o (C2,T2) = (C1 + T1*C2, T1*T2).
 // One workgroup per tile, same lane -> pixel mapping as k_composite.
@@ -3065,16 +2916,9 @@ void launch_project(hipStream_t s, bool debug, const Frame& f, const DrawDev* dr
     if (n_chunks == 0) return;
     const uint32_t n_super = n_chunks / 256u + 1u;      // super_sums = [pairs x 16 n_super][visible x 16 n_super][exclusive pair prefix x n_super] (kSuperStride), zeroed by the caller
     const bool full = f.surface_type == 2u || f.draw_mode != 0u;
-    // GSWT_PROJECT_HALVES=2 (measurement only): 512-thread workgroups, two launch-list entries each.  Built in round 4 against the
-    // "dispatch-bound" reading of the kernel's trace and LOST at every size, same bits: c3 83.4 us against 76.2, c3h 101.5 / 97.2,
-    // c5 530 / 464 (profiles/r04_project_halves.txt) -- a workgroup now lives as long as the slower of its two chunks and holds 8 wave
-    // slots until then; halving what the dispatcher hands out does not pay for that.
-    static const bool wide = [] { const char* e = getenv("GSWT_PROJECT_HALVES"); return e && atoi(e) == 2; }();
 #define GSWT_LAUNCH_PROJECT_S(D, F, S)                                                                                         \
-    if (!D && wide) GSWT_LAUNCH((k_project<false, F, S, 2>), dim3(((n_launch / 8u + 1u) / 2u) * 8u), dim3(512), s, f, draws, chunk_tab, static_list, merged_list, \
-                       merged_map, tex, hmap, draw_culled, cell_culled, live_cnt, live_tab, rects, recs, depths, block_sums, super_sums, n_super, dbg, col_f); \
-    else GSWT_LAUNCH((k_project<D, F, S>), dim3(n_launch), dim3(256), s, f, draws, chunk_tab, static_list, merged_list,        \
-                       merged_map, tex, hmap, draw_culled, cell_culled, live_cnt, live_tab, rects, recs, depths, block_sums, super_sums, n_super, dbg, col_f)
+    GSWT_LAUNCH((k_project<D, F, S>), dim3(n_launch), dim3(256), s, f, draws, chunk_tab, static_list, merged_list,             \
+                merged_map, tex, hmap, draw_culled, cell_culled, live_cnt, live_tab, rects, recs, depths, block_sums, super_sums, n_super, dbg, col_f)
 #define GSWT_LAUNCH_PROJECT(D, F) do { if (strict) GSWT_LAUNCH_PROJECT_S(D, F, true); else GSWT_LAUNCH_PROJECT_S(D, F, false); } while (0)
     if (debug && full) { GSWT_LAUNCH_PROJECT(true, true); }
     else if (debug) { GSWT_LAUNCH_PROJECT(true, false); }
@@ -3094,9 +2938,8 @@ void launch_emit(hipStream_t s, const Frame& f, uint32_t n_chunks, const uint2* 
     const uint32_t n_super = n_chunks / 256u + 1u;      // [pairs x n_super][visible x n_super][exclusive pair prefix x n_super]
     const uint32_t* const excl = super_sums + 2u * kSuperStride * n_super;
     const float* const no_f = nullptr; uint32_t* const no_u = nullptr;
-    // over k_cull's table of live chunks (GSWT_EMIT_TAB=0: over every chunk of the frame, four consecutive ones per workgroup)
-    static const bool tab = !(getenv("GSWT_EMIT_TAB") && atoi(getenv("GSWT_EMIT_TAB")) == 0);
-    if (tab && live_cnt && live_cid && n_launch) {
+    // over k_cull's table of live chunks; without one (the debug-varyings frame) over every chunk of the frame, four consecutive ones per workgroup
+    if (live_cnt && live_cid && n_launch) {
         const uint32_t* const cnt2 = live_cnt + 8u * kSuperStride;               // k_totals' copy of the live counts
         const dim3 grid(((n_launch / 8u + kEmitGroup - 1u) / kEmitGroup) * 8u);
         if (dkeys) GSWT_LAUNCH((k_emit<true, true>), grid, dim3(256), s, f, rects, block_sums, excl, n_chunks, pair_cap, counters, keys, vals, depths, dkeys, krange, cnt2, live_cid);
@@ -3136,9 +2979,7 @@ int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* key
 {
     if (n_cap == 0) return 0;
     const uint32_t nblk = (n_cap + kSortBlock - 1) / kSortBlock, nsup = (nblk >> kSupShift) + 1;
-    // (GSWT_SORT_WIDE_MAX_M: tuning override of kSortWideMax in units of 2^20 items, read once)
-    static const uint32_t wide_max = [] { const char* e = getenv("GSWT_SORT_WIDE_MAX_M"); return e ? (uint32_t)atoi(e) << 20 : kSortWideMax; }();
-    const int threads = n_cap <= wide_max ? 512 : 256;
+    const int threads = n_cap <= kSortWideMax ? 512 : 256;
     int cur = 0;
     const int passes = (key_bits + 7) / 8;
     uint32_t* hist_rows = ws + (size_t)passes * ((size_t)256 * nsup + 256);      // behind the zeroed part (radix_ws_zero_words)
@@ -3231,70 +3072,7 @@ void launch_composite(hipStream_t s, const Frame& f, const uint2* ranges, const 
                 fold ? 1u : 0u, report_max ? 1u : 0u);
     }
     const bool early = f.t_eps > 0.0f, depth = f.has_depth != 0, colf = f.draw_mode != 0u;
-    // (the shipped compositors carry ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED; the experiment variants record them around the launch)
-#ifdef GSWT_EXPERIMENTS
-    if (ev_begin && (f.dbg_flags & (0x20000 | 0x4000 | 0x1000))) hipEventRecord(ev_begin, s);
-    if (f.dbg_flags & 0x20000) {         // experiment: two packed waves per item with shared staging (0x2000: 256-pair batches instead of 128)
-#define GSWT_LAUNCH_COMPOSITE_P2(E, D, C, NB2, OCC)                                                                             \
-        GSWT_LAUNCH((k_composite_p2<E, D, C, NB2, OCC>), dim3(max_items), dim3(128), s, f, item_base, item_tab, vals, recs, depths, col_f, \
-                    bg_rgba, bg_depth, out, partials, n_tiles, out_rows)
-        // 0x40000: the register allocator is told to fit 8 waves per SIMD (64 VGPRs) instead of taking what it likes
-#define GSWT_LAUNCH_COMPOSITE_P2N(E, D, C) { if (f.dbg_flags & 0x2000) GSWT_LAUNCH_COMPOSITE_P2(E, D, C, 2, 4); else if ((f.dbg_flags & 0x40000) && !D && !C) GSWT_LAUNCH_COMPOSITE_P2(E, false, false, 1, 8); else GSWT_LAUNCH_COMPOSITE_P2(E, D, C, 1, 4); }
-        if (colf) {
-            if (depth) GSWT_LAUNCH_COMPOSITE_P2N(false, true, true)
-            else GSWT_LAUNCH_COMPOSITE_P2N(false, false, true)
-        }
-        else if (early && depth) GSWT_LAUNCH_COMPOSITE_P2N(true, true, false)
-        else if (early) GSWT_LAUNCH_COMPOSITE_P2N(true, false, false)
-        else if (depth) GSWT_LAUNCH_COMPOSITE_P2N(false, true, false)
-        else GSWT_LAUNCH_COMPOSITE_P2N(false, false, false)
-#undef GSWT_LAUNCH_COMPOSITE_P2N
-#undef GSWT_LAUNCH_COMPOSITE_P2
-        if (ev_end) hipEventRecord(ev_end, s);
-        GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, item_base, partials, bg_rgba, out, n_tiles, out_rows, (const unsigned long long*)counters, host_counters);
-        return;
-    }
-    if (f.dbg_flags & 0x4000) {          // experiment: independent strip waves (0x8000: two strips per wave, 0x10000: four; 0x2000: 128-pair batches)
-        const uint32_t items8 = (max_items + 7u) & ~7u;
-#define GSWT_LAUNCH_COMPOSITE_S(E, D, C, NB, SPW)                                                                                  \
-        GSWT_LAUNCH((k_composite_s<E, D, C, NB, SPW>), dim3(items8 * (4u / SPW)), dim3(64), s, f, item_base, item_tab, vals, recs, depths, col_f, \
-                    bg_rgba, bg_depth, out, partials, n_tiles, out_rows)
-#define GSWT_LAUNCH_COMPOSITE_SN(E, D, C)                                                                                          \
-        {                                                                                                                          \
-            const int spw = (f.dbg_flags & 0x10000) ? 4 : (f.dbg_flags & 0x8000) ? 2 : 1;                                          \
-            if (f.dbg_flags & 0x2000) { if (spw == 4) GSWT_LAUNCH_COMPOSITE_S(E, D, C, 2, 4); else if (spw == 2) GSWT_LAUNCH_COMPOSITE_S(E, D, C, 2, 2); else GSWT_LAUNCH_COMPOSITE_S(E, D, C, 2, 1); } \
-            else { if (spw == 4) GSWT_LAUNCH_COMPOSITE_S(E, D, C, 1, 4); else if (spw == 2) GSWT_LAUNCH_COMPOSITE_S(E, D, C, 1, 2); else GSWT_LAUNCH_COMPOSITE_S(E, D, C, 1, 1); } \
-        }
-        if (early && !depth && !colf) GSWT_LAUNCH_COMPOSITE_SN(true, false, false)
-        else if (!early && !depth && !colf) GSWT_LAUNCH_COMPOSITE_SN(false, false, false)
-        else if (depth && !colf) { if (early) GSWT_LAUNCH_COMPOSITE_S(true, true, false, 1, 1); else GSWT_LAUNCH_COMPOSITE_S(false, true, false, 1, 1); }
-        else { if (depth) GSWT_LAUNCH_COMPOSITE_S(false, true, true, 1, 1); else GSWT_LAUNCH_COMPOSITE_S(false, false, true, 1, 1); }
-#undef GSWT_LAUNCH_COMPOSITE_SN
-#undef GSWT_LAUNCH_COMPOSITE_S
-        if (ev_end) hipEventRecord(ev_end, s);
-        GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, item_base, partials, bg_rgba, out, n_tiles, out_rows, (const unsigned long long*)counters, host_counters);
-        return;
-    }
-    if (f.dbg_flags & 0x1000) {          // experiment: the one-wave-per-item packed compositor (0x2000: 64-pair batches instead of 128)
-#define GSWT_LAUNCH_COMPOSITE_P(E, D, C, NB)                                                                                    \
-        GSWT_LAUNCH((k_composite_p<E, D, C, NB>), dim3(max_items), dim3(64), s, f, item_base, item_tab, vals, recs, depths, col_f, \
-                    bg_rgba, bg_depth, out, partials, n_tiles, out_rows)
-#define GSWT_LAUNCH_COMPOSITE_PN(E, D, C) { if (f.dbg_flags & 0x2000) GSWT_LAUNCH_COMPOSITE_P(E, D, C, 1); else GSWT_LAUNCH_COMPOSITE_P(E, D, C, 2); }
-        if (colf) {
-            if (depth) GSWT_LAUNCH_COMPOSITE_PN(false, true, true)
-            else GSWT_LAUNCH_COMPOSITE_PN(false, false, true)
-        }
-        else if (early && depth) GSWT_LAUNCH_COMPOSITE_PN(true, true, false)
-        else if (early) GSWT_LAUNCH_COMPOSITE_PN(true, false, false)
-        else if (depth) GSWT_LAUNCH_COMPOSITE_PN(false, true, false)
-        else GSWT_LAUNCH_COMPOSITE_PN(false, false, false)
-#undef GSWT_LAUNCH_COMPOSITE_PN
-#undef GSWT_LAUNCH_COMPOSITE_P
-        if (ev_end) hipEventRecord(ev_end, s);
-        GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, item_base, partials, bg_rgba, out, n_tiles, out_rows, (const unsigned long long*)counters, host_counters);
-        return;
-    }
-#endif
+    // (the compositors carry ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED)
     if (variant == 1) {                  // GSWT_OPT_COMPOSITE = 1: decoupled waves (k_composite_dw), same image bit for bit
 #define GSWT_LAUNCH_COMPOSITE_DW(E, D, C)                                                                                      \
         GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, item_base, item_tab, vals, recs, \
@@ -3310,7 +3088,7 @@ void launch_composite(hipStream_t s, const Frame& f, const uint2* ranges, const 
     }
     if (fold) {
 #define GSWT_LAUNCH_COMPOSITE_F(E, D, C)                                                                                       \
-        GSWT_LAUNCH_TIMED((k_composite<E, D, C, false, false, true>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, ranges, item_base, item_tab, seg, vals, recs, \
+        GSWT_LAUNCH_TIMED((k_composite<E, D, C, true>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, ranges, item_base, item_tab, seg, vals, recs, \
                            depths, col_f, bg_rgba, bg_depth, out, partials, n_tiles, out_rows, tile_tick, (const unsigned long long*)counters, host_counters)
         if (colf) { if (depth) GSWT_LAUNCH_COMPOSITE_F(false, true, true); else GSWT_LAUNCH_COMPOSITE_F(false, false, true); }
         else if (early && depth) GSWT_LAUNCH_COMPOSITE_F(true, true, false);
@@ -3320,16 +3098,10 @@ void launch_composite(hipStream_t s, const Frame& f, const uint2* ranges, const 
 #undef GSWT_LAUNCH_COMPOSITE_F
         return;
     }
-#define GSWT_LAUNCH_COMPOSITE_K(E, D, C, PK, DW)                                                                               \
-    GSWT_LAUNCH_TIMED((k_composite<E, D, C, PK, DW>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, ranges, item_base, item_tab, seg, vals, recs, \
+#define GSWT_LAUNCH_COMPOSITE(E, D, C)                                                                                         \
+    GSWT_LAUNCH_TIMED((k_composite<E, D, C>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, ranges, item_base, item_tab, seg, vals, recs, \
                        depths, col_f, bg_rgba, bg_depth, out, partials, n_tiles, out_rows, (uint32_t*)nullptr, (const unsigned long long*)nullptr, (unsigned long long*)nullptr)
-#ifdef GSWT_EXPERIMENTS      // measured and slower (profiles/r03_composite_variants.txt): 0x80000 the packed-coordinate step (15 VALU instead of 19), 0x100000 the register-broadcast (DPP) walk
-#define GSWT_LAUNCH_COMPOSITE(E, D, C) do { if ((f.dbg_flags & 0x180000) == 0x180000) GSWT_LAUNCH_COMPOSITE_K(E, D, C, true, true); /* 0x180000: the scalar step with the blend predicated by v_cndmask behind a ballot test (round 2's form) instead of EXEC masking */ \
-        else if (f.dbg_flags & 0x80000) GSWT_LAUNCH_COMPOSITE_K(E, D, C, true, false); else if (f.dbg_flags & 0x100000) GSWT_LAUNCH_COMPOSITE_K(E, D, C, false, true); else GSWT_LAUNCH_COMPOSITE_K(E, D, C, false, false); } while (0)
-#else
-#define GSWT_LAUNCH_COMPOSITE(E, D, C) GSWT_LAUNCH_COMPOSITE_K(E, D, C, false, false)
-#endif
-        if (colf) {                       // debug draw modes: float colours from the side buffer
+    if (colf) {                       // debug draw modes: float colours from the side buffer
         if (depth) GSWT_LAUNCH_COMPOSITE(false, true, true);
         else GSWT_LAUNCH_COMPOSITE(false, false, true);
     }
@@ -3338,7 +3110,6 @@ void launch_composite(hipStream_t s, const Frame& f, const uint2* ranges, const 
     else if (depth) GSWT_LAUNCH_COMPOSITE(false, true, false);
     else GSWT_LAUNCH_COMPOSITE(false, false, false);
 #undef GSWT_LAUNCH_COMPOSITE
-#undef GSWT_LAUNCH_COMPOSITE_K
     GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, item_base, partials, bg_rgba, out, n_tiles, out_rows, (const unsigned long long*)counters, host_counters);
 }
 

@@ -172,8 +172,7 @@ GSWT_API int gswt_set_stream(gswt_ctx *ctx, void *hip_stream);
 enum { GSWT_OPT_NO_LOD_PREFILTER = 1, GSWT_OPT_DEBUG_VARYINGS = 2,
        GSWT_OPT_SEGMENT = 3 /* pairs per compositor work item, multiple of 256 (default 1536; dense scenes with the early-out on
                                gain from up to 4096: a segment cannot skip what the segments in front of it already saturated) */,
-       GSWT_OPT_DEBUG_FLAGS = 4 /* ablation bits for profiling (the image is wrong when nonzero): only the measurement build
-                                   (-DGSWT_EXPERIMENTS, `make variants`) has them; the product library rejects a nonzero value */,
+       GSWT_OPT_DEBUG_FLAGS = 4 /* reserved: 0 is accepted, any other value returns GSWT_ERR_BAD_ARG */,
        GSWT_OPT_TIMING = 5 /* hipEvent timing: 0 none, 1 frame + k_composite, 2 every stage (default) */,
        GSWT_OPT_PAIR_CAP = 6 /* test hook: pin the pair-buffer capacity to `value` pairs until a frame overflows it (0: automatic) */,
        GSWT_OPT_NO_MERGE_REUSE = 7 /* gswt_set_draws_merge_groups re-sorts every merged group at every sort event instead of copying

@@ -141,7 +141,7 @@ def test_error_codes(renderer):
         renderer.render(cam, orc.scene_uniforms(num_lod=2), 64, 48, shard=(3, 2))
     with pytest.raises(GSWTError):
         renderer.set_option(L.GSWT_OPT_SEGMENT, 100)
-    # the profiling ablations (wrong images by design) are not in the product library: it cannot be switched into them
+    # GSWT_OPT_DEBUG_FLAGS is a reserved key: 0 is accepted, anything else is refused
     with pytest.raises(GSWTError) as e:
         renderer.set_option(L.GSWT_OPT_DEBUG_FLAGS, 4)
     assert e.value.code == L.GSWT_ERR_BAD_ARG

@@ -15,10 +15,8 @@ W, H = w["width"], w["height"]
 su = wang.scene_uniforms()
 r = GSWTRenderer(0)
 r.set_option(L.GSWT_OPT_TIMING, 0)
-if os.environ.get("GSWT_SEGMENT"):                 # kernel-variant sweeps: pairs per compositor work item, ablation / variant bits
+if os.environ.get("GSWT_SEGMENT"):                 # kernel-variant sweeps: pairs per compositor work item
     r.set_option(L.GSWT_OPT_SEGMENT, int(os.environ["GSWT_SEGMENT"], 0))
-if os.environ.get("GSWT_DBG_FLAGS"):
-    r.set_option(L.GSWT_OPT_DEBUG_FLAGS, int(os.environ["GSWT_DBG_FLAGS"], 0))
 if os.environ.get("GSWT_VS", "") == "v2":
     r.set_option(L.GSWT_OPT_STRICT_VS, 0)
 if os.environ.get("GSWT_NO_CHUNK_CULL"):
