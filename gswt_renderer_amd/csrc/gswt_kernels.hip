@@ -1259,7 +1259,9 @@ __global__ __launch_bounds__(256) void k_emit(const Frame f, const uint2* __rest
             return;
         }
         if (count == 0) continue;
-        const uint32_t dkey = __float_as_uint(dep[k]);               // depth in [0, 1]: bit order = value order
+        // depth in [0, 1]: bit order = value order once -0.0 (which k_project lets through) is made +0.0 -- the oracle's float
+        // comparison ties the two, its key 0x80000000 would sort last
+        const uint32_t dkey = __float_as_uint(dep[k] + 0.0f);
         if (DEPTH) { kmn = min(kmn, dkey); kmx = max(kmx, dkey); }
         if (sc > 1) {                                                // row shards: this rank's rows of the rect, numbered locally
             for (int ty = ty0 + ((f.shard_index - ty0 % sc) + sc) % sc; ty <= ty1; ty += sc) {

@@ -105,9 +105,23 @@ def test_preprocess_bit_exact(tiles):
                 assert np.array_equal(li[l][t][v], pp.gs_lod_id[l][t][v])
 
 
+def _far_cams(scale):
+    """Cameras |x|, |y| ~ scale from the origin (the reference recentres its map on the camera, wangtile.rs:1684, so after a long
+    flight every position is this far out), mixed signs; each second camera steps into the next tile so the map recentres."""
+    cams = []
+    for sx, sy in ((1, -1), (-1, 1), (-1, -1)):
+        x, y = sx * scale + 0.37e-3 * scale, sy * scale - 0.61e-3 * scale
+        cams += [((x, y, 3.0), (x + 1.0, y + 2.0, 2.5)), ((x + 4.3, y - 0.2, 3.0), (x + 5.0, y + 1.5, 2.5))]
+    return cams
+
+
+FAR_SCALES = [1e3, 1e4, 1e5]
+
+
 def test_camera_uniforms_bit_exact():
+    far = [(p, t, 640, 480) for s in FAR_SCALES for p, t in _far_cams(s)] + [(p, t, 333, 777) for p, t in _far_cams(1e5)]
     for (pos, tgt, W, H) in [((0, 0, 5), (0, 1, 5), 640, 480), ((4.2, 1.0, 3.0), (5.0, 3.0, 2.5), 1920, 1080),
-                             ((-3.3, 7.1, 0.4), (-2.0, -5.0, 1.0), 333, 777)]:
+                             ((-3.3, 7.1, 0.4), (-2.0, -5.0, 1.0), 333, 777)] + far:
         cu, vp = host.camera_uniforms(pos, tgt, (0, 0, 1), 45.0, 0.1, 2400.0, W, H)
         oc = orc.Camera(W, H, pos, tgt, [0, 0, 1])
         assert bytes(cu) == bytes(oc.uniforms())
@@ -176,6 +190,20 @@ def test_wangtile_worker_bit_exact(tiles, cfg):
     _check_worker(tiles, cfg, CAMS)
 
 
+@pytest.mark.parametrize("scale", FAR_SCALES)
+@pytest.mark.parametrize("cfg", CONFIGS[:2] + CONFIGS[3:4], ids=["flat", "heightmap", "heightmap-merge-dist"])
+def test_wangtile_worker_far_from_origin_bit_exact(tiles, cfg, scale):
+    """Flat and HeightMap maps recentred 1e3..1e5 from the origin (pos_to_coord / coord_to_pos and every tile offset out there)."""
+    centres = _check_worker(tiles, cfg, _far_cams(scale))
+    assert len(set(centres)) == 6 and min(abs(c) for cc in centres for c in cc) >= 0.9 * scale / 4.0, centres
+
+
+@pytest.mark.parametrize("cfg", SPHERE_CONFIGS[:2])
+def test_wangtile_worker_sphere_far_cameras_bit_exact(tiles, cfg):
+    """The Sphere map never shifts; cameras 1e3 world units out (inside the 2400 far plane) still see it."""
+    _check_worker(tiles, cfg, [((1e3, -2e3, 500.0), (0, 0, 0)), ((-1.9e3, 1.1e3, -700.0), (0, 0, 1.0)), ((3.0, -19.0, 6.0), (0, 0, 0))])
+
+
 def _check_worker(tiles, cfg, cams):
     verts, _, pp = tiles
     w = host.WangTile(host.TileSet.from_vertices(verts))
@@ -186,6 +214,7 @@ def _check_worker(tiles, cfg, cams):
     assert np.array_equal(np.array(conf.lod_transition_dist[:3], dtype=np.float32), np.array(ou.lod_transition_dist, dtype=np.float32))
     if cfg["surface_type"] == 1:
         assert np.array_equal(w.height_map().ravel(), ou.height_map)
+    centres = []
     with np.errstate(all="ignore"):
         for pos, tgt in cams:
             cu, vp = host.camera_uniforms(pos, tgt, (0, 0, 1), 45.0, 0.1, 2400.0, 320, 240)
@@ -196,6 +225,7 @@ def _check_worker(tiles, cfg, cams):
                 oids = [ow.tile_map[i][j].tid[1] for i in range(ou.tile_map_wh[0]) for j in range(ou.tile_map_wh[1])]
                 assert w.tile_ids().tolist() == oids
                 assert tuple(sd.center_coord) == tuple(osd["center_coord"])
+                centres.append(tuple(sd.center_coord))
                 assert (sd.splat_count, sd.blending_splat_count) == (osd["splat_count"], osd["blending_splat_count"])
                 assert list(sd.lod_instance_count[:3]) == osd["lod_instance_count"]
             s, os_ = w.sort_tiles(pos, vp), ow.sort_tiles(pos, vp)
@@ -229,6 +259,7 @@ def _check_worker(tiles, cfg, cams):
                     assert d.merged == 1 and d.merged_has_lod == (1 if val["single_lod_id"] == -1 else 0)
             osu = wo.scene_uniforms_from_data(ou, ow.center_coord)
             assert bytes(w.scene_uniforms()) == bytes(osu)
+    return centres
 
 
 def test_wang_constraints_and_graph_order_properties(tiles):
