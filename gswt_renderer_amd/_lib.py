@@ -173,6 +173,8 @@ SYMBOLS = {
     "gswt_render_fence": (C.c_int, [_P, C.c_int]),
     "gswt_frame_slots": (C.c_int, []),
     "gswt_skybox_configure": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "gswt_skybox_configure_equirect": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
+    "gswt_skybox_download": (C.c_int, [_P, _P]),
     "gswt_skybox_render": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "gswt_proxy_configure": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
     "gswt_proxy_render": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int]),

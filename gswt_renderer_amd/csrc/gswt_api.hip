@@ -50,6 +50,7 @@ void launch_tile_depth_sort(hipStream_t, const uint2*, uint32_t*, uint32_t*, uin
 uint32_t tile_depth_sort_cap();
 void launch_unshard(hipStream_t, const float4*, float4*, int, int, int, int, int);
 void launch_skybox(hipStream_t, const float*, float, float, int, int, int, int, const float4*, float4*);
+void launch_skybox_bake(hipStream_t, const SkyBakeArgs&, const float4*, float4*);
 void launch_proxy(hipStream_t, const ProxyArgs&, const float*, const float4*, float4*, float*);
 void launch_fill_f32(hipStream_t, float*, size_t, float);
 }  // namespace gswt
@@ -1758,6 +1759,68 @@ try {
     c->sky_size = face_size; c->sky_equi = equirectangular ? 1 : 0;
     return GSWT_OK;
 } GSWT_CATCH("gswt_skybox_configure")
+
+// The bake views of skybox.rs:584-617 as cgmath's Matrix4::look_at_rh(origin, target, up) builds them: f = normalize(target),
+// s = normalize(f x up), u = s x f (the view's rows are s, u, -f).  Their entries are 0 / +-1, so the f32 arithmetic is exact.
+static void sky_bake_basis(const float t[3], const float up[3], float out[9])
+{
+    const float fl = sqrtf((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+    const float f[3] = {t[0] / fl, t[1] / fl, t[2] / fl};
+    float s[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
+    const float sl = sqrtf((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]);
+    for (float& v : s) v /= sl;
+    const float u[3] = {s[1] * f[2] - s[2] * f[1], s[2] * f[0] - s[0] * f[2], s[0] * f[1] - s[1] * f[0]};
+    for (int k = 0; k < 3; k++) { out[k] = s[k]; out[3 + k] = u[k]; out[6 + k] = f[k]; }
+}
+
+namespace {
+struct DevTmp {           // a device buffer that lives for one call
+    void* p = nullptr;
+    ~DevTmp() { if (p) hipFree(p); }
+};
+}  // namespace
+
+int gswt_skybox_configure_equirect(gswt_ctx* c, const float* equi_rgba, int equi_width, int equi_height, int face_size)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!equi_rgba) return fail(c, GSWT_ERR_BAD_ARG, "gswt_skybox_configure_equirect: null panorama");
+    if (equi_width <= 0 || equi_width > 32768 || equi_height <= 0 || equi_height > 32768)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_skybox_configure_equirect: bad panorama size %d x %d", equi_width, equi_height);
+    if (face_size <= 0 || face_size > 16384) return fail(c, GSWT_ERR_BAD_ARG, "gswt_skybox_configure_equirect: bad face size %d", face_size);
+    hipSetDevice(c->device);
+    HIP_TRY(c, sync_all(c));
+    // the panorama is staged for this call only (up to 16 GiB at the size limit; the reference's 4096 x 2048 is 128 MiB)
+    const size_t ne = (size_t)equi_width * equi_height, nf = (size_t)6 * face_size * face_size;
+    DevTmp equi;
+    HIP_TRY(c, hipMalloc(&equi.p, ne * 16));
+    HIP_TRY(c, hipMemcpy(equi.p, equi_rgba, ne * 16, hipMemcpyHostToDevice));
+    HIP_TRY(c, null_stream_done());
+    HIP_TRY(c, c->sky_faces.ensure(nf));          // a failed allocation keeps the old buffer
+    // Up to here a failure leaves the previous skybox as it was; from here on the faces are being overwritten (or the old buffer
+    // is gone), so a failed bake leaves no skybox (gswt_skybox_render returns GSWT_ERR_STATE) rather than a half-written one.
+    c->sky_size = 0;
+    SkyBakeArgs a;
+    static const float target[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, -1}, {0, 0, 1}};
+    static const float up[6][3] = {{0, 1, 0}, {0, 1, 0}, {0, 0, 1}, {0, 0, -1}, {0, 1, 0}, {0, 1, 0}};
+    for (int i = 0; i < 6; i++) sky_bake_basis(target[i], up[i], a.basis[i]);
+    a.face_size = face_size; a.equi_w = equi_width; a.equi_h = equi_height;
+    launch_skybox_bake(c->stream, a, reinterpret_cast<const float4*>(equi.p), c->sky_faces.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->sky_size = face_size; c->sky_equi = 1;
+    return GSWT_OK;
+} GSWT_CATCH("gswt_skybox_configure_equirect")
+
+int gswt_skybox_download(gswt_ctx* c, float* faces_rgba_host)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!faces_rgba_host) return fail(c, GSWT_ERR_BAD_ARG, "gswt_skybox_download: null destination");
+    if (c->sky_size == 0) return fail(c, GSWT_ERR_STATE, "gswt_skybox_download before a skybox configure");
+    hipSetDevice(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(faces_rgba_host, c->sky_faces.p, (size_t)6 * c->sky_size * c->sky_size * 16, hipMemcpyDeviceToHost));
+    return GSWT_OK;
+} GSWT_CATCH("gswt_skybox_download")
 
 int gswt_skybox_render(gswt_ctx* c, const gswt_camera_uniforms* cam, int width, int height, float* out_rgba_dev)
 try {

@@ -131,6 +131,13 @@ struct SkyArgs {
     int width, height, face_size, equirectangular;
 };
 
+// k_skybox_bake (skybox.rs:490-668): per face i the rows s, u, f of the bake view look_at_rh(0, target_i, up_i) (skybox.rs:584-617);
+// the view ray of the face pixel at NDC (x, y) is s*x + u*y + f
+struct SkyBakeArgs {
+    float basis[6][9];    // [face] = s.xyz, u.xyz, f.xyz
+    int face_size, equi_w, equi_h;
+};
+
 struct ProxyArgs {
     // proxy.wgsl Uniforms
     float height_offset, tile_width, width_scale, clip_height, brightness;

@@ -2,6 +2,8 @@
 // per-pixel compute kernels: their outputs are the bg_rgba / bg_depth inputs of gswt_render.
 //
 //   k_skybox : skybox.wgsl vs_main + fs_main (cube map lookup along the pixel's view ray), skybox.rs:457-488
+//   k_skybox_bake : skybox.wgsl vs_bake + fs_bake (skybox.rs:490-668), configure time: an equirectangular HDR panorama baked
+//              into the cube map k_skybox samples
 //   k_proxy  : proxy.wgsl vs_main + fs_main + depth state (proxy.rs:96-134,366-447): the height-mapped ground grid.  Instead of
 //              pushing up to 2 x 2048^2 triangles through a rasteriser, every pixel casts its view ray at the height field
 //              (2-D DDA over the grid cells, two triangles per cell); the nearest fragment with depth in [0, 1] is exactly
@@ -274,6 +276,57 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
     proxy_tex_bilinear(tex + a.mip_off[l1], a.tex_size >> l1, uv[0], uv[1], c1);
     rgba[pi] = make_float4((c0[0] * (1.0f - fl) + c1[0] * fl) * a.brightness, (c0[1] * (1.0f - fl) + c1[1] * fl) * a.brightness,
                            (c0[2] * (1.0f - fl) + c1[2] * fl) * a.brightness, 1.0f);
+}
+
+// ---- skybox bake -----------------------------------------------------------------------------------
+// skybox.wgsl vs_bake + fs_bake: one render pass per face draws the unit cube from the origin with perspective(90 deg, 1, 0.1, 10)
+// and look_at_rh(0, target_i, up_i) into the face; the interpolated cube position is a positive multiple of the pixel's view ray,
+// s*ndc_x/P00 + u*ndc_y/P11 + f, and P00 = P11 cancels in the normalize.  Then SampleSphericalMap with its truncated constants
+// (skybox.wgsl:89-96), one bilinear tap of the Rgba32Float panorama (Linear, Repeat in u and v, level 0; row 0 = v 0) and the
+// Reinhard + 1/2.2 gamma tone map (skybox.wgsl:74-84).  One lane per output texel, a wave per 64 texels of a row (1 KB of float4).
+__global__ __launch_bounds__(256) void k_skybox_bake(const SkyBakeArgs a, const float4* __restrict__ equi, float4* __restrict__ faces)
+{
+    const int n = a.face_size;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), face = blockIdx.z;
+    if (x >= n || y >= n) return;
+    const float nx = ((float)x + 0.5f) / (float)n * 2.0f - 1.0f;
+    const float ny = 1.0f - ((float)y + 0.5f) / (float)n * 2.0f;
+    const float* b = a.basis[face];
+    float dx = (b[0] * nx + b[3] * ny) + b[6];
+    float dy = (b[1] * nx + b[4] * ny) + b[7];
+    float dz = (b[2] * nx + b[5] * ny) + b[8];
+    const float len = sqrtf((dx * dx + dy * dy) + dz * dz);
+    dx /= len; dy /= len; dz /= len;
+    const float u = atan2f(dz, dx) * 0.1591f + 0.5f;
+    const float v = asinf(fminf(fmaxf(dy, -1.0f), 1.0f)) * 0.3183f + 0.5f;
+    const int w = a.equi_w, h = a.equi_h;
+    const float sx = u * (float)w - 0.5f, sy = v * (float)h - 0.5f;
+    const float fx0 = floorf(sx), fy0 = floorf(sy);
+    const float tx = sx - fx0, ty = sy - fy0;
+    const int xa = p_wrap_repeat(fx0, w), ya = p_wrap_repeat(fy0, h);
+    const int xb = xa + 1 == w ? 0 : xa + 1, yb = ya + 1 == h ? 0 : ya + 1;
+    const float4 c00 = equi[(size_t)ya * w + xa], c10 = equi[(size_t)ya * w + xb];
+    const float4 c01 = equi[(size_t)yb * w + xa], c11 = equi[(size_t)yb * w + xb];
+    float c[3];
+    c[0] = (c00.x * (1.0f - tx) + c10.x * tx) * (1.0f - ty) + (c01.x * (1.0f - tx) + c11.x * tx) * ty;
+    c[1] = (c00.y * (1.0f - tx) + c10.y * tx) * (1.0f - ty) + (c01.y * (1.0f - tx) + c11.y * tx) * ty;
+    c[2] = (c00.z * (1.0f - tx) + c10.z * tx) * (1.0f - ty) + (c01.z * (1.0f - tx) + c11.z * tx) * ty;
+    const float gamma = (float)(1.0 / 2.2);          // the f32 constant of pow(color, vec3(1.0/2.2))
+    for (int k = 0; k < 3; k++) {
+        const float r = c[k] / (c[k] + 1.0f);
+        c[k] = exp2f(log2f(r) * gamma);              // pow(r, g) = exp2(g * log2 r); r = 0 -> 0
+    }
+    // Non-temporal: the 403 MB of faces are not read again by this kernel (k_skybox_bake, 4096 x 2048 -> 2048^2 x 6, rocprofv3
+    // mean of 22 calls: 227.3 us against 232.9 us with plain stores; profiles/skybox_bake_2048.txt)
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    const f4v o = {c[0], c[1], c[2], 1.0f};
+    __builtin_nontemporal_store(o, reinterpret_cast<f4v*>(faces) + ((size_t)face * n + y) * n + x);
+}
+
+void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi, float4* faces)
+{
+    const int n = a.face_size;
+    hipLaunchKernelGGL(k_skybox_bake, dim3((n + 63) / 64, (n + 3) / 4, 6), dim3(256), 0, s, a, equi, faces);
 }
 
 __global__ __launch_bounds__(256) void k_fill_f32(float* __restrict__ p, size_t n, float v)

@@ -223,6 +223,22 @@ class GSWTRenderer:
         f = np.ascontiguousarray(faces, dtype=np.float32)
         assert f.ndim == 4 and f.shape[0] == 6 and f.shape[1] == f.shape[2] and f.shape[3] == 4
         self._check(self._lib.gswt_skybox_configure(self._h, _ptr(f), f.shape[1], 1 if equirectangular else 0))
+        self._sky_size = f.shape[1]
+
+    def skybox_configure_equirect(self, equi: np.ndarray, face_size: int = 2048):
+        """Skybox::configure with an HDR panorama (skybox.rs:490-668): equi [h, w, 4] f32, linear, row 0 at the top, baked
+        on the device into a face_size^2 x 6 cube map that is then sampled as is_equi."""
+        e = np.ascontiguousarray(equi, dtype=np.float32)
+        assert e.ndim == 3 and e.shape[2] == 4
+        self._check(self._lib.gswt_skybox_configure_equirect(self._h, _ptr(e), e.shape[1], e.shape[0], int(face_size)))
+        self._sky_size = int(face_size)
+
+    def skybox_download(self) -> np.ndarray:
+        """The current cube map, [6, n, n, 4] f32 (+X -X +Y -Y +Z -Z)."""
+        n = getattr(self, "_sky_size", 0)
+        out = np.empty((6, n, n, 4) if n else (1,), np.float32)       # (before any configure the call fails before writing)
+        self._check(self._lib.gswt_skybox_download(self._h, _ptr(out)))
+        return out
 
     def skybox_render(self, camera, width: int, height: int, out_device_ptr: int):
         """Skybox::render (skybox.rs:457) into a device RGBA f32 buffer."""

@@ -324,6 +324,16 @@ typedef struct gswt_proxy_uniforms {
 /* Skybox::configure (skybox.rs:341-455): the cube map, 6 faces (+X -X +Y -Y +Z -Z) of face_size^2 RGBA f32 texels
  * (host pointer).  `equirectangular` is Skybox.is_equi (skybox.wgsl:35-38). */
 GSWT_API int gswt_skybox_configure(gswt_ctx *ctx, const float *faces_rgba, int face_size, int equirectangular);
+/* Skybox::configure with an HDR panorama (skybox.rs:490-668, skybox.wgsl:62-96): bakes the equirectangular image
+ * (host pointer, equi_width x equi_height RGBA f32, row-major, linear HDR, row 0 at the top; alpha ignored) into the
+ * cube map on the device -- per texel the face's view ray, SampleSphericalMap, one bilinear Repeat tap, Reinhard and
+ * 1/2.2 gamma -- and sets is_equi.  The reference bakes at face_size = CUBEMAP_RESO = 2048.  The panorama is staged in
+ * a temporary device buffer for the call only.  GSWT_ERR_BAD_ARG (nothing launched, previous skybox kept) for a null
+ * pointer, equi_width / equi_height outside 1..32768 or face_size outside 1..16384. */
+GSWT_API int gswt_skybox_configure_equirect(gswt_ctx *ctx, const float *equi_rgba, int equi_width, int equi_height, int face_size);
+/* Copies the current cube map to the host: 6 * face_size^2 * 4 floats (+X -X +Y -Y +Z -Z), as gswt_skybox_configure
+ * takes them.  GSWT_ERR_STATE before any skybox configure. */
+GSWT_API int gswt_skybox_download(gswt_ctx *ctx, float *faces_rgba_host);
 /* Skybox::render (skybox.rs:457-488): LoadOp::Clear + the cube drawn at depth 1 = every pixel of out_rgba_dev
  * (W*H*4 f32, device) is overwritten with (cube rgb, 1). */
 GSWT_API int gswt_skybox_render(gswt_ctx *ctx, const gswt_camera_uniforms *camera, int width, int height, float *out_rgba_dev);
