@@ -25,45 +25,23 @@
 #include <cstring>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
-
-namespace gswt {
-void launch_cull(hipStream_t, const Frame&, const DrawDev*, uint32_t, uint32_t*, uint32_t*, uint32_t, uint32_t*, uint32_t, uint32_t*, uint32_t, uint32_t*, uint32_t,
-                 uint32_t*, uint4*, uint32_t*, uint32_t, const uint2*, uint32_t, const float*, bool, uint32_t*);
-void launch_merge_copy(hipStream_t, const MergeCopy*, const uint2*, uint32_t, const uint2*, const MergeSources&, uint32_t*, uint32_t*);
-void launch_chunk_tabs(hipStream_t, const DrawDev*, const uint32_t*, uint32_t, uint2*, uint2*, const uint64_t*, uint64_t);
-size_t radix_ws_words(uint32_t, int);
-size_t radix_ws_zero_words(uint32_t, int);
-void launch_merge_build(hipStream_t, const MergeSeg*, uint32_t, const uint2*, uint32_t, MergeGroup*, uint32_t, const int32_t*, uint32_t, const unsigned long long*,
-                        uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, int, uint32_t*, uint32_t*);
-void launch_project(hipStream_t, bool, const Frame&, const DrawDev*, const uint2*, uint32_t, uint32_t, const uint32_t*, const uint32_t*,
-                    const uint32_t*, const uint4*, const float*, const uint32_t*, const uint32_t*, uint32_t*, const uint4*, uint2*, Rec*, float*, uint32_t*, uint32_t*,
-                    unsigned long long*, Varyings*, float4*, uint32_t, bool);
-void launch_totals(hipStream_t, uint32_t*, uint32_t, unsigned long long*, uint32_t);
-void launch_emit(hipStream_t, const Frame&, uint32_t, const uint2*, const uint32_t*, const uint32_t*, uint32_t, unsigned long long*,
-                 uint32_t*, uint32_t*, const float*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, uint32_t);
-int launch_sort(hipStream_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, const unsigned long long*, int, uint32_t*, uint2* = nullptr,
-                const uint32_t* = nullptr, uint32_t* = nullptr, uint32_t* = nullptr);
-void launch_composite(hipStream_t, const Frame&, const uint2*, const uint32_t*, const Rec*, const float*, const float4*, const float4*, const float*, float4*, int, int,
-                      uint32_t, uint32_t, uint32_t*, uint4*, float4*, hipEvent_t, hipEvent_t, unsigned long long*, unsigned long long*, int, const uint32_t*, uint32_t, uint32_t*, bool, bool);
-void launch_tile_depth_sort(hipStream_t, const uint2*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, int, uint32_t*, unsigned long long*);
-uint32_t tile_depth_sort_cap();
-void launch_unshard(hipStream_t, const float4*, float4*, int, int, int, int, int);
-void launch_skybox(hipStream_t, const float*, float, float, int, int, int, int, const float4*, float4*);
-void launch_skybox_bake(hipStream_t, const SkyBakeArgs&, const float4*, float4*);
-void launch_proxy(hipStream_t, const ProxyArgs&, const float*, const float4*, float4*, float*);
-void launch_fill_f32(hipStream_t, float*, size_t, float);
-}  // namespace gswt
 
 using namespace gswt;
 
 namespace {
 
+// Device and pinned host buffers own their memory: freed when the buffer goes out of scope (or by release()), moved but never copied.
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;  // elements
-    hipError_t ensure(size_t n, bool keep = false, hipStream_t s = nullptr)
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { release(); }
+    hipError_t ensure(size_t n)
     {
         if (n <= cap) return hipSuccess;
         size_t ncap = n + n / 4 + 1024;
@@ -74,8 +52,6 @@ struct DevBuf {
         if (log_alloc) fprintf(stderr, "gswt alloc: %zu -> %zu bytes%s\n", cap * sizeof(T), ncap * sizeof(T), p ? " (grow: frees the old buffer)" : "");
         hipError_t e = hipMalloc(&np, ncap * sizeof(T));
         if (e != hipSuccess) return e;
-        if (keep && p && cap) hipMemcpy(np, p, cap * sizeof(T), hipMemcpyDeviceToDevice);
-        (void)s;
         if (p) hipFree(p);
         p = np; cap = ncap;
         return hipSuccess;
@@ -100,6 +76,10 @@ template <typename T>
 struct HostBuf {
     T* p = nullptr;
     size_t cap = 0;
+    HostBuf() = default;
+    HostBuf(HostBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    HostBuf& operator=(HostBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~HostBuf() { release(); }
     hipError_t ensure(size_t n)
     {
         if (n <= cap) return hipSuccess;
@@ -215,11 +195,15 @@ struct FrameArgs {
     float4* d_out = nullptr;
 };
 
+// A frame's events on its slot's stream.  GSWT_OPT_TIMING >= 1 records kEvStart, kEvEnd and the compositor kernel's pair, 2 also the
+// stage boundaries in between (nothing runs between kEvSorted and kEvRanges); kEvDone follows the frame's last command in any case.
+enum FrameEvent { kEvStart, kEvProjected, kEvEmitted, kEvSorted, kEvRanges, kEvEnd, kEvCompositeBegin, kEvCompositeEnd, kEvDone, kFrameEvents };
+
 // One frame in flight.  Each slot owns a stream and every per-frame buffer, so two frames overlap on the GPU:
 // the latency-bound kernels of one (sort passes, single-workgroup scans, tails) fill the gaps of the other.
 struct FrameSlot {
     hipStream_t stream = nullptr;
-    hipEvent_t ev[10] = {};
+    hipEvent_t ev[kFrameEvents] = {};
     hipEvent_t ev_in = nullptr;            // recorded on the ctx stream at enqueue: the frame starts after it
     hipEvent_t ev_gather = nullptr;        // recorded on the ctx stream behind the frame's gather + re-assembly (gswt_render_gather / gswt_group_render_gather)
     bool gather_recorded = false;
@@ -242,7 +226,7 @@ struct FrameSlot {
     DevBuf<uint32_t> live_cnt;             // entries per XCD list of live_tab (8 words, a cache line apart; zero between frames) + k_totals' copy for k_emit
     DevBuf<uint32_t> live_cid;             // live_tab's chunks as chunk numbers in slot order (k_emit walks the same table)
     DevBuf<uint32_t> cell_culled;          // column-band shards: per map cell, 1 = no splat of that tile instance can reach the band
-    DevBuf<uint32_t> block_sums, draw_culled, scan_ws, keys_a, keys_b, vals_a, vals_b, ghist;
+    DevBuf<uint32_t> block_sums, draw_culled, keys_a, keys_b, vals_a, vals_b, ghist;
     DevBuf<uint2> ranges;
     DevBuf<uint32_t> item_base;
     DevBuf<uint4> item_tab;
@@ -270,7 +254,7 @@ struct FrameSlot {
     }
     void release_buffers()
     {
-        rects.release(); recs.release(); cell_culled.release(); live_tab.release(); live_cid.release(); live_cnt.release(); block_sums.release(); draw_culled.release(); scan_ws.release(); keys_a.release();
+        rects.release(); recs.release(); cell_culled.release(); live_tab.release(); live_cid.release(); live_cnt.release(); block_sums.release(); draw_culled.release(); keys_a.release();
         keys_b.release(); vals_a.release(); vals_b.release(); ghist.release(); ranges.release(); item_base.release();
         aux_a.release(); aux_b.release(); partials.release(); item_tab.release(); col_f.release(); depths.release();
     }
@@ -351,7 +335,7 @@ struct gswt_ctx {
     // -- 17.8 k positions for 10.7 k live chunks -- and c5's is 80 k of 366 k: 736-742 against 723-728 frames/s.  The cut is only taken where it
     // removes at least half of the grid.)
     uint32_t live_hint = 0;                // longest live list (per XCD) of the last finished frame; 0: none yet
-    uint32_t depth_max_tile_len = 0;       // longest tile list of the last finished depth-ordered frame (0: none yet -- try tile-local)
+    uint32_t depth_max_tile_len = 0;       // longest tile list of the last finished depth-ordered frame (0: none yet; gswt_debug_depth_stats)
     unsigned long long stat_depth_local = 0, stat_depth_global = 0;     // depth-ordered frames enqueued on either path (re-runs included)
     int last_slot = 0;
     DevBuf<float4> bg_rgba, out_img;
@@ -1267,7 +1251,6 @@ static int validate_frame(gswt_ctx* c, const gswt_camera_uniforms* cam, const gs
     return GSWT_OK;
 }
 
-// Enqueues every kernel of one frame on the ctx stream.  All pointers in `a` are device pointers.
 // GSWT_OPT_GRAPH: the frame's launch sequence was recorded, not launched (gswt_device.h); replay it as one hipGraphLaunch on the
 // slot's stream.  The graph is a chain of kernel nodes; it is rebuilt when the sequence of kernels changes (another template
 // variant, a k_radix_supscan more or less) and otherwise only the nodes whose grid or arguments differ from the previous frame of
@@ -1314,32 +1297,15 @@ static int replay_graph(gswt_ctx* c, FrameSlot& sl)
     return GSWT_OK;
 }
 
-static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
+// The frame constants of k_cull .. k_combine: the uniforms as the kernels read them, the screen tiles of the frame's shard and the
+// band-cull bounds of a column shard.  Host arithmetic only.
+static Frame make_frame(const gswt_ctx& c, const FrameArgs& a)
 {
-    const FrameArgs& a = sl.args;
-    DrawSet& D = c->sets[sl.set];
     const gswt_camera_uniforms* cam = &a.cam;
     const gswt_scene_uniforms* su = &a.su;
     const gswt_render_config* cfg = &a.cfg;
     const int width = a.width, height = a.height;
-    hipStream_t s = sl.stream;
     const int sc = cfg->shard_count <= 1 ? 1 : cfg->shard_count;
-    {
-        const size_t n_slots_all = (size_t)D.n_chunks * kChunk;
-        HIP_TRY(c, sl.rects.ensure(n_slots_all + 1));
-        HIP_TRY(c, sl.recs.ensure(n_slots_all + 1));
-        HIP_TRY(c, sl.block_sums.ensure_roomy((size_t)D.n_chunks + 1));
-        HIP_TRY(c, sl.live_tab.ensure_roomy((size_t)D.n_launch + 8));
-        HIP_TRY(c, sl.live_cid.ensure_roomy((size_t)D.n_launch + 8));
-        // (cleared ON THE SLOT'S STREAM: the slot streams are non-blocking, so a null-stream hipMemset -- asynchronous to the host for
-        // device memory -- could land after this frame's k_cull had filled the counts: the slot's FIRST frame then projected nothing
-        // and came back as background.  Seen once five slots made test_async_all_slots_in_flight_and_slot_reuse the first user of slot 4.)
-        if (!sl.live_cnt.p) { HIP_TRY(c, sl.live_cnt.ensure(16 * kSuperStride)); HIP_TRY(c, hipMemsetAsync(sl.live_cnt.p, 0, sl.live_cnt.cap * 4, s)); }
-        HIP_TRY(c, sl.draw_culled.ensure_roomy((size_t)D.n_draws + 1));
-        if (su->draw_mode != 0u) HIP_TRY(c, sl.col_f.ensure(n_slots_all + 1));
-        if (a.d_bgd || cfg->order_mode == GSWT_ORDER_DEPTH) HIP_TRY(c, sl.depths.ensure(n_slots_all + 1));
-    }
-
     Frame f;
     memset(&f, 0, sizeof(f));
     memcpy(f.V, cam->view, 64);
@@ -1384,22 +1350,22 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         // the columns of F are finite differences of lz R, |.| <= 2.5 R / block_w, and lz itself).  Not the point-cloud covariance.
         f.band_cull = (su->surface_type <= 2u && !(su->point_cloud_radius > 0.0f)) ? 1 : 0;
     }
-    for (int k = 0; k < 3; k++) { f.loc_lo[k] = c->loc_lo[k]; f.loc_hi[k] = c->loc_hi[k]; }
-    f.loc_max_trace = c->loc_max_trace;
+    for (int k = 0; k < 3; k++) { f.loc_lo[k] = c.loc_lo[k]; f.loc_hi[k] = c.loc_hi[k]; }
+    f.loc_max_trace = c.loc_max_trace;
     f.surf_zlo = f.surf_zhi = 0.0f; f.surf_f2 = 1.0f;
     if (su->surface_type == 1u) {
         const float hz = su->height_map_scale[2];
-        f.surf_zlo = std::min(c->hm_min * hz, c->hm_max * hz); f.surf_zhi = std::max(c->hm_min * hz, c->hm_max * hz);
+        f.surf_zlo = std::min(c.hm_min * hz, c.hm_max * hz); f.surf_zhi = std::max(c.hm_min * hz, c.hm_max * hz);
         // slopes of the mapped surface per world unit: |dh/du| hz / x_range, |dh/dv| hz / y_range (gswt.wgsl:565-599)
         const float xr = (2.0f * (float)su->map_half_wh[0] + 1.0f) * su->tile_width * su->height_map_scale[0];
         const float yr = (2.0f * (float)su->map_half_wh[1] + 1.0f) * su->tile_width * su->height_map_scale[1];
-        const float sx = c->hm_du * std::fabs(hz) / std::fabs(xr), sy = c->hm_dv * std::fabs(hz) / std::fabs(yr);
+        const float sx = c.hm_du * std::fabs(hz) / std::fabs(xr), sy = c.hm_dv * std::fabs(hz) / std::fabs(yr);
         f.surf_f2 = (3.0f + sx * sx + sy * sy) * 1.01f;
         // a non-finite height map (gswt_configure leaves +-3e38 bounds), an infinite or NaN range or slope bound: no band culling at all
         // (fminf / fmaxf drop NaN operands, so a box with NaN corners used to read as "misses the band")
         const float fmax_ = 3.0e38f;
         if (!(f.surf_f2 == f.surf_f2) || !(f.surf_zlo == f.surf_zlo) || !(f.surf_zhi == f.surf_zhi) || !(std::fabs(f.surf_f2) < fmax_) ||
-            !(std::fabs(f.surf_zlo) < fmax_) || !(std::fabs(f.surf_zhi) < fmax_) || !(c->hm_du < fmax_) || !(c->hm_dv < fmax_)) f.band_cull = 0;
+            !(std::fabs(f.surf_zlo) < fmax_) || !(std::fabs(f.surf_zhi) < fmax_) || !(c.hm_du < fmax_) || !(c.hm_dv < fmax_)) f.band_cull = 0;
     }
     if (su->surface_type == 2u) {
         const float block_w = ((float)su->map_half_wh[0] * 2.0f) * su->tile_width / 5.0f;
@@ -1407,28 +1373,135 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         f.surf_f2 = (2.0f * g * g + 1.0f) * 1.01f;
         if (!(block_w > 0.0f) || !(f.surf_f2 == f.surf_f2) || su->map_half_wh[0] == 0u || su->map_half_wh[1] == 0u) f.band_cull = 0;
     }
-    f.hm_w = c->hm_w; f.hm_h = c->hm_h;
+    f.hm_w = c.hm_w; f.hm_h = c.hm_h;
     f.map_wh_y = 2u * su->map_half_wh[1] + (su->surface_type != 2u ? 1u : 0u);
     // (0 = "divide": a one-row map, map_wh_y == 1, would wrap the magic to 0 and the multiply-high quotient to 0 -- ADVICE r3)
     f.map_wh_y_magic = f.map_wh_y >= 2u && f.map_wh_y < 65536u ? 0xFFFFFFFFu / f.map_wh_y + 1u : 0u;
     f.tiles_x_magic = f.tiles_x > 0 && f.tiles_x < 65536 ? 0xFFFFFFFFu / (uint32_t)f.tiles_x + 1u : 0u;
+    return f;
+}
 
+// Every buffer of the slot's frame: sized for n_tiles screen tiles, `cap` pairs and the two sorts' key widths (depth_bits 0: no global
+// depth passes), carved and pointed to in `b` with the lengths k_cull clears.
+static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, const Frame& f, int n_tiles, uint32_t cap, int key_bits, int depth_bits,
+                              FrameBufs& b)
+{
+    const FrameArgs& a = sl.args;
+    const size_t nt = (size_t)n_tiles, n_slots_all = (size_t)D.n_chunks * kChunk;
+    const bool depth_order = a.cfg.order_mode == GSWT_ORDER_DEPTH, need_depths = a.d_bgd != nullptr || depth_order;
+    const uint32_t seg = (uint32_t)c->opt_segment;
+    b.n_cells = f.band_cull ? (2u * f.map_half_wh[0] + 1u) * (2u * f.map_half_wh[1] + 1u) : 0u;
+    HIP_TRY(c, sl.rects.ensure(n_slots_all + 1));
+    HIP_TRY(c, sl.recs.ensure(n_slots_all + 1));
+    HIP_TRY(c, sl.block_sums.ensure_roomy((size_t)D.n_chunks + 1));
+    HIP_TRY(c, sl.live_tab.ensure_roomy((size_t)D.n_launch + 8));
+    HIP_TRY(c, sl.live_cid.ensure_roomy((size_t)D.n_launch + 8));
+    // (cleared ON THE SLOT'S STREAM: the slot streams are non-blocking, so a null-stream hipMemset -- asynchronous to the host for
+    // device memory -- could land after this frame's k_cull had filled the counts: the slot's FIRST frame then projected nothing
+    // and came back as background.  Seen once five slots made test_async_all_slots_in_flight_and_slot_reuse the first user of slot 4.)
+    if (!sl.live_cnt.p) { HIP_TRY(c, sl.live_cnt.ensure(16 * kSuperStride)); HIP_TRY(c, hipMemsetAsync(sl.live_cnt.p, 0, sl.live_cnt.cap * 4, sl.stream)); }
+    HIP_TRY(c, sl.draw_culled.ensure_roomy((size_t)D.n_draws + 1));
+    HIP_TRY(c, sl.cell_culled.ensure((size_t)b.n_cells + 1));
+    if (a.su.draw_mode != 0u) HIP_TRY(c, sl.col_f.ensure(n_slots_all + 1));
+    if (need_depths) HIP_TRY(c, sl.depths.ensure(n_slots_all + 1));
+    if (c->opt_debug_varyings) HIP_TRY(c, c->dbg.ensure((size_t)D.n_entries + 1));
+    // the `ranges` region (uint2 units): every tile's (~start, end) and one more, then one ticket word per tile for GSWT_OPT_COMPOSITE = 2,
+    // then the tile-local depth sort's two lists of long tiles; the word parts are padded to whole uint2s plus one.  k_cull clears the
+    // ranges, the tickets, the first list and the second list's count.
+    const size_t range_words = 2 * (nt + 1), tick_words = nt, list_words = tile_depth_list_words(nt);
+    auto uint2s = [](size_t words) { return (words + 1) / 2 + 1; };
+    HIP_TRY(c, sl.ranges.ensure(range_words / 2 + uint2s(tick_words) + 2 * uint2s(list_words)));
+    b.n_zero_ranges = (uint32_t)(range_words + tick_words + list_words + 1);
+    // the `ghist` region (u32): [counters][super-group sums][pair sort workspace][depth sort workspace]; each workspace has its zeroed part
+    // (group rows, digit totals) in front of its per-workgroup rows (written in full).  k_cull clears the head up to the end of the pair
+    // sort's zeroed part, and the depth sort's zeroed part.
+    const size_t counter_words = 16, n_super = (size_t)D.n_chunks / 256 + 1;
+    const size_t super_words = (2 * (size_t)kSuperStride + 1) * n_super;     // pair sums, visible sums (a cache line per word), exclusive pair prefix (k_totals)
+    const size_t rw_pair = radix_ws_words(cap, key_bits), rw_depth = depth_bits ? radix_ws_words(cap, depth_bits) : 0;
+    HIP_TRY(c, sl.ghist.ensure_roomy(counter_words + super_words + rw_pair + rw_depth + 16));
+    b.n_zero_head = (uint32_t)(counter_words + super_words + radix_ws_zero_words(cap, key_bits));
+    b.n_zero_depth = depth_bits ? (uint32_t)radix_ws_zero_words(cap, depth_bits) : 0u;
+    HIP_TRY(c, sl.keys_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.keys_b.ensure_roomy((size_t)cap + 1));
+    HIP_TRY(c, sl.vals_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.vals_b.ensure_roomy((size_t)cap + 1));
+    if (depth_order) { HIP_TRY(c, sl.aux_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.aux_b.ensure_roomy((size_t)cap + 1)); }
+    HIP_TRY(c, sl.item_base.ensure_roomy(nt + 2));
+    HIP_TRY(c, sl.partials.ensure_roomy((nt + cap / seg + 1) * 256));
+    HIP_TRY(c, sl.item_tab.ensure_roomy(nt + cap / seg + 2));
+
+    b.draws = D.draws.p; b.n_chunks = D.n_chunks; b.chunk_tab = D.chunk_tab.p; b.chunk_tab_xcd = D.chunk_tab_xcd.p;
+    b.static_list = c->static_list.p; b.merged_list = D.merged_list.p; b.merged_map = D.merged_map.p;
+    b.tex = c->tex.p; b.hmap = c->hmap.p; b.boxes = c->static_boxes.p;
+    b.bg_rgba = a.d_bg; b.bg_depth = a.d_bgd; b.out = a.d_out; b.host_counters = sl.hc_dev;
+    b.n_tiles = (uint32_t)n_tiles; b.pair_cap = cap; b.seg = seg;
+    b.rects = sl.rects.p; b.recs = sl.recs.p; b.depths = need_depths ? sl.depths.p : nullptr; b.col_f = sl.col_f.p; b.dbg = c->dbg.p;
+    b.draw_culled = sl.draw_culled.p; b.cell_culled = sl.cell_culled.p;
+    b.live_cnt = sl.live_cnt.p; b.live_cid = sl.live_cid.p; b.live_tab = sl.live_tab.p; b.block_sums = sl.block_sums.p;
+    b.counters = reinterpret_cast<unsigned long long*>(sl.ghist.p);
+    b.krange = reinterpret_cast<uint32_t*>(b.counters + 5);
+    b.super_sums = sl.ghist.p + counter_words;
+    b.radix_pair = b.super_sums + super_words;
+    b.radix_depth = b.radix_pair + rw_pair;
+    b.keys_a = sl.keys_a.p; b.keys_b = sl.keys_b.p; b.vals_a = sl.vals_a.p; b.vals_b = sl.vals_b.p; b.aux_a = sl.aux_a.p; b.aux_b = sl.aux_b.p;
+    b.ranges = sl.ranges.p;
+    b.tile_tick = reinterpret_cast<uint32_t*>(sl.ranges.p) + range_words;
+    b.long_tiles = b.tile_tick + tick_words;
+    b.item_base = sl.item_base.p; b.item_tab = sl.item_tab.p; b.partials = sl.partials.p;
+    return GSWT_OK;
+}
+
+// Emits the frame's (tile, slot) pairs and sorts them; *sorted = the slots in composite order.
+// Reference order: the pairs in slot order, stably sorted on the tile bits.  Depth order: inside a tile true depth order, equal depths in
+// slot order, by one of two paths.  Tile-local: the tile passes carry the depth bits as payload, then k_tile_depth_sort orders every tile's
+// slice (lists of any length).  Global (GSWT_OPT_DEPTH_SORT = 1): the depth passes in use first (payload: the tile ids), then the tile
+// passes.  The last tile pass also leaves every screen tile's [start, end) of the sorted list in b.ranges (zeroed by k_cull).
+static int emit_and_sort(gswt_ctx* c, const FrameSlot& sl, const Frame& f, const FrameBufs& b, int key_bits, const uint32_t** sorted)
+{
+    hipStream_t s = sl.stream;
+    const uint32_t n_launch = c->opt_debug_varyings ? 0u : sl.n_launch_eff;       // (the debug-varyings frame emits from every chunk)
+    const unsigned long long* const n_pairs = b.counters + 1;
+    const uint32_t cap = b.pair_cap;
+    if (sl.args.cfg.order_mode != GSWT_ORDER_DEPTH) {
+        launch_emit(s, f, b, b.keys_a, nullptr, nullptr, n_launch);
+        if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(sl.ev[kEvEmitted], s));
+        const int where = launch_sort(s, b.keys_a, b.vals_a, b.keys_b, b.vals_b, cap, n_pairs, key_bits, b.radix_pair, b.ranges);
+        *sorted = where ? b.vals_b : b.vals_a;
+    } else if (sl.depth_local) {
+        launch_emit(s, f, b, b.keys_a, b.aux_a, nullptr, n_launch);
+        if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(sl.ev[kEvEmitted], s));
+        const int where = launch_sort(s, b.keys_a, b.vals_a, b.keys_b, b.vals_b, cap, n_pairs, key_bits, b.radix_pair, b.ranges, nullptr, b.aux_a, b.aux_b);
+        uint32_t* const vals = where ? b.vals_b : b.vals_a;
+        launch_tile_depth_sort(s, b.ranges, vals, where ? b.aux_b : b.aux_a, where ? b.vals_a : b.vals_b, where ? b.aux_a : b.aux_b, (int)b.n_tiles,
+                               b.long_tiles, b.counters);
+        *sorted = vals;
+    } else {
+        launch_emit(s, f, b, b.aux_a, b.keys_a, b.krange, n_launch);
+        if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(sl.ev[kEvEmitted], s));
+        const int wd = launch_sort(s, b.keys_a, b.vals_a, b.keys_b, b.vals_b, cap, n_pairs, 8 * (int)sl.depth_passes, b.radix_depth, nullptr, b.krange,
+                                   b.aux_a, b.aux_b);
+        // (the depth keys are dead now: keys_a serves as the other half of the tile-key ping-pong)
+        uint32_t* const tiles_in = wd ? b.aux_b : b.aux_a;
+        uint32_t* const vals_in = wd ? b.vals_b : b.vals_a;
+        uint32_t* const vals_other = wd ? b.vals_a : b.vals_b;
+        const int where = launch_sort(s, tiles_in, vals_in, b.keys_a, vals_other, cap, n_pairs, key_bits, b.radix_pair, b.ranges);
+        *sorted = where ? vals_other : vals_in;
+    }
+    return GSWT_OK;
+}
+
+// Enqueues every kernel of one frame on the slot's stream.  All pointers in sl.args are device pointers.
+static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
+{
+    const FrameArgs& a = sl.args;
+    DrawSet& D = c->sets[sl.set];
+    hipStream_t s = sl.stream;
+    const Frame f = make_frame(*c, a);
     const int rsc = f.shard_count;                                  // row-shard count (1 in column mode)
     const int tiles_y_local = rsc > 1 ? (f.tiles_y - f.shard_index + rsc - 1) / rsc : f.tiles_y;
     const int n_tiles = f.tiles_x * (tiles_y_local > 0 ? tiles_y_local : 0);
-    const int out_rows = rsc > 1 ? gswt_shard_rows_padded(height, rsc) : height;
+    const int out_rows = rsc > 1 ? gswt_shard_rows_padded(a.height, rsc) : a.height;
     const size_t out_px = (size_t)out_rows * f.out_w;
     sl.n_tiles = n_tiles;
-    float4* const d_out = a.d_out;
-    // (behind the per-tile ranges: one ticket word per tile for GSWT_OPT_COMPOSITE = 2, cleared with them by k_cull)
-    // (and behind those: the tile-local depth sort's two lists of long tiles, each [0] = count + n_tiles entries, cleared likewise)
-    HIP_TRY(c, sl.ranges.ensure((size_t)n_tiles + 1 + ((size_t)n_tiles + 1) / 2 + 1 + 2 * (((size_t)n_tiles + 2) / 2 + 1)));
-    uint32_t* const d_tile_tick = reinterpret_cast<uint32_t*>(sl.ranges.p + (size_t)n_tiles + 1);
-    uint32_t* const d_long_tiles = d_tile_tick + n_tiles;
     const bool dbg = c->opt_debug_varyings != 0;
-    const bool need_depths = a.d_bgd != nullptr || cfg->order_mode == GSWT_ORDER_DEPTH;
-    if (dbg) HIP_TRY(c, c->dbg.ensure((size_t)D.n_entries + 1));
-
     // The pair count P is only known on the device.  Everything downstream of k_project is launched
     // for a capacity `pair_cap` (blocks past the real P do nothing), so a frame needs no host round
     // trip; the count and an overflow flag travel back with the frame.  If P exceeded the capacity
@@ -1436,40 +1509,16 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
     int key_bits = 1;
     while ((1 << key_bits) < n_tiles) key_bits++;
     if (c->pair_cap == 0) c->pair_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(D.n_entries / 4, 1u << 20), 0xFFFFFF00ull);
-    const uint32_t cap = c->pair_cap;
-    sl.cap = cap;
-    HIP_TRY(c, sl.keys_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.keys_b.ensure_roomy((size_t)cap + 1));
-    HIP_TRY(c, sl.vals_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.vals_b.ensure_roomy((size_t)cap + 1));
-    const bool depth_order = cfg->order_mode == GSWT_ORDER_DEPTH;
-    const size_t n_super = (size_t)D.n_chunks / 256 + 1;
-    const size_t n_super2 = (2 * (size_t)kSuperStride + 1) * n_super;     // pair sums, visible sums (a cache line per word), exclusive pair prefix (k_totals)
-    // GSWT_ORDER_DEPTH: the pair list is sorted on the depth bits first, with as many 8-bit passes as the key ranges of the recent frames
-    // needed (k_items flags a frame that needs more: finish_frame re-runs it); the tile ids travel as the payload of those passes
+    sl.cap = c->pair_cap;
+    // GSWT_ORDER_DEPTH: the global depth passes take as many 8-bit passes as the key ranges of the recent frames needed (k_items flags a
+    // frame that needs more: finish_frame re-runs it).  GSWT_OPT_DEPTH_SORT: 0 / 2 = the tile-local sort, 1 = the global passes.
+    const bool depth_order = a.cfg.order_mode == GSWT_ORDER_DEPTH;
     sl.depth_passes = depth_order ? std::min<uint32_t>(std::max<uint32_t>(c->depth_passes, 1u), 4u) : 0u;
-    // a re-run after the tile-local path flagged a list that does not fit takes the global passes (finish_frame raised depth_max_tile_len)
-    // (GSWT_OPT_DEPTH_SORT: 0 = tile-local while the longest list fits its LDS buffer, 1 = always the global passes, 2 = as 0)
-    sl.depth_local = depth_order && c->opt_depth_sort != 1;      // (no list is too long for it: k_tile_depth_sort_xl)
-    const int depth_bits = sl.depth_local ? 0 : 8 * (int)sl.depth_passes;
+    sl.depth_local = depth_order && c->opt_depth_sort != 1;
     if (depth_order) (sl.depth_local ? c->stat_depth_local : c->stat_depth_global)++;
-    if (depth_order) { HIP_TRY(c, sl.aux_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.aux_b.ensure_roomy((size_t)cap + 1)); }
-    // radix workspaces: per sort the zeroed part (group rows, digit totals) in front of its per-workgroup rows (written in full)
-    const size_t rz_pair = radix_ws_zero_words(cap, key_bits), rz_depth = depth_bits ? radix_ws_zero_words(cap, depth_bits) : 0;
-    const size_t rw_pair = radix_ws_words(cap, key_bits), rw_depth = depth_bits ? radix_ws_words(cap, depth_bits) : 0;
-    // one contiguous u32 region whose head k_cull clears: [counters: 16][super_sums: n_super2][pair sort: zeroed part .. rows][depth sort likewise]
-    HIP_TRY(c, sl.ghist.ensure_roomy(16 + n_super2 + rw_pair + rw_depth + 16));
-    uint32_t* const zero_a = sl.ghist.p;
-    unsigned long long* const d_counters = reinterpret_cast<unsigned long long*>(zero_a);
-    uint32_t* const d_super = zero_a + 16;
-    uint32_t* const d_radix = d_super + n_super2;
-    uint32_t* const d_radix_depth = d_radix + rw_pair;
-    uint32_t* const d_krange = reinterpret_cast<uint32_t*>(d_counters + 5);     // counters[5]: (~smallest, largest) depth key of the frame (k_emit<DEPTH>)
-    const uint32_t seg = (uint32_t)c->opt_segment;
-    HIP_TRY(c, sl.item_base.ensure_roomy((size_t)n_tiles + 2));
-    HIP_TRY(c, sl.partials.ensure_roomy(((size_t)n_tiles + cap / seg + 1) * 256));
-    HIP_TRY(c, sl.item_tab.ensure_roomy((size_t)n_tiles + cap / seg + 2));
-    unsigned long long* const d_P = d_counters + 1;
-    hipEvent_t* ev = sl.ev;
-    // ---- cull (+ clears the frame's accumulators) + project
+    FrameBufs b;
+    int rc = plan_frame_buffers(c, sl, D, f, n_tiles, sl.cap, key_bits, sl.depth_local ? 0 : 8 * (int)sl.depth_passes, b);
+    if (rc != GSWT_OK) return rc;
     // the frame starts after everything submitted to the ctx stream so far (inputs produced there, earlier readers of
     // the output buffer, the device-side merged-list build and the draw bounds of its draw set), on the slot's own stream
     // (an idle ctx stream has nothing to wait for; a cross-stream event wait per frame is not free: c3 static camera 4 700 -> 4 900 frames/s)
@@ -1483,7 +1532,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         if (hipEventQuery(D.ev_up) == hipSuccess) D.built = true;
         else HIP_TRY(c, hipStreamWaitEvent(s, D.ev_up, 0));
     }
-    if (sc > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(d_out, 0, out_px * 16, s));
+    if (a.cfg.shard_count > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(a.d_out, 0, out_px * 16, s));
     // GSWT_OPT_GRAPH: from here to the end of the frame the launch sites record instead of launching (frames that carry timing
     // events, debug varyings and shards without tiles launch as before)
     const bool use_graph = c->opt_graph != 0 && c->opt_timing == 0 && !dbg && n_tiles > 0 && sl.hc_dev != nullptr;
@@ -1491,15 +1540,10 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         explicit RecorderScope(GraphRec* r) { if (r) { r->n = 0; r->overflow = false; } graph_recorder() = r; }
         ~RecorderScope() { graph_recorder() = nullptr; }
     } recorder_scope(use_graph ? &sl.grec : nullptr);
-    if (c->opt_timing >= 1) HIP_TRY(c, hipEventRecord(ev[0], s));
-    const uint32_t n_cells = f.band_cull ? (2u * su->map_half_wh[0] + 1u) * (2u * su->map_half_wh[1] + 1u) : 0u;
-    HIP_TRY(c, sl.cell_culled.ensure((size_t)n_cells + 1));
-    // cleared per frame: counters, super-group sums and the atomically accumulated part of the sort's tables.  The pair sort's zeroed
-    // part is contiguous with the head; the depth sort's (behind the pair sort's rows) is the kernel's second clear range.
-    const size_t n_zero_a = 16 + n_super2 + rz_pair;
-    launch_cull(s, f, D.draws.p, D.n_draws, sl.draw_culled.p, sl.cell_culled.p, n_cells, zero_a, (uint32_t)n_zero_a,
-                reinterpret_cast<uint32_t*>(sl.ranges.p), ((uint32_t)n_tiles + 1u) * 2u + (uint32_t)n_tiles + ((uint32_t)n_tiles + 2u), sl.block_sums.p, D.n_chunks, sl.live_cnt.p, sl.live_tab.p,
-                d_radix_depth, (uint32_t)rz_depth, D.chunk_tab.p, D.n_chunks, c->static_boxes.p, c->opt_no_chunk_cull == 0 && !dbg, sl.live_cid.p);
+    hipEvent_t* ev = sl.ev;
+    if (c->opt_timing >= 1) HIP_TRY(c, hipEventRecord(ev[kEvStart], s));
+    // ---- cull (+ clears the frame's accumulators) + project
+    launch_cull(s, f, b, c->opt_no_chunk_cull == 0 && !dbg);
     {
         uint64_t eff = D.n_launch;
         if (!dbg && !sl.full_grid && c->live_hint) {
@@ -1508,51 +1552,19 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         }
         sl.n_launch_eff = (uint32_t)eff;
     }
-    launch_project(s, dbg, f, D.draws.p, D.chunk_tab_xcd.p, sl.n_launch_eff, D.n_chunks, c->static_list.p, D.merged_list.p, D.merged_map.p,
-                   c->tex.p, c->hmap.p, sl.draw_culled.p, sl.cell_culled.p, sl.live_cnt.p, sl.live_tab.p, sl.rects.p, sl.recs.p, need_depths ? sl.depths.p : nullptr, sl.block_sums.p, d_super,
-                   d_counters, c->dbg.p, sl.col_f.p, cap, sl.strict_vs);
-    if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[1], s));
-    // ---- emit + sort
-    // reference order: pairs in composite (slot) order, stably sorted on the tile bits.  Depth order: the same pairs with their depth bits,
-    // stably sorted on the depth bits in use first (payload: the tile id), then on the tile bits: inside a tile true depth order, equal
-    // depths in composite order.  The last tile pass also leaves every screen tile's [start, end) of the sorted list in sl.ranges (zeroed by k_cull).
-    const uint32_t* vals_sorted = nullptr;
-    if (!depth_order) {
-        launch_emit(s, f, D.n_chunks, sl.rects.p, sl.block_sums.p, d_super, cap, d_counters, sl.keys_a.p, sl.vals_a.p, nullptr, nullptr, nullptr, dbg ? nullptr : sl.live_cnt.p, sl.live_cid.p, sl.n_launch_eff);
-        if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[3], s));
-        const int where = launch_sort(s, sl.keys_a.p, sl.vals_a.p, sl.keys_b.p, sl.vals_b.p, cap, d_P, key_bits, d_radix, sl.ranges.p);
-        vals_sorted = where ? sl.vals_b.p : sl.vals_a.p;
-    } else if (sl.depth_local) {
-        // tile-local path: tile ids are the sort key, the depth bits its payload; then every tile's slice is depth-sorted in LDS
-        launch_emit(s, f, D.n_chunks, sl.rects.p, sl.block_sums.p, d_super, cap, d_counters, sl.keys_a.p, sl.vals_a.p, sl.depths.p, sl.aux_a.p, nullptr, dbg ? nullptr : sl.live_cnt.p, sl.live_cid.p, sl.n_launch_eff);
-        if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[3], s));
-        const int where = launch_sort(s, sl.keys_a.p, sl.vals_a.p, sl.keys_b.p, sl.vals_b.p, cap, d_P, key_bits, d_radix, sl.ranges.p, nullptr, sl.aux_a.p, sl.aux_b.p);
-        uint32_t* const vals_t = where ? sl.vals_b.p : sl.vals_a.p;
-        launch_tile_depth_sort(s, sl.ranges.p, vals_t, where ? sl.aux_b.p : sl.aux_a.p, where ? sl.vals_a.p : sl.vals_b.p, where ? sl.aux_a.p : sl.aux_b.p, n_tiles,
-                               d_long_tiles, d_counters);
-        vals_sorted = vals_t;
-    } else {
-        launch_emit(s, f, D.n_chunks, sl.rects.p, sl.block_sums.p, d_super, cap, d_counters, sl.aux_a.p, sl.vals_a.p, sl.depths.p, sl.keys_a.p, d_krange, dbg ? nullptr : sl.live_cnt.p, sl.live_cid.p, sl.n_launch_eff);
-        if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[3], s));
-        const int wd = launch_sort(s, sl.keys_a.p, sl.vals_a.p, sl.keys_b.p, sl.vals_b.p, cap, d_P, depth_bits, d_radix_depth, nullptr, d_krange, sl.aux_a.p, sl.aux_b.p);
-        // (the depth keys are dead now: keys_a serves as the other half of the tile-key ping-pong)
-        uint32_t* const tiles_in = wd ? sl.aux_b.p : sl.aux_a.p;
-        uint32_t* const vals_in = wd ? sl.vals_b.p : sl.vals_a.p;
-        uint32_t* const vals_other = wd ? sl.vals_a.p : sl.vals_b.p;
-        const int where = launch_sort(s, tiles_in, vals_in, sl.keys_a.p, vals_other, cap, d_P, key_bits, d_radix, sl.ranges.p);
-        vals_sorted = where ? vals_other : vals_in;
-    }
-    if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[4], s));
-    // ---- ranges
-    if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[5], s));
-    // ---- composite
-    launch_composite(s, f, sl.ranges.p, vals_sorted, sl.recs.p, sl.depths.p, sl.col_f.p, a.d_bg, a.d_bgd, d_out, n_tiles, out_rows, seg, cap,
-                     sl.item_base.p, sl.item_tab.p, sl.partials.p, c->opt_timing >= 1 ? ev[7] : nullptr, c->opt_timing >= 1 ? ev[8] : nullptr,
-                     d_counters, sl.hc_dev, c->opt_composite, depth_order && !sl.depth_local ? d_krange : nullptr, sl.depth_passes, d_tile_tick, depth_order,
-                     c->opt_item_order != 0);
+    launch_project(s, f, b, sl.n_launch_eff, dbg, sl.strict_vs);
+    if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvProjected], s));
+    // ---- emit + sort, ranges, composite
+    const uint32_t* vals = nullptr;
+    rc = emit_and_sort(c, sl, f, b, key_bits, &vals);
+    if (rc != GSWT_OK) return rc;
+    if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvSorted], s));
+    if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvRanges], s));
+    launch_composite(s, f, b, vals, out_rows, c->opt_composite, depth_order && !sl.depth_local ? b.krange : nullptr, sl.depth_passes, depth_order,
+                     c->opt_item_order != 0, c->opt_timing >= 1 ? ev[kEvCompositeBegin] : nullptr, c->opt_timing >= 1 ? ev[kEvCompositeEnd] : nullptr);
     c->last_n_tiles = (uint32_t)n_tiles;
     c->last_slot = (int)(&sl - c->slots);
-    if (c->opt_timing >= 1) HIP_TRY(c, hipEventRecord(ev[6], s));
+    if (c->opt_timing >= 1) HIP_TRY(c, hipEventRecord(ev[kEvEnd], s));
     if (use_graph) {
         graph_recorder() = nullptr;
         const int grc = replay_graph(c, sl);
@@ -1561,8 +1573,8 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
     HIP_TRY(c, hipGetLastError());
     // k_combine (the frame's last kernel) stores the result counters into the pinned host words itself; only a frame
     // without screen tiles has no such launch
-    if (n_tiles == 0 || !sl.hc_dev) HIP_TRY(c, hipMemcpyAsync(sl.hc, d_counters, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipEventRecord(ev[9], s));
+    if (n_tiles == 0 || !sl.hc_dev) HIP_TRY(c, hipMemcpyAsync(sl.hc, b.counters, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipEventRecord(ev[kEvDone], s));
     sl.timing_level = c->opt_timing;
     return GSWT_OK;
 }
@@ -1571,7 +1583,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
 static int finish_frame(gswt_ctx* c, FrameSlot& sl)
 {
     for (int attempt = 0;; attempt++) {
-        HIP_TRY(c, hipEventSynchronize(sl.ev[9]));
+        HIP_TRY(c, hipEventSynchronize(sl.ev[kEvDone]));
         const unsigned long long P64 = sl.hc[1];
         if (P64 >= 0xFFFFFF00ull) return fail(c, GSWT_ERR_CAPACITY, "gswt_render: %llu pairs exceed 2^32", P64);
         if (sl.hc[3] == 0 && P64 <= sl.cap) break;
@@ -1581,8 +1593,9 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
         if (sl.args.cfg.order_mode == GSWT_ORDER_DEPTH) {
             const uint32_t need = (uint32_t)(sl.hc[2] & 0xFFFFFFFFull), max_len = (uint32_t)(sl.hc[2] >> 32);
             if (!sl.depth_local && need > sl.depth_passes) { c->depth_passes = std::min<uint32_t>(need, 4u); c->depth_passes_low_run = 0; }
-            // the tile-local depth sort met a list longer than its LDS buffer: the re-run takes the global passes (k_items may not have
-            // seen the whole frame's lengths yet when the flag was raised, so at least cap + 1)
+            // a re-run tile-local frame (pair overflow, short launch grid: lists of any length fit k_tile_depth_sort) keeps the same path;
+            // gswt_debug_depth_stats reports at least one list past the LDS buffer (k_items may not have seen the whole frame's lengths yet
+            // when the flag was raised)
             if (sl.depth_local) c->depth_max_tile_len = std::max<uint32_t>(std::max<uint32_t>(max_len, c->depth_max_tile_len), tile_depth_sort_cap() + 1u);
         }
         sl.full_grid = true;                                   // (whatever flagged it: the re-run covers the whole launch table)
@@ -1597,7 +1610,7 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
     if (!c->opt_fixed_pair_cap && (uint64_t)P + P / 4 > c->pair_cap) c->pair_cap = (uint32_t)std::min<uint64_t>((uint64_t)P + P / 2 + 4096, 0xFFFFFF00ull);
     if (sl.args.cfg.order_mode == GSWT_ORDER_DEPTH) {
         const uint32_t need = std::min<uint32_t>(std::max<uint32_t>((uint32_t)(sl.hc[2] & 0xFFFFFFFFull), 1u), 4u);
-        c->depth_max_tile_len = (uint32_t)(sl.hc[2] >> 32);        // (every depth-ordered frame reports it: the next one picks its path by it)
+        c->depth_max_tile_len = (uint32_t)(sl.hc[2] >> 32);        // (every depth-ordered frame reports it: gswt_debug_depth_stats)
         if (sl.depth_local) { /* the pass count is the kernel's own business there */ }
         else if (need < c->depth_passes && sl.depth_passes == c->depth_passes) {
             c->depth_passes_low_max = c->depth_passes_low_run ? std::max(c->depth_passes_low_max, need) : need;
@@ -1608,24 +1621,31 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
     memset(&t, 0, sizeof(t));
     hipEvent_t* ev = sl.ev;
     if (sl.timing_level >= 2) {
-        HIP_TRY(c, hipEventElapsedTime(&t.ms_project, ev[0], ev[1]));
-        HIP_TRY(c, hipEventElapsedTime(&t.ms_emit, ev[1], ev[3]));
-        HIP_TRY(c, hipEventElapsedTime(&t.ms_sort, ev[3], ev[4]));
-        HIP_TRY(c, hipEventElapsedTime(&t.ms_ranges, ev[4], ev[5]));
-        HIP_TRY(c, hipEventElapsedTime(&t.ms_composite, ev[5], ev[6]));
+        HIP_TRY(c, hipEventElapsedTime(&t.ms_project, ev[kEvStart], ev[kEvProjected]));
+        HIP_TRY(c, hipEventElapsedTime(&t.ms_emit, ev[kEvProjected], ev[kEvEmitted]));
+        HIP_TRY(c, hipEventElapsedTime(&t.ms_sort, ev[kEvEmitted], ev[kEvSorted]));
+        HIP_TRY(c, hipEventElapsedTime(&t.ms_ranges, ev[kEvSorted], ev[kEvRanges]));
+        HIP_TRY(c, hipEventElapsedTime(&t.ms_composite, ev[kEvRanges], ev[kEvEnd]));
     }
     if (sl.timing_level >= 1) {
-        HIP_TRY(c, hipEventElapsedTime(&t.ms_total, ev[0], ev[6]));
-        HIP_TRY(c, hipEventElapsedTime(&t.ms_composite_kernel, ev[7], ev[8]));
+        HIP_TRY(c, hipEventElapsedTime(&t.ms_total, ev[kEvStart], ev[kEvEnd]));
+        HIP_TRY(c, hipEventElapsedTime(&t.ms_composite_kernel, ev[kEvCompositeBegin], ev[kEvCompositeEnd]));
     }
     t.n_draws = c->sets[sl.set].n_draws; t.n_instanced = c->sets[sl.set].n_entries; t.n_visible = sl.hc[0]; t.n_pairs = P; t.n_tiles = (uint32_t)sl.n_tiles;
     return GSWT_OK;
 }
 
-static void fill_args(FrameArgs& a, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
-                      int width, int height, const float4* d_bg, const float* d_bgd, float4* d_out)
+// Submits a frame in slot `sl` (gswt_render, gswt_render_async): the slot's stream on first use, the draw set current now, the arguments.
+static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
+                        int width, int height, const float4* d_bg, const float* d_bgd, float4* d_out)
 {
+    if (!sl.stream) HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));      // a slot past the fourth: first use
+    activate_pending(c, false);
+    sl.set = c->cur_set;
+    FrameArgs& a = sl.args;
     a.cam = *cam; a.su = *su; a.cfg = *cfg; a.width = width; a.height = height; a.d_bg = d_bg; a.d_bgd = d_bgd; a.d_out = d_out;
+    sl.strict_vs = c->opt_strict_vs != 0;
+    return enqueue_frame(c, sl);
 }
 
 int gswt_render(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
@@ -1657,12 +1677,7 @@ try {
     for (int k = 0; k < kFrameSlots; k++) if (!c->slots[k].pending) { si0 = k; break; }
     FrameSlot& sl = c->slots[si0];
     if (sl.pending) return fail(c, GSWT_ERR_STATE, "gswt_render: every frame slot holds an uncollected gswt_render_async ticket");
-    if (!sl.stream) HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-    activate_pending(c, false);
-    sl.set = c->cur_set;
-    fill_args(sl.args, cam, su, cfg, width, height, d_bg, d_bgd, d_out);
-    sl.strict_vs = c->opt_strict_vs != 0;
-    rc = enqueue_frame(c, sl);
+    rc = submit_frame(c, sl, cam, su, cfg, width, height, d_bg, d_bgd, d_out);
     if (rc != GSWT_OK) return rc;
     rc = finish_frame(c, sl);
     if (rc != GSWT_OK) return rc;
@@ -1689,20 +1704,15 @@ try {
         for (int k = 1; k < kFrameSlots; k++) if (c->slots[k].seq < c->slots[si].seq) si = k;
     }
     FrameSlot& sl = c->slots[si];
-    if (!sl.stream) HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));      // a slot past the fourth: first use
     if (sl.pending) {                   // every slot in flight: the oldest frame is collected here and its slot reused
         sl.pending = false;
         if (sl.collected) { sl.collected = false; rc = sl.collected_rc; } else rc = finish_frame(c, sl);
         if (rc != GSWT_OK) return rc;
     }
     sl.seq = ++c->frame_seq;
-    activate_pending(c, false);
-    sl.set = c->cur_set;
-    sl.strict_vs = c->opt_strict_vs != 0;
     sl.gather_recorded = false;
-    fill_args(sl.args, cam, su, cfg, width, height, reinterpret_cast<const float4*>(bg_rgba_dev), bg_depth_dev,
-              reinterpret_cast<float4*>(out_rgba_dev));
-    rc = enqueue_frame(c, sl);
+    rc = submit_frame(c, sl, cam, su, cfg, width, height, reinterpret_cast<const float4*>(bg_rgba_dev), bg_depth_dev,
+                      reinterpret_cast<float4*>(out_rgba_dev));
     if (rc != GSWT_OK) return rc;
     sl.pending = true; sl.collected = false;
     *ticket = si;
@@ -1742,7 +1752,7 @@ try {
         sl.collected = true;
     }
     if (sl.collected_rc != GSWT_OK) return sl.collected_rc;
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, sl.ev[9], 0));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, sl.ev[kEvDone], 0));
     return GSWT_OK;
 } GSWT_CATCH("gswt_render_fence")
 
@@ -1773,13 +1783,6 @@ static void sky_bake_basis(const float t[3], const float up[3], float out[9])
     for (int k = 0; k < 3; k++) { out[k] = s[k]; out[3 + k] = u[k]; out[6 + k] = f[k]; }
 }
 
-namespace {
-struct DevTmp {           // a device buffer that lives for one call
-    void* p = nullptr;
-    ~DevTmp() { if (p) hipFree(p); }
-};
-}  // namespace
-
 int gswt_skybox_configure_equirect(gswt_ctx* c, const float* equi_rgba, int equi_width, int equi_height, int face_size)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;
@@ -1791,8 +1794,8 @@ try {
     HIP_TRY(c, sync_all(c));
     // the panorama is staged for this call only (up to 16 GiB at the size limit; the reference's 4096 x 2048 is 128 MiB)
     const size_t ne = (size_t)equi_width * equi_height, nf = (size_t)6 * face_size * face_size;
-    DevTmp equi;
-    HIP_TRY(c, hipMalloc(&equi.p, ne * 16));
+    DevBuf<float4> equi;
+    HIP_TRY(c, equi.ensure(ne));
     HIP_TRY(c, hipMemcpy(equi.p, equi_rgba, ne * 16, hipMemcpyHostToDevice));
     HIP_TRY(c, null_stream_done());
     HIP_TRY(c, c->sky_faces.ensure(nf));          // a failed allocation keeps the old buffer
@@ -1804,7 +1807,7 @@ try {
     static const float up[6][3] = {{0, 1, 0}, {0, 1, 0}, {0, 0, 1}, {0, 0, -1}, {0, 1, 0}, {0, 1, 0}};
     for (int i = 0; i < 6; i++) sky_bake_basis(target[i], up[i], a.basis[i]);
     a.face_size = face_size; a.equi_w = equi_width; a.equi_h = equi_height;
-    launch_skybox_bake(c->stream, a, reinterpret_cast<const float4*>(equi.p), c->sky_faces.p);
+    launch_skybox_bake(c->stream, a, equi.p, c->sky_faces.p);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->sky_size = face_size; c->sky_equi = 1;
@@ -2092,7 +2095,6 @@ try {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(counters_out, d_cnt, 32, hipMemcpyDeviceToHost));
     if (super_excl_out) HIP_TRY(c, hipMemcpy(super_excl_out, buf.p + 2 * S * (size_t)n_super, (size_t)n_super * 4, hipMemcpyDeviceToHost));
-    buf.release();
     return GSWT_OK;
 } GSWT_CATCH("gswt_debug_totals")
 
@@ -2116,7 +2118,6 @@ try {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(keys, where ? kb.p : ka.p, n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(vals, where ? vb.p : va.p, n * 4, hipMemcpyDeviceToHost));
-    ka.release(); kb.release(); va.release(); vb.release(); ws.release();
     return GSWT_OK;
 } GSWT_CATCH("gswt_debug_sort")
 
@@ -2136,11 +2137,12 @@ try {
     if (at != n) return fail(c, GSWT_ERR_BAD_ARG, "gswt_debug_tile_depth_sort: the lengths sum to %zu, not %zu", at, n);
     DevBuf<uint2> d_rg; DevBuf<uint32_t> d_vals, d_keys, d_vals2, d_keys2, d_long; DevBuf<unsigned long long> d_cnt;
     HIP_TRY(c, d_rg.ensure(n_tiles)); HIP_TRY(c, d_vals.ensure(n + 1)); HIP_TRY(c, d_keys.ensure(n + 1)); HIP_TRY(c, d_vals2.ensure(n + 1)); HIP_TRY(c, d_keys2.ensure(n + 1));
-    HIP_TRY(c, d_long.ensure(2 * n_tiles + 4)); HIP_TRY(c, d_cnt.ensure(8));
+    const size_t long_words = 2 * tile_depth_list_words(n_tiles);
+    HIP_TRY(c, d_long.ensure(long_words)); HIP_TRY(c, d_cnt.ensure(8));
     HIP_TRY(c, hipMemcpy(d_rg.p, rg.data(), n_tiles * 8, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d_vals.p, vals, n * 4, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d_keys.p, dkeys, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemset(d_long.p, 0, (2 * n_tiles + 4) * 4));
+    HIP_TRY(c, hipMemset(d_long.p, 0, long_words * 4));
     HIP_TRY(c, hipMemset(d_cnt.p, 0, 64));
     launch_tile_depth_sort(c->stream, d_rg.p, d_vals.p, d_keys.p, d_vals2.p, d_keys2.p, (int)n_tiles, d_long.p, d_cnt.p);
     HIP_TRY(c, hipGetLastError());
@@ -2149,7 +2151,6 @@ try {
     HIP_TRY(c, hipMemcpy(cnt, d_cnt.p, 32, hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(vals, d_vals.p, n * 4, hipMemcpyDeviceToHost));
     if (flagged_out) *flagged_out = cnt[3] != 0ull;
-    d_rg.release(); d_vals.release(); d_keys.release(); d_vals2.release(); d_keys2.release(); d_long.release(); d_cnt.release();
     return GSWT_OK;
 } GSWT_CATCH("gswt_debug_tile_depth_sort")
 
@@ -2192,10 +2193,10 @@ try {
     FrameSlot& a = c->slots[ticket_ref];
     FrameSlot& b = c->slots[ticket];
     if (a.timing_level < 1 || b.timing_level < 1) return fail(c, GSWT_ERR_STATE, "gswt_debug_frame_times: frames without timing events");
-    HIP_TRY(c, hipEventElapsedTime(&out_ms[0], a.ev[0], b.ev[0]));
-    HIP_TRY(c, hipEventElapsedTime(&out_ms[1], a.ev[0], b.ev[6]));
+    HIP_TRY(c, hipEventElapsedTime(&out_ms[0], a.ev[kEvStart], b.ev[kEvStart]));
+    HIP_TRY(c, hipEventElapsedTime(&out_ms[1], a.ev[kEvStart], b.ev[kEvEnd]));
     out_ms[2] = __builtin_nanf("");
-    if (b.gather_recorded) HIP_TRY(c, hipEventElapsedTime(&out_ms[2], a.ev[0], b.ev_gather));
+    if (b.gather_recorded) HIP_TRY(c, hipEventElapsedTime(&out_ms[2], a.ev[kEvStart], b.ev_gather));
     return GSWT_OK;
 } GSWT_CATCH("gswt_debug_frame_times")
 

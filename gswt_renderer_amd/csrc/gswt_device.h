@@ -233,4 +233,75 @@ bool kernel_events_enabled();
         }                                                                                                \
     } while (0)
 
+// ---- host side: what one frame's kernels read and write (gswt_api.hip: plan_frame_buffers) ------------------------------------------
+struct FrameBufs {
+    // inputs: the frame's draw set, the scene, the caller's images (bg_rgba / bg_depth null: none) and the slot's pinned result words
+    const DrawDev* draws;
+    const uint2 *chunk_tab, *chunk_tab_xcd;    // slot order; k_project's launch order
+    const uint32_t *static_list, *merged_list, *merged_map;
+    const uint4* tex;
+    const float *hmap, *boxes;                 // boxes: tile-local bounds of every chunk of the static lists (k_cull's chunk cull)
+    const float4* bg_rgba; const float* bg_depth; float4* out;
+    unsigned long long* host_counters;         // as the device sees them (null: copied behind the frame)
+    // the sizes the buffers were planned for
+    uint32_t n_chunks, n_cells, n_tiles, pair_cap, seg;
+    // per slot (= composite order), per draw, per map cell (the band cull), per chunk
+    uint2* rects; Rec* recs; float4* col_f; Varyings* dbg;
+    float* depths;                             // null unless the frame is depth-tested or depth-ordered
+    uint32_t *draw_culled, *cell_culled, *live_cnt, *live_cid, *block_sums; uint4* live_tab;
+    // the `ghist` region: counters (krange = counters[5], k_emit<DEPTH>), k_project's super-group sums, the two sorts' radix workspaces
+    unsigned long long* counters;
+    uint32_t *krange, *super_sums, *radix_pair, *radix_depth;
+    // per pair: tile keys, slots, and the depth order's tile ids / depth bits
+    uint32_t *keys_a, *keys_b, *vals_a, *vals_b, *aux_a, *aux_b;
+    // the `ranges` region: per tile (~start, end), GSWT_OPT_COMPOSITE = 2's tickets, the tile-local depth sort's lists of long tiles
+    uint2* ranges; uint32_t *tile_tick, *long_tiles;
+    uint32_t* item_base; uint4* item_tab; float4* partials;
+    // the words k_cull clears: the head of `ghist` to the end of the pair sort's zeroed part, the `ranges` region, the depth sort's zeroed part
+    uint32_t n_zero_head, n_zero_ranges, n_zero_depth;
+};
+
+// ---- launch wrappers (gswt_kernels.hip, gswt_passes.hip) ------------------------------------------------------------------------------
+void launch_chunk_tabs(hipStream_t s, const DrawDev* draws, const uint32_t* xcd_first, uint32_t n_draws, uint2* chunk_tab, uint2* chunk_tab_xcd,
+                       const uint64_t per_xcd[8], uint64_t longest);
+void launch_merge_build(hipStream_t s, const MergeSeg* segs, uint32_t n_segs, const uint2* blocks, uint32_t n_blocks, MergeGroup* groups, uint32_t n_groups,
+                        const int32_t* raw, uint32_t n_total, const unsigned long long* n_total_dev, uint32_t* ka, uint32_t* va,
+                        uint32_t* kb, uint32_t* vb, uint32_t* radix_ws, int group_bits, uint32_t* merged_list, uint32_t* merged_map);
+void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks, uint32_t n_blocks, const uint2* remap, const MergeSources& src,
+                       uint32_t* new_list, uint32_t* new_map);
+
+// The frame: k_cull (+ the clears of b.n_zero_*), k_project + k_totals over the first n_launch positions of the launch table, k_emit
+// (keys -> `keys`, slots -> b.vals_a; depth-ordered frames also the depth bits -> dkeys and, with krange, the frame's key range; n_launch 0:
+// over every chunk instead of the live table), k_items + the compositor over the sorted slots `vals`.
+void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_cull);
+void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict);
+void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
+void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
+                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end);
+void launch_totals(hipStream_t s, uint32_t* super_sums, uint32_t n_super, unsigned long long* counters, uint32_t pair_cap);
+
+// LSD radix sort of (keys, vals) on key bits [0, key_bits), ping-pong between the a and b buffers; returns 0 if the result is in a, 1 if in b.
+// The item count is read on the device (*n_ptr), grids are sized for n_cap.  ws: radix_ws_words(n_cap, key_bits) words whose first
+// radix_ws_zero_words(n_cap, key_bits) are zero on entry.  ranges (zero on entry): the last pass also writes every key's (~start, end);
+// krange: the key range the passes cover (depth keys); aux: a payload carried with the vals.
+size_t radix_ws_words(uint32_t n_cap, int key_bits);
+size_t radix_ws_zero_words(uint32_t n_cap, int key_bits);
+int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n_cap,
+                const unsigned long long* n_ptr, int key_bits, uint32_t* ws, uint2* ranges = nullptr, const uint32_t* krange = nullptr,
+                uint32_t* aux_a = nullptr, uint32_t* aux_b = nullptr);
+
+// GSWT_ORDER_DEPTH, tile-local path: depth-sorts every tile's slice of the tile-sorted list in place.  long_list: two lists of tiles, each
+// tile_depth_list_words(n_tiles) words ([0] count, [1 .. n_tiles] tiles), back to back; both counts zero on entry.
+void launch_tile_depth_sort(hipStream_t s, const uint2* ranges, uint32_t* vals, uint32_t* dkeys, uint32_t* vals_scratch, uint32_t* dkeys_scratch, int n_tiles,
+                            uint32_t* long_list, unsigned long long* counters);
+inline size_t tile_depth_list_words(size_t n_tiles) { return n_tiles + 1; }
+uint32_t tile_depth_sort_cap();
+
+void launch_unshard(hipStream_t s, const float4* gathered, float4* out, int width, int height, int shard_count, int rows_padded, int band_px);
+void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int width, int height, int face_size, int equirect,
+                   const float4* faces, float4* out);
+void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi, float4* faces);
+void launch_proxy(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth);
+void launch_fill_f32(hipStream_t s, float* p, size_t n, float v);
+
 }  // namespace gswt

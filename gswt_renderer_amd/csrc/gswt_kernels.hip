@@ -2898,29 +2898,24 @@ bool kernel_events_enabled()
     return on;
 }
 
-void launch_cull(hipStream_t s, const Frame& f, const DrawDev* draws, uint32_t n_draws, uint32_t* draw_culled, uint32_t* cell_culled, uint32_t n_cells,
-                 uint32_t* zero_a, uint32_t n_zero_a, uint32_t* zero_b, uint32_t n_zero_b, uint32_t* zero_c, uint32_t n_zero_c,
-                 uint32_t* live_cnt, uint4* live_tab, uint32_t* zero_d, uint32_t n_zero_d,
-                 const uint2* chunk_tab, uint32_t n_chunks, const float* boxes, bool chunk_cull, uint32_t* live_cid)
+void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_cull)
 {
-    (void)n_draws;
-    uint32_t grid = (n_chunks + 255u) / 256u;              // one thread per chunk; the clears and the cell table stride over the grid
+    uint32_t grid = (b.n_chunks + 255u) / 256u;            // one thread per chunk; the clears and the cell table stride over the grid
     if (grid < 32) grid = 32;
-    GSWT_LAUNCH(k_cull, dim3(grid), dim3(256), s, f, draws, draw_culled, cell_culled, n_cells, zero_a, n_zero_a, zero_b, n_zero_b, zero_c, n_zero_c, zero_d, n_zero_d,
-                chunk_tab, n_chunks, boxes, chunk_cull && boxes ? 1u : 0u, live_cnt, live_tab, live_cid);
+    GSWT_LAUNCH(k_cull, dim3(grid), dim3(256), s, f, b.draws, b.draw_culled, b.cell_culled, b.n_cells, reinterpret_cast<uint32_t*>(b.counters), b.n_zero_head,
+                reinterpret_cast<uint32_t*>(b.ranges), b.n_zero_ranges, b.block_sums, b.n_chunks, b.radix_depth, b.n_zero_depth,
+                b.chunk_tab, b.n_chunks, b.boxes, chunk_cull && b.boxes ? 1u : 0u, b.live_cnt, b.live_tab, b.live_cid);
 }
 
-void launch_project(hipStream_t s, bool debug, const Frame& f, const DrawDev* draws, const uint2* chunk_tab, uint32_t n_launch, uint32_t n_chunks,
-                    const uint32_t* static_list, const uint32_t* merged_list, const uint32_t* merged_map, const uint4* tex,
-                    const float* hmap, const uint32_t* draw_culled, const uint32_t* cell_culled, uint32_t* live_cnt, const uint4* live_tab, uint2* rects, Rec* recs, float* depths, uint32_t* block_sums,
-                    uint32_t* super_sums, unsigned long long* counters, Varyings* dbg, float4* col_f, uint32_t pair_cap, bool strict)
+void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict)
 {
-    if (n_chunks == 0) return;
-    const uint32_t n_super = n_chunks / 256u + 1u;      // super_sums = [pairs x 16 n_super][visible x 16 n_super][exclusive pair prefix x n_super] (kSuperStride), zeroed by the caller
+    if (b.n_chunks == 0) return;
+    const uint32_t n_super = b.n_chunks / 256u + 1u;    // super_sums = [pairs x 16 n_super][visible x 16 n_super][exclusive pair prefix x n_super] (kSuperStride), zeroed by k_cull
     const bool full = f.surface_type == 2u || f.draw_mode != 0u;
 #define GSWT_LAUNCH_PROJECT_S(D, F, S)                                                                                         \
-    GSWT_LAUNCH((k_project<D, F, S>), dim3(n_launch), dim3(256), s, f, draws, chunk_tab, static_list, merged_list,             \
-                merged_map, tex, hmap, draw_culled, cell_culled, live_cnt, live_tab, rects, recs, depths, block_sums, super_sums, n_super, dbg, col_f)
+    GSWT_LAUNCH((k_project<D, F, S>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,   \
+                b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums, \
+                b.super_sums, n_super, b.dbg, b.col_f)
 #define GSWT_LAUNCH_PROJECT(D, F) do { if (strict) GSWT_LAUNCH_PROJECT_S(D, F, true); else GSWT_LAUNCH_PROJECT_S(D, F, false); } while (0)
     if (debug && full) { GSWT_LAUNCH_PROJECT(true, true); }
     else if (debug) { GSWT_LAUNCH_PROJECT(true, false); }
@@ -2928,36 +2923,32 @@ void launch_project(hipStream_t s, bool debug, const Frame& f, const DrawDev* dr
     else { GSWT_LAUNCH_PROJECT(false, false); }
 #undef GSWT_LAUNCH_PROJECT
 #undef GSWT_LAUNCH_PROJECT_S
-    GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, super_sums, n_super, counters, super_sums + 2u * kSuperStride * n_super, pair_cap, live_cnt, n_launch / 8u);
+    GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, n_super, b.counters, b.super_sums + 2u * kSuperStride * n_super, b.pair_cap, b.live_cnt, n_launch / 8u);
 }
 
 // keys: tile ids, vals: slots.  GSWT_ORDER_DEPTH (dkeys != nullptr): also each pair's depth bits -> dkeys and the frame's key range -> krange.
-void launch_emit(hipStream_t s, const Frame& f, uint32_t n_chunks, const uint2* rects, const uint32_t* block_sums,
-                 const uint32_t* super_sums, uint32_t pair_cap, unsigned long long* counters, uint32_t* keys, uint32_t* vals,
-                 const float* depths, uint32_t* dkeys, uint32_t* krange, const uint32_t* live_cnt, const uint32_t* live_cid, uint32_t n_launch)
+void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch)
 {
+    const uint32_t n_chunks = b.n_chunks, pair_cap = b.pair_cap;
     if (n_chunks == 0) return;
     const uint32_t n_super = n_chunks / 256u + 1u;      // [pairs x n_super][visible x n_super][exclusive pair prefix x n_super]
-    const uint32_t* const excl = super_sums + 2u * kSuperStride * n_super;
+    const uint32_t* const excl = b.super_sums + 2u * kSuperStride * n_super;
     const float* const no_f = nullptr; uint32_t* const no_u = nullptr;
-    // over k_cull's table of live chunks; without one (the debug-varyings frame) over every chunk of the frame, four consecutive ones per workgroup
-    if (live_cnt && live_cid && n_launch) {
-        const uint32_t* const cnt2 = live_cnt + 8u * kSuperStride;               // k_totals' copy of the live counts
-        const dim3 grid(((n_launch / 8u + kEmitGroup - 1u) / kEmitGroup) * 8u);
-        if (dkeys) GSWT_LAUNCH((k_emit<true, true>), grid, dim3(256), s, f, rects, block_sums, excl, n_chunks, pair_cap, counters, keys, vals, depths, dkeys, krange, cnt2, live_cid);
-        else GSWT_LAUNCH((k_emit<false, true>), grid, dim3(256), s, f, rects, block_sums, excl, n_chunks, pair_cap, counters, keys, vals, no_f, no_u, no_u, cnt2, live_cid);
-    } else {
-        const dim3 grid((n_chunks + kEmitGroup - 1u) / kEmitGroup);
-        const uint32_t* const no_c = nullptr;
-        if (dkeys) GSWT_LAUNCH((k_emit<true, false>), grid, dim3(256), s, f, rects, block_sums, excl, n_chunks, pair_cap, counters, keys, vals, depths, dkeys, krange, no_c, no_c);
-        else GSWT_LAUNCH((k_emit<false, false>), grid, dim3(256), s, f, rects, block_sums, excl, n_chunks, pair_cap, counters, keys, vals, no_f, no_u, no_u, no_c, no_c);
-    }
+    // over k_cull's table of live chunks (k_totals' copy of its counts); without one (n_launch 0: the debug-varyings frame) over every chunk of
+    // the frame, four consecutive ones per workgroup
+    const uint32_t* const cnt2 = n_launch ? b.live_cnt + 8u * kSuperStride : nullptr;
+    const uint32_t* const cid = n_launch ? b.live_cid : nullptr;
+    const dim3 grid(n_launch ? ((n_launch / 8u + kEmitGroup - 1u) / kEmitGroup) * 8u : (n_chunks + kEmitGroup - 1u) / kEmitGroup);
+#define GSWT_LAUNCH_EMIT(D, L)                                                                                                 \
+    GSWT_LAUNCH((k_emit<D, L>), grid, dim3(256), s, f, b.rects, b.block_sums, excl, n_chunks, pair_cap, b.counters, keys, b.vals_a, \
+                D ? b.depths : no_f, D ? dkeys : no_u, D ? krange : no_u, cnt2, cid)
+    if (n_launch) { if (dkeys) GSWT_LAUNCH_EMIT(true, true); else GSWT_LAUNCH_EMIT(false, true); }
+    else if (dkeys) GSWT_LAUNCH_EMIT(true, false);
+    else GSWT_LAUNCH_EMIT(false, false);
+#undef GSWT_LAUNCH_EMIT
 }
 
-// Sorts (keys, vals) by key bits [0, key_bits); the pair count is read on the device (*n_ptr), grids are
-// sized for `n_cap`.  Result ends in (keys_a, vals_a) or (keys_b, vals_b): returns 0 if in a, 1 if in b.
-// ws: per pass [ghist 256 x nblk][gsup 256 x nsup][gtot 256]; the gsup/gtot parts must be zero on entry
-// (radix_ws_words() u32 in total, zeroed by k_cull each frame).
+// ws: per pass [ghist 256 x nblk][gsup 256 x nsup][gtot 256] (gswt_device.h: launch_sort)
 size_t radix_ws_words(uint32_t n_cap, int key_bits)
 {
     const uint32_t nblk = (n_cap + kSortBlock - 1) / kSortBlock, nsup = (nblk >> kSupShift) + 1;
@@ -2976,8 +2967,7 @@ size_t radix_ws_zero_words(uint32_t n_cap, int key_bits)
 }
 
 int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n_cap,
-                const unsigned long long* n_ptr, int key_bits, uint32_t* ws, uint2* ranges = nullptr, const uint32_t* krange = nullptr,
-                uint32_t* aux_a = nullptr, uint32_t* aux_b = nullptr)
+                const unsigned long long* n_ptr, int key_bits, uint32_t* ws, uint2* ranges, const uint32_t* krange, uint32_t* aux_a, uint32_t* aux_b)
 {
     if (n_cap == 0) return 0;
     const uint32_t nblk = (n_cap + kSortBlock - 1) / kSortBlock, nsup = (nblk >> kSupShift) + 1;
@@ -3032,10 +3022,7 @@ void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks
     if (n_blocks) hipLaunchKernelGGL(k_mg_copy, dim3(n_blocks), dim3(256), 0, s, jobs, blocks, remap, src, new_list, new_map);
 }
 
-// `ranges` must be zero on entry (k_cull clears it each frame)
-
-// GSWT_ORDER_DEPTH, tile-local path: depth-sorts every screen tile's slice of the (tile-sorted) pair list in LDS; dkeys = the pairs' depth
-// bits in the same order (the tile sort's payload)
+// dkeys = the pairs' depth bits in the order of vals (the tile sort's payload)
 void launch_tile_depth_sort(hipStream_t s, const uint2* ranges, uint32_t* vals, uint32_t* dkeys, uint32_t* vals_scratch, uint32_t* dkeys_scratch, int n_tiles,
                             uint32_t* long_list, unsigned long long* counters)
 {
@@ -3052,67 +3039,60 @@ uint32_t tile_depth_sort_cap() { return kTileSortCap; }
 
 // ranges -> per-tile segment counts -> item_base (exclusive scan, item_base[n_tiles] = #items) ->
 // k_composite over an upper bound of items -> k_combine.
-void launch_composite(hipStream_t s, const Frame& f, const uint2* ranges, const uint32_t* vals, const Rec* recs, const float* depths,
-                      const float4* col_f, const float4* bg_rgba, const float* bg_depth, float4* out, int n_tiles, int out_rows,
-                      uint32_t seg, uint32_t n_pairs, uint32_t* item_base, uint4* item_tab, float4* partials,
-                      hipEvent_t ev_begin, hipEvent_t ev_end, unsigned long long* counters, unsigned long long* host_counters, int variant,
-                      const uint32_t* krange, uint32_t depth_passes, uint32_t* tile_tick, bool report_max, bool heavy_first)
+void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
+                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
+    const int n_tiles = (int)b.n_tiles;
+    const uint32_t seg = b.seg;
     if (n_tiles == 0) {                 // a shard without screen tiles (more ranks than tile columns): the events still exist
         if (ev_begin) hipEventRecord(ev_begin, s);
         if (ev_end) hipEventRecord(ev_end, s);
         return;
     }
-    const uint32_t max_items = (uint32_t)n_tiles + n_pairs / seg + 1u;
-    // variant 2 (GSWT_OPT_FOLD_COMBINE): k_composite folds the segment partials itself and writes the empty tiles: no k_combine launch
-    const bool fold = variant == 2 && tile_tick != nullptr && host_counters != nullptr;
-    if (heavy_first) {
-        GSWT_LAUNCH(k_items<true>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, ranges, n_tiles, seg, item_base, item_tab, max_items, krange, depth_passes, counters,
-                fold ? 1u : 0u, report_max ? 1u : 0u);
-    } else {
-        GSWT_LAUNCH(k_items<false>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, ranges, n_tiles, seg, item_base, item_tab, max_items, krange, depth_passes, counters,
-                fold ? 1u : 0u, report_max ? 1u : 0u);
-    }
+    const uint32_t max_items = (uint32_t)n_tiles + b.pair_cap / seg + 1u;
+    // variant 2 (GSWT_OPT_FOLD_COMBINE): k_composite folds the segment b.partials itself and writes the empty tiles: no k_combine launch
+    const bool fold = variant == 2 && b.tile_tick != nullptr && b.host_counters != nullptr;
+    if (heavy_first)
+        GSWT_LAUNCH(k_items<true>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, b.ranges, n_tiles, seg, b.item_base, b.item_tab, max_items, krange, depth_passes, b.counters,
+                    fold ? 1u : 0u, report_max ? 1u : 0u);
+    else
+        GSWT_LAUNCH(k_items<false>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, b.ranges, n_tiles, seg, b.item_base, b.item_tab, max_items, krange, depth_passes, b.counters,
+                    fold ? 1u : 0u, report_max ? 1u : 0u);
     const bool early = f.t_eps > 0.0f, depth = f.has_depth != 0, colf = f.draw_mode != 0u;
+    // the compositor instantiation <early-out, depth test, float colours> the frame needs (debug draw modes: float colours from the side buffer)
+#define GSWT_COMPOSITE_EDC(LAUNCH)                                                                                             \
+    do {                                                                                                                       \
+        if (colf) { if (depth) LAUNCH(false, true, true); else LAUNCH(false, false, true); }                                   \
+        else if (early && depth) LAUNCH(true, true, false);                                                                    \
+        else if (early) LAUNCH(true, false, false);                                                                            \
+        else if (depth) LAUNCH(false, true, false);                                                                            \
+        else LAUNCH(false, false, false);                                                                                      \
+    } while (0)
     // (the compositors carry ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED)
     if (variant == 1) {                  // GSWT_OPT_COMPOSITE = 1: decoupled waves (k_composite_dw), same image bit for bit
 #define GSWT_LAUNCH_COMPOSITE_DW(E, D, C)                                                                                      \
-        GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, item_base, item_tab, vals, recs, \
-                           depths, col_f, bg_rgba, bg_depth, out, partials, n_tiles, out_rows)
-        if (colf) { if (depth) GSWT_LAUNCH_COMPOSITE_DW(false, true, true); else GSWT_LAUNCH_COMPOSITE_DW(false, false, true); }
-        else if (early && depth) GSWT_LAUNCH_COMPOSITE_DW(true, true, false);
-        else if (early) GSWT_LAUNCH_COMPOSITE_DW(true, false, false);
-        else if (depth) GSWT_LAUNCH_COMPOSITE_DW(false, true, false);
-        else GSWT_LAUNCH_COMPOSITE_DW(false, false, false);
+        GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs, \
+                           b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows)
+        GSWT_COMPOSITE_EDC(GSWT_LAUNCH_COMPOSITE_DW);
 #undef GSWT_LAUNCH_COMPOSITE_DW
-        GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, item_base, partials, bg_rgba, out, n_tiles, out_rows, (const unsigned long long*)counters, host_counters);
+        GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows, (const unsigned long long*)b.counters, b.host_counters);
         return;
     }
     if (fold) {
 #define GSWT_LAUNCH_COMPOSITE_F(E, D, C)                                                                                       \
-        GSWT_LAUNCH_TIMED((k_composite<E, D, C, true>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, ranges, item_base, item_tab, seg, vals, recs, \
-                           depths, col_f, bg_rgba, bg_depth, out, partials, n_tiles, out_rows, tile_tick, (const unsigned long long*)counters, host_counters)
-        if (colf) { if (depth) GSWT_LAUNCH_COMPOSITE_F(false, true, true); else GSWT_LAUNCH_COMPOSITE_F(false, false, true); }
-        else if (early && depth) GSWT_LAUNCH_COMPOSITE_F(true, true, false);
-        else if (early) GSWT_LAUNCH_COMPOSITE_F(true, false, false);
-        else if (depth) GSWT_LAUNCH_COMPOSITE_F(false, true, false);
-        else GSWT_LAUNCH_COMPOSITE_F(false, false, false);
+        GSWT_LAUNCH_TIMED((k_composite<E, D, C, true>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals, b.recs, \
+                           b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.tile_tick, (const unsigned long long*)b.counters, b.host_counters)
+        GSWT_COMPOSITE_EDC(GSWT_LAUNCH_COMPOSITE_F);
 #undef GSWT_LAUNCH_COMPOSITE_F
         return;
     }
 #define GSWT_LAUNCH_COMPOSITE(E, D, C)                                                                                         \
-    GSWT_LAUNCH_TIMED((k_composite<E, D, C>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, ranges, item_base, item_tab, seg, vals, recs, \
-                       depths, col_f, bg_rgba, bg_depth, out, partials, n_tiles, out_rows, (uint32_t*)nullptr, (const unsigned long long*)nullptr, (unsigned long long*)nullptr)
-    if (colf) {                       // debug draw modes: float colours from the side buffer
-        if (depth) GSWT_LAUNCH_COMPOSITE(false, true, true);
-        else GSWT_LAUNCH_COMPOSITE(false, false, true);
-    }
-    else if (early && depth) GSWT_LAUNCH_COMPOSITE(true, true, false);
-    else if (early) GSWT_LAUNCH_COMPOSITE(true, false, false);
-    else if (depth) GSWT_LAUNCH_COMPOSITE(false, true, false);
-    else GSWT_LAUNCH_COMPOSITE(false, false, false);
+    GSWT_LAUNCH_TIMED((k_composite<E, D, C>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals, b.recs, \
+                       b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, (uint32_t*)nullptr, (const unsigned long long*)nullptr, (unsigned long long*)nullptr)
+    GSWT_COMPOSITE_EDC(GSWT_LAUNCH_COMPOSITE);
 #undef GSWT_LAUNCH_COMPOSITE
-    GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, item_base, partials, bg_rgba, out, n_tiles, out_rows, (const unsigned long long*)counters, host_counters);
+#undef GSWT_COMPOSITE_EDC
+    GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows, (const unsigned long long*)b.counters, b.host_counters);
 }
 
 // k_totals alone on caller-provided sums (unit test of the 64-bit pair count)

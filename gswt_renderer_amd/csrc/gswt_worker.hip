@@ -21,14 +21,12 @@
 #include <string>
 
 #include "../../include/gswt_hip.h"
+#include "gswt_device.h"
 #define GSWT_HD __host__ __device__
 #include "host/gswt_math.h"
 #include "host/gswt_surface.h"
 
 namespace gswt {
-int launch_sort(hipStream_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, const unsigned long long*, int, uint32_t*, uint2* = nullptr, const uint32_t* = nullptr,
-                uint32_t* = nullptr, uint32_t* = nullptr);
-size_t radix_ws_words(uint32_t, int);
 int ctx_device(const gswt_ctx*);
 }  // namespace gswt
 
