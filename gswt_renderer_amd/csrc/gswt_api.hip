@@ -270,7 +270,7 @@ struct gswt_ctx {
     // scene
     DevBuf<uint4> tex;
     size_t n_splats = 0;
-    float loc_lo[3] = {}, loc_hi[3] = {}, loc_max_trace = 0.0f;      // tile-local bounds of the splat centres, largest covariance trace
+    float loc_lo[3] = {}, loc_hi[3] = {}, loc_max_trace = 0.0f;      // tile-local bounds of the splat centres, largest covariance bound (trace when PSD)
     DevBuf<uint32_t> static_list;
     DevBuf<float> static_boxes;            // tile-local bounding box (lo.xyz, hi.xyz) of every 256-entry chunk of every static list (k_live's chunk cull)
     std::vector<ListRef> lists;
@@ -673,7 +673,7 @@ try {
     HIP_TRY(c, c->tex.ensure(2 * n_splats));
     HIP_TRY(c, hipMemcpy(c->tex.p, tex_data, n_splats * 32, hipMemcpyHostToDevice));
     c->n_splats = n_splats;
-    {   // tile-local bounds of every splat centre and the largest covariance trace: what the band cull of column-sharded frames
+    {   // tile-local bounds of every splat centre and the largest covariance bound: what the band cull of column-sharded frames
         // places at a map cell's origin (every Wang-tile instance is the same tile-local content)
         float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
         float tr_max = 0.0f;
@@ -692,7 +692,17 @@ try {
                 if (!(p[k] == p[k]) || p[k] > 3e38f || p[k] < -3e38f) { odd = true; continue; }
                 lo[k] = std::min(lo[k], p[k]); hi[k] = std::max(hi[k], p[k]);
             }
-            const float tr = half_val(r[4] & 0xFFFFu) + half_val(r[5] >> 16) + half_val(r[6] >> 16);      // xx + yy + zz
+            // the projected extent is bounded by the sum of the decoded covariance's POSITIVE eigenvalues: the trace when the decoded
+            // matrix is positive semi-definite, otherwise at most (trace + sqrt(3) |S|_F) / 2 (nuclear norm <= sqrt(3) Frobenius norm).
+            // The decode makes stored covariances indefinite: an overflowed (Inf) diagonal reads as 0 beside finite off-diagonals
+            // (lambda_1 up to several times the trace), a raw row may hold a negative diagonal.
+            const double xx = half_val(r[4] & 0xFFFFu), xy = half_val(r[4] >> 16), xz = half_val(r[5] & 0xFFFFu);
+            const double yy = half_val(r[5] >> 16), yz = half_val(r[6] & 0xFFFFu), zz = half_val(r[6] >> 16);
+            const double tr_d = xx + yy + zz;
+            const bool psd = xx >= 0.0 && yy >= 0.0 && zz >= 0.0 && xx * yy - xy * xy >= 0.0 && xx * zz - xz * xz >= 0.0 &&
+                             yy * zz - yz * yz >= 0.0 && xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz) >= 0.0;
+            const double fro = std::sqrt(xx * xx + yy * yy + zz * zz + 2.0 * (xy * xy + xz * xz + yz * yz));
+            const float tr = psd ? (float)tr_d : (float)(0.5 * (tr_d + 1.7320508075688772 * fro) * (1.0 + 1e-6));
             if (tr == tr) tr_max = std::max(tr_max, tr);
         }
         if (odd || lo[0] > hi[0]) { for (int k = 0; k < 3; k++) { lo[k] = -3.402823466e+38f; hi[k] = 3.402823466e+38f; } }    // never cull

@@ -983,8 +983,9 @@ __global__ __launch_bounds__(256) void k_project(
             if (!((uu > 0.0f) && (ww > 0.0f) && (uu < __builtin_inff()) && (ww < __builtin_inff()))) break;
             if (DEBUG) vout.visible = 1;
             visible = true;
-            // depth_compare Less against the 1.0 clear when no proxy depth is bound (renderer.rs:182,436)
-            if (!f.has_depth && !(depth < 1.0f)) { visible = false; break; }
+            // depth_compare Less against the 1.0 clear when no proxy depth is bound (renderer.rs:182,436): a vertex-stage survivor
+            // (counted in n_visible) that no fragment of can pass -- no pairs
+            if (!f.has_depth && !(depth < 1.0f)) break;
             const float ruu = 1.0f / uu, rww = 1.0f / ww;
             const float r_iux = ux * ruu, r_iuy = uy * ruu, r_ivx = wx * rww, r_ivy = wy * rww;
             // half extents of |p| <= 2, inflated by 1e-5 relative + 1e-3 px (conservative under f32 rounding)

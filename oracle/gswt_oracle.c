@@ -962,7 +962,8 @@ typedef struct {
     uint64_t n_instanced;   /* sum of draw counts                */
     uint64_t n_visible;     /* survivors of the vertex stage     */
     uint64_t n_pairs16;     /* (splat, 16x16 block) pairs: blocks holding >= 1 pixel centre inside the
-                               splat's axis-aligned bounding box of |p| <= 2 (frag_setup's hx, hy) */
+                               splat's axis-aligned bounding box of |p| <= 2 (frag_setup's hx, hy); none
+                               for a splat of depth 1.0 without bg_depth (it cannot pass the depth test) */
 } orc_stats;
 
 /*
@@ -1013,7 +1014,9 @@ ORC_API int orc_render(const orc_camera *cam, const orc_scene *scene, const uint
                 vis_d++;
                 float fx0 = ceilf(fs[k].cxp - fs[k].hx - 0.5f), fx1 = floorf(fs[k].cxp + fs[k].hx - 0.5f);
                 float fy0 = ceilf(fs[k].cyp - fs[k].hy - 0.5f), fy1 = floorf(fs[k].cyp + fs[k].hy - 0.5f);
-                if (fx1 >= fx0 && fy1 >= fy0 && fx1 >= 0.0f && fy1 >= 0.0f && fx0 <= (float)(W - 1) && fy0 <= (float)(H - 1)) {
+                /* no pairs for a splat whose every fragment fails the `Less` test against the 1.0 clear (depth == 1.0, no bg_depth) */
+                if ((bg_depth || sp[k].depth < 1.0f) &&
+                    fx1 >= fx0 && fy1 >= fy0 && fx1 >= 0.0f && fy1 >= 0.0f && fx0 <= (float)(W - 1) && fy0 <= (float)(H - 1)) {
                     int x0 = fx0 < 0 ? 0 : (int)fx0, x1 = fx1 > (float)(W - 1) ? W - 1 : (int)fx1;
                     int y0 = fy0 < 0 ? 0 : (int)fy0, y1 = fy1 > (float)(H - 1) ? H - 1 : (int)fy1;
                     pairs_d += (uint64_t)((x1 >> 4) - (x0 >> 4) + 1) * (uint64_t)((y1 >> 4) - (y0 >> 4) + 1);

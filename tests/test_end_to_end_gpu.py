@@ -16,13 +16,14 @@ TOL = 1e-4
 
 
 def _run_case(renderer, cfg, cam, W, Hh, *, lod0=600, n_lod=3, bg=False, t_eps=0.0, shard=None, culling_dist=1.0, order_mode=0,
-              render_config=None, shard_cols=False, stats=None):
-    """render_config: RenderConfig fields of SceneUniforms (draw_mode, point_cloud_radius, use_clip, clip_height)."""
+              render_config=None, shard_cols=False, stats=None, verts=None, max_pairs=None):
+    """render_config: RenderConfig fields of SceneUniforms (draw_mode, point_cloud_radius, use_clip, clip_height).
+    verts: the tile set (default synth.make_tileset(n_lod, 16, lod0)); max_pairs: the oracle's n_pairs16 must stay below it, checked
+    before the frame goes to the GPU."""
     rc = dict(render_config or {})
-    verts = synth.make_tileset(n_lod=n_lod, n_tile=16, lod0_count=lod0)
-    pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer)
+    if verts is None:
+        verts = synth.make_tileset(n_lod=n_lod, n_tile=16, lod0_count=lod0)
     cu, vp = host.camera_uniforms(cam[0], cam[1], (0, 0, 1), 45.0, 0.1, 2400.0, W, Hh)
-    pipe.update(cam[0], vp)
     # oracle side
     pp = orc.preprocess([[orc.scene_load(v) for v in lod] for lod in verts])
     ow = wo.WangTile(pp)
@@ -40,6 +41,10 @@ def _run_case(renderer, cfg, cam, W, Hh, *, lod0=600, n_lod=3, bg=False, t_eps=0
         bg_depth = rng.uniform(0.97, 1.0, size=(Hh, W)).astype(np.float32)
     ref, st = orc.render(ocam.uniforms(), osu, pp.tex, odraws, W, Hh, height_map=hm, bg_rgba=bg_rgba, bg_depth=bg_depth,
                          order_mode=order_mode)
+    if max_pairs is not None:
+        assert st["n_pairs16"] < max_pairs, st
+    pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer)
+    pipe.update(cam[0], vp)
     kinds = {"plain": 0, "blend": 0, "merged": 0}
     for d in odraws:
         kinds["merged" if d.tile.single_draw else ("blend" if d.tile.changing else "plain")] += 1
