@@ -39,6 +39,9 @@ GSWT_OPT_NO_CHUNK_CULL = 15
 GSWT_OPT_ITEM_ORDER = 16
 GSWT_SHARD_ROWS = 0
 GSWT_SHARD_COLUMNS = 1
+GSWT_OUT_RGBA32F = 0          # RenderConfig.out_format: RGBA f32, 16 bytes per pixel
+GSWT_OUT_RGBA8_UNORM = 1      # bytes R, G, B, A per pixel
+GSWT_OUT_BGRA8_UNORM = 2      # bytes B, G, R, A per pixel
 
 
 class CameraUniforms(C.Structure):
@@ -89,7 +92,7 @@ class MergeMember(C.Structure):
 class RenderConfig(C.Structure):
     _fields_ = [("culling_dist", C.c_float), ("lod_enable_mask", C.c_uint32), ("order_mode", C.c_int32),
                 ("transmittance_eps", C.c_float), ("shard_index", C.c_int32), ("shard_count", C.c_int32),
-                ("shard_mode", C.c_int32), ("_pad", C.c_uint32)]
+                ("shard_mode", C.c_int32), ("out_format", C.c_uint32)]
 
 
 class Timings(C.Structure):
@@ -182,6 +185,7 @@ SYMBOLS = {
     "gswt_shard_rows_padded": (C.c_int, [C.c_int, C.c_int]),
     "gswt_unshard": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "gswt_unshard_mode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "gswt_unshard_format": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gswt_shard_cols_padded": (C.c_int, [C.c_int, C.c_int]),
     "gswt_comm_unique_id": (C.c_int, [_P]),
     "gswt_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),

@@ -125,6 +125,8 @@ constexpr const char* kStreamLayout = "c012p34s";
 // round robin the merged lists of the last kDrawSets - 1 = 9 sort events stay addressable for gswt_set_draws_merge_groups
 constexpr int kDrawSets = kFrameSlots + 5;
 static_assert(kDrawSets <= kMergeSources, "MergeSources holds one pointer pair per draw set");
+static_assert(sizeof(gswt_render_config) == 32 && offsetof(gswt_render_config, out_format) == 28, "gswt_render_config layout");
+static_assert(GSWT_OUT_RGBA32F == kOutF32 && GSWT_OUT_RGBA8_UNORM == kOutRGBA8 && GSWT_OUT_BGRA8_UNORM == kOutBGRA8, "output formats");
 template <typename T>
 struct Ref { T* p = nullptr; };
 
@@ -459,7 +461,7 @@ const char* rccl_load()
 constexpr int kNcclFloat = 7;      // ncclFloat32 (rccl.h ncclDataType_t)
 
 // geometry of a slot's shard image (what its frame wrote to args.d_out)
-struct ShardGeom { int world, mode, out_rows, out_w; size_t px; };
+struct ShardGeom { int world, mode, out_rows, out_w, fmt; size_t px, bytes; };
 ShardGeom shard_geom(const FrameSlot& sl)
 {
     ShardGeom g;
@@ -470,6 +472,8 @@ ShardGeom shard_geom(const FrameSlot& sl)
     g.out_rows = g.world > 1 && !cols ? gswt_shard_rows_padded(sl.args.height, g.world) : sl.args.height;
     g.out_w = cols ? gswt_shard_cols_padded(sl.args.width, g.world) : sl.args.width;
     g.px = (size_t)g.out_rows * g.out_w;
+    g.fmt = (int)cfg.out_format;
+    g.bytes = g.px * out_pixel_bytes(g.fmt);
     return g;
 }
 
@@ -1258,6 +1262,8 @@ static int validate_frame(gswt_ctx* c, const gswt_camera_uniforms* cam, const gs
     const int sc = cfg->shard_count <= 1 ? 1 : cfg->shard_count;
     if (sc > 1 && (cfg->shard_index < 0 || cfg->shard_index >= sc)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: bad shard index");
     if (cfg->shard_mode != GSWT_SHARD_ROWS && cfg->shard_mode != GSWT_SHARD_COLUMNS) return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: unknown shard mode %d", cfg->shard_mode);
+    if (cfg->out_format != GSWT_OUT_RGBA32F && cfg->out_format != GSWT_OUT_RGBA8_UNORM && cfg->out_format != GSWT_OUT_BGRA8_UNORM)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: unknown out_format %u", cfg->out_format);
     return GSWT_OK;
 }
 
@@ -1542,7 +1548,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         if (hipEventQuery(D.ev_up) == hipSuccess) D.built = true;
         else HIP_TRY(c, hipStreamWaitEvent(s, D.ev_up, 0));
     }
-    if (a.cfg.shard_count > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(a.d_out, 0, out_px * 16, s));
+    if (a.cfg.shard_count > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(a.d_out, 0, out_px * out_pixel_bytes((int)a.cfg.out_format), s));
     // GSWT_OPT_GRAPH: from here to the end of the frame the launch sites record instead of launching (frames that carry timing
     // events, debug varyings and shards without tiles launch as before)
     const bool use_graph = c->opt_graph != 0 && c->opt_timing == 0 && !dbg && n_tiles > 0 && sl.hc_dev != nullptr;
@@ -1571,7 +1577,8 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
     if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvSorted], s));
     if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvRanges], s));
     launch_composite(s, f, b, vals, out_rows, c->opt_composite, depth_order && !sl.depth_local ? b.krange : nullptr, sl.depth_passes, depth_order,
-                     c->opt_item_order != 0, c->opt_timing >= 1 ? ev[kEvCompositeBegin] : nullptr, c->opt_timing >= 1 ? ev[kEvCompositeEnd] : nullptr);
+                     c->opt_item_order != 0, c->opt_timing >= 1 ? ev[kEvCompositeBegin] : nullptr, c->opt_timing >= 1 ? ev[kEvCompositeEnd] : nullptr,
+                     (int)a.cfg.out_format);
     c->last_n_tiles = (uint32_t)n_tiles;
     c->last_slot = (int)(&sl - c->slots);
     if (c->opt_timing >= 1) HIP_TRY(c, hipEventRecord(ev[kEvEnd], s));
@@ -1672,6 +1679,7 @@ try {
     const bool cols = sc > 1 && cfg->shard_mode == GSWT_SHARD_COLUMNS;
     const int out_rows = sc > 1 && !cols ? gswt_shard_rows_padded(height, sc) : height;
     const size_t out_px = (size_t)out_rows * (cols ? gswt_shard_cols_padded(width, sc) : width), npx = (size_t)width * height;
+    const size_t out_bytes = out_px * out_pixel_bytes((int)cfg->out_format);
     const float4* d_bg = nullptr; const float* d_bgd = nullptr; float4* d_out = nullptr;
     if (bg_rgba) {
         if (bg_on_device) d_bg = reinterpret_cast<const float4*>(bg_rgba);
@@ -1682,7 +1690,7 @@ try {
         else { HIP_TRY(c, c->bg_depth.ensure(npx)); HIP_TRY(c, hipMemcpyAsync(c->bg_depth.p, bg_depth, npx * 4, hipMemcpyHostToDevice, s)); d_bgd = c->bg_depth.p; }
     }
     if (out_on_device) d_out = reinterpret_cast<float4*>(out_rgba);
-    else { HIP_TRY(c, c->out_img.ensure(out_px)); d_out = c->out_img.p; }
+    else { HIP_TRY(c, c->out_img.ensure((out_bytes + 15) / 16)); d_out = c->out_img.p; }
     int si0 = 0;
     for (int k = 0; k < kFrameSlots; k++) if (!c->slots[k].pending) { si0 = k; break; }
     FrameSlot& sl = c->slots[si0];
@@ -1692,7 +1700,7 @@ try {
     rc = finish_frame(c, sl);
     if (rc != GSWT_OK) return rc;
     if (!out_on_device) {
-        HIP_TRY(c, hipMemcpyAsync(out_rgba, d_out, out_px * 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(out_rgba, d_out, out_bytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
     return GSWT_OK;
@@ -1919,15 +1927,20 @@ try {
 
 int gswt_unshard_mode(gswt_ctx* c, const float* gathered, int width, int height, int shard_count, int shard_mode, float* out_rgba)
 try {
-    if (!c || !gathered || !out_rgba || width <= 0 || height <= 0 || shard_count < 1) return GSWT_ERR_BAD_ARG;
+    return gswt_unshard_format(c, gathered, width, height, shard_count, shard_mode, GSWT_OUT_RGBA32F, out_rgba);
+} GSWT_CATCH("gswt_unshard_mode")
+
+int gswt_unshard_format(gswt_ctx* c, const void* gathered, int width, int height, int shard_count, int shard_mode, int out_format, void* out)
+try {
+    if (!c || !gathered || !out || width <= 0 || height <= 0 || shard_count < 1) return GSWT_ERR_BAD_ARG;
     if (shard_mode != GSWT_SHARD_ROWS && shard_mode != GSWT_SHARD_COLUMNS) return GSWT_ERR_BAD_ARG;
+    if (out_format != GSWT_OUT_RGBA32F && out_format != GSWT_OUT_RGBA8_UNORM && out_format != GSWT_OUT_BGRA8_UNORM) return GSWT_ERR_BAD_ARG;
     hipSetDevice(c->device);
-    launch_unshard(c->stream, reinterpret_cast<const float4*>(gathered), reinterpret_cast<float4*>(out_rgba), width, height,
-                   shard_count, gswt_shard_rows_padded(height, shard_count),
-                   shard_mode == GSWT_SHARD_COLUMNS ? gswt_shard_cols_padded(width, shard_count) : 0);
+    launch_unshard(c->stream, gathered, out, width, height, shard_count, gswt_shard_rows_padded(height, shard_count),
+                   shard_mode == GSWT_SHARD_COLUMNS ? gswt_shard_cols_padded(width, shard_count) : 0, out_format);
     HIP_TRY(c, hipGetLastError());
     return GSWT_OK;
-} GSWT_CATCH("gswt_unshard_mode")
+} GSWT_CATCH("gswt_unshard_format")
 
 // ---- multi-GPU gather ------------------------------------------------------------------------------------------------
 int gswt_comm_unique_id(void* id_out)
@@ -2005,14 +2018,15 @@ try {
     hipSetDevice(c->device);
     if (g.world == 1) {                                   // nothing to gather: the shard is the frame
         if (reinterpret_cast<float4*>(frame_out_dev) != sl.args.d_out)
-            HIP_TRY(c, hipMemcpyAsync(frame_out_dev, sl.args.d_out, g.px * 16, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(frame_out_dev, sl.args.d_out, g.bytes, hipMemcpyDeviceToDevice, c->stream));
         return GSWT_OK;
     }
-    HIP_TRY(c, c->gather_buf.ensure((size_t)g.world * g.px));
-    const int nrc = g_rccl.AllGather(sl.args.d_out, c->gather_buf.p, g.px * 4, kNcclFloat, c->comm, c->stream);
+    HIP_TRY(c, c->gather_buf.ensure(((size_t)g.world * g.bytes + 15) / 16));
+    // (the shard moves as 4-byte words whatever its format: g.bytes is a multiple of 4)
+    const int nrc = g_rccl.AllGather(sl.args.d_out, c->gather_buf.p, g.bytes / 4, kNcclFloat, c->comm, c->stream);
     if (nrc != 0) return fail(c, GSWT_ERR_RCCL, "ncclAllGather: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nrc) : "error");
-    launch_unshard(c->stream, c->gather_buf.p, reinterpret_cast<float4*>(frame_out_dev), sl.args.width, sl.args.height, g.world,
-                   gswt_shard_rows_padded(sl.args.height, g.world), g.mode == GSWT_SHARD_COLUMNS ? g.out_w : 0);
+    launch_unshard(c->stream, c->gather_buf.p, frame_out_dev, sl.args.width, sl.args.height, g.world,
+                   gswt_shard_rows_padded(sl.args.height, g.world), g.mode == GSWT_SHARD_COLUMNS ? g.out_w : 0, g.fmt);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(sl.ev_gather, c->stream));
     sl.gather_recorded = true;
@@ -2034,8 +2048,13 @@ try {
         const ShardGeom g = shard_geom(sl);
         if (g.world != n || sl.args.cfg.shard_index != r || g.mode != g0.mode || g.px != g0.px || sl.args.width != ctxs[0]->slots[tickets[0]].args.width)
             return fail(c, GSWT_ERR_BAD_ARG, "gswt_group_render_gather: rank %d rendered shard %d of %d", r, sl.args.cfg.shard_index, g.world);
+        if (g.fmt != g0.fmt)
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_group_render_gather: rank %d rendered out_format %d, rank 0 out_format %d", r, g.fmt, g0.fmt);
+    }
+    for (int r = 0; r < n; r++) {
+        gswt_ctx* c = ctxs[r];
         hipSetDevice(c->device);
-        HIP_TRY(c, c->gather_buf.ensure((size_t)n * g.px));
+        HIP_TRY(c, c->gather_buf.ensure(((size_t)n * g0.bytes + 15) / 16));
     }
     // 2. push: rank r copies its shard into slot r of every peer's gather buffer (xGMI peer copies; a plain copy on one device).
     // A peer's gather buffer may still be read by the re-assembly of the PREVIOUS gather on the peer's own stream (gathers are
@@ -2047,7 +2066,8 @@ try {
         for (int p = 0; p < n; p++)
             if (p != r && ctxs[p]->unshard_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, ctxs[p]->ev_unshard, 0));
         for (int p = 0; p < n; p++)
-            HIP_TRY(c, hipMemcpyPeerAsync(ctxs[p]->gather_buf.p + (size_t)r * g0.px, ctxs[p]->device, sl.args.d_out, c->device, g0.px * 16, c->stream));
+            HIP_TRY(c, hipMemcpyPeerAsync(reinterpret_cast<char*>(ctxs[p]->gather_buf.p) + (size_t)r * g0.bytes, ctxs[p]->device, sl.args.d_out, c->device,
+                                          g0.bytes, c->stream));
         HIP_TRY(c, hipEventRecord(c->ev_push, c->stream));
     }
     // 3. every rank waits (on the device) for all pushes, then re-assembles the frame
@@ -2058,10 +2078,10 @@ try {
         for (int r = 0; r < n; r++) HIP_TRY(c, hipStreamWaitEvent(c->stream, ctxs[r]->ev_push, 0));
         if (n == 1) {
             if (reinterpret_cast<float4*>(frames_out_dev[p]) != sl.args.d_out)
-                HIP_TRY(c, hipMemcpyAsync(frames_out_dev[p], c->gather_buf.p, g0.px * 16, hipMemcpyDeviceToDevice, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(frames_out_dev[p], c->gather_buf.p, g0.bytes, hipMemcpyDeviceToDevice, c->stream));
         } else {
-            launch_unshard(c->stream, c->gather_buf.p, reinterpret_cast<float4*>(frames_out_dev[p]), sl.args.width, sl.args.height, n,
-                           gswt_shard_rows_padded(sl.args.height, n), g0.mode == GSWT_SHARD_COLUMNS ? g0.out_w : 0);
+            launch_unshard(c->stream, c->gather_buf.p, frames_out_dev[p], sl.args.width, sl.args.height, n,
+                           gswt_shard_rows_padded(sl.args.height, n), g0.mode == GSWT_SHARD_COLUMNS ? g0.out_w : 0, g0.fmt);
             HIP_TRY(c, hipGetLastError());
         }
         HIP_TRY(c, hipEventRecord(c->ev_unshard, c->stream));

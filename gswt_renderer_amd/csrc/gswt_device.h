@@ -14,6 +14,9 @@ constexpr int kTile = 16;            // screen tile edge, pixels (BASELINE north
 constexpr int kChunk = 256;          // list entries per projection workgroup
 constexpr uint32_t kLodShift = 28;   // packed list entry = gs_index | lod_id << 28
 constexpr uint32_t kIdxMask = (1u << kLodShift) - 1u;
+// output image formats, GSWT_OUT_* of gswt_hip.h: RGBA f32 (16 B per pixel), bytes R G B A, bytes B G R A (4 B per pixel)
+constexpr int kOutF32 = 0, kOutRGBA8 = 1, kOutBGRA8 = 2;
+inline size_t out_pixel_bytes(int out_format) { return out_format == kOutF32 ? 16u : 4u; }
 
 // Device-side draw descriptor: what one reference draw call binds (renderer.rs:499-590).
 struct DrawDev {
@@ -276,8 +279,9 @@ void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks
 void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_cull);
 void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict);
 void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
+// b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer).
 void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
-                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end);
+                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format);
 void launch_totals(hipStream_t s, uint32_t* super_sums, uint32_t n_super, unsigned long long* counters, uint32_t pair_cap);
 
 // LSD radix sort of (keys, vals) on key bits [0, key_bits), ping-pong between the a and b buffers; returns 0 if the result is in a, 1 if in b.
@@ -297,7 +301,9 @@ void launch_tile_depth_sort(hipStream_t s, const uint2* ranges, uint32_t* vals, 
 inline size_t tile_depth_list_words(size_t n_tiles) { return n_tiles + 1; }
 uint32_t tile_depth_sort_cap();
 
-void launch_unshard(hipStream_t s, const float4* gathered, float4* out, int width, int height, int shard_count, int rows_padded, int band_px);
+// out_format: kOut* (16- or 4-byte pixels)
+void launch_unshard(hipStream_t s, const void* gathered, void* out, int width, int height, int shard_count, int rows_padded, int band_px,
+                    int out_format);
 void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int width, int height, int face_size, int equirect,
                    const float4* faces, float4* out);
 void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi, float4* faces);

@@ -2370,6 +2370,20 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
 // the gather latency was already covered by the other workgroups of the CU.  "stage-only 58 us" in the ablation is
 // what staging costs with nothing to hide behind, not a serial share of the full kernel.
 
+// The store of a final pixel (k_composite, k_composite_dw, k_combine) in an 8-bit output format (gswt_hip.h, GSWT_OUT_*; kOutF32 stores the
+// float4 as it is, in the kernels' own statement).  Per channel q(x) = round_half_even(min(max(x, 0), 1) * 255) -- fmaxf drops a NaN (-> 0),
+// the product is one binary32 multiplication (-ffp-contract=off), v_rndne_f32 rounds half to even, the integral result converts exactly --,
+// packed into ONE 32-bit store per lane: the 16 lanes of a pixel row of the tile (the lane -> pixel map) write 64 contiguous bytes.  (The
+// compiler folds the clamp into the blend's final v_fma_f32 as its clamp modifier, which also takes NaN to 0.)
+__device__ __forceinline__ uint32_t unorm8(float x) { return (uint32_t)__builtin_rintf(fminf(fmaxf(x, 0.0f), 1.0f) * 255.0f); }
+template <int OUTF>
+__device__ __forceinline__ void store_unorm8(float4* out, size_t i, const float4& o)
+{
+    static_assert(OUTF == kOutRGBA8 || OUTF == kOutBGRA8, "8-bit formats only");
+    const uint32_t r = unorm8(o.x), g = unorm8(o.y), b = unorm8(o.z), a = unorm8(o.w);
+    reinterpret_cast<uint32_t*>(out)[i] = OUTF == kOutBGRA8 ? (b | g << 8 | r << 16 | a << 24) : (r | g << 8 | b << 16 | a << 24);
+}
+
 // FOLD (GSWT_OPT_FOLD_COMBINE, round 4): no k_combine behind the compositor.  (a) k_items hands out an empty work item for every tile
 // without pairs: its background is written here.  (b) The segments of a long tile list are folded by whichever of their workgroups finishes
 // LAST: every segment stores its partial (C, T) with agent-scope (sc1) stores -- the L2 of an XCD is not coherent with the other seven
@@ -2378,7 +2392,8 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
 // k_combine does: the image is bit-identical whichever workgroup that is.  (c) Workgroup 0 publishes the frame's counters to the host.
 // One ticket per multi-segment work item on ITS tile's word: ~700 atomics per c3 frame on ~250 addresses (a single frame-wide ticket
 // word would serialise at ~8 ns per atomic on the memory side).
-template <bool EARLY, bool DEPTH, bool COLF, bool FOLD = false>
+// OUTF: the output format (kOut*); only the final store differs.
+template <bool EARLY, bool DEPTH, bool COLF, bool FOLD, int OUTF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || COLF) ? 7 : 8, 8))) void k_composite(const Frame f, const uint2* __restrict__ ranges,
                                                    const uint32_t* __restrict__ item_base, const uint4* __restrict__ item_tab,
                                                    uint32_t seg, const uint32_t* __restrict__ vals, const Rec* __restrict__ recs,
@@ -2605,7 +2620,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
         o.z = fmaf(T, bg.z, ab);
         o.w = fmaf(T, bg.w, 1.0f - T);
         const int orow = tyl * kTile + lyi;      // compacted row inside the shard image
-        if (orow < out_rows) out[(size_t)orow * f.out_w + (px - f.out_x0)] = o;
+        if constexpr (OUTF == kOutF32) { if (orow < out_rows) out[(size_t)orow * f.out_w + (px - f.out_x0)] = o; }
+        else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px - f.out_x0), o);
     }
 }
 
@@ -2635,7 +2651,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
 __device__ __forceinline__ uint32_t lds_peek(const uint32_t* p) { return *reinterpret_cast<const volatile uint32_t*>(p); }
 constexpr int kDwSleep = 1;            // s_sleep units (64 clocks) between two polls of a counter
 
-template <bool EARLY, bool DEPTH, bool COLF>
+template <bool EARLY, bool DEPTH, bool COLF, int OUTF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : DEPTH ? 7 : 8, 8))) void k_composite_dw(const Frame f,
                                                    const uint32_t* __restrict__ item_base, const uint4* __restrict__ item_tab,
                                                    const uint32_t* __restrict__ vals, const Rec* __restrict__ recs,
@@ -2802,12 +2818,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
         o.z = fmaf(T, bg.z, ab);
         o.w = fmaf(T, bg.w, 1.0f - T);
         const int orow = tyl * kTile + lyi2;
-        if (orow < out_rows) out[(size_t)orow * f.out_w + (px2 - f.out_x0)] = o;
+        if constexpr (OUTF == kOutF32) { if (orow < out_rows) out[(size_t)orow * f.out_w + (px2 - f.out_x0)] = o; }
+        else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px2 - f.out_x0), o);
     }
 }
 
 // Folds the per-segment partials of multi-segment tiles: (C1,T1) o (C2,T2) = (C1 + T1*C2, T1*T2).
 // One workgroup per tile, same lane -> pixel mapping as k_composite.
+template <int OUTF>
 __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* __restrict__ item_base,
                                                  const float4* __restrict__ partials, const float4* __restrict__ bg_rgba,
                                                  float4* __restrict__ out, int n_tiles, int out_rows,
@@ -2854,12 +2872,14 @@ __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* 
     o.z = fmaf(T, bg.z, ab);
     o.w = fmaf(T, bg.w, 1.0f - T);
     const int orow = tyl * kTile + lyi;
-    if (orow < out_rows) out[(size_t)orow * f.out_w + (px - f.out_x0)] = o;
+    if constexpr (OUTF == kOutF32) { if (orow < out_rows) out[(size_t)orow * f.out_w + (px - f.out_x0)] = o; }
+    else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px - f.out_x0), o);
 }
 
 // all-gathered shards -> frame.  rows: shard = tile row % count (rows_padded rows each, full width);
-// columns: shard = tile column / band_tiles (height rows each, band_px wide)
-__global__ void k_unshard(const float4* __restrict__ gathered, float4* __restrict__ out, int width, int height,
+// columns: shard = tile column / band_tiles (height rows each, band_px wide).  P: the pixel (float4, or uint32_t for the 8-bit formats)
+template <typename P>
+__global__ void k_unshard(const P* __restrict__ gathered, P* __restrict__ out, int width, int height,
                           int shard_count, int rows_padded, int band_px)
 {
     int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3039,9 +3059,10 @@ void launch_tile_depth_sort(hipStream_t s, const uint2* ranges, uint32_t* vals, 
 uint32_t tile_depth_sort_cap() { return kTileSortCap; }
 
 // ranges -> per-tile segment counts -> item_base (exclusive scan, item_base[n_tiles] = #items) ->
-// k_composite over an upper bound of items -> k_combine.
-void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
-                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end)
+// k_composite over an upper bound of items -> k_combine, storing the image in format OUTF.
+template <int OUTF>
+static void launch_composite_t(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
+                               uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
     const int n_tiles = (int)b.n_tiles;
     const uint32_t seg = b.seg;
@@ -3072,28 +3093,36 @@ void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const u
     // (the compositors carry ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED)
     if (variant == 1) {                  // GSWT_OPT_COMPOSITE = 1: decoupled waves (k_composite_dw), same image bit for bit
 #define GSWT_LAUNCH_COMPOSITE_DW(E, D, C)                                                                                      \
-        GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs, \
+        GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs, \
                            b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows)
         GSWT_COMPOSITE_EDC(GSWT_LAUNCH_COMPOSITE_DW);
 #undef GSWT_LAUNCH_COMPOSITE_DW
-        GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows, (const unsigned long long*)b.counters, b.host_counters);
+        GSWT_LAUNCH(k_combine<OUTF>, dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows, (const unsigned long long*)b.counters, b.host_counters);
         return;
     }
     if (fold) {
 #define GSWT_LAUNCH_COMPOSITE_F(E, D, C)                                                                                       \
-        GSWT_LAUNCH_TIMED((k_composite<E, D, C, true>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals, b.recs, \
+        GSWT_LAUNCH_TIMED((k_composite<E, D, C, true, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals, b.recs, \
                            b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.tile_tick, (const unsigned long long*)b.counters, b.host_counters)
         GSWT_COMPOSITE_EDC(GSWT_LAUNCH_COMPOSITE_F);
 #undef GSWT_LAUNCH_COMPOSITE_F
         return;
     }
 #define GSWT_LAUNCH_COMPOSITE(E, D, C)                                                                                         \
-    GSWT_LAUNCH_TIMED((k_composite<E, D, C>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals, b.recs, \
+    GSWT_LAUNCH_TIMED((k_composite<E, D, C, false, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals, b.recs, \
                        b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, (uint32_t*)nullptr, (const unsigned long long*)nullptr, (unsigned long long*)nullptr)
     GSWT_COMPOSITE_EDC(GSWT_LAUNCH_COMPOSITE);
 #undef GSWT_LAUNCH_COMPOSITE
 #undef GSWT_COMPOSITE_EDC
-    GSWT_LAUNCH(k_combine, dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows, (const unsigned long long*)b.counters, b.host_counters);
+    GSWT_LAUNCH(k_combine<OUTF>, dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows, (const unsigned long long*)b.counters, b.host_counters);
+}
+
+void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
+                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format)
+{
+    if (out_format == kOutRGBA8) launch_composite_t<kOutRGBA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    else if (out_format == kOutBGRA8) launch_composite_t<kOutBGRA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    else launch_composite_t<kOutF32>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
 }
 
 // k_totals alone on caller-provided sums (unit test of the 64-bit pair count)
@@ -3102,9 +3131,16 @@ void launch_totals(hipStream_t s, uint32_t* super_sums, uint32_t n_super, unsign
     hipLaunchKernelGGL(k_totals, dim3(1), dim3(256), 0, s, super_sums, n_super, counters, super_sums + 2u * kSuperStride * n_super, pair_cap, (uint32_t*)nullptr, 0xFFFFFFFFu);
 }
 
-void launch_unshard(hipStream_t s, const float4* gathered, float4* out, int width, int height, int shard_count, int rows_padded, int band_px)
+void launch_unshard(hipStream_t s, const void* gathered, void* out, int width, int height, int shard_count, int rows_padded, int band_px,
+                    int out_format)
 {
-    hipLaunchKernelGGL(k_unshard, dim3((width + 255) / 256, height), dim3(256), 0, s, gathered, out, width, height, shard_count, rows_padded, band_px);
+    const dim3 grid((width + 255) / 256, height);
+    if (out_format == kOutF32)
+        hipLaunchKernelGGL(k_unshard<float4>, grid, dim3(256), 0, s, static_cast<const float4*>(gathered), static_cast<float4*>(out), width, height,
+                           shard_count, rows_padded, band_px);
+    else
+        hipLaunchKernelGGL(k_unshard<uint32_t>, grid, dim3(256), 0, s, static_cast<const uint32_t*>(gathered), static_cast<uint32_t*>(out), width,
+                           height, shard_count, rows_padded, band_px);
 }
 
 }  // namespace gswt

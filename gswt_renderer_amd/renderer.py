@@ -29,6 +29,13 @@ def _shard_args(shard):
     return int(shard[0]), int(shard[1]), mode
 
 
+def _out_dtype(out_format: int):
+    """numpy dtype of one channel of an image in out_format (GSWT_OUT_*)."""
+    if out_format in (L.GSWT_OUT_RGBA8_UNORM, L.GSWT_OUT_BGRA8_UNORM):
+        return np.uint8
+    return np.float32          # (an unknown format is refused by the library, GSWT_ERR_BAD_ARG, before anything is written)
+
+
 def make_draw(tile: L.TileUniforms, *, base=None, merged_range=None, merged_has_lod=False, corners=None,
               lod=None) -> L.Draw:
     """One draw of the loop renderer.rs:466-591.  base = (lod, tile, view) of a static list or
@@ -159,15 +166,17 @@ class GSWTRenderer:
     def render(self, camera, scene, width: int, height: int, *, culling_dist: float = 1.0,
                lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
                transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba=None, bg_depth=None,
-               out_device_ptr: int | None = None, bg_on_device: bool = False):
+               out_device_ptr: int | None = None, bg_on_device: bool = False, out_format: int = L.GSWT_OUT_RGBA32F):
         """camera / scene: 176 / 160-byte uniform blocks (any ctypes struct or bytes of that layout).
-        Returns the image [rows, W, 4] f32 on the host, or None when out_device_ptr is given."""
+        Returns the image [rows, W, 4] on the host -- f32 for GSWT_OUT_RGBA32F, uint8 in the channel order of
+        GSWT_OUT_RGBA8_UNORM / GSWT_OUT_BGRA8_UNORM --, or None when out_device_ptr is given."""
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()
         cfg.culling_dist, cfg.lod_enable_mask, cfg.order_mode = culling_dist, lod_enable_mask & 0xFFFFFFFF, order_mode
         cfg.transmittance_eps = transmittance_eps
         cfg.shard_index, cfg.shard_count, cfg.shard_mode = _shard_args(shard)
+        cfg.out_format = out_format & 0xFFFFFFFF
         rows, out_w = height, width
         if cfg.shard_count > 1 and cfg.shard_mode == L.GSWT_SHARD_COLUMNS:
             out_w = self._lib.gswt_shard_cols_padded(width, cfg.shard_count)
@@ -184,21 +193,24 @@ class GSWTRenderer:
             self._check(self._lib.gswt_render(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
                                               1 if bg_on_device else 0, C.c_void_p(out_device_ptr), 1))
             return None
-        out = np.empty((rows, out_w, 4), dtype=np.float32)
+        out = np.empty((rows, out_w, 4), dtype=_out_dtype(out_format))
         self._check(self._lib.gswt_render(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
                                           1 if bg_on_device else 0, _ptr(out), 0))
         return out
 
     def render_async(self, camera, scene, width: int, height: int, out_device_ptr: int, *, culling_dist: float = 1.0,
                      lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
-                     transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba_ptr: int = 0, bg_depth_ptr: int = 0) -> int:
-        """Queues a frame (device pointers only) and returns a ticket for render_wait."""
+                     transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba_ptr: int = 0, bg_depth_ptr: int = 0,
+                     out_format: int = L.GSWT_OUT_RGBA32F) -> int:
+        """Queues a frame (device pointers only) and returns a ticket for render_wait.  out_device_ptr holds rows x out_w x 4
+        f32, or bytes for the 8-bit out_format values."""
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()
         cfg.culling_dist, cfg.lod_enable_mask, cfg.order_mode = culling_dist, lod_enable_mask & 0xFFFFFFFF, order_mode
         cfg.transmittance_eps = transmittance_eps
         cfg.shard_index, cfg.shard_count, cfg.shard_mode = _shard_args(shard)
+        cfg.out_format = out_format & 0xFFFFFFFF
         ticket = C.c_int(-1)
         self._check(self._lib.gswt_render_async(self._h, cam, sc, C.byref(cfg), width, height,
                                                 C.c_void_p(bg_rgba_ptr) if bg_rgba_ptr else None,
@@ -267,6 +279,13 @@ class GSWTRenderer:
         m = L.GSWT_SHARD_COLUMNS if mode in ("cols", "columns", L.GSWT_SHARD_COLUMNS) and mode != 0 else L.GSWT_SHARD_ROWS
         self._check(self._lib.gswt_unshard_mode(self._h, C.c_void_p(gathered_device_ptr), width, height, shard_count, m,
                                                 C.c_void_p(out_device_ptr)))
+
+    def unshard_format(self, gathered_device_ptr: int, width: int, height: int, shard_count: int, mode, out_format: int,
+                       out_device_ptr: int):
+        """unshard_mode for any output format (GSWT_OUT_*: 16- or 4-byte pixels)."""
+        m = L.GSWT_SHARD_COLUMNS if mode in ("cols", "columns", L.GSWT_SHARD_COLUMNS) and mode != 0 else L.GSWT_SHARD_ROWS
+        self._check(self._lib.gswt_unshard_format(self._h, C.c_void_p(gathered_device_ptr), width, height, shard_count, m, out_format,
+                                                  C.c_void_p(out_device_ptr)))
 
     def unshard(self, gathered_device_ptr: int, width: int, height: int, shard_count: int, out_device_ptr: int):
         self._check(self._lib.gswt_unshard(self._h, C.c_void_p(gathered_device_ptr), width, height, shard_count,

@@ -136,10 +136,22 @@ typedef struct {
     int32_t shard_index;
     int32_t shard_count;
     int32_t shard_mode;       /* GSWT_SHARD_* */
-    uint32_t _pad;
+    uint32_t out_format;      /* GSWT_OUT_*; 0 (a zero-initialised config) is the RGBA f32 image */
 } gswt_render_config;
 
 enum { GSWT_SHARD_ROWS = 0, GSWT_SHARD_COLUMNS = 1 };
+
+/* Output image formats (gswt_render_config.out_format).  GSWT_OUT_RGBA32F: 16 bytes per pixel, premultiplied colour and alpha as
+ * four floats.  The 8-bit formats are the layouts of the reference's non-sRGB swapchain surface (state.rs:96-101: Rgba8Unorm /
+ * Bgra8Unorm), 4 bytes per pixel, written by the compositor's own store.  Each byte is q(x) of the float x the same frame writes in
+ * GSWT_OUT_RGBA32F:
+ *     q(x) = (uint8) round_half_even(fminf(fmaxf(x, 0.0f), 1.0f) * 255.0f)      (one binary32 product, not fused; NaN -> 0)
+ * so an 8-bit frame equals q of its f32 frame bit for bit, in every mode and compositor variant.  No gamma step (the surface is not
+ * sRGB).  This is NOT the reference's own 8-bit result: its blend state rounds the 8-bit target after every blended splat.
+ * For the 8-bit formats every `float *` output pointer of gswt_render / gswt_render_async / the gathers addresses
+ * rows_out x out_w x 4 BYTES (pass the byte buffer cast to float *); shard geometry (gswt_shard_rows_padded,
+ * gswt_shard_cols_padded) counts pixels and does not change. */
+enum { GSWT_OUT_RGBA32F = 0, GSWT_OUT_RGBA8_UNORM = 1 /* bytes R, G, B, A */, GSWT_OUT_BGRA8_UNORM = 2 /* bytes B, G, R, A */ };
 
 /* Per-stage device times of the last gswt_render (hipEvent, ms) and workload sizes.  ms_ranges is ~0 since the per-tile
  * [start, end) table is left by the last pass of the pair sort (its time is inside ms_sort); ms_scan is unused (no scan launch). */
@@ -262,8 +274,10 @@ GSWT_API int gswt_debug_read_merged(gswt_ctx *ctx, uint32_t *packed_list, uint32
  * colour attachment content the pass loads (LoadOp::Load, :425; skybox/proxy output) or
  * NULL for transparent black; bg_depth (W*H f32) is the proxy depth buffer (:433-434) or
  * NULL for the 1.0 clear (:436).  out_rgba receives rows_out*W*4 f32 where rows_out = H,
- * or the shard's rows when cfg->shard_count > 1 (see gswt_shard_rows).  Pointers are
- * device pointers when *_on_device is nonzero, host pointers otherwise. */
+ * or the shard's rows when cfg->shard_count > 1 (see gswt_shard_rows); for the 8-bit
+ * cfg->out_format values rows_out*W*4 bytes.  Pointers are device pointers when
+ * *_on_device is nonzero, host pointers otherwise.  An out_format other than GSWT_OUT_*
+ * returns GSWT_ERR_BAD_ARG before anything is enqueued. */
 GSWT_API int gswt_render(gswt_ctx *ctx, const gswt_camera_uniforms *camera,
                          const gswt_scene_uniforms *scene, const gswt_render_config *cfg,
                          int width, int height,
@@ -361,12 +375,16 @@ GSWT_API int gswt_unshard(gswt_ctx *ctx, const float *gathered, int width, int h
 /* The same for either shard mode (GSWT_SHARD_COLUMNS: the gathered shards are H x gswt_shard_cols_padded images). */
 GSWT_API int gswt_unshard_mode(gswt_ctx *ctx, const float *gathered, int width, int height,
                                int shard_count, int shard_mode, float *out_rgba);
+/* The same for any output format (GSWT_OUT_*: 16 or 4 bytes per pixel); gswt_unshard_mode is out_format = GSWT_OUT_RGBA32F of it. */
+GSWT_API int gswt_unshard_format(gswt_ctx *ctx, const void *gathered, int width, int height,
+                                 int shard_count, int shard_mode, int out_format, void *out);
 
 /* ---- multi-GPU: the framebuffer all-gather behind the ABI (new; the reference is single-GPU) ---------------------
  * One ctx per GPU.  Every rank renders its shard (cfg->shard_index = rank, shard_count = world) with gswt_render_async,
  * then gswt_render_gather(ticket, frame) = overflow-safe fence + all-gather of the equal-sized shard images + the index
  * permutation of gswt_unshard_mode, all on the ctx stream: `frame` (W*H*4 f32, device) then holds the whole image on
- * every rank.  Two transports:
+ * every rank.  A gather moves the image in the format its frame was rendered in (cfg->out_format: W*H*4 bytes for the 8-bit
+ * formats); in a group gather every rank's frame must have the same format (GSWT_ERR_BAD_ARG otherwise).  Two transports:
  *   RCCL (one process per GPU, xGMI): rank 0 calls gswt_comm_unique_id, ships the 128 bytes to the other ranks by any
  *     means (MPI, a file, torch.distributed ...), every rank calls gswt_comm_init(ctx, id, rank, world) ->
  *     ncclCommInitRank; the gather is one ncclAllGather.  librccl is loaded on first use (dlopen), so a single-GPU host
