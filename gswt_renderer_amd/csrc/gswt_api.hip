@@ -302,8 +302,7 @@ struct gswt_ctx {
     // GSWT_OPT_STRICT_VS (default ON since round 4: k_project<.,.,STRICT> costs +1 us of 71 at c3 and nothing in frames/s): vs_main is
     // evaluated operator by operator as gswt.wgsl:152-258 writes it; 0 selects the fma-chain / single-reciprocal sequence v2
     int opt_strict_vs = 1;
-    // GSWT_OPT_COMPOSITE: 0 = k_composite + k_combine, 1 = k_composite_dw (decoupled waves) + k_combine, 2 = k_composite<FOLD>: the last
-    // segment of a tile to finish folds the partials, empty tiles are work items, no k_combine launch
+    // GSWT_OPT_COMPOSITE: 0 = k_composite + k_combine, 1 = k_composite_dw (decoupled waves) + k_combine, 2 = the same as 0
     int opt_composite = 0;
     int opt_no_chunk_cull = 0;             // GSWT_OPT_NO_CHUNK_CULL: k_cull keeps every chunk of a surviving draw (A/B and tests: same image)
     unsigned long long stat_graph_launches = 0, stat_graph_rebuilds = 0, stat_graph_node_updates = 0;
@@ -1421,13 +1420,12 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     if (a.su.draw_mode != 0u) HIP_TRY(c, sl.col_f.ensure(n_slots_all + 1));
     if (need_depths) HIP_TRY(c, sl.depths.ensure(n_slots_all + 1));
     if (c->opt_debug_varyings) HIP_TRY(c, c->dbg.ensure((size_t)D.n_entries + 1));
-    // the `ranges` region (uint2 units): every tile's (~start, end) and one more, then one ticket word per tile for GSWT_OPT_COMPOSITE = 2,
-    // then the tile-local depth sort's two lists of long tiles; the word parts are padded to whole uint2s plus one.  k_cull clears the
-    // ranges, the tickets, the first list and the second list's count.
-    const size_t range_words = 2 * (nt + 1), tick_words = nt, list_words = tile_depth_list_words(nt);
+    // the `ranges` region (uint2 units): every tile's (~start, end) and one more, then the tile-local depth sort's two lists of long tiles;
+    // the list parts are padded to whole uint2s plus one.  k_cull clears the ranges, the first list and the second list's count.
+    const size_t range_words = 2 * (nt + 1), list_words = tile_depth_list_words(nt);
     auto uint2s = [](size_t words) { return (words + 1) / 2 + 1; };
-    HIP_TRY(c, sl.ranges.ensure(range_words / 2 + uint2s(tick_words) + 2 * uint2s(list_words)));
-    b.n_zero_ranges = (uint32_t)(range_words + tick_words + list_words + 1);
+    HIP_TRY(c, sl.ranges.ensure(range_words / 2 + 2 * uint2s(list_words)));
+    b.n_zero_ranges = (uint32_t)(range_words + list_words + 1);
     // the `ghist` region (u32): [counters][super-group sums][pair sort workspace][depth sort workspace]; each workspace has its zeroed part
     // (group rows, digit totals) in front of its per-workgroup rows (written in full).  k_cull clears the head up to the end of the pair
     // sort's zeroed part, and the depth sort's zeroed part.
@@ -1459,8 +1457,7 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     b.radix_depth = b.radix_pair + rw_pair;
     b.keys_a = sl.keys_a.p; b.keys_b = sl.keys_b.p; b.vals_a = sl.vals_a.p; b.vals_b = sl.vals_b.p; b.aux_a = sl.aux_a.p; b.aux_b = sl.aux_b.p;
     b.ranges = sl.ranges.p;
-    b.tile_tick = reinterpret_cast<uint32_t*>(sl.ranges.p) + range_words;
-    b.long_tiles = b.tile_tick + tick_words;
+    b.long_tiles = reinterpret_cast<uint32_t*>(sl.ranges.p) + range_words;
     b.item_base = sl.item_base.p; b.item_tab = sl.item_tab.p; b.partials = sl.partials.p;
     return GSWT_OK;
 }

@@ -257,8 +257,8 @@ struct FrameBufs {
     uint32_t *krange, *super_sums, *radix_pair, *radix_depth;
     // per pair: tile keys, slots, and the depth order's tile ids / depth bits
     uint32_t *keys_a, *keys_b, *vals_a, *vals_b, *aux_a, *aux_b;
-    // the `ranges` region: per tile (~start, end), GSWT_OPT_COMPOSITE = 2's tickets, the tile-local depth sort's lists of long tiles
-    uint2* ranges; uint32_t *tile_tick, *long_tiles;
+    // the `ranges` region: per tile (~start, end), the tile-local depth sort's lists of long tiles
+    uint2* ranges; uint32_t* long_tiles;
     uint32_t* item_base; uint4* item_tab; float4* partials;
     // the words k_cull clears: the head of `ghist` to the end of the pair sort's zeroed part, the `ranges` region, the depth sort's zeroed part
     uint32_t n_zero_head, n_zero_ranges, n_zero_depth;

@@ -10,7 +10,7 @@
 //   k_items       : work items (tile, segment of its list: GSWT_OPT_SEGMENT pairs) from the per-tile [start, end) the last pass leaves
 //   k_composite   : front-to-back alpha compositing (fs_main gswt.wgsl:425-435 + blend/depth state
 //                   renderer.rs:118-129,179-185): LDS-staged batches, per-sub-block lists, wave ballot early termination;
-//                   k_composite_dw: the same with the four waves of an item decoupled; <FOLD>: folds the segment partials itself
+//                   k_composite_dw: the same with the four waves of an item decoupled
 //   k_combine     : folds the segment partials of long tile lists; k_unshard : all-gathered shards -> frame
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off.  Contraction is OFF for the
@@ -2043,10 +2043,8 @@ template <bool HEAVY>
 __global__ __launch_bounds__(1024) void k_items(const uint2* __restrict__ ranges, int n_tiles, uint32_t seg,
                                                 uint32_t* __restrict__ item_base, uint4* __restrict__ item_tab, uint32_t max_items,
                                                 const uint32_t* __restrict__ krange, uint32_t n_launched, unsigned long long* __restrict__ counters,
-                                                uint32_t all_tiles, uint32_t report_max)
+                                                uint32_t report_max)
 {
-    // all_tiles (GSWT_OPT_FOLD_COMBINE): a tile without pairs gets one EMPTY work item -- k_composite then writes its background, and no
-    // k_combine launch follows the compositor
     if (krange && blockIdx.x == 0u && threadIdx.x == 0u) {
         const uint32_t need = sort_passes_needed(krange);
         *reinterpret_cast<uint32_t*>(counters + 2) = need;                   // (the low half: the high one takes the longest tile list)
@@ -2081,8 +2079,7 @@ __global__ __launch_bounds__(1024) void k_items(const uint2* __restrict__ ranges
 #pragma unroll
             for (int j = 0; j < kPer; j++) {
                 const uint32_t len = e[j].y - e[j].x;
-                const uint32_t qq = seg_pow2 ? (len + seg - 1u) >> seg_sh : (len + seg - 1u) / seg;
-                part += all_tiles ? max(qq, 1u) : qq;
+                part += seg_pow2 ? (len + seg - 1u) >> seg_sh : (len + seg - 1u) / seg;
             }
         }
         const uint32_t pi = wave_incl_scan(part, lane);
@@ -2103,8 +2100,7 @@ __global__ __launch_bounds__(1024) void k_items(const uint2* __restrict__ ranges
 #pragma unroll
     for (int j = 0; j < kPer; j++) {
         const uint32_t len = r[j].y - r[j].x;
-        uint32_t q = seg_pow2 ? (len + seg - 1u) >> seg_sh : (len + seg - 1u) / seg;   // (a 32-bit divide is ~40 VALU)
-        if (all_tiles) q = max(q, 1u);
+        const uint32_t q = seg_pow2 ? (len + seg - 1u) >> seg_sh : (len + seg - 1u) / seg;   // (a 32-bit divide is ~40 VALU)
         cnt[j] = base + j * 1024 + (int)threadIdx.x < n_tiles ? q : 0u;
     }
 #pragma unroll
@@ -2370,8 +2366,8 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
 // the gather latency was already covered by the other workgroups of the CU.  "stage-only 58 us" in the ablation is
 // what staging costs with nothing to hide behind, not a serial share of the full kernel.
 
-// The store of a final pixel (k_composite, k_composite_dw, k_combine) in an 8-bit output format (gswt_hip.h, GSWT_OUT_*; kOutF32 stores the
-// float4 as it is, in the kernels' own statement).  Per channel q(x) = round_half_even(min(max(x, 0), 1) * 255) -- fmaxf drops a NaN (-> 0),
+// The store of a final pixel (comp_final_pixel) in an 8-bit output format (gswt_hip.h, GSWT_OUT_*; kOutF32 stores the float4 as it is).
+// Per channel q(x) = round_half_even(min(max(x, 0), 1) * 255) -- fmaxf drops a NaN (-> 0),
 // the product is one binary32 multiplication (-ffp-contract=off), v_rndne_f32 rounds half to even, the integral result converts exactly --,
 // packed into ONE 32-bit store per lane: the 16 lanes of a pixel row of the tile (the lane -> pixel map) write 64 contiguous bytes.  (The
 // compiler folds the clamp into the blend's final v_fma_f32 as its clamp modifier, which also takes NaN to 0.)
@@ -2384,26 +2380,97 @@ __device__ __forceinline__ void store_unorm8(float4* out, size_t i, const float4
     reinterpret_cast<uint32_t*>(out)[i] = OUTF == kOutBGRA8 ? (b | g << 8 | r << 16 | a << 24) : (r | g << 8 | b << 16 | a << 24);
 }
 
-// FOLD (GSWT_OPT_FOLD_COMBINE, round 4): no k_combine behind the compositor.  (a) k_items hands out an empty work item for every tile
-// without pairs: its background is written here.  (b) The segments of a long tile list are folded by whichever of their workgroups finishes
-// LAST: every segment stores its partial (C, T) with agent-scope (sc1) stores -- the L2 of an XCD is not coherent with the other seven
-// inside a kernel, and the segments of one tile run on different XCDs --, waits for them, and takes a ticket on the tile's counter; the
-// workgroup that draws the last ticket reads all partials back (sc1 loads) and folds them front to back in segment order, exactly as
-// k_combine does: the image is bit-identical whichever workgroup that is.  (c) Workgroup 0 publishes the frame's counters to the host.
-// One ticket per multi-segment work item on ITS tile's word: ~700 atomics per c3 frame on ~250 addresses (a single frame-wide ticket
-// word would serialise at ~8 ns per atomic on the memory side).
+// ---- the pieces k_composite, k_composite_dw and k_combine share: one statement each, so that the three stay bit-identical ----
+// Where a work item's screen tile lies: tile row tyl inside this shard's image (the rows it stores) and pixel origin (bx, by) in the frame
+// (a row-sharded ctx owns tile rows shard_index, + shard_count, ...)
+struct CompTile { int tyl, bx, by; };
+__device__ __forceinline__ CompTile comp_tile(const Frame& f, uint32_t tile)
+{
+    int tx, tyl;
+    tile_xy(f, tile, tx, tyl);
+    const int sc = f.shard_count <= 1 ? 1 : f.shard_count;
+    const int ty = tyl * sc + (sc > 1 ? f.shard_index : 0);
+    return {tyl, (tx + f.col0) * kTile, ty * kTile};
+}
+
+// Stages one pair for the bin + walk: its LDS record at index `at` (s_q0, s_q1; s_dep with a depth buffer, s_q2 with float colours) and
+// its sub-block mask at s_bb[bi], from the first two quads of its Rec (ra, rb), its depth rbw and its float colour rd.  (hW, hHn, c0x, c0y):
+// the tile's half of F3 (k_composite).
+template <bool DEPTH, bool COLF>
+__device__ __forceinline__ void comp_stage(float hW, float hHn, float c0x, float c0y, const float4& ra, const float4& rb, float rbw, const float4& rd,
+                                           float4* s_q0, float4* s_q1, float4* s_q2, float* s_dep, uint32_t* s_bb, uint32_t at, uint32_t bi)
+{
+    // F3: per-(splat, tile) constants
+    const float ox = fmaf(hW, rb.x, c0x), oy = fmaf(hHn, rb.y, c0y);
+    const float nku = -fmaf(ra.x, ox, ra.y * oy);
+    const float nkv = -fmaf(ra.z, ox, ra.w * oy);
+    const float l2a = __builtin_amdgcn_logf(rb.z);                           // v_log_f32 = log2; log2(0) = -inf -> B = 0
+    s_q0[at] = make_float4(ra.x, ra.y, nku, l2a);
+    s_q1[at] = make_float4(ra.z, ra.w, nkv, rb.w);
+    // Pixel half extents of |p| <= 2 from the inverse map: the quad axes are u = iu / |iu|^2, w = iv / |iv|^2 and the
+    // box is 2 sqrt(u.x^2 + w.x^2) by 2 sqrt(u.y^2 + w.y^2).  Approximate reciprocals / roots (1 ulp) under a 1e-4
+    // relative + 2e-3 px margin: the box only has to CONTAIN every pixel centre with r^2 <= 4 (it decides which
+    // sub-block lists a pair enters, never a pixel's coverage), and k_project's own box decided the pair's tiles.
+    const float ria = __builtin_amdgcn_rcpf(fmaf(ra.y, ra.y, ra.x * ra.x)), rib = __builtin_amdgcn_rcpf(fmaf(ra.w, ra.w, ra.z * ra.z));
+    const float qux = ra.x * ria, quy = ra.y * ria, qwx = ra.z * rib, qwy = ra.w * rib;
+    const float bhx = fmaf(2.0f * __builtin_amdgcn_sqrtf(fmaf(qwx, qwx, qux * qux)), 1.0001f, 0.002f);
+    const float bhy = fmaf(2.0f * __builtin_amdgcn_sqrtf(fmaf(qwy, qwy, quy * quy)), 1.0001f, 0.002f);
+    // Pixel box, tile-local, as the integer pixel ranges whose centres it holds: x_lo <= k + 0.5  <=>  ceil(x_lo - 0.5) <= k and
+    // x_hi >= k + 0.5  <=>  floor(x_hi - 0.5) >= k for every integer k (x - 0.5 is exact in binary32 wherever the
+    // outcome can depend on it), so the byte form bins exactly like the float box did; 16 -> 4 bytes of LDS per pair.
+    // Clamped to [-2, 17]: only 0..15 are ever compared.
+    const int xa = min(max((int)ceilf((ox - bhx) - 0.5f), -2), 17), xb = min(max((int)floorf((ox + bhx) - 0.5f), -2), 17);
+    const int ya = min(max((int)ceilf((oy - bhy) - 0.5f), -2), 17), yb = min(max((int)floorf((oy + bhy) - 0.5f), -2), 17);
+    // The 16 sub-blocks the box touches, as a bit mask (bit 4 s + g: strip s, column group g), computed ONCE here instead of four
+    // column and one row test per wave and pair in the bin loop: columns g with 4 g + 3 >= xa and 4 g <= xb are g_lo .. g_hi,
+    // g_lo = max(xa >> 2, 0), g_hi = min(xb >> 2, 3) (arithmetic shifts: xa, xb in [-2, 17]); rows likewise; the outer product of the
+    // two 4-bit masks is one multiplication (the row bits spread to positions 0, 4, 8, 12: no carries).
+    const int gx0 = max(xa >> 2, 0), gx1 = min(xb >> 2, 3), gy0 = max(ya >> 2, 0), gy1 = min(yb >> 2, 3);
+    const uint32_t cx = gx1 >= gx0 ? (2u << gx1) - (1u << gx0) : 0u;
+    const uint32_t ry = gy1 >= gy0 ? (2u << gy1) - (1u << gy0) : 0u;
+    const uint32_t spread = (ry & 1u) | ((ry & 2u) << 3) | ((ry & 4u) << 6) | ((ry & 8u) << 9);
+    s_bb[bi] = cx * spread;
+    if (DEPTH) s_dep[at] = rbw;
+    if (COLF) s_q2[at] = rd;
+}
+
+// The null record at LDS index `at` (list padding): p.x = +inf for every pixel (0 * l + inf), so r^2 = +inf and no pixel is ever inside
+template <bool DEPTH, bool COLF>
+__device__ __forceinline__ void comp_null_record(float4* s_q0, float4* s_q1, float4* s_q2, float* s_dep, uint32_t at)
+{
+    s_q0[at] = make_float4(0.f, 0.f, __builtin_inff(), 0.f);
+    s_q1[at] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (DEPTH) s_dep[at] = 0.0f;
+    if (COLF) s_q2[at] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// A final pixel (px, py inside the frame): the background under the transmittance left, stored in format OUTF at row orow of this shard's
+// image (rows from out_rows on pad the last tile row: not stored)
+template <int OUTF>
+__device__ __forceinline__ void comp_final_pixel(const Frame& f, const float4* bg_rgba, float4* out, int out_rows, int px, int py, int orow,
+                                                 float T, float ar, float ag, float ab)
+{
+    float4 bg = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (bg_rgba) bg = bg_rgba[(size_t)py * f.width + px];
+    float4 o;
+    o.x = fmaf(T, bg.x, ar);
+    o.y = fmaf(T, bg.y, ag);
+    o.z = fmaf(T, bg.z, ab);
+    o.w = fmaf(T, bg.w, 1.0f - T);
+    if constexpr (OUTF == kOutF32) { if (orow < out_rows) out[(size_t)orow * f.out_w + (px - f.out_x0)] = o; }
+    else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px - f.out_x0), o);
+}
+
 // OUTF: the output format (kOut*); only the final store differs.
-template <bool EARLY, bool DEPTH, bool COLF, bool FOLD, int OUTF>
+template <bool EARLY, bool DEPTH, bool COLF, int OUTF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || COLF) ? 7 : 8, 8))) void k_composite(const Frame f, const uint2* __restrict__ ranges,
                                                    const uint32_t* __restrict__ item_base, const uint4* __restrict__ item_tab,
                                                    uint32_t seg, const uint32_t* __restrict__ vals, const Rec* __restrict__ recs,
                                                    const float* __restrict__ depths, const float4* __restrict__ col_f,
                                                    const float4* __restrict__ bg_rgba, const float* __restrict__ bg_depth,
                                                    float4* __restrict__ out, float4* __restrict__ partials,
-                                                   int n_tiles, int out_rows, uint32_t* __restrict__ tile_tick,
-                                                   const unsigned long long* __restrict__ counters, unsigned long long* __restrict__ host_counters)
+                                                   int n_tiles, int out_rows)
 {
-    __shared__ uint32_t s_last;
     __shared__ float4 s_q0[257], s_q1[257];                     // [256] = the null record (list padding)
     __shared__ uint32_t s_bb[256];                              // the 16 sub-blocks a staged pair's pixel box touches (bit 4 strip + column group)
     __shared__ float4 s_q2[COLF ? 257 : 1];
@@ -2422,8 +2489,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
 #endif
     const uint32_t n_items = item_base[n_tiles];
     const uint4 it = item_tab[item];                 // (in flight together with n_items; garbage past n_items, unused)
-    // FOLD: this is the frame's last kernel -- the four result counters go straight into the slot's pinned host words
-    if (FOLD && item == 0u && threadIdx.x < 5u && host_counters) host_counters[threadIdx.x] = counters[threadIdx.x];
     if (item >= n_items) return;
     GSWT_TR(1, GSWT_NOW())
     GSWT_TR(4, it.w - it.z)
@@ -2432,11 +2497,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
 #endif
     const int tile = (int)it.x;
     const bool multi_seg = (it.y & 1u) != 0u;
-    int tx, tyl;
-    tile_xy(f, (uint32_t)tile, tx, tyl);
-    const int sc = f.shard_count <= 1 ? 1 : f.shard_count;
-    const int ty = tyl * sc + (sc > 1 ? f.shard_index : 0);
-    const int bx = (tx + f.col0) * kTile, by = ty * kTile;
+    const auto [tyl, bx, by] = comp_tile(f, (uint32_t)tile);
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));      // uniform per wave: everything derived from it stays scalar
     const uint32_t grp = lane >> 4, gi = lane & 15u;                 // wave = 16 x 4 strip, 16-lane group = 4 x 4 sub-block
@@ -2462,13 +2523,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     if (DEPTH && inside) dbuf = bg_depth[(size_t)py * f.width + px];
     const float t_eps = f.t_eps;
     bool wave_live = true;
-    // the null record: p.x = +inf for every pixel (0 * l + inf), so r^2 = +inf and no pixel is ever inside
     if (tid == 0) {
         if (EARLY) s_dead = make_uint4(0u, 0u, 0u, 0u);
-        s_q0[kNullRec] = make_float4(0.f, 0.f, __builtin_inff(), 0.f);
-        s_q1[kNullRec] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (DEPTH) s_dep[DEPTH ? kNullRec : 0u] = 0.0f;
-        if (COLF) s_q2[COLF ? kNullRec : 0u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        comp_null_record<DEPTH, COLF>(s_q0, s_q1, s_q2, s_dep, kNullRec);
     }
     // Software-pipelined gather: the records of batch b+1 and the slot indices of batch b+2 are in flight
     // while batch b is binned and walked (two dependent HBM latencies per batch otherwise sit between barriers).
@@ -2495,42 +2552,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     }
     for (uint32_t base = rg.x; base < rg.y; base += 256u) {
         const uint32_t n = min(256u, rg.y - base);
-        if (tid < n) {
-            // F3: per-(splat, tile) constants
-            const float ox = fmaf(hW, rb.x, c0x), oy = fmaf(hHn, rb.y, c0y);
-            const float nku = -fmaf(ra.x, ox, ra.y * oy);
-            const float nkv = -fmaf(ra.z, ox, ra.w * oy);
-            const float l2a = __builtin_amdgcn_logf(rb.z);                           // v_log_f32 = log2; log2(0) = -inf -> B = 0
-            s_q0[tid] = make_float4(ra.x, ra.y, nku, l2a);
-            s_q1[tid] = make_float4(ra.z, ra.w, nkv, rb.w);
-            // Pixel half extents of |p| <= 2 from the inverse map: the quad axes are u = iu / |iu|^2, w = iv / |iv|^2 and the
-            // box is 2 sqrt(u.x^2 + w.x^2) by 2 sqrt(u.y^2 + w.y^2).  Approximate reciprocals / roots (1 ulp) under a 1e-4
-            // relative + 2e-3 px margin: the box only has to CONTAIN every pixel centre with r^2 <= 4 (it decides which
-            // sub-block lists a pair enters, never a pixel's coverage), and k_project's own box decided the pair's tiles.
-            const float ria = __builtin_amdgcn_rcpf(fmaf(ra.y, ra.y, ra.x * ra.x)), rib = __builtin_amdgcn_rcpf(fmaf(ra.w, ra.w, ra.z * ra.z));
-            const float qux = ra.x * ria, quy = ra.y * ria, qwx = ra.z * rib, qwy = ra.w * rib;
-            const float bhx = fmaf(2.0f * __builtin_amdgcn_sqrtf(fmaf(qwx, qwx, qux * qux)), 1.0001f, 0.002f);
-            const float bhy = fmaf(2.0f * __builtin_amdgcn_sqrtf(fmaf(qwy, qwy, quy * quy)), 1.0001f, 0.002f);
-            // Pixel box, tile-local, as the integer pixel ranges whose centres it holds: x_lo <= k + 0.5  <=>  ceil(x_lo - 0.5) <= k and
-            // x_hi >= k + 0.5  <=>  floor(x_hi - 0.5) >= k for every integer k (x - 0.5 is exact in binary32 wherever the
-            // outcome can depend on it), so the byte form bins exactly like the float box did; 16 -> 4 bytes of LDS per pair.
-            // Clamped to [-2, 17]: only 0..15 are ever compared.
-            const int xa = min(max((int)ceilf((ox - bhx) - 0.5f), -2), 17), xb = min(max((int)floorf((ox + bhx) - 0.5f), -2), 17);
-            const int ya = min(max((int)ceilf((oy - bhy) - 0.5f), -2), 17), yb = min(max((int)floorf((oy + bhy) - 0.5f), -2), 17);
-            // The 16 sub-blocks the box touches, as a bit mask (bit 4 s + g: strip s, column group g), computed ONCE here instead of four
-            // column and one row test per wave and pair in the bin loop: columns g with 4 g + 3 >= xa and 4 g <= xb are g_lo .. g_hi,
-            // g_lo = max(xa >> 2, 0), g_hi = min(xb >> 2, 3) (arithmetic shifts: xa, xb in [-2, 17]); rows likewise; the outer product of the
-            // two 4-bit masks is one multiplication (the row bits spread to positions 0, 4, 8, 12: no carries).
-            {
-                const int gx0 = max(xa >> 2, 0), gx1 = min(xb >> 2, 3), gy0 = max(ya >> 2, 0), gy1 = min(yb >> 2, 3);
-                const uint32_t cx = gx1 >= gx0 ? (2u << gx1) - (1u << gx0) : 0u;
-                const uint32_t ry = gy1 >= gy0 ? (2u << gy1) - (1u << gy0) : 0u;
-                const uint32_t spread = (ry & 1u) | ((ry & 2u) << 3) | ((ry & 4u) << 6) | ((ry & 8u) << 9);
-                s_bb[tid] = cx * spread;
-            }
-            if (DEPTH) s_dep[tid] = rbw;
-            if (COLF) s_q2[tid] = rd;
-        }
+        if (tid < n) comp_stage<DEPTH, COLF>(hW, hHn, c0x, c0y, ra, rb, rbw, rd, s_q0, s_q1, s_q2, s_dep, s_bb, tid, tid);
         __syncthreads();
 #ifdef GSWT_TRACE
         if (tr_first) { GSWT_TR(2, GSWT_NOW()) tr_first = false; }
@@ -2562,47 +2584,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     GSWT_TR(6, tr_walk)
     const float k255 = 1.0f / 255.0f;      // colour is continuous: sum(w * byte) / 255 vs sum(w * (byte / 255)) differ in the last bits only
     if (!COLF) { ar *= k255; ag *= k255; ab *= k255; }
-    // (the partial's slot: the tile's first + the segment's number -- the table position only while the table is in tile order)
-    const uint32_t pslot = multi_seg ? item_base[tile] + (it.y >> 1) : 0u;
-    if (multi_seg && !FOLD) {
-        // partial (C, T) of this segment; k_combine folds the segments front to back
-        partials[(size_t)pslot * 256u + tid] = make_float4(ar, ag, ab, T);
+    if (multi_seg) {
+        // partial (C, T) of this segment, in the slot the tile's first + the segment's number (the table position only while the table is
+        // in tile order); k_combine folds the segments front to back
+        partials[(size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid] = make_float4(ar, ag, ab, T);
         return;
-    }
-    if (multi_seg && FOLD) {
-        float* const pp = reinterpret_cast<float*>(partials + (size_t)pslot * 256u + tid);
-        __hip_atomic_store(pp + 0, ar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(pp + 1, ag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(pp + 2, ab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(pp + 3, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_s_waitcnt(0);                   // this thread's partial has been written through
-        __syncthreads();                                 // ... and so have the other 255
-        const uint32_t i0 = item_base[tile], n_seg = item_base[tile + 1] - i0;
-        if (tid == 0) s_last = __hip_atomic_fetch_add(&tile_tick[tile], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n_seg - 1u ? 1u : 0u;
-        __syncthreads();
-        if (s_last == 0u) return;
-        // the last segment to finish folds them all, front to back: (C1, T1) o (C2, T2) = (C1 + T1 C2, T1 T2) -- k_combine's loop
-        T = 1.0f; ar = 0.0f; ag = 0.0f; ab = 0.0f;
-        for (uint32_t s0 = 0; s0 < n_seg; s0 += 4u) {
-            float4 p[4];
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; k++) {
-                const float* q = reinterpret_cast<const float*>(partials + (size_t)(i0 + min(s0 + k, n_seg - 1u)) * 256u + tid);
-                p[k].x = __hip_atomic_load(q + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                p[k].y = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                p[k].z = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                p[k].w = __hip_atomic_load(q + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; k++) {
-                if (s0 + k < n_seg) {                     // workgroup-uniform
-                    ar = fmaf(T, p[k].x, ar);
-                    ag = fmaf(T, p[k].y, ag);
-                    ab = fmaf(T, p[k].z, ab);
-                    T = T * p[k].w;
-                }
-            }
-        }
     }
     // pixel coordinates again, from a copy of the thread id the compiler cannot connect to the one above: otherwise px, py
     // and the output row stay in VGPRs across the whole walk (the kernel sits exactly at the 64-VGPR / 8-wave limit)
@@ -2610,19 +2596,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     asm volatile("" : "+v"(tid2));
     const int lxi2 = (int)(((tid2 & 63u) >> 4) * 4u + (tid2 & 3u)), lyi2 = (int)((tid2 >> 6) * 4u + ((tid2 & 15u) >> 2));
     const int px2 = bx + lxi2, py2 = by + lyi2;
-    if (px2 < f.width && py2 < f.height) {
-        const int px = px2, py = py2, lyi = lyi2;
-        float4 bg = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (bg_rgba) bg = bg_rgba[(size_t)py * f.width + px];
-        float4 o;
-        o.x = fmaf(T, bg.x, ar);
-        o.y = fmaf(T, bg.y, ag);
-        o.z = fmaf(T, bg.z, ab);
-        o.w = fmaf(T, bg.w, 1.0f - T);
-        const int orow = tyl * kTile + lyi;      // compacted row inside the shard image
-        if constexpr (OUTF == kOutF32) { if (orow < out_rows) out[(size_t)orow * f.out_w + (px - f.out_x0)] = o; }
-        else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px - f.out_x0), o);
-    }
+    if (px2 < f.width && py2 < f.height) comp_final_pixel<OUTF>(f, bg_rgba, out, out_rows, px2, py2, tyl * kTile + lyi2, T, ar, ag, ab);
 }
 
 // Measured and dropped again in round 2 (the item STREAM: a resident grid of workgroups, each taking items b, b + G, b + 2G, ...
@@ -2673,11 +2647,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
     if (item >= n_items) return;
     const int tile = (int)it.x;
     const bool multi_seg = (it.y & 1u) != 0u;
-    int tx, tyl;
-    tile_xy(f, (uint32_t)tile, tx, tyl);
-    const int sc = f.shard_count <= 1 ? 1 : f.shard_count;
-    const int ty = tyl * sc + (sc > 1 ? f.shard_index : 0);
-    const int bx = (tx + f.col0) * kTile, by = ty * kTile;
+    const auto [tyl, bx, by] = comp_tile(f, (uint32_t)tile);
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const uint32_t grp = lane >> 4, gi = lane & 15u;
@@ -2699,10 +2669,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
     bool wave_live = true, counted_dead = false;
     if (tid < NBUF) {
         s_staged[tid] = 0u; s_done[tid] = 0u;
-        s_q0[tid * BS + B] = make_float4(0.f, 0.f, __builtin_inff(), 0.f);      // the null record of buffer tid: r^2 = +inf for every pixel
-        s_q1[tid * BS + B] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (DEPTH) s_dep[DEPTH ? tid * BS + B : 0u] = 0.0f;
-        if (COLF) s_q2[COLF ? tid * BS + B : 0u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        comp_null_record<DEPTH, COLF>(s_q0, s_q1, s_q2, s_dep, tid * BS + B);      // the null record of buffer tid
     }
     if (tid == 0) s_dead = 0u;
     const uint32_t n_pairs = rg.y - rg.x;
@@ -2745,28 +2712,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             const uint32_t li = half * 64u + lane;      // my pair inside the batch
-            if (ks * B + li < n_pairs) {
-                const uint32_t at = sb * BS + li;
-                const float ox = fmaf(hW, rb.x, c0x), oy = fmaf(hHn, rb.y, c0y);
-                const float nku = -fmaf(ra.x, ox, ra.y * oy);
-                const float nkv = -fmaf(ra.z, ox, ra.w * oy);
-                const float l2a = __builtin_amdgcn_logf(rb.z);
-                s_q0[at] = make_float4(ra.x, ra.y, nku, l2a);
-                s_q1[at] = make_float4(ra.z, ra.w, nkv, rb.w);
-                const float ria = __builtin_amdgcn_rcpf(fmaf(ra.y, ra.y, ra.x * ra.x)), rib = __builtin_amdgcn_rcpf(fmaf(ra.w, ra.w, ra.z * ra.z));
-                const float qux = ra.x * ria, quy = ra.y * ria, qwx = ra.z * rib, qwy = ra.w * rib;
-                const float bhx = fmaf(2.0f * __builtin_amdgcn_sqrtf(fmaf(qwx, qwx, qux * qux)), 1.0001f, 0.002f);
-                const float bhy = fmaf(2.0f * __builtin_amdgcn_sqrtf(fmaf(qwy, qwy, quy * quy)), 1.0001f, 0.002f);
-                const int xa = min(max((int)ceilf((ox - bhx) - 0.5f), -2), 17), xb = min(max((int)floorf((ox + bhx) - 0.5f), -2), 17);
-                const int ya = min(max((int)ceilf((oy - bhy) - 0.5f), -2), 17), yb = min(max((int)floorf((oy + bhy) - 0.5f), -2), 17);
-                const int gx0 = max(xa >> 2, 0), gx1 = min(xb >> 2, 3), gy0 = max(ya >> 2, 0), gy1 = min(yb >> 2, 3);
-                const uint32_t cx = gx1 >= gx0 ? (2u << gx1) - (1u << gx0) : 0u;
-                const uint32_t ry = gy1 >= gy0 ? (2u << gy1) - (1u << gy0) : 0u;
-                const uint32_t spread = (ry & 1u) | ((ry & 2u) << 3) | ((ry & 4u) << 6) | ((ry & 8u) << 9);
-                s_bb[sb * B + li] = cx * spread;
-                if (DEPTH) s_dep[DEPTH ? at : 0u] = rbw;
-                if (COLF) s_q2[COLF ? at : 0u] = rd;
-            }
+            if (ks * B + li < n_pairs) comp_stage<DEPTH, COLF>(hW, hHn, c0x, c0y, ra, rb, rbw, rd, s_q0, s_q1, s_q2, s_dep, s_bb, sb * BS + li, sb * B + li);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane == 0u) atomicAdd(&s_staged[sb], 1u);
             ks += 2u; sb += 2u; if (sb >= 3u) { sb -= 3u; su += 1u; }
@@ -2802,29 +2748,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
     const float k255 = 1.0f / 255.0f;
     if (!COLF) { ar *= k255; ag *= k255; ab *= k255; }
     if (multi_seg) {
-        partials[(size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid] = make_float4(ar, ag, ab, T);      // (k_composite: pslot)
+        partials[(size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid] = make_float4(ar, ag, ab, T);
         return;
     }
-    uint32_t tid2 = threadIdx.x;
+    uint32_t tid2 = threadIdx.x;                         // (k_composite: the opaque copy of the thread id)
     asm volatile("" : "+v"(tid2));
     const int lxi2 = (int)(((tid2 & 63u) >> 4) * 4u + (tid2 & 3u)), lyi2 = (int)((tid2 >> 6) * 4u + ((tid2 & 15u) >> 2));
     const int px2 = bx + lxi2, py2 = by + lyi2;
-    if (px2 < f.width && py2 < f.height) {
-        float4 bg = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (bg_rgba) bg = bg_rgba[(size_t)py2 * f.width + px2];
-        float4 o;
-        o.x = fmaf(T, bg.x, ar);
-        o.y = fmaf(T, bg.y, ag);
-        o.z = fmaf(T, bg.z, ab);
-        o.w = fmaf(T, bg.w, 1.0f - T);
-        const int orow = tyl * kTile + lyi2;
-        if constexpr (OUTF == kOutF32) { if (orow < out_rows) out[(size_t)orow * f.out_w + (px2 - f.out_x0)] = o; }
-        else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px2 - f.out_x0), o);
-    }
+    if (px2 < f.width && py2 < f.height) comp_final_pixel<OUTF>(f, bg_rgba, out, out_rows, px2, py2, tyl * kTile + lyi2, T, ar, ag, ab);
 }
 
 // Folds the per-segment partials of multi-segment tiles: (C1,T1) o (C2,T2) = (C1 + T1*C2, T1*T2).
-// One workgroup per tile, same lane -> pixel mapping as k_composite.
+// One workgroup per tile, same lane -> pixel map as k_composite.
 template <int OUTF>
 __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* __restrict__ item_base,
                                                  const float4* __restrict__ partials, const float4* __restrict__ bg_rgba,
@@ -2837,15 +2772,12 @@ __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* 
     if (tile == 0 && threadIdx.x < 5u && host_counters) host_counters[threadIdx.x] = counters[threadIdx.x];
     const uint32_t i0 = item_base[tile], n_seg = item_base[tile + 1] - i0;
     if (n_seg == 1u) return;                      // the tile's only work item wrote the pixels itself; n_seg == 0: no pairs, background only
-    int tx, tyl;
-    tile_xy(f, (uint32_t)tile, tx, tyl);
-    const int sc = f.shard_count <= 1 ? 1 : f.shard_count;
-    const int ty = tyl * sc + (sc > 1 ? f.shard_index : 0);
+    const auto [tyl, bx, by] = comp_tile(f, (uint32_t)tile);
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t grp = lane >> 4, gi = lane & 15u;      // same lane -> pixel map as k_composite
     const int lxi = (int)grp * 4 + (int)(gi & 3u);
     const int lyi = (int)wave * 4 + (int)(gi >> 2);
-    const int px = (tx + f.col0) * kTile + lxi, py = ty * kTile + lyi;
+    const int px = bx + lxi, py = by + lyi;
     if (px >= f.width || py >= f.height) return;
     float T = 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f;
     // eight segments' partials in flight together (clamped, unmasked): a horizon tile of c5 has 40 segments, and one dependent
@@ -2864,16 +2796,7 @@ __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* 
             }
         }
     }
-    float4 bg = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (bg_rgba) bg = bg_rgba[(size_t)py * f.width + px];
-    float4 o;
-    o.x = fmaf(T, bg.x, ar);
-    o.y = fmaf(T, bg.y, ag);
-    o.z = fmaf(T, bg.z, ab);
-    o.w = fmaf(T, bg.w, 1.0f - T);
-    const int orow = tyl * kTile + lyi;
-    if constexpr (OUTF == kOutF32) { if (orow < out_rows) out[(size_t)orow * f.out_w + (px - f.out_x0)] = o; }
-    else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px - f.out_x0), o);
+    comp_final_pixel<OUTF>(f, bg_rgba, out, out_rows, px, py, tyl * kTile + lyi, T, ar, ag, ab);
 }
 
 // all-gathered shards -> frame.  rows: shard = tile row % count (rows_padded rows each, full width);
@@ -3058,6 +2981,21 @@ void launch_tile_depth_sort(hipStream_t s, const uint2* ranges, uint32_t* vals, 
 }
 uint32_t tile_depth_sort_cap() { return kTileSortCap; }
 
+// Calls fn(E, D, C) with the std::bool_constant arguments of the compositor instantiation <early-out, depth test, float colours> the frame
+// needs (debug draw modes: float colours from the side buffer, no early-out).
+template <typename Fn>
+static void with_composite_edc(const Frame& f, Fn&& fn)
+{
+    const bool early = f.t_eps > 0.0f, depth = f.has_depth != 0, colf = f.draw_mode != 0u;
+    using T = std::true_type;
+    using F = std::false_type;
+    if (colf) { if (depth) fn(F{}, T{}, T{}); else fn(F{}, F{}, T{}); }
+    else if (early && depth) fn(T{}, T{}, F{});
+    else if (early) fn(T{}, F{}, F{});
+    else if (depth) fn(F{}, T{}, F{});
+    else fn(F{}, F{}, F{});
+}
+
 // ranges -> per-tile segment counts -> item_base (exclusive scan, item_base[n_tiles] = #items) ->
 // k_composite over an upper bound of items -> k_combine, storing the image in format OUTF.
 template <int OUTF>
@@ -3072,48 +3010,22 @@ static void launch_composite_t(hipStream_t s, const Frame& f, const FrameBufs& b
         return;
     }
     const uint32_t max_items = (uint32_t)n_tiles + b.pair_cap / seg + 1u;
-    // variant 2 (GSWT_OPT_FOLD_COMBINE): k_composite folds the segment b.partials itself and writes the empty tiles: no k_combine launch
-    const bool fold = variant == 2 && b.tile_tick != nullptr && b.host_counters != nullptr;
     if (heavy_first)
         GSWT_LAUNCH(k_items<true>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, b.ranges, n_tiles, seg, b.item_base, b.item_tab, max_items, krange, depth_passes, b.counters,
-                    fold ? 1u : 0u, report_max ? 1u : 0u);
+                    report_max ? 1u : 0u);
     else
         GSWT_LAUNCH(k_items<false>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, b.ranges, n_tiles, seg, b.item_base, b.item_tab, max_items, krange, depth_passes, b.counters,
-                    fold ? 1u : 0u, report_max ? 1u : 0u);
-    const bool early = f.t_eps > 0.0f, depth = f.has_depth != 0, colf = f.draw_mode != 0u;
-    // the compositor instantiation <early-out, depth test, float colours> the frame needs (debug draw modes: float colours from the side buffer)
-#define GSWT_COMPOSITE_EDC(LAUNCH)                                                                                             \
-    do {                                                                                                                       \
-        if (colf) { if (depth) LAUNCH(false, true, true); else LAUNCH(false, false, true); }                                   \
-        else if (early && depth) LAUNCH(true, true, false);                                                                    \
-        else if (early) LAUNCH(true, false, false);                                                                            \
-        else if (depth) LAUNCH(false, true, false);                                                                            \
-        else LAUNCH(false, false, false);                                                                                      \
-    } while (0)
-    // (the compositors carry ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED)
-    if (variant == 1) {                  // GSWT_OPT_COMPOSITE = 1: decoupled waves (k_composite_dw), same image bit for bit
-#define GSWT_LAUNCH_COMPOSITE_DW(E, D, C)                                                                                      \
-        GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs, \
-                           b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows)
-        GSWT_COMPOSITE_EDC(GSWT_LAUNCH_COMPOSITE_DW);
-#undef GSWT_LAUNCH_COMPOSITE_DW
-        GSWT_LAUNCH(k_combine<OUTF>, dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows, (const unsigned long long*)b.counters, b.host_counters);
-        return;
-    }
-    if (fold) {
-#define GSWT_LAUNCH_COMPOSITE_F(E, D, C)                                                                                       \
-        GSWT_LAUNCH_TIMED((k_composite<E, D, C, true, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals, b.recs, \
-                           b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.tile_tick, (const unsigned long long*)b.counters, b.host_counters)
-        GSWT_COMPOSITE_EDC(GSWT_LAUNCH_COMPOSITE_F);
-#undef GSWT_LAUNCH_COMPOSITE_F
-        return;
-    }
-#define GSWT_LAUNCH_COMPOSITE(E, D, C)                                                                                         \
-    GSWT_LAUNCH_TIMED((k_composite<E, D, C, false, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals, b.recs, \
-                       b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, (uint32_t*)nullptr, (const unsigned long long*)nullptr, (unsigned long long*)nullptr)
-    GSWT_COMPOSITE_EDC(GSWT_LAUNCH_COMPOSITE);
-#undef GSWT_LAUNCH_COMPOSITE
-#undef GSWT_COMPOSITE_EDC
+                    report_max ? 1u : 0u);
+    // GSWT_OPT_COMPOSITE = 1: decoupled waves (k_composite_dw), same image bit for bit; 0 and 2: k_composite.  (The compositors carry
+    // ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED.)
+    with_composite_edc(f, [&](auto E, auto D, auto C) {
+        if (variant == 1)
+            GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs,
+                              b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows);
+        else
+            GSWT_LAUNCH_TIMED((k_composite<E, D, C, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals,
+                              b.recs, b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows);
+    });
     GSWT_LAUNCH(k_combine<OUTF>, dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows, (const unsigned long long*)b.counters, b.host_counters);
 }
 

@@ -209,9 +209,9 @@ enum { GSWT_OPT_NO_LOD_PREFILTER = 1, GSWT_OPT_DEBUG_VARYINGS = 2,
                                      bits is flagged on the device and re-run with more, like a pair-buffer overflow */,
        GSWT_OPT_COMPOSITE = 13 /* compositor kernel: 0 (default) k_composite -- 256-pair batches staged by the whole workgroup, two barriers per
                                   batch; 1 k_composite_dw -- the four waves of a work item decoupled (128-pair batches through a ring of three LDS
-                                  buffers, ready / consumed counters instead of barriers); 2 k_composite<FOLD> -- the segments of a long tile list
-                                  are folded by whichever of their workgroups finishes last (agent-scope stores + a ticket per tile), tiles
-                                  without pairs are work items: no k_combine launch behind the compositor.  Same image bit for bit */,
+                                  buffers, ready / consumed counters instead of barriers); 2 is accepted and runs what 0 runs (its own
+                                  compositor, which folded the segments itself instead of launching k_combine, was removed); 3 and above are
+                                  refused.  Same image bit for bit */,
        GSWT_OPT_DEPTH_SORT = 14 /* how GSWT_ORDER_DEPTH orders the pairs: 0 (default) / 2 = tile passes first (depth bits as payload), then every
                                    screen tile's slice is depth-sorted by one wave / workgroup (k_tile_depth_sort: inside LDS up to 16 384 pairs,
                                    through global memory beyond); 1 = global radix passes on the depth bits in front of the tile passes.

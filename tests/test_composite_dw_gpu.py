@@ -58,9 +58,8 @@ def test_decoupled_waves_variants(renderer, kw):
     assert np.abs(a.astype(np.float64) - ref).max() <= 1e-4 + kw.get("t_eps", 0.0)
 
 
-# ---- GSWT_OPT_COMPOSITE = 2: k_composite<FOLD> -- no k_combine launch: the last segment of a tile to finish folds the partials (agent-scope
-# stores / loads + a ticket per tile), tiles without pairs are (empty) work items, workgroup 0 publishes the counters.  The fold order is
-# k_combine's, so the image is bit-identical WHICHEVER workgroup finishes last: any lost update across the XCDs' L2 caches would show here.
+# ---- GSWT_OPT_COMPOSITE = 2: once k_composite<FOLD> (no k_combine launch; removed), now an alias of the default k_composite + k_combine
+# chain.  It stays accepted, and its images and counts must stay bit-identical to option 0's.
 def _variant(renderer, v, fn):
     renderer.set_option(L.GSWT_OPT_COMPOSITE, v)
     try:
