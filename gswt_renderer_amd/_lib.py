@@ -42,6 +42,8 @@ GSWT_SHARD_COLUMNS = 1
 GSWT_OUT_RGBA32F = 0          # RenderConfig.out_format: RGBA f32, 16 bytes per pixel
 GSWT_OUT_RGBA8_UNORM = 1      # bytes R, G, B, A per pixel
 GSWT_OUT_BGRA8_UNORM = 2      # bytes B, G, R, A per pixel
+GSWT_PROXY_SRC_RGBA8 = 0      # gswt_proxy_configure_image: 8-bit RGBA source, 4 bytes per texel
+GSWT_PROXY_SRC_RGBA16 = 1     # 16-bit RGBA source, 8 bytes per texel
 
 
 class CameraUniforms(C.Structure):
@@ -180,6 +182,8 @@ SYMBOLS = {
     "gswt_skybox_download": (C.c_int, [_P, _P]),
     "gswt_skybox_render": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "gswt_proxy_configure": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
+    "gswt_proxy_configure_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gswt_proxy_download": (C.c_int, [_P, _P]),
     "gswt_proxy_render": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
     "gswt_shard_rows": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "gswt_shard_rows_padded": (C.c_int, [C.c_int, C.c_int]),

@@ -1875,6 +1875,74 @@ try {
     return GSWT_OK;
 } GSWT_CATCH("gswt_proxy_configure")
 
+// upload_proxy_texture + Proxy::configure (proxy.rs:513-554, 289-318): every level resampled from the original image on the device
+// (gswt_passes.hip, "proxy texture mip build").  The source, the tap tables, the intermediate and the partial sums live for this
+// call only; the staged source rows are padded to 16 bytes so that every lane's 16-byte load is aligned.
+int gswt_proxy_configure_image(gswt_ctx* c, const void* pixels, int width, int height, int src_format, int tex_size, int grid_dim)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!pixels) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_configure_image: null image");
+    if (width <= 0 || width > 16384 || height <= 0 || height > 16384)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_configure_image: bad image size %d x %d", width, height);
+    if (src_format != GSWT_PROXY_SRC_RGBA8 && src_format != GSWT_PROXY_SRC_RGBA16)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_configure_image: bad source format %d", src_format);
+    if (tex_size <= 0 || tex_size > 16384 || (tex_size & (tex_size - 1)) != 0)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_configure_image: texture size %d is not a power of two in 1..16384", tex_size);
+    if (grid_dim <= 0 || grid_dim > 32768) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_configure_image: bad grid %d", grid_dim);
+    hipSetDevice(c->device);
+    HIP_TRY(c, sync_all(c));
+    const int u16 = src_format == GSWT_PROXY_SRC_RGBA16 ? 1 : 0;
+    const size_t row_bytes = (size_t)width * (u16 ? 8 : 4), pitch = (row_bytes + 15) / 16 * 16;
+    int n_mips = 0;
+    uint32_t mip_off[16] = {};
+    size_t total = 0, n_tmp = 0, n_part = 0, n_wv = 0, n_wh = 0;
+    std::vector<ProxyMipArgs> plan;
+    for (int n = tex_size; n >= 1; n >>= 1, n_mips++) {
+        mip_off[n_mips] = (uint32_t)total;
+        total += (size_t)n * n;
+        plan.push_back(plan_proxy_mip(width, height, n, u16, (int)pitch));
+        n_tmp = std::max(n_tmp, proxy_mip_tmp_texels(plan.back()));
+        n_part = std::max(n_part, proxy_mip_part_texels(plan.back()));
+        n_wv = std::max(n_wv, proxy_mip_weights(plan.back(), 0));
+        n_wh = std::max(n_wh, proxy_mip_weights(plan.back(), 1));
+    }
+    DevBuf<uint8_t> src;
+    DevBuf<float4> tmp, part;
+    DevBuf<int2> ranges;
+    DevBuf<float> wv, wh;
+    HIP_TRY(c, src.ensure(pitch * height));
+    HIP_TRY(c, hipMemcpy2D(src.p, pitch, pixels, row_bytes, row_bytes, height, hipMemcpyHostToDevice));
+    HIP_TRY(c, null_stream_done());
+    HIP_TRY(c, tmp.ensure(n_tmp));
+    HIP_TRY(c, part.ensure(n_part));
+    HIP_TRY(c, ranges.ensure((size_t)2 * tex_size));
+    HIP_TRY(c, wv.ensure(n_wv));
+    HIP_TRY(c, wh.ensure(n_wh));
+    HIP_TRY(c, c->proxy_tex.ensure(total));       // a failed allocation keeps the old texture
+    // From here on the old texture is being overwritten: a failure leaves no proxy (proxy_size = 0), never a half-written one.
+    c->proxy_size = 0; c->proxy_mips = 0;
+    for (int l = 0; l < n_mips; l++)
+        launch_proxy_mip(c->stream, plan[l], src.p, ranges.p, wv.p, wh.p, tmp.p, part.p, c->proxy_tex.p + mip_off[l]);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    memcpy(c->proxy_mip_off, mip_off, sizeof(mip_off));
+    c->proxy_size = tex_size; c->proxy_mips = n_mips; c->proxy_grid_dim = grid_dim;
+    return GSWT_OK;
+} GSWT_CATCH("gswt_proxy_configure_image")
+
+int gswt_proxy_download(gswt_ctx* c, float* mips_rgba_host)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!mips_rgba_host) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_download: null destination");
+    if (c->proxy_size == 0) return fail(c, GSWT_ERR_STATE, "gswt_proxy_download before a proxy configure");
+    hipSetDevice(c->device);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    size_t total = 0;                             // the levels are packed (proxy_mip_off)
+    for (int l = 0; l < c->proxy_mips; l++) total += (size_t)(c->proxy_size >> l) * (c->proxy_size >> l);
+    HIP_TRY(c, hipMemcpy(mips_rgba_host, c->proxy_tex.p, total * 16, hipMemcpyDeviceToHost));
+    return GSWT_OK;
+} GSWT_CATCH("gswt_proxy_download")
+
 int gswt_proxy_render(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, float* rgba_dev, float* depth_dev, int clear_depth)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;

@@ -141,6 +141,24 @@ struct SkyBakeArgs {
     int face_size, equi_w, equi_h;
 };
 
+// One level of the proxy texture's Lanczos3 mip build (upload_proxy_texture, proxy.rs:513-554: image::imageops::resize of the
+// ORIGINAL image to n x n): plan_proxy_mip fills it; the tap tables, the vertical pass (h -> n rows, f32 intermediate
+// [n][src_w]) and the horizontal pass (src_w -> n columns, quantised into the chain) of gswt_passes.hip read it.
+struct ProxyMipArgs {
+    int src_w, src_h, n;
+    int u16;                // 0: RGBA8 source (4 B per texel), 1: RGBA16 (8 B per texel)
+    int pitch;              // staged source row pitch in bytes, a multiple of 16
+    int copy;               // (n, n) == (src_w, src_h): the crate copies; the level is a conversion, not a resample
+    int stride_v, stride_h; // weights per output in the vertical / horizontal tap table (>= any output's tap count)
+    int splits, chunk;      // vertical pass: the taps of every output split into `splits` runs of `chunk`; > 1: partial sums
+    float maxv;             // 255 or 65535
+};
+ProxyMipArgs plan_proxy_mip(int src_w, int src_h, int n, int u16, int pitch);
+// device elements each buffer of one level's build needs (0 for a copy level)
+inline size_t proxy_mip_tmp_texels(const ProxyMipArgs& a) { return a.copy ? 0 : (size_t)a.n * a.src_w; }
+inline size_t proxy_mip_part_texels(const ProxyMipArgs& a) { return a.copy || a.splits == 1 ? 0 : (size_t)a.splits * a.n * a.src_w; }
+inline size_t proxy_mip_weights(const ProxyMipArgs& a, int axis) { return a.copy ? 0 : (size_t)a.n * (axis == 0 ? a.stride_v : a.stride_h); }
+
 struct ProxyArgs {
     // proxy.wgsl Uniforms
     float height_offset, tile_width, width_scale, clip_height, brightness;
@@ -308,6 +326,10 @@ void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int
                    const float4* faces, float4* out);
 void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi, float4* faces);
 void launch_proxy(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth);
+// One level of the proxy mip build into dst (n x n float4).  src: the staged source, a.pitch bytes per row.  ranges: 2 n int2,
+// wv / wh: the tap weights, tmp: the intermediate, part: the partial sums (sizes: proxy_mip_* above; unused on a copy level).
+void launch_proxy_mip(hipStream_t s, const ProxyMipArgs& a, const uint8_t* src, int2* ranges, float* wv, float* wh, float4* tmp,
+                      float4* part, float4* dst);
 void launch_fill_f32(hipStream_t s, float* p, size_t n, float v);
 
 }  // namespace gswt

@@ -4,6 +4,8 @@
 //   k_skybox : skybox.wgsl vs_main + fs_main (cube map lookup along the pixel's view ray), skybox.rs:457-488
 //   k_skybox_bake : skybox.wgsl vs_bake + fs_bake (skybox.rs:490-668), configure time: an equirectangular HDR panorama baked
 //              into the cube map k_skybox samples
+//   k_lanczos_taps / k_lanczos_v / k_lanczos_v_sum / k_lanczos_h / k_proxy_mip_copy : configure time, the proxy texture's
+//              Lanczos3 mip chain from its 8- / 16-bit RGBA image (upload_proxy_texture, proxy.rs:513-554)
 //   k_proxy  : proxy.wgsl vs_main + fs_main + depth state (proxy.rs:96-134,366-447): the height-mapped ground grid.  Instead of
 //              pushing up to 2 x 2048^2 triangles through a rasteriser, every pixel casts its view ray at the height field
 //              (2-D DDA over the grid cells, two triangles per cell); the nearest fragment with depth in [0, 1] is exactly
@@ -12,6 +14,8 @@
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (same flags as gswt_kernels.hip).
 #include "gswt_device.h"
+
+#include <algorithm>
 
 namespace gswt {
 
@@ -327,6 +331,229 @@ void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi,
 {
     const int n = a.face_size;
     hipLaunchKernelGGL(k_skybox_bake, dim3((n + 63) / 64, (n + 3) / 4, 6), dim3(256), 0, s, a, equi, faces);
+}
+
+// ---- proxy texture mip build ------------------------------------------------------------------------
+// upload_proxy_texture (proxy.rs:513-554): level n = image::imageops::resize(original, n, n, Lanczos3), then to_rgba32f.  For an
+// 8- / 16-bit RGBA image the crate runs, all in f32:
+//   per axis (in -> out): ratio = in / out, sratio = max(ratio, 1), support = 3 sratio; output o has centre c = (o + 0.5) ratio,
+//     taps i in [left, right) with left = clamp(floor(c - support), 0, in - 1), right = clamp(ceil(c + support), left + 1, in),
+//     weights L((i - (c - 0.5)) / sratio) divided by their sum (taps outside the image are dropped, the rest renormalised);
+//     L(x) = sinc(x) sinc(x / 3) for |x| < 3, sinc(t) = sin(pi t) / (pi t);
+//   a vertical pass (h -> n rows) into an unclamped f32 image in source units, then a horizontal pass (w -> n columns) whose
+//   outputs are clamp(t, 0, MAX) rounded half away from zero; to_rgba32f divides by MAX.  (n, n) == (w, h) is a plain copy.
+// Accumulation is t = t + v * w (-ffp-contract=off: no fma), like the crate's loop.  The crate sums in tap order; here the
+// vertical pass may split an output's taps into runs summed separately and the horizontal pass spreads them over G lanes,
+// both reduced in a fixed order: the result is deterministic, and within the f32 rounding of a reordered sum of the crate's.
+
+constexpr float kPiF = 3.14159265358979323846f;     // core::f32::consts::PI
+
+__device__ __forceinline__ float lanczos3(float x)
+{
+    if (!(fabsf(x) < 3.0f)) return 0.0f;
+    const float x3 = x / 3.0f;
+    const float a = x * kPiF, b = x3 * kPiF;
+    const float s0 = x == 0.0f ? 1.0f : sinf(a) / a;           // full-precision sinf, IEEE division
+    const float s1 = x3 == 0.0f ? 1.0f : sinf(b) / b;
+    return s0 * s1;
+}
+
+// Tap tables of one level, both axes (blockIdx.y: 0 vertical over the source rows, 1 horizontal over its columns): one wave per
+// output; ranges[axis * n + o] = (left, count), w[o * stride + k] = the normalised weight of source index left + k.
+__global__ __launch_bounds__(64) void k_lanczos_taps(const ProxyMipArgs a, int2* __restrict__ ranges, float* __restrict__ wv,
+                                                     float* __restrict__ wh)
+{
+    const int axis = blockIdx.y, o = blockIdx.x, lane = threadIdx.x;
+    const int in = axis == 0 ? a.src_h : a.src_w, stride = axis == 0 ? a.stride_v : a.stride_h;
+    float* w = (axis == 0 ? wv : wh) + (size_t)o * stride;
+    const float ratio = (float)in / (float)a.n;
+    const float sratio = ratio < 1.0f ? 1.0f : ratio;
+    const float support = 3.0f * sratio;
+    const float c = ((float)o + 0.5f) * ratio;
+    const int left = min(max((int)floorf(c - support), 0), in - 1);
+    const int right = min(max((int)ceilf(c + support), left + 1), in);
+    const int cnt = min(right - left, stride);                  // (plan_proxy_mip sizes stride above any count)
+    const float cc = c - 0.5f;
+    float part = 0.0f;
+    for (int k = lane; k < cnt; k += 64) {
+        const float r = lanczos3(((float)(left + k) - cc) / sratio);
+        w[k] = r;
+        part = part + r;
+    }
+    for (int off = 32; off > 0; off >>= 1) part = part + __shfl_down(part, off, 64);
+    const float sum = __shfl(part, 0, 64);
+    for (int k = lane; k < cnt; k += 64) w[k] = w[k] / sum;     // each lane rescales what it wrote
+    if (lane == 0) ranges[axis * a.n + o] = make_int2(left, cnt);
+}
+
+// 16 source bytes: 4 RGBA8 texels (R in the low byte of each dword) or 2 RGBA16 texels (R in the low half of the first dword)
+template <bool U16>
+__device__ __forceinline__ void unpack16(const uint4 q, float4* v)
+{
+    if (U16) {
+        v[0] = make_float4((float)(q.x & 0xffffu), (float)(q.x >> 16), (float)(q.y & 0xffffu), (float)(q.y >> 16));
+        v[1] = make_float4((float)(q.z & 0xffffu), (float)(q.z >> 16), (float)(q.w & 0xffffu), (float)(q.w >> 16));
+    } else {
+        const uint32_t d[4] = {q.x, q.y, q.z, q.w};
+        for (int p = 0; p < 4; p++)
+            v[p] = make_float4((float)(d[p] & 255u), (float)((d[p] >> 8) & 255u), (float)((d[p] >> 16) & 255u), (float)(d[p] >> 24));
+    }
+}
+
+// Vertical pass: lane = one 16-byte column group of the source (4 or 2 texels), blockIdx.y = output row o, blockIdx.z = run s of
+// o's taps.  Every lane of a wave loads 16 B of the same source row (1 KiB per wave-instruction); the weight is wave-uniform.
+// out: the intermediate [n][src_w] (one run) or the partial sums [splits][n][src_w].
+template <bool U16>
+__global__ __launch_bounds__(64) void k_lanczos_v(const ProxyMipArgs a, const uint8_t* __restrict__ src, const int2* __restrict__ ranges,
+                                                  const float* __restrict__ wv, float4* __restrict__ out)
+{
+    constexpr int P = U16 ? 2 : 4;
+    const int g = blockIdx.x * 64 + threadIdx.x, o = blockIdx.y, s = blockIdx.z;
+    const int x0 = g * P;
+    if (x0 >= a.src_w) return;
+    const int2 r = ranges[o];
+    const int k0 = s * a.chunk, k1 = min(r.y, k0 + a.chunk);
+    const float* w = wv + (size_t)o * a.stride_v;
+    const uint8_t* col = src + (size_t)r.x * a.pitch + (size_t)g * 16;
+    float4 acc[P];
+    for (int p = 0; p < P; p++) acc[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll 4
+    for (int k = k0; k < k1; k++) {
+        float4 v[P];
+        unpack16<U16>(*reinterpret_cast<const uint4*>(col + (size_t)k * a.pitch), v);
+        const float wk = w[k];
+        for (int p = 0; p < P; p++) {
+            acc[p].x = acc[p].x + v[p].x * wk;
+            acc[p].y = acc[p].y + v[p].y * wk;
+            acc[p].z = acc[p].z + v[p].z * wk;
+            acc[p].w = acc[p].w + v[p].w * wk;
+        }
+    }
+    float4* dst = out + ((size_t)s * a.n + o) * a.src_w + x0;
+    for (int p = 0; p < P; p++)
+        if (x0 + p < a.src_w) dst[p] = acc[p];
+}
+
+// The runs of a split vertical pass, summed in run order.
+__global__ __launch_bounds__(256) void k_lanczos_v_sum(const ProxyMipArgs a, const float4* __restrict__ part, float4* __restrict__ out)
+{
+    const size_t m = (size_t)a.n * a.src_w, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    float4 t = part[i];
+    for (int s = 1; s < a.splits; s++) {
+        const float4 v = part[(size_t)s * m + i];
+        t.x = t.x + v.x; t.y = t.y + v.y; t.z = t.z + v.z; t.w = t.w + v.w;
+    }
+    out[i] = t;
+}
+
+__device__ __forceinline__ float quantise(float t, float maxv)
+{
+    return roundf(fminf(fmaxf(t, 0.0f), maxv)) / maxv;          // clamp, FloatNearest (half away from zero), to_rgba32f
+}
+
+// Horizontal pass: G consecutive lanes per output texel (o, y) take its taps k = j, j + G, ... (adjacent lanes read adjacent
+// intermediate texels), then a shuffle tree in a fixed order; lane j = 0 stores the quantised texel.
+template <int G>
+__global__ __launch_bounds__(256) void k_lanczos_h(const ProxyMipArgs a, const float4* __restrict__ tmp, const int2* __restrict__ ranges,
+                                                   const float* __restrict__ wh, float4* __restrict__ dst)
+{
+    const int o = blockIdx.x * (256 / G) + threadIdx.x / G, j = threadIdx.x % G, y = blockIdx.y;
+    float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (o < a.n) {
+        const int2 r = ranges[a.n + o];
+        const float* w = wh + (size_t)o * a.stride_h;
+        const float4* row = tmp + (size_t)y * a.src_w + r.x;
+        for (int k = j; k < r.y; k += G) {
+            const float4 v = row[k];
+            const float wk = w[k];
+            t.x = t.x + v.x * wk; t.y = t.y + v.y * wk; t.z = t.z + v.z * wk; t.w = t.w + v.w * wk;
+        }
+    }
+    for (int off = G / 2; off > 0; off >>= 1) {
+        t.x = t.x + __shfl_down(t.x, off, G); t.y = t.y + __shfl_down(t.y, off, G);
+        t.z = t.z + __shfl_down(t.z, off, G); t.w = t.w + __shfl_down(t.w, off, G);
+    }
+    if (j == 0 && o < a.n)
+        dst[(size_t)y * a.n + o] = make_float4(quantise(t.x, a.maxv), quantise(t.y, a.maxv), quantise(t.z, a.maxv), quantise(t.w, a.maxv));
+}
+
+// Copy level: x / MAX per channel, 16 source bytes per lane.
+template <bool U16>
+__global__ __launch_bounds__(64) void k_proxy_mip_copy(const ProxyMipArgs a, const uint8_t* __restrict__ src, float4* __restrict__ dst)
+{
+    constexpr int P = U16 ? 2 : 4;
+    const int g = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y;
+    const int x0 = g * P;
+    if (x0 >= a.n) return;
+    float4 v[P];
+    unpack16<U16>(*reinterpret_cast<const uint4*>(src + (size_t)y * a.pitch + (size_t)g * 16), v);
+    float4* d = dst + (size_t)y * a.n + x0;
+    for (int p = 0; p < P; p++)
+        if (x0 + p < a.n) d[p] = make_float4(v[p].x / a.maxv, v[p].y / a.maxv, v[p].z / a.maxv, v[p].w / a.maxv);
+}
+
+ProxyMipArgs plan_proxy_mip(int src_w, int src_h, int n, int u16, int pitch)
+{
+    ProxyMipArgs a{};
+    a.src_w = src_w; a.src_h = src_h; a.n = n; a.u16 = u16; a.pitch = pitch;
+    a.copy = n == src_w && n == src_h;
+    a.maxv = u16 ? 65535.0f : 255.0f;
+    // A count is right - left <= ceil(fl(c + support)) - floor(fl(c - support)) < 2 support + 2 + (rounding of the two sums,
+    // < 2^-6 at these sizes): at most floor(2 support) + 3 taps, and never more than the axis has.
+    auto stride = [n](int in) {
+        const float ratio = (float)in / (float)n, support = 3.0f * (ratio < 1.0f ? 1.0f : ratio);
+        return std::min(in, (int)(2.0f * support) + 4);
+    };
+    a.stride_v = stride(src_h); a.stride_h = stride(src_w);
+    // Split the vertical taps when the level has few outputs: aim at ~2048 waves, runs of at least 64 taps.  splits * n *
+    // groups <= 2048 bounds the partial sums at 2048 * 64 * 4 texels * 16 B = 8 MiB.
+    const int groups = ((src_w + (u16 ? 1 : 3)) / (u16 ? 2 : 4) + 63) / 64;
+    const long base = (long)groups * n;
+    a.splits = 1;
+    if (a.stride_v >= 128 && base < 2048) a.splits = (int)std::max(1L, std::min(2048 / base, (long)(a.stride_v / 64)));
+    a.chunk = (a.stride_v + a.splits - 1) / a.splits;
+    a.splits = (a.stride_v + a.chunk - 1) / a.chunk;
+    return a;
+}
+
+template <int G>
+static void launch_lanczos_h(hipStream_t s, const ProxyMipArgs& a, const float4* tmp, const int2* ranges, const float* wh, float4* dst)
+{
+    hipLaunchKernelGGL(k_lanczos_h<G>, dim3((a.n + 256 / G - 1) / (256 / G), a.n), dim3(256), 0, s, a, tmp, ranges, wh, dst);
+}
+
+void launch_proxy_mip(hipStream_t s, const ProxyMipArgs& a, const uint8_t* src, int2* ranges, float* wv, float* wh, float4* tmp,
+                      float4* part, float4* dst)
+{
+    const int P = a.u16 ? 2 : 4;
+    if (a.copy) {
+        const dim3 grid(((a.n + P - 1) / P + 63) / 64, a.n);
+        if (a.u16) hipLaunchKernelGGL(k_proxy_mip_copy<true>, grid, dim3(64), 0, s, a, src, dst);
+        else hipLaunchKernelGGL(k_proxy_mip_copy<false>, grid, dim3(64), 0, s, a, src, dst);
+        return;
+    }
+    hipLaunchKernelGGL(k_lanczos_taps, dim3(a.n, 2), dim3(64), 0, s, a, ranges, wv, wh);
+    const dim3 vgrid(((a.src_w + P - 1) / P + 63) / 64, a.n, a.splits);
+    float4* vout = a.splits > 1 ? part : tmp;
+    if (a.u16) hipLaunchKernelGGL(k_lanczos_v<true>, vgrid, dim3(64), 0, s, a, src, ranges, wv, vout);
+    else hipLaunchKernelGGL(k_lanczos_v<false>, vgrid, dim3(64), 0, s, a, src, ranges, wv, vout);
+    if (a.splits > 1) {
+        const size_t m = (size_t)a.n * a.src_w;
+        hipLaunchKernelGGL(k_lanczos_v_sum, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, s, a, part, tmp);
+    }
+    // G lanes per output: about 16 taps per lane or more, up to a wave
+    int G = 1;
+    while (G < 64 && G * 16 < a.stride_h) G *= 2;
+    switch (G) {
+    case 1: launch_lanczos_h<1>(s, a, tmp, ranges, wh, dst); break;
+    case 2: launch_lanczos_h<2>(s, a, tmp, ranges, wh, dst); break;
+    case 4: launch_lanczos_h<4>(s, a, tmp, ranges, wh, dst); break;
+    case 8: launch_lanczos_h<8>(s, a, tmp, ranges, wh, dst); break;
+    case 16: launch_lanczos_h<16>(s, a, tmp, ranges, wh, dst); break;
+    case 32: launch_lanczos_h<32>(s, a, tmp, ranges, wh, dst); break;
+    default: launch_lanczos_h<64>(s, a, tmp, ranges, wh, dst); break;
+    }
 }
 
 __global__ __launch_bounds__(256) void k_fill_f32(float* __restrict__ p, size_t n, float v)

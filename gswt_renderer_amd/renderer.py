@@ -262,6 +262,46 @@ class GSWTRenderer:
         ms = [np.ascontiguousarray(m, dtype=np.float32) for m in mips]
         arr = (C.c_void_p * len(ms))(*[m.ctypes.data for m in ms])
         self._check(self._lib.gswt_proxy_configure(self._h, arr, ms[0].shape[0], len(ms), grid_dim))
+        self._proxy_chain = (ms[0].shape[0], len(ms))
+
+    def proxy_configure_image(self, img: np.ndarray, tex_size: int | None = None, grid_dim: int = 2048):
+        """upload_proxy_texture + Proxy::configure (proxy.rs:513-554) from the decoded image: the Lanczos3 mip chain
+        tex_size, tex_size / 2, ..., 1 is built on the device from img, [h, w, 4], [h, w, 3] or [h, w] uint8 or uint16 (row 0
+        first).  Missing channels are expanded as image's to_rgba8 / to_rgba16 do: grey -> (g, g, g, MAX), RGB -> (r, g, b, MAX).
+
+        tex_size defaults to the largest power of two <= w, computed exactly.  The reference computes it as
+        2^floor(ln(w) / ln(2)) in f32, which at w = 8192 gives 4096 or 8192 depending on how its logf rounds; a host that
+        must match it passes its own value."""
+        a = np.asarray(img)
+        if a.dtype not in (np.uint8, np.uint16):
+            raise TypeError(f"proxy image must be uint8 or uint16, not {a.dtype}")
+        if a.ndim == 2:
+            a = a[..., None]
+        if a.ndim != 3 or a.shape[2] not in (1, 3, 4):
+            raise ValueError(f"proxy image must be [h, w], [h, w, 3] or [h, w, 4], not {tuple(np.shape(img))}")
+        if a.shape[2] != 4:
+            rgba = np.empty(a.shape[:2] + (4,), a.dtype)
+            rgba[..., :3] = a[..., :3] if a.shape[2] == 3 else a
+            rgba[..., 3] = np.iinfo(a.dtype).max
+            a = rgba
+        a = np.ascontiguousarray(a)
+        h, w = a.shape[:2]
+        n = (1 << (int(w).bit_length() - 1)) if tex_size is None else int(tex_size)
+        fmt = L.GSWT_PROXY_SRC_RGBA16 if a.dtype == np.uint16 else L.GSWT_PROXY_SRC_RGBA8
+        self._check(self._lib.gswt_proxy_configure_image(self._h, _ptr(a), w, h, fmt, n, int(grid_dim)))
+        self._proxy_chain = (n, n.bit_length())
+
+    def proxy_download(self) -> list:
+        """The current proxy mip chain: [n >> level, n >> level, 4] f32 arrays, level 0 first."""
+        n, levels = getattr(self, "_proxy_chain", (0, 0))
+        sizes = [n >> l for l in range(levels)]
+        flat = np.empty((sum(s * s for s in sizes), 4) if n else (1,), np.float32)   # (no proxy: the call fails before writing)
+        self._check(self._lib.gswt_proxy_download(self._h, _ptr(flat)))
+        out, off = [], 0
+        for s in sizes:
+            out.append(flat[off:off + s * s].reshape(s, s, 4))
+            off += s * s
+        return out
 
     def proxy_render(self, uniforms, width: int, height: int, rgba_device_ptr: int, depth_device_ptr: int, clear_depth: bool):
         """One draw of Proxy::render (proxy.rs:366); uniforms: 224-byte proxy.wgsl Uniforms block."""

@@ -355,6 +355,29 @@ GSWT_API int gswt_skybox_render(gswt_ctx *ctx, const gswt_camera_uniforms *camer
  * pointers) and the grid dimension of the "full" proxy (Proxy::GRID_DIM = 2048, proxy.rs:29).  The height map is the one
  * given to gswt_configure. */
 GSWT_API int gswt_proxy_configure(gswt_ctx *ctx, const float *const *mips, int tex_size, int n_mips, int grid_dim);
+#define GSWT_PROXY_SRC_RGBA8   0   /* decoded 8-bit RGBA, 4 B per texel (PNG/JPEG via to_rgba8) */
+#define GSWT_PROXY_SRC_RGBA16  1   /* decoded 16-bit RGBA, 8 B per texel (16-bit PNG via to_rgba16) */
+/* upload_proxy_texture + Proxy::configure (proxy.rs:513-554, 289-318) from the decoded image: `pixels` (host pointer) is
+ * width x height texels of src_format, row-major, row 0 first, channels R G B A (img.to_rgba8().into_raw() or to_rgba16()).
+ * Builds the whole chain tex_size, tex_size / 2, ..., 1 (log2(tex_size) + 1 levels) on the device, each level resampled from
+ * the ORIGINAL image as image::imageops::resize(.., n, n, Lanczos3) + to_rgba32f does: a vertical then a horizontal Lanczos3
+ * pass in f32, window clipped and renormalised at the image edges, the result clamped, rounded half away from zero and
+ * divided by 255 / 65535; a level with (n, n) == (width, height) is a copy.  Afterwards the context is exactly as after
+ * gswt_proxy_configure with that chain (gswt_proxy_download reads it back).  tex_size is the caller's max_size (the
+ * reference computes 2^floor(ln(width) / ln(2)) in f32, whose value at width 8192 depends on the logf rounding); it may
+ * exceed width or height (then the same formula upsamples).
+ * Device memory for the call, besides the chain (tex_size^2 * 16 * 4/3 B): the source (rows padded to 16 B), the f32
+ * intermediate of the largest resampled level (width * n * 16 B: 128 MiB for a 4096^2 image at tex_size 4096, whose level 0
+ * is a copy; 4 GiB at the 16384 limit, not strip-mined), partial sums of the small levels (<= 8 MiB) and the tap tables,
+ * each staging buffer with up to a quarter of allocator headroom.
+ * GSWT_ERR_BAD_ARG (nothing staged, previous proxy kept) for a null image, width / height outside 1..16384, an unknown
+ * src_format, tex_size not a power of two in 1..16384 or grid_dim outside 1..32768.  A failure after the old texture starts
+ * being overwritten leaves no proxy (as before any configure). */
+GSWT_API int gswt_proxy_configure_image(gswt_ctx *ctx, const void *pixels, int width, int height, int src_format,
+                                        int tex_size, int grid_dim);
+/* Copies the current proxy chain to the host, levels packed tex_size >> l for l = 0.., each (tex_size >> l)^2 RGBA f32 texels,
+ * whichever configure call produced it.  GSWT_ERR_STATE before any proxy configure. */
+GSWT_API int gswt_proxy_download(gswt_ctx *ctx, float *mips_rgba_host);
 /* ONE draw of Proxy::render (proxy.rs:366-447): u->map_proxy selects the GRID_DIM grid (0, `proxy_full`) or the tile-map
  * grid (1, `proxy_map`).  rgba_dev (W*H*4) and depth_dev (W*H) are device buffers updated in place: colour LoadOp::Load,
  * depth test Less with depth write.  clear_depth != 0 first fills depth_dev with 1.0 (the pass's LoadOp::Clear(1.0)). */
