@@ -1704,14 +1704,16 @@ __global__ __launch_bounds__(256) void k_mg_keys(const MergeSeg* __restrict__ se
     const uint2 b = blocks[blockIdx.x];
     const MergeSeg sg = segs[b.x];
     const MergeGroup g = groups[sg.group];
-    // scene.rs:669-676: depth_inv = 65535 / (max - min) (f32), bucket = floor((d - min) as f32 * depth_inv) as i32, clamped
-    const float depth_inv = 65535.0f / (float)(int32_t)(g.mx - g.mn);
+    // scene.rs:669-676: depth_inv = 65535 / (max - min) (f32), bucket = floor((d - min) as f32 * depth_inv) as i32, clamped.
+    // Both differences are Rust's wrapping i32 subtractions (a span beyond 2^31 - 1 wraps negative): done in u32 here, where
+    // wrapping is defined.
+    const float depth_inv = 65535.0f / (float)(int32_t)((uint32_t)g.mx - (uint32_t)g.mn);
 #pragma unroll
     for (uint32_t k = 0; k < 4u; k++) {
         const uint32_t i = b.y + k * 256u + threadIdx.x;
         if (i >= sg.len) break;
         const int32_t d = raw[sg.src + i];
-        const float v = floorf((float)(int32_t)(d - g.mn) * depth_inv);
+        const float v = floorf((float)(int32_t)((uint32_t)d - (uint32_t)g.mn) * depth_inv);
         int32_t bk;
         if (v != v) bk = 0;                                  // NaN (max == min: 0 * inf) -> 0
         else if (v >= 2147483648.0f) bk = 2147483647;

@@ -41,6 +41,13 @@ enum { MS_NONE = 0, MS_FROM = 1, MS_TO = 2 };
 enum { ERR_LOD0_HIGHER = 1, ERR_NO_CORNERS = 2, ERR_AXIS_UNWRAP = 4 };
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 constexpr uint16_t kNone16 = 0xFFFFu;
+// Map size limits (gswt_worker_create returns GSWT_ERR_CAPACITY beyond them, include/gswt_hip.h).  Every map table is u16 with
+// 0xFFFF as its empty value: edge ids run up to 2 x cells - 1, so 32 767 cells is the largest map whose ids all stay below it.
+// k_w_merge's tables (merge_lds_bytes) must fit kMergeLdsMax of dynamic LDS beside its static 0.5 KB: up to 17 749 cells.
+constexpr size_t kMaxCells = 32767;
+constexpr size_t kMergeLdsMax = 156u * 1024u;
+constexpr size_t kGraphLdsMax = 140u * 1024u;       // k_w_order_seq's graph tables (graph_tab_bytes) in LDS up to this, global memory beyond
+inline size_t merge_lds_bytes(size_t cells) { return (3 * cells + 3 * (cells / 2 + 1)) * sizeof(uint16_t); }
 
 // counters of one sort event (device words)
 enum { C_N_ORDER = 0, C_N_GROUPS, C_N_MEMBERS, C_ERR, C_N_NODES, C_POOL, C_MERGED_LO, C_MERGED_HI, C_COUNT };
@@ -966,8 +973,8 @@ try {
         !cfg->splat_count || !cfg->presort_dirs || !cfg->neighbors || cfg->surface_type > 2 || cfg->tile_sort_type > 3 || cfg->merge_type > 2 ||
         (cfg->surface_type == 1 && (!cfg->height_map || cfg->hm_w == 0 || cfg->hm_h == 0)) || !(cfg->tile_width > 0.0f))
         return bail(GSWT_ERR_BAD_ARG);
-    // u16 tables (map indices, node and edge ids up to 2 x cells) and an edge-merge LDS block of 9 bytes per cell
-    if (cells > 16000 * 2 || 2 * cells >= 65535) return bail(GSWT_ERR_CAPACITY);
+    // u16 tables: map indices and node ids below `cells`, edge ids below 2 x cells, 0xFFFF the empty link (kMaxCells)
+    if (cells > kMaxCells) return bail(GSWT_ERR_CAPACITY);
     if (hipSetDevice(w->device) != hipSuccess) return bail(GSWT_ERR_HIP);
     if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess) return bail(GSWT_ERR_HIP);
     w->cells = (int)cells;
@@ -1026,15 +1033,22 @@ try {
     d.sp.height_map = w->height_map.p; d.lod_dist = w->lod_dist.p; d.tile_center = w->tile_center.p; d.tile_aabb = w->tile_aabb.p;
     d.presort_dirs = w->presort_dirs.p; d.splat_count = w->splat_count.p; d.nb = w->nb.p; d.cell = w->cell.p; d.st = w->st.p;
     d.head_off = w->head_off.p; d.head_len = w->head_len.p; d.pool = w->pool.p; d.counts = w->counts.p;
-    // LDS budgets: the edge-merge tables (9 B per cell) must fit; the graph tables do for small maps and live in global memory otherwise
-    w->lds_merge = (3 * cells + 3 * (cells / 2 + 1)) * sizeof(uint16_t);
-    if (cfg->merge_type == MERGE_EDGE && w->lds_merge > 156u * 1024u) return bail(GSWT_ERR_CAPACITY);
+    // LDS budgets: the edge-merge tables (9 B per cell) must fit; the graph tables do for small maps and live in global memory otherwise.
+    // Only an Edge merge uses k_w_merge's tables: an Axis merge launches it without dynamic LDS, so a map of any accepted size can.
+    w->lds_merge = cfg->merge_type == MERGE_EDGE ? merge_lds_bytes(cells) : 0;
+    if (w->lds_merge > kMergeLdsMax) return bail(GSWT_ERR_CAPACITY);
     w->lds_graph = graph_tab_bytes((int)cells);
-    w->graph_in_lds = w->lds_graph <= 140u * 1024u;     // beside the kernel's 8 KB of static LDS
-    if (w->lds_merge > 48u * 1024u && hipFuncSetAttribute(reinterpret_cast<const void*>(k_w_merge), hipFuncAttributeMaxDynamicSharedMemorySize, (int)w->lds_merge) != hipSuccess)
-        return bail(GSWT_ERR_HIP);
-    if (w->graph_in_lds && w->lds_graph > 48u * 1024u &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_w_order_seq<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)w->lds_graph) != hipSuccess)
+    w->graph_in_lds = w->lds_graph <= kGraphLdsMax;     // beside the kernel's 8 KB of static LDS
+    // A kernel's dynamic-LDS limit is process-wide: it is raised to the budget itself, not to this worker's need, so that a smaller
+    // worker created later does not lower it under a larger one's launches.  (A failed call's error is taken back off the thread,
+    // where the ctx's next launch check would otherwise find it.)
+    auto raise_lds = [](const void* f, size_t bytes) {
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        return false;
+    };
+    if (w->lds_merge > 48u * 1024u && !raise_lds(reinterpret_cast<const void*>(k_w_merge), kMergeLdsMax)) return bail(GSWT_ERR_HIP);
+    if (w->graph_in_lds && w->lds_graph > 48u * 1024u && !raise_lds(reinterpret_cast<const void*>(k_w_order_seq<true>), kGraphLdsMax))
         return bail(GSWT_ERR_HIP);
 #undef WTRY
     guard.w = nullptr;

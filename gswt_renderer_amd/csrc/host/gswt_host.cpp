@@ -211,11 +211,12 @@ void sort_raw_depth(const int32_t* depths, size_t n, uint32_t* order_out)
     int32_t mn = depths[0], mx = depths[0];
     for (size_t i = 1; i < n; i++) { mn = std::min(mn, depths[i]); mx = std::max(mx, depths[i]); }
     const int32_t size16 = 65536;
-    float depth_inv = (float)(size16 - 1) / (float)(int32_t)(mx - mn);
+    // (max - min) and (d - min) wrap as Rust's release-build i32 subtraction does: in u32, where the wrap is defined
+    float depth_inv = (float)(size16 - 1) / (float)(int32_t)((uint32_t)mx - (uint32_t)mn);
     std::vector<uint32_t> counts(size16, 0), starts(size16, 0);
     std::vector<int32_t> bucket(n);
     for (size_t i = 0; i < n; i++) {
-        int32_t d = rust_as_i32(std::floor((float)(int32_t)(depths[i] - mn) * depth_inv));
+        int32_t d = rust_as_i32(std::floor((float)(int32_t)((uint32_t)depths[i] - (uint32_t)mn) * depth_inv));
         d = std::min(std::max(d, 0), size16 - 1);
         bucket[i] = d;
         counts[d]++;

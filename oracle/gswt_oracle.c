@@ -176,14 +176,15 @@ ORC_API void orc_sort_raw_depth(const int32_t *depths, size_t n, uint32_t *order
         if (depths[i] > mx) mx = depths[i];
     }
     const int32_t size16 = 65536;
-    /* (max - min) is an i32 subtraction in Rust (debug builds would panic on
-     * overflow; release wraps).  Raw depths are bounded by 4096*|pos| so no wrap. */
-    float depth_inv = (float)(size16 - 1) / (float)(int32_t)(mx - mn);
+    /* (max - min) and (d - min) are i32 subtractions in Rust: release builds wrap
+     * (a span beyond 2^31 - 1 comes out negative).  Done in u32, where C defines
+     * the wrap, and converted back. */
+    float depth_inv = (float)(size16 - 1) / (float)(int32_t)((uint32_t)mx - (uint32_t)mn);
     uint32_t *counts = (uint32_t *)calloc((size_t)size16, 4);
     uint32_t *starts = (uint32_t *)calloc((size_t)size16, 4);
     int32_t *bucket = (int32_t *)malloc(n * 4);
     for (size_t i = 0; i < n; i++) {
-        float v = floorf((float)(int32_t)(depths[i] - mn) * depth_inv);
+        float v = floorf((float)(int32_t)((uint32_t)depths[i] - (uint32_t)mn) * depth_inv);
         int32_t d = rust_f32_as_i32(v);
         if (d < 0) d = 0;
         if (d > size16 - 1) d = size16 - 1;
