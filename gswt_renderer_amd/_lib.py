@@ -37,6 +37,14 @@ GSWT_OPT_COMPOSITE = 13
 GSWT_OPT_DEPTH_SORT = 14
 GSWT_OPT_NO_CHUNK_CULL = 15
 GSWT_OPT_ITEM_ORDER = 16
+# gswt_debug_read_scene items
+GSWT_SCENE_TEX = 0
+GSWT_SCENE_RAW_DEPTH = 1
+GSWT_SCENE_RAW_TABLES = 2
+GSWT_SCENE_STATIC_LIST = 3
+GSWT_SCENE_STATIC_BOXES = 4
+GSWT_SCENE_LISTS = 5
+GSWT_SCENE_BOUNDS = 6
 GSWT_SHARD_ROWS = 0
 GSWT_SHARD_COLUMNS = 1
 GSWT_OUT_RGBA32F = 0          # RenderConfig.out_format: RGBA f32, 16 bytes per pixel
@@ -172,6 +180,8 @@ SYMBOLS = {
     "gswt_upload_raw_depth": (C.c_int, [_P, _P, _P, _P]),
     "gswt_set_draws_merge_groups": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int]),
     "gswt_debug_read_merged": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gswt_upload_scene_rows": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int]),
+    "gswt_debug_read_scene": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gswt_render": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int]),
     "gswt_render_async": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "gswt_render_wait": (C.c_int, [_P, C.c_int]),

@@ -109,6 +109,15 @@ struct MergeCopy {
     uint32_t src_set;         // which retained draw set holds the source list (MergeSources)
     uint32_t _pad[2];
 };
+// Scene preparation on the device (gswt_upload_scene_rows, gswt_scene.hip).  One static list [lod][tile][view] of the arena: its pair list
+// at pair_base, then its self list; pair_box / self_box: the first chunk box of each in static_boxes (chunk k = the k-th 256 entries from
+// the END of the list, as k_project walks it).  Also the host-side table of gswt_upload_scene.
+struct SceneList { uint32_t pair_base, pair_count, self_base, self_count, pair_box, self_box; };
+constexpr int kSceneMaxViews = 16;
+struct SceneViews {
+    uint32_t n_view;
+    float vp[kSceneMaxViews][16];     // sort_projection * view of every presort view, column-major
+};
 // The merged arrays of the retained draw sets a copy job may read from: the lists of the last kMergeSources - 1 sort events stay
 // addressable, keyed by (view, ordered member tile ids, transition states) -- the reference's LRU of merged lists (wangtile.rs:427,575-593).
 constexpr int kMergeSources = 12;
@@ -288,6 +297,20 @@ void launch_chunk_tabs(hipStream_t s, const DrawDev* draws, const uint32_t* xcd_
 void launch_merge_build(hipStream_t s, const MergeSeg* segs, uint32_t n_segs, const uint2* blocks, uint32_t n_blocks, MergeGroup* groups, uint32_t n_groups,
                         const int32_t* raw, uint32_t n_total, const unsigned long long* n_total_dev, uint32_t* ka, uint32_t* va,
                         uint32_t* kb, uint32_t* vb, uint32_t* radix_ws, int group_bits, uint32_t* merged_list, uint32_t* merged_map);
+// Base lists of one presort view: the k_mg_* keys of gswt_upload_scene_rows' groups (one per (lod, tile)) and the stable radix sort;
+// returns launch_sort's 0 / 1 (sorted keys / vals in ka, va or kb, vb).  Arguments as launch_merge_build.
+int launch_scene_sort(hipStream_t s, const MergeSeg* segs, const uint2* blocks, uint32_t n_blocks, MergeGroup* groups, const int32_t* raw,
+                      uint32_t n_total, const unsigned long long* n_total_dev, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb,
+                      uint32_t* radix_ws, int group_bits);
+// gswt_scene.hip.  bounds: 8 words, {INT_MAX x3, INT_MIN x3, 0, 0} on entry (k_scene_tex).
+void launch_scene_tex(hipStream_t s, const uint4* rows, uint32_t n, uint4* tex, int32_t* bounds);
+void launch_scene_raw(hipStream_t s, const uint4* rows, uint32_t n, const uint32_t* moff, const uint32_t* cnt, uint32_t n_lt, const SceneViews& vps,
+                      int32_t* raw);
+void launch_scene_scatter(hipStream_t s, const MergeSeg* segs, uint32_t n_segs, const MergeGroup* groups, const uint32_t* sorted_keys,
+                          const uint32_t* sorted_vals, uint32_t n_total, uint32_t* arena, uint32_t arena_n);
+void launch_scene_self(hipStream_t s, const SceneList* lists, uint32_t n_lists, uint32_t lists_per_lod, uint32_t* arena);
+void launch_scene_boxes(hipStream_t s, const SceneList* lists, uint32_t n_lists, uint32_t n_boxes, const uint32_t* arena, const uint4* tex,
+                        uint32_t n_splats, float* boxes);
 void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks, uint32_t n_blocks, const uint2* remap, const MergeSources& src,
                        uint32_t* new_list, uint32_t* new_map);
 

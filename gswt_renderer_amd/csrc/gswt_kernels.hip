@@ -2962,6 +2962,16 @@ void launch_merge_build(hipStream_t s, const MergeSeg* segs, uint32_t n_segs, co
                        n_total, merged_list, merged_map);
 }
 
+int launch_scene_sort(hipStream_t s, const MergeSeg* segs, const uint2* blocks, uint32_t n_blocks, MergeGroup* groups, const int32_t* raw,
+                      uint32_t n_total, const unsigned long long* n_total_dev, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb,
+                      uint32_t* radix_ws, int group_bits)
+{
+    if (n_total == 0 || n_blocks == 0) return 0;
+    hipLaunchKernelGGL(k_mg_minmax, dim3(n_blocks), dim3(256), 0, s, segs, blocks, raw, groups);
+    hipLaunchKernelGGL(k_mg_keys, dim3(n_blocks), dim3(256), 0, s, segs, blocks, raw, groups, ka, va);
+    return launch_sort(s, ka, va, kb, vb, n_total, n_total_dev, 16 + group_bits, radix_ws);
+}
+
 void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks, uint32_t n_blocks, const uint2* remap, const MergeSources& src,
                        uint32_t* new_list, uint32_t* new_map)
 {

@@ -51,37 +51,7 @@ int fail(int code, const char* fmt, ...)
     catch (const std::exception& e) { return fail(GSWT_ERR_IO, NAME ": %s", e.what()); }                     \
     catch (...) { return fail(GSWT_ERR_IO, NAME ": unknown exception"); }
 
-// ------------------------------------------------------------------------------------------
-// halves (utils.rs:66-73; half 2.7.1 f16::from_f32, round to nearest even)
-// ------------------------------------------------------------------------------------------
-uint32_t float_to_half(float value)
-{
-    uint32_t x;
-    memcpy(&x, &value, 4);
-    uint32_t sign = x & 0x80000000u, exp = x & 0x7F800000u, man = x & 0x007FFFFFu;
-    if (exp == 0x7F800000u) {
-        uint32_t nan_bit = man == 0 ? 0 : 0x0200u;
-        return (sign >> 16) | 0x7C00u | nan_bit | (man >> 13);
-    }
-    uint32_t half_sign = sign >> 16;
-    int32_t half_exp = (int32_t)(exp >> 23) - 127 + 15;
-    if (half_exp >= 0x1F) return half_sign | 0x7C00u;
-    if (half_exp <= 0) {
-        if (14 - half_exp > 24) return half_sign;
-        man |= 0x00800000u;
-        uint32_t shift = (uint32_t)(14 - half_exp);
-        uint32_t half_man = man >> shift;
-        uint32_t round_bit = 1u << (shift - 1);
-        if ((man & round_bit) != 0 && (man & (3 * round_bit - 1)) != 0) half_man += 1;
-        return half_sign | half_man;
-    }
-    uint32_t half_e = (uint32_t)half_exp << 10, half_man = man >> 13;
-    const uint32_t round_bit = 0x00001000u;
-    if ((man & round_bit) != 0 && (man & (3 * round_bit - 1)) != 0) return (half_sign | half_e | half_man) + 1;
-    return half_sign | half_e | half_man;
-}
-
-uint32_t pack_half_2x16(float x, float y) { return float_to_half(x) | (float_to_half(y) << 16); }
+// (halves, utils.rs:66-73: float_to_half / pack_half_2x16 in gswt_math.h, shared with the device's scene build)
 
 // ------------------------------------------------------------------------------------------
 // scene::Scene (scene.rs:50-57): splat_count + 32 B/splat buffer
@@ -150,48 +120,7 @@ int parse_ply_header(const uint8_t* data, size_t len, size_t* header_size, size_
 // Scene::generate_texture, scene.rs:306-411
 void generate_texture(const uint8_t* rows32, size_t n, uint32_t* tex)
 {
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t* row = rows32 + 32 * i;
-        float fb[6];
-        memcpy(fb, row, 24);
-        uint32_t* t = tex + 8 * i;
-        memcpy(t, row, 12);
-        t[3] = 0;
-        memcpy(&t[7], row + 24, 4);
-        float rot[4];
-        for (int k = 0; k < 4; k++) rot[k] = ((float)row[28 + k] / 255.0f) * 2.0f - 1.0f;
-        float r[9];
-        r[0] = 1.0f - 2.0f * (rot[2] * rot[2] + rot[3] * rot[3]);
-        r[1] = 2.0f * (rot[1] * rot[2] + rot[0] * rot[3]);
-        r[2] = 2.0f * (rot[1] * rot[3] - rot[0] * rot[2]);
-        r[3] = 2.0f * (rot[1] * rot[2] - rot[0] * rot[3]);
-        r[4] = 1.0f - 2.0f * (rot[1] * rot[1] + rot[3] * rot[3]);
-        r[5] = 2.0f * (rot[2] * rot[3] + rot[0] * rot[1]);
-        r[6] = 2.0f * (rot[1] * rot[3] + rot[0] * rot[2]);
-        r[7] = 2.0f * (rot[2] * rot[3] - rot[0] * rot[1]);
-        r[8] = 1.0f - 2.0f * (rot[1] * rot[1] + rot[2] * rot[2]);
-        float m[9];   // r * diag(scale): the products with the zeros of diag() contribute +-0
-        for (int c = 0; c < 3; c++)
-            for (int rr = 0; rr < 3; rr++) {
-                float acc = 0.0f;
-                for (int k = 0; k < 3; k++) {
-                    float sk = (k == c) ? fb[3 + c] : 0.0f;
-                    float term = r[3 * k + rr] * sk;
-                    acc = (k == 0) ? term : acc + term;
-                }
-                m[3 * c + rr] = acc;
-            }
-        float sg[6];
-        sg[0] = m[0] * m[0] + m[3] * m[3] + m[6] * m[6];
-        sg[1] = m[0] * m[1] + m[3] * m[4] + m[6] * m[7];
-        sg[2] = m[0] * m[2] + m[3] * m[5] + m[6] * m[8];
-        sg[3] = m[1] * m[1] + m[4] * m[4] + m[7] * m[7];
-        sg[4] = m[1] * m[2] + m[4] * m[5] + m[7] * m[8];
-        sg[5] = m[2] * m[2] + m[5] * m[5] + m[8] * m[8];
-        t[4] = pack_half_2x16(4.0f * sg[0], 4.0f * sg[1]);
-        t[5] = pack_half_2x16(4.0f * sg[2], 4.0f * sg[3]);
-        t[6] = pack_half_2x16(4.0f * sg[4], 4.0f * sg[5]);
-    }
+    for (size_t i = 0; i < n; i++) generate_texture_row(rows32 + 32 * i, tex + 8 * i);
 }
 
 // raw depth of Scene::sort_self, scene.rs:537-552
@@ -200,7 +129,7 @@ void raw_depth(const Scene& sc, const float* vp, std::vector<int32_t>& out)
     out.resize(sc.splat_count);
     for (size_t i = 0; i < sc.splat_count; i++) {
         const float* p = sc.f(i);
-        out[i] = rust_as_i32((vp[2] * p[0] + vp[6] * p[1] + vp[10] * p[2]) * 4096.0f);
+        out[i] = raw_depth_of(vp, p[0], p[1], p[2]);
     }
 }
 
@@ -526,12 +455,20 @@ struct gswt_wang {
     std::vector<gswt_merge_group> m_groups;
     std::vector<gswt_merge_member> m_members;
     bool device_merge = false;
+    bool rows_only = false;                                 // gswt_wang_new_rows: no texture, raw depths or base lists on the host
+    std::vector<float> presort_vp;                          // [n_view][16] sort_projection * view of every presort view
+    std::vector<const uint8_t*> row_ptrs;                   // gswt_wang_rows tables, [lod * n_tile + tile]
+    std::vector<uint32_t> row_counts, row_offsets;
     std::vector<const int32_t*> rd_ptrs;
     std::vector<uint32_t> rd_counts, rd_offsets;
     std::vector<float> wk_center, wk_aabb, wk_dirs;          // flat tables of gswt_wang_worker_config
     std::vector<uint32_t> wk_counts;
     std::vector<int32_t> wk_nb;
 
+    // splats of tile scene (l, t), and the length of its base lists (that LOD followed by the next one, wangtile.rs:221-252):
+    // what the base lists' sizes are on a full wang, derived from the counts alone so that a rows-only wang has them too
+    size_t cnt(size_t l, size_t t) const { return tiles[l][t].splat_count; }
+    size_t list_len(size_t l, size_t t) const { return cnt(l, t) + (l + 1 < n_lod ? cnt(l + 1, t) : 0); }
     TileBaseData& tb(size_t l, size_t t, size_t v) { return base[(l * n_tile + t) * n_view + v]; }
     const TileBaseData& tb(size_t l, size_t t, size_t v) const { return base[(l * n_tile + t) * n_view + v]; }
     TileInstance* at(int x, int y) { return tile_map[(size_t)x * map_h + y].get(); }
@@ -562,7 +499,9 @@ SurfaceParams surface_params(const gswt_wang& w)
 }
 
 // ---- WangTile::preprocess, wangtile.rs:71-255 ---------------------------------------------
-int preprocess(gswt_wang& w)
+// full = false (gswt_wang_new_rows): everything but generate_texture, the raw depths and the base lists, which
+// gswt_upload_scene_rows builds on the device
+int preprocess(gswt_wang& w, bool full)
 {
     w.n_lod = w.tiles.size();
     w.n_tile = w.tiles[0].size();
@@ -604,10 +543,12 @@ int preprocess(gswt_wang& w)
     for (size_t l = 0; l < w.n_lod; l++)
         for (size_t t = 0; t < w.n_tile; t++) { w.merge_offset[l][t] = (uint32_t)total; total += w.tiles[l][t].splat_count; }
     w.merged_count = total;
-    w.tex.assign(8 * total, 0);
-    for (size_t l = 0; l < w.n_lod; l++)
-        for (size_t t = 0; t < w.n_tile; t++)
-            generate_texture(w.tiles[l][t].buffer.data(), w.tiles[l][t].splat_count, w.tex.data() + 8 * (size_t)w.merge_offset[l][t]);
+    if (full) {
+        w.tex.assign(8 * total, 0);
+        for (size_t l = 0; l < w.n_lod; l++)
+            for (size_t t = 0; t < w.n_tile; t++)
+                generate_texture(w.tiles[l][t].buffer.data(), w.tiles[l][t].splat_count, w.tex.data() + 8 * (size_t)w.merge_offset[l][t]);
+    }
     // avg scale, :128-142
     w.lod_avg_scale.clear();
     for (size_t l = 0; l < w.n_lod; l++) {
@@ -630,21 +571,21 @@ int preprocess(gswt_wang& w)
     float proj[16];
     perspective(90.0f, 1.0f, 0.1f, 10.0f, proj);
     w.presort_dirs.clear();
-    std::vector<std::vector<float>> vps;
+    w.presort_vp.assign(9 * 16, 0.0f);
     for (int k = 0; k < 9; k++) {
         V3 d = normalize(V3{raw[k][0], raw[k][1], raw[k][2]});
         w.presort_dirs.push_back(d);
-        float view[16], vp[16];
+        float view[16];
         V3 up = (d.x != 0.0f || d.y != 0.0f) ? V3{0, 0, 1} : V3{0, 1, 0};
         look_at_rh(V3{0, 0, 0}, d, up, view);
-        mat4_mul(proj, view, vp);
-        vps.emplace_back(vp, vp + 16);
+        mat4_mul(proj, view, w.presort_vp.data() + 16 * k);
     }
     w.n_view = 9;
+    if (!full) return GSWT_OK;
     w.base.assign(w.n_lod * w.n_tile * w.n_view, TileBaseData{});
     for (size_t l = 0; l < w.n_lod; l++)
         for (size_t t = 0; t < w.n_tile; t++)
-            for (size_t k = 0; k < w.n_view; k++) raw_depth(w.tiles[l][t], vps[k].data(), w.tb(l, t, k).raw_depth);
+            for (size_t k = 0; k < w.n_view; k++) raw_depth(w.tiles[l][t], w.presort_vp.data() + 16 * k, w.tb(l, t, k).raw_depth);
     // base lists, :221-252
     std::vector<int32_t> cat;
     std::vector<uint32_t> order;
@@ -1422,17 +1363,54 @@ try {
     auto* w = new gswt_wang();
     w->tiles = std::move(ts->s);
     delete ts;
-    int rc = preprocess(*w);
+    int rc = preprocess(*w, true);
     if (rc) { delete w; return rc; }
     *out = w;
     return GSWT_OK;
 } GSWT_CATCH("gswt_wang_new")
+
+int gswt_wang_new_rows(gswt_tileset* ts, gswt_wang** out)
+try {
+    if (!ts || !out) return fail(GSWT_ERR_BAD_ARG, "gswt_wang_new_rows: null argument");
+    auto* w = new gswt_wang();
+    w->tiles = std::move(ts->s);
+    delete ts;
+    w->rows_only = true;
+    w->device_merge = true;
+    int rc = preprocess(*w, false);
+    if (rc) { delete w; return rc; }
+    *out = w;
+    return GSWT_OK;
+} GSWT_CATCH("gswt_wang_new_rows")
+
+int gswt_wang_rows(gswt_wang* w, const uint8_t* const** rows, const uint32_t** counts, const uint32_t** merge_offset)
+try {
+    if (!w || !rows || !counts || !merge_offset) return fail(GSWT_ERR_BAD_ARG, "gswt_wang_rows: null argument");
+    w->row_ptrs.clear(); w->row_counts.clear(); w->row_offsets.clear();
+    for (size_t l = 0; l < w->n_lod; l++)
+        for (size_t t = 0; t < w->n_tile; t++) {
+            w->row_ptrs.push_back(w->tiles[l][t].buffer.data());
+            w->row_counts.push_back((uint32_t)w->cnt(l, t));
+            w->row_offsets.push_back(w->merge_offset[l][t]);
+        }
+    *rows = w->row_ptrs.data(); *counts = w->row_counts.data(); *merge_offset = w->row_offsets.data();
+    return GSWT_OK;
+} GSWT_CATCH("gswt_wang_rows")
+
+int gswt_wang_presort_view_proj(const gswt_wang* w, float* out, int cap)
+try {
+    if (!w || !out) return fail(GSWT_ERR_BAD_ARG, "gswt_wang_presort_view_proj: null argument");
+    if (cap < (int)w->presort_vp.size()) return fail(GSWT_ERR_CAPACITY, "gswt_wang_presort_view_proj: need %zu floats", w->presort_vp.size());
+    memcpy(out, w->presort_vp.data(), w->presort_vp.size() * sizeof(float));
+    return (int)w->n_view;
+} GSWT_CATCH("gswt_wang_presort_view_proj")
 
 void gswt_wang_destroy(gswt_wang* w) { delete w; }
 
 int gswt_wang_preload(gswt_wang* w, gswt_preload* out)
 try {
     if (!w || !out) return GSWT_ERR_BAD_ARG;
+    if (w->rows_only) return fail(GSWT_ERR_STATE, "gswt_wang_preload: a rows-only wang has no texture or base lists (gswt_upload_scene_rows builds them)");
     out->tex_data = w->tex.data();
     out->n_splats = w->merged_count;
     out->n_lod = (int)w->n_lod; out->n_tile = (int)w->n_tile; out->n_view = (int)w->n_view;
@@ -1458,6 +1436,11 @@ try {
 
 const int32_t* gswt_wang_raw_depth(const gswt_wang* w, int lod, int tile, int view, size_t* n)
 {
+    if (w && w->rows_only) {
+        fail(GSWT_ERR_STATE, "gswt_wang_raw_depth: a rows-only wang has no raw depths");
+        if (n) *n = 0;
+        return nullptr;
+    }
     const auto& rd = w->tb(lod, tile, view).raw_depth;
     if (n) *n = rd.size();
     return rd.data();
@@ -1559,12 +1542,12 @@ try {
         for (int i = 0; i < w->map_w; i++)
             for (int j = 0; j < w->map_h; j++) {
                 const TileInstance* ti = w->at(i, j);
-                size_t c = w->tb(ti->lod, ti->tile, 0).splat_count;
+                size_t c = w->list_len(ti->lod, ti->tile);
                 out->splat_count += c; out->blending_splat_count += c;
                 out->lod_splat_count[ti->lod] += c; out->lod_instance_count[ti->lod] += 1;
                 bool blend_lower = ti->lod < w->n_lod - 1;
-                if (ti->transition == TR_CHANGING_HIGHER) { out->blending_splat_count += w->tb(ti->lod - 1, ti->tile, 0).splat_count; blend_lower = false; }
-                if (blend_lower) out->blending_splat_count += w->tb(ti->lod + 1, ti->tile, 0).splat_count;
+                if (ti->transition == TR_CHANGING_HIGHER) { out->blending_splat_count += w->list_len(ti->lod - 1, ti->tile); blend_lower = false; }
+                if (blend_lower) out->blending_splat_count += w->list_len(ti->lod + 1, ti->tile);
             }
     }
     return GSWT_OK;
@@ -1580,6 +1563,7 @@ try {
 int gswt_wang_raw_depth_tables(gswt_wang* w, const int32_t* const** ptrs, const uint32_t** counts, const uint32_t** merge_offset)
 try {
     if (!w || !ptrs || !counts || !merge_offset) return GSWT_ERR_BAD_ARG;
+    if (w->rows_only) return fail(GSWT_ERR_STATE, "gswt_wang_raw_depth_tables: a rows-only wang has no raw depths (gswt_upload_scene_rows builds them)");
     w->rd_ptrs.clear(); w->rd_counts.clear(); w->rd_offsets.clear();
     for (size_t l = 0; l < w->n_lod; l++)
         for (size_t t = 0; t < w->n_tile; t++) {
@@ -1618,7 +1602,7 @@ try {
         w->wk_aabb.insert(w->wk_aabb.end(), {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z});
     }
     for (size_t l = 0; l < w->n_lod; l++)
-        for (size_t t = 0; t < w->n_tile; t++) w->wk_counts.push_back((uint32_t)w->tb(l, t, 0).raw_depth.size());
+        for (size_t t = 0; t < w->n_tile; t++) w->wk_counts.push_back((uint32_t)w->cnt(l, t));
     for (const V3& d : w->presort_dirs) w->wk_dirs.insert(w->wk_dirs.end(), {d.x, d.y, d.z});
     for (int x = 0; x < w->map_w; x++)
         for (int y = 0; y < w->map_h; y++)
@@ -1710,6 +1694,8 @@ int gswt_wang_sort_tiles(gswt_wang* w, const float cam_pos[3], const float vp[16
 try {
     if (!w || !cam_pos || !vp || !out) return fail(GSWT_ERR_BAD_ARG, "gswt_wang_sort_tiles: null argument");
     if (!w->initialized) return fail(GSWT_ERR_STATE, "WangTile::sort_tiles before build_tiles");
+    if (w->rows_only && !w->device_merge)
+        return fail(GSWT_ERR_STATE, "gswt_wang_sort_tiles: a rows-only wang has no host base lists; merged lists need device merge");
     const bool need_corner = w->user.tile_sort_type == SORT_GRAPH || w->user.merge_type == MERGE_EDGE;
     (void)need_corner;
     V3 cam{cam_pos[0], cam_pos[1], cam_pos[2]};
@@ -1783,8 +1769,8 @@ try {
                 if (mt->transition == TR_CHANGING_LOWER) mm.other_lod = (int32_t)mt->lod + 1;
                 else if (mt->transition == TR_CHANGING_HIGHER) mm.other_lod = (int32_t)mt->lod - 1;
                 if (mt->transition != TR_NONE) do_transition = true;
-                group_len += w->tb(mt->lod, mt->tile, view_id).raw_depth.size();
-                if (mm.other_lod >= 0) group_len += w->tb((size_t)mm.other_lod, mt->tile, view_id).raw_depth.size();
+                group_len += w->cnt(mt->lod, mt->tile);
+                if (mm.other_lod >= 0) group_len += w->cnt((size_t)mm.other_lod, mt->tile);
                 w->m_members.push_back(mm);
             }
             st.merged = 1;

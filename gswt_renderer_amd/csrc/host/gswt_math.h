@@ -156,4 +156,85 @@ GSWT_HD inline uint8_t rust_as_u8(float v)
     return (uint8_t)v;
 }
 
+// ---- scene preparation, shared by libgswt_host (WangTile::preprocess) and libgswt_hip (gswt_upload_scene_rows) ----------------
+
+// half 2.7.1 f16::from_f32 (round to nearest even), utils.rs:66-73
+GSWT_HD inline uint32_t float_to_half(float value)
+{
+    uint32_t x;
+    memcpy(&x, &value, 4);
+    uint32_t sign = x & 0x80000000u, exp = x & 0x7F800000u, man = x & 0x007FFFFFu;
+    if (exp == 0x7F800000u) {
+        uint32_t nan_bit = man == 0 ? 0 : 0x0200u;
+        return (sign >> 16) | 0x7C00u | nan_bit | (man >> 13);
+    }
+    uint32_t half_sign = sign >> 16;
+    int32_t half_exp = (int32_t)(exp >> 23) - 127 + 15;
+    if (half_exp >= 0x1F) return half_sign | 0x7C00u;
+    if (half_exp <= 0) {
+        if (14 - half_exp > 24) return half_sign;
+        man |= 0x00800000u;
+        uint32_t shift = (uint32_t)(14 - half_exp);
+        uint32_t half_man = man >> shift;
+        uint32_t round_bit = 1u << (shift - 1);
+        if ((man & round_bit) != 0 && (man & (3 * round_bit - 1)) != 0) half_man += 1;
+        return half_sign | half_man;
+    }
+    uint32_t half_e = (uint32_t)half_exp << 10, half_man = man >> 13;
+    const uint32_t round_bit = 0x00001000u;
+    if ((man & round_bit) != 0 && (man & (3 * round_bit - 1)) != 0) return (half_sign | half_e | half_man) + 1;
+    return half_sign | half_e | half_man;
+}
+
+GSWT_HD inline uint32_t pack_half_2x16(float x, float y) { return float_to_half(x) | (float_to_half(y) << 16); }
+
+// One splat of Scene::generate_texture, scene.rs:306-411: 32-byte row -> 8 u32 texture words
+GSWT_HD inline void generate_texture_row(const uint8_t* row, uint32_t* t)
+{
+    float fb[6];
+    memcpy(fb, row, 24);
+    memcpy(t, row, 12);
+    t[3] = 0;
+    memcpy(&t[7], row + 24, 4);
+    float rot[4];
+    for (int k = 0; k < 4; k++) rot[k] = ((float)row[28 + k] / 255.0f) * 2.0f - 1.0f;
+    float r[9];
+    r[0] = 1.0f - 2.0f * (rot[2] * rot[2] + rot[3] * rot[3]);
+    r[1] = 2.0f * (rot[1] * rot[2] + rot[0] * rot[3]);
+    r[2] = 2.0f * (rot[1] * rot[3] - rot[0] * rot[2]);
+    r[3] = 2.0f * (rot[1] * rot[2] - rot[0] * rot[3]);
+    r[4] = 1.0f - 2.0f * (rot[1] * rot[1] + rot[3] * rot[3]);
+    r[5] = 2.0f * (rot[2] * rot[3] + rot[0] * rot[1]);
+    r[6] = 2.0f * (rot[1] * rot[3] + rot[0] * rot[2]);
+    r[7] = 2.0f * (rot[2] * rot[3] - rot[0] * rot[1]);
+    r[8] = 1.0f - 2.0f * (rot[1] * rot[1] + rot[2] * rot[2]);
+    float m[9];   // r * diag(scale): the products with the zeros of diag() contribute +-0
+    for (int c = 0; c < 3; c++)
+        for (int rr = 0; rr < 3; rr++) {
+            float acc = 0.0f;
+            for (int k = 0; k < 3; k++) {
+                float sk = (k == c) ? fb[3 + c] : 0.0f;
+                float term = r[3 * k + rr] * sk;
+                acc = (k == 0) ? term : acc + term;
+            }
+            m[3 * c + rr] = acc;
+        }
+    float sg[6];
+    sg[0] = m[0] * m[0] + m[3] * m[3] + m[6] * m[6];
+    sg[1] = m[0] * m[1] + m[3] * m[4] + m[6] * m[7];
+    sg[2] = m[0] * m[2] + m[3] * m[5] + m[6] * m[8];
+    sg[3] = m[1] * m[1] + m[4] * m[4] + m[7] * m[7];
+    sg[4] = m[1] * m[2] + m[4] * m[5] + m[7] * m[8];
+    sg[5] = m[2] * m[2] + m[5] * m[5] + m[8] * m[8];
+    t[4] = pack_half_2x16(4.0f * sg[0], 4.0f * sg[1]);
+    t[5] = pack_half_2x16(4.0f * sg[2], 4.0f * sg[3]);
+    t[6] = pack_half_2x16(4.0f * sg[4], 4.0f * sg[5]);
+}
+
+// raw depth of one splat centre for a presort view (Scene::sort_self, scene.rs:537-552)
+GSWT_HD inline int32_t raw_depth_of(const float* vp, float x, float y, float z)
+{
+    return rust_as_i32((vp[2] * x + vp[6] * y + vp[10] * z) * 4096.0f);
+}
+
 }  // namespace gswt_host

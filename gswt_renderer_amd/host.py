@@ -112,6 +112,9 @@ HOST_SYMBOLS = {
     "gswt_wang_new": (C.c_int, [_P, C.POINTER(_P)]),
     "gswt_wang_destroy": (None, [_P]),
     "gswt_wang_preload": (C.c_int, [_P, _P]),
+    "gswt_wang_new_rows": (C.c_int, [_P, C.POINTER(_P)]),
+    "gswt_wang_rows": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "gswt_wang_presort_view_proj": (C.c_int, [_P, _P, C.c_int]),
     "gswt_wang_tile_base": (C.c_int, [_P, C.c_int, _P, _P]),
     "gswt_wang_lod_avg_scale": (C.c_int, [_P, _P, C.c_int]),
     "gswt_wang_raw_depth": (_P, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
@@ -263,21 +266,54 @@ class SortData:
 class WangTile:
     """wangtile.rs:18-39"""
 
-    def __init__(self, tileset: TileSet):
-        """WangTile::new (takes ownership of the tile set) -> preprocess."""
+    def __init__(self, tileset: TileSet, rows_only: bool = False):
+        """WangTile::new (takes ownership of the tile set) -> preprocess.  rows_only: gswt_wang_new_rows -- the texture, raw
+        depths and base lists are left to the device (GSWTRenderer.upload_scene_rows); device merge is on."""
         lib = load()
         h = C.c_void_p()
+        self._n_lod, self._n_tile = tileset.dims() if tileset._h else (0, 0)
         th, tileset._h = tileset._h, None      # gswt_wang_new consumes the tile set, also when it fails
-        _check(lib.gswt_wang_new(th, C.byref(h)))
+        _check((lib.gswt_wang_new_rows if rows_only else lib.gswt_wang_new)(th, C.byref(h)))
         self._h = h
         self._lib = lib
+        self.rows_only = rows_only
         self.user = None
         self.conf = None
         self.scene_data = None
-        p = Preload()
-        _check(lib.gswt_wang_preload(h, C.byref(p)))
-        self.n_tiles = (p.n_lod, p.n_tile, p.n_view)
-        self._preload = p
+        if rows_only:
+            self._preload = None
+            n_view = _check(lib.gswt_wang_presort_view_proj(h, (C.c_float * 256)(), 256))
+            self.n_tiles = (self._n_lod, self._n_tile, n_view)
+        else:
+            p = Preload()
+            _check(lib.gswt_wang_preload(h, C.byref(p)))
+            self.n_tiles = (p.n_lod, p.n_tile, p.n_view)
+            self._preload = p
+
+    def _need_host_lists(self, what):
+        """The texture, raw depths and base lists exist on the host only for a full wang."""
+        if self.rows_only:
+            raise GSWTHostError(L.GSWT_ERR_STATE, f"WangTile.{what}: a rows-only wang has no host texture, raw depths or base lists "
+                                                  "(GSWTRenderer.upload_scene_rows builds them on the device)")
+
+    def rows_tables(self):
+        """gswt_wang_rows: (row pointers, counts, merge offsets) ctypes arrays, [lod * n_tile + tile]."""
+        rows, cnts, offs = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self._lib.gswt_wang_rows(self._h, C.byref(rows), C.byref(cnts), C.byref(offs)))
+        n = self._n_lod * self._n_tile
+        return (C.cast(rows, C.POINTER(C.c_void_p * n)).contents, C.cast(cnts, C.POINTER(C.c_uint32 * n)).contents,
+                C.cast(offs, C.POINTER(C.c_uint32 * n)).contents)
+
+    def rows(self, lod, tile) -> np.ndarray:
+        """The normalised 32-byte rows of tile scene (lod, tile) (a copy), [n, 32] u8."""
+        rows, cnts, _ = self.rows_tables()
+        k = lod * self._n_tile + tile
+        return np.ctypeslib.as_array(C.cast(rows[k], C.POINTER(C.c_uint8)), shape=(cnts[k], 32)).copy()
+
+    def presort_view_proj(self) -> np.ndarray:
+        out = (C.c_float * 256)()
+        n = _check(self._lib.gswt_wang_presort_view_proj(self._h, out, 256))
+        return np.array(out[:16 * n], dtype=np.float32).reshape(n, 16)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -293,6 +329,7 @@ class WangTile:
     # -- preload() ------------------------------------------------------------------
     def preload(self):
         """PreloadData: (tex_data [U,8] u32 view, gs_index[lod][tile][view], gs_lod_id[...])."""
+        self._need_host_lists("preload")
         p = self._preload
         tex = np.ctypeslib.as_array(C.cast(p.tex_data, C.POINTER(C.c_uint32)), shape=(p.n_splats, 8))
         gi, li = [], []
@@ -315,12 +352,17 @@ class WangTile:
 
     def upload_raw_depth_to(self, renderer):
         """gswt_upload_raw_depth with this WangTile's raw-depth tables (needed for device-side merged lists)."""
+        self._need_host_lists("upload_raw_depth_to")
         ptrs, cnts, offs = C.c_void_p(), C.c_void_p(), C.c_void_p()
         _check(self._lib.gswt_wang_raw_depth_tables(self._h, C.byref(ptrs), C.byref(cnts), C.byref(offs)))
         renderer._check(renderer._lib.gswt_upload_raw_depth(renderer._h, ptrs, cnts, offs))
 
     def upload_to(self, renderer):
-        """GSWTRenderer::new(preload_data): hand the PreloadData pointers straight to libgswt_hip."""
+        """GSWTRenderer::new(preload_data): hand the PreloadData pointers straight to libgswt_hip (a rows-only wang: the
+        device build, GSWTRenderer.upload_scene_rows)."""
+        if self.rows_only:
+            renderer.upload_scene_rows(self)
+            return
         p = self._preload
         renderer._check(renderer._lib.gswt_upload_scene(renderer._h, p.tex_data, p.n_splats, p.lists, p.n_lod, p.n_tile, p.n_view))
         renderer.n_lists = self.n_tiles
@@ -337,6 +379,7 @@ class WangTile:
         return np.array(out[:n], dtype=np.float32)
 
     def raw_depth(self, lod, tile, view):
+        self._need_host_lists("raw_depth")
         n = C.c_size_t()
         p = self._lib.gswt_wang_raw_depth(self._h, lod, tile, view, C.byref(n))
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), shape=(n.value,)).copy()

@@ -13,16 +13,20 @@ from .renderer import GSWTRenderer
 
 class GSWTPipeline:
     def __init__(self, verts_or_zip, user: host.UserData, device_id: int = 0, renderer: GSWTRenderer | None = None,
-                 device_merge: bool = False):
+                 device_merge: bool = False, device_preprocess: bool = False):
         if isinstance(verts_or_zip, (str, bytes, bytearray)):
             ts = host.TileSet.from_zip(verts_or_zip)
         else:
             ts = host.TileSet.from_vertices(verts_or_zip)
-        self.wang = host.WangTile(ts)                      # State::new: WangTile::new(scene_vec)
+        # device_preprocess: the texture, raw depths and base lists are built on the GPU from the rows (implies device_merge)
+        self.wang = host.WangTile(ts, rows_only=device_preprocess)   # State::new: WangTile::new(scene_vec)
         self.renderer = renderer or GSWTRenderer(device_id)
-        self.wang.upload_to(self.renderer)                 # GSWTRenderer::new(.., wang.preload())
-        self.device_merge = device_merge
-        if device_merge:                                   # merged-group lists are then built on the GPU per sort event
+        self.device_merge = device_merge or device_preprocess
+        if device_preprocess:
+            self.renderer.upload_scene_rows(self.wang)     # GSWTRenderer::new(.., wang.preload()), built on the device
+        else:
+            self.wang.upload_to(self.renderer)             # GSWTRenderer::new(.., wang.preload())
+        if device_merge and not device_preprocess:         # merged-group lists are then built on the GPU per sort event
             self.wang.upload_raw_depth_to(self.renderer)
             self.wang.set_device_merge(True)
         self.configure(user)

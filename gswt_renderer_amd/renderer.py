@@ -109,6 +109,23 @@ class GSWTRenderer:
         self._check(self._lib.gswt_upload_scene(self._h, _ptr(tex), tex.shape[0], arr, n_lod, n_tile, n_view))
         self.n_lists = (n_lod, n_tile, n_view)
 
+    def upload_scene_rows(self, wang):
+        """GSWTRenderer::new from a rows-only WangTile: the texture, raw depths, base lists and static arena are built on the
+        device from the normalised rows (gswt_upload_scene_rows); device-side merged lists work right after it."""
+        rows, cnts, _ = wang.rows_tables()
+        n_lod, n_tile, n_view = wang.n_tiles
+        vp = np.ascontiguousarray(wang.presort_view_proj(), dtype=np.float32)
+        self._check(self._lib.gswt_upload_scene_rows(self._h, rows, cnts, n_lod, n_tile, _ptr(vp), n_view))
+        self.n_lists = (n_lod, n_tile, n_view)
+
+    def read_scene(self, what: int) -> bytes:
+        """gswt_debug_read_scene: one item of the device's scene state (L.GSWT_SCENE_*) as raw bytes."""
+        n = C.c_size_t()
+        self._check(self._lib.gswt_debug_read_scene(self._h, what, None, 0, C.byref(n)))
+        buf = (C.c_uint8 * max(1, n.value))()
+        self._check(self._lib.gswt_debug_read_scene(self._h, what, buf, n.value, C.byref(n)))
+        return bytes(buf[:n.value])
+
     # -- GSWTRenderer::configure (renderer.rs:351) -----------------------------------
     def configure(self, height_map: np.ndarray | None):
         if height_map is None:

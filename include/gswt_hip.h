@@ -267,6 +267,24 @@ GSWT_API int gswt_upload_raw_depth(gswt_ctx *ctx, const int32_t *const *raw_dept
 GSWT_API int gswt_set_draws_merge_groups(gswt_ctx *ctx, const gswt_draw *draws, int n_draws,
                                          const gswt_merge_group *groups, int n_groups,
                                          const gswt_merge_member *members, int n_members);
+/* GSWTRenderer::new from a rows-only wang (gswt_wang_new_rows): uploads the normalised 32-byte rows of every tile scene
+ * (rows32 / counts [n_lod*n_tile], lod-major; gswt_wang_rows) and builds on the device what gswt_upload_scene(preload) +
+ * gswt_upload_raw_depth(raw_depth_tables) of a full wang leave behind, bit for bit: the texture (generate_texture), the raw
+ * depths of every presort view, the base lists (sort_raw_depth of each tile's LOD followed by the next LOD), the static
+ * arena with its pair and self lists, their 256-entry chunk boxes and the tile-local bounds.  presort_vp: the n_view
+ * sort_projection * view matrices (gswt_wang_presort_view_proj), n_view <= 16.  gswt_set_draws_merge_groups works right
+ * after it.  Refused before anything is enqueued: null rows, an empty tile scene, n_lod > 16, more than 2^28 splats, more
+ * than 65 536 (lod, tile) lists (the list id takes 16 bits of the sort key).  Returns when the build has finished. */
+GSWT_API int gswt_upload_scene_rows(gswt_ctx *ctx, const uint8_t *const *rows32, const uint32_t *counts, int n_lod, int n_tile,
+                                    const float *presort_vp, int n_view);
+/* Test hook: reads back one item of the scene state for comparing two contexts.  n_bytes receives its size; out may be
+ * NULL to ask for the size only.  Items: the texture (32 B per splat), the raw-depth arena (i32), its tables (raw_off
+ * [n_lod*n_tile*n_view], counts, merge offsets [n_lod*n_tile], u32), the static arena (u32), the chunk boxes (6 f32 each),
+ * the list table (pair_base, pair_count, self_base, self_count, pair_box, self_box: 6 u32 per list [lod][tile][view]), the
+ * local bounds (lo.xyz, hi.xyz, largest covariance bound: 7 f32). */
+enum { GSWT_SCENE_TEX = 0, GSWT_SCENE_RAW_DEPTH = 1, GSWT_SCENE_RAW_TABLES = 2, GSWT_SCENE_STATIC_LIST = 3, GSWT_SCENE_STATIC_BOXES = 4,
+       GSWT_SCENE_LISTS = 5, GSWT_SCENE_BOUNDS = 6 };
+GSWT_API int gswt_debug_read_scene(gswt_ctx *ctx, int what, void *out, size_t cap_bytes, size_t *n_bytes);
 /* Test hook: the device-resident merged arrays (gs_index | lod << 28, map id), n entries each. Host pointers. */
 GSWT_API int gswt_debug_read_merged(gswt_ctx *ctx, uint32_t *packed_list, uint32_t *map_id, size_t capacity, size_t *n);
 

@@ -124,6 +124,19 @@ typedef struct {
  * set is destroyed either way), runs preprocess. */
 GSWT_API int gswt_wang_new(gswt_tileset *ts, gswt_wang **out);
 GSWT_API void gswt_wang_destroy(gswt_wang *w);
+/* WangTile::new without the heavy half of preprocess: tile AABBs and centres, the rows' height normalisation, merge
+ * offsets, LOD average scales and the presort views, exactly as gswt_wang_new computes them; generate_texture, the raw
+ * depths and the base lists are left to the device (gswt_upload_scene_rows).  Takes ownership of the tile set like
+ * gswt_wang_new.  Device merge is on from the start.  On such a wang gswt_wang_preload, gswt_wang_raw_depth_tables and
+ * gswt_wang_sort_tiles without device merge return GSWT_ERR_STATE, gswt_wang_raw_depth returns NULL (n = 0); each sets
+ * gswt_host_last_error.  Everything else behaves as on a full wang. */
+GSWT_API int gswt_wang_new_rows(gswt_tileset *ts, gswt_wang **out);
+/* The normalised 32-byte rows of every tile scene (the bytes generate_texture / the raw depths read), their splat counts
+ * and merge offsets, each indexed [lod*n_tile+tile].  Pointers valid until the wang is destroyed. */
+GSWT_API int gswt_wang_rows(gswt_wang *w, const uint8_t *const **rows, const uint32_t **counts, const uint32_t **merge_offset);
+/* The n_view sort_projection * view matrices of the presort views (wangtile.rs:144-174), 16 floats each, column-major.
+ * cap: floats out holds.  Returns n_view. */
+GSWT_API int gswt_wang_presort_view_proj(const gswt_wang *w, float *out, int cap);
 /* WangTile::preload (wangtile.rs:340-347) */
 GSWT_API int gswt_wang_preload(gswt_wang *w, gswt_preload *out);
 /* preprocess outputs used by tests: per-tile centre / aabb, per-LOD avg scale, raw depths */
