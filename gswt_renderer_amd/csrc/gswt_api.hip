@@ -195,6 +195,7 @@ struct FrameArgs {
     const float4* d_bg = nullptr;
     const float* d_bgd = nullptr;
     float4* d_out = nullptr;
+    float* d_out_depth = nullptr;          // gswt_render_depth / gswt_render_async_depth: the frame's depth image (null: none)
 };
 
 // A frame's events on its slot's stream.  GSWT_OPT_TIMING >= 1 records kEvStart, kEvEnd and the compositor kernel's pair, 2 also the
@@ -239,8 +240,9 @@ struct FrameSlot {
     bool full_grid = false;                // this (re-run) frame launches k_project / k_emit over the whole launch table, whatever the hint says
     uint32_t n_launch_eff = 0;             // positions of the launch table this frame's grids cover
     DevBuf<float4> partials;
+    DevBuf<float> partials_z;              // frames that write their depth: a segment's partial depth beside its partial colour
     DevBuf<float4> col_f;                  // debug draw modes: float colours per slot
-    DevBuf<float> depths;                  // per-slot depth: frames with a proxy depth buffer or GSWT_ORDER_DEPTH only
+    DevBuf<float> depths;                  // per-slot depth: frames with a proxy depth buffer, GSWT_ORDER_DEPTH or a depth image only
     // hipGraph replay (GSWT_OPT_GRAPH): the chain of kernel nodes of this slot's frames and the argument records they were last set to
     GraphRec grec;
     hipGraph_t graph = nullptr;
@@ -258,7 +260,7 @@ struct FrameSlot {
     {
         rects.release(); recs.release(); cell_culled.release(); live_tab.release(); live_cid.release(); live_cnt.release(); block_sums.release(); draw_culled.release(); keys_a.release();
         keys_b.release(); vals_a.release(); vals_b.release(); ghist.release(); ranges.release(); item_base.release();
-        aux_a.release(); aux_b.release(); partials.release(); item_tab.release(); col_f.release(); depths.release();
+        aux_a.release(); aux_b.release(); partials.release(); partials_z.release(); item_tab.release(); col_f.release(); depths.release();
     }
 };
 
@@ -341,7 +343,7 @@ struct gswt_ctx {
     unsigned long long stat_depth_local = 0, stat_depth_global = 0;     // depth-ordered frames enqueued on either path (re-runs included)
     int last_slot = 0;
     DevBuf<float4> bg_rgba, out_img;
-    DevBuf<float> bg_depth;
+    DevBuf<float> bg_depth, out_depth_img;       // (gswt_render's staging of host images)
     DevBuf<Varyings> dbg;
     // options
     int opt_no_prefilter = 0;
@@ -594,7 +596,7 @@ void gswt_destroy(gswt_ctx* c)
     c->gather_buf.release();
     c->tex.release(); c->static_list.release(); c->static_boxes.release(); c->hmap.release(); for (auto& ds : c->sets) ds.release();
     c->raw_depth.release(); 
-    c->mg_ws.release(); c->sky_faces.release(); c->proxy_tex.release(); c->bg_rgba.release(); c->out_img.release(); c->bg_depth.release(); c->dbg.release();
+    c->mg_ws.release(); c->sky_faces.release(); c->proxy_tex.release(); c->bg_rgba.release(); c->out_img.release(); c->bg_depth.release(); c->out_depth_img.release(); c->dbg.release();
     for (auto& sl : c->slots) {
         sl.release_graph();
         sl.release_buffers();
@@ -1605,7 +1607,7 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
 {
     const FrameArgs& a = sl.args;
     const size_t nt = (size_t)n_tiles, n_slots_all = (size_t)D.n_chunks * kChunk;
-    const bool depth_order = a.cfg.order_mode == GSWT_ORDER_DEPTH, need_depths = a.d_bgd != nullptr || depth_order;
+    const bool depth_order = a.cfg.order_mode == GSWT_ORDER_DEPTH, need_depths = a.d_bgd != nullptr || depth_order || a.d_out_depth != nullptr;
     const uint32_t seg = (uint32_t)c->opt_segment;
     b.n_cells = f.band_cull ? (2u * f.map_half_wh[0] + 1u) * (2u * f.map_half_wh[1] + 1u) : 0u;
     HIP_TRY(c, sl.rects.ensure(n_slots_all + 1));
@@ -1642,12 +1644,13 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     if (depth_order) { HIP_TRY(c, sl.aux_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.aux_b.ensure_roomy((size_t)cap + 1)); }
     HIP_TRY(c, sl.item_base.ensure_roomy(nt + 2));
     HIP_TRY(c, sl.partials.ensure_roomy((nt + cap / seg + 1) * 256));
+    if (a.d_out_depth) HIP_TRY(c, sl.partials_z.ensure_roomy((nt + cap / seg + 1) * 256));
     HIP_TRY(c, sl.item_tab.ensure_roomy(nt + cap / seg + 2));
 
     b.draws = D.draws.p; b.n_chunks = D.n_chunks; b.chunk_tab = D.chunk_tab.p; b.chunk_tab_xcd = D.chunk_tab_xcd.p;
     b.static_list = c->static_list.p; b.merged_list = D.merged_list.p; b.merged_map = D.merged_map.p;
     b.tex = c->tex.p; b.hmap = c->hmap.p; b.boxes = c->static_boxes.p;
-    b.bg_rgba = a.d_bg; b.bg_depth = a.d_bgd; b.out = a.d_out; b.host_counters = sl.hc_dev;
+    b.bg_rgba = a.d_bg; b.bg_depth = a.d_bgd; b.out = a.d_out; b.out_depth = a.d_out_depth; b.host_counters = sl.hc_dev;
     b.n_tiles = (uint32_t)n_tiles; b.pair_cap = cap; b.seg = seg;
     b.rects = sl.rects.p; b.recs = sl.recs.p; b.depths = need_depths ? sl.depths.p : nullptr; b.col_f = sl.col_f.p; b.dbg = c->dbg.p;
     b.draw_culled = sl.draw_culled.p; b.cell_culled = sl.cell_culled.p;
@@ -1660,7 +1663,7 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     b.keys_a = sl.keys_a.p; b.keys_b = sl.keys_b.p; b.vals_a = sl.vals_a.p; b.vals_b = sl.vals_b.p; b.aux_a = sl.aux_a.p; b.aux_b = sl.aux_b.p;
     b.ranges = sl.ranges.p;
     b.long_tiles = reinterpret_cast<uint32_t*>(sl.ranges.p) + range_words;
-    b.item_base = sl.item_base.p; b.item_tab = sl.item_tab.p; b.partials = sl.partials.p;
+    b.item_base = sl.item_base.p; b.item_tab = sl.item_tab.p; b.partials = sl.partials.p; b.partials_z = a.d_out_depth ? sl.partials_z.p : nullptr;
     return GSWT_OK;
 }
 
@@ -1748,6 +1751,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         else HIP_TRY(c, hipStreamWaitEvent(s, D.ev_up, 0));
     }
     if (a.cfg.shard_count > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(a.d_out, 0, out_px * out_pixel_bytes((int)a.cfg.out_format), s));
+    if (a.cfg.shard_count > 1 && out_px > 0 && a.d_out_depth) HIP_TRY(c, hipMemsetAsync(a.d_out_depth, 0, out_px * sizeof(float), s));
     // GSWT_OPT_GRAPH: from here to the end of the frame the launch sites record instead of launching (frames that carry timing
     // events, debug varyings and shards without tiles launch as before)
     const bool use_graph = c->opt_graph != 0 && c->opt_timing == 0 && !dbg && n_tiles > 0 && sl.hc_dev != nullptr;
@@ -1853,13 +1857,14 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
 
 // Submits a frame in slot `sl` (gswt_render, gswt_render_async): the slot's stream on first use, the draw set current now, the arguments.
 static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
-                        int width, int height, const float4* d_bg, const float* d_bgd, float4* d_out)
+                        int width, int height, const float4* d_bg, const float* d_bgd, float4* d_out, float* d_out_depth)
 {
     if (!sl.stream) HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));      // a slot past the fourth: first use
     activate_pending(c, false);
     sl.set = c->cur_set;
     FrameArgs& a = sl.args;
     a.cam = *cam; a.su = *su; a.cfg = *cfg; a.width = width; a.height = height; a.d_bg = d_bg; a.d_bgd = d_bgd; a.d_out = d_out;
+    a.d_out_depth = d_out_depth;
     sl.strict_vs = c->opt_strict_vs != 0;
     return enqueue_frame(c, sl);
 }
@@ -1867,10 +1872,19 @@ static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* 
 int gswt_render(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
                 int width, int height, const float* bg_rgba, const float* bg_depth, int bg_on_device, float* out_rgba,
                 int out_on_device)
+{
+    return gswt_render_depth(c, cam, su, cfg, width, height, bg_rgba, bg_depth, bg_on_device, out_rgba, nullptr, out_on_device);
+}
+
+int gswt_render_depth(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
+                      int width, int height, const float* bg_rgba, const float* bg_depth, int bg_on_device, float* out_rgba,
+                      float* out_depth, int out_on_device)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;
     int rc = validate_frame(c, cam, su, cfg, width, height, out_rgba);
     if (rc != GSWT_OK) return rc;
+    if (out_depth && static_cast<const void*>(out_depth) == static_cast<const void*>(out_rgba))
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render_depth: out_depth is out_rgba");
     hipSetDevice(c->device);
     hipStream_t s = c->stream;
     HIP_TRY(c, collect_pending(c));                // frames still in flight from the async API keep their tickets
@@ -1879,7 +1893,7 @@ try {
     const int out_rows = sc > 1 && !cols ? gswt_shard_rows_padded(height, sc) : height;
     const size_t out_px = (size_t)out_rows * (cols ? gswt_shard_cols_padded(width, sc) : width), npx = (size_t)width * height;
     const size_t out_bytes = out_px * out_pixel_bytes((int)cfg->out_format);
-    const float4* d_bg = nullptr; const float* d_bgd = nullptr; float4* d_out = nullptr;
+    const float4* d_bg = nullptr; const float* d_bgd = nullptr; float4* d_out = nullptr; float* d_outz = nullptr;
     if (bg_rgba) {
         if (bg_on_device) d_bg = reinterpret_cast<const float4*>(bg_rgba);
         else { HIP_TRY(c, c->bg_rgba.ensure(npx)); HIP_TRY(c, hipMemcpyAsync(c->bg_rgba.p, bg_rgba, npx * 16, hipMemcpyHostToDevice, s)); d_bg = c->bg_rgba.p; }
@@ -1890,16 +1904,21 @@ try {
     }
     if (out_on_device) d_out = reinterpret_cast<float4*>(out_rgba);
     else { HIP_TRY(c, c->out_img.ensure((out_bytes + 15) / 16)); d_out = c->out_img.p; }
+    if (out_depth) {
+        if (out_on_device) d_outz = out_depth;
+        else { HIP_TRY(c, c->out_depth_img.ensure(out_px)); d_outz = c->out_depth_img.p; }
+    }
     int si0 = 0;
     for (int k = 0; k < kFrameSlots; k++) if (!c->slots[k].pending) { si0 = k; break; }
     FrameSlot& sl = c->slots[si0];
     if (sl.pending) return fail(c, GSWT_ERR_STATE, "gswt_render: every frame slot holds an uncollected gswt_render_async ticket");
-    rc = submit_frame(c, sl, cam, su, cfg, width, height, d_bg, d_bgd, d_out);
+    rc = submit_frame(c, sl, cam, su, cfg, width, height, d_bg, d_bgd, d_out, d_outz);
     if (rc != GSWT_OK) return rc;
     rc = finish_frame(c, sl);
     if (rc != GSWT_OK) return rc;
     if (!out_on_device) {
         HIP_TRY(c, hipMemcpyAsync(out_rgba, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+        if (out_depth) HIP_TRY(c, hipMemcpyAsync(out_depth, d_outz, out_px * sizeof(float), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
     return GSWT_OK;
@@ -1907,10 +1926,19 @@ try {
 
 int gswt_render_async(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
                       int width, int height, const float* bg_rgba_dev, const float* bg_depth_dev, float* out_rgba_dev, int* ticket)
+{
+    return gswt_render_async_depth(c, cam, su, cfg, width, height, bg_rgba_dev, bg_depth_dev, out_rgba_dev, nullptr, ticket);
+}
+
+int gswt_render_async_depth(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
+                            int width, int height, const float* bg_rgba_dev, const float* bg_depth_dev, float* out_rgba_dev,
+                            float* out_depth_dev, int* ticket)
 try {
     if (!c || !ticket) return GSWT_ERR_BAD_ARG;
     int rc = validate_frame(c, cam, su, cfg, width, height, out_rgba_dev);
     if (rc != GSWT_OK) return rc;
+    if (out_depth_dev && static_cast<const void*>(out_depth_dev) == static_cast<const void*>(out_rgba_dev))
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render_async_depth: out_depth_dev is out_rgba_dev");
     hipSetDevice(c->device);
     // lowest free slot (a caller that keeps fewer frames in flight than there are slots then cycles over fewer buffer sets:
     // the per-frame buffers of a c5-sized frame are ~5 GB per slot); all busy: the oldest frame is collected first
@@ -1929,7 +1957,7 @@ try {
     sl.seq = ++c->frame_seq;
     sl.gather_recorded = false;
     rc = submit_frame(c, sl, cam, su, cfg, width, height, reinterpret_cast<const float4*>(bg_rgba_dev), bg_depth_dev,
-                      reinterpret_cast<float4*>(out_rgba_dev));
+                      reinterpret_cast<float4*>(out_rgba_dev), out_depth_dev);
     if (rc != GSWT_OK) return rc;
     sl.pending = true; sl.collected = false;
     *ticket = si;

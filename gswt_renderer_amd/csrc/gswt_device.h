@@ -272,12 +272,13 @@ struct FrameBufs {
     const uint4* tex;
     const float *hmap, *boxes;                 // boxes: tile-local bounds of every chunk of the static lists (k_cull's chunk cull)
     const float4* bg_rgba; const float* bg_depth; float4* out;
+    float* out_depth;                          // the frame's depth image (f32, the colour's geometry); null: none (gswt_render_depth)
     unsigned long long* host_counters;         // as the device sees them (null: copied behind the frame)
     // the sizes the buffers were planned for
     uint32_t n_chunks, n_cells, n_tiles, pair_cap, seg;
     // per slot (= composite order), per draw, per map cell (the band cull), per chunk
     uint2* rects; Rec* recs; float4* col_f; Varyings* dbg;
-    float* depths;                             // null unless the frame is depth-tested or depth-ordered
+    float* depths;                             // null unless the frame is depth-tested, depth-ordered or writes its depth
     uint32_t *draw_culled, *cell_culled, *live_cnt, *live_cid, *block_sums; uint4* live_tab;
     // the `ghist` region: counters (krange = counters[5], k_emit<DEPTH>), k_project's super-group sums, the two sorts' radix workspaces
     unsigned long long* counters;
@@ -287,6 +288,7 @@ struct FrameBufs {
     // the `ranges` region: per tile (~start, end), the tile-local depth sort's lists of long tiles
     uint2* ranges; uint32_t* long_tiles;
     uint32_t* item_base; uint4* item_tab; float4* partials;
+    float* partials_z;                         // a segment's partial depth per pixel beside `partials` (out_depth only)
     // the words k_cull clears: the head of `ghist` to the end of the pair sort's zeroed part, the `ranges` region, the depth sort's zeroed part
     uint32_t n_zero_head, n_zero_ranges, n_zero_depth;
 };
@@ -320,7 +322,8 @@ void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks
 void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_cull);
 void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict);
 void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
-// b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer).
+// b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer), b.out_depth (when
+// set) the depth image in f32.
 void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
                       uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format);
 void launch_totals(hipStream_t s, uint32_t* super_sums, uint32_t n_super, unsigned long long* counters, uint32_t pair_cap);

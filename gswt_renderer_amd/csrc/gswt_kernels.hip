@@ -2239,11 +2239,13 @@ constexpr uint32_t kNullRec = 256u;        // LDS record no pixel is ever inside
 // List entries are LDS byte offsets of the records (u16), padded to an even length with the offset of a null record
 // whose r^2 is +inf: the walk needs neither a shift nor an `i < n` test nor a mid-pair exit.
 // BATCH: pairs per staged batch (256 in k_composite, 128 in k_composite_dw); the list stride and the null record's index follow it.
-template <bool EARLY, bool DEPTH, bool COLF, uint32_t BATCH = 256u>
+// ZOUT: also blends the splats' depths (s_dep, staged as for the depth test) into az with the colour's weights (gswt_hip.h, depth output).
+template <bool EARLY, bool DEPTH, bool COLF, bool ZOUT, uint32_t BATCH = 256u>
 __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLane& g, uint32_t n, const float4* s_q0, const float4* s_q1,
                                                    const float4* s_q2, const uint32_t* s_bb, const float* s_dep, uint16_t* wlist,
-                                                   float dbuf, float t_eps, float& T, float& ar, float& ag, float& ab, bool& wave_live)
+                                                   float dbuf, float t_eps, float& T, float& ar, float& ag, float& ab, float& az, bool& wave_live)
 {
+    constexpr bool SDEP = DEPTH || ZOUT;                                       // the pairs' depths are staged in s_dep
     const uint32_t lane = g.lane, grp = g.grp;
     const float lx = g.lx, ly = g.ly;
     constexpr uint32_t kStride = BATCH == 256u ? kListStride : BATCH + 8u;     // u16 entries per sub-block list
@@ -2305,6 +2307,7 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
             ar = fmaf(wgt, COLF ? Q2.x : (float)(cw & 0xFFu), ar);                                  \
             ag = fmaf(wgt, COLF ? Q2.y : (float)((cw >> 8) & 0xFFu), ag);                           \
             ab = fmaf(wgt, COLF ? Q2.z : (float)((cw >> 16) & 0xFFu), ab);                          \
+            if (ZOUT) az = fmaf(wgt, DV, az);                                                       \
             T = T - wgt;                                                                            \
         }                                                                                           \
     }
@@ -2317,18 +2320,18 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
         float4 a0 = GSWT_REC0(kA), a1 = GSWT_REC1(kA);
         float4 a2 = make_float4(0.f, 0.f, 0.f, 0.f), b2 = a2;
         if (COLF) a2 = GSWT_REC2(kA);
-        float da = DEPTH ? GSWT_RECD(kA) : 0.0f, db = 0.0f;
+        float da = SDEP ? GSWT_RECD(kA) : 0.0f, db = 0.0f;
         for (uint32_t i = 0; i < n_steps; i += 2u) {
             kA = my_list[i + 2u];                                          // entry of step i+2: issued BEFORE the record reads, so that pinning it
             const float4 b0 = GSWT_REC0(kB), b1 = GSWT_REC1(kB);           // (below) waits for the oldest LDS read only, not for the records behind it
             if (COLF) b2 = GSWT_REC2(kB);
-            if (DEPTH) db = GSWT_RECD(kB);
+            if (SDEP) db = GSWT_RECD(kB);
             asm("" : "+v"(kA));
             GSWT_STEP(a0, a1, a2, da)
             kB = my_list[i + 3u];                                          // entry of step i+3
             a0 = GSWT_REC0(kA); a1 = GSWT_REC1(kA);                        // record of step i+2
             if (COLF) a2 = GSWT_REC2(kA);
-            if (DEPTH) da = GSWT_RECD(kA);
+            if (SDEP) da = GSWT_RECD(kA);
             asm("" : "+v"(kB));
             GSWT_STEP(b0, b1, b2, db)
         }
@@ -2447,11 +2450,16 @@ __device__ __forceinline__ void comp_null_record(float4* s_q0, float4* s_q1, flo
 }
 
 // A final pixel (px, py inside the frame): the background under the transmittance left, stored in format OUTF at row orow of this shard's
-// image (rows from out_rows on pad the last tile row: not stored)
-template <int OUTF>
+// image (rows from out_rows on pad the last tile row: not stored).  ZOUT: the depth az blended over the background depth z_bg (the proxy's
+// bg_depth, 1.0 = the clear value without one) the same way, Z = T z_bg + az, stored as f32 at the same place of out_depth.
+template <int OUTF, bool ZOUT>
 __device__ __forceinline__ void comp_final_pixel(const Frame& f, const float4* bg_rgba, float4* out, int out_rows, int px, int py, int orow,
-                                                 float T, float ar, float ag, float ab)
+                                                 float T, float ar, float ag, float ab, const float* bg_depth, float* out_depth, float az)
 {
+    if constexpr (ZOUT) {
+        const float zb = bg_depth ? bg_depth[(size_t)py * f.width + px] : 1.0f;
+        if (orow < out_rows) out_depth[(size_t)orow * f.out_w + (px - f.out_x0)] = fmaf(T, zb, az);
+    }
     float4 bg = make_float4(0.f, 0.f, 0.f, 0.f);
     if (bg_rgba) bg = bg_rgba[(size_t)py * f.width + px];
     float4 o;
@@ -2463,20 +2471,21 @@ __device__ __forceinline__ void comp_final_pixel(const Frame& f, const float4* b
     else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px - f.out_x0), o);
 }
 
-// OUTF: the output format (kOut*); only the final store differs.
-template <bool EARLY, bool DEPTH, bool COLF, int OUTF>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || COLF) ? 7 : 8, 8))) void k_composite(const Frame f, const uint2* __restrict__ ranges,
+// OUTF: the output format (kOut*); only the final store differs.  ZOUT: the frame also writes its depth image (out_depth; a multi-segment
+// item leaves its partial depth in partials_z): the pairs' depths are staged as for the depth test, whether or not they are also tested.
+template <bool EARLY, bool DEPTH, bool COLF, int OUTF, bool ZOUT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || COLF || ZOUT) ? 7 : 8, 8))) void k_composite(const Frame f, const uint2* __restrict__ ranges,
                                                    const uint32_t* __restrict__ item_base, const uint4* __restrict__ item_tab,
                                                    uint32_t seg, const uint32_t* __restrict__ vals, const Rec* __restrict__ recs,
                                                    const float* __restrict__ depths, const float4* __restrict__ col_f,
                                                    const float4* __restrict__ bg_rgba, const float* __restrict__ bg_depth,
                                                    float4* __restrict__ out, float4* __restrict__ partials,
-                                                   int n_tiles, int out_rows)
+                                                   int n_tiles, int out_rows, float* __restrict__ out_depth, float* __restrict__ partials_z)
 {
     __shared__ float4 s_q0[257], s_q1[257];                     // [256] = the null record (list padding)
     __shared__ uint32_t s_bb[256];                              // the 16 sub-blocks a staged pair's pixel box touches (bit 4 strip + column group)
     __shared__ float4 s_q2[COLF ? 257 : 1];
-    __shared__ float s_dep[DEPTH ? 257 : 1];
+    __shared__ float s_dep[(DEPTH || ZOUT) ? 257 : 1];
     __shared__ uint16_t s_list[4][4][kListStride];     // [wave][sub-block][i] -> LDS byte offset of the i-th hit's record
     __shared__ uint4 s_dead;                           // EARLY: .x .. .w = wave 0 .. 3 has no pixel with T >= t_eps left
     // work item -> (tile, segment) through the table k_items left behind.  Consecutive items are dealt
@@ -2520,14 +2529,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     // Transmittance doubles as the "still active" state: a lane is live while T >= t_eps.  Pixels
     // outside the target start at T = 0 when early-out is on (never live); with t_eps = 0 they just
     // accumulate and are never stored.
-    float T = (EARLY && !inside) ? 0.0f : 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f;
+    float T = (EARLY && !inside) ? 0.0f : 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, az = 0.0f;
     float dbuf = 1.0f;
     if (DEPTH && inside) dbuf = bg_depth[(size_t)py * f.width + px];
     const float t_eps = f.t_eps;
     bool wave_live = true;
     if (tid == 0) {
         if (EARLY) s_dead = make_uint4(0u, 0u, 0u, 0u);
-        comp_null_record<DEPTH, COLF>(s_q0, s_q1, s_q2, s_dep, kNullRec);
+        comp_null_record<DEPTH || ZOUT, COLF>(s_q0, s_q1, s_q2, s_dep, kNullRec);
     }
     // Software-pipelined gather: the records of batch b+1 and the slot indices of batch b+2 are in flight
     // while batch b is binned and walked (two dependent HBM latencies per batch otherwise sit between barriers).
@@ -2542,7 +2551,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
             const float4* rp = reinterpret_cast<const float4*>(recs + (SLOT));                      \
             ra = rp[0];                                                                             \
             rb = rp[1];                                                                             \
-            if (DEPTH) rbw = depths[(SLOT)];                                                        \
+            if (DEPTH || ZOUT) rbw = depths[(SLOT)];                                                \
         }
     uint32_t slot_nxt = 0;
     const uint32_t last_pair = rg.y - 1u;
@@ -2554,7 +2563,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     }
     for (uint32_t base = rg.x; base < rg.y; base += 256u) {
         const uint32_t n = min(256u, rg.y - base);
-        if (tid < n) comp_stage<DEPTH, COLF>(hW, hHn, c0x, c0y, ra, rb, rbw, rd, s_q0, s_q1, s_q2, s_dep, s_bb, tid, tid);
+        if (tid < n) comp_stage<DEPTH || ZOUT, COLF>(hW, hHn, c0x, c0y, ra, rb, rbw, rd, s_q0, s_q1, s_q2, s_dep, s_bb, tid, tid);
         __syncthreads();
 #ifdef GSWT_TRACE
         if (tr_first) { GSWT_TR(2, GSWT_NOW()) tr_first = false; }
@@ -2566,7 +2575,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
             slot_nxt = vals[min(base + 512u + tid, last_pair)];
         }
         if (wave_live)
-            composite_bin_walk<EARLY, DEPTH, COLF>(f, cl, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, wave_live);
+            composite_bin_walk<EARLY, DEPTH, COLF, ZOUT>(f, cl, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, az, wave_live);
 #ifdef GSWT_TRACE
         tr_walk += GSWT_NOW() - tr_t0;
 #endif
@@ -2589,7 +2598,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     if (multi_seg) {
         // partial (C, T) of this segment, in the slot the tile's first + the segment's number (the table position only while the table is
         // in tile order); k_combine folds the segments front to back
-        partials[(size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid] = make_float4(ar, ag, ab, T);
+        const size_t pi = (size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid;
+        partials[pi] = make_float4(ar, ag, ab, T);
+        if (ZOUT) partials_z[pi] = az;
         return;
     }
     // pixel coordinates again, from a copy of the thread id the compiler cannot connect to the one above: otherwise px, py
@@ -2598,7 +2609,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     asm volatile("" : "+v"(tid2));
     const int lxi2 = (int)(((tid2 & 63u) >> 4) * 4u + (tid2 & 3u)), lyi2 = (int)((tid2 >> 6) * 4u + ((tid2 & 15u) >> 2));
     const int px2 = bx + lxi2, py2 = by + lyi2;
-    if (px2 < f.width && py2 < f.height) comp_final_pixel<OUTF>(f, bg_rgba, out, out_rows, px2, py2, tyl * kTile + lyi2, T, ar, ag, ab);
+    if (px2 < f.width && py2 < f.height)
+        comp_final_pixel<OUTF, ZOUT>(f, bg_rgba, out, out_rows, px2, py2, tyl * kTile + lyi2, T, ar, ag, ab, bg_depth, out_depth, az);
 }
 
 // Measured and dropped again in round 2 (the item STREAM: a resident grid of workgroups, each taking items b, b + G, b + 2G, ...
@@ -2627,20 +2639,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
 __device__ __forceinline__ uint32_t lds_peek(const uint32_t* p) { return *reinterpret_cast<const volatile uint32_t*>(p); }
 constexpr int kDwSleep = 1;            // s_sleep units (64 clocks) between two polls of a counter
 
-template <bool EARLY, bool DEPTH, bool COLF, int OUTF>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : DEPTH ? 7 : 8, 8))) void k_composite_dw(const Frame f,
+template <bool EARLY, bool DEPTH, bool COLF, int OUTF, bool ZOUT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : (DEPTH || ZOUT) ? 7 : 8, 8))) void k_composite_dw(const Frame f,
                                                    const uint32_t* __restrict__ item_base, const uint4* __restrict__ item_tab,
                                                    const uint32_t* __restrict__ vals, const Rec* __restrict__ recs,
                                                    const float* __restrict__ depths, const float4* __restrict__ col_f,
                                                    const float4* __restrict__ bg_rgba, const float* __restrict__ bg_depth,
                                                    float4* __restrict__ out, float4* __restrict__ partials,
-                                                   int n_tiles, int out_rows)
+                                                   int n_tiles, int out_rows, float* __restrict__ out_depth, float* __restrict__ partials_z)
 {
     constexpr uint32_t B = 128u, NBUF = 3u, BS = B + 1u;        // pairs per batch, ring depth, records per buffer (the last one = the null record)
     __shared__ float4 s_q0[NBUF * BS], s_q1[NBUF * BS];
     __shared__ uint32_t s_bb[NBUF * B];
     __shared__ float4 s_q2[COLF ? NBUF * BS : 1];
-    __shared__ float s_dep[DEPTH ? NBUF * BS : 1];
+    __shared__ float s_dep[(DEPTH || ZOUT) ? NBUF * BS : 1];
     __shared__ uint16_t s_list[4][4][B + 8u];
     __shared__ uint32_t s_staged[NBUF], s_done[NBUF], s_dead;
     const uint32_t item = blockIdx.x;
@@ -2664,14 +2676,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
     uint16_t* const wlist = &s_list[wave][0][0];
     const CompLane cl = {lx, ly, (int)(wave * 4u), lane, grp};
     const uint2 rg = make_uint2(it.z, it.w);
-    float T = (EARLY && !inside) ? 0.0f : 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f;
+    float T = (EARLY && !inside) ? 0.0f : 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, az = 0.0f;
     float dbuf = 1.0f;
     if (DEPTH && inside) dbuf = bg_depth[(size_t)py * f.width + px];
     const float t_eps = f.t_eps;
     bool wave_live = true, counted_dead = false;
     if (tid < NBUF) {
         s_staged[tid] = 0u; s_done[tid] = 0u;
-        comp_null_record<DEPTH, COLF>(s_q0, s_q1, s_q2, s_dep, tid * BS + B);      // the null record of buffer tid
+        comp_null_record<DEPTH || ZOUT, COLF>(s_q0, s_q1, s_q2, s_dep, tid * BS + B);      // the null record of buffer tid
     }
     if (tid == 0) s_dead = 0u;
     const uint32_t n_pairs = rg.y - rg.x;
@@ -2689,7 +2701,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
             const float4* rp = reinterpret_cast<const float4*>(recs + (SLOT));                      \
             ra = rp[0];                                                                             \
             rb = rp[1];                                                                             \
-            if (DEPTH) rbw = depths[(SLOT)];                                                        \
+            if (DEPTH || ZOUT) rbw = depths[(SLOT)];                                                \
             if (COLF) rd = col_f[(SLOT)];                                                           \
         }
     if (n_pairs) {
@@ -2714,7 +2726,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             const uint32_t li = half * 64u + lane;      // my pair inside the batch
-            if (ks * B + li < n_pairs) comp_stage<DEPTH, COLF>(hW, hHn, c0x, c0y, ra, rb, rbw, rd, s_q0, s_q1, s_q2, s_dep, s_bb, sb * BS + li, sb * B + li);
+            if (ks * B + li < n_pairs) comp_stage<DEPTH || ZOUT, COLF>(hW, hHn, c0x, c0y, ra, rb, rbw, rd, s_q0, s_q1, s_q2, s_dep, s_bb, sb * BS + li, sb * B + li);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane == 0u) atomicAdd(&s_staged[sb], 1u);
             ks += 2u; sb += 2u; if (sb >= 3u) { sb -= 3u; su += 1u; }
@@ -2734,8 +2746,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
         }
         const uint32_t n = min(B, n_pairs - k * B);
         if (wave_live)
-            composite_bin_walk<EARLY, DEPTH, COLF, B>(f, cl, n, s_q0 + kb * BS, s_q1 + kb * BS, s_q2 + (COLF ? kb * BS : 0u), s_bb + kb * B,
-                                                                    s_dep + (DEPTH ? kb * BS : 0u), wlist, dbuf, t_eps, T, ar, ag, ab, wave_live);
+            composite_bin_walk<EARLY, DEPTH, COLF, ZOUT, B>(f, cl, n, s_q0 + kb * BS, s_q1 + kb * BS, s_q2 + (COLF ? kb * BS : 0u), s_bb + kb * B,
+                                                            s_dep + ((DEPTH || ZOUT) ? kb * BS : 0u), wlist, dbuf, t_eps, T, ar, ag, ab, az, wave_live);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if (lane == 0u) {
             atomicAdd(&s_done[kb], 1u);
@@ -2750,23 +2762,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
     const float k255 = 1.0f / 255.0f;
     if (!COLF) { ar *= k255; ag *= k255; ab *= k255; }
     if (multi_seg) {
-        partials[(size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid] = make_float4(ar, ag, ab, T);
+        const size_t pi = (size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid;
+        partials[pi] = make_float4(ar, ag, ab, T);
+        if (ZOUT) partials_z[pi] = az;
         return;
     }
     uint32_t tid2 = threadIdx.x;                         // (k_composite: the opaque copy of the thread id)
     asm volatile("" : "+v"(tid2));
     const int lxi2 = (int)(((tid2 & 63u) >> 4) * 4u + (tid2 & 3u)), lyi2 = (int)((tid2 >> 6) * 4u + ((tid2 & 15u) >> 2));
     const int px2 = bx + lxi2, py2 = by + lyi2;
-    if (px2 < f.width && py2 < f.height) comp_final_pixel<OUTF>(f, bg_rgba, out, out_rows, px2, py2, tyl * kTile + lyi2, T, ar, ag, ab);
+    if (px2 < f.width && py2 < f.height)
+        comp_final_pixel<OUTF, ZOUT>(f, bg_rgba, out, out_rows, px2, py2, tyl * kTile + lyi2, T, ar, ag, ab, bg_depth, out_depth, az);
 }
 
 // Folds the per-segment partials of multi-segment tiles: (C1,T1) o (C2,T2) = (C1 + T1*C2, T1*T2).
-// One workgroup per tile, same lane -> pixel map as k_composite.
-template <int OUTF>
+// One workgroup per tile, same lane -> pixel map as k_composite.  ZOUT: the partial depths fold like a colour channel (Z1 + T1*Z2).
+template <int OUTF, bool ZOUT>
 __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* __restrict__ item_base,
                                                  const float4* __restrict__ partials, const float4* __restrict__ bg_rgba,
                                                  float4* __restrict__ out, int n_tiles, int out_rows,
-                                                 const unsigned long long* __restrict__ counters, unsigned long long* __restrict__ host_counters)
+                                                 const unsigned long long* __restrict__ counters, unsigned long long* __restrict__ host_counters,
+                                                 const float* __restrict__ partials_z, const float* __restrict__ bg_depth, float* __restrict__ out_depth)
 {
     const int tile = blockIdx.x;
     // last kernel of the frame: the four result counters go straight into the slot's pinned host words (instead of a
@@ -2781,24 +2797,30 @@ __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* 
     const int lyi = (int)wave * 4 + (int)(gi >> 2);
     const int px = bx + lxi, py = by + lyi;
     if (px >= f.width || py >= f.height) return;
-    float T = 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f;
+    float T = 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, az = 0.0f;
     // eight segments' partials in flight together (clamped, unmasked): a horizon tile of c5 has 40 segments, and one dependent
     // 4-KB load per segment made the longest tile the kernel's duration (59 us at c5)
     for (uint32_t s0 = 0; s0 < n_seg; s0 += 8u) {
         float4 p[8];
+        float pz[8];
 #pragma unroll
-        for (uint32_t k = 0; k < 8u; k++) p[k] = partials[(size_t)(i0 + min(s0 + k, n_seg - 1u)) * 256u + tid];
+        for (uint32_t k = 0; k < 8u; k++) {
+            const size_t pi = (size_t)(i0 + min(s0 + k, n_seg - 1u)) * 256u + tid;
+            p[k] = partials[pi];
+            if (ZOUT) pz[k] = partials_z[pi];
+        }
 #pragma unroll
         for (uint32_t k = 0; k < 8u; k++) {
             if (s0 + k < n_seg) {                 // workgroup-uniform
                 ar = fmaf(T, p[k].x, ar);
                 ag = fmaf(T, p[k].y, ag);
                 ab = fmaf(T, p[k].z, ab);
+                if (ZOUT) az = fmaf(T, pz[k], az);
                 T = T * p[k].w;
             }
         }
     }
-    comp_final_pixel<OUTF>(f, bg_rgba, out, out_rows, px, py, tyl * kTile + lyi, T, ar, ag, ab);
+    comp_final_pixel<OUTF, ZOUT>(f, bg_rgba, out, out_rows, px, py, tyl * kTile + lyi, T, ar, ag, ab, bg_depth, out_depth, az);
 }
 
 // all-gathered shards -> frame.  rows: shard = tile row % count (rows_padded rows each, full width);
@@ -3009,8 +3031,8 @@ static void with_composite_edc(const Frame& f, Fn&& fn)
 }
 
 // ranges -> per-tile segment counts -> item_base (exclusive scan, item_base[n_tiles] = #items) ->
-// k_composite over an upper bound of items -> k_combine, storing the image in format OUTF.
-template <int OUTF>
+// k_composite over an upper bound of items -> k_combine, storing the image in format OUTF (and with ZOUT the depth image b.out_depth).
+template <int OUTF, bool ZOUT>
 static void launch_composite_t(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
                                uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
@@ -3032,21 +3054,31 @@ static void launch_composite_t(hipStream_t s, const Frame& f, const FrameBufs& b
     // ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED.)
     with_composite_edc(f, [&](auto E, auto D, auto C) {
         if (variant == 1)
-            GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs,
-                              b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows);
+            GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C, OUTF, ZOUT>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs,
+                              b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z);
         else
-            GSWT_LAUNCH_TIMED((k_composite<E, D, C, OUTF>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals,
-                              b.recs, b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows);
+            GSWT_LAUNCH_TIMED((k_composite<E, D, C, OUTF, ZOUT>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals,
+                              b.recs, b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z);
     });
-    GSWT_LAUNCH(k_combine<OUTF>, dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows, (const unsigned long long*)b.counters, b.host_counters);
+    GSWT_LAUNCH((k_combine<OUTF, ZOUT>), dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows,
+                (const unsigned long long*)b.counters, b.host_counters, (const float*)b.partials_z, b.bg_depth, b.out_depth);
+}
+
+// The frame's depth image is written when b.out_depth is set (gswt_render_depth): the ZOUT instantiations of the compositors.
+template <int OUTF>
+static void launch_composite_z(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
+                               uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+    if (b.out_depth) launch_composite_t<OUTF, true>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    else launch_composite_t<OUTF, false>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
 }
 
 void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
                       uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format)
 {
-    if (out_format == kOutRGBA8) launch_composite_t<kOutRGBA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-    else if (out_format == kOutBGRA8) launch_composite_t<kOutBGRA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-    else launch_composite_t<kOutF32>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    if (out_format == kOutRGBA8) launch_composite_z<kOutRGBA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    else if (out_format == kOutBGRA8) launch_composite_z<kOutBGRA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    else launch_composite_z<kOutF32>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
 }
 
 // k_totals alone on caller-provided sums (unit test of the 64-bit pair count)

@@ -183,10 +183,14 @@ class GSWTRenderer:
     def render(self, camera, scene, width: int, height: int, *, culling_dist: float = 1.0,
                lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
                transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba=None, bg_depth=None,
-               out_device_ptr: int | None = None, bg_on_device: bool = False, out_format: int = L.GSWT_OUT_RGBA32F):
+               out_device_ptr: int | None = None, bg_on_device: bool = False, out_format: int = L.GSWT_OUT_RGBA32F,
+               depth: bool = False, out_depth_device_ptr: int | None = None):
         """camera / scene: 176 / 160-byte uniform blocks (any ctypes struct or bytes of that layout).
         Returns the image [rows, W, 4] on the host -- f32 for GSWT_OUT_RGBA32F, uint8 in the channel order of
-        GSWT_OUT_RGBA8_UNORM / GSWT_OUT_BGRA8_UNORM --, or None when out_device_ptr is given."""
+        GSWT_OUT_RGBA8_UNORM / GSWT_OUT_BGRA8_UNORM --, or None when out_device_ptr is given.
+        depth=True: returns (image, depth), depth the composited depth image [rows, W] f32 of gswt_render_depth (NDC depth
+        blended like a colour channel over bg_depth, or 1.0 without one).  With out_device_ptr the depth goes to
+        out_depth_device_ptr (rows x out_w f32 on the device) when that is given."""
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()
@@ -207,10 +211,16 @@ class GSWTRenderer:
             bgd_a = np.ascontiguousarray(bg_depth, dtype=np.float32) if bg_depth is not None else None
             bgc, bgd = _ptr(bgc_a), _ptr(bgd_a)
         if out_device_ptr is not None:
-            self._check(self._lib.gswt_render(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
-                                              1 if bg_on_device else 0, C.c_void_p(out_device_ptr), 1))
+            zd = C.c_void_p(out_depth_device_ptr) if out_depth_device_ptr else None
+            self._check(self._lib.gswt_render_depth(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
+                                                    1 if bg_on_device else 0, C.c_void_p(out_device_ptr), zd, 1))
             return None
         out = np.empty((rows, out_w, 4), dtype=_out_dtype(out_format))
+        if depth:
+            z = np.empty((rows, out_w), dtype=np.float32)
+            self._check(self._lib.gswt_render_depth(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
+                                                    1 if bg_on_device else 0, _ptr(out), _ptr(z), 0))
+            return out, z
         self._check(self._lib.gswt_render(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
                                           1 if bg_on_device else 0, _ptr(out), 0))
         return out
@@ -218,9 +228,10 @@ class GSWTRenderer:
     def render_async(self, camera, scene, width: int, height: int, out_device_ptr: int, *, culling_dist: float = 1.0,
                      lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
                      transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba_ptr: int = 0, bg_depth_ptr: int = 0,
-                     out_format: int = L.GSWT_OUT_RGBA32F) -> int:
+                     out_format: int = L.GSWT_OUT_RGBA32F, out_depth_ptr: int = 0) -> int:
         """Queues a frame (device pointers only) and returns a ticket for render_wait.  out_device_ptr holds rows x out_w x 4
-        f32, or bytes for the 8-bit out_format values."""
+        f32, or bytes for the 8-bit out_format values; out_depth_ptr (optional) receives the depth image, rows x out_w f32
+        (gswt_render_async_depth)."""
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()
@@ -229,10 +240,11 @@ class GSWTRenderer:
         cfg.shard_index, cfg.shard_count, cfg.shard_mode = _shard_args(shard)
         cfg.out_format = out_format & 0xFFFFFFFF
         ticket = C.c_int(-1)
-        self._check(self._lib.gswt_render_async(self._h, cam, sc, C.byref(cfg), width, height,
-                                                C.c_void_p(bg_rgba_ptr) if bg_rgba_ptr else None,
-                                                C.c_void_p(bg_depth_ptr) if bg_depth_ptr else None,
-                                                C.c_void_p(out_device_ptr), C.byref(ticket)))
+        self._check(self._lib.gswt_render_async_depth(self._h, cam, sc, C.byref(cfg), width, height,
+                                                      C.c_void_p(bg_rgba_ptr) if bg_rgba_ptr else None,
+                                                      C.c_void_p(bg_depth_ptr) if bg_depth_ptr else None,
+                                                      C.c_void_p(out_device_ptr), C.c_void_p(out_depth_ptr) if out_depth_ptr else None,
+                                                      C.byref(ticket)))
         return ticket.value
 
     def frame_slots(self) -> int:

@@ -325,6 +325,31 @@ GSWT_API int gswt_render_async(gswt_ctx *ctx, const gswt_camera_uniforms *camera
                                int width, int height, const float *bg_rgba_dev, const float *bg_depth_dev,
                                float *out_rgba_dev, int *ticket);
 GSWT_API int gswt_frame_slots(void);   /* frames that may be in flight at once */
+
+/* gswt_render / gswt_render_async that also write the frame's composited DEPTH image.  out_depth receives rows_out*W f32
+ * (the colour output's geometry in every shard mode; the padding rows / columns of a shard are zeroed like the colour's),
+ * whatever cfg->out_format is; NULL behaves exactly as gswt_render / gswt_render_async, which are these calls with NULL.
+ * Definition, per pixel: the splats are walked in the compositor's blend order with the colour's coverage decisions, its
+ * weights w_i = T_i * e_i and its early-out (transmittance_eps), and
+ *     Z = T_final * z_bg + sum_i w_i * z_i
+ * where z_i is the splat's NDC depth -- clip z / w of the centre, the value the proxy depth test compares (renderer.rs:181-182)
+ * -- and z_bg is bg_depth[p] with a proxy depth buffer bound, 1.0 (the clear value, :436) without one.  So depth is blended
+ * like one more colour channel over a background surface at z_bg: a pixel no splat covers gets exactly z_bg, and the
+ * normalised expected depth of the splats alone is (Z - T_final * z_bg) / (1 - T_final), T_final being the transmittance
+ * left (1 - alpha of the f32 colour output when no bg_rgba is bound).  Z is in the depth-buffer convention (NDC z, 0 near .. 1 far), not linear view depth.  Pointer rules are
+ * those of gswt_render (out_depth is a host pointer unless out_on_device) and gswt_render_async (device pointers; frames in
+ * flight together must write different depth buffers as well); a frame re-run after a pair-buffer overflow rewrites its depth.
+ * A missing out_rgba, or an out_depth that is out_rgba, returns GSWT_ERR_BAD_ARG before anything is enqueued.  The depth image
+ * is not part of the gathers (gswt_render_gather, gswt_unshard*). */
+GSWT_API int gswt_render_depth(gswt_ctx *ctx, const gswt_camera_uniforms *camera,
+                               const gswt_scene_uniforms *scene, const gswt_render_config *cfg,
+                               int width, int height,
+                               const float *bg_rgba, const float *bg_depth, int bg_on_device,
+                               float *out_rgba, float *out_depth, int out_on_device);
+GSWT_API int gswt_render_async_depth(gswt_ctx *ctx, const gswt_camera_uniforms *camera,
+                                     const gswt_scene_uniforms *scene, const gswt_render_config *cfg,
+                                     int width, int height, const float *bg_rgba_dev, const float *bg_depth_dev,
+                                     float *out_rgba_dev, float *out_depth_dev, int *ticket);
 GSWT_API int gswt_render_wait(gswt_ctx *ctx, int ticket);
 GSWT_API int gswt_render_fence(gswt_ctx *ctx, int ticket);
 

@@ -200,6 +200,35 @@ impl GSWTRenderer {
         })
     }
 
+    /// `render` that also writes the frame's composited depth image: `depth` = `width * height` floats, the splats' NDC depth
+    /// blended with the colour's weights over the background depth (1.0 without a proxy depth buffer; see `gswt_render_depth`).
+    pub fn render_depth(
+        &mut self,
+        camera: &hip::GswtCameraUniforms,
+        scene: &hip::GswtSceneUniforms,
+        cfg: &hip::GswtRenderConfig,
+        width: u32,
+        height: u32,
+        bg: Option<(&[f32], &[f32])>,
+        out: &mut [f32],
+        depth: &mut [f32],
+    ) -> Result<()> {
+        let n = (width as usize) * (height as usize);
+        if out.len() < 4 * n || depth.len() < n {
+            return Err(GswtError { code: hip::GSWT_ERR_BAD_ARG, message: "output slice too small".into() });
+        }
+        let (bg_rgba, bg_depth) = match bg {
+            Some((c, d)) if c.len() >= 4 * n && d.len() >= n => (c.as_ptr(), d.as_ptr()),
+            Some(_) => return Err(GswtError { code: hip::GSWT_ERR_BAD_ARG, message: "background slices too small".into() }),
+            None => (ptr::null(), ptr::null()),
+        };
+        self.check(unsafe {
+            hip::gswt_render_depth(
+                self.ctx, camera, scene, cfg, width as c_int, height as c_int, bg_rgba, bg_depth, 0, out.as_mut_ptr(), depth.as_mut_ptr(), 0,
+            )
+        })
+    }
+
     /// Pipelined form (device pointers): up to `gswt_frame_slots()` frames overlap on the GPU.
     pub fn render_async(
         &mut self,
@@ -215,6 +244,28 @@ impl GSWTRenderer {
         let mut ticket: c_int = -1;
         self.check(unsafe {
             hip::gswt_render_async(self.ctx, camera, scene, cfg, width as c_int, height as c_int, bg_rgba_dev, bg_depth_dev, out_rgba_dev, &mut ticket)
+        })?;
+        Ok(ticket)
+    }
+
+    /// `render_async` that also writes the depth image to `out_depth_dev` (device, one f32 per output pixel; null: none).
+    pub fn render_async_depth(
+        &mut self,
+        camera: &hip::GswtCameraUniforms,
+        scene: &hip::GswtSceneUniforms,
+        cfg: &hip::GswtRenderConfig,
+        width: u32,
+        height: u32,
+        bg_rgba_dev: *const f32,
+        bg_depth_dev: *const f32,
+        out_rgba_dev: *mut f32,
+        out_depth_dev: *mut f32,
+    ) -> Result<i32> {
+        let mut ticket: c_int = -1;
+        self.check(unsafe {
+            hip::gswt_render_async_depth(
+                self.ctx, camera, scene, cfg, width as c_int, height as c_int, bg_rgba_dev, bg_depth_dev, out_rgba_dev, out_depth_dev, &mut ticket,
+            )
         })?;
         Ok(ticket)
     }
