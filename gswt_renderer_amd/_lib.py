@@ -50,6 +50,8 @@ GSWT_SHARD_COLUMNS = 1
 GSWT_OUT_RGBA32F = 0          # RenderConfig.out_format: RGBA f32, 16 bytes per pixel
 GSWT_OUT_RGBA8_UNORM = 1      # bytes R, G, B, A per pixel
 GSWT_OUT_BGRA8_UNORM = 2      # bytes B, G, R, A per pixel
+GSWT_VIDEO_NV12 = 16          # 4:2:0 video, BT.709 limited range: plane Y, then one plane of interleaved Cb, Cr pairs
+GSWT_VIDEO_I420 = 17          # plane Y, then plane Cb, then plane Cr (rows / 2 x out_w / 2 each); width and height even
 GSWT_PROXY_SRC_RGBA8 = 0      # gswt_proxy_configure_image: 8-bit RGBA source, 4 bytes per texel
 GSWT_PROXY_SRC_RGBA16 = 1     # 16-bit RGBA source, 8 bytes per texel
 
@@ -203,6 +205,7 @@ SYMBOLS = {
     "gswt_unshard_mode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gswt_unshard_format": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gswt_shard_cols_padded": (C.c_int, [C.c_int, C.c_int]),
+    "gswt_out_image_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "gswt_comm_unique_id": (C.c_int, [_P]),
     "gswt_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "gswt_comm_destroy": (C.c_int, [_P]),

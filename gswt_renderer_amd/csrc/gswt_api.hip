@@ -127,6 +127,7 @@ constexpr int kDrawSets = kFrameSlots + 5;
 static_assert(kDrawSets <= kMergeSources, "MergeSources holds one pointer pair per draw set");
 static_assert(sizeof(gswt_render_config) == 32 && offsetof(gswt_render_config, out_format) == 28, "gswt_render_config layout");
 static_assert(GSWT_OUT_RGBA32F == kOutF32 && GSWT_OUT_RGBA8_UNORM == kOutRGBA8 && GSWT_OUT_BGRA8_UNORM == kOutBGRA8, "output formats");
+static_assert(GSWT_VIDEO_NV12 == kOutNV12 && GSWT_VIDEO_I420 == kOutI420, "video output formats");
 template <typename T>
 struct Ref { T* p = nullptr; };
 
@@ -475,7 +476,7 @@ ShardGeom shard_geom(const FrameSlot& sl)
     g.out_w = cols ? gswt_shard_cols_padded(sl.args.width, g.world) : sl.args.width;
     g.px = (size_t)g.out_rows * g.out_w;
     g.fmt = (int)cfg.out_format;
-    g.bytes = g.px * out_pixel_bytes(g.fmt);
+    g.bytes = out_image_bytes(g.fmt, g.out_rows, g.out_w);
     return g;
 }
 
@@ -1465,8 +1466,10 @@ static int validate_frame(gswt_ctx* c, const gswt_camera_uniforms* cam, const gs
     const int sc = cfg->shard_count <= 1 ? 1 : cfg->shard_count;
     if (sc > 1 && (cfg->shard_index < 0 || cfg->shard_index >= sc)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: bad shard index");
     if (cfg->shard_mode != GSWT_SHARD_ROWS && cfg->shard_mode != GSWT_SHARD_COLUMNS) return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: unknown shard mode %d", cfg->shard_mode);
-    if (cfg->out_format != GSWT_OUT_RGBA32F && cfg->out_format != GSWT_OUT_RGBA8_UNORM && cfg->out_format != GSWT_OUT_BGRA8_UNORM)
+    if (cfg->out_format > (uint32_t)kOutI420 || out_image_bytes((int)cfg->out_format, 2, 2) == 0)
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: unknown out_format %u", cfg->out_format);
+    if (out_is_video((int)cfg->out_format) && ((width | height) & 1))
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: the video formats need an even target size, not %dx%d", width, height);
     return GSWT_OK;
 }
 
@@ -1750,7 +1753,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         if (hipEventQuery(D.ev_up) == hipSuccess) D.built = true;
         else HIP_TRY(c, hipStreamWaitEvent(s, D.ev_up, 0));
     }
-    if (a.cfg.shard_count > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(a.d_out, 0, out_px * out_pixel_bytes((int)a.cfg.out_format), s));
+    if (a.cfg.shard_count > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(a.d_out, 0, out_image_bytes((int)a.cfg.out_format, out_rows, f.out_w), s));
     if (a.cfg.shard_count > 1 && out_px > 0 && a.d_out_depth) HIP_TRY(c, hipMemsetAsync(a.d_out_depth, 0, out_px * sizeof(float), s));
     // GSWT_OPT_GRAPH: from here to the end of the frame the launch sites record instead of launching (frames that carry timing
     // events, debug varyings and shards without tiles launch as before)
@@ -1891,8 +1894,9 @@ try {
     const int sc = cfg->shard_count <= 1 ? 1 : cfg->shard_count;
     const bool cols = sc > 1 && cfg->shard_mode == GSWT_SHARD_COLUMNS;
     const int out_rows = sc > 1 && !cols ? gswt_shard_rows_padded(height, sc) : height;
-    const size_t out_px = (size_t)out_rows * (cols ? gswt_shard_cols_padded(width, sc) : width), npx = (size_t)width * height;
-    const size_t out_bytes = out_px * out_pixel_bytes((int)cfg->out_format);
+    const int out_w = cols ? gswt_shard_cols_padded(width, sc) : width;
+    const size_t out_px = (size_t)out_rows * out_w, npx = (size_t)width * height;
+    const size_t out_bytes = out_image_bytes((int)cfg->out_format, out_rows, out_w);
     const float4* d_bg = nullptr; const float* d_bgd = nullptr; float4* d_out = nullptr; float* d_outz = nullptr;
     if (bg_rgba) {
         if (bg_on_device) d_bg = reinterpret_cast<const float4*>(bg_rgba);
@@ -2220,6 +2224,8 @@ try {
     return gswt_unshard_mode(c, gathered, width, height, shard_count, GSWT_SHARD_ROWS, out_rgba);
 } GSWT_CATCH("gswt_unshard")
 
+size_t gswt_out_image_bytes(int out_format, int rows, int out_w) { return out_image_bytes(out_format, rows, out_w); }
+
 int gswt_unshard_mode(gswt_ctx* c, const float* gathered, int width, int height, int shard_count, int shard_mode, float* out_rgba)
 try {
     return gswt_unshard_format(c, gathered, width, height, shard_count, shard_mode, GSWT_OUT_RGBA32F, out_rgba);
@@ -2229,7 +2235,7 @@ int gswt_unshard_format(gswt_ctx* c, const void* gathered, int width, int height
 try {
     if (!c || !gathered || !out || width <= 0 || height <= 0 || shard_count < 1) return GSWT_ERR_BAD_ARG;
     if (shard_mode != GSWT_SHARD_ROWS && shard_mode != GSWT_SHARD_COLUMNS) return GSWT_ERR_BAD_ARG;
-    if (out_format != GSWT_OUT_RGBA32F && out_format != GSWT_OUT_RGBA8_UNORM && out_format != GSWT_OUT_BGRA8_UNORM) return GSWT_ERR_BAD_ARG;
+    if (out_image_bytes(out_format, height, width) == 0) return GSWT_ERR_BAD_ARG;      // unknown format, or a video format at an odd size
     hipSetDevice(c->device);
     launch_unshard(c->stream, gathered, out, width, height, shard_count, gswt_shard_rows_padded(height, shard_count),
                    shard_mode == GSWT_SHARD_COLUMNS ? gswt_shard_cols_padded(width, shard_count) : 0, out_format);

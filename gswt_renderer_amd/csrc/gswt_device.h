@@ -16,7 +16,21 @@ constexpr uint32_t kLodShift = 28;   // packed list entry = gs_index | lod_id <<
 constexpr uint32_t kIdxMask = (1u << kLodShift) - 1u;
 // output image formats, GSWT_OUT_* of gswt_hip.h: RGBA f32 (16 B per pixel), bytes R G B A, bytes B G R A (4 B per pixel)
 constexpr int kOutF32 = 0, kOutRGBA8 = 1, kOutBGRA8 = 2;
-inline size_t out_pixel_bytes(int out_format) { return out_format == kOutF32 ? 16u : 4u; }
+// ... and the 4:2:0 video formats, GSWT_VIDEO_*: plane Y (rows x out_w bytes), then the interleaved Cb Cr plane (NV12) or the Cb and the Cr
+// plane (I420), rows / 2 x out_w / 2 samples each; rows and out_w even
+constexpr int kOutNV12 = 16, kOutI420 = 17;
+constexpr bool out_is_video(int out_format) { return out_format == kOutNV12 || out_format == kOutI420; }
+// Bytes of a rows x out_w image in out_format: THE place that knows the layouts (gswt_out_image_bytes exports it).  0: unknown format,
+// negative size, or a video format with an odd size.
+inline size_t out_image_bytes(int out_format, int rows, int out_w)
+{
+    if (rows < 0 || out_w < 0) return 0;
+    const size_t px = (size_t)rows * (size_t)out_w;
+    if (out_format == kOutF32) return px * 16u;
+    if (out_format == kOutRGBA8 || out_format == kOutBGRA8) return px * 4u;
+    if (out_is_video(out_format)) return ((rows | out_w) & 1) ? 0 : px + px / 2u;
+    return 0;
+}
 
 // Device-side draw descriptor: what one reference draw call binds (renderer.rs:499-590).
 struct DrawDev {
@@ -322,8 +336,8 @@ void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks
 void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_cull);
 void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict);
 void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
-// b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer), b.out_depth (when
-// set) the depth image in f32.
+// b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer, the video formats
+// their planes of out_rows x f.out_w samples, both even), b.out_depth (when set) the depth image in f32.
 void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
                       uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format);
 void launch_totals(hipStream_t s, uint32_t* super_sums, uint32_t n_super, unsigned long long* counters, uint32_t pair_cap);
@@ -345,7 +359,7 @@ void launch_tile_depth_sort(hipStream_t s, const uint2* ranges, uint32_t* vals, 
 inline size_t tile_depth_list_words(size_t n_tiles) { return n_tiles + 1; }
 uint32_t tile_depth_sort_cap();
 
-// out_format: kOut* (16- or 4-byte pixels)
+// out_format: kOut* (16- or 4-byte pixels, or the video planes, reassembled plane by plane: width, height, rows_padded, band_px even)
 void launch_unshard(hipStream_t s, const void* gathered, void* out, int width, int height, int shard_count, int rows_padded, int band_px,
                     int out_format);
 void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int width, int height, int face_size, int equirect,

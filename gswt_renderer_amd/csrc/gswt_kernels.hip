@@ -2385,6 +2385,49 @@ __device__ __forceinline__ void store_unorm8(float4* out, size_t i, const float4
     reinterpret_cast<uint32_t*>(out)[i] = OUTF == kOutBGRA8 ? (b | g << 8 | r << 16 | a << 24) : (r | g << 8 | b << 16 | a << 24);
 }
 
+// The store of a final pixel in a 4:2:0 video format (gswt_hip.h, GSWT_VIDEO_*: BT.709, limited range), at (row, col) of this shard's
+// rows x out_w image; every operation is the one binary32 operation the header writes, in its order.  Luma: one byte per lane.  Chroma: the
+// lane -> pixel map (lx = (lane >> 4) * 4 + (lane & 3), ly = wave * 4 + ((lane & 15) >> 2)) puts the 2x2 block of an even (row, col) in
+// lanes l, l ^ 1, l ^ 4, l ^ 5 of one 16-lane DPP row, so the block's mean takes two DPP moves per component and no LDS: quad_perm [1,0,3,2]
+// adds the horizontal neighbour (l ^ 1), row_shl:4 hands lane l the sum of lane l + 4 (= l ^ 4 for the block's top lanes, whose bit 2 is
+// clear), and the top-left lane stores.  rows and out_w are even and the image's origin in the frame is a multiple of the tile, so a block is
+// wholly inside the frame or wholly outside: all four of its lanes reach this store together (every caller's bounds test removes
+// whole blocks).
+template <int CTRL>
+__device__ __forceinline__ float dpp_move_f32(float x)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float block_mean_2x2(float c)
+{
+    const float h = c + dpp_move_f32<0xB1>(c);               // quad_perm:[1,0,3,2]: c00 + c01 in the top lanes, c10 + c11 in the bottom ones
+    return (h + dpp_move_f32<0x104>(h)) * 0.25f;            // row_shl:4: (c00 + c01) + (c10 + c11) in the top lanes
+}
+template <int OUTF>
+__device__ __forceinline__ void store_video(float4* out, int rows, int out_w, int row, int col, bool inside, const float4& o)
+{
+    static_assert(OUTF == kOutNV12 || OUTF == kOutI420, "video formats only");
+    const float r = fminf(fmaxf(o.x, 0.0f), 1.0f), g = fminf(fmaxf(o.y, 0.0f), 1.0f), b = fminf(fmaxf(o.z, 0.0f), 1.0f);
+    const float yl = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+    const uint32_t y8 = (uint32_t)__builtin_rintf(16.0f + 219.0f * yl);
+    constexpr float kCb = (float)(1.0 / 1.8556), kCr = (float)(1.0 / 1.5748);
+    const float mb = block_mean_2x2((b - yl) * kCb), mr = block_mean_2x2((r - yl) * kCr);
+    if (!inside) return;
+    uint8_t* const plane_y = reinterpret_cast<uint8_t*>(out);
+    plane_y[(size_t)row * out_w + col] = (uint8_t)y8;
+    if (((row | col) & 1) != 0) return;
+    const uint32_t cb8 = (uint32_t)__builtin_rintf(128.0f + 224.0f * mb), cr8 = (uint32_t)__builtin_rintf(128.0f + 224.0f * mr);
+    uint8_t* const plane_c = plane_y + (size_t)rows * out_w;
+    if constexpr (OUTF == kOutNV12) {
+        // (row / 2) * out_w + col: the pair's byte offset, even
+        *reinterpret_cast<uint16_t*>(plane_c + (size_t)(row >> 1) * out_w + col) = (uint16_t)(cb8 | cr8 << 8);
+    } else {
+        const size_t half_w = (size_t)(out_w >> 1), ci = (size_t)(row >> 1) * half_w + (col >> 1);
+        plane_c[ci] = (uint8_t)cb8;
+        plane_c[(size_t)(rows >> 1) * half_w + ci] = (uint8_t)cr8;
+    }
+}
+
 // ---- the pieces k_composite, k_composite_dw and k_combine share: one statement each, so that the three stay bit-identical ----
 // Where a work item's screen tile lies: tile row tyl inside this shard's image (the rows it stores) and pixel origin (bx, by) in the frame
 // (a row-sharded ctx owns tile rows shard_index, + shard_count, ...)
@@ -2468,6 +2511,7 @@ __device__ __forceinline__ void comp_final_pixel(const Frame& f, const float4* b
     o.z = fmaf(T, bg.z, ab);
     o.w = fmaf(T, bg.w, 1.0f - T);
     if constexpr (OUTF == kOutF32) { if (orow < out_rows) out[(size_t)orow * f.out_w + (px - f.out_x0)] = o; }
+    else if constexpr (out_is_video(OUTF)) store_video<OUTF>(out, out_rows, f.out_w, orow, px - f.out_x0, orow < out_rows, o);
     else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px - f.out_x0), o);
 }
 
@@ -2844,6 +2888,28 @@ __global__ void k_unshard(const P* __restrict__ gathered, P* __restrict__ out, i
     out[(size_t)y * width + x] = gathered[src];
 }
 
+// The same for ONE PLANE of a video format (P: its sample, a byte or NV12's Cb Cr pair; TILE: the plane's rows per screen tile row, kTile or,
+// for the half-size chroma planes, kTile / 2).  gathered / out: the plane inside shard 0's image / inside the frame; stride: samples from
+// one shard's image to the next (the whole image of all planes, not this plane alone); width, height, rows_padded, band_px: the plane's.
+template <typename P, int TILE>
+__global__ void k_unshard_plane(const P* __restrict__ gathered, P* __restrict__ out, int width, int height,
+                                int shard_count, int rows_padded, int band_px, size_t stride)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= width || y >= height) return;
+    size_t src;
+    if (band_px > 0) {
+        const int shard = x / band_px;
+        src = (size_t)shard * stride + (size_t)y * band_px + (x - shard * band_px);
+    } else {
+        const int ty = y / TILE;
+        const int shard = ty % shard_count, tyl = ty / shard_count;
+        src = (size_t)shard * stride + ((size_t)tyl * TILE + (y % TILE)) * width + x;
+    }
+    out[(size_t)y * width + x] = gathered[src];
+}
+
 // ---- launch wrappers (called from gswt_api.hip) -------------------------------------
 void launch_chunk_tabs(hipStream_t s, const DrawDev* draws, const uint32_t* xcd_first, uint32_t n_draws, uint2* chunk_tab, uint2* chunk_tab_xcd,
                        const uint64_t per_xcd[8], uint64_t longest)
@@ -3076,7 +3142,9 @@ static void launch_composite_z(hipStream_t s, const Frame& f, const FrameBufs& b
 void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
                       uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format)
 {
-    if (out_format == kOutRGBA8) launch_composite_z<kOutRGBA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    if (out_format == kOutNV12) launch_composite_z<kOutNV12>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    else if (out_format == kOutI420) launch_composite_z<kOutI420>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    else if (out_format == kOutRGBA8) launch_composite_z<kOutRGBA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
     else if (out_format == kOutBGRA8) launch_composite_z<kOutBGRA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
     else launch_composite_z<kOutF32>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
 }
@@ -3091,7 +3159,23 @@ void launch_unshard(hipStream_t s, const void* gathered, void* out, int width, i
                     int out_format)
 {
     const dim3 grid((width + 255) / 256, height);
-    if (out_format == kOutF32)
+    if (out_is_video(out_format)) {
+        // plane by plane: Y as bytes; the chroma planes are half-size images whose tile is 8 rows (k_unshard's TILE), NV12's as 2-byte pairs
+        const uint8_t* const src = static_cast<const uint8_t*>(gathered);
+        uint8_t* const dst = static_cast<uint8_t*>(out);
+        const int n = shard_count < 1 ? 1 : shard_count, hw = width / 2, hh = height / 2;
+        // a shard's own image: rows_padded x width (rows), height x band_px (columns)
+        const size_t shard_px = band_px > 0 ? (size_t)height * band_px : (size_t)rows_padded * width, frame_px = (size_t)width * height;
+        const dim3 hgrid((hw + 255) / 256, hh);
+        hipLaunchKernelGGL((k_unshard_plane<uint8_t, kTile>), grid, dim3(256), 0, s, src, dst, width, height, n, rows_padded, band_px, shard_px * 3u / 2u);
+        if (out_format == kOutNV12)
+            hipLaunchKernelGGL((k_unshard_plane<uint16_t, kTile / 2>), hgrid, dim3(256), 0, s, reinterpret_cast<const uint16_t*>(src + shard_px),
+                               reinterpret_cast<uint16_t*>(dst + frame_px), hw, hh, n, rows_padded / 2, band_px / 2, shard_px * 3u / 4u);
+        else
+            for (int p = 0; p < 2; p++)
+                hipLaunchKernelGGL((k_unshard_plane<uint8_t, kTile / 2>), hgrid, dim3(256), 0, s, src + shard_px + p * (shard_px / 4u),
+                                   dst + frame_px + p * (frame_px / 4u), hw, hh, n, rows_padded / 2, band_px / 2, shard_px * 3u / 2u);
+    } else if (out_format == kOutF32)
         hipLaunchKernelGGL(k_unshard<float4>, grid, dim3(256), 0, s, static_cast<const float4*>(gathered), static_cast<float4*>(out), width, height,
                            shard_count, rows_padded, band_px);
     else

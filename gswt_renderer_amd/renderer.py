@@ -36,6 +36,16 @@ def _out_dtype(out_format: int):
     return np.float32          # (an unknown format is refused by the library, GSWT_ERR_BAD_ARG, before anything is written)
 
 
+def video_planes(buf: np.ndarray, out_format: int, rows: int, out_w: int):
+    """The planes of a GSWT_VIDEO_* image of rows x out_w pixels held in the flat uint8 array buf (views, no copy):
+    (y, cbcr) with shapes [rows, out_w], [rows / 2, out_w / 2, 2] for NV12, (y, cb, cr) with [rows / 2, out_w / 2] chroma for I420."""
+    n, hr, hw = rows * out_w, rows // 2, out_w // 2
+    y = buf[:n].reshape(rows, out_w)
+    if out_format == L.GSWT_VIDEO_NV12:
+        return y, buf[n:n + 2 * hr * hw].reshape(hr, hw, 2)
+    return y, buf[n:n + hr * hw].reshape(hr, hw), buf[n + hr * hw:n + 2 * hr * hw].reshape(hr, hw)
+
+
 def make_draw(tile: L.TileUniforms, *, base=None, merged_range=None, merged_has_lod=False, corners=None,
               lod=None) -> L.Draw:
     """One draw of the loop renderer.rs:466-591.  base = (lod, tile, view) of a static list or
@@ -188,6 +198,10 @@ class GSWTRenderer:
         """camera / scene: 176 / 160-byte uniform blocks (any ctypes struct or bytes of that layout).
         Returns the image [rows, W, 4] on the host -- f32 for GSWT_OUT_RGBA32F, uint8 in the channel order of
         GSWT_OUT_RGBA8_UNORM / GSWT_OUT_BGRA8_UNORM --, or None when out_device_ptr is given.
+        out_format GSWT_VIDEO_NV12 / GSWT_VIDEO_I420 (4:2:0, BT.709 limited range; width and height even): returns the planes as
+        uint8 arrays instead of one image, (y, cbcr) with shapes [rows, W], [rows / 2, W / 2, 2] for NV12 and (y, cb, cr) with
+        [rows / 2, W / 2] chroma planes for I420; out_device_ptr then addresses gswt_out_image_bytes(out_format, rows, W) bytes.
+        With depth=True the depth image follows the planes: (y, cbcr, depth) / (y, cb, cr, depth).
         depth=True: returns (image, depth), depth the composited depth image [rows, W] f32 of gswt_render_depth (NDC depth
         blended like a colour channel over bg_depth, or 1.0 without one).  With out_device_ptr the depth goes to
         out_depth_device_ptr (rows x out_w f32 on the device) when that is given."""
@@ -215,22 +229,28 @@ class GSWTRenderer:
             self._check(self._lib.gswt_render_depth(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
                                                     1 if bg_on_device else 0, C.c_void_p(out_device_ptr), zd, 1))
             return None
-        out = np.empty((rows, out_w, 4), dtype=_out_dtype(out_format))
+        video = out_format in (L.GSWT_VIDEO_NV12, L.GSWT_VIDEO_I420)
+        if video:       # (an odd size has no plane layout, 0 bytes: the library refuses the call before it writes anything)
+            out = np.empty(max(int(self._lib.gswt_out_image_bytes(out_format, rows, out_w)), 16), dtype=np.uint8)
+            planes = lambda: video_planes(out, out_format, rows, out_w)
+        else:
+            out = np.empty((rows, out_w, 4), dtype=_out_dtype(out_format))
         if depth:
             z = np.empty((rows, out_w), dtype=np.float32)
             self._check(self._lib.gswt_render_depth(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
                                                     1 if bg_on_device else 0, _ptr(out), _ptr(z), 0))
-            return out, z
+            return planes() + (z,) if video else (out, z)
         self._check(self._lib.gswt_render(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
                                           1 if bg_on_device else 0, _ptr(out), 0))
-        return out
+        return planes() if video else out
 
     def render_async(self, camera, scene, width: int, height: int, out_device_ptr: int, *, culling_dist: float = 1.0,
                      lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
                      transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba_ptr: int = 0, bg_depth_ptr: int = 0,
                      out_format: int = L.GSWT_OUT_RGBA32F, out_depth_ptr: int = 0) -> int:
         """Queues a frame (device pointers only) and returns a ticket for render_wait.  out_device_ptr holds rows x out_w x 4
-        f32, or bytes for the 8-bit out_format values; out_depth_ptr (optional) receives the depth image, rows x out_w f32
+        f32, or bytes for the 8-bit out_format values, or the planes of a GSWT_VIDEO_* format (gswt_out_image_bytes(out_format,
+        rows, out_w) bytes, width and height even; see video_planes); out_depth_ptr (optional) receives the depth image, rows x out_w f32
         (gswt_render_async_depth)."""
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
@@ -351,7 +371,8 @@ class GSWTRenderer:
 
     def unshard_format(self, gathered_device_ptr: int, width: int, height: int, shard_count: int, mode, out_format: int,
                        out_device_ptr: int):
-        """unshard_mode for any output format (GSWT_OUT_*: 16- or 4-byte pixels)."""
+        """unshard_mode for any output format (GSWT_OUT_*: 16- or 4-byte pixels; GSWT_VIDEO_*: every gathered shard is a complete
+        image of planes, the frame is reassembled plane by plane)."""
         m = L.GSWT_SHARD_COLUMNS if mode in ("cols", "columns", L.GSWT_SHARD_COLUMNS) and mode != 0 else L.GSWT_SHARD_ROWS
         self._check(self._lib.gswt_unshard_format(self._h, C.c_void_p(gathered_device_ptr), width, height, shard_count, m, out_format,
                                                   C.c_void_p(out_device_ptr)))

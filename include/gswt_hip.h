@@ -136,7 +136,7 @@ typedef struct {
     int32_t shard_index;
     int32_t shard_count;
     int32_t shard_mode;       /* GSWT_SHARD_* */
-    uint32_t out_format;      /* GSWT_OUT_*; 0 (a zero-initialised config) is the RGBA f32 image */
+    uint32_t out_format;      /* GSWT_OUT_* or GSWT_VIDEO_*; 0 (a zero-initialised config) is the RGBA f32 image */
 } gswt_render_config;
 
 enum { GSWT_SHARD_ROWS = 0, GSWT_SHARD_COLUMNS = 1 };
@@ -152,6 +152,30 @@ enum { GSWT_SHARD_ROWS = 0, GSWT_SHARD_COLUMNS = 1 };
  * rows_out x out_w x 4 BYTES (pass the byte buffer cast to float *); shard geometry (gswt_shard_rows_padded,
  * gswt_shard_cols_padded) counts pixels and does not change. */
 enum { GSWT_OUT_RGBA32F = 0, GSWT_OUT_RGBA8_UNORM = 1 /* bytes R, G, B, A */, GSWT_OUT_BGRA8_UNORM = 2 /* bytes B, G, R, A */ };
+
+/* 4:2:0 video frames (gswt_render_config.out_format, accepted wherever an output format is): what a video encoder reads, BT.709,
+ * limited ("video") range, 12 bits per pixel, written by the compositor's own store (nothing in the reference corresponds to them).
+ * width and height must be even (GSWT_ERR_BAD_ARG before anything is enqueued otherwise).  The output pointer addresses the planes
+ * back to back without padding, rows_out * out_w * 3 / 2 bytes (gswt_out_image_bytes); a shard's buffer is itself a complete small
+ * image of out_w x rows_out (both multiples of 16), its padding rows / columns zero bytes in every plane.
+ * A video frame is a pure function of the GSWT_OUT_RGBA32F pixels o the same call would write (alpha is dropped), every operation
+ * one binary32 operation, not fused:
+ *     c   = fminf(fmaxf(o.c, 0), 1)                      for c = r, g, b   (NaN -> 0, as q() above)
+ *     yl  = (0.2126f * r + 0.7152f * g) + 0.0722f * b    BT.709 luma, left to right
+ *     Y   = (uint8) round_half_even(16.0f + 219.0f * yl)                    16..235
+ *     cb  = (b - yl) * fl(1 / 1.8556),   cr = (r - yl) * fl(1 / 1.5748)     per pixel, in [-0.5, 0.5]; fl = the double quotient rounded to binary32
+ *     per 2x2 block (x, y even):  m = ((c00 + c01) + (c10 + c11)) * 0.25f   c00 top left, c01 top right, c10 bottom left
+ *     Cb  = (uint8) round_half_even(128.0f + 224.0f * m_cb),  Cr likewise   16..240
+ * Chroma is the plain mean of the block's four samples, i.e. sited at the block's centre (as JPEG / MPEG-1, not the co-sited-left
+ * convention of MPEG-2 / H.264's default).  So a video frame equals this function of its f32 frame byte for byte, in every mode and
+ * compositor variant.  The depth image of gswt_render_depth stays rows_out x out_w f32. */
+enum {
+    GSWT_VIDEO_NV12 = 16,  /* plane Y (rows x out_w bytes), then ONE plane of interleaved Cb, Cr pairs (rows/2 x out_w bytes) */
+    GSWT_VIDEO_I420 = 17   /* plane Y, then plane Cb (rows/2 x out_w/2 bytes), then plane Cr (the same size) */
+};
+/* Bytes of a rows x out_w image in any output format (16 / 4 bytes per pixel, or the planes above); 0 for an unknown format, a
+ * negative size or odd video dimensions.  The library sizes its own copies, clears and gathers with it. */
+GSWT_API size_t gswt_out_image_bytes(int out_format, int rows, int out_w);
 
 /* Per-stage device times of the last gswt_render (hipEvent, ms) and workload sizes.  ms_ranges is ~0 since the per-tile
  * [start, end) table is left by the last pass of the pair sort (its time is inside ms_sort); ms_scan is unused (no scan launch). */
@@ -293,9 +317,11 @@ GSWT_API int gswt_debug_read_merged(gswt_ctx *ctx, uint32_t *packed_list, uint32
  * NULL for transparent black; bg_depth (W*H f32) is the proxy depth buffer (:433-434) or
  * NULL for the 1.0 clear (:436).  out_rgba receives rows_out*W*4 f32 where rows_out = H,
  * or the shard's rows when cfg->shard_count > 1 (see gswt_shard_rows); for the 8-bit
- * cfg->out_format values rows_out*W*4 bytes.  Pointers are device pointers when
- * *_on_device is nonzero, host pointers otherwise.  An out_format other than GSWT_OUT_*
- * returns GSWT_ERR_BAD_ARG before anything is enqueued. */
+ * cfg->out_format values rows_out*W*4 bytes, for the video ones rows_out*W*3/2 bytes
+ * (gswt_out_image_bytes).  Pointers are device pointers when *_on_device is nonzero,
+ * host pointers otherwise.  An out_format other than GSWT_OUT_* / GSWT_VIDEO_*, or a
+ * video format with an odd width or height, returns GSWT_ERR_BAD_ARG before anything is
+ * enqueued. */
 GSWT_API int gswt_render(gswt_ctx *ctx, const gswt_camera_uniforms *camera,
                          const gswt_scene_uniforms *scene, const gswt_render_config *cfg,
                          int width, int height,
@@ -441,7 +467,8 @@ GSWT_API int gswt_unshard(gswt_ctx *ctx, const float *gathered, int width, int h
 /* The same for either shard mode (GSWT_SHARD_COLUMNS: the gathered shards are H x gswt_shard_cols_padded images). */
 GSWT_API int gswt_unshard_mode(gswt_ctx *ctx, const float *gathered, int width, int height,
                                int shard_count, int shard_mode, float *out_rgba);
-/* The same for any output format (GSWT_OUT_*: 16 or 4 bytes per pixel); gswt_unshard_mode is out_format = GSWT_OUT_RGBA32F of it. */
+/* The same for any output format (GSWT_OUT_*: 16 or 4 bytes per pixel; GSWT_VIDEO_*: every shard a complete image of planes, reassembled
+ * plane by plane, width and height even); gswt_unshard_mode is out_format = GSWT_OUT_RGBA32F of it. */
 GSWT_API int gswt_unshard_format(gswt_ctx *ctx, const void *gathered, int width, int height,
                                  int shard_count, int shard_mode, int out_format, void *out);
 

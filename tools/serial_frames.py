@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """N frames of a workload one at a time (no overlap): for per-kernel isolated durations under rocprofv3 --kernel-trace.
-GSWT_OUT=rgba8 | bgra8 renders the frames in that 8-bit output format (default f32)."""
+GSWT_OUT=rgba8 | bgra8 | nv12 | i420 renders the frames in that 8-bit or 4:2:0 video output format (default f32)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,8 +36,9 @@ shard = None
 if os.environ.get("GSWT_SHARD"):                   # "rank,world[,cols]": one rank's share of a sharded frame
     a = os.environ["GSWT_SHARD"].split(",")
     shard = (int(a[0]), int(a[1]), "cols") if len(a) > 2 else (int(a[0]), int(a[1]))
-fmt = {"f32": L.GSWT_OUT_RGBA32F, "rgba8": L.GSWT_OUT_RGBA8_UNORM, "bgra8": L.GSWT_OUT_BGRA8_UNORM}[os.environ.get("GSWT_OUT", "f32")]
-out = torch.empty((H, W, 4), dtype=torch.float32 if fmt == L.GSWT_OUT_RGBA32F else torch.uint8, device="cuda")
+fmt = {"f32": L.GSWT_OUT_RGBA32F, "rgba8": L.GSWT_OUT_RGBA8_UNORM, "bgra8": L.GSWT_OUT_BGRA8_UNORM, "nv12": L.GSWT_VIDEO_NV12,
+       "i420": L.GSWT_VIDEO_I420}[os.environ.get("GSWT_OUT", "f32")]
+out = torch.empty((H * W * 16,), dtype=torch.uint8, device="cuda")      # (the largest format's size)
 torch.cuda.synchronize()
 for i in range(n):
     r.render_wait(r.render_async(cu, su, W, H, out.data_ptr(), transmittance_eps=1e-5, order_mode=order, out_format=fmt, **({"shard": shard} if shard else {})))
