@@ -112,7 +112,7 @@ class Timings(C.Structure):
                 ("ms_sort", C.c_float), ("ms_ranges", C.c_float), ("ms_composite", C.c_float),
                 ("ms_total", C.c_float), ("n_draws", C.c_uint32), ("n_instanced", C.c_uint64),
                 ("n_visible", C.c_uint64), ("n_pairs", C.c_uint64), ("n_tiles", C.c_uint32),
-                ("_pad", C.c_uint32), ("ms_composite_kernel", C.c_float), ("_pad2", C.c_float)]
+                ("_pad", C.c_uint32), ("ms_composite_kernel", C.c_float), ("ms_pick_resolve", C.c_float)]
 
 
 class SortedTile(C.Structure):
@@ -155,7 +155,15 @@ class WorkerConfig(C.Structure):
                 ("neighbors", C.c_void_p)]
 
 
+class Pick(C.Structure):
+    """gswt_pick: one pixel of the pick image (gswt_render_pick)."""
+    _fields_ = [("map_index", C.c_uint32), ("entry", C.c_uint32), ("depth", C.c_float), ("weight", C.c_float)]
+
+
+PICK_NONE = 0xFFFFFFFF        # map_index and entry of a pixel no splat covers
+
 assert C.sizeof(Cell) == 260 and C.sizeof(CellState) == 20
+assert C.sizeof(Pick) == 16
 
 assert C.sizeof(CameraUniforms) == 176 and C.sizeof(SceneUniforms) == 160 and C.sizeof(TileUniforms) == 80
 
@@ -188,6 +196,8 @@ SYMBOLS = {
     "gswt_render_async": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "gswt_render_depth": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int]),
     "gswt_render_async_depth": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int)]),
+    "gswt_render_pick": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_int]),
+    "gswt_render_async_pick": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     "gswt_render_wait": (C.c_int, [_P, C.c_int]),
     "gswt_render_fence": (C.c_int, [_P, C.c_int]),
     "gswt_frame_slots": (C.c_int, []),

@@ -197,11 +197,12 @@ struct FrameArgs {
     const float* d_bgd = nullptr;
     float4* d_out = nullptr;
     float* d_out_depth = nullptr;          // gswt_render_depth / gswt_render_async_depth: the frame's depth image (null: none)
+    gswt_pick* d_out_pick = nullptr;       // gswt_render_pick / gswt_render_async_pick: the frame's pick image (null: none)
 };
 
 // A frame's events on its slot's stream.  GSWT_OPT_TIMING >= 1 records kEvStart, kEvEnd and the compositor kernel's pair, 2 also the
 // stage boundaries in between (nothing runs between kEvSorted and kEvRanges); kEvDone follows the frame's last command in any case.
-enum FrameEvent { kEvStart, kEvProjected, kEvEmitted, kEvSorted, kEvRanges, kEvEnd, kEvCompositeBegin, kEvCompositeEnd, kEvDone, kFrameEvents };
+enum FrameEvent { kEvStart, kEvProjected, kEvEmitted, kEvSorted, kEvRanges, kEvEnd, kEvCompositeBegin, kEvCompositeEnd, kEvPickBegin, kEvPickEnd, kEvDone, kFrameEvents };
 
 // One frame in flight.  Each slot owns a stream and every per-frame buffer, so two frames overlap on the GPU:
 // the latency-bound kernels of one (sort passes, single-workgroup scans, tails) fill the gaps of the other.
@@ -242,6 +243,8 @@ struct FrameSlot {
     uint32_t n_launch_eff = 0;             // positions of the launch table this frame's grids cover
     DevBuf<float4> partials;
     DevBuf<float> partials_z;              // frames that write their depth: a segment's partial depth beside its partial colour
+    DevBuf<uint2> partials_pick;           // frames that write their pick: a segment's (largest weight, pair) beside its partial colour
+    bool pick_timed = false;               // this frame's k_pick_resolve carries kEvPickBegin / kEvPickEnd
     DevBuf<float4> col_f;                  // debug draw modes: float colours per slot
     DevBuf<float> depths;                  // per-slot depth: frames with a proxy depth buffer, GSWT_ORDER_DEPTH or a depth image only
     // hipGraph replay (GSWT_OPT_GRAPH): the chain of kernel nodes of this slot's frames and the argument records they were last set to
@@ -261,7 +264,7 @@ struct FrameSlot {
     {
         rects.release(); recs.release(); cell_culled.release(); live_tab.release(); live_cid.release(); live_cnt.release(); block_sums.release(); draw_culled.release(); keys_a.release();
         keys_b.release(); vals_a.release(); vals_b.release(); ghist.release(); ranges.release(); item_base.release();
-        aux_a.release(); aux_b.release(); partials.release(); partials_z.release(); item_tab.release(); col_f.release(); depths.release();
+        aux_a.release(); aux_b.release(); partials.release(); partials_z.release(); partials_pick.release(); item_tab.release(); col_f.release(); depths.release();
     }
 };
 
@@ -345,6 +348,7 @@ struct gswt_ctx {
     int last_slot = 0;
     DevBuf<float4> bg_rgba, out_img;
     DevBuf<float> bg_depth, out_depth_img;       // (gswt_render's staging of host images)
+    DevBuf<uint4> out_pick_img;
     DevBuf<Varyings> dbg;
     // options
     int opt_no_prefilter = 0;
@@ -597,7 +601,7 @@ void gswt_destroy(gswt_ctx* c)
     c->gather_buf.release();
     c->tex.release(); c->static_list.release(); c->static_boxes.release(); c->hmap.release(); for (auto& ds : c->sets) ds.release();
     c->raw_depth.release(); 
-    c->mg_ws.release(); c->sky_faces.release(); c->proxy_tex.release(); c->bg_rgba.release(); c->out_img.release(); c->bg_depth.release(); c->out_depth_img.release(); c->dbg.release();
+    c->mg_ws.release(); c->sky_faces.release(); c->proxy_tex.release(); c->bg_rgba.release(); c->out_img.release(); c->bg_depth.release(); c->out_depth_img.release(); c->out_pick_img.release(); c->dbg.release();
     for (auto& sl : c->slots) {
         sl.release_graph();
         sl.release_buffers();
@@ -1072,6 +1076,7 @@ static int set_draws_impl(gswt_ctx* c, const gswt_draw* draws, int n_draws, cons
         d.tile_idx = g.tile.tile_id[1]; d.tile_view = g.tile.tile_id[2];
         d.single_lod_id = g.tile.single_lod_id;
         d.map_coord[0] = g.tile.map_coord[0]; d.map_coord[1] = g.tile.map_coord[1];
+        d.map_index = g.tile.map_index;
         d.off[0] = g.tile.offset[0]; d.off[1] = g.tile.offset[1]; d.off[2] = g.tile.offset[2];
         d.cull_enable = g.cull_enable;
         d.lod = g.lod;
@@ -1610,7 +1615,7 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
 {
     const FrameArgs& a = sl.args;
     const size_t nt = (size_t)n_tiles, n_slots_all = (size_t)D.n_chunks * kChunk;
-    const bool depth_order = a.cfg.order_mode == GSWT_ORDER_DEPTH, need_depths = a.d_bgd != nullptr || depth_order || a.d_out_depth != nullptr;
+    const bool depth_order = a.cfg.order_mode == GSWT_ORDER_DEPTH, need_depths = a.d_bgd != nullptr || depth_order || a.d_out_depth != nullptr || a.d_out_pick != nullptr;
     const uint32_t seg = (uint32_t)c->opt_segment;
     b.n_cells = f.band_cull ? (2u * f.map_half_wh[0] + 1u) * (2u * f.map_half_wh[1] + 1u) : 0u;
     HIP_TRY(c, sl.rects.ensure(n_slots_all + 1));
@@ -1648,12 +1653,14 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     HIP_TRY(c, sl.item_base.ensure_roomy(nt + 2));
     HIP_TRY(c, sl.partials.ensure_roomy((nt + cap / seg + 1) * 256));
     if (a.d_out_depth) HIP_TRY(c, sl.partials_z.ensure_roomy((nt + cap / seg + 1) * 256));
+    if (a.d_out_pick) HIP_TRY(c, sl.partials_pick.ensure_roomy((nt + cap / seg + 1) * 256));
     HIP_TRY(c, sl.item_tab.ensure_roomy(nt + cap / seg + 2));
 
     b.draws = D.draws.p; b.n_chunks = D.n_chunks; b.chunk_tab = D.chunk_tab.p; b.chunk_tab_xcd = D.chunk_tab_xcd.p;
     b.static_list = c->static_list.p; b.merged_list = D.merged_list.p; b.merged_map = D.merged_map.p;
     b.tex = c->tex.p; b.hmap = c->hmap.p; b.boxes = c->static_boxes.p;
     b.bg_rgba = a.d_bg; b.bg_depth = a.d_bgd; b.out = a.d_out; b.out_depth = a.d_out_depth; b.host_counters = sl.hc_dev;
+    b.out_pick = reinterpret_cast<uint4*>(a.d_out_pick);
     b.n_tiles = (uint32_t)n_tiles; b.pair_cap = cap; b.seg = seg;
     b.rects = sl.rects.p; b.recs = sl.recs.p; b.depths = need_depths ? sl.depths.p : nullptr; b.col_f = sl.col_f.p; b.dbg = c->dbg.p;
     b.draw_culled = sl.draw_culled.p; b.cell_culled = sl.cell_culled.p;
@@ -1667,6 +1674,10 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     b.ranges = sl.ranges.p;
     b.long_tiles = reinterpret_cast<uint32_t*>(sl.ranges.p) + range_words;
     b.item_base = sl.item_base.p; b.item_tab = sl.item_tab.p; b.partials = sl.partials.p; b.partials_z = a.d_out_depth ? sl.partials_z.p : nullptr;
+    b.partials_pick = a.d_out_pick ? sl.partials_pick.p : nullptr;
+    const bool time_pick = a.d_out_pick != nullptr && c->opt_timing >= 1;
+    b.ev_pick_begin = time_pick ? sl.ev[kEvPickBegin] : nullptr; b.ev_pick_end = time_pick ? sl.ev[kEvPickEnd] : nullptr;
+    sl.pick_timed = time_pick && n_tiles > 0;
     return GSWT_OK;
 }
 
@@ -1755,6 +1766,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
     }
     if (a.cfg.shard_count > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(a.d_out, 0, out_image_bytes((int)a.cfg.out_format, out_rows, f.out_w), s));
     if (a.cfg.shard_count > 1 && out_px > 0 && a.d_out_depth) HIP_TRY(c, hipMemsetAsync(a.d_out_depth, 0, out_px * sizeof(float), s));
+    if (a.cfg.shard_count > 1 && out_px > 0 && a.d_out_pick) HIP_TRY(c, hipMemsetAsync(a.d_out_pick, 0, out_px * sizeof(gswt_pick), s));
     // GSWT_OPT_GRAPH: from here to the end of the frame the launch sites record instead of launching (frames that carry timing
     // events, debug varyings and shards without tiles launch as before)
     const bool use_graph = c->opt_graph != 0 && c->opt_timing == 0 && !dbg && n_tiles > 0 && sl.hc_dev != nullptr;
@@ -1794,7 +1806,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         if (grc != GSWT_OK) return grc;
     }
     HIP_TRY(c, hipGetLastError());
-    // k_combine (the frame's last kernel) stores the result counters into the pinned host words itself; only a frame
+    // k_combine (the last kernel of the frame, or the last but k_pick_resolve) stores the result counters into the pinned host words itself; only a frame
     // without screen tiles has no such launch
     if (n_tiles == 0 || !sl.hc_dev) HIP_TRY(c, hipMemcpyAsync(sl.hc, b.counters, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipEventRecord(ev[kEvDone], s));
@@ -1853,6 +1865,7 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
     if (sl.timing_level >= 1) {
         HIP_TRY(c, hipEventElapsedTime(&t.ms_total, ev[kEvStart], ev[kEvEnd]));
         HIP_TRY(c, hipEventElapsedTime(&t.ms_composite_kernel, ev[kEvCompositeBegin], ev[kEvCompositeEnd]));
+        if (sl.pick_timed) HIP_TRY(c, hipEventElapsedTime(&t.ms_pick_resolve, ev[kEvPickBegin], ev[kEvPickEnd]));
     }
     t.n_draws = c->sets[sl.set].n_draws; t.n_instanced = c->sets[sl.set].n_entries; t.n_visible = sl.hc[0]; t.n_pairs = P; t.n_tiles = (uint32_t)sl.n_tiles;
     return GSWT_OK;
@@ -1860,14 +1873,14 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
 
 // Submits a frame in slot `sl` (gswt_render, gswt_render_async): the slot's stream on first use, the draw set current now, the arguments.
 static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
-                        int width, int height, const float4* d_bg, const float* d_bgd, float4* d_out, float* d_out_depth)
+                        int width, int height, const float4* d_bg, const float* d_bgd, float4* d_out, float* d_out_depth, gswt_pick* d_out_pick)
 {
     if (!sl.stream) HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));      // a slot past the fourth: first use
     activate_pending(c, false);
     sl.set = c->cur_set;
     FrameArgs& a = sl.args;
     a.cam = *cam; a.su = *su; a.cfg = *cfg; a.width = width; a.height = height; a.d_bg = d_bg; a.d_bgd = d_bgd; a.d_out = d_out;
-    a.d_out_depth = d_out_depth;
+    a.d_out_depth = d_out_depth; a.d_out_pick = d_out_pick;
     sl.strict_vs = c->opt_strict_vs != 0;
     return enqueue_frame(c, sl);
 }
@@ -1882,12 +1895,21 @@ int gswt_render(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_u
 int gswt_render_depth(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
                       int width, int height, const float* bg_rgba, const float* bg_depth, int bg_on_device, float* out_rgba,
                       float* out_depth, int out_on_device)
+{
+    return gswt_render_pick(c, cam, su, cfg, width, height, bg_rgba, bg_depth, bg_on_device, out_rgba, out_depth, nullptr, out_on_device);
+}
+
+int gswt_render_pick(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
+                     int width, int height, const float* bg_rgba, const float* bg_depth, int bg_on_device, float* out_rgba,
+                     float* out_depth, gswt_pick* out_pick, int out_on_device)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;
     int rc = validate_frame(c, cam, su, cfg, width, height, out_rgba);
     if (rc != GSWT_OK) return rc;
     if (out_depth && static_cast<const void*>(out_depth) == static_cast<const void*>(out_rgba))
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_render_depth: out_depth is out_rgba");
+    if (out_pick && (static_cast<const void*>(out_pick) == static_cast<const void*>(out_rgba) || static_cast<const void*>(out_pick) == static_cast<const void*>(out_depth)))
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render_pick: out_pick is out_rgba or out_depth");
     hipSetDevice(c->device);
     hipStream_t s = c->stream;
     HIP_TRY(c, collect_pending(c));                // frames still in flight from the async API keep their tickets
@@ -1897,7 +1919,7 @@ try {
     const int out_w = cols ? gswt_shard_cols_padded(width, sc) : width;
     const size_t out_px = (size_t)out_rows * out_w, npx = (size_t)width * height;
     const size_t out_bytes = out_image_bytes((int)cfg->out_format, out_rows, out_w);
-    const float4* d_bg = nullptr; const float* d_bgd = nullptr; float4* d_out = nullptr; float* d_outz = nullptr;
+    const float4* d_bg = nullptr; const float* d_bgd = nullptr; float4* d_out = nullptr; float* d_outz = nullptr; gswt_pick* d_outp = nullptr;
     if (bg_rgba) {
         if (bg_on_device) d_bg = reinterpret_cast<const float4*>(bg_rgba);
         else { HIP_TRY(c, c->bg_rgba.ensure(npx)); HIP_TRY(c, hipMemcpyAsync(c->bg_rgba.p, bg_rgba, npx * 16, hipMemcpyHostToDevice, s)); d_bg = c->bg_rgba.p; }
@@ -1912,17 +1934,22 @@ try {
         if (out_on_device) d_outz = out_depth;
         else { HIP_TRY(c, c->out_depth_img.ensure(out_px)); d_outz = c->out_depth_img.p; }
     }
+    if (out_pick) {
+        if (out_on_device) d_outp = out_pick;
+        else { HIP_TRY(c, c->out_pick_img.ensure(out_px)); d_outp = reinterpret_cast<gswt_pick*>(c->out_pick_img.p); }
+    }
     int si0 = 0;
     for (int k = 0; k < kFrameSlots; k++) if (!c->slots[k].pending) { si0 = k; break; }
     FrameSlot& sl = c->slots[si0];
     if (sl.pending) return fail(c, GSWT_ERR_STATE, "gswt_render: every frame slot holds an uncollected gswt_render_async ticket");
-    rc = submit_frame(c, sl, cam, su, cfg, width, height, d_bg, d_bgd, d_out, d_outz);
+    rc = submit_frame(c, sl, cam, su, cfg, width, height, d_bg, d_bgd, d_out, d_outz, d_outp);
     if (rc != GSWT_OK) return rc;
     rc = finish_frame(c, sl);
     if (rc != GSWT_OK) return rc;
     if (!out_on_device) {
         HIP_TRY(c, hipMemcpyAsync(out_rgba, d_out, out_bytes, hipMemcpyDeviceToHost, s));
         if (out_depth) HIP_TRY(c, hipMemcpyAsync(out_depth, d_outz, out_px * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out_pick) HIP_TRY(c, hipMemcpyAsync(out_pick, d_outp, out_px * sizeof(gswt_pick), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
     return GSWT_OK;
@@ -1937,12 +1964,22 @@ int gswt_render_async(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_s
 int gswt_render_async_depth(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
                             int width, int height, const float* bg_rgba_dev, const float* bg_depth_dev, float* out_rgba_dev,
                             float* out_depth_dev, int* ticket)
+{
+    return gswt_render_async_pick(c, cam, su, cfg, width, height, bg_rgba_dev, bg_depth_dev, out_rgba_dev, out_depth_dev, nullptr, ticket);
+}
+
+int gswt_render_async_pick(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
+                           int width, int height, const float* bg_rgba_dev, const float* bg_depth_dev, float* out_rgba_dev,
+                           float* out_depth_dev, gswt_pick* out_pick_dev, int* ticket)
 try {
     if (!c || !ticket) return GSWT_ERR_BAD_ARG;
     int rc = validate_frame(c, cam, su, cfg, width, height, out_rgba_dev);
     if (rc != GSWT_OK) return rc;
     if (out_depth_dev && static_cast<const void*>(out_depth_dev) == static_cast<const void*>(out_rgba_dev))
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_render_async_depth: out_depth_dev is out_rgba_dev");
+    if (out_pick_dev && (static_cast<const void*>(out_pick_dev) == static_cast<const void*>(out_rgba_dev) ||
+                         static_cast<const void*>(out_pick_dev) == static_cast<const void*>(out_depth_dev)))
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render_async_pick: out_pick_dev is out_rgba_dev or out_depth_dev");
     hipSetDevice(c->device);
     // lowest free slot (a caller that keeps fewer frames in flight than there are slots then cycles over fewer buffer sets:
     // the per-frame buffers of a c5-sized frame are ~5 GB per slot); all busy: the oldest frame is collected first
@@ -1961,7 +1998,7 @@ try {
     sl.seq = ++c->frame_seq;
     sl.gather_recorded = false;
     rc = submit_frame(c, sl, cam, su, cfg, width, height, reinterpret_cast<const float4*>(bg_rgba_dev), bg_depth_dev,
-                      reinterpret_cast<float4*>(out_rgba_dev), out_depth_dev);
+                      reinterpret_cast<float4*>(out_rgba_dev), out_depth_dev, out_pick_dev);
     if (rc != GSWT_OK) return rc;
     sl.pending = true; sl.collected = false;
     *ticket = si;

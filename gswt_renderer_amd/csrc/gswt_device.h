@@ -54,6 +54,8 @@ struct DrawDev {
     uint32_t map_coord[2];    // TileUniforms.map_coord (sphere surface)
     uint32_t box_base;        // static draws: first chunk box of the draw's list (chunk k = the k-th 256 entries from the END of the list); ~0: none
     uint32_t xcd;             // the XCD (0..7) all chunks of this draw are projected on (gswt_set_draws: the least loaded one when the draw is planned)
+    uint32_t map_index;       // TileUniforms.map_index: the tile instance a static draw's splats belong to (pick output; a merged draw's come from merged_map)
+    uint32_t _pad;
 };
 
 // Per-frame constants (kernel argument, by value).
@@ -287,12 +289,13 @@ struct FrameBufs {
     const float *hmap, *boxes;                 // boxes: tile-local bounds of every chunk of the static lists (k_cull's chunk cull)
     const float4* bg_rgba; const float* bg_depth; float4* out;
     float* out_depth;                          // the frame's depth image (f32, the colour's geometry); null: none (gswt_render_depth)
+    uint4* out_pick;                           // the frame's pick image (gswt_pick records, the colour's geometry); null: none (gswt_render_pick)
     unsigned long long* host_counters;         // as the device sees them (null: copied behind the frame)
     // the sizes the buffers were planned for
     uint32_t n_chunks, n_cells, n_tiles, pair_cap, seg;
     // per slot (= composite order), per draw, per map cell (the band cull), per chunk
     uint2* rects; Rec* recs; float4* col_f; Varyings* dbg;
-    float* depths;                             // null unless the frame is depth-tested, depth-ordered or writes its depth
+    float* depths;                             // null unless the frame is depth-tested, depth-ordered or writes its depth or pick image
     uint32_t *draw_culled, *cell_culled, *live_cnt, *live_cid, *block_sums; uint4* live_tab;
     // the `ghist` region: counters (krange = counters[5], k_emit<DEPTH>), k_project's super-group sums, the two sorts' radix workspaces
     unsigned long long* counters;
@@ -303,6 +306,8 @@ struct FrameBufs {
     uint2* ranges; uint32_t* long_tiles;
     uint32_t* item_base; uint4* item_tab; float4* partials;
     float* partials_z;                         // a segment's partial depth per pixel beside `partials` (out_depth only)
+    uint2* partials_pick;                      // a segment's (largest weight, its pair) per pixel beside `partials` (out_pick only)
+    hipEvent_t ev_pick_begin, ev_pick_end;     // GSWT_OPT_TIMING: the events k_pick_resolve's launch carries (null: none)
     // the words k_cull clears: the head of `ghist` to the end of the pair sort's zeroed part, the `ranges` region, the depth sort's zeroed part
     uint32_t n_zero_head, n_zero_ranges, n_zero_depth;
 };
@@ -337,7 +342,8 @@ void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_c
 void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict);
 void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
 // b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer, the video formats
-// their planes of out_rows x f.out_w samples, both even), b.out_depth (when set) the depth image in f32.
+// their planes of out_rows x f.out_w samples, both even), b.out_depth (when set) the depth image in f32, b.out_pick (when set) the pick image
+// (gswt_pick records; then `vals` is also what k_pick_resolve reads behind the compositors).
 void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
                       uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format);
 void launch_totals(hipStream_t s, uint32_t* super_sums, uint32_t n_super, unsigned long long* counters, uint32_t pair_cap);

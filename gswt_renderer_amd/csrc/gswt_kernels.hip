@@ -2240,10 +2240,14 @@ constexpr uint32_t kNullRec = 256u;        // LDS record no pixel is ever inside
 // whose r^2 is +inf: the walk needs neither a shift nor an `i < n` test nor a mid-pair exit.
 // BATCH: pairs per staged batch (256 in k_composite, 128 in k_composite_dw); the list stride and the null record's index follow it.
 // ZOUT: also blends the splats' depths (s_dep, staged as for the depth test) into az with the colour's weights (gswt_hip.h, depth output).
-template <bool EARLY, bool DEPTH, bool COLF, bool ZOUT, uint32_t BATCH = 256u>
-__device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLane& g, uint32_t n, const float4* s_q0, const float4* s_q1,
+// PICK: also keeps the lane's largest weight so far (wmax, strict >: the front-most of equal weights stays) and the pair that had it (wpair,
+// its index in the sorted pair list; pair_base = the index of the batch's first pair).  Inside the walk the winner is the STEP number -- uniform,
+// so the select takes it from an SGPR -- and the step's list entry is looked up once behind the loop (gswt_hip.h, pick output).
+template <bool EARLY, bool DEPTH, bool COLF, bool ZOUT, bool PICK, uint32_t BATCH>
+__device__ __forceinline__ void composite_bin_walk_pick(const Frame& f, const CompLane& g, uint32_t n, const float4* s_q0, const float4* s_q1,
                                                    const float4* s_q2, const uint32_t* s_bb, const float* s_dep, uint16_t* wlist,
-                                                   float dbuf, float t_eps, float& T, float& ar, float& ag, float& ab, float& az, bool& wave_live)
+                                                   float dbuf, float t_eps, float& T, float& ar, float& ag, float& ab, float& az, bool& wave_live,
+                                                   uint32_t pair_base, float& wmax, uint32_t& wpair)
 {
     constexpr bool SDEP = DEPTH || ZOUT;                                       // the pairs' depths are staged in s_dep
     const uint32_t lane = g.lane, grp = g.grp;
@@ -2288,7 +2292,7 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
 #define GSWT_REC1(O) (*reinterpret_cast<const float4*>(q1b + (O)))
 #define GSWT_REC2(O) (*reinterpret_cast<const float4*>(q2b + (O)))
 #define GSWT_RECD(O) (*reinterpret_cast<const float*>(dpb + ((O) >> 2)))
-#define GSWT_STEP(Q0, Q1, Q2, DV)                                                                   \
+#define GSWT_STEP(Q0, Q1, Q2, DV, STEP)                                                             \
     {                                                                                               \
         const float pu_y = fmaf(Q0.y, ly, Q0.z);                                                    \
         const float pv_y = fmaf(Q1.y, ly, Q1.z);                                                    \
@@ -2308,6 +2312,7 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
             ag = fmaf(wgt, COLF ? Q2.y : (float)((cw >> 8) & 0xFFu), ag);                           \
             ab = fmaf(wgt, COLF ? Q2.z : (float)((cw >> 16) & 0xFFu), ab);                          \
             if (ZOUT) az = fmaf(wgt, DV, az);                                                       \
+            if (PICK) { if (wgt > wmax) { wmax = wgt; wstep = (STEP); } }                           \
             T = T - wgt;                                                                            \
         }                                                                                           \
     }
@@ -2321,20 +2326,22 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
         float4 a2 = make_float4(0.f, 0.f, 0.f, 0.f), b2 = a2;
         if (COLF) a2 = GSWT_REC2(kA);
         float da = SDEP ? GSWT_RECD(kA) : 0.0f, db = 0.0f;
+        uint32_t wstep = 0xFFFFFFFFu;                                      // PICK: the step of this batch that raised wmax last (none yet)
         for (uint32_t i = 0; i < n_steps; i += 2u) {
             kA = my_list[i + 2u];                                          // entry of step i+2: issued BEFORE the record reads, so that pinning it
             const float4 b0 = GSWT_REC0(kB), b1 = GSWT_REC1(kB);           // (below) waits for the oldest LDS read only, not for the records behind it
             if (COLF) b2 = GSWT_REC2(kB);
             if (SDEP) db = GSWT_RECD(kB);
             asm("" : "+v"(kA));
-            GSWT_STEP(a0, a1, a2, da)
+            GSWT_STEP(a0, a1, a2, da, i)
             kB = my_list[i + 3u];                                          // entry of step i+3
             a0 = GSWT_REC0(kA); a1 = GSWT_REC1(kA);                        // record of step i+2
             if (COLF) a2 = GSWT_REC2(kA);
             if (SDEP) da = GSWT_RECD(kA);
             asm("" : "+v"(kB));
-            GSWT_STEP(b0, b1, b2, db)
+            GSWT_STEP(b0, b1, b2, db, i + 1u)
         }
+        if (PICK) { if (wstep != 0xFFFFFFFFu) wpair = pair_base + ((uint32_t)my_list[wstep] >> 4); }      // entry = 16 x the pair's index in the batch
     }
 #undef GSWT_STEP
 #undef GSWT_REC0
@@ -2344,6 +2351,18 @@ __device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLan
     // Saturated pixels keep accumulating weights below t_eps (the oracle has no cut at all); the early-out is per wave
     // and per batch: once no pixel of the strip has T >= t_eps the wave stops binning and walking.
     if (EARLY && ballot64(T >= t_eps) == 0ull) wave_live = false;
+}
+
+// composite_bin_walk_pick without PICK: the walk of a frame without a pick output (the decoupled-waves compositor runs no other)
+template <bool EARLY, bool DEPTH, bool COLF, bool ZOUT, uint32_t BATCH = 256u>
+__device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLane& g, uint32_t n, const float4* s_q0, const float4* s_q1,
+                                                   const float4* s_q2, const uint32_t* s_bb, const float* s_dep, uint16_t* wlist,
+                                                   float dbuf, float t_eps, float& T, float& ar, float& ag, float& ab, float& az, bool& wave_live)
+{
+    float wmax = 0.0f;
+    uint32_t wpair = 0u;
+    composite_bin_walk_pick<EARLY, DEPTH, COLF, ZOUT, false, BATCH>(f, g, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, az, wave_live,
+                                                               0u, wmax, wpair);
 }
 
 // Measured and dropped in the walk (all bit-identical, c3, base 97 us):
@@ -2515,16 +2534,31 @@ __device__ __forceinline__ void comp_final_pixel(const Frame& f, const float4* b
     else if (orow < out_rows) store_unorm8<OUTF>(out, (size_t)orow * f.out_w + (px - f.out_x0), o);
 }
 
+// The pick of a final pixel (px, py inside the frame), stored at row orow of this shard's pick image as k_pick_resolve expects it: a hit as
+// (pair, 0, 0, weight > 0) -- the pair's index in the sorted list, resolved in place afterwards --, a pixel no splat covers as the final no-hit
+// record (~0, ~0, z_bg, 0), z_bg as the depth image has it.
+__device__ __forceinline__ void comp_final_pick(const Frame& f, const float* bg_depth, uint4* out_pick, int out_rows, int px, int py, int orow,
+                                                float wmax, uint32_t wpair)
+{
+    if (orow >= out_rows) return;
+    uint4 o = make_uint4(wpair, 0u, 0u, __float_as_uint(wmax));
+    if (!(wmax > 0.0f)) o = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, __float_as_uint(bg_depth ? bg_depth[(size_t)py * f.width + px] : 1.0f), 0u);
+    out_pick[(size_t)orow * f.out_w + (px - f.out_x0)] = o;
+}
+
 // OUTF: the output format (kOut*); only the final store differs.  ZOUT: the frame also writes its depth image (out_depth; a multi-segment
 // item leaves its partial depth in partials_z): the pairs' depths are staged as for the depth test, whether or not they are also tested.
-template <bool EARLY, bool DEPTH, bool COLF, int OUTF, bool ZOUT>
+// PICK: the frame also writes its pick image (out_pick, raw: comp_final_pick; a multi-segment item leaves its (largest weight, pair) in
+// partials_pick).  No staging of its own: the winner's depth is read by k_pick_resolve.
+template <bool EARLY, bool DEPTH, bool COLF, int OUTF, bool ZOUT, bool PICK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || COLF || ZOUT) ? 7 : 8, 8))) void k_composite(const Frame f, const uint2* __restrict__ ranges,
                                                    const uint32_t* __restrict__ item_base, const uint4* __restrict__ item_tab,
                                                    uint32_t seg, const uint32_t* __restrict__ vals, const Rec* __restrict__ recs,
                                                    const float* __restrict__ depths, const float4* __restrict__ col_f,
                                                    const float4* __restrict__ bg_rgba, const float* __restrict__ bg_depth,
                                                    float4* __restrict__ out, float4* __restrict__ partials,
-                                                   int n_tiles, int out_rows, float* __restrict__ out_depth, float* __restrict__ partials_z)
+                                                   int n_tiles, int out_rows, float* __restrict__ out_depth, float* __restrict__ partials_z,
+                                                   uint4* __restrict__ out_pick, uint2* __restrict__ partials_pick)
 {
     __shared__ float4 s_q0[257], s_q1[257];                     // [256] = the null record (list padding)
     __shared__ uint32_t s_bb[256];                              // the 16 sub-blocks a staged pair's pixel box touches (bit 4 strip + column group)
@@ -2578,6 +2612,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     if (DEPTH && inside) dbuf = bg_depth[(size_t)py * f.width + px];
     const float t_eps = f.t_eps;
     bool wave_live = true;
+    float wmax = 0.0f;                               // PICK: the largest weight of the item so far and its pair
+    uint32_t wpair = 0u;
     if (tid == 0) {
         if (EARLY) s_dead = make_uint4(0u, 0u, 0u, 0u);
         comp_null_record<DEPTH || ZOUT, COLF>(s_q0, s_q1, s_q2, s_dep, kNullRec);
@@ -2619,7 +2655,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
             slot_nxt = vals[min(base + 512u + tid, last_pair)];
         }
         if (wave_live)
-            composite_bin_walk<EARLY, DEPTH, COLF, ZOUT>(f, cl, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, az, wave_live);
+            composite_bin_walk_pick<EARLY, DEPTH, COLF, ZOUT, PICK, 256u>(f, cl, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, az, wave_live,
+                                                                     base, wmax, wpair);
 #ifdef GSWT_TRACE
         tr_walk += GSWT_NOW() - tr_t0;
 #endif
@@ -2645,6 +2682,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
         const size_t pi = (size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid;
         partials[pi] = make_float4(ar, ag, ab, T);
         if (ZOUT) partials_z[pi] = az;
+        if (PICK) partials_pick[pi] = make_uint2(__float_as_uint(wmax), wpair);
         return;
     }
     // pixel coordinates again, from a copy of the thread id the compiler cannot connect to the one above: otherwise px, py
@@ -2653,8 +2691,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     asm volatile("" : "+v"(tid2));
     const int lxi2 = (int)(((tid2 & 63u) >> 4) * 4u + (tid2 & 3u)), lyi2 = (int)((tid2 >> 6) * 4u + ((tid2 & 15u) >> 2));
     const int px2 = bx + lxi2, py2 = by + lyi2;
-    if (px2 < f.width && py2 < f.height)
+    if (px2 < f.width && py2 < f.height) {
+        if constexpr (PICK) comp_final_pick(f, bg_depth, out_pick, out_rows, px2, py2, tyl * kTile + lyi2, wmax, wpair);
         comp_final_pixel<OUTF, ZOUT>(f, bg_rgba, out, out_rows, px2, py2, tyl * kTile + lyi2, T, ar, ag, ab, bg_depth, out_depth, az);
+    }
 }
 
 // Measured and dropped again in round 2 (the item STREAM: a resident grid of workgroups, each taking items b, b + G, b + 2G, ...
@@ -2821,15 +2861,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : 
 
 // Folds the per-segment partials of multi-segment tiles: (C1,T1) o (C2,T2) = (C1 + T1*C2, T1*T2).
 // One workgroup per tile, same lane -> pixel map as k_composite.  ZOUT: the partial depths fold like a colour channel (Z1 + T1*Z2).
-template <int OUTF, bool ZOUT>
+// PICK: a segment walks from T = 1, so its largest local weight w' is its candidate and T_prefix * w' that candidate's weight in the pixel: the
+// fold keeps the largest, front to back with a strict > (gswt_hip.h, pick output).
+template <int OUTF, bool ZOUT, bool PICK>
 __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* __restrict__ item_base,
                                                  const float4* __restrict__ partials, const float4* __restrict__ bg_rgba,
                                                  float4* __restrict__ out, int n_tiles, int out_rows,
                                                  const unsigned long long* __restrict__ counters, unsigned long long* __restrict__ host_counters,
-                                                 const float* __restrict__ partials_z, const float* __restrict__ bg_depth, float* __restrict__ out_depth)
+                                                 const float* __restrict__ partials_z, const float* __restrict__ bg_depth, float* __restrict__ out_depth,
+                                                 const uint2* __restrict__ partials_pick, uint4* __restrict__ out_pick)
 {
     const int tile = blockIdx.x;
-    // last kernel of the frame: the four result counters go straight into the slot's pinned host words (instead of a
+    // last kernel of a frame without a pick image (k_pick_resolve follows otherwise; the host reads the words behind the frame's final event
+    // either way): the four result counters go straight into the slot's pinned host words (instead of a
     // separate 32-byte device-to-host copy, ~4 us of stream time and one more API call per frame)
     if (tile == 0 && threadIdx.x < 5u && host_counters) host_counters[threadIdx.x] = counters[threadIdx.x];
     const uint32_t i0 = item_base[tile], n_seg = item_base[tile + 1] - i0;
@@ -2842,16 +2886,20 @@ __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* 
     const int px = bx + lxi, py = by + lyi;
     if (px >= f.width || py >= f.height) return;
     float T = 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, az = 0.0f;
+    float wmax = 0.0f;
+    uint32_t wpair = 0u;
     // eight segments' partials in flight together (clamped, unmasked): a horizon tile of c5 has 40 segments, and one dependent
     // 4-KB load per segment made the longest tile the kernel's duration (59 us at c5)
     for (uint32_t s0 = 0; s0 < n_seg; s0 += 8u) {
         float4 p[8];
         float pz[8];
+        uint2 pp[8];
 #pragma unroll
         for (uint32_t k = 0; k < 8u; k++) {
             const size_t pi = (size_t)(i0 + min(s0 + k, n_seg - 1u)) * 256u + tid;
             p[k] = partials[pi];
             if (ZOUT) pz[k] = partials_z[pi];
+            if (PICK) pp[k] = partials_pick[pi];
         }
 #pragma unroll
         for (uint32_t k = 0; k < 8u; k++) {
@@ -2860,11 +2908,46 @@ __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* 
                 ag = fmaf(T, p[k].y, ag);
                 ab = fmaf(T, p[k].z, ab);
                 if (ZOUT) az = fmaf(T, pz[k], az);
+                if (PICK) {
+                    const float wc = T * __uint_as_float(pp[k].x);
+                    if (wc > wmax) { wmax = wc; wpair = pp[k].y; }
+                }
                 T = T * p[k].w;
             }
         }
     }
+    if constexpr (PICK) comp_final_pick(f, bg_depth, out_pick, out_rows, px, py, tyl * kTile + lyi, wmax, wpair);
     comp_final_pixel<OUTF, ZOUT>(f, bg_rgba, out, out_rows, px, py, tyl * kTile + lyi, T, ar, ag, ab, bg_depth, out_depth, az);
+}
+
+// The raw pick image of the compositors -> the public records (gswt_pick), in place, one lane per output pixel.  A raw hit (weight > 0)
+// names a pair of the sorted list `vals` the compositor walked: pair -> slot -> draw (chunk_tab) -> the list word at k_project's address
+// li = list_base + (count - 1 - r), r = slot - slot_base -> the member's map id (merged_map) or the draw's own -> depths[slot].  Everything
+// else -- no-hit records, the zero bytes of a shard's padding -- has weight 0 and stays.  (A frame whose pair buffer overflowed is re-run;
+// until then its pairs may name anything: indices are bounded, not trusted.)
+__global__ __launch_bounds__(256) void k_pick_resolve(uint4* __restrict__ out_pick, uint32_t n_px, const uint32_t* __restrict__ vals, uint32_t pair_cap,
+                                                      const uint2* __restrict__ chunk_tab, uint32_t n_chunks, const DrawDev* __restrict__ draws,
+                                                      const uint32_t* __restrict__ static_list, const uint32_t* __restrict__ merged_list,
+                                                      const uint32_t* __restrict__ merged_map, const float* __restrict__ depths)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_px) return;
+    const uint4 raw = out_pick[i];
+    if (raw.w == 0u) return;
+    uint4 o = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, __float_as_uint(1.0f), 0u);
+    if (raw.x < pair_cap) {
+        const uint32_t slot = vals[raw.x];
+        if ((slot >> 8) < n_chunks) {
+            const DrawDev& d = draws[chunk_tab[slot >> 8].x];
+            const uint32_t r = slot - d.slot_base;
+            if (r < d.count) {
+                const uint32_t li = d.list_base + (d.count - 1u - r);
+                const bool mrg = d.merged != 0u;
+                o = make_uint4(mrg ? merged_map[li] : d.map_index, (mrg ? merged_list : static_list)[li], __float_as_uint(depths[slot]), raw.w);
+            }
+        }
+    }
+    out_pick[i] = o;
 }
 
 // all-gathered shards -> frame.  rows: shard = tile row % count (rows_padded rows each, full width);
@@ -3098,7 +3181,9 @@ static void with_composite_edc(const Frame& f, Fn&& fn)
 
 // ranges -> per-tile segment counts -> item_base (exclusive scan, item_base[n_tiles] = #items) ->
 // k_composite over an upper bound of items -> k_combine, storing the image in format OUTF (and with ZOUT the depth image b.out_depth).
-template <int OUTF, bool ZOUT>
+// PICK: the pick image b.out_pick as well -- always through k_composite (its decoupled-waves twin is a bit-identical A/B switch and has no PICK
+// instantiation) --, resolved in place by k_pick_resolve from the same `vals`.
+template <int OUTF, bool ZOUT, bool PICK>
 static void launch_composite_t(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
                                uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
@@ -3119,24 +3204,35 @@ static void launch_composite_t(hipStream_t s, const Frame& f, const FrameBufs& b
     // GSWT_OPT_COMPOSITE = 1: decoupled waves (k_composite_dw), same image bit for bit; 0 and 2: k_composite.  (The compositors carry
     // ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED.)
     with_composite_edc(f, [&](auto E, auto D, auto C) {
-        if (variant == 1)
+        if (variant == 1 && !PICK)
             GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C, OUTF, ZOUT>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs,
                               b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z);
         else
-            GSWT_LAUNCH_TIMED((k_composite<E, D, C, OUTF, ZOUT>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals,
-                              b.recs, b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z);
+            GSWT_LAUNCH_TIMED((k_composite<E, D, C, OUTF, ZOUT, PICK>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals,
+                              b.recs, b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z,
+                              b.out_pick, b.partials_pick);
     });
-    GSWT_LAUNCH((k_combine<OUTF, ZOUT>), dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows,
-                (const unsigned long long*)b.counters, b.host_counters, (const float*)b.partials_z, b.bg_depth, b.out_depth);
+    GSWT_LAUNCH((k_combine<OUTF, ZOUT, PICK>), dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows,
+                (const unsigned long long*)b.counters, b.host_counters, (const float*)b.partials_z, b.bg_depth, b.out_depth,
+                (const uint2*)b.partials_pick, b.out_pick);
+    if (PICK) {
+        const uint32_t n_px = (uint32_t)out_rows * (uint32_t)f.out_w;
+        GSWT_LAUNCH_TIMED(k_pick_resolve, dim3((n_px + 255u) / 256u), dim3(256), s, b.ev_pick_begin, b.ev_pick_end, b.out_pick, n_px, vals, b.pair_cap, b.chunk_tab, b.n_chunks, b.draws,
+                    b.static_list, b.merged_list, b.merged_map, (const float*)b.depths);
+    }
 }
 
-// The frame's depth image is written when b.out_depth is set (gswt_render_depth): the ZOUT instantiations of the compositors.
+// The frame's depth image is written when b.out_depth is set (gswt_render_depth): the ZOUT instantiations of the compositors; its pick image
+// when b.out_pick is set (gswt_render_pick): the PICK ones.
 template <int OUTF>
 static void launch_composite_z(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
                                uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
-    if (b.out_depth) launch_composite_t<OUTF, true>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-    else launch_composite_t<OUTF, false>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    if (b.out_pick) {
+        if (b.out_depth) launch_composite_t<OUTF, true, true>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+        else launch_composite_t<OUTF, false, true>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    } else if (b.out_depth) launch_composite_t<OUTF, true, false>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    else launch_composite_t<OUTF, false, false>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
 }
 
 void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,

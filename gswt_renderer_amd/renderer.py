@@ -13,6 +13,13 @@ import numpy as np
 from . import _lib as L
 
 
+# one record of the pick image (gswt_pick, include/gswt_hip.h): the splat with the largest blend weight at the pixel.  entry is the list
+# word gs_index | lod_id << 28; a pixel no splat covers has map_index = entry = PICK_NONE, weight 0 and the background depth.
+PICK_DTYPE = np.dtype([("map_index", "<u4"), ("entry", "<u4"), ("depth", "<f4"), ("weight", "<f4")])
+PICK_NONE = L.PICK_NONE
+assert PICK_DTYPE.itemsize == C.sizeof(L.Pick)
+
+
 class GSWTError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"gswt error {code}: {msg}")
@@ -194,7 +201,8 @@ class GSWTRenderer:
                lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
                transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba=None, bg_depth=None,
                out_device_ptr: int | None = None, bg_on_device: bool = False, out_format: int = L.GSWT_OUT_RGBA32F,
-               depth: bool = False, out_depth_device_ptr: int | None = None):
+               depth: bool = False, out_depth_device_ptr: int | None = None, pick: bool = False,
+               out_pick_device_ptr: int | None = None):
         """camera / scene: 176 / 160-byte uniform blocks (any ctypes struct or bytes of that layout).
         Returns the image [rows, W, 4] on the host -- f32 for GSWT_OUT_RGBA32F, uint8 in the channel order of
         GSWT_OUT_RGBA8_UNORM / GSWT_OUT_BGRA8_UNORM --, or None when out_device_ptr is given.
@@ -204,7 +212,11 @@ class GSWTRenderer:
         With depth=True the depth image follows the planes: (y, cbcr, depth) / (y, cb, cr, depth).
         depth=True: returns (image, depth), depth the composited depth image [rows, W] f32 of gswt_render_depth (NDC depth
         blended like a colour channel over bg_depth, or 1.0 without one).  With out_device_ptr the depth goes to
-        out_depth_device_ptr (rows x out_w f32 on the device) when that is given."""
+        out_depth_device_ptr (rows x out_w f32 on the device) when that is given.
+        pick=True: the pick image of gswt_render_pick, [rows, W] records of PICK_DTYPE (per pixel the tile instance and list word
+        of the splat with the largest blend weight, its depth and that weight), follows as the last element: (image, pick),
+        (image, depth, pick), or behind the planes and the depth of a video format.  With out_device_ptr it goes to
+        out_pick_device_ptr (rows x out_w x 16 bytes on the device) when that is given."""
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()
@@ -226,8 +238,9 @@ class GSWTRenderer:
             bgc, bgd = _ptr(bgc_a), _ptr(bgd_a)
         if out_device_ptr is not None:
             zd = C.c_void_p(out_depth_device_ptr) if out_depth_device_ptr else None
-            self._check(self._lib.gswt_render_depth(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
-                                                    1 if bg_on_device else 0, C.c_void_p(out_device_ptr), zd, 1))
+            pd = C.c_void_p(out_pick_device_ptr) if out_pick_device_ptr else None
+            self._check(self._lib.gswt_render_pick(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
+                                                   1 if bg_on_device else 0, C.c_void_p(out_device_ptr), zd, pd, 1))
             return None
         video = out_format in (L.GSWT_VIDEO_NV12, L.GSWT_VIDEO_I420)
         if video:       # (an odd size has no plane layout, 0 bytes: the library refuses the call before it writes anything)
@@ -235,11 +248,13 @@ class GSWTRenderer:
             planes = lambda: video_planes(out, out_format, rows, out_w)
         else:
             out = np.empty((rows, out_w, 4), dtype=_out_dtype(out_format))
-        if depth:
-            z = np.empty((rows, out_w), dtype=np.float32)
-            self._check(self._lib.gswt_render_depth(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
-                                                    1 if bg_on_device else 0, _ptr(out), _ptr(z), 0))
-            return planes() + (z,) if video else (out, z)
+        if depth or pick:
+            z = np.empty((rows, out_w), dtype=np.float32) if depth else None
+            pk = np.empty((rows, out_w), dtype=PICK_DTYPE) if pick else None
+            self._check(self._lib.gswt_render_pick(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
+                                                   1 if bg_on_device else 0, _ptr(out), _ptr(z), _ptr(pk), 0))
+            extra = tuple(a for a in (z, pk) if a is not None)
+            return (planes() if video else (out,)) + extra
         self._check(self._lib.gswt_render(self._h, cam, sc, C.byref(cfg), width, height, bgc, bgd,
                                           1 if bg_on_device else 0, _ptr(out), 0))
         return planes() if video else out
@@ -247,11 +262,11 @@ class GSWTRenderer:
     def render_async(self, camera, scene, width: int, height: int, out_device_ptr: int, *, culling_dist: float = 1.0,
                      lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
                      transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba_ptr: int = 0, bg_depth_ptr: int = 0,
-                     out_format: int = L.GSWT_OUT_RGBA32F, out_depth_ptr: int = 0) -> int:
+                     out_format: int = L.GSWT_OUT_RGBA32F, out_depth_ptr: int = 0, out_pick_ptr: int = 0) -> int:
         """Queues a frame (device pointers only) and returns a ticket for render_wait.  out_device_ptr holds rows x out_w x 4
         f32, or bytes for the 8-bit out_format values, or the planes of a GSWT_VIDEO_* format (gswt_out_image_bytes(out_format,
         rows, out_w) bytes, width and height even; see video_planes); out_depth_ptr (optional) receives the depth image, rows x out_w f32
-        (gswt_render_async_depth)."""
+        (gswt_render_async_depth); out_pick_ptr (optional) the pick image, rows x out_w records of PICK_DTYPE (gswt_render_async_pick)."""
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()
@@ -260,11 +275,11 @@ class GSWTRenderer:
         cfg.shard_index, cfg.shard_count, cfg.shard_mode = _shard_args(shard)
         cfg.out_format = out_format & 0xFFFFFFFF
         ticket = C.c_int(-1)
-        self._check(self._lib.gswt_render_async_depth(self._h, cam, sc, C.byref(cfg), width, height,
-                                                      C.c_void_p(bg_rgba_ptr) if bg_rgba_ptr else None,
-                                                      C.c_void_p(bg_depth_ptr) if bg_depth_ptr else None,
-                                                      C.c_void_p(out_device_ptr), C.c_void_p(out_depth_ptr) if out_depth_ptr else None,
-                                                      C.byref(ticket)))
+        self._check(self._lib.gswt_render_async_pick(self._h, cam, sc, C.byref(cfg), width, height,
+                                                     C.c_void_p(bg_rgba_ptr) if bg_rgba_ptr else None,
+                                                     C.c_void_p(bg_depth_ptr) if bg_depth_ptr else None,
+                                                     C.c_void_p(out_device_ptr), C.c_void_p(out_depth_ptr) if out_depth_ptr else None,
+                                                     C.c_void_p(out_pick_ptr) if out_pick_ptr else None, C.byref(ticket)))
         return ticket.value
 
     def frame_slots(self) -> int:

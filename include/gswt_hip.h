@@ -188,7 +188,7 @@ typedef struct {
     uint32_t n_tiles;     /* screen tiles composited by this ctx  */
     uint32_t _pad;
     float ms_composite_kernel; /* k_composite alone (ms_composite also covers work-item setup + k_combine) */
-    float _pad2;
+    float ms_pick_resolve;     /* k_pick_resolve alone (part of ms_composite; 0 on a frame without a pick image) */
 } gswt_timings;
 
 /* ---- lifecycle ------------------------------------------------------------------- */
@@ -376,6 +376,44 @@ GSWT_API int gswt_render_async_depth(gswt_ctx *ctx, const gswt_camera_uniforms *
                                      const gswt_scene_uniforms *scene, const gswt_render_config *cfg,
                                      int width, int height, const float *bg_rgba_dev, const float *bg_depth_dev,
                                      float *out_rgba_dev, float *out_depth_dev, int *ticket);
+
+/* gswt_render_depth / gswt_render_async_depth that also write the frame's PICK image: which tile instance and which splat
+ * each pixel shows.  out_pick receives rows_out*W records of 16 bytes (the colour output's geometry in every shard mode; the
+ * padding rows / columns of a shard are zero bytes like the other outputs), whatever cfg->out_format is; out_depth may be
+ * NULL; a NULL out_pick behaves exactly as gswt_render_depth / gswt_render_async_depth, which are these calls with NULL.
+ * Definition, per pixel: the splats are walked in the compositor's blend order with the colour's coverage decisions
+ * (|p|^2 <= 4, the proxy depth test when bg_depth is bound), its weights w_i = T_i * e_i and its early-out
+ * (transmittance_eps).  The pixel's pick is the splat with the LARGEST w_i -- the one that contributes most to the pixel's
+ * colour; among equal weights the front-most wins (the comparison is a strict >).  A pixel no splat covers gets
+ * map_index = entry = 0xFFFFFFFF, weight = 0 and depth = z_bg: bg_depth[p] with a proxy depth buffer bound, 1.0 without
+ * one (the depth image's convention).
+ * A tile's list may be walked in segments (GSWT_OPT_SEGMENT).  A segment starts from T = 1, so its weights are the pixel's
+ * divided by the transmittance in front of the segment and its own winner is its candidate; the candidates are compared as
+ * T_prefix * w'_max, front to back, again with a strict >.  What is promised about identity: it is exact wherever the winner
+ * leads by more than rounding (weights are binary32; the segmented product rounds once more); between candidates whose
+ * weights agree to rounding either may be returned.  The returned weight and depth always belong to the returned splat.
+ * Pointer rules are those of the depth output: out_pick is a host pointer (staged) unless out_on_device; frames in flight
+ * together must write different pick buffers; a frame re-run after a pair-buffer overflow rewrites its pick.  A missing
+ * out_rgba, or an out_pick equal to out_rgba or out_depth, returns GSWT_ERR_BAD_ARG before anything is enqueued.  Pick
+ * frames run under GSWT_OPT_GRAPH and GSWT_OPT_TIMING as depth-output frames do.  With GSWT_OPT_COMPOSITE = 1 a pick frame
+ * is composited by the default kernel, not the decoupled-waves one: the two are bit-identical A/B switches, so colour,
+ * depth and pick are what either would give.  The pick image is not part of the gathers (gswt_render_gather,
+ * gswt_unshard*). */
+typedef struct {
+    uint32_t map_index;  /* tile instance: TileUniforms.map_index of a static draw, the member's map id of a merged one */
+    uint32_t entry;      /* the list word of the splat: gs_index | lod_id << 28 */
+    float depth;         /* that splat's NDC depth: the value the depth test compares, bit-identical to the vertex stage's */
+    float weight;        /* its w_i, in (0, 1] */
+} gswt_pick;
+GSWT_API int gswt_render_pick(gswt_ctx *ctx, const gswt_camera_uniforms *camera,
+                              const gswt_scene_uniforms *scene, const gswt_render_config *cfg,
+                              int width, int height,
+                              const float *bg_rgba, const float *bg_depth, int bg_on_device,
+                              float *out_rgba, float *out_depth, gswt_pick *out_pick, int out_on_device);
+GSWT_API int gswt_render_async_pick(gswt_ctx *ctx, const gswt_camera_uniforms *camera,
+                                    const gswt_scene_uniforms *scene, const gswt_render_config *cfg,
+                                    int width, int height, const float *bg_rgba_dev, const float *bg_depth_dev,
+                                    float *out_rgba_dev, float *out_depth_dev, gswt_pick *out_pick_dev, int *ticket);
 GSWT_API int gswt_render_wait(gswt_ctx *ctx, int ticket);
 GSWT_API int gswt_render_fence(gswt_ctx *ctx, int ticket);
 

@@ -191,6 +191,7 @@ HIP_CITES = {
     "gswt_merge_group": "one MergedFrom tile: view + members (wangtile.rs:595-670)",
     "gswt_merge_member": "one member of a merged group",
     "gswt_timings": "per-stage device times and workload sizes of the last frame",
+    "gswt_pick": "one pixel of the pick image (gswt_render_pick): the splat with the largest blend weight, 16 B",
 }
 HOST_CITES = {
     "gswt_user_data": "structure::UserData (structure.rs:15-65), the fields the worker reads",
