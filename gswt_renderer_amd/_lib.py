@@ -37,6 +37,8 @@ GSWT_OPT_COMPOSITE = 13
 GSWT_OPT_DEPTH_SORT = 14
 GSWT_OPT_NO_CHUNK_CULL = 15
 GSWT_OPT_ITEM_ORDER = 16
+GSWT_OPT_PROJECTION = 17            # 0 perspective (default), 1 orthographic (gswt_renderer_amd/ortho.py)
+GSWT_PROJECTION_PERSPECTIVE, GSWT_PROJECTION_ORTHO = 0, 1
 # gswt_debug_read_scene items
 GSWT_SCENE_TEX = 0
 GSWT_SCENE_RAW_DEPTH = 1

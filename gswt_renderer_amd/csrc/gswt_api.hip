@@ -23,6 +23,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <unordered_map>
 #include <utility>
@@ -237,6 +238,7 @@ struct FrameSlot {
     DevBuf<uint4> item_tab;
     DevBuf<uint32_t> aux_a, aux_b;         // GSWT_ORDER_DEPTH: the pairs' tile ids, carried through the depth passes as the sort's payload
     bool strict_vs = false;                // GSWT_OPT_STRICT_VS as it stood when the frame was submitted (a re-run keeps it)
+    bool ortho = false;                    // GSWT_OPT_PROJECTION likewise: k_project<.,.,true,ORTHO> (frames in flight and re-runs keep their own)
     uint32_t depth_passes = 0;             // GSWT_ORDER_DEPTH: radix passes this frame's depth sort was launched with
     bool depth_local = false;              // ... or the tile-local depth sort (k_tile_depth_sort)
     bool full_grid = false;                // this (re-run) frame launches k_project / k_emit over the whole launch table, whatever the hint says
@@ -309,6 +311,9 @@ struct gswt_ctx {
     // GSWT_OPT_STRICT_VS (default ON since round 4: k_project<.,.,STRICT> costs +1 us of 71 at c3 and nothing in frames/s): vs_main is
     // evaluated operator by operator as gswt.wgsl:152-258 writes it; 0 selects the fma-chain / single-reciprocal sequence v2
     int opt_strict_vs = 1;
+    // GSWT_OPT_PROJECTION: 0 = perspective (vs_main as written), 1 = orthographic (k_project<.,.,.,ORTHO>: the constant affine Jacobian in place of
+    // gswt.wgsl:213-232).  Read when a frame is submitted (validate_frame, submit_frame); setting it waits for nothing.
+    int opt_projection = 0;
     // GSWT_OPT_COMPOSITE: 0 = k_composite + k_combine, 1 = k_composite_dw (decoupled waves) + k_combine, 2 = the same as 0
     int opt_composite = 0;
     int opt_no_chunk_cull = 0;             // GSWT_OPT_NO_CHUNK_CULL: k_cull keeps every chunk of a surviving draw (A/B and tests: same image)
@@ -645,6 +650,9 @@ try {
     case GSWT_OPT_DEFER_SWAP: c->opt_defer_swap = value; return GSWT_OK;
     case GSWT_OPT_GRAPH: c->opt_graph = value; return GSWT_OK;
     case GSWT_OPT_STRICT_VS: c->opt_strict_vs = value != 0; return GSWT_OK;
+    case GSWT_OPT_PROJECTION:
+        if (value != 0 && value != 1) return fail(c, GSWT_ERR_BAD_ARG, "GSWT_OPT_PROJECTION: 0 (perspective) or 1 (orthographic), not %d", value);
+        c->opt_projection = value; return GSWT_OK;
     case GSWT_OPT_COMPOSITE:
         if (value < 0 || value > 2) return fail(c, GSWT_ERR_BAD_ARG, "unknown compositor variant %d", value);
         c->opt_composite = value; return GSWT_OK;
@@ -1475,6 +1483,21 @@ static int validate_frame(gswt_ctx* c, const gswt_camera_uniforms* cam, const gs
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: unknown out_format %u", cfg->out_format);
     if (out_is_video((int)cfg->out_format) && ((width | height) & 1))
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: the video formats need an even target size, not %dx%d", width, height);
+    if (c->opt_projection == 1) {
+        // an orthographic frame (GSWT_OPT_PROJECTION = 1): the projection must be affine (clip w = 1 exactly), focal is pixels per world unit,
+        // and only the strict vertex stage and row shards have an orthographic form
+        const float* P = cam->projection;
+        if (!(P[3] == 0.0f && P[7] == 0.0f && P[11] == 0.0f && P[15] == 1.0f))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 needs an affine projection, bottom row (0, 0, 0, 1), not (%g, %g, %g, %g)",
+                        P[3], P[7], P[11], P[15]);
+        for (int k = 0; k < 2; k++)
+            if (!(cam->focal[k] > 0.0f) || !(cam->focal[k] < std::numeric_limits<float>::infinity()))
+                return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 needs a finite focal > 0 (pixels per world unit), not focal[%d] = %g", k, cam->focal[k]);
+        if (!c->opt_strict_vs)
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no orthographic form)");
+        if (sc > 1 && cfg->shard_mode == GSWT_SHARD_COLUMNS)
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 does not take column-band shards (their band cull is perspective-only); use GSWT_SHARD_ROWS");
+    }
     return GSWT_OK;
 }
 
@@ -1786,7 +1809,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         }
         sl.n_launch_eff = (uint32_t)eff;
     }
-    launch_project(s, f, b, sl.n_launch_eff, dbg, sl.strict_vs);
+    launch_project(s, f, b, sl.n_launch_eff, dbg, sl.strict_vs, sl.ortho);
     if (c->opt_timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvProjected], s));
     // ---- emit + sort, ranges, composite
     const uint32_t* vals = nullptr;
@@ -1882,6 +1905,7 @@ static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* 
     a.cam = *cam; a.su = *su; a.cfg = *cfg; a.width = width; a.height = height; a.d_bg = d_bg; a.d_bgd = d_bgd; a.d_out = d_out;
     a.d_out_depth = d_out_depth; a.d_out_pick = d_out_pick;
     sl.strict_vs = c->opt_strict_vs != 0;
+    sl.ortho = c->opt_projection == 1;
     return enqueue_frame(c, sl);
 }
 

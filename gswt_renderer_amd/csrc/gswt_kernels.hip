@@ -587,7 +587,11 @@ __device__ unsigned long long g_trace[kTraceItems * 8];
 // the same operations, in the same order, as the CPU checker's strict mode, per splat bit for bit.  The default (sequence v2, DESIGN.md
 // section 4) evaluates the same expressions with fma chains and one reciprocal per quotient -- also legal WGSL, ~25 % fewer instructions,
 // and up to 5e-4 away from this one on thin ellipses (lambda2 = mid - radius cancels).
-template <bool DEBUG, bool FULL, bool STRICT>
+// ORTHO (GSWT_OPT_PROJECTION = 1, STRICT only): the orthographic vertex stage.  vs_main as above except A8's Jacobian, gswt.wgsl:213-232: the
+// projection is affine, so J_T is the constant ((fx, 0, 0), (0, fy, 0), (0, 0, 0)) with fx, fy = focal in pixels per world unit -- no t, no
+// quotient by t.z, no htan_fov clamp.  T and cov2d stay the written full products.  Everything around it (instancing, surface mapping, clip test,
+// LOD blend against cam_pos, the 1.2 w frustum test with w = 1, eigen-decomposition, colour, A10) is the same code.
+template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO>
 __global__ __launch_bounds__(256) void k_project(
     const Frame f, const DrawDev* __restrict__ draws, const uint2* __restrict__ chunk_tab,
     const uint32_t* __restrict__ static_list, const uint32_t* __restrict__ merged_list,
@@ -820,18 +824,26 @@ __global__ __launch_bounds__(256) void k_project(
                     for (int k = 0; k < 9; k++) K[k] = R[k];
                 }
                 // A8 :207-258
-                const float dd0 = c0 - f.cam_pos[0], dd1 = c1 - f.cam_pos[1], dd2 = c2 - f.cam_pos[2];
-                float t[3];
-                for (int rr = 0; rr < 3; rr++) t[rr] = (f.V[rr] * dd0 + f.V[4 + rr] * dd1) + f.V[8 + rr] * dd2;
-                const float txtz = t[0] / t[2], tytz = t[1] / t[2];
-                const float limx = 1.3f * f.htan[0], limy = 1.3f * f.htan[1];
-                t[0] = clampf(txtz, -limx, limx) * t[2];
-                t[1] = clampf(tytz, -limy, limy) * t[2];
-                const float tz2 = t[2] * t[2];
-                // J_T columns: (fx / tz, 0, -fx tx / tz^2), (0, fy / tz, -fy ty / tz^2), (0, 0, 0)
-                const float JT[9] = {f.focal[0] / t[2], 0.0f, (-f.focal[0] * t[0]) / tz2,
-                                     0.0f, f.focal[1] / t[2], (-f.focal[1] * t[1]) / tz2,
-                                     0.0f, 0.0f, 0.0f};
+                float JT[9];
+                if (ORTHO) {
+                    // J_T columns of the affine projection: (fx, 0, 0), (0, fy, 0), (0, 0, 0)
+                    JT[0] = f.focal[0]; JT[1] = 0.0f; JT[2] = 0.0f;
+                    JT[3] = 0.0f; JT[4] = f.focal[1]; JT[5] = 0.0f;
+                    JT[6] = 0.0f; JT[7] = 0.0f; JT[8] = 0.0f;
+                } else {
+                    const float dd0 = c0 - f.cam_pos[0], dd1 = c1 - f.cam_pos[1], dd2 = c2 - f.cam_pos[2];
+                    float t[3];
+                    for (int rr = 0; rr < 3; rr++) t[rr] = (f.V[rr] * dd0 + f.V[4 + rr] * dd1) + f.V[8 + rr] * dd2;
+                    const float txtz = t[0] / t[2], tytz = t[1] / t[2];
+                    const float limx = 1.3f * f.htan[0], limy = 1.3f * f.htan[1];
+                    t[0] = clampf(txtz, -limx, limx) * t[2];
+                    t[1] = clampf(tytz, -limy, limy) * t[2];
+                    const float tz2 = t[2] * t[2];
+                    // J_T columns: (fx / tz, 0, -fx tx / tz^2), (0, fy / tz, -fy ty / tz^2), (0, 0, 0)
+                    JT[0] = f.focal[0] / t[2]; JT[1] = 0.0f; JT[2] = (-f.focal[0] * t[0]) / tz2;
+                    JT[3] = 0.0f; JT[4] = f.focal[1] / t[2]; JT[5] = (-f.focal[1] * t[1]) / tz2;
+                    JT[6] = 0.0f; JT[7] = 0.0f; JT[8] = 0.0f;
+                }
                 float Tm[9];                        // T = transpose(view3) * J_T
                 for (int cc = 0; cc < 3; cc++)
                     for (int rr = 0; rr < 3; rr++)
@@ -3024,16 +3036,18 @@ void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_c
                 b.chunk_tab, b.n_chunks, b.boxes, chunk_cull && b.boxes ? 1u : 0u, b.live_cnt, b.live_tab, b.live_cid);
 }
 
-void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict)
+void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict, bool ortho)
 {
     if (b.n_chunks == 0) return;
     const uint32_t n_super = b.n_chunks / 256u + 1u;    // super_sums = [pairs x 16 n_super][visible x 16 n_super][exclusive pair prefix x n_super] (kSuperStride), zeroed by k_cull
     const bool full = f.surface_type == 2u || f.draw_mode != 0u;
-#define GSWT_LAUNCH_PROJECT_S(D, F, S)                                                                                         \
-    GSWT_LAUNCH((k_project<D, F, S>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,   \
+#define GSWT_LAUNCH_PROJECT_S(D, F, S, O)                                                                                      \
+    GSWT_LAUNCH((k_project<D, F, S, O>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list, \
                 b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums, \
                 b.super_sums, n_super, b.dbg, b.col_f)
-#define GSWT_LAUNCH_PROJECT(D, F) do { if (strict) GSWT_LAUNCH_PROJECT_S(D, F, true); else GSWT_LAUNCH_PROJECT_S(D, F, false); } while (0)
+    // (the orthographic stage exists in its strict form only: gswt_api.hip refuses an orthographic frame with GSWT_OPT_STRICT_VS = 0)
+#define GSWT_LAUNCH_PROJECT(D, F) do { if (ortho) GSWT_LAUNCH_PROJECT_S(D, F, true, true); else if (strict) GSWT_LAUNCH_PROJECT_S(D, F, true, false); \
+                                       else GSWT_LAUNCH_PROJECT_S(D, F, false, false); } while (0)
     if (debug && full) { GSWT_LAUNCH_PROJECT(true, true); }
     else if (debug) { GSWT_LAUNCH_PROJECT(true, false); }
     else if (full) { GSWT_LAUNCH_PROJECT(false, true); }

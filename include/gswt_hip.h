@@ -244,7 +244,28 @@ enum { GSWT_OPT_NO_LOD_PREFILTER = 1, GSWT_OPT_DEBUG_VARYINGS = 2,
                                       survives the reference's tile cull is projected, as until round 3).  Same image bit for bit: the cull
                                       only leaves out chunks none of whose splats vs_main's own frustum test (gswt.wgsl:163-167) would keep */,
        GSWT_OPT_ITEM_ORDER = 16 /* order in which the compositor's work items (screen tile, segment of its pair list) are handed out: 0 = tile
-                                  order, 1 = heaviest first (full segments, then the remainders by falling length).  Same image bit for bit */ };
+                                  order, 1 = heaviest first (full segments, then the remainders by falling length).  Same image bit for bit */,
+       GSWT_OPT_PROJECTION = 17 /* 0 (default): perspective, vs_main as written.  1: orthographic -- top-down maps, minimaps, sun-direction depth
+                                   maps, height fields.  The vertex stage is vs_main except gswt.wgsl:213-232: the perspective Jacobian (focal / t.z,
+                                   the 1.3 * htan_fov clamp, -focal t / t.z^2) is replaced by the constant affine one, J_T columns (fx, 0, 0),
+                                   (0, fy, 0), (0, 0, 0); T = transpose(view3) * J_T and cov2d = transpose(T) * Vrk * T stay the written full
+                                   products, operator by operator as GSWT_OPT_STRICT_VS.  For these frames `projection` is an affine matrix
+                                   (bottom row exactly (0, 0, 0, 1), OpenGL depth convention like the perspective one), `focal` is PIXELS PER WORLD
+                                   UNIT, |0.5 P[0][0] W| and |0.5 P[1][1] H|, htan_fov is ignored, and cam_pos is only the reference point of the
+                                   LOD transition (gswt.wgsl:91-150: cam_dist = distance(center, cam_pos)) -- e.g. the main view's eye.  The
+                                   frustum test (1.2 w with w = 1: a 1.2x box in NDC), surface mapping, clip test, eigen-decomposition, colour and
+                                   depth (q.z / q.w of opengl_to_wgpu * projection, here LINEAR in view depth) are the same code; depth, pick,
+                                   every output format, both order modes, row shards, GSWT_OPT_GRAPH and frames in flight work unchanged.
+                                   Read when a frame is submitted (gswt_render*, gswt_render_async*, depth and pick forms): setting it waits for
+                                   nothing, frames in flight and a frame re-run after a pair-buffer overflow keep the projection they were
+                                   submitted with.  With the option on a submit returns GSWT_ERR_BAD_ARG before anything is enqueued for: a
+                                   projection whose bottom row is not (0, 0, 0, 1); a focal component that is not finite or <= 0;
+                                   GSWT_OPT_STRICT_VS = 0 (sequence v2 has no orthographic form); GSWT_SHARD_COLUMNS with shard_count > 1 (the
+                                   band cull is perspective-specific).  Any value other than 0 / 1 is refused.  gswt_skybox_render and
+                                   gswt_proxy_render remain perspective-only: an orthographic frame takes whatever bg_rgba / bg_depth the caller
+                                   gives it.  Order: the worker's tile order is by distance from the sort event's camera, so a top-down view that
+                                   shares the main view's draw set should use GSWT_ORDER_DEPTH, which is exact per splat; GSWT_ORDER_REFERENCE
+                                   also runs and is well defined (draw rank x list position).  The CPU oracle has no orthographic mode */ };
 GSWT_API int gswt_set_option(gswt_ctx *ctx, int key, int value);
 
 /* GSWTRenderer::new (renderer.rs:31-349): uploads PreloadData.tile_splats_merged.tex_data
