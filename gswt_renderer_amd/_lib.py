@@ -39,6 +39,7 @@ GSWT_OPT_NO_CHUNK_CULL = 15
 GSWT_OPT_ITEM_ORDER = 16
 GSWT_OPT_PROJECTION = 17            # 0 perspective (default), 1 orthographic (gswt_renderer_amd/ortho.py)
 GSWT_PROJECTION_PERSPECTIVE, GSWT_PROJECTION_ORTHO = 0, 1
+GSWT_OPT_ANTIALIAS = 18             # variance of the screen-space pixel filter in 1/1024 px^2: 0 off (default), 1..4096
 # gswt_debug_read_scene items
 GSWT_SCENE_TEX = 0
 GSWT_SCENE_RAW_DEPTH = 1

@@ -199,6 +199,7 @@ struct FrameArgs {
     float4* d_out = nullptr;
     float* d_out_depth = nullptr;          // gswt_render_depth / gswt_render_async_depth: the frame's depth image (null: none)
     gswt_pick* d_out_pick = nullptr;       // gswt_render_pick / gswt_render_async_pick: the frame's pick image (null: none)
+    float aa_s = 0.0f;                     // GSWT_OPT_ANTIALIAS as it stood when the frame was submitted: s = 4 v / splat_scale^2 (a re-run keeps it)
 };
 
 // A frame's events on its slot's stream.  GSWT_OPT_TIMING >= 1 records kEvStart, kEvEnd and the compositor kernel's pair, 2 also the
@@ -314,6 +315,8 @@ struct gswt_ctx {
     // GSWT_OPT_PROJECTION: 0 = perspective (vs_main as written), 1 = orthographic (k_project<.,.,.,ORTHO>: the constant affine Jacobian in place of
     // gswt.wgsl:213-232).  Read when a frame is submitted (validate_frame, submit_frame); setting it waits for nothing.
     int opt_projection = 0;
+    // GSWT_OPT_ANTIALIAS: variance of the pixel filter in 1/1024 px^2 (0 = off, 1..4096).  Read when a frame is submitted, like the projection.
+    int opt_antialias = 0;
     // GSWT_OPT_COMPOSITE: 0 = k_composite + k_combine, 1 = k_composite_dw (decoupled waves) + k_combine, 2 = the same as 0
     int opt_composite = 0;
     int opt_no_chunk_cull = 0;             // GSWT_OPT_NO_CHUNK_CULL: k_cull keeps every chunk of a surviving draw (A/B and tests: same image)
@@ -653,6 +656,9 @@ try {
     case GSWT_OPT_PROJECTION:
         if (value != 0 && value != 1) return fail(c, GSWT_ERR_BAD_ARG, "GSWT_OPT_PROJECTION: 0 (perspective) or 1 (orthographic), not %d", value);
         c->opt_projection = value; return GSWT_OK;
+    case GSWT_OPT_ANTIALIAS:
+        if (value < 0 || value > 4096) return fail(c, GSWT_ERR_BAD_ARG, "GSWT_OPT_ANTIALIAS: 0 (off) or 1..4096 (filter variance in 1/1024 px^2), not %d", value);
+        c->opt_antialias = value; return GSWT_OK;
     case GSWT_OPT_COMPOSITE:
         if (value < 0 || value > 2) return fail(c, GSWT_ERR_BAD_ARG, "unknown compositor variant %d", value);
         c->opt_composite = value; return GSWT_OK;
@@ -1456,6 +1462,13 @@ try {
 } GSWT_CATCH("gswt_shard_rows")
 
 // ---- frame machinery ------------------------------------------------------------------------------
+// GSWT_OPT_ANTIALIAS: s = 4 v / splat_scale^2 with v = value / 1024 (exact), one binary32 operation per operator (include/gswt_hip.h)
+static float antialias_s(int value, float splat_scale)
+{
+    const float v = (float)value / 1024.0f;
+    return (4.0f * v) / (splat_scale * splat_scale);
+}
+
 // A frame is enqueued without any host round trip (enqueue_frame) and collected later (finish_frame).
 // gswt_render = enqueue + finish; gswt_render_async / gswt_render_wait expose the two halves so a caller
 // can queue frame i+1 before collecting frame i (two slots, same stream, executed in order).
@@ -1497,6 +1510,18 @@ static int validate_frame(gswt_ctx* c, const gswt_camera_uniforms* cam, const gs
             return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no orthographic form)");
         if (sc > 1 && cfg->shard_mode == GSWT_SHARD_COLUMNS)
             return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 does not take column-band shards (their band cull is perspective-only); use GSWT_SHARD_ROWS");
+    }
+    if (c->opt_antialias > 0) {
+        // a filtered frame (GSWT_OPT_ANTIALIAS > 0): only the strict vertex stage has a filtered form, and s = 4 v / splat_scale^2 needs a splat_scale
+        if (!c->opt_strict_vs)
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_ANTIALIAS > 0 needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no filtered form)");
+        if (su->splat_scale == 0.0f || !(std::fabs(su->splat_scale) < std::numeric_limits<float>::infinity()))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_ANTIALIAS > 0 needs a finite splat_scale != 0, not %g", su->splat_scale);
+        // ... and one whose square neither overflows (s = 0: the filter would switch off silently) nor underflows (s = inf: every alpha 0)
+        const float s = antialias_s(c->opt_antialias, su->splat_scale);
+        if (!(s > 0.0f && s < std::numeric_limits<float>::infinity()))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_ANTIALIAS = %d with splat_scale %g gives s = 4 v / splat_scale^2 = %g, not a finite positive number",
+                        c->opt_antialias, su->splat_scale, s);
     }
     return GSWT_OK;
 }
@@ -1628,6 +1653,7 @@ static Frame make_frame(const gswt_ctx& c, const FrameArgs& a)
     // (0 = "divide": a one-row map, map_wh_y == 1, would wrap the magic to 0 and the multiply-high quotient to 0 -- ADVICE r3)
     f.map_wh_y_magic = f.map_wh_y >= 2u && f.map_wh_y < 65536u ? 0xFFFFFFFFu / f.map_wh_y + 1u : 0u;
     f.tiles_x_magic = f.tiles_x > 0 && f.tiles_x < 65536 ? 0xFFFFFFFFu / (uint32_t)f.tiles_x + 1u : 0u;
+    f.aa_s = a.aa_s;
     return f;
 }
 
@@ -1906,6 +1932,8 @@ static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* 
     a.d_out_depth = d_out_depth; a.d_out_pick = d_out_pick;
     sl.strict_vs = c->opt_strict_vs != 0;
     sl.ortho = c->opt_projection == 1;
+    // (validate_frame refused a splat_scale with which s is not a finite positive number)
+    a.aa_s = c->opt_antialias > 0 ? antialias_s(c->opt_antialias, su->splat_scale) : 0.0f;
     return enqueue_frame(c, sl);
 }
 

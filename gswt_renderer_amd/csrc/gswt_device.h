@@ -94,6 +94,7 @@ struct Frame {
     int32_t hm_w, hm_h;
     uint32_t tiles_x_magic;                // floor(2^32 / tiles_x) + 1: tile -> (column, row) by multiply-high for tile ids below 2^16 (tile_xy)
     uint32_t map_wh_y, map_wh_y_magic;     // height of the tile map in cells (gswt.wgsl:53-56) and floor(2^32 / it) + 1 (quotients of 16-bit map ids by multiply-high)
+    float aa_s;                            // GSWT_OPT_ANTIALIAS: s = 4 v / splat_scale^2, what the pixel filter adds to cov2d's diagonal (0: off)
 };
 
 // Projected splat record consumed by the compositor (32 B, two 16-B words; one 32-B-aligned sector per gather).

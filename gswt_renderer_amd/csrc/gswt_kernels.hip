@@ -375,7 +375,8 @@ __device__ __forceinline__ bool band_misses(const Frame& f, const float lo[3], c
     const float smax = fmaxf(fabsf(f.scene_scale[0]), fmaxf(fabsf(f.scene_scale[1]), fabsf(f.scene_scale[2])));
     const float hx = 1.3f * f.htan[0], hy = 1.3f * f.htan[1];
     const float jn2 = (f.focal[0] * f.focal[0] * (1.0f + hx * hx) + f.focal[1] * f.focal[1] * (1.0f + hy * hy)) / (wmin * wmin);
-    const float lam = jn2 * smax * smax * fmaxf(f.loc_max_trace, 0.0f) * f.surf_f2;
+    // (GSWT_OPT_ANTIALIAS: the pixel filter adds aa_s to both eigenvalues of cov2d; the 1024 clamp applies after it, so the cap below stays)
+    const float lam = jn2 * smax * smax * fmaxf(f.loc_max_trace, 0.0f) * f.surf_f2 + f.aa_s;
     const float ss = fabsf(f.splat_scale);
     const float rad = fminf(2.0f * ss * sqrtf(lam), 1448.2f * ss) * 1.25f + 2.0f;
     if (!(rad == rad)) return false;
@@ -591,7 +592,9 @@ __device__ unsigned long long g_trace[kTraceItems * 8];
 // projection is affine, so J_T is the constant ((fx, 0, 0), (0, fy, 0), (0, 0, 0)) with fx, fy = focal in pixels per world unit -- no t, no
 // quotient by t.z, no htan_fov clamp.  T and cov2d stay the written full products.  Everything around it (instancing, surface mapping, clip test,
 // LOD blend against cam_pos, the 1.2 w frustum test with w = 1, eigen-decomposition, colour, A10) is the same code.
-template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO>
+// AA (GSWT_OPT_ANTIALIAS > 0, STRICT only): the screen-space pixel filter, f.aa_s on both eigenvalues of cov2d and the opacity compensation
+// (include/gswt_hip.h).  A template parameter, not a branch on f.aa_s: the branch cost k_project 0.5 us at c3 with the filter off.
+template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO, bool AA>
 __global__ __launch_bounds__(256) void k_project(
     const Frame f, const DrawDev* __restrict__ draws, const uint2* __restrict__ chunk_tab,
     const uint32_t* __restrict__ static_list, const uint32_t* __restrict__ merged_list,
@@ -864,8 +867,15 @@ __global__ __launch_bounds__(256) void k_project(
                 const float vx = c01, vy = l1 - c00;
                 const float vlen = sqrtf(vx * vx + vy * vy);
                 const float ex = vx / vlen, ey = vy / vlen;
-                const float smaj = fminf(sqrtf(2.0f * l1), 1024.0f);
-                const float smin = fminf(sqrtf(2.0f * l2), 1024.0f);
+                // GSWT_OPT_ANTIALIAS (no counterpart in vs_main): the pixel filter adds s to both eigenvalues -- the rejection above and the
+                // direction stay those of the unfiltered cov2d -- and comp keeps the integrated opacity.  AA = false compiles what there was
+                float l1f = l1, l2f = l2, comp = 1.0f;
+                if (AA) {
+                    l1f = l1 + f.aa_s; l2f = l2 + f.aa_s;
+                    comp = clampf(sqrtf(l1 / l1f) * sqrtf(l2 / l2f), 0.0f, 1.0f);      // (fmaxf drops a NaN: 0)
+                }
+                const float smaj = fminf(sqrtf(2.0f * l1f), 1024.0f);
+                const float smin = fminf(sqrtf(2.0f * l2f), 1024.0f);
                 majx = smaj * ex; majy = smaj * ey;
                 minx = smin * ey; miny = smin * -ex;
                 // A9 :260-265, 402-410
@@ -878,6 +888,7 @@ __global__ __launch_bounds__(256) void k_project(
                     if (lod_id != higher_lod) ca = ca * t_ratio;
                     else ca = ca * (1.0f - t_ratio);
                 }
+                if (AA) ca = ca * comp;
                 // A10 :415-419
                 ndcx = q[0] / q[3]; ndcy = q[1] / q[3]; depth = q[2] / q[3];
                 if (DEBUG) {
@@ -3041,18 +3052,22 @@ void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t 
     if (b.n_chunks == 0) return;
     const uint32_t n_super = b.n_chunks / 256u + 1u;    // super_sums = [pairs x 16 n_super][visible x 16 n_super][exclusive pair prefix x n_super] (kSuperStride), zeroed by k_cull
     const bool full = f.surface_type == 2u || f.draw_mode != 0u;
-#define GSWT_LAUNCH_PROJECT_S(D, F, S, O)                                                                                      \
-    GSWT_LAUNCH((k_project<D, F, S, O>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list, \
+#define GSWT_LAUNCH_PROJECT_S(D, F, S, O, A)                                                                                     \
+    GSWT_LAUNCH((k_project<D, F, S, O, A>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list, \
                 b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums, \
                 b.super_sums, n_super, b.dbg, b.col_f)
     // (the orthographic stage exists in its strict form only: gswt_api.hip refuses an orthographic frame with GSWT_OPT_STRICT_VS = 0)
-#define GSWT_LAUNCH_PROJECT(D, F) do { if (ortho) GSWT_LAUNCH_PROJECT_S(D, F, true, true); else if (strict) GSWT_LAUNCH_PROJECT_S(D, F, true, false); \
-                                       else GSWT_LAUNCH_PROJECT_S(D, F, false, false); } while (0)
+    // (nor has the pixel filter another: AA is a parameter of the STRICT instantiations only, and gswt_api.hip refuses a filtered v2 frame)
+    const bool aa = f.aa_s > 0.0f;
+#define GSWT_LAUNCH_PROJECT_A(D, F, O) do { if (aa) GSWT_LAUNCH_PROJECT_S(D, F, true, O, true); else GSWT_LAUNCH_PROJECT_S(D, F, true, O, false); } while (0)
+#define GSWT_LAUNCH_PROJECT(D, F) do { if (ortho) GSWT_LAUNCH_PROJECT_A(D, F, true); else if (strict) GSWT_LAUNCH_PROJECT_A(D, F, false); \
+                                       else GSWT_LAUNCH_PROJECT_S(D, F, false, false, false); } while (0)
     if (debug && full) { GSWT_LAUNCH_PROJECT(true, true); }
     else if (debug) { GSWT_LAUNCH_PROJECT(true, false); }
     else if (full) { GSWT_LAUNCH_PROJECT(false, true); }
     else { GSWT_LAUNCH_PROJECT(false, false); }
 #undef GSWT_LAUNCH_PROJECT
+#undef GSWT_LAUNCH_PROJECT_A
 #undef GSWT_LAUNCH_PROJECT_S
     GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, n_super, b.counters, b.super_sums + 2u * kSuperStride * n_super, b.pair_cap, b.live_cnt, n_launch / 8u);
 }

@@ -202,7 +202,7 @@ class GSWTRenderer:
                transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba=None, bg_depth=None,
                out_device_ptr: int | None = None, bg_on_device: bool = False, out_format: int = L.GSWT_OUT_RGBA32F,
                depth: bool = False, out_depth_device_ptr: int | None = None, pick: bool = False,
-               out_pick_device_ptr: int | None = None, projection: int | None = None):
+               out_pick_device_ptr: int | None = None, projection: int | None = None, antialias: float | None = None):
         """camera / scene: 176 / 160-byte uniform blocks (any ctypes struct or bytes of that layout).
         Returns the image [rows, W, 4] on the host -- f32 for GSWT_OUT_RGBA32F, uint8 in the channel order of
         GSWT_OUT_RGBA8_UNORM / GSWT_OUT_BGRA8_UNORM --, or None when out_device_ptr is given.
@@ -218,9 +218,13 @@ class GSWTRenderer:
         (image, depth, pick), or behind the planes and the depth of a video format.  With out_device_ptr it goes to
         out_pick_device_ptr (rows x out_w x 16 bytes on the device) when that is given.
         projection: when given, sets GSWT_OPT_PROJECTION first (0 perspective, 1 orthographic: `camera` is then the block of an
-        ortho.OrthoCamera); omitted, the context keeps the projection it has."""
+        ortho.OrthoCamera); omitted, the context keeps the projection it has.
+        antialias: when given, sets GSWT_OPT_ANTIALIAS first: the variance of the screen-space pixel filter in px^2 (0.3 is the
+        usual 3DGS constant, 0.1 Mip-Splatting's, 0 switches it off; rounded to 1/1024 px^2); omitted, the context keeps its value."""
         if projection is not None:
             self.set_option(L.GSWT_OPT_PROJECTION, int(projection))
+        if antialias is not None:
+            self.set_option(L.GSWT_OPT_ANTIALIAS, int(round(float(antialias) * 1024)))
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()
@@ -267,14 +271,16 @@ class GSWTRenderer:
                      lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
                      transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba_ptr: int = 0, bg_depth_ptr: int = 0,
                      out_format: int = L.GSWT_OUT_RGBA32F, out_depth_ptr: int = 0, out_pick_ptr: int = 0,
-                     projection: int | None = None) -> int:
+                     projection: int | None = None, antialias: float | None = None) -> int:
         """Queues a frame (device pointers only) and returns a ticket for render_wait.  out_device_ptr holds rows x out_w x 4
         f32, or bytes for the 8-bit out_format values, or the planes of a GSWT_VIDEO_* format (gswt_out_image_bytes(out_format,
         rows, out_w) bytes, width and height even; see video_planes); out_depth_ptr (optional) receives the depth image, rows x out_w f32
         (gswt_render_async_depth); out_pick_ptr (optional) the pick image, rows x out_w records of PICK_DTYPE (gswt_render_async_pick).
-        projection: as in render (the frame keeps the projection it was submitted with, whatever is set afterwards)."""
+        projection, antialias: as in render (the frame keeps the values it was submitted with, whatever is set afterwards)."""
         if projection is not None:
             self.set_option(L.GSWT_OPT_PROJECTION, int(projection))
+        if antialias is not None:
+            self.set_option(L.GSWT_OPT_ANTIALIAS, int(round(float(antialias) * 1024)))
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()

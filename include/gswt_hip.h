@@ -265,7 +265,39 @@ enum { GSWT_OPT_NO_LOD_PREFILTER = 1, GSWT_OPT_DEBUG_VARYINGS = 2,
                                    gswt_proxy_render remain perspective-only: an orthographic frame takes whatever bg_rgba / bg_depth the caller
                                    gives it.  Order: the worker's tile order is by distance from the sort event's camera, so a top-down view that
                                    shares the main view's draw set should use GSWT_ORDER_DEPTH, which is exact per splat; GSWT_ORDER_REFERENCE
-                                   also runs and is well defined (draw rank x list position).  The CPU oracle has no orthographic mode */ };
+                                   also runs and is well defined (draw rank x list position).  The CPU oracle has no orthographic mode */,
+       GSWT_OPT_ANTIALIAS = 18 /* anti-aliased splats: a screen-space low-pass with opacity compensation.  `value` is the variance of an
+                                  isotropic Gaussian pixel filter in 1/1024 px^2 OF THE SCREEN: 0 (default) off, 1..4096 on, anything else
+                                  refused (GSWT_ERR_BAD_ARG).  v = value / 1024 is exact in binary32; 307 is about 0.3 px^2, the usual 3DGS
+                                  constant, 102 about 0.1 px^2, the Mip-Splatting one.  vs_main has no such filter (gswt.wgsl:245-258: cov2d
+                                  goes straight into the eigen-decomposition), so with the option off a splat whose footprint is below a
+                                  pixel is drawn at full opacity or not at all, depending on where its centre falls between pixel centres.
+                                  Why s = 4 v / splat_scale^2: the fragment stage weights a pixel at offset x = 0.5 splat_scale (p.x major +
+                                  p.y minor) by exp(-|p|^2) with major = sqrt(2 lambda1) e, so a splat's on-screen Gaussian has covariance
+                                  (splat_scale^2 / 4) cov2d; convolving it with the pixel filter adds v I on screen, i.e. s I on cov2d.  The
+                                  host computes s once per frame in binary32 as (4.0f * v) / (splat_scale * splat_scale).
+                                  Vertex stage: the strict sequence is unchanged up to and including `if (l2 < 0) discard` -- the rejection
+                                  is decided on the unfiltered l2 and the direction (ex, ey) comes from the unfiltered c01, l1 - c00 (adding
+                                  s I does not change eigenvectors).  Then, one binary32 operation per written operator, nothing fused:
+                                      l1f = l1 + s;  l2f = l2 + s;
+                                      smaj = fminf(sqrtf(2.0f * l1f), 1024.0f);   smin = fminf(sqrtf(2.0f * l2f), 1024.0f);
+                                      comp = clamp(sqrtf(l1 / l1f) * sqrtf(l2 / l2f), 0.0f, 1.0f);      a NaN gives 0
+                                  major / minor are built from smaj, smin, ex, ey as before, and alpha = alpha * comp goes after the
+                                  LOD-transition product and before the near fade.  comp keeps the splat's integrated opacity: alpha'
+                                  sqrt(l1f l2f) = alpha sqrt(l1 l2).  Everything downstream reads the stored axes and alpha and follows
+                                  without change: the pair rectangle and the compositor's |p|^2 <= 4, depth and pick weights, every output
+                                  format, both order modes, shards (the column-band cull bounds a splat's reach with lambda + s),
+                                  GSWT_OPT_PROJECTION = 1, the surface mappings, the point-cloud radius and the debug draw modes (the filter
+                                  sits after cov2d in all of them).  gswt_debug_read_projected reports the filtered axes and the compensated
+                                  alpha.  The visible set can only grow: a splat with l2 == 0, or whose |minor|^2 underflowed in the fragment
+                                  setup, was invisible and is now drawn.  Read when a frame is submitted, like GSWT_OPT_PROJECTION: setting
+                                  it waits for nothing; frames in flight and a frame re-run after a pair-buffer overflow keep the value they
+                                  were submitted with.  With value > 0 a submit returns GSWT_ERR_BAD_ARG before anything is enqueued for
+                                  GSWT_OPT_STRICT_VS = 0 (sequence v2 has no filtered form) and for a splat_scale that is zero or not finite, or
+                                  so large or small that s as computed above is not a finite positive number (|splat_scale| beyond about
+                                  1.8e19, or below about 2e-19 at value 4096).
+                                  Out of scope: the uncompensated "dilate only" variant; a filter for gswt_skybox_render / gswt_proxy_render;
+                                  the CPU oracle, which has no filter */ };
 GSWT_API int gswt_set_option(gswt_ctx *ctx, int key, int value);
 
 /* GSWTRenderer::new (renderer.rs:31-349): uploads PreloadData.tile_splats_merged.tex_data
