@@ -20,15 +20,10 @@
 #include <new>
 #include <string>
 
-#include "../../include/gswt_hip.h"
-#include "gswt_device.h"
+#include "gswt_ctx.h"
 #define GSWT_HD __host__ __device__
 #include "host/gswt_math.h"
 #include "host/gswt_surface.h"
-
-namespace gswt {
-int ctx_device(const gswt_ctx*);
-}  // namespace gswt
 
 using namespace gswt_host;
 
@@ -950,10 +945,7 @@ int read_counts(gswt_worker* w)
 }  // namespace
 
 // No C++ exception may unwind through the C ABI (std::string / std::mutex / std::lock_guard can throw, and these entry points are
-// called from a second host thread): every int-returning entry point below is a function-try-block.
-#define GSWT_WCATCH                                             \
-    catch (const std::bad_alloc&) { return GSWT_ERR_CAPACITY; } \
-    catch (...) { return GSWT_ERR_HIP; }
+// called from a second host thread): every int-returning entry point below is a function-try-block closed by GSWT_CATCH (gswt_ctx.h).
 
 extern "C" {
 
@@ -963,10 +955,10 @@ try {
     *out = nullptr;
     gswt_worker* w = new (std::nothrow) gswt_worker();
     if (!w) return GSWT_ERR_CAPACITY;
-    // (an exception thrown below -- std::string, std::mutex, allocation -- unwinds into GSWT_WCATCH: the guard destroys the half-built worker)
+    // (an exception thrown below -- std::string, std::mutex, allocation -- unwinds into GSWT_CATCH: the guard destroys the half-built worker)
     struct Guard { gswt_worker* w; ~Guard() { if (w) gswt_worker_destroy(w); } } guard{w};
     w->ctx = ctx;
-    w->device = gswt::ctx_device(ctx);
+    w->device = ctx->device;
     auto bail = [&](int code) { guard.w = nullptr; gswt_worker_destroy(w); return code; };
     const size_t cells = (size_t)cfg->map_w * cfg->map_h;
     if (cells == 0 || cfg->n_lod == 0 || cfg->n_lod > 16 || cfg->n_tile == 0 || cfg->n_view == 0 || !cfg->lod_transition_dist || !cfg->tile_center || !cfg->tile_aabb ||
@@ -1054,7 +1046,7 @@ try {
     guard.w = nullptr;
     *out = w;
     return GSWT_OK;
-} GSWT_WCATCH
+} GSWT_CATCH
 
 void gswt_worker_destroy(gswt_worker* w)
 {
@@ -1092,7 +1084,7 @@ try {
     }
     w->have_cells = true; w->have_lod = false; w->have_sort = false; w->sort_pending = false;
     return GSWT_OK;
-} GSWT_WCATCH
+} GSWT_CATCH
 
 int gswt_worker_update_lod(gswt_worker* w, const float cam_pos[3])
 try {
@@ -1105,7 +1097,7 @@ try {
     WHIP(hipGetLastError());
     w->have_lod = true;
     return GSWT_OK;
-} GSWT_WCATCH
+} GSWT_CATCH
 
 int gswt_worker_sort_tiles(gswt_worker* w, const float cam_pos[3], const float vp16[16])
 try {
@@ -1146,7 +1138,7 @@ try {
     WHIP(hipGetLastError());
     w->have_sort = true; w->sort_pending = true;
     return GSWT_OK;
-} GSWT_WCATCH
+} GSWT_CATCH
 
 int gswt_worker_read_cell_state(gswt_worker* w, gswt_cell_state* out, size_t capacity)
 try {
@@ -1157,7 +1149,7 @@ try {
     WHIP(hipMemcpy(out, w->st.p, (size_t)w->cells * sizeof(gswt_cell_state), hipMemcpyDeviceToHost));
     for (int i = 0; i < w->cells; i++) if (out[i].merge != MS_TO) out[i].merged_to = 0;
     return GSWT_OK;
-} GSWT_WCATCH
+} GSWT_CATCH
 
 int gswt_worker_fetch(gswt_worker* w)
 try {
@@ -1188,7 +1180,7 @@ try {
     }
     w->sort_pending = false;
     return GSWT_OK;
-} GSWT_WCATCH
+} GSWT_CATCH
 
 int gswt_worker_read_sort(gswt_worker* w, gswt_sort_data* out)
 try {
@@ -1207,7 +1199,7 @@ try {
     out->n_groups = c[C_N_GROUPS]; out->n_members = c[C_N_MEMBERS];
     out->groups = h.groups.p; out->members = h.members.p;
     return GSWT_OK;
-} GSWT_WCATCH
+} GSWT_CATCH
 
 int gswt_set_draws_from_worker(gswt_ctx* ctx, gswt_worker* w)
 try {
@@ -1228,6 +1220,6 @@ try {
         w->in_use = -1;
     }
     return r;                                          // failure text: gswt_last_error(ctx)
-} GSWT_WCATCH
+} GSWT_CATCH
 
 }  // extern "C"

@@ -23,7 +23,7 @@ I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 class Ctx:
     """A renderer with a one-splat scene (never rendered here) and a synthetic raw-depth table: raw[lt][view] (lt = lod * N_TILE + tile)."""
 
-    def __init__(self, counts, gen, seed=0):
+    def __init__(self, counts, gen, seed=0, upload_raw=True):
         from gswt_renderer_amd.renderer import GSWTRenderer
         self.r = GSWTRenderer(0)
         lists = [[[np.zeros(1, np.uint32)] * N_VIEW for _ in range(N_TILE)] for _ in range(N_LOD)]
@@ -34,7 +34,8 @@ class Ctx:
         self.offset = np.ascontiguousarray(rng.integers(0, 1 << 26, NLT), dtype=np.uint32)
         self.raw = [[np.ascontiguousarray(gen(lt, v, int(self.counts[lt]), rng), dtype=np.int32) for v in range(N_VIEW)] for lt in range(NLT)]
         ptrs = (C.c_void_p * (NLT * N_VIEW))(*[self.raw[lt][v].ctypes.data if self.counts[lt] else None for lt in range(NLT) for v in range(N_VIEW)])
-        self.r._check(self.r._lib.gswt_upload_raw_depth(self.r._h, ptrs, self.counts.ctypes.data, self.offset.ctypes.data))
+        if upload_raw:
+            self.r._check(self.r._lib.gswt_upload_raw_depth(self.r._h, ptrs, self.counts.ctypes.data, self.offset.ctypes.data))
 
     def close(self):
         self.r.close()
@@ -42,8 +43,8 @@ class Ctx:
     def group_len(self, members):
         return sum(int(self.counts[l * N_TILE + t]) for _, lod, t, other in members for l in (lod, other) if l >= 0)
 
-    def submit(self, groups, draws=True):
-        """groups: [(view, [(map_index, lod, tile, other_lod), ...])] -> the C call's return code."""
+    def tables(self, groups, draws=True):
+        """groups: [(view, [(map_index, lod, tile, other_lod), ...])] -> the C call's arrays and counts (D, nd, G, ng, M, nm)."""
         mem = [m for _, ms in groups for m in ms]
         G = (L.MergeGroup * max(1, len(groups)))()
         M = (L.MergeMember * max(1, len(mem)))()
@@ -62,7 +63,11 @@ class Ctx:
                 nd += 1
             first += len(ms)
             base += n
-        return self.r._lib.gswt_set_draws_merge_groups(self.r._h, D, nd, G, len(groups), M, len(mem))
+        return D, nd, G, len(groups), M, len(mem)
+
+    def submit(self, groups, draws=True):
+        """-> the C call's return code."""
+        return self.r._lib.gswt_set_draws_merge_groups(self.r._h, *self.tables(groups, draws))
 
     def expect(self, groups):
         lists, maps = [np.zeros(0, np.uint32)], [np.zeros(0, np.uint32)]
@@ -244,6 +249,51 @@ def test_reuse_across_events_matches_no_reuse():
         finally:
             ctx.close()
     assert np.array_equal(results[0][0], results[1][0]) and np.array_equal(results[0][1], results[1][1])
+
+
+def test_refused_events_leave_the_previous_lists_and_the_ctx_usable():
+    """Every refusal of gswt_set_draws_merge_groups past the group cap -- a group's member range, view id, a member's lod or tile, a
+    merged draw's count, group or single_draw flag (GSWT_ERR_BAD_ARG), and an event before gswt_upload_raw_depth (GSWT_ERR_STATE) --
+    leaves the lists of the previous event current and byte-identical, and the events after them build and reuse as usual."""
+    ctx = Ctx(_scene_counts(), _uniform())
+    bare = Ctx(_scene_counts(), _uniform(), upload_raw=False)
+    try:
+        rng = np.random.default_rng(31)
+        first = _random_groups(rng, 40)
+        kept = [a.copy() for a in ctx.check(first, "first event")]
+
+        def unchanged(tag):
+            got = ctx.r.read_merged()
+            assert np.array_equal(got[0], kept[0]) and np.array_equal(got[1], kept[1]), tag
+
+        def group_past_members(D, nd, G, ng, M, nm): G[ng - 1].n_members += 1
+        def view_out_of_range(D, nd, G, ng, M, nm): G[3].view_id = N_VIEW
+        def lod_out_of_range(D, nd, G, ng, M, nm): M[5].lod = N_LOD
+        def tile_out_of_range(D, nd, G, ng, M, nm): M[5].tile = N_TILE
+        def count_off_by_one(D, nd, G, ng, M, nm): D[7].merged_count += 1
+        def group_out_of_range(D, nd, G, ng, M, nm): D[7].merged_group = ng
+        def no_single_draw(D, nd, G, ng, M, nm): D[7].tile.single_draw = 0
+
+        for spoil in (group_past_members, view_out_of_range, lod_out_of_range, tile_out_of_range, count_off_by_one, group_out_of_range,
+                      no_single_draw):
+            t = ctx.tables(_random_groups(rng, 40))
+            assert t[1] == 40 and t[3] == 40 and t[5] > 5        # (every count of the tile set is > 0: one merged draw per group)
+            spoil(*t)
+            rc = ctx.r._lib.gswt_set_draws_merge_groups(ctx.r._h, *t)
+            assert rc == L.GSWT_ERR_BAD_ARG, (spoil.__name__, rc, ctx.r._lib.gswt_last_error(ctx.r._h).decode())
+            unchanged(spoil.__name__)
+        rc = bare.submit(_random_groups(rng, 40))
+        assert rc == L.GSWT_ERR_STATE, (rc, bare.r._lib.gswt_last_error(bare.r._h).decode())
+        assert bare.r.read_merged()[0].size == 0
+        unchanged("an event refused on another context")
+
+        ctx.check(_random_groups(rng, 40), "a fresh event after the refusals")
+        reused0 = ctx.r.merge_stats()[1]
+        ctx.check(first[:20] + _random_groups(rng, 20), "an event that repeats groups of the first one")
+        assert ctx.r.merge_stats()[1] > reused0
+    finally:
+        ctx.close()
+        bare.close()
 
 
 def test_c5_map_event_with_hundreds_of_groups(renderer):

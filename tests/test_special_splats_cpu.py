@@ -121,7 +121,7 @@ def test_every_half_pattern_decodes_as_the_shader():
 
 
 def band_half_val(h):
-    """Python restatement of half_val in gswt_upload_scene (gswt_api.hip), in float32 like the C++."""
+    """Python restatement of half_val in gswt_upload_scene (gswt_api_scene.hip), in float32 like the C++."""
     h = int(h)
     e, fr = (h >> 10) & 0x1F, h & 0x3FF
     if e == 31:

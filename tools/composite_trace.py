@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-work-item phase stamps of the compositor from a -DGSWT_TRACE build of the library (GSWT_HIP_LIB=build_var/libgswt_hip_trace.so):
 one frame per segment length (pairs per work item), the raw stamps saved to trace_<workload>_<seg>.npy in the working directory and a summary printed.
-Build: hipcc <Makefile flags> -DGSWT_TRACE -shared gswt_kernels.hip gswt_passes.hip gswt_api.hip gswt_worker.hip -o build_var/libgswt_hip_trace.so"""
+Build: make -C gswt_renderer_amd/csrc variants (hipcc <Makefile flags> -DGSWT_TRACE -shared $(SRCS), the Makefile's source list, -o build_var/libgswt_hip_trace.so)"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
