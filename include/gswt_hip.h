@@ -123,7 +123,10 @@ typedef struct {
 /* The parts of RenderConfig (structure.rs:346-388) read on the hot path. */
 typedef struct {
     float culling_dist;       /* render_config.culling_dist, renderer.rs:490 */
-    uint32_t lod_enable_mask; /* bit l = render_config.lod_enable[l], renderer.rs:495 */
+    uint32_t lod_enable_mask; /* bit l = render_config.lod_enable[l], renderer.rs:495.  A draw is kept iff bit
+                                 (gswt_draw.lod & 31) is set: gswt_draw.lod is tid.0 -- of a blending draw the tile's own LOD,
+                                 not base_lod; of a merged draw its head's -- and a lod of 32 or more wraps (32 reads bit 0),
+                                 where the reference would index past lod_enable and panic */
     int32_t order_mode;       /* GSWT_ORDER_* */
     float transmittance_eps;  /* front-to-back early-out threshold; 0 = never stop early */
     /* screen-tile sharding for multi-GPU; shard_count <= 1 renders the whole frame.
