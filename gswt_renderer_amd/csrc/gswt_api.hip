@@ -15,6 +15,7 @@
 //   rects/recs   8 + 32 B / slot  per-frame projection output, slot = composite order (+ 4 B depth side array when depth-tested)
 //   keys/vals    2 x (4+4) B / pair  ping-pong for the tile sort
 #include "gswt_ctx.h"
+#include "host/gswt_surface.h"
 
 #include <algorithm>
 #include <limits>
@@ -26,17 +27,6 @@ using namespace gswt;
 // (validate_frame .. gswt_render_fence, graph replay included: its helpers are static and inline into each other, and the per-frame host
 // time is part of the benchmark) and the frame debug readers.  gswt_api_scene.hip: the scene uploads; gswt_api_draws.hip: sort events;
 // gswt_api_passes.hip: skybox and proxy; gswt_api_comm.hip: sharding and the two gather transports.  gswt_ctx.h is what they share.
-
-// cgmath Matrix4 * Matrix4 (camera.rs:86-88): out[c][r] = sum_k a[k][r] * b[c][k], left to right
-static void mat4_mul(const float* a, const float* b, float* out)
-{
-    for (int c = 0; c < 4; c++)
-        for (int r = 0; r < 4; r++) {
-            float acc = a[r] * b[4 * c];
-            for (int k = 1; k < 4; k++) acc = acc + a[4 * k + r] * b[4 * c + k];
-            out[4 * c + r] = acc;
-        }
-}
 
 static int finish_frame(gswt_ctx* c, FrameSlot& sl);
 
@@ -211,7 +201,7 @@ try {
     hipSetDevice(c->device);
     HIP_TRY(c, collect_pending(c));
     if (!height_map || hm_w <= 0 || hm_h <= 0) { c->hm_w = c->hm_h = 0; return GSWT_OK; }
-    HIP_TRY(c, c->hmap.ensure((size_t)hm_w * hm_h + 2));         // + padding: k_project reads a cell's two texels of a row as one 8-byte load
+    HIP_TRY(c, c->hmap.ensure((size_t)hm_w * hm_h + 2));         // + padding: sample_height (k_project, k_proxy) loads a row's two texels as 8 bytes
     HIP_TRY(c, hipMemcpy(c->hmap.p, height_map, (size_t)hm_w * hm_h * 4, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(c->hmap.p + (size_t)hm_w * hm_h, 0, 8));
     {
@@ -221,7 +211,7 @@ try {
             for (int x = 0; x < hm_w; x++) {
                 const float h = height_map[(size_t)y * hm_w + x];
                 const float hr = height_map[(size_t)y * hm_w + (x + 1 == hm_w ? 0 : x + 1)], hd = height_map[(size_t)(y + 1 == hm_h ? 0 : y + 1) * hm_w + x];
-                if (!(h == h) || h > 3e38f || h < -3e38f) finite = false;
+                if (!gswt_host::finite_coord(h)) finite = false;
                 mn = std::min(mn, h); mx = std::max(mx, h);
                 du = std::max(du, std::fabs(hr - h)); dv = std::max(dv, std::fabs(hd - h));
             }
@@ -358,7 +348,7 @@ static Frame make_frame(const gswt_ctx& c, const FrameArgs& a, const ShardGeom& 
     memset(&f, 0, sizeof(f));
     memcpy(f.V, cam->view, 64);
     gl_to_wgpu_projection(cam->projection, f.GP);
-    mat4_mul(cam->projection, cam->view, f.VP);
+    gswt_host::mat4_mul(cam->projection, cam->view, f.VP);
     f.focal[0] = cam->focal[0]; f.focal[1] = cam->focal[1];
     f.htan[0] = cam->htan_fov[0]; f.htan[1] = cam->htan_fov[1];
     f.cam_pos[0] = cam->cam_pos[0]; f.cam_pos[1] = cam->cam_pos[1]; f.cam_pos[2] = cam->cam_pos[2];
@@ -393,8 +383,8 @@ static Frame make_frame(const gswt_ctx& c, const FrameArgs& a, const ShardGeom& 
         const float hz = su->height_map_scale[2];
         f.surf_zlo = std::min(c.hm_min * hz, c.hm_max * hz); f.surf_zhi = std::max(c.hm_min * hz, c.hm_max * hz);
         // slopes of the mapped surface per world unit: |dh/du| hz / x_range, |dh/dv| hz / y_range (gswt.wgsl:565-599)
-        const float xr = (2.0f * (float)su->map_half_wh[0] + 1.0f) * su->tile_width * su->height_map_scale[0];
-        const float yr = (2.0f * (float)su->map_half_wh[1] + 1.0f) * su->tile_width * su->height_map_scale[1];
+        const float xr = gswt_host::hm_axis_range(su->map_half_wh[0], su->tile_width, su->height_map_scale[0]);
+        const float yr = gswt_host::hm_axis_range(su->map_half_wh[1], su->tile_width, su->height_map_scale[1]);
         const float sx = c.hm_du * std::fabs(hz) / std::fabs(xr), sy = c.hm_dv * std::fabs(hz) / std::fabs(yr);
         f.surf_f2 = (3.0f + sx * sx + sy * sy) * 1.01f;
         // a non-finite height map (gswt_configure leaves +-3e38 bounds), an infinite or NaN range or slope bound: no band culling at all

@@ -2,6 +2,7 @@
 // gswt_upload_scene_rows (the same tables built on the device from the normalised rows, kernels in gswt_scene.hip),
 // gswt_upload_raw_depth (the raw depths of the device-side merged-list build) and gswt_debug_read_scene.
 #include "gswt_ctx.h"
+#include "host/gswt_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,31 +40,15 @@ try {
         float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
         float tr_max = 0.0f;
         bool odd = false;
-        auto half_val = [](uint32_t h) -> float {           // halfToFloat of the shader (gswt.wgsl:478-494), upper bound is enough
-            const uint32_t e = (h >> 10) & 0x1Fu, fr = h & 0x3FFu;
-            if (e == 31u) return 0.0f;
-            const float m = e == 0u ? (float)fr * 2.98023223876953125e-08f : ldexpf(1.0f + (float)fr / 1024.0f, (int)e - 15);
-            return (h & 0x8000u) ? -m : m;
-        };
         for (size_t i = 0; i < n_splats; i++) {
             const uint32_t* r = tex_data + 8 * i;
             float p[3];
             memcpy(p, r, 12);
             for (int k = 0; k < 3; k++) {
-                if (!(p[k] == p[k]) || p[k] > 3e38f || p[k] < -3e38f) { odd = true; continue; }
+                if (!gswt_host::finite_coord(p[k])) { odd = true; continue; }
                 lo[k] = std::min(lo[k], p[k]); hi[k] = std::max(hi[k], p[k]);
             }
-            // the projected extent is bounded by the sum of the decoded covariance's POSITIVE eigenvalues: the trace when the decoded
-            // matrix is positive semi-definite, otherwise at most (trace + sqrt(3) |S|_F) / 2 (nuclear norm <= sqrt(3) Frobenius norm).
-            // The decode makes stored covariances indefinite: an overflowed (Inf) diagonal reads as 0 beside finite off-diagonals
-            // (lambda_1 up to several times the trace), a raw row may hold a negative diagonal.
-            const double xx = half_val(r[4] & 0xFFFFu), xy = half_val(r[4] >> 16), xz = half_val(r[5] & 0xFFFFu);
-            const double yy = half_val(r[5] >> 16), yz = half_val(r[6] & 0xFFFFu), zz = half_val(r[6] >> 16);
-            const double tr_d = xx + yy + zz;
-            const bool psd = xx >= 0.0 && yy >= 0.0 && zz >= 0.0 && xx * yy - xy * xy >= 0.0 && xx * zz - xz * xz >= 0.0 &&
-                             yy * zz - yz * yz >= 0.0 && xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz) >= 0.0;
-            const double fro = std::sqrt(xx * xx + yy * yy + zz * zz + 2.0 * (xy * xy + xz * xz + yz * yz));
-            const float tr = psd ? (float)tr_d : (float)(0.5 * (tr_d + 1.7320508075688772 * fro) * (1.0 + 1e-6));
+            const float tr = gswt_host::cov_extent_bound(r);      // (k_scene_tex folds the same bound on the device)
             if (tr == tr) tr_max = std::max(tr_max, tr);
         }
         commit_local_bounds(c, lo, hi, odd, tr_max);
@@ -72,19 +57,20 @@ try {
     c->lists.assign(nl, ListRef{});
     std::vector<uint32_t> arena;
     std::vector<float> boxes;               // six floats per chunk
-    // bounding box of every chunk of list [base, base + count): chunk k = entries count - 256 (k + 1) .. count - 256 k - 1 (k_project's order);
+    // bounding box of every chunk (chunk_entry_range: k_project's order) of list [base, base + count);
     // a chunk that holds a non-finite position gets the infinite box (never culled)
     auto add_boxes = [&](uint32_t base, uint32_t count) -> uint32_t {
         const uint32_t first = (uint32_t)(boxes.size() / 6);
         for (uint32_t k = 0; (size_t)k * kChunk < count; k++) {
-            const uint32_t hi_i = count - k * (uint32_t)kChunk, lo_i = hi_i > (uint32_t)kChunk ? hi_i - (uint32_t)kChunk : 0u;
+            uint32_t lo_i, hi_i;
+            chunk_entry_range(count, k, lo_i, hi_i);
             float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
             bool odd = false;
             for (uint32_t j = lo_i; j < hi_i; j++) {
                 float pq[3];
                 memcpy(pq, tex_data + 8 * (size_t)(arena[base + j] & kIdxMask), 12);
                 for (int a = 0; a < 3; a++) {
-                    if (!(pq[a] == pq[a]) || pq[a] > 3e38f || pq[a] < -3e38f) odd = true;
+                    if (!gswt_host::finite_coord(pq[a])) odd = true;
                     lo[a] = std::min(lo[a], pq[a]); hi[a] = std::max(hi[a], pq[a]);
                 }
             }

@@ -12,6 +12,13 @@ namespace gswt {
 
 constexpr int kTile = 16;            // screen tile edge, pixels (BASELINE north_star: 16x16 binning)
 constexpr int kChunk = 256;          // list entries per projection workgroup
+// Chunk k of a list of `count` entries is its k-th 256 entries from the END, [count - 256 (k + 1), count - 256 k) cut at 0: the order
+// k_project walks a list in, and what a chunk box of the static lists bounds (gswt_upload_scene on the host, k_scene_boxes).
+__host__ __device__ inline void chunk_entry_range(uint32_t count, uint32_t k, uint32_t& lo, uint32_t& hi)
+{
+    hi = count - k * (uint32_t)kChunk;
+    lo = hi > (uint32_t)kChunk ? hi - (uint32_t)kChunk : 0u;
+}
 constexpr uint32_t kLodShift = 28;   // packed list entry = gs_index | lod_id << 28
 constexpr uint32_t kIdxMask = (1u << kLodShift) - 1u;
 // output image formats, GSWT_OUT_* of gswt_hip.h: RGBA f32 (16 B per pixel), bytes R G B A, bytes B G R A (4 B per pixel)

@@ -1,0 +1,94 @@
+// gswt_device_fn.h -- the device functions more than one kernel file uses, defined once: lane masks, the bit casts, the hot path's half
+// decode and the repeat sampler of the height map.  Included by the four kernel files only (gswt_kernels.hip, gswt_passes.hip,
+// gswt_scene.hip, gswt_worker.hip); the host-only C-ABI files never see it.
+//
+// It is also THE place that makes host/gswt_math.h and host/gswt_surface.h __host__ __device__ (GSWT_HD) for the kernel files: what the
+// host library and the kernels must compute alike (the sphere mapping, the scene's texture words, the worker's surface_mapping) is
+// written there once and compiled into both.
+// Wavefront = 64 lanes.
+#pragma once
+#include "gswt_device.h"
+
+#define GSWT_HD __host__ __device__
+#include "host/gswt_math.h"
+#include "host/gswt_surface.h"
+
+namespace gswt {
+
+// Lane mask of a predicate.  (Not __ballot(int): its argument is an int, so the compiler first materialises the predicate as 0 / 1 in a
+// vector register and compares that again -- two vector instructions per ballot that v_cmp had already answered.)
+__device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// bits of a lane mask below the calling lane (v_mbcnt_lo / _hi): a lane's rank among the lanes the mask names
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+__device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }
+__device__ __forceinline__ float clampf(float e, float lo, float hi) { return fminf(fmaxf(e, lo), hi); }
+
+// halfToFloat, gswt.wgsl:478-494: normals as IEEE; subnormals scale 2^-15 (f * 2^-25);
+// Inf/NaN -> 0.  The definition is gswt_host::half_to_float (host/gswt_math.h, the shader's arithmetic): this is the hot path's form of
+// it and must equal it on all 65536 bit patterns, signs of zero included.
+// (v_cvt_f32_f16 is exact for every finite half, subnormals included: the shader's subnormal scale is half of IEEE's, and its
+// Inf / NaN are 0 -- two selects on the exponent field instead of a branchy bit construction.)
+__device__ __forceinline__ float half_decode(uint32_t h)
+{
+    // on the CONVERTED value: a half's Inf / NaN converts to Inf / NaN (-> 0), its subnormals and zeros to |x| < 2^-14, the smallest normal
+    // half (-> x / 2: exact), everything else is already the shader's value
+    const float x = __half2float(__ushort_as_half((unsigned short)h));
+    const float y = fabsf(x) < 6.103515625e-05f ? x * 0.5f : x;
+    return __builtin_amdgcn_class(x, 0x3 | 0x4 | 0x200) ? 0.0f : y;      // signalling / quiet NaN, -Inf, +Inf
+}
+
+// x mod w for the repeat sampler, identical to ((x % w) + w) % w in integer arithmetic but without the 64-bit
+// division sequences (5 samples x 4 wraps per splat made the HeightMap path ~3000 instructions): the quotient is
+// estimated in float (exact operands below 2^23, so it is off by at most one) and fixed up with two compares.
+__device__ __noinline__ int wrap_repeat_slow(float fx, int w)
+{
+    const long xl = (long)fx;
+    return (int)(((xl % w) + w) % w);
+}
+
+__device__ __forceinline__ int wrap_repeat(float fx, int w)
+{
+    if (fabsf(fx) < 8388608.0f && w < 8388608) {
+        const int x = (int)fx;
+        // a power-of-two map (the reference resizes its random maps to 1024 x 1024, wangtile.rs:405-412): two's-complement AND is the
+        // mathematical modulus; the branch is uniform
+        if ((w & (w - 1)) == 0) return x & (w - 1);
+        int r = x - w * (int)floorf((float)x / (float)w);
+        if (r < 0) r += w;
+        if (r >= w) r -= w;
+        return r;
+    }
+    return wrap_repeat_slow(fx, w);                 // far outside any real map: the exact 64-bit path, out of line
+}
+
+// WebGPU bilinear sample, R32Float, repeat addressing, level 0 (renderer.rs:376-388): the height map of k_project and of k_proxy.
+// The two texels of a row are neighbours unless the cell straddles the map's seam: one 8-byte load per row (the buffer carries one
+// float of padding behind its last row: gswt_configure), the seam case re-reads column 0.  Same texels, same arithmetic as four scalar
+// loads: a splat on the HeightMap surface issues 10 height loads instead of 20.
+__device__ __forceinline__ float sample_height(const float* __restrict__ hm, int w, int h, float u, float v)
+{
+    float x = u * (float)w - 0.5f;
+    float y = v * (float)h - 0.5f;
+    float fx0 = floorf(x), fy0 = floorf(y);
+    float tx = x - fx0, ty = y - fy0;
+    const int xa = wrap_repeat(fx0, w), ya = wrap_repeat(fy0, h);
+    const int yb = ya + 1 == h ? 0 : ya + 1;
+    const float* r0 = hm + (size_t)ya * w + xa;
+    const float* r1 = hm + (size_t)yb * w + xa;
+    // (a two-float vector type with 4-byte alignment: global memory takes a dword-aligned 8-byte load as ONE global_load_dwordx2;
+    // a memcpy of 8 bytes at alignment 4 is lowered to two dword loads)
+    typedef float hm_pair __attribute__((ext_vector_type(2), aligned(4)));
+    hm_pair p0 = *reinterpret_cast<const hm_pair*>(r0), p1 = *reinterpret_cast<const hm_pair*>(r1);
+    if (xa + 1 == w) { p0.y = hm[(size_t)ya * w]; p1.y = hm[(size_t)yb * w]; }
+    float i00 = p0.x, i10 = p0.y;
+    float i01 = p1.x, i11 = p1.y;
+    float i0 = i00 * (1.0f - tx) + i10 * tx;
+    float i1 = i01 * (1.0f - tx) + i11 * tx;
+    return i0 * (1.0f - ty) + i1 * ty;
+}
+
+}  // namespace gswt

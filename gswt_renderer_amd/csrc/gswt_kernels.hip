@@ -18,18 +18,11 @@
 // depth test) are the canonical sequences of DESIGN.md and must round exactly like the
 // CPU oracle; every fused multiply-add below is an explicit fmaf().
 // Wavefront = 64 lanes everywhere in this file.
-#include "gswt_device.h"
+// What other kernel files use too (lane masks, half decode, the height map's sampler) is in gswt_device_fn.h; what the host computes
+// as well (canonical sin / cos, the sphere unfolding, the height-map coordinates) is gswt_host:: of host/gswt_surface.h, one source.
+#include "gswt_device_fn.h"
 
 namespace gswt {
-
-// Lane mask of a predicate.  (Not __ballot(int): its argument is an int, so the compiler first materialises the predicate as 0 / 1 in a
-// vector register and compares that again -- two vector instructions per ballot that v_cmp had already answered.)
-__device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-// bits of a lane mask below the calling lane (v_mbcnt_lo / _hi): a lane's rank among the lanes the mask names
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 // Wave-wide scans and sums through DPP (data-parallel primitives: the neighbour's register arrives with the VALU instruction) instead of
 // __shfl_up / __shfl_down, which compile to ds_bpermute_b32 -- an LDS-crossbar round trip per step, six of them in a dependent chain per
@@ -79,134 +72,12 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(v, 0u), 63);
 }
 
-
-__device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }
-__device__ __forceinline__ float clampf(float e, float lo, float hi) { return fminf(fmaxf(e, lo), hi); }
-
-// halfToFloat, gswt.wgsl:478-494: normals as IEEE; subnormals scale 2^-15 (f * 2^-25);
-// Inf/NaN -> 0.
-// (v_cvt_f32_f16 is exact for every finite half, subnormals included: the shader's subnormal scale is half of IEEE's, and its
-// Inf / NaN are 0 -- two selects on the exponent field instead of a branchy bit construction.)
-__device__ __forceinline__ float half_decode(uint32_t h)
-{
-    // on the CONVERTED value: a half's Inf / NaN converts to Inf / NaN (-> 0), its subnormals and zeros to |x| < 2^-14, the smallest normal
-    // half (-> x / 2: exact), everything else is already the shader's value
-    const float x = __half2float(__ushort_as_half((unsigned short)h));
-    const float y = fabsf(x) < 6.103515625e-05f ? x * 0.5f : x;
-    return __builtin_amdgcn_class(x, 0x3 | 0x4 | 0x200) ? 0.0f : y;      // signalling / quiet NaN, -Inf, +Inf
-}
-
-// x mod w for the repeat sampler, identical to ((x % w) + w) % w in integer arithmetic but without the 64-bit
-// division sequences (5 samples x 4 wraps per splat made the HeightMap path ~3000 instructions): the quotient is
-// estimated in float (exact operands below 2^23, so it is off by at most one) and fixed up with two compares.
-__device__ __noinline__ int wrap_repeat_slow(float fx, int w)
-{
-    const long xl = (long)fx;
-    return (int)(((xl % w) + w) % w);
-}
-
-__device__ __forceinline__ int wrap_repeat(float fx, int w)
-{
-    if (fabsf(fx) < 8388608.0f && w < 8388608) {
-        const int x = (int)fx;
-        // a power-of-two map (the reference resizes its random maps to 1024 x 1024, wangtile.rs:405-412): two's-complement AND is the
-        // mathematical modulus; the branch is uniform
-        if ((w & (w - 1)) == 0) return x & (w - 1);
-        int r = x - w * (int)floorf((float)x / (float)w);
-        if (r < 0) r += w;
-        if (r >= w) r -= w;
-        return r;
-    }
-    return wrap_repeat_slow(fx, w);                 // far outside any real map: the exact 64-bit path, out of line
-}
-
-// WebGPU bilinear sample, R32Float, repeat addressing, level 0 (renderer.rs:376-388).
-// The two texels of a row are neighbours unless the cell straddles the map's seam: one 8-byte load per row (the buffer carries one
-// float of padding behind its last row), the seam case re-reads column 0.  Same texels, same arithmetic as four scalar loads:
-// a splat on the HeightMap surface issues 10 height loads instead of 20.
-__device__ __forceinline__ float sample_height(const float* __restrict__ hm, int w, int h, float u, float v)
-{
-    float x = u * (float)w - 0.5f;
-    float y = v * (float)h - 0.5f;
-    float fx0 = floorf(x), fy0 = floorf(y);
-    float tx = x - fx0, ty = y - fy0;
-    const int xa = wrap_repeat(fx0, w), ya = wrap_repeat(fy0, h);
-    const int yb = ya + 1 == h ? 0 : ya + 1;
-    const float* r0 = hm + (size_t)ya * w + xa;
-    const float* r1 = hm + (size_t)yb * w + xa;
-    // (a two-float vector type with 4-byte alignment: global memory takes a dword-aligned 8-byte load as ONE global_load_dwordx2;
-    // a memcpy of 8 bytes at alignment 4 is lowered to two dword loads)
-    typedef float hm_pair __attribute__((ext_vector_type(2), aligned(4)));
-    hm_pair p0 = *reinterpret_cast<const hm_pair*>(r0), p1 = *reinterpret_cast<const hm_pair*>(r1);
-    if (xa + 1 == w) { p0.y = hm[(size_t)ya * w]; p1.y = hm[(size_t)yb * w]; }
-    float i00 = p0.x, i10 = p0.y;
-    float i01 = p1.x, i11 = p1.y;
-    float i0 = i00 * (1.0f - tx) + i10 * tx;
-    float i1 = i01 * (1.0f - tx) + i11 * tx;
-    return i0 * (1.0f - ty) + i1 * ty;
-}
-
-// Canonical sin / cos (operation sequence fixed in DESIGN.md section 4; the CPU checker restates it): WGSL leaves sin()/cos()
-// accuracy to the implementation, so what must hold is CPU-oracle == GPU bit for bit.
-__device__ __forceinline__ void csincosf(float x, float& sn, float& cs)
-{
-    const float kf = rintf(x * 0.636619772367581343f);
-    float r = fmaf(kf, -1.5703125f, x);
-    r = fmaf(kf, -4.837512969970703125e-4f, r);
-    r = fmaf(kf, -7.54978995489188216e-8f, r);
-    const float z = r * r;
-    float ps = fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f);
-    ps = fmaf(ps, z, -1.6666654611e-1f);
-    const float s = fmaf(ps * z, r, r);
-    float pc = fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f);
-    pc = fmaf(pc, z, 4.166664568298827e-2f);
-    const float c = fmaf(pc * z, z, fmaf(-0.5f, z, 1.0f));
-    const int q = (int)kf & 3;
-    float so = (q & 1) ? c : s, co = (q & 1) ? s : c;
-    if (q == 2 || q == 3) so = -so;
-    if (q == 1 || q == 2) co = -co;
-    sn = so; cs = co;
-}
-
-// sphere_get_uv + sphere_uv_to_pos, gswt.wgsl:515-564
-__device__ __forceinline__ void sphere_point(float block_w, float bidx, float bidy, float bx, float by, float p[3])
-{
-    const float PI = 3.1415926535897932384626433832795f;
-    float u, v;
-    if (bidy == 0.0f) {
-        if (by < bx) {
-            if (bx - by == block_w) u = 0.0f;
-            else u = (by / (block_w - (bx - by)) + bidx) / 5.0f;
-            v = ((block_w - (bx - by)) / block_w) / 3.0f;
-        } else {
-            u = (bx / block_w + bidx) / 5.0f + ((by - bx) / block_w) * 0.1f;
-            v = ((by - bx) / block_w) / 3.0f + (1.0f / 3.0f);
-        }
-    } else {
-        if (by < bx) {
-            u = (bx / block_w + bidx) / 5.0f + ((block_w - (bx - by)) / block_w) * 0.1f;
-            v = ((block_w - (bx - by)) / block_w) / 3.0f + (1.0f / 3.0f);
-        } else {
-            if (by - bx == block_w) u = 0.0f;
-            else u = (bx / (block_w - (by - bx)) + bidx) / 5.0f + 0.1f;
-            v = ((by - bx) / block_w) / 3.0f + (2.0f / 3.0f);
-        }
-    }
-    u = u + 0.5f * floorf(v);
-    u = u * (2.0f * PI);
-    v = (v - 0.5f) * PI;
-    float su, cu, sv, cv;
-    csincosf(u, su, cu);
-    csincosf(v, sv, cv);
-    p[0] = cv * cu; p[1] = cv * su; p[2] = sv;
-}
-
-// rand(), gswt.wgsl:502-504
+// rand(), gswt.wgsl:502-504 (the canonical sin of DESIGN.md section 4: host/gswt_surface.h)
 __device__ __forceinline__ float dbg_rand(float cx, float cy)
 {
     const float d = cx * 12.9898f + cy * 78.233f;
     float sn, cs;
-    csincosf(d, sn, cs);
+    gswt_host::csincosf(d, sn, cs);
     const float v = sn * 43758.5453f;
     return v - floorf(v);
 }
@@ -335,8 +206,9 @@ __device__ __forceinline__ bool sphere_cell_box(const Frame& f, float bidx, floa
     for (int k = 0; k < 3; k++) { blo[k] = 3.402823466e+38f; bhi[k] = -3.402823466e+38f; }
     for (int j = 0; j < n; j++)
         for (int i = 0; i < n; i++) {
-            float p[3];
-            sphere_point(block_w, bidx, bidy, bx0 + (bx1 - bx0) * (((float)i + 0.5f) / (float)n), by0 + (by1 - by0) * (((float)j + 0.5f) / (float)n), p);
+            const gswt_host::V3 pt = gswt_host::sphere_point(block_w, bidx, bidy, bx0 + (bx1 - bx0) * (((float)i + 0.5f) / (float)n),
+                                                             by0 + (by1 - by0) * (((float)j + 0.5f) / (float)n));
+            const float p[3] = {pt.x, pt.y, pt.z};
             for (int k = 0; k < 3; k++) { blo[k] = fminf(blo[k], p[k] * f.sphere_radius - rho); bhi[k] = fmaxf(bhi[k], p[k] * f.sphere_radius + rho); }
         }
     return blo[0] == blo[0] && bhi[0] == bhi[0] && blo[1] == blo[1] && bhi[1] == bhi[1] && blo[2] == blo[2] && bhi[2] == bhi[2];
@@ -697,10 +569,10 @@ __global__ __launch_bounds__(256) void k_project(
             float F[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
             if (f.surface_type == 1u) {
                 const float DELTA = 0.001f;
-                float xr = (2.0f * (float)f.map_half_wh[0] + 1.0f) * f.tile_width * f.height_map_scale[0];
-                float yr = (2.0f * (float)f.map_half_wh[1] + 1.0f) * f.tile_width * f.height_map_scale[1];
-                float h_u = (c0 + (float)f.map_half_wh[0] * f.tile_width) / xr;
-                float h_v = (c1 + (float)f.map_half_wh[1] * f.tile_width) / yr;
+                float xr = gswt_host::hm_axis_range(f.map_half_wh[0], f.tile_width, f.height_map_scale[0]);
+                float yr = gswt_host::hm_axis_range(f.map_half_wh[1], f.tile_width, f.height_map_scale[1]);
+                float h_u = gswt_host::hm_axis_coord(c0, f.map_half_wh[0], f.tile_width, xr);
+                float h_v = gswt_host::hm_axis_coord(c1, f.map_half_wh[1], f.tile_width, yr);
                 float hz = f.height_map_scale[2];
                 float nz = sample_height(hmap, f.hm_w, f.hm_h, h_u, h_v) * hz;
                 float dt = DELTA;
@@ -723,7 +595,8 @@ __global__ __launch_bounds__(256) void k_project(
                 c2 = nz + F[8] * z;
                 mapped_z = nz;
             } else if (FULL && f.surface_type == 2u) {
-                // surface_mapping, gswt.wgsl:600-623 (icosahedral-strip parametrisation, 5 x 2 blocks)
+                // surface_mapping, gswt.wgsl:600-623 (icosahedral-strip parametrisation, 5 x 2 blocks); sphere_get_uv + sphere_uv_to_pos
+                // (gswt.wgsl:515-564) are gswt_host::sphere_point, the one the host's tile centres use
                 const float DELTA = 0.001f;
                 const float xmax = ((float)f.map_half_wh[0] * 2.0f) * f.tile_width;
                 const float ymax = ((float)f.map_half_wh[1] * 2.0f) * f.tile_width;
@@ -739,14 +612,17 @@ __global__ __launch_bounds__(256) void k_project(
                     bidy = (float)(2u * (map_id % map_height) / (f.map_half_wh[1] * 2u));
                 }
                 const float bx = nx - bidx * block_w, by = ny - bidy * block_w;
-                float lz[3], pr[3], pl[3], pu[3], pd[3];
-                sphere_point(block_w, bidx, bidy, bx, by, lz);
+                using gswt_host::V3;
+                using gswt_host::sphere_point;
+                const V3 lzv = sphere_point(block_w, bidx, bidy, bx, by);
                 const float R = f.sphere_radius;
                 const float dt = DELTA * ymax;
-                sphere_point(block_w, bidx, bidy, bx + dt, by, pr);
-                sphere_point(block_w, bidx, bidy, bx - dt, by, pl);
-                sphere_point(block_w, bidx, bidy, bx, by + dt, pu);
-                sphere_point(block_w, bidx, bidy, bx, by - dt, pd);
+                const V3 prv = sphere_point(block_w, bidx, bidy, bx + dt, by), plv = sphere_point(block_w, bidx, bidy, bx - dt, by);
+                const V3 puv = sphere_point(block_w, bidx, bidy, bx, by + dt), pdv = sphere_point(block_w, bidx, bidy, bx, by - dt);
+                // (by component for the loop below: the nine entries written out from the V3 fields schedule k_project<FULL> differently,
+                // and the device assembly of this file is kept byte for byte)
+                const float lz[3] = {lzv.x, lzv.y, lzv.z}, pr[3] = {prv.x, prv.y, prv.z}, pl[3] = {plv.x, plv.y, plv.z};
+                const float pu[3] = {puv.x, puv.y, puv.z}, pd[3] = {pdv.x, pdv.y, pdv.z};
                 for (int k = 0; k < 3; k++) {
                     F[k] = (pr[k] * R - pl[k] * R) / (2.0f * dt);
                     F[3 + k] = (pu[k] * R - pd[k] * R) / (2.0f * dt);

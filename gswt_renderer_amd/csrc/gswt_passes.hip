@@ -10,10 +10,12 @@
 //              pushing up to 2 x 2048^2 triangles through a rasteriser, every pixel casts its view ray at the height field
 //              (2-D DDA over the grid cells, two triangles per cell); the nearest fragment with depth in [0, 1] is exactly
 //              what depth-test-Less rasterisation keeps.  Implicit-LOD trilinear texturing from the uv differences to the
-//              right / lower pixel on the fragment's plane.
+//              right / lower pixel on the fragment's plane.  The height map is read through sample_height, the splat path's
+//              sampler (gswt_device_fn.h: one definition, the padded buffer of gswt_configure); the repeat wraps of the proxy
+//              texture and of the panorama are its wrap_repeat.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (same flags as gswt_kernels.hip).
-#include "gswt_device.h"
+#include "gswt_device_fn.h"
 
 #include <algorithm>
 
@@ -81,40 +83,6 @@ void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int
 // ---- proxy -----------------------------------------------------------------------------------------
 
 
-// x mod w of the repeat samplers without 64-bit division (see gswt_kernels.hip): float quotient + two fix-ups
-__device__ __noinline__ int p_wrap_repeat_slow(float fx, int w)
-{
-    const long xl = (long)fx;
-    return (int)(((xl % w) + w) % w);
-}
-
-__device__ __forceinline__ int p_wrap_repeat(float fx, int w)
-{
-    if (fabsf(fx) < 8388608.0f && w < 8388608) {
-        const int x = (int)fx;
-        int r = x - w * (int)floorf((float)x / (float)w);
-        if (r < 0) r += w;
-        if (r >= w) r -= w;
-        return r;
-    }
-    return p_wrap_repeat_slow(fx, w);
-}
-
-// WebGPU bilinear, R32Float, repeat (same sampler as the splat kernel's height map)
-__device__ __forceinline__ float p_sample_height(const float* __restrict__ hm, int w, int h, float u, float v)
-{
-    float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
-    float fx0 = floorf(x), fy0 = floorf(y);
-    float tx = x - fx0, ty = y - fy0;
-    const int xa = p_wrap_repeat(fx0, w), ya = p_wrap_repeat(fy0, h);
-    const int xb = xa + 1 == w ? 0 : xa + 1, yb = ya + 1 == h ? 0 : ya + 1;
-    float i00 = hm[ya * w + xa], i10 = hm[ya * w + xb];
-    float i01 = hm[yb * w + xa], i11 = hm[yb * w + xb];
-    float i0 = i00 * (1.0f - tx) + i10 * tx;
-    float i1 = i01 * (1.0f - tx) + i11 * tx;
-    return i0 * (1.0f - ty) + i1 * ty;
-}
-
 __device__ __forceinline__ void pixel_ray(const float* V, float p00, float p11, int x, int y, int W, int H, float d[3])
 {
     const float nx = ((float)x + 0.5f) / (float)W * 2.0f - 1.0f;
@@ -128,11 +96,11 @@ __device__ __forceinline__ void pixel_ray(const float* V, float p00, float p11, 
 __device__ __forceinline__ float proxy_mapped_height(const ProxyArgs& a, const float* __restrict__ hm, float rx, float ry)
 {
     if (a.surface_type != 1u) return 0.0f;
-    const float xr = (2.0f * (float)a.map_half_wh[0] + 1.0f) * a.tile_width * a.height_map_scale[0];
-    const float yr = (2.0f * (float)a.map_half_wh[1] + 1.0f) * a.tile_width * a.height_map_scale[1];
-    const float h_u = (rx + (float)a.map_half_wh[0] * a.tile_width) / xr;
-    const float h_v = (ry + (float)a.map_half_wh[1] * a.tile_width) / yr;
-    return p_sample_height(hm, a.hm_w, a.hm_h, h_u, h_v) * a.height_map_scale[2];
+    const float xr = gswt_host::hm_axis_range(a.map_half_wh[0], a.tile_width, a.height_map_scale[0]);
+    const float yr = gswt_host::hm_axis_range(a.map_half_wh[1], a.tile_width, a.height_map_scale[1]);
+    const float h_u = gswt_host::hm_axis_coord(rx, a.map_half_wh[0], a.tile_width, xr);
+    const float h_v = gswt_host::hm_axis_coord(ry, a.map_half_wh[1], a.tile_width, yr);
+    return sample_height(hm, a.hm_w, a.hm_h, h_u, h_v) * a.height_map_scale[2];
 }
 
 __device__ __forceinline__ bool proxy_depth(const ProxyArgs& a, const float hp[3], float& depth)
@@ -187,7 +155,7 @@ __device__ __forceinline__ void proxy_tex_bilinear(const float4* __restrict__ lv
     const float x = u * (float)n - 0.5f, y = v * (float)n - 0.5f;
     const float fx0 = floorf(x), fy0 = floorf(y);
     const float wx = x - fx0, wy = y - fy0;
-    const int xa = p_wrap_repeat(fx0, n), ya = p_wrap_repeat(fy0, n);
+    const int xa = wrap_repeat(fx0, n), ya = wrap_repeat(fy0, n);
     const int xb = xa + 1 == n ? 0 : xa + 1, yb = ya + 1 == n ? 0 : ya + 1;
     const float4 c00 = lvl[ya * n + xa], c10 = lvl[ya * n + xb], c01 = lvl[yb * n + xa], c11 = lvl[yb * n + xb];
     out[0] = (c00.x * (1.0f - wx) + c10.x * wx) * (1.0f - wy) + (c01.x * (1.0f - wx) + c11.x * wx) * wy;
@@ -307,7 +275,7 @@ __global__ __launch_bounds__(256) void k_skybox_bake(const SkyBakeArgs a, const 
     const float sx = u * (float)w - 0.5f, sy = v * (float)h - 0.5f;
     const float fx0 = floorf(sx), fy0 = floorf(sy);
     const float tx = sx - fx0, ty = sy - fy0;
-    const int xa = p_wrap_repeat(fx0, w), ya = p_wrap_repeat(fy0, h);
+    const int xa = wrap_repeat(fx0, w), ya = wrap_repeat(fy0, h);
     const int xb = xa + 1 == w ? 0 : xa + 1, yb = ya + 1 == h ? 0 : ya + 1;
     const float4 c00 = equi[(size_t)ya * w + xa], c10 = equi[(size_t)ya * w + xb];
     const float4 c01 = equi[(size_t)yb * w + xa], c11 = equi[(size_t)yb * w + xb];

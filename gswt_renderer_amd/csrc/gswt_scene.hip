@@ -9,36 +9,21 @@
 //   k_scene_self    : self list = the pair list's own-LOD entries, order kept (stable compaction, one workgroup per list)
 //   k_scene_boxes   : tile-local bounding box of every 256-entry chunk of every static list (one wave per chunk)
 //
-// Built with -ffp-contract=off like the host library: the texture words, raw depths and bounds are the host's bit for bit.
+// Built with -ffp-contract=off like the host library: the texture words, raw depths and bounds are the host's bit for bit -- the
+// per-record arithmetic (texture row, raw depth, half decode, covariance bound, finite test) is gswt_host:: of host/gswt_math.h, the
+// chunk ranges chunk_entry_range of gswt_device.h: the sources the host path compiles.
 // Wavefront = 64 lanes.
-#include "gswt_device.h"
-#define GSWT_HD __host__ __device__
-#include "host/gswt_math.h"
+#include "gswt_device_fn.h"
 
 namespace gswt {
 
 namespace {
-
-__device__ __forceinline__ unsigned long long scene_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-__device__ __forceinline__ uint32_t scene_lanes_below(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 // order-preserving map f32 -> i32 (and back: the map is its own inverse); -0 sorts below +0, which the bounds compare as equal
 __device__ __forceinline__ int32_t f2ord(float f)
 {
     const int32_t i = __float_as_int(f);
     return i >= 0 ? i : i ^ 0x7FFFFFFF;
-}
-
-// halfToFloat of the shader (gswt.wgsl:478-494) as gswt_upload_scene's host loop decodes it: Inf / NaN read as 0
-__device__ __forceinline__ float scene_half_val(uint32_t h)
-{
-    const uint32_t e = (h >> 10) & 0x1Fu, fr = h & 0x3FFu;
-    if (e == 31u) return 0.0f;
-    const float m = e == 0u ? (float)fr * 2.98023223876953125e-08f : ldexpf(1.0f + (float)fr / 1024.0f, (int)e - 15);
-    return (h & 0x8000u) ? -m : m;
 }
 
 __device__ __forceinline__ uint32_t scene_find_lt(const uint32_t* __restrict__ moff, uint32_t n_lt, uint32_t g)
@@ -66,16 +51,10 @@ __global__ __launch_bounds__(256) void k_scene_tex(const uint4* __restrict__ row
         // gswt_upload_scene's loop over the texture records
         for (int k = 0; k < 3; k++) {
             const float p = __uint_as_float(t[k]);
-            if (!(p == p) || p > 3e38f || p < -3e38f) { odd = 1; continue; }
+            if (!gswt_host::finite_coord(p)) { odd = 1; continue; }
             lo[k] = min(lo[k], f2ord(p)); hi[k] = max(hi[k], f2ord(p));
         }
-        const double xx = scene_half_val(t[4] & 0xFFFFu), xy = scene_half_val(t[4] >> 16), xz = scene_half_val(t[5] & 0xFFFFu);
-        const double yy = scene_half_val(t[5] >> 16), yz = scene_half_val(t[6] & 0xFFFFu), zz = scene_half_val(t[6] >> 16);
-        const double tr_d = xx + yy + zz;
-        const bool psd = xx >= 0.0 && yy >= 0.0 && zz >= 0.0 && xx * yy - xy * xy >= 0.0 && xx * zz - xz * xz >= 0.0 &&
-                         yy * zz - yz * yz >= 0.0 && xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz) >= 0.0;
-        const double fro = sqrt(xx * xx + yy * yy + zz * zz + 2.0 * (xy * xy + xz * xz + yz * yz));
-        const float tr = psd ? (float)tr_d : (float)(0.5 * (tr_d + 1.7320508075688772 * fro) * (1.0 + 1e-6));
+        const float tr = gswt_host::cov_extent_bound(t);
         if (tr > 0.0f) tr_max = max(tr_max, __float_as_uint(tr));      // (the host's max from 0 keeps +0 for any tr <= 0)
     }
     int32_t v[8] = {lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], odd, (int32_t)tr_max};
@@ -149,8 +128,8 @@ __global__ __launch_bounds__(256) void k_scene_self(const SceneList* __restrict_
             const uint32_t j = base + (uint32_t)k * 256u + threadIdx.x;
             e[k] = j < L.pair_count ? arena[L.pair_base + j] : 0u;
             keep[k] = j < L.pair_count && (e[k] >> kLodShift) == lod;
-            const unsigned long long m = scene_ballot(keep[k]);
-            rank[k] = scene_lanes_below(m);
+            const unsigned long long m = ballot64(keep[k]);
+            rank[k] = lanes_below(m);
             if ((threadIdx.x & 63u) == 0) s_cnt[k * 4 + wave] = (uint32_t)__popcll(m);
         }
         __syncthreads();
@@ -174,7 +153,7 @@ __global__ __launch_bounds__(256) void k_scene_self(const SceneList* __restrict_
 }
 
 // One wave per chunk box.  Box b belongs to the list whose pair_box is the largest <= b; chunk k of a list of `count` entries covers
-// [count - 256 (k + 1), count - 256 k) (k_project's order).  A chunk that holds a non-finite coordinate gets the infinite box.
+// chunk_entry_range(count, k), its k-th 256 entries from the end (k_project's order).  A chunk that holds a non-finite coordinate gets the infinite box.
 __global__ __launch_bounds__(256) void k_scene_boxes(const SceneList* __restrict__ lists, uint32_t n_lists, uint32_t n_boxes,
                                                      const uint32_t* __restrict__ arena, const uint4* __restrict__ tex, uint32_t n_splats,
                                                      float* __restrict__ boxes)
@@ -188,20 +167,21 @@ __global__ __launch_bounds__(256) void k_scene_boxes(const SceneList* __restrict
     const bool pair = b - L.pair_box < n_pair_boxes;
     const uint32_t base = pair ? L.pair_base : L.self_base, count = pair ? L.pair_count : L.self_count;
     const uint32_t k = pair ? b - L.pair_box : b - L.self_box;
-    const uint32_t hi_i = count - k * (uint32_t)kChunk, lo_i = hi_i > (uint32_t)kChunk ? hi_i - (uint32_t)kChunk : 0u;
+    uint32_t lo_i, hi_i;
+    chunk_entry_range(count, k, lo_i, hi_i);
     float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
     bool odd = false;
     for (uint32_t j = lo_i + lane; j < hi_i; j += 64u) {
         const uint4 r = tex[2 * (size_t)min(arena[base + j] & kIdxMask, n_splats - 1u)];
         const float p[3] = {__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z)};
         for (int a = 0; a < 3; a++) {
-            if (!(p[a] == p[a]) || p[a] > 3e38f || p[a] < -3e38f) odd = true;
+            if (!gswt_host::finite_coord(p[a])) odd = true;
             lo[a] = fminf(lo[a], p[a]); hi[a] = fmaxf(hi[a], p[a]);
         }
     }
     for (int off = 32; off > 0; off >>= 1)
         for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], __shfl_down(lo[a], off, 64)); hi[a] = fmaxf(hi[a], __shfl_down(hi[a], off, 64)); }
-    odd = scene_ballot(odd) != 0ull;
+    odd = ballot64(odd) != 0ull;
     if (lane == 0) {
         float* o = boxes + 6 * (size_t)b;
         for (int a = 0; a < 3; a++) { o[a] = odd ? -__builtin_inff() : lo[a]; o[3 + a] = odd ? __builtin_inff() : hi[a]; }

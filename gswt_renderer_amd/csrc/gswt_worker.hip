@@ -10,8 +10,8 @@
 // data-parallel part around them (edge numbering, adjacency lists, group finalisation) spread over the workgroup.
 //
 // Float discipline: the vector / matrix helpers and surface_mapping are the SAME sources libgswt_host compiles
-// (host/gswt_math.h, host/gswt_surface.h under GSWT_HD), built with -ffp-contract=off: one rounding per operator, IEEE
-// division and square root (hipcc's default for fp32), so every stage is bit-identical to gswt_wang_sort_tiles.
+// (host/gswt_math.h, host/gswt_surface.h under GSWT_HD, which gswt_device_fn.h sets), built with -ffp-contract=off: one rounding
+// per operator, IEEE division and square root (hipcc's default for fp32), so every stage is bit-identical to gswt_wang_sort_tiles.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -20,10 +20,8 @@
 #include <new>
 #include <string>
 
+#include "gswt_device_fn.h"      // (first: it makes host/gswt_math.h and host/gswt_surface.h __host__ __device__)
 #include "gswt_ctx.h"
-#define GSWT_HD __host__ __device__
-#include "host/gswt_math.h"
-#include "host/gswt_surface.h"
 
 using namespace gswt_host;
 

@@ -1,8 +1,8 @@
 // gswt_math.h -- f32 vector / matrix helpers with cgmath 0.18's operand order.
 // One rounding per operator (build with -ffp-contract=off); column-major matrices.
 #pragma once
-// GSWT_HD: empty for g++ (libgswt_host); gswt_worker.hip defines it as __host__ __device__ so the device-side worker stages
-// run the very same operator sequences.
+// GSWT_HD: empty for g++ (libgswt_host) and for the host-only files of libgswt_hip; gswt_device_fn.h defines it as __host__ __device__ for
+// the kernel files, so the device runs the very same operator sequences.
 #ifndef GSWT_HD
 #define GSWT_HD
 #endif
@@ -98,7 +98,8 @@ GSWT_HD inline M3 mat3_from_quat(Quat q)            // cgmath From<Quaternion> f
     return r;
 }
 
-// Matrix4 * Matrix4 and Matrix4 * (x, y, z, w), flat column-major [4*c + r]
+// cgmath Matrix4 * Matrix4 (camera.rs:86-88: out[c][r] = sum_k a[k][r] * b[c][k], left to right) and Matrix4 * (x, y, z, w),
+// flat column-major [4*c + r]
 GSWT_HD inline void mat4_mul(const float* a, const float* b, float* out)
 {
     for (int c = 0; c < 4; c++)
@@ -187,6 +188,34 @@ GSWT_HD inline uint32_t float_to_half(float value)
 }
 
 GSWT_HD inline uint32_t pack_half_2x16(float x, float y) { return float_to_half(x) | (float_to_half(y) << 16); }
+
+// halfToFloat of the shader (gswt.wgsl:478-494), its arithmetic: normals as IEEE, subnormals fr * 2^-25 (half of IEEE's), Inf / NaN read
+// as 0.  THE definition: the kernels' half_decode (gswt_device_fn.h) is a faster form that equals it on all 65536 bit patterns.
+GSWT_HD inline float half_to_float(uint32_t h)
+{
+    const uint32_t e = (h >> 10) & 0x1Fu, fr = h & 0x3FFu;
+    if (e == 31u) return 0.0f;
+    const float m = e == 0u ? (float)fr * 2.98023223876953125e-08f : std::ldexp(1.0f + (float)fr / 1024.0f, (int)e - 15);
+    return (h & 0x8000u) ? -m : m;
+}
+
+// A coordinate the scene's bounds can hold: not NaN and within +-3e38 (an Inf, or a value about to overflow, makes its box infinite)
+GSWT_HD inline bool finite_coord(float p) { return !(!(p == p) || p > 3e38f || p < -3e38f); }
+
+// Bound of one texture record's (t: its eight words) projected extent, for the band cull: the sum of the decoded covariance's POSITIVE
+// eigenvalues is at most the trace when the decoded matrix is positive semi-definite, otherwise at most (trace + sqrt(3) |S|_F) / 2
+// (nuclear norm <= sqrt(3) Frobenius norm).  The decode makes stored covariances indefinite: an overflowed (Inf) diagonal reads as 0
+// beside finite off-diagonals (lambda_1 up to several times the trace), a raw row may hold a negative diagonal.
+GSWT_HD inline float cov_extent_bound(const uint32_t* t)
+{
+    const double xx = half_to_float(t[4] & 0xFFFFu), xy = half_to_float(t[4] >> 16), xz = half_to_float(t[5] & 0xFFFFu);
+    const double yy = half_to_float(t[5] >> 16), yz = half_to_float(t[6] & 0xFFFFu), zz = half_to_float(t[6] >> 16);
+    const double tr_d = xx + yy + zz;
+    const bool psd = xx >= 0.0 && yy >= 0.0 && zz >= 0.0 && xx * yy - xy * xy >= 0.0 && xx * zz - xz * xz >= 0.0 &&
+                     yy * zz - yz * yz >= 0.0 && xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz) >= 0.0;
+    const double fro = std::sqrt(xx * xx + yy * yy + zz * zz + 2.0 * (xy * xy + xz * xz + yz * yz));
+    return psd ? (float)tr_d : (float)(0.5 * (tr_d + 1.7320508075688772 * fro) * (1.0 + 1e-6));
+}
 
 // One splat of Scene::generate_texture, scene.rs:306-411: 32-byte row -> 8 u32 texture words
 GSWT_HD inline void generate_texture_row(const uint8_t* row, uint32_t* t)

@@ -1,6 +1,7 @@
 // gswt_surface.h -- WangTile::surface_mapping (wangtile.rs:1352-1494) and its helpers (height-map fetch :1220-1349, the
-// sphere unfolding :1410-1461), shared by libgswt_host (g++) and the device-side worker stages of libgswt_hip (hipcc, GSWT_HD =
-// __host__ __device__): one source, one operator sequence, so tile centres, corners and LOD distances agree bit for bit.
+// sphere unfolding :1410-1461), shared by libgswt_host (g++) and the kernels of libgswt_hip (hipcc, GSWT_HD = __host__ __device__:
+// the worker stages run surface_mapping, k_project and k_cull the sphere unfolding): one source, one operator sequence, so tile
+// centres, corners, LOD distances and the splats' sphere mapping agree bit for bit.
 #pragma once
 #include "gswt_math.h"
 
@@ -50,9 +51,10 @@ GSWT_HD inline void map_fetch_bilinear_aux(const SurfaceParams& w, float u, floa
     res[4] = bil(tx, ty - dy);
 }
 
-// Canonical sin / cos: Rust's f32::sin / cos are platform libm calls, so their last bits are
-// unpinnable; the host uses the one sequence the device kernels use (k = rint(x 2/pi), three-term Cody-Waite with
-// fmaf, Cephes minimax polynomials), so tile centres / corners agree with the GPU's sphere mapping.
+// Canonical sin / cos (the CPU checker restates it): WGSL leaves sin() / cos() accuracy to the implementation
+// and Rust's f32::sin / cos are platform libm calls, so their last bits are unpinnable; host and kernels run this one sequence
+// (k = rint(x 2/pi), three-term Cody-Waite with fmaf, Cephes minimax polynomials), so tile centres / corners agree with the GPU's
+// sphere mapping and CPU oracle == GPU bit for bit.
 GSWT_HD inline void csincosf(float x, float& sn, float& cs)
 {
     const float kf = std::rint(x * 0.636619772367581343f);
@@ -73,7 +75,7 @@ GSWT_HD inline void csincosf(float x, float& sn, float& cs)
     sn = so; cs = co;
 }
 
-// get_uv + uv_to_pos closures of surface_mapping, wangtile.rs:1410-1461
+// get_uv + uv_to_pos closures of surface_mapping, wangtile.rs:1410-1461 = sphere_get_uv + sphere_uv_to_pos, gswt.wgsl:515-564
 GSWT_HD inline V3 sphere_point(float block_w, float bidx, float bidy, float bx, float by)
 {
     const float PI = 3.14159265358979323846f;
@@ -105,6 +107,11 @@ GSWT_HD inline V3 sphere_point(float block_w, float bidx, float bidy, float bx, 
     csincosf(v, sv, cv);
     return V3{cv * cu, cv * su, sv};
 }
+
+// The shader's height-map coordinates (gswt.wgsl:565-599; k_proxy's grid and the band cull's slope bound use the same): the world
+// range the map spans along one axis, (2 map_half + 1) tiles scaled, and a world coordinate's place in it.  One rounding per operator.
+GSWT_HD inline float hm_axis_range(uint32_t map_half, float tile_width, float scale) { return (2.0f * (float)map_half + 1.0f) * tile_width * scale; }
+GSWT_HD inline float hm_axis_coord(float p, uint32_t map_half, float tile_width, float range) { return (p + (float)map_half * tile_width) / range; }
 
 // ---- WangTile::surface_mapping, wangtile.rs:1352-1494 --------------------------------------
 GSWT_HD inline void surface_mapping(const SurfaceParams& w, int mcx, int mcy, V3 pos, bool to_world, V3& new_pos, M3& transform)

@@ -15,6 +15,10 @@ from tests import proxy_raster_ref as R
 
 DEPTH_TOL = 1e-6
 DEPTH_FACTOR = 2.0
+# Every scene with the 16 x 16 height map and with a 12 x 12 one: the repeat sampler wraps a power-of-two map with an AND and any
+# other size with a quotient and two fix-ups, and k_proxy shares that sampler with the splats.  (The 16 x 16 cases keep their ids.)
+HM_SIZES = (16, 12)
+MAP_CASES = [pytest.param(name, n, id=name if n == 16 else f"{name}-hm{n}") for n in HM_SIZES for name in sorted(R.SCENES)]
 
 
 def _oracle(us, W, H, grid_dim, hm, mips):
@@ -24,12 +28,12 @@ def _oracle(us, W, H, grid_dim, hm, mips):
     return depth, rgba
 
 
-def run_scene(name, draw_fn):
+def run_scene(name, draw_fn, hm=None):
     cam_kw, draws, grid_dim, opt = R.SCENES[name]
     W, H = R.W0, R.H0
     cam = R.scene_camera(cam_kw, W, H)
     us = R.scene_uniforms(cam, draws)
-    hm, mips = R.height_map(), R.mip_chain()
+    hm, mips = R.height_map() if hm is None else hm, R.mip_chain()
     got_d, got_c = draw_fn(us, W, H, grid_dim, hm, mips)
     eps = opt.get("eps_edge", 1e-4)
     ref_d, ref_c, amb, res, ctol = R.reference(us, W, H, grid_dim=grid_dim, hm=hm, mips=mips, eps_edge=eps)
@@ -45,9 +49,9 @@ def run_scene(name, draw_fn):
     return derr, emu
 
 
-@pytest.mark.parametrize("name", sorted(R.SCENES))
-def test_oracle_matches_rasterised_mesh(name):
-    run_scene(name, _oracle)
+@pytest.mark.parametrize("name,hm_n", MAP_CASES)
+def test_oracle_matches_rasterised_mesh(name, hm_n):
+    run_scene(name, _oracle, R.height_map(n=hm_n))
 
 
 def test_oracle_matches_rasterised_mesh_reference_scale():

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from tests import proxy_raster_ref as R
-from tests.test_proxy_raster_cpu import DEPTH_TOL, run_scene
+from tests.test_proxy_raster_cpu import DEPTH_TOL, MAP_CASES, run_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +25,10 @@ def _kernel(renderer):
     return draw
 
 
-@pytest.mark.parametrize("name", sorted(R.SCENES))
-def test_kernel_matches_rasterised_mesh(renderer, name):
+@pytest.mark.parametrize("name,hm_n", MAP_CASES)
+def test_kernel_matches_rasterised_mesh(renderer, name, hm_n):
     try:
-        run_scene(name, _kernel(renderer))
+        run_scene(name, _kernel(renderer), R.height_map(n=hm_n))
     finally:
         renderer.configure(None)
 

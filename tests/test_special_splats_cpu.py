@@ -121,7 +121,8 @@ def test_every_half_pattern_decodes_as_the_shader():
 
 
 def band_half_val(h):
-    """Python restatement of half_val in gswt_upload_scene (gswt_api_scene.hip), in float32 like the C++."""
+    """Python restatement of half_to_float (host/gswt_math.h: the decode of gswt_upload_scene's and k_scene_tex's band-cull bound), in
+    float32 like the C++."""
     h = int(h)
     e, fr = (h >> 10) & 0x1F, h & 0x3FF
     if e == 31:
@@ -138,8 +139,8 @@ def test_band_cull_half_val_never_below_the_shader():
 
 
 def band_cov_bound(halves6):
-    """Python restatement of the per-record bound of gswt_upload_scene: the sum of the positive eigenvalues of the decoded
-    covariance, bounded from above -- the trace when the decoded matrix is positive semi-definite (every principal minor >= 0),
+    """Python restatement of the per-record bound of gswt_upload_scene (cov_extent_bound, host/gswt_math.h): the sum of the positive
+    eigenvalues of the decoded covariance, bounded from above -- the trace when the decoded matrix is positive semi-definite (every principal minor >= 0),
     otherwise (trace + sqrt(3) |S|_F) / 2 (the nuclear norm is at most sqrt(3) times the Frobenius norm)."""
     xx, xy, xz, yy, yz, zz = [float(band_half_val(h)) for h in halves6]
     tr = xx + yy + zz
