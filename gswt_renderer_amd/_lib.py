@@ -187,6 +187,7 @@ SYMBOLS = {
     "gswt_last_error": (C.c_char_p, [_P]),
     "gswt_set_stream": (C.c_int, [_P, _P]),
     "gswt_set_option": (C.c_int, [_P, C.c_int, C.c_int]),
+    "gswt_set_atmosphere": (C.c_int, [_P, _P]),
     "gswt_upload_scene": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int]),
     "gswt_configure": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "gswt_set_draws": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_size_t]),

@@ -195,6 +195,35 @@ try {
     }
 } GSWT_CATCH
 
+int gswt_set_atmosphere(gswt_ctx* c, const gswt_atmosphere* a)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!a) { c->atm = gswt_atmosphere{}; return GSWT_OK; }
+    const float inf = std::numeric_limits<float>::infinity();
+    const struct { const char* name; float v; } fields[] = {
+        {"fade_start", a->fade_start}, {"fade_end", a->fade_end}, {"fog_density", a->fog_density}, {"fog_start", a->fog_start},
+        {"fog_max", a->fog_max}, {"fog_color[0]", a->fog_color[0]}, {"fog_color[1]", a->fog_color[1]}, {"fog_color[2]", a->fog_color[2]}};
+    for (const auto& fd : fields)
+        if (!(std::fabs(fd.v) < inf)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_atmosphere: %s = %g is not finite", fd.name, fd.v);
+    if (a->fade_start != 0.0f || a->fade_end != 0.0f) {
+        if (!(a->fade_start >= 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_atmosphere: fade_start = %g, not >= 0", a->fade_start);
+        if (!(a->fade_end > a->fade_start))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_atmosphere: fade_end = %g, not above fade_start = %g", a->fade_end, a->fade_start);
+        const float inv = 1.0f / (a->fade_end - a->fade_start);
+        if (!(std::fabs(inv) < inf))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_atmosphere: fade_end - fade_start = %g is too small: 1 / it is not finite", a->fade_end - a->fade_start);
+    }
+    if (!(a->fog_density >= 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_atmosphere: fog_density = %g, not 0 (off) or > 0", a->fog_density);
+    if (!(a->fog_start >= 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_atmosphere: fog_start = %g, not >= 0", a->fog_start);
+    if (a->fog_density > 0.0f && !(a->fog_max > 0.0f && a->fog_max <= 1.0f))
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_atmosphere: fog_max = %g, not in (0, 1]", a->fog_max);
+    for (int k = 0; k < 3; k++)
+        if (!(a->fog_color[k] >= 0.0f && a->fog_color[k] <= 1.0f))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_atmosphere: fog_color[%d] = %g, not in [0, 1]", k, a->fog_color[k]);
+    c->atm = *a;
+    return GSWT_OK;
+} GSWT_CATCH
+
 int gswt_configure(gswt_ctx* c, const float* height_map, int hm_w, int hm_h)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;
@@ -287,6 +316,9 @@ static int validate_frame(gswt_ctx* c, const gswt_camera_uniforms* cam, const gs
             return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_ANTIALIAS = %d with splat_scale %g gives s = 4 v / splat_scale^2 = %g, not a finite positive number",
                         c->opt.antialias, su->splat_scale, s);
     }
+    // a frame with the far fade or the fog on (gswt_set_atmosphere): only the strict vertex stage has an atmospheric form
+    if ((c->atm.fade_end > 0.0f || c->atm.fog_density > 0.0f) && !c->opt.strict_vs)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: gswt_set_atmosphere's fade or fog needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no atmospheric form)");
     return GSWT_OK;
 }
 
@@ -405,6 +437,7 @@ static Frame make_frame(const gswt_ctx& c, const FrameArgs& a, const ShardGeom& 
     f.map_wh_y_magic = f.map_wh_y >= 2u && f.map_wh_y < 65536u ? 0xFFFFFFFFu / f.map_wh_y + 1u : 0u;
     f.tiles_x_magic = f.tiles_x > 0 && f.tiles_x < 65536 ? 0xFFFFFFFFu / (uint32_t)f.tiles_x + 1u : 0u;
     f.aa_s = a.aa_s;
+    f.atm = a.atm;
     return f;
 }
 
@@ -686,6 +719,7 @@ static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* 
     a.ortho = c->opt.projection == 1;
     // (validate_frame refused a splat_scale with which s is not a finite positive number)
     a.aa_s = c->opt.antialias > 0 ? antialias_s(c->opt.antialias, su->splat_scale) : 0.0f;
+    a.atm = atmo_constants(c->atm);
     return enqueue_frame(c, sl);
 }
 

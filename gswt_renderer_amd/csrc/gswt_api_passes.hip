@@ -213,6 +213,7 @@ try {
     a.hm_w = c->hm_w; a.hm_h = c->hm_h; a.tex_size = c->proxy_size > 0 ? c->proxy_size : 1; a.n_mips = c->proxy_mips > 0 ? c->proxy_mips : 1;
     memcpy(a.mip_off, c->proxy_mip_off, sizeof(a.mip_off));
     a.width = width; a.height = height;
+    a.atm = atmo_constants(c->atm);           // the block in force now: the fog part (the fade does not apply: the proxy is what the splats fade into)
     if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
     launch_proxy(c->stream, a, c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
     HIP_TRY(c, hipGetLastError());

@@ -175,6 +175,7 @@ struct FrameArgs {
     bool strict_vs = false;                // GSWT_OPT_STRICT_VS as it stood when the frame was submitted (a re-run keeps it)
     bool ortho = false;                    // GSWT_OPT_PROJECTION likewise: k_project<.,.,true,ORTHO> (frames in flight and re-runs keep their own)
     float aa_s = 0.0f;                     // GSWT_OPT_ANTIALIAS as it stood when the frame was submitted: s = 4 v / splat_scale^2 (a re-run keeps it)
+    Atmo atm = {};                         // gswt_set_atmosphere's block likewise, with its derived constants (all zero: off)
 };
 
 // A frame's events on its slot's stream.  GSWT_OPT_TIMING >= 1 records kEvStart, kEvEnd and the compositor kernel's pair, 2 also the
@@ -238,8 +239,8 @@ struct FrameSlot {
     }
 };
 
-// gswt_set_option's values with their defaults.  strict_vs, projection and antialias are snapshotted into FrameArgs when a frame is
-// submitted; every other one is read when the frame (or the sort event) is enqueued.
+// gswt_set_option's values with their defaults.  strict_vs, projection and antialias (and gswt_set_atmosphere's block, gswt_ctx::atm) are
+// snapshotted into FrameArgs when a frame is submitted; every other one is read when the frame (or the sort event) is enqueued.
 struct Options {
     int no_prefilter = 0;                  // GSWT_OPT_NO_LOD_PREFILTER
     int debug_varyings = 0;
@@ -284,6 +285,8 @@ struct gswt_ctx {
     bool own_stream = true;
     std::string err;
     gswt::Options opt;
+    // gswt_set_atmosphere: the block in force, validated (all zero: off).  Read when a frame is submitted and when gswt_proxy_render is called.
+    gswt_atmosphere atm = {};
     // scene
     gswt::DevBuf<uint4> tex;
     size_t n_splats = 0;
@@ -414,6 +417,19 @@ inline void activate_pending(gswt_ctx* c, bool force)
     if (!now && c->opt.defer_swap >= 2) now = c->pending_frames-- <= 0;                       // a fixed number of frames later: the same on every rank
     else if (!now) now = !P.ev_up || hipEventQuery(P.ev_up) == hipSuccess;                    // as soon as it has been built
     if (now) { c->cur_set = c->pending_set; c->pending_set = -1; }
+}
+
+// gswt_set_atmosphere's block as the kernels read it: the derived constants in binary32, one operation per operator (include/gswt_hip.h).
+// A part that is off leaves its fields zero.
+inline Atmo atmo_constants(const gswt_atmosphere& a)
+{
+    Atmo m = {};
+    if (a.fade_end > 0.0f) { m.fade_end = a.fade_end; m.fade_inv = 1.0f / (a.fade_end - a.fade_start); }
+    if (a.fog_density > 0.0f) {
+        m.fog_density = a.fog_density; m.fog_start = a.fog_start; m.fog_max = a.fog_max;
+        for (int k = 0; k < 3; k++) m.fog_color[k] = a.fog_color[k];
+    }
+    return m;
 }
 
 // opengl_to_wgpu * projection (gswt.wgsl:152-160, proxy.wgsl:84-91): clip z = (z + w) / 2, the other rows as they are

@@ -65,6 +65,14 @@ struct DrawDev {
     uint32_t _pad;
 };
 
+// gswt_set_atmosphere's block as the kernels read it (include/gswt_hip.h): the host derives it once per frame / proxy pass in binary32.
+// All zero: off.  fade_end > 0: the far fade is on; fog_density > 0: the distance fog is on.
+struct Atmo {
+    float fade_end, fade_inv;              // fade_inv = 1.0f / (fade_end - fade_start)
+    float fog_density, fog_start, fog_max;
+    float fog_color[3];
+};
+
 // Per-frame constants (kernel argument, by value).
 struct Frame {
     float V[16];       // view
@@ -102,6 +110,7 @@ struct Frame {
     uint32_t tiles_x_magic;                // floor(2^32 / tiles_x) + 1: tile -> (column, row) by multiply-high for tile ids below 2^16 (tile_xy)
     uint32_t map_wh_y, map_wh_y_magic;     // height of the tile map in cells (gswt.wgsl:53-56) and floor(2^32 / it) + 1 (quotients of 16-bit map ids by multiply-high)
     float aa_s;                            // GSWT_OPT_ANTIALIAS: s = 4 v / splat_scale^2, what the pixel filter adds to cov2d's diagonal (0: off)
+    Atmo atm;                              // gswt_set_atmosphere as it stood when the frame was submitted (k_project<.., ATM> only)
 };
 
 // Projected splat record consumed by the compositor (32 B, two 16-B words; one 32-B-aligned sector per gather).
@@ -208,6 +217,7 @@ struct ProxyArgs {
     int hm_w, hm_h, tex_size, n_mips;
     uint32_t mip_off[16];          // float4 offsets of the mip levels
     int width, height;
+    Atmo atm;                      // gswt_set_atmosphere as it stands when the pass is called: k_proxy<FOG> reads the fog part
 };
 
 // ---- hipGraph replay of a frame's launch sequence (GSWT_OPT_GRAPH) -------------------------------------------------------------
@@ -347,6 +357,7 @@ void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks
 // (keys -> `keys`, slots -> b.vals_a; depth-ordered frames also the depth bits -> dkeys and, with krange, the frame's key range; n_launch 0:
 // over every chunk instead of the live table), k_items + the compositor over the sorted slots `vals`.
 void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_cull);
+// (the atmosphere is on when f.atm.fade_end > 0 or f.atm.fog_density > 0: strict frames only, gswt_api.hip refuses the others)
 void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict, bool ortho);
 void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
 // b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer, the video formats

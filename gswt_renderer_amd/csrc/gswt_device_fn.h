@@ -26,6 +26,15 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long m)
 
 __device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }
 __device__ __forceinline__ float clampf(float e, float lo, float hi) { return fminf(fmaxf(e, lo), hi); }
+// gswt_set_atmosphere's fog amount F(dist) (include/gswt_hip.h), shared by k_project<.., ATM> and k_proxy<FOG>: every written operator one
+// binary32 operation, e = __expf(-x) (the hardware exp2 of x * log2(e): within 2 ulp of exp(-x) where it matters, x e^-x <= 0.37).
+// A NaN dist gives F = 0 (fmaxf drops it); an infinite x gives F = fog_max.
+__device__ __forceinline__ float fog_amount(const Atmo& a, float dist)
+{
+    const float x = a.fog_density * fmaxf(dist - a.fog_start, 0.0f);
+    const float e = __expf(-x);
+    return a.fog_max * (1.0f - e);
+}
 
 // halfToFloat, gswt.wgsl:478-494: normals as IEEE; subnormals scale 2^-15 (f * 2^-25);
 // Inf/NaN -> 0.  The definition is gswt_host::half_to_float (host/gswt_math.h, the shader's arithmetic): this is the hot path's form of

@@ -466,7 +466,10 @@ __device__ unsigned long long g_trace[kTraceItems * 8];
 // LOD blend against cam_pos, the 1.2 w frustum test with w = 1, eigen-decomposition, colour, A10) is the same code.
 // AA (GSWT_OPT_ANTIALIAS > 0, STRICT only): the screen-space pixel filter, f.aa_s on both eigenvalues of cov2d and the opacity compensation
 // (include/gswt_hip.h).  A template parameter, not a branch on f.aa_s: the branch cost k_project 0.5 us at c3 with the filter off.
-template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO, bool AA>
+// ATM (gswt_set_atmosphere with either part on, STRICT only): the per-splat far fade and distance fog of include/gswt_hip.h, both functions of
+// A5's camera distance.  A template parameter like AA, so that a frame with the block off launches the instantiation it always did; which
+// of the two parts is on is a uniform branch on f.atm inside the ATM instantiations only.
+template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO, bool AA, bool ATM>
 __global__ __launch_bounds__(256) void k_project(
     const Frame f, const DrawDev* __restrict__ draws, const uint2* __restrict__ chunk_tab,
     const uint32_t* __restrict__ static_list, const uint32_t* __restrict__ merged_list,
@@ -636,12 +639,24 @@ __global__ __launch_bounds__(256) void k_project(
                 mapped_z = n2;
             }
             if (f.use_clip == 1u && mapped_z < f.clip_height) break;
+            // gswt_set_atmosphere (no counterpart in vs_main): dist is A5's cam_dist expression, computed once here; a splat the far fade takes
+            // to t == 0 is discarded right away (not visible, no pairs), like A5's t_ratio discards.  A NaN dist clamps to t = 0 (fmaxf drops it).
+            float atm_dist = 0.0f, atm_fs = 1.0f;
+            if (ATM) {
+                const float dx = c0 - f.cam_pos[0], dy = c1 - f.cam_pos[1], dz = c2 - f.cam_pos[2];
+                atm_dist = sqrtf((dx * dx + dy * dy) + dz * dz);
+                if (f.atm.fade_end > 0.0f) {
+                    const float t = clampf((f.atm.fade_end - atm_dist) * f.atm.fade_inv, 0.0f, 1.0f);
+                    if (t == 0.0f) break;
+                    atm_fs = (t * t) * (3.0f - 2.0f * t);
+                }
+            }
             // A5 :91-150
             float t_ratio = -1.0f;
             uint32_t higher_lod = 0u;
             if (d.changing == 1u) {
                 float dx = c0 - f.cam_pos[0], dy = c1 - f.cam_pos[1], dz = c2 - f.cam_pos[2];
-                float cam_dist = sqrtf((dx * dx + dy * dy) + dz * dz);
+                float cam_dist = ATM ? atm_dist : sqrtf((dx * dx + dy * dy) + dz * dz);
                 if (d.single_draw == 1u) {
                     if (lod_id == 0u) higher_lod = 0u;
                     else if (lod_id == f.num_lod - 1u) higher_lod = lod_id - 1u;
@@ -660,6 +675,7 @@ __global__ __launch_bounds__(256) void k_project(
             }
             float majx, majy, minx, miny, cr, cg, cb, ca, ndcx, ndcy, depth;
             float q[4];
+            uint32_t col_word = w1.w;       // the record's colour word: the splat's own bytes unless the fog re-quantises them
             if (STRICT) {
                 // A6 :152-167, operator by operator
                 float cv[4];
@@ -765,6 +781,23 @@ __global__ __launch_bounds__(256) void k_project(
                     else ca = ca * (1.0f - t_ratio);
                 }
                 if (AA) ca = ca * comp;
+                if (ATM) {
+                    // far fade: behind the LOD-transition product and the pixel filter's comp (1.0f with the fade off: exact)
+                    ca = ca * atm_fs;
+                    // distance fog: the colour goes toward fog_color by F(dist) and back into the record's 8 bits, so that Rec and the compositors
+                    // stay what they are; the debug draw modes keep their float colours (col_f)
+                    if (f.atm.fog_density > 0.0f && f.draw_mode == 0u) {
+                        const float F = fog_amount(f.atm, atm_dist);
+                        const float fr = cr * (1.0f - F) + f.atm.fog_color[0] * F;
+                        const float fg = cg * (1.0f - F) + f.atm.fog_color[1] * F;
+                        const float fb = cb * (1.0f - F) + f.atm.fog_color[2] * F;
+                        const uint32_t br = (uint32_t)rintf(fminf(fmaxf(fr, 0.0f), 1.0f) * 255.0f);
+                        const uint32_t bg = (uint32_t)rintf(fminf(fmaxf(fg, 0.0f), 1.0f) * 255.0f);
+                        const uint32_t bb = (uint32_t)rintf(fminf(fmaxf(fb, 0.0f), 1.0f) * 255.0f);
+                        col_word = br | bg << 8 | bb << 16 | (w1.w & 0xFF000000u);
+                        cr = (float)br / 255.0f; cg = (float)bg / 255.0f; cb = (float)bb / 255.0f;     // what the compositor will read
+                    }
+                }
                 // A10 :415-419
                 ndcx = q[0] / q[3]; ndcy = q[1] / q[3]; depth = q[2] / q[3];
                 if (DEBUG) {
@@ -908,7 +941,7 @@ __global__ __launch_bounds__(256) void k_project(
                     Rec* dst = recs + slot;
                     reinterpret_cast<float4*>(dst)[0] = make_float4(r_iux, r_iuy, r_ivx, r_ivy);
                     // (the centre travels in NDC: the compositor takes its offset from a tile origin with one rounding, F3 of DESIGN.md section 4)
-                    reinterpret_cast<float4*>(dst)[1] = make_float4(ndcx, ndcy, ca, __uint_as_float(w1.w));
+                    reinterpret_cast<float4*>(dst)[1] = make_float4(ndcx, ndcy, ca, __uint_as_float(col_word));
                     if (depths) depths[slot] = depth;
                     if (FULL && f.draw_mode != 0u) col_f[slot] = make_float4(cr, cg, cb, 0.0f);   // debug colours are not bytes
                 }
@@ -2928,22 +2961,25 @@ void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t 
     if (b.n_chunks == 0) return;
     const uint32_t n_super = b.n_chunks / 256u + 1u;    // super_sums = [pairs x 16 n_super][visible x 16 n_super][exclusive pair prefix x n_super] (kSuperStride), zeroed by k_cull
     const bool full = f.surface_type == 2u || f.draw_mode != 0u;
-#define GSWT_LAUNCH_PROJECT_S(D, F, S, O, A)                                                                                     \
-    GSWT_LAUNCH((k_project<D, F, S, O, A>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list, \
+#define GSWT_LAUNCH_PROJECT_S(D, F, S, O, A, M)                                                                                  \
+    GSWT_LAUNCH((k_project<D, F, S, O, A, M>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list, \
                 b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums, \
                 b.super_sums, n_super, b.dbg, b.col_f)
     // (the orthographic stage exists in its strict form only: gswt_api.hip refuses an orthographic frame with GSWT_OPT_STRICT_VS = 0)
     // (nor has the pixel filter another: AA is a parameter of the STRICT instantiations only, and gswt_api.hip refuses a filtered v2 frame)
-    const bool aa = f.aa_s > 0.0f;
-#define GSWT_LAUNCH_PROJECT_A(D, F, O) do { if (aa) GSWT_LAUNCH_PROJECT_S(D, F, true, O, true); else GSWT_LAUNCH_PROJECT_S(D, F, true, O, false); } while (0)
+    // (nor has the atmosphere: ATM likewise, and a frame with gswt_set_atmosphere's block off launches the ATM = false instantiation it always did)
+    const bool aa = f.aa_s > 0.0f, atm = f.atm.fade_end > 0.0f || f.atm.fog_density > 0.0f;
+#define GSWT_LAUNCH_PROJECT_M(D, F, O, A) do { if (atm) GSWT_LAUNCH_PROJECT_S(D, F, true, O, A, true); else GSWT_LAUNCH_PROJECT_S(D, F, true, O, A, false); } while (0)
+#define GSWT_LAUNCH_PROJECT_A(D, F, O) do { if (aa) GSWT_LAUNCH_PROJECT_M(D, F, O, true); else GSWT_LAUNCH_PROJECT_M(D, F, O, false); } while (0)
 #define GSWT_LAUNCH_PROJECT(D, F) do { if (ortho) GSWT_LAUNCH_PROJECT_A(D, F, true); else if (strict) GSWT_LAUNCH_PROJECT_A(D, F, false); \
-                                       else GSWT_LAUNCH_PROJECT_S(D, F, false, false, false); } while (0)
+                                       else GSWT_LAUNCH_PROJECT_S(D, F, false, false, false, false); } while (0)
     if (debug && full) { GSWT_LAUNCH_PROJECT(true, true); }
     else if (debug) { GSWT_LAUNCH_PROJECT(true, false); }
     else if (full) { GSWT_LAUNCH_PROJECT(false, true); }
     else { GSWT_LAUNCH_PROJECT(false, false); }
 #undef GSWT_LAUNCH_PROJECT
 #undef GSWT_LAUNCH_PROJECT_A
+#undef GSWT_LAUNCH_PROJECT_M
 #undef GSWT_LAUNCH_PROJECT_S
     GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, n_super, b.counters, b.super_sums + 2u * kSuperStride * n_super, b.pair_cap, b.live_cnt, n_launch / 8u);
 }

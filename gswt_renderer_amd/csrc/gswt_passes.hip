@@ -163,6 +163,9 @@ __device__ __forceinline__ void proxy_tex_bilinear(const float4* __restrict__ lv
     out[2] = (c00.z * (1.0f - wx) + c10.z * wx) * (1.0f - wy) + (c01.z * (1.0f - wx) + c11.z * wx) * wy;
 }
 
+// FOG (gswt_set_atmosphere's fog part on when the pass is called): a pixel the proxy writes goes toward fog_color by F of the ray's hit distance
+// from the eye, behind `brightness`; the depth, the pixels left alone and the black_background output are what they are without it.
+template <bool FOG>
 __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* __restrict__ hm, const float4* __restrict__ tex,
                                                float4* __restrict__ rgba, float* __restrict__ depth_buf)
 {
@@ -246,8 +249,15 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
     float c0[3], c1[3];
     proxy_tex_bilinear(tex + a.mip_off[l0], a.tex_size >> l0, uv[0], uv[1], c0);
     proxy_tex_bilinear(tex + a.mip_off[l1], a.tex_size >> l1, uv[0], uv[1], c1);
-    rgba[pi] = make_float4((c0[0] * (1.0f - fl) + c1[0] * fl) * a.brightness, (c0[1] * (1.0f - fl) + c1[1] * fl) * a.brightness,
-                           (c0[2] * (1.0f - fl) + c1[2] * fl) * a.brightness, 1.0f);
+    float4 px = make_float4((c0[0] * (1.0f - fl) + c1[0] * fl) * a.brightness, (c0[1] * (1.0f - fl) + c1[1] * fl) * a.brightness,
+                            (c0[2] * (1.0f - fl) + c1[2] * fl) * a.brightness, 1.0f);
+    if (FOG) {
+        const float F = fog_amount(a.atm, best_t * sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]));
+        px.x = px.x * (1.0f - F) + a.atm.fog_color[0] * F;
+        px.y = px.y * (1.0f - F) + a.atm.fog_color[1] * F;
+        px.z = px.z * (1.0f - F) + a.atm.fog_color[2] * F;
+    }
+    rgba[pi] = px;
 }
 
 // ---- skybox bake -----------------------------------------------------------------------------------
@@ -537,7 +547,9 @@ void launch_fill_f32(hipStream_t s, float* p, size_t n, float v)
 
 void launch_proxy(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth)
 {
-    hipLaunchKernelGGL(k_proxy, dim3((a.width + 15) / 16, (a.height + 15) / 16), dim3(256), 0, s, a, hm, tex, rgba, depth);
+    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+    if (a.atm.fog_density > 0.0f) hipLaunchKernelGGL(k_proxy<true>, grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
+    else hipLaunchKernelGGL(k_proxy<false>, grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
 }
 
 }  // namespace gswt

@@ -303,6 +303,70 @@ enum { GSWT_OPT_NO_LOD_PREFILTER = 1, GSWT_OPT_DEBUG_VARYINGS = 2,
                                   the CPU oracle, which has no filter */ };
 GSWT_API int gswt_set_option(gswt_ctx *ctx, int key, int value);
 
+/* ---- atmosphere: per-splat far fade and distance fog --------------------------------------------
+ * The splat tiles of the unbounded terrain end at the tile cull (`culling_dist`, renderer.rs:472-494), which drops whole tile
+ * instances: full-opacity tiles appear and vanish at the far edge as the camera moves.  The reference has no remedy (vs_main has
+ * neither a fade nor a fog).  This block adds the two every terrain renderer ships, both per splat and both functions of the camera
+ * distance A5 computes for the LOD transition:
+ *   far fade : a splat's alpha ramps to zero between fade_start and fade_end, so that the splat layer dissolves into the proxy ground;
+ *   fog      : a splat's colour goes toward fog_color with distance (aerial perspective), and so does the proxy ground under it.
+ * NULL or an all-zero block: off, the default; a frame with the block off launches exactly the kernels it launches without this
+ * call and is bit for bit the same frame.  A part is on when fade_end > 0 / fog_density > 0.
+ *
+ * Validation when a block is given: every field finite; fade_start = fade_end = 0 (no fade) or 0 <= fade_start < fade_end with
+ * 1.0f / (fade_end - fade_start) finite; fog_density = 0 (no fog) or > 0; fog_start >= 0; fog_max in (0, 1] when fog_density > 0;
+ * every fog_color component in [0, 1].  Anything else returns GSWT_ERR_BAD_ARG with the field named in gswt_last_error, and the
+ * block in force stays.
+ *
+ * The block is copied into the frame when it is submitted (gswt_render*, gswt_render_async*, depth and pick forms), like
+ * GSWT_OPT_ANTIALIAS: setting it waits for nothing, frames in flight and a frame re-run after a pair-buffer overflow keep the block
+ * they were submitted with.  With either part on, a submit returns GSWT_ERR_BAD_ARG before anything is enqueued when
+ * GSWT_OPT_STRICT_VS = 0 (sequence v2 has no atmospheric form).  The host derives fade_inv = 1.0f / (fade_end - fade_start) once
+ * per frame in binary32.
+ *
+ * Vertex stage (strict sequence).  Every written operator is one correctly rounded binary32 operation, nothing fused:
+ *     d = center - cam_pos;   dist = sqrtf((dx*dx + dy*dy) + dz*dz)
+ * on the surface-mapped centre: A5's cam_dist expression, computed once, after the clip-height test, and reused by A5 when the draw
+ * is changing.  For orthographic frames cam_pos is what it already is there, the reference point of the LOD transition: a minimap
+ * fades and fogs around the main view's eye.
+ *   Fade (fade_end > 0):
+ *     t = clampf((fade_end - dist) * fade_inv, 0, 1)
+ *     t == 0 discards the splat right there: it is not visible (not in n_visible) and makes no pairs, like A5's t_ratio discards.
+ *     A NaN dist clamps to 0.  Otherwise
+ *     fs = (t * t) * (3.0f - 2.0f * t);   alpha = alpha * fs
+ *     with the product after the LOD-transition product and after the pixel filter's comp.  The smoothstep has no kink in
+ *     brightness at either end of the ramp.
+ *   Fog (fog_density > 0 and draw_mode == 0):
+ *     x = fog_density * fmaxf(dist - fog_start, 0.0f)
+ *     F = fog_max * (1.0f - e),   e = __expf(-x): the hardware exp2 of (-x) * log2(e), within 2 ulp of exp(-x) for x up to a few units
+ *         and always within 1e-7 absolute (e <= 1 and x e^-x <= 0.37)
+ *     per channel  c' = c * (1.0f - F) + fog_c * F
+ *     byte' = (uint32_t)rintf(fminf(fmaxf(c', 0), 1) * 255.0f)
+ *     and the record's colour word becomes byte'_r | byte'_g << 8 | byte'_b << 16 | (word & 0xFF000000).
+ *     Re-quantising to the record's 8-bit colour is deliberate: the projected record stays 32 bytes, the compositors are untouched and
+ *     every one of their forms stays available (early-out, depth test, depth and pick outputs, GSWT_OPT_COMPOSITE = 1).  The added
+ *     error is at most half a code per splat, uncorrelated between splats.
+ *   In the debug draw modes (draw_mode != 0) the colours stay the debug colours and only the fade applies.
+ * gswt_debug_read_projected reports what the compositor will read: rgba[k] = (float)byte' / 255.0f for the three colours and the
+ * faded alpha in rgba[3].
+ * Untouched: pair rectangles, the tile / chunk / column-band culls (their bounds only have to hold without the atmosphere, which can
+ * only remove splats), the sorts, the compositors and the pick resolve.  A chunk-level cull by fade_end is not part of this.
+ *
+ * Proxy pass.  gswt_proxy_render reads the block in force when it is called.  With the fog on, a pixel the proxy writes gets
+ *     dist = best_t * sqrtf((d0*d0 + d1*d1) + d2*d2)      the ray's hit distance from cam_pos
+ *     rgb' = rgb * (1.0f - F) + fog_color * F              the same F(dist), after `brightness`, alpha 1
+ * The depth it writes, the pixels it does not write and the black_background output are unchanged.  The fade does not apply to the
+ * proxy: it is what the splats fade into.  gswt_skybox_render is not fogged: pick fog_color near the sky's horizon colour, so that
+ * the fogged ground meets the sky without a seam. */
+typedef struct {
+    float fade_start, fade_end;   /* world units from cam_pos.  Both 0: no fade.  Otherwise 0 <= fade_start < fade_end. */
+    float fog_density;            /* per world unit.  0: no fog.  Otherwise > 0. */
+    float fog_start;              /* >= 0: fog begins at this distance */
+    float fog_max;                /* in (0, 1] when fog_density > 0: cap on the fog amount */
+    float fog_color[3];           /* each in [0, 1] */
+} gswt_atmosphere;                /* 32 bytes */
+GSWT_API int gswt_set_atmosphere(gswt_ctx *ctx, const gswt_atmosphere *a);   /* NULL or an all-zero block: off (the default) */
+
 /* GSWTRenderer::new (renderer.rs:31-349): uploads PreloadData.tile_splats_merged.tex_data
  * (8 u32 per splat, renderer.rs:236-248) and all static base lists (renderer.rs:290-327).
  * lists is [n_lod][n_tile][n_view] row-major. */
