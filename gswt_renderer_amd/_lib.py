@@ -213,6 +213,7 @@ SYMBOLS = {
     "gswt_proxy_configure_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gswt_proxy_download": (C.c_int, [_P, _P]),
     "gswt_proxy_render": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
+    "gswt_proxy_render_ortho": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
     "gswt_shard_rows": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "gswt_shard_rows_padded": (C.c_int, [C.c_int, C.c_int]),
     "gswt_unshard": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),

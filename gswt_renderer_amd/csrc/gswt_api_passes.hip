@@ -181,16 +181,9 @@ try {
     return GSWT_OK;
 } GSWT_CATCH
 
-int gswt_proxy_render(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, float* rgba_dev, float* depth_dev, int clear_depth)
-try {
-    if (!c) return GSWT_ERR_BAD_ARG;
-    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: bad argument");
-    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render before gswt_proxy_configure");
-    if (u->surface_type == 1u && (c->hm_w == 0 || c->hm_h == 0)) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render: HeightMap surface without gswt_configure height map");
-    if (!(u->tile_width > 0.0f) || (!u->map_proxy && !(u->width_scale > 0.0f))) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: cell size must be positive");
-    if (u->projection[0] == 0.0f || u->projection[5] == 0.0f) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: singular projection");
-    hipSetDevice(c->device);
-    ProxyArgs a;
+// The kernel's argument block of one proxy draw: the uniforms, the grid they select (proxy.rs:136-163 / 219-251) and the context's resources.
+static void proxy_args(const gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, ProxyArgs& a)
+{
     memset(&a, 0, sizeof(a));
     a.height_offset = u->height_offset; a.tile_width = u->tile_width; a.width_scale = u->width_scale; a.clip_height = u->clip_height;
     a.brightness = u->brightness; a.surface_type = u->surface_type; a.use_clip = u->use_clip; a.black_background = u->black_background;
@@ -214,8 +207,76 @@ try {
     memcpy(a.mip_off, c->proxy_mip_off, sizeof(a.mip_off));
     a.width = width; a.height = height;
     a.atm = atmo_constants(c->atm);           // the block in force now: the fog part (the fade does not apply: the proxy is what the splats fade into)
+}
+
+int gswt_proxy_render(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, float* rgba_dev, float* depth_dev, int clear_depth)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: bad argument");
+    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render before gswt_proxy_configure");
+    if (u->surface_type == 1u && (c->hm_w == 0 || c->hm_h == 0)) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render: HeightMap surface without gswt_configure height map");
+    if (!(u->tile_width > 0.0f) || (!u->map_proxy && !(u->width_scale > 0.0f))) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: cell size must be positive");
+    if (u->projection[0] == 0.0f || u->projection[5] == 0.0f) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: singular projection");
+    hipSetDevice(c->device);
+    ProxyArgs a;
+    proxy_args(c, u, width, height, a);
     if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
     launch_proxy(c->stream, a, c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
+    HIP_TRY(c, hipGetLastError());
+    return GSWT_OK;
+} GSWT_CATCH
+
+// The orthographic form (include/gswt_hip.h, "orthographic proxy pass"): the same block under an affine projection, k_proxy<., ORTHO>.
+int gswt_proxy_render_ortho(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, float* rgba_dev, float* depth_dev, int clear_depth)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: bad argument");
+    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_ortho before gswt_proxy_configure");
+    if (u->surface_type == 1u && (c->hm_w == 0 || c->hm_h == 0)) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_ortho: HeightMap surface without gswt_configure height map");
+    if (!(u->tile_width > 0.0f) || (!u->map_proxy && !(u->width_scale > 0.0f))) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: tile_width / width_scale: cell size must be positive");
+    const float* P = u->projection;
+    if (!(P[3] == 0.0f && P[7] == 0.0f && P[11] == 0.0f && P[15] == 1.0f))
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: projection must be affine, bottom row (0, 0, 0, 1), not (%g, %g, %g, %g)", P[3], P[7], P[11], P[15]);
+    for (int k : {1, 2, 4, 6, 8, 9})
+        if (!(P[k] == 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: projection[%d] = %g: not of ortho() form (no shear or rotation)", k, P[k]);
+    for (int k : {0, 5, 10})
+        if (!std::isfinite(P[k]) || P[k] == 0.0f) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: projection[%d] = %g: singular projection", k, P[k]);
+    for (int k : {12, 13, 14})
+        if (!std::isfinite(P[k])) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: projection[%d] = %g is not finite", k, P[k]);
+    ProxyArgs a;
+    proxy_args(c, u, width, height, a);
+    // The rays run the way depth grows (depth = GP[10] z + GP[14]: along -z of the camera for an ortho() matrix with near < far, sz = -1) and
+    // start at z0, an eighth of the depth range before the depth-0 plane.  The kernel works in the grid frame, world - g, g = (gx0, gy0, 0):
+    // ortho_o = R^-1 ((0, 0, z0) - t) - g, the view's translation becomes t + R g, cam_pos becomes cam_pos - g, and the texture coordinate the
+    // frame lacks, g / tile_width / 4, is reduced to its fraction (Repeat addressing).  Binary64, each rounded once.
+    const double g10 = a.GP[10], g14 = a.GP[14];
+    const double zn = (0.0 - g14) / g10, zf = (1.0 - g14) / g10;
+    const float sz = g10 < 0.0 ? -1.0f : 1.0f;
+    const double z0 = zn - (double)sz * 0.125 * std::fabs(zf - zn);
+    const float* V = u->view;                 // column-major: R[r][k] = V[4 k + r], t[r] = V[12 + r]
+    const double r[3][3] = {{V[0], V[4], V[8]}, {V[1], V[5], V[9]}, {V[2], V[6], V[10]}};
+    const double b[3] = {0.0 - V[12], 0.0 - V[13], z0 - V[14]};
+    const double co[3][3] = {{r[1][1] * r[2][2] - r[1][2] * r[2][1], r[1][2] * r[2][0] - r[1][0] * r[2][2], r[1][0] * r[2][1] - r[1][1] * r[2][0]},
+                             {r[0][2] * r[2][1] - r[0][1] * r[2][2], r[0][0] * r[2][2] - r[0][2] * r[2][0], r[0][1] * r[2][0] - r[0][0] * r[2][1]},
+                             {r[0][1] * r[1][2] - r[0][2] * r[1][1], r[0][2] * r[1][0] - r[0][0] * r[1][2], r[0][0] * r[1][1] - r[0][1] * r[1][0]}};
+    const double det = r[0][0] * co[0][0] + r[0][1] * co[0][1] + r[0][2] * co[0][2];
+    const double g[3] = {a.gx0, a.gy0, 0.0};
+    for (int k = 0; k < 3; k++) {             // R^-1 = cofactor^T / det
+        const double w = (co[0][k] * b[0] + co[1][k] * b[1] + co[2][k] * b[2]) / det;
+        a.ortho_o[k] = (float)(w - g[k]);
+        if (!std::isfinite(a.ortho_o[k])) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: view is singular or not finite");
+        a.V[12 + k] = (float)((double)V[12 + k] + (r[k][0] * g[0] + r[k][1] * g[1]));
+        a.cam[k] = (float)((double)u->cam_pos[k] - g[k]);
+    }
+    for (int k = 0; k < 2; k++) {
+        const double t = g[k] / (double)u->tile_width / 4.0;
+        a.ortho_uv0[k] = (float)(t - std::floor(t));
+    }
+    a.ortho_t[0] = P[12]; a.ortho_t[1] = P[13];
+    a.ortho_d[0] = sz * V[2]; a.ortho_d[1] = sz * V[6]; a.ortho_d[2] = sz * V[10];
+    hipSetDevice(c->device);
+    if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
+    launch_proxy_ortho(c->stream, a, c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
     HIP_TRY(c, hipGetLastError());
     return GSWT_OK;
 } GSWT_CATCH

@@ -218,6 +218,12 @@ struct ProxyArgs {
     uint32_t mip_off[16];          // float4 offsets of the mip levels
     int width, height;
     Atmo atm;                      // gswt_set_atmosphere as it stands when the pass is called: k_proxy<FOG> reads the fog part
+    // gswt_proxy_render_ortho only (k_proxy<., true>; zero for the perspective pass, which never reads them).  That kernel works in the
+    // GRID FRAME, world - (gx0, gy0, 0): V[12..14] and cam are given in it, so that no sum cancels at the magnitude of the world coordinates.
+    float ortho_t[2];              // projection[12], projection[13]
+    float ortho_o[3];              // grid-frame point of camera-space (0, 0, z0): the ray origin of ndc (p[12], p[13])
+    float ortho_d[3];              // the rays' direction: -(V[2], V[6], V[10]), or its negative where depth falls along the view axis
+    float ortho_uv0[2];            // frac((gx0, gy0) / tile_width / 4): what the grid frame's uv lacks, up to whole texture periods
 };
 
 // ---- hipGraph replay of a frame's launch sequence (GSWT_OPT_GRAPH) -------------------------------------------------------------
@@ -391,6 +397,7 @@ void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int
                    const float4* faces, float4* out);
 void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi, float4* faces);
 void launch_proxy(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth);
+void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth);
 // One level of the proxy mip build into dst (n x n float4).  src: the staged source, a.pitch bytes per row.  ranges: 2 n int2,
 // wv / wh: the tap weights, tmp: the intermediate, part: the partial sums (sizes: proxy_mip_* above; unused on a copy level).
 void launch_proxy_mip(hipStream_t s, const ProxyMipArgs& a, const uint8_t* src, int2* ranges, float* wv, float* wh, float4* tmp,

@@ -93,6 +93,18 @@ __device__ __forceinline__ void pixel_ray(const float* V, float p00, float p11, 
     d[2] = (V[8] * vx + V[9] * vy) + V[10] * vz;
 }
 
+// gswt_proxy_render_ortho (include/gswt_hip.h, "Ray of pixel (x, y)"): the origin of the pixel's ray, in the grid frame (world - (gx0, gy0, 0)).
+// All rays share the direction ortho_d, -(V[2], V[6], V[10]); ortho_o is the point of camera-space (0, 0, z0), inverted in binary64 by the host.
+__device__ __forceinline__ void ortho_origin(const ProxyArgs& a, int x, int y, float o[3])
+{
+    const float nx = ((float)x + 0.5f) / (float)a.width * 2.0f - 1.0f;
+    const float ny = 1.0f - ((float)y + 0.5f) / (float)a.height * 2.0f;
+    const float cx = (nx - a.ortho_t[0]) / a.p00, cy = (ny - a.ortho_t[1]) / a.p11;
+    o[0] = (a.V[0] * cx + a.V[1] * cy) + a.ortho_o[0];
+    o[1] = (a.V[4] * cx + a.V[5] * cy) + a.ortho_o[1];
+    o[2] = (a.V[8] * cx + a.V[9] * cy) + a.ortho_o[2];
+}
+
 __device__ __forceinline__ float proxy_mapped_height(const ProxyArgs& a, const float* __restrict__ hm, float rx, float ry)
 {
     if (a.surface_type != 1u) return 0.0f;
@@ -165,18 +177,28 @@ __device__ __forceinline__ void proxy_tex_bilinear(const float4* __restrict__ lv
 
 // FOG (gswt_set_atmosphere's fog part on when the pass is called): a pixel the proxy writes goes toward fog_color by F of the ray's hit distance
 // from the eye, behind `brightness`; the depth, the pixels left alone and the black_background output are what they are without it.
-template <bool FOG>
+// ORTHO (gswt_proxy_render_ortho): parallel rays, one origin per pixel (ortho_origin); a.cam is the reference point the fog distance is
+// measured from, not the origin.  The grid walk, the hit and depth tests and the texturing are the same code; the rays of the right and
+// the lower pixel differ from the pixel's own by their origin instead of their direction.  Rays, vertices, a.cam and the view's translation
+// are in the grid frame, whose lattice starts at (0, 0): far from the world origin nothing here is rounded at the world coordinates'
+// magnitude but the lattice itself (rx, ry: the reference's f32 vertices).
+template <bool FOG, bool ORTHO = false>
 __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* __restrict__ hm, const float4* __restrict__ tex,
                                                float4* __restrict__ rgba, float* __restrict__ depth_buf)
 {
     const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= a.width || y >= a.height) return;
-    const float o[3] = {a.cam[0], a.cam[1], a.cam[2]};
+    float o[3] = {a.cam[0], a.cam[1], a.cam[2]};
     float d[3];
-    pixel_ray(a.V, a.p00, a.p11, x, y, a.width, a.height, d);
+    if (ORTHO) {
+        ortho_origin(a, x, y, o);
+        d[0] = a.ortho_d[0]; d[1] = a.ortho_d[1]; d[2] = a.ortho_d[2];
+    } else
+        pixel_ray(a.V, a.p00, a.p11, x, y, a.width, a.height, d);
     float best_t = 3.0e38f, dep = 1.0f, nrm[3] = {0.0f, 0.0f, 1.0f}, pa[3] = {0.0f, 0.0f, 0.0f};
     bool hit = false;
-    const float ogx = (o[0] - a.gx0) / a.cs, ogy = (o[1] - a.gy0) / a.cs;
+    const float fx0 = ORTHO ? 0.0f : a.gx0, fy0 = ORTHO ? 0.0f : a.gy0;      // the lattice's origin in the rays' frame
+    const float ogx = (o[0] - fx0) / a.cs, ogy = (o[1] - fy0) / a.cs;
     const float dgx = d[0] / a.cs, dgy = d[1] / a.cs;
     float t0 = 0.0f, t1 = 3.0e38f;
     bool ok = true;
@@ -192,14 +214,14 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
         if (a.surface_type != 1u) {
             const float tz = (a.height_offset - o[2]) / d[2];
             const float hx = o[0] + tz * d[0], hy = o[1] + tz * d[1];
-            const float cxf = (hx - a.gx0) / a.cs, cyf = (hy - a.gy0) / a.cs;
+            const float cxf = (hx - fx0) / a.cs, cyf = (hy - fy0) / a.cs;
             if (d[2] != 0.0f && tz > 0.0f && cxf >= 0.0f && cxf <= (float)a.nx && cyf >= 0.0f && cyf <= (float)a.ny &&
                 !(a.use_clip == 1u && 0.0f < a.clip_height)) {
                 const float hp[3] = {hx, hy, o[2] + tz * d[2]};
                 float dz;
                 if (proxy_depth(a, hp, dz)) {
                     hit = true; dep = dz; best_t = tz;
-                    pa[0] = a.gx0; pa[1] = a.gy0; pa[2] = a.height_offset;
+                    pa[0] = fx0; pa[1] = fy0; pa[2] = a.height_offset;
                 }
             }
         } else {
@@ -217,12 +239,13 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
                     const int vi = ci + (k & 1), vj = cj + (k >> 1);
                     const float rx = a.gx0 + (float)vi * a.cs, ry = a.gy0 + (float)vj * a.cs;
                     m[k] = proxy_mapped_height(a, hm, rx, ry);
-                    v[k][0] = rx; v[k][1] = ry; v[k][2] = a.height_offset + m[k];
+                    v[k][0] = ORTHO ? rx - a.gx0 : rx; v[k][1] = ORTHO ? ry - a.gy0 : ry; v[k][2] = a.height_offset + m[k];
                 }
                 const bool h1 = proxy_tri(a, o, d, v[0], v[1], v[2], m[0], m[1], m[2], best_t, dep, nrm, pa);
                 const bool h2 = proxy_tri(a, o, d, v[1], v[3], v[2], m[1], m[3], m[2], best_t, dep, nrm, pa);
                 hit = hit || h1 || h2;
                 if (hit) break;
+                if (ORTHO && dgx == 0.0f && dgy == 0.0f) break;   // straight down: the one cell under the pixel
                 if (tmx < tmy) { ci += sx; tmx += tdx; } else { cj += sy; tmy += tdy; }
                 if (ci < 0 || ci >= a.nx || cj < 0 || cj >= a.ny) break;
             }
@@ -234,13 +257,21 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
     if (a.black_background == 1u) { rgba[pi] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
     float uv[2], uvx[2], uvy[2], dxr[3], dyr[3];
     proxy_plane_uv(a, o, d, pa, nrm, uv);
-    pixel_ray(a.V, a.p00, a.p11, x + 1, y, a.width, a.height, dxr);
-    pixel_ray(a.V, a.p00, a.p11, x, y + 1, a.width, a.height, dyr);
-    proxy_plane_uv(a, o, dxr, pa, nrm, uvx);
-    proxy_plane_uv(a, o, dyr, pa, nrm, uvy);
+    if (ORTHO) {                                                 // (dxr, dyr: the neighbours' origins)
+        ortho_origin(a, x + 1, y, dxr);
+        ortho_origin(a, x, y + 1, dyr);
+        proxy_plane_uv(a, dxr, d, pa, nrm, uvx);
+        proxy_plane_uv(a, dyr, d, pa, nrm, uvy);
+    } else {
+        pixel_ray(a.V, a.p00, a.p11, x + 1, y, a.width, a.height, dxr);
+        pixel_ray(a.V, a.p00, a.p11, x, y + 1, a.width, a.height, dyr);
+        proxy_plane_uv(a, o, dxr, pa, nrm, uvx);
+        proxy_plane_uv(a, o, dyr, pa, nrm, uvy);
+    }
     const float sz = (float)a.tex_size;
     const float ax = (uvx[0] - uv[0]) * sz, ay = (uvx[1] - uv[1]) * sz, bx = (uvy[0] - uv[0]) * sz, by = (uvy[1] - uv[1]) * sz;
     const float rho = fmaxf(sqrtf(ax * ax + ay * ay), sqrtf(bx * bx + by * by));
+    if (ORTHO) { uv[0] = uv[0] + a.ortho_uv0[0]; uv[1] = uv[1] + a.ortho_uv0[1]; }      // grid frame -> world, modulo the texture's period
     float lod = log2f(rho);
     if (!(lod > 0.0f)) lod = 0.0f;
     if (lod > (float)(a.n_mips - 1)) lod = (float)(a.n_mips - 1);
@@ -252,7 +283,13 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
     float4 px = make_float4((c0[0] * (1.0f - fl) + c1[0] * fl) * a.brightness, (c0[1] * (1.0f - fl) + c1[1] * fl) * a.brightness,
                             (c0[2] * (1.0f - fl) + c1[2] * fl) * a.brightness, 1.0f);
     if (FOG) {
-        const float F = fog_amount(a.atm, best_t * sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]));
+        float dist;
+        if (ORTHO) {
+            const float fx = (o[0] + best_t * d[0]) - a.cam[0], fy = (o[1] + best_t * d[1]) - a.cam[1], fz = (o[2] + best_t * d[2]) - a.cam[2];
+            dist = sqrtf((fx * fx + fy * fy) + fz * fz);
+        } else
+            dist = best_t * sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        const float F = fog_amount(a.atm, dist);
         px.x = px.x * (1.0f - F) + a.atm.fog_color[0] * F;
         px.y = px.y * (1.0f - F) + a.atm.fog_color[1] * F;
         px.z = px.z * (1.0f - F) + a.atm.fog_color[2] * F;
@@ -550,6 +587,13 @@ void launch_proxy(hipStream_t s, const ProxyArgs& a, const float* hm, const floa
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
     if (a.atm.fog_density > 0.0f) hipLaunchKernelGGL(k_proxy<true>, grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
     else hipLaunchKernelGGL(k_proxy<false>, grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
+}
+
+void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth)
+{
+    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+    if (a.atm.fog_density > 0.0f) hipLaunchKernelGGL((k_proxy<true, true>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
+    else hipLaunchKernelGGL((k_proxy<false, true>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
 }
 
 }  // namespace gswt

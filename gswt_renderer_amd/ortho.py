@@ -8,8 +8,11 @@ reference point of the LOD transition only.  NDC depth is LINEAR in the distance
 depth = (d - near) / (far - near), so under a `top_down` camera the depth and pick images are height fields
 (`height_from_depth`).
 
-The matrices are evaluated in float64 and rounded to float32 once per element.  The skybox and proxy passes have no
-orthographic form: such a frame takes whatever bg_rgba / bg_depth the caller gives it.
+The matrices are evaluated in float64 and rounded to float32 once per element.  The ground under an orthographic frame is
+the proxy pass's orthographic form: ``GSWTRenderer.proxy_render(cam.proxy_uniforms(...), W, H, rgba, depth, clear, projection=1)``
+(gswt_proxy_render_ortho) writes the colour and depth images the frame then takes as bg_rgba / bg_depth, so a height field
+holds the terrain where no splat covers it and a sun-direction depth map contains the ground.  The skybox has no orthographic
+form.
 """
 from __future__ import annotations
 
@@ -95,6 +98,28 @@ class OrthoCamera:
         p = self.lod_pos.astype(F32)
         cu.cam_pos[:] = [float(p[0]), float(p[1]), float(p[2]), 0.0]
         return cu
+
+    def proxy_uniforms(self, **fields) -> L.ProxyUniforms:
+        """The 224-byte proxy block of gswt_proxy_render_ortho for this camera: its view and projection, cam_pos = lod_pos (the
+        reference point the fog distance is measured from) and the caller's remaining fields of gswt_proxy_uniforms by name --
+        scalars, and map_half_wh / center_coord / height_map_scale (3 or 4 values) as sequences.  Defaults: tile_width, width_scale,
+        brightness and height_map_scale 1, everything else 0."""
+        u = L.ProxyUniforms()
+        u.tile_width = u.width_scale = u.brightness = 1.0
+        u.height_map_scale[:] = [1.0, 1.0, 1.0, 0.0]
+        for name, value in fields.items():
+            if name in ("view", "projection", "cam_pos", "_pad0") or not hasattr(u, name):
+                raise TypeError(f"proxy_uniforms: {name!r} is not a field the caller sets")
+            if name in ("map_half_wh", "center_coord", "height_map_scale"):
+                vals = list(value)
+                getattr(u, name)[:len(vals)] = [float(v) for v in vals] if name == "height_map_scale" else [int(v) for v in vals]
+            else:
+                setattr(u, name, value)
+        u.view[:] = [float(x) for x in self.view]
+        u.projection[:] = [float(x) for x in self.projection]
+        p = self.lod_pos.astype(F32)
+        u.cam_pos[:] = [float(p[0]), float(p[1]), float(p[2]), 0.0]
+        return u
 
     def view_proj(self) -> np.ndarray:
         """projection * view, column-major float32[16], each element the left-to-right binary32 sum of its four products."""

@@ -397,11 +397,16 @@ class GSWTRenderer:
             off += s * s
         return out
 
-    def proxy_render(self, uniforms, width: int, height: int, rgba_device_ptr: int, depth_device_ptr: int, clear_depth: bool):
-        """One draw of Proxy::render (proxy.rs:366); uniforms: 224-byte proxy.wgsl Uniforms block."""
+    def proxy_render(self, uniforms, width: int, height: int, rgba_device_ptr: int, depth_device_ptr: int, clear_depth: bool,
+                     projection: int = 0):
+        """One draw of Proxy::render (proxy.rs:366); uniforms: 224-byte proxy.wgsl Uniforms block.  projection = 1: the orthographic
+        pass, gswt_proxy_render_ortho, over a block of `ortho.OrthoCamera.proxy_uniforms` (the context's GSWT_OPT_PROJECTION plays
+        no part either way)."""
+        if projection not in (0, 1):
+            raise ValueError(f"proxy_render: projection must be 0 (perspective) or 1 (orthographic), not {projection!r}")
         u = (C.c_char * 224).from_buffer_copy(bytes(uniforms))
-        self._check(self._lib.gswt_proxy_render(self._h, u, width, height, C.c_void_p(rgba_device_ptr), C.c_void_p(depth_device_ptr),
-                                                1 if clear_depth else 0))
+        fn = self._lib.gswt_proxy_render_ortho if projection == 1 else self._lib.gswt_proxy_render
+        self._check(fn(self._h, u, width, height, C.c_void_p(rgba_device_ptr), C.c_void_p(depth_device_ptr), 1 if clear_depth else 0))
 
     def shard_rows_padded(self, height: int, shard_count: int) -> int:
         return int(self._lib.gswt_shard_rows_padded(height, shard_count))

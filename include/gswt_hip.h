@@ -264,9 +264,10 @@ enum { GSWT_OPT_NO_LOD_PREFILTER = 1, GSWT_OPT_DEBUG_VARYINGS = 2,
                                    submitted with.  With the option on a submit returns GSWT_ERR_BAD_ARG before anything is enqueued for: a
                                    projection whose bottom row is not (0, 0, 0, 1); a focal component that is not finite or <= 0;
                                    GSWT_OPT_STRICT_VS = 0 (sequence v2 has no orthographic form); GSWT_SHARD_COLUMNS with shard_count > 1 (the
-                                   band cull is perspective-specific).  Any value other than 0 / 1 is refused.  gswt_skybox_render and
-                                   gswt_proxy_render remain perspective-only: an orthographic frame takes whatever bg_rgba / bg_depth the caller
-                                   gives it.  Order: the worker's tile order is by distance from the sort event's camera, so a top-down view that
+                                   band cull is perspective-specific).  Any value other than 0 / 1 is refused.  gswt_skybox_render remains
+                                   perspective-only (a straight-down map never sees the sky); the ground under an orthographic frame comes from
+                                   gswt_proxy_render_ortho, an entry point of its own that does not read this option, and the frame takes its
+                                   outputs as bg_rgba / bg_depth like any others.  Order: the worker's tile order is by distance from the sort event's camera, so a top-down view that
                                    shares the main view's draw set should use GSWT_ORDER_DEPTH, which is exact per splat; GSWT_ORDER_REFERENCE
                                    also runs and is well defined (draw rank x list position).  The CPU oracle has no orthographic mode */,
        GSWT_OPT_ANTIALIAS = 18 /* anti-aliased splats: a screen-space low-pass with opacity compensation.  `value` is the variance of an
@@ -610,6 +611,67 @@ GSWT_API int gswt_proxy_download(gswt_ctx *ctx, float *mips_rgba_host);
  * depth test Less with depth write.  clear_depth != 0 first fills depth_dev with 1.0 (the pass's LoadOp::Clear(1.0)). */
 GSWT_API int gswt_proxy_render(gswt_ctx *ctx, const gswt_proxy_uniforms *u, int width, int height, float *rgba_dev, float *depth_dev,
                                int clear_depth);
+/* ---- orthographic proxy pass: the ground under top-down maps, minimaps, height fields and sun-direction depth maps ----
+ * ONE proxy draw under an orthographic camera: the same 224-byte block, the same buffers (colour loaded, depth tested Less and
+ * written, clear_depth != 0 fills depth_dev with 1.0 first), on the ctx stream; map_proxy selects the grid as above.  It is an
+ * entry point of its own, NOT a reading of GSWT_OPT_PROJECTION: gswt_proxy_render, its validation and its launch do not depend on
+ * that option or on this call.  The fields mean what they mean in an orthographic gswt_camera_uniforms: `projection` is an affine
+ * OpenGL-convention ortho() matrix, `view` the look-at, and `cam_pos` the REFERENCE POINT, not the eye -- the pass uses it for the
+ * fog distance only.  gswt_skybox_render has no orthographic form.
+ *
+ * Returns GSWT_ERR_BAD_ARG with the reason in gswt_last_error, nothing enqueued and clear_depth not performed, for: everything
+ * gswt_proxy_render refuses (null pointers, width / height <= 0, tile_width <= 0, width_scale <= 0 with the full grid); a
+ * projection p (column-major) whose bottom row p[3], p[7], p[11], p[15] is not exactly (0, 0, 0, 1); p[1], p[2], p[4], p[6],
+ * p[8], p[9] not all zero (not of ortho() form); p[0], p[5] or p[10] zero or not finite; p[12], p[13] or p[14] not finite; a view
+ * whose upper 3x3 cannot be inverted to finite numbers.  GSWT_ERR_STATE as gswt_proxy_render: no proxy texture unless
+ * black_background (a depth-only ground -- the height-field and shadow-map use -- needs no texture), a HeightMap surface without
+ * a height map.
+ *
+ * The definition.  Every written operator is one binary32 operation, nothing fused, except the host part marked (binary64).
+ * V = view, GP = opengl_to_wgpu * projection as in the perspective pass (GP[10] = 0.5f * p[10] + 0.5f * p[11], GP[14] = 0.5f *
+ * p[14] + 0.5f * p[15]; depth = GP[10] z + GP[14] of camera-space z, q.w = 1).
+ *   The pass works in the GRID FRAME, world - g with g = (gx0, gy0, 0), (gx0, gy0) the binary32 position of lattice point (0, 0) as the
+ *   perspective pass computes it: far from the world origin (1e5: ulp 0.008) the rays, the triangles and the depth are then of the
+ *   size of the map, and nothing but the lattice itself -- the reference's binary32 vertices -- is rounded at the world coordinates'
+ *   magnitude.  A lattice vertex (rx, ry, z) of the perspective pass enters as (rx - gx0, ry - gy0, z).
+ *   Host, once per call (binary64 from the binary32 entries, each result rounded to binary32 once):
+ *     zn = (0 - GP[14]) / GP[10],  zf = (1 - GP[14]) / GP[10]            camera-space z of depth 0 and depth 1
+ *     sz = -1 if GP[10] < 0 (depth grows along -z of the camera: ortho() with near < far), else +1
+ *     z0 = zn - sz * 0.125 * |zf - zn|                                    the rays run the way depth grows and start an eighth of
+ *                                                                         the depth range before the depth-0 plane: the whole range
+ *                                                                         [0, 1] lies at ray parameter > 0, also with near < 0
+ *     e  = R^-1 ((0, 0, z0) - t) - g,  R = upper 3x3 of V, t = (V[12], V[13], V[14]), the inverse by cofactors / determinant
+ *     t' = t + R g            the view's translation in the grid frame: the depth of a hit is (V with t' for t, then GP) applied to it
+ *     c' = cam_pos - g        the fog's reference point in the grid frame
+ *     uv0 = frac(g.xy / tile_width / 4)       what the grid frame's texture coordinate lacks, whole periods dropped (Repeat)
+ *   Ray of pixel (x, y):
+ *     ndc.x = ((float)x + 0.5f) / (float)W * 2.0f - 1.0f;   ndc.y = 1.0f - ((float)y + 0.5f) / (float)H * 2.0f      (as the perspective pass)
+ *     cx = (ndc.x - p[12]) / p[0];   cy = (ndc.y - p[13]) / p[5]
+ *     o[k] = (V[4k] * cx + V[4k+1] * cy) + e[k],  k = 0, 1, 2       i.e. R^T (cx, cy, 0) + e = R^T (c - t) - g with c = (cx, cy, z0)
+ *     d = sz * (V[2], V[6], V[10])                                   the view axis -(V[2], V[6], V[10]) (its negative for a matrix
+ *                                                                    whose depth falls along it), the same for every pixel
+ *   Why the host inverts: in binary32 R^T (c - t) cancels at the magnitude of the world coordinates and adds three products rounded
+ *   there per component, different from pixel to pixel -- a lateral error of the ray that a slope turns into a depth error.  Here every
+ *   large term is a constant of the frame, folded in binary64, and the per-pixel arithmetic is at the size of the view.  R^T stands
+ *   in for R^-1 only on (cx, cy, 0), where a look-at's 2^-24 departure from orthonormal is 2^-24 of the view's extent.
+ *   The ray parameter has no meaning of its own: the pass keeps the nearest fragment whose depth lies in [0, 1].
+ *   Hit: the lattice, the two triangles per cell and their diagonal, the inclusive Moeller-Trumbore tests, the use_clip /
+ *   clip_height discard on the interpolated mapped height and the depth (V then GP applied to o + t d, q.z / q.w) are the
+ *   perspective pass's code.  The flat-surface branch cuts the plane z = height_offset directly.
+ *   Grid walk: the perspective pass's 2-D DDA from the pixel's own origin.  A ray with d.x == d.y == 0 (every pixel of a top_down
+ *   camera) tests the one cell under it and stops; a ray with one zero component walks a single row or column; at most
+ *   nx + ny + 2 cells in any case.
+ *   Texture LOD: the rays of the right and the lower pixel -- the same d from the origins of (x + 1, y) and (x, y + 1) -- are cut
+ *   with the hit triangle's plane; rho = max |delta uv| * tex_size, lod = clamp(log2 rho, 0, n_mips - 1), trilinear Repeat taps
+ *   and `brightness` as in the perspective pass.
+ *   Texture coordinate: the perspective pass's (o + t d).xy / tile_width / 4 on the hit triangle's plane, in the grid frame, + uv0
+ *   (added after the LOD differences are taken).
+ *   Fog (gswt_set_atmosphere's fog part in force when the pass is called): hit = o + t d per component, (dx, dy, dz) = hit - c',
+ *   dist = sqrtf((dx*dx + dy*dy) + dz*dz), rgb' = rgb * (1.0f - F) + fog_color * F with the F(dist) above -- the reference point the
+ *   orthographic splat stage fades and fogs around, so the ground and the splats of a minimap fog by the same distance.
+ *   The depth written, the pixels not written and the black_background output do not depend on the fog. */
+GSWT_API int gswt_proxy_render_ortho(gswt_ctx *ctx, const gswt_proxy_uniforms *u, int width, int height, float *rgba_dev, float *depth_dev,
+                                     int clear_depth);
 
 
 /* Number of pixel rows the shard (index, count) owns for a frame of `height` rows. */
