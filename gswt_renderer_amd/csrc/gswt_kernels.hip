@@ -450,6 +450,452 @@ __device__ unsigned long long g_trace[kTraceItems * 8];
 #define GSWT_TR(K, V)
 #define GSWT_NOW() 0ull
 #endif
+
+// ---- k_project's stages, in the order the kernel calls them (A1..A10: vs_main of gswt.wgsl; F1, F2: DESIGN.md section 4).  A stage that discards the
+// splat returns false and the kernel leaves; the discards are tested in vs_main's order (n_visible depends on it). ----
+// What A3..A5 and the atmosphere hand to the vertex sequences
+struct Mapped {
+    float c0, c1, c2;                       // the centre: scene space behind A3, on the surface behind A4
+    float F[9];                             // A4's surface frame (column major), the identity without a surface
+    float mapped_z;
+    float t_ratio; uint32_t higher_lod;     // A5
+    float atm_dist, atm_fs;                 // atmosphere_fade: A5's camera distance and the far fade's alpha factor
+};
+// What a vertex sequence yields
+struct VertexOut {
+    float majx, majy, minx, miny, cr, cg, cb, ca, ndcx, ndcy, depth;
+    uint32_t col_word;                      // the record's colour word: the splat's own bytes unless the fog re-quantises them
+    float fade;                             // clamp(z/w + 1, 0, 1) on rgba: identically 1 for 0 <= z/w, kept for the debug output only
+};
+
+// A3 :52-65 -- the offset of the entry's tile: the draw's own, or that of the member tile map_id of a merged group
+__device__ __forceinline__ void tile_offset(const Frame& f, const DrawDev& d, uint32_t map_id, float& ox, float& oy, float& oz)
+{
+    ox = d.off[0]; oy = d.off[1]; oz = d.off[2];
+    if (d.single_draw == 1u) {
+        uint32_t map_wh_y = 2u * f.map_half_wh[1];
+        if (f.surface_type != 2u) map_wh_y += 1u;
+        // map_id / map_wh_y with a uniform divisor: for operands below 2^16 the quotient is the high word of map_id * (floor(2^32 / d) + 1)
+        // (three instructions instead of the ~40 of a 32-bit division); larger maps take the division
+        uint32_t mq, mr;
+        if (f.map_wh_y_magic != 0u && map_id < 65536u) {
+            mq = __umulhi(map_id, f.map_wh_y_magic);
+            mr = map_id - mq * map_wh_y;
+        } else { mq = map_id / map_wh_y; mr = map_id % map_wh_y; }
+        ox = (float)((int32_t)(mq - f.map_half_wh[0]) + f.center_coord[0]) * f.tile_width;
+        oy = (float)((int32_t)(mr - f.map_half_wh[1]) + f.center_coord[1]) * f.tile_width;
+        oz = 0.0f;
+    }
+}
+
+// A4 :75-87, surface HeightMap: the centre onto the height field, F = its tangent frame there
+__device__ __forceinline__ void map_height_surface(const Frame& f, const float* hmap, Mapped& m)
+{
+    const float DELTA = 0.001f;
+    float xr = gswt_host::hm_axis_range(f.map_half_wh[0], f.tile_width, f.height_map_scale[0]);
+    float yr = gswt_host::hm_axis_range(f.map_half_wh[1], f.tile_width, f.height_map_scale[1]);
+    float h_u = gswt_host::hm_axis_coord(m.c0, f.map_half_wh[0], f.tile_width, xr);
+    float h_v = gswt_host::hm_axis_coord(m.c1, f.map_half_wh[1], f.tile_width, yr);
+    float hz = f.height_map_scale[2];
+    float nz = sample_height(hmap, f.hm_w, f.hm_h, h_u, h_v) * hz;
+    float dt = DELTA;
+    float h_r = sample_height(hmap, f.hm_w, f.hm_h, h_u + dt, h_v) * hz;
+    float h_l = sample_height(hmap, f.hm_w, f.hm_h, h_u - dt, h_v) * hz;
+    float h_up = sample_height(hmap, f.hm_w, f.hm_h, h_u, h_v + dt) * hz;
+    float h_d = sample_height(hmap, f.hm_w, f.hm_h, h_u, h_v - dt) * hz;
+    float lx[3] = {1.0f, 0.0f, (h_r - h_l) / (2.0f * dt * xr)};
+    float ly[3] = {0.0f, 1.0f, (h_up - h_d) / (2.0f * dt * yr)};
+    float cz0 = lx[1] * ly[2] - lx[2] * ly[1];
+    float cz1 = lx[2] * ly[0] - lx[0] * ly[2];
+    float cz2 = lx[0] * ly[1] - lx[1] * ly[0];
+    float len = sqrtf((cz0 * cz0 + cz1 * cz1) + cz2 * cz2);
+    float* const F = m.F;
+    F[0] = lx[0]; F[1] = lx[1]; F[2] = lx[2];
+    F[3] = ly[0]; F[4] = ly[1]; F[5] = ly[2];
+    F[6] = cz0 / len; F[7] = cz1 / len; F[8] = cz2 / len;
+    float z = m.c2;
+    m.c0 = m.c0 + F[6] * z;
+    m.c1 = m.c1 + F[7] * z;
+    m.c2 = nz + F[8] * z;
+    m.mapped_z = nz;
+}
+
+// A4, surface Sphere: surface_mapping, gswt.wgsl:600-623 (icosahedral-strip parametrisation, 5 x 2 blocks); sphere_get_uv + sphere_uv_to_pos
+// (gswt.wgsl:515-564) are gswt_host::sphere_point, the one the host's tile centres use
+__device__ __forceinline__ void map_sphere_surface(const Frame& f, const DrawDev& d, uint32_t map_id, Mapped& m)
+{
+    const float DELTA = 0.001f;
+    const float xmax = ((float)f.map_half_wh[0] * 2.0f) * f.tile_width;
+    const float ymax = ((float)f.map_half_wh[1] * 2.0f) * f.tile_width;
+    const float block_w = xmax / 5.0f;
+    const float nx = m.c0 - (float)(f.center_coord[0] - (int32_t)f.map_half_wh[0]) * f.tile_width;
+    const float ny = m.c1 - (float)(f.center_coord[1] - (int32_t)f.map_half_wh[1]) * f.tile_width;
+    float bidx = (float)(5u * d.map_coord[0] / (f.map_half_wh[0] * 2u));
+    float bidy = (float)(2u * d.map_coord[1] / (f.map_half_wh[1] * 2u));
+    if (d.single_draw == 1u) {
+        const uint32_t map_height = 2u * f.map_half_wh[1];
+        bidx = (float)(5u * (map_id / map_height) / (f.map_half_wh[0] * 2u));
+        bidy = (float)(2u * (map_id % map_height) / (f.map_half_wh[1] * 2u));
+    }
+    const float bx = nx - bidx * block_w, by = ny - bidy * block_w;
+    using gswt_host::V3;
+    using gswt_host::sphere_point;
+    const V3 lzv = sphere_point(block_w, bidx, bidy, bx, by);
+    const float R = f.sphere_radius;
+    const float dt = DELTA * ymax;
+    const V3 prv = sphere_point(block_w, bidx, bidy, bx + dt, by), plv = sphere_point(block_w, bidx, bidy, bx - dt, by);
+    const V3 puv = sphere_point(block_w, bidx, bidy, bx, by + dt), pdv = sphere_point(block_w, bidx, bidy, bx, by - dt);
+    // (by component for the loop below: the nine entries written out from the V3 fields schedule k_project<FULL> differently, and its
+    // instantiations are held to the registers and instruction counts recorded in profiles/project_stages_ab.txt; the device assembly of
+    // every other kernel of this file is kept byte for byte)
+    const float lz[3] = {lzv.x, lzv.y, lzv.z}, pr[3] = {prv.x, prv.y, prv.z}, pl[3] = {plv.x, plv.y, plv.z};
+    const float pu[3] = {puv.x, puv.y, puv.z}, pd[3] = {pdv.x, pdv.y, pdv.z};
+    float* const F = m.F;
+    for (int k = 0; k < 3; k++) {
+        F[k] = (pr[k] * R - pl[k] * R) / (2.0f * dt);
+        F[3 + k] = (pu[k] * R - pd[k] * R) / (2.0f * dt);
+        F[6 + k] = lz[k];
+    }
+    const float z = m.c2;
+    const float n0 = lz[0] * R, n1 = lz[1] * R, n2 = lz[2] * R;
+    m.c0 = n0 + F[6] * z;
+    m.c1 = n1 + F[7] * z;
+    m.c2 = n2 + F[8] * z;
+    m.mapped_z = n2;
+}
+
+// gswt_set_atmosphere (no counterpart in vs_main): dist is A5's cam_dist expression, computed once here; a splat the far fade takes
+// to t == 0 is discarded right away (not visible, no pairs), like A5's t_ratio discards.  A NaN dist clamps to t = 0 (fmaxf drops it).
+__device__ __forceinline__ bool atmosphere_fade(const Frame& f, Mapped& m)
+{
+    const float dx = m.c0 - f.cam_pos[0], dy = m.c1 - f.cam_pos[1], dz = m.c2 - f.cam_pos[2];
+    m.atm_dist = sqrtf((dx * dx + dy * dy) + dz * dz);
+    if (f.atm.fade_end > 0.0f) {
+        const float t = clampf((f.atm.fade_end - m.atm_dist) * f.atm.fade_inv, 0.0f, 1.0f);
+        if (t == 0.0f) return false;
+        m.atm_fs = (t * t) * (3.0f - 2.0f * t);
+    }
+    return true;
+}
+
+// A5 :91-150 -- a tile in transition between two LODs: which of them this splat blends against and how far the blend is; a splat whose share
+// of the blend is zero is discarded
+template <bool ATM>
+__device__ __forceinline__ bool lod_transition(const Frame& f, const DrawDev& d, uint32_t lod_id, Mapped& m)
+{
+    if (d.changing == 1u) {
+        float dx = m.c0 - f.cam_pos[0], dy = m.c1 - f.cam_pos[1], dz = m.c2 - f.cam_pos[2];
+        float cam_dist = ATM ? m.atm_dist : sqrtf((dx * dx + dy * dy) + dz * dz);
+        uint32_t higher_lod;
+        if (d.single_draw == 1u) {
+            if (lod_id == 0u) higher_lod = 0u;
+            else if (lod_id == f.num_lod - 1u) higher_lod = lod_id - 1u;
+            else {
+                float d1 = f.transition_dist[(lod_id - 1u) & 15u];
+                float d2 = f.transition_dist[lod_id & 15u];
+                higher_lod = (cam_dist - d1 < d2 - cam_dist) ? lod_id - 1u : lod_id;
+            }
+        } else {
+            higher_lod = (d.changing_to_lower == 1) ? d.tile_lod : d.tile_lod - 1u;
+        }
+        float td = f.transition_dist[higher_lod & 15u];
+        float thw = f.transition_width_ratio * td;
+        const float t_ratio = clampf((cam_dist - td) / thw + 0.5f, 0.0f, 1.0f);
+        m.t_ratio = t_ratio; m.higher_lod = higher_lod;
+        if ((lod_id == higher_lod + 1u && t_ratio == 0.0f) || (lod_id == higher_lod && t_ratio == 1.0f)) return false;
+    }
+    return true;
+}
+
+// A7 :169-205, first half, the same in both sequences: Vrk from the record's six halves, or the point cloud's isotropic one
+__device__ __forceinline__ void splat_cov3(const Frame& f, const DrawDev& d, const uint4& w1, float (&K)[9])
+{
+    {
+        float a = half_decode(w1.x & 0xFFFFu), b = half_decode(w1.x >> 16);
+        float cc = half_decode(w1.y & 0xFFFFu), dd = half_decode(w1.y >> 16);
+        float e = half_decode(w1.z & 0xFFFFu), ff = half_decode(w1.z >> 16);
+        K[0] = a; K[1] = b; K[2] = cc; K[3] = b; K[4] = dd; K[5] = e; K[6] = cc; K[7] = e; K[8] = ff;
+    }
+    if (f.point_cloud_radius > 0.0f) {
+        float pr = f.point_cloud_radius;
+        if (f.draw_mode > 0u) pr *= ldexpf(1.0f, (int)d.tile_lod);
+        K[0] = pr; K[1] = 0; K[2] = 0; K[3] = 0; K[4] = pr; K[5] = 0; K[6] = 0; K[7] = 0; K[8] = pr;
+    }
+}
+
+// A9 :268-399, 402-410 behind the byte -> float conversion, the same in both sequences: the debug draw modes' colours, and the share of a LOD
+// transition's blend in alpha
+template <bool FULL>
+__device__ __forceinline__ void lod_blend_color(const Frame& f, const DrawDev& d, const uint4& w0, uint32_t lod_id, const Mapped& m, VertexOut& v)
+{
+    if (FULL && f.draw_mode != 0u) debug_draw_color(f, d, u2f(w0.x), u2f(w0.y), lod_id, m.t_ratio, v.cr, v.cg, v.cb);   // :268-399
+    if (d.changing == 1u) {
+        if (lod_id != m.higher_lod) v.ca = v.ca * m.t_ratio;
+        else v.ca = v.ca * (1.0f - m.t_ratio);
+    }
+}
+
+// distance fog: the colour goes toward fog_color by F(dist) and back into the record's 8 bits, so that Rec and the compositors
+// stay what they are; the debug draw modes keep their float colours (col_f)
+__device__ __forceinline__ void fog_requantise(const Frame& f, float atm_dist, uint32_t rgba8, VertexOut& v)
+{
+    const float F = fog_amount(f.atm, atm_dist);
+    const float fr = v.cr * (1.0f - F) + f.atm.fog_color[0] * F;
+    const float fg = v.cg * (1.0f - F) + f.atm.fog_color[1] * F;
+    const float fb = v.cb * (1.0f - F) + f.atm.fog_color[2] * F;
+    const uint32_t br = (uint32_t)rintf(fminf(fmaxf(fr, 0.0f), 1.0f) * 255.0f);
+    const uint32_t bg = (uint32_t)rintf(fminf(fmaxf(fg, 0.0f), 1.0f) * 255.0f);
+    const uint32_t bb = (uint32_t)rintf(fminf(fmaxf(fb, 0.0f), 1.0f) * 255.0f);
+    v.col_word = br | bg << 8 | bb << 16 | (rgba8 & 0xFF000000u);
+    v.cr = (float)br / 255.0f; v.cg = (float)bg / 255.0f; v.cb = (float)bb / 255.0f;     // what the compositor will read
+}
+
+// A6..A10, STRICT: operator by operator as the shader text writes them (the comment above k_project)
+template <bool FULL, bool ORTHO, bool AA, bool ATM>
+__device__ __forceinline__ bool vertex_strict(const Frame& f, const DrawDev& d, const uint4& w0, const uint4& w1, uint32_t lod_id, const Mapped& m, VertexOut& v)
+{
+    const float c0 = m.c0, c1 = m.c1, c2 = m.c2;
+    const float* const F = m.F;
+    // A6 :152-167
+    float cv[4], q[4];
+    for (int rr = 0; rr < 4; rr++) cv[rr] = ((f.V[rr] * c0 + f.V[4 + rr] * c1) + f.V[8 + rr] * c2) + f.V[12 + rr] * 1.0f;
+    for (int rr = 0; rr < 4; rr++)
+        q[rr] = ((f.GP[rr] * cv[0] + f.GP[4 + rr] * cv[1]) + f.GP[8 + rr] * cv[2]) + f.GP[12 + rr] * cv[3];
+    const float clip = 1.2f * q[3];
+    if (q[2] < -clip || q[0] < -clip || q[0] > clip || q[1] < -clip || q[1] > clip) return false;
+    // A7 :169-205
+    float K[9];
+    splat_cov3(f, d, w1, K);
+    if (f.surface_type > 0u) {          // Vrk = transform * Vrk * transpose(transform)
+        float FK[9], R[9];
+        for (int cc = 0; cc < 3; cc++)
+            for (int rr = 0; rr < 3; rr++)
+                FK[3 * cc + rr] = (F[rr] * K[3 * cc] + F[3 + rr] * K[3 * cc + 1]) + F[6 + rr] * K[3 * cc + 2];
+        for (int cc = 0; cc < 3; cc++)
+            for (int rr = 0; rr < 3; rr++)
+                R[3 * cc + rr] = (FK[rr] * F[cc] + FK[3 + rr] * F[3 + cc]) + FK[6 + rr] * F[6 + cc];
+        for (int k = 0; k < 9; k++) K[k] = R[k];
+    }
+    {                                   // scene_scale_mat * Vrk * transpose(scene_scale_mat): the full matrix products, zeros included
+        const float S[9] = {f.scene_scale[0], 0.0f, 0.0f, 0.0f, f.scene_scale[1], 0.0f, 0.0f, 0.0f, f.scene_scale[2]};
+        float SK[9], R[9];
+        for (int cc = 0; cc < 3; cc++)
+            for (int rr = 0; rr < 3; rr++)
+                SK[3 * cc + rr] = (S[rr] * K[3 * cc] + S[3 + rr] * K[3 * cc + 1]) + S[6 + rr] * K[3 * cc + 2];
+        for (int cc = 0; cc < 3; cc++)
+            for (int rr = 0; rr < 3; rr++)
+                R[3 * cc + rr] = (SK[rr] * S[cc] + SK[3 + rr] * S[3 + cc]) + SK[6 + rr] * S[6 + cc];
+        for (int k = 0; k < 9; k++) K[k] = R[k];
+    }
+    // A8 :207-258
+    float JT[9];
+    if (ORTHO) {
+        // J_T columns of the affine projection: (fx, 0, 0), (0, fy, 0), (0, 0, 0)
+        JT[0] = f.focal[0]; JT[1] = 0.0f; JT[2] = 0.0f;
+        JT[3] = 0.0f; JT[4] = f.focal[1]; JT[5] = 0.0f;
+        JT[6] = 0.0f; JT[7] = 0.0f; JT[8] = 0.0f;
+    } else {
+        const float dd0 = c0 - f.cam_pos[0], dd1 = c1 - f.cam_pos[1], dd2 = c2 - f.cam_pos[2];
+        float t[3];
+        for (int rr = 0; rr < 3; rr++) t[rr] = (f.V[rr] * dd0 + f.V[4 + rr] * dd1) + f.V[8 + rr] * dd2;
+        const float txtz = t[0] / t[2], tytz = t[1] / t[2];
+        const float limx = 1.3f * f.htan[0], limy = 1.3f * f.htan[1];
+        t[0] = clampf(txtz, -limx, limx) * t[2];
+        t[1] = clampf(tytz, -limy, limy) * t[2];
+        const float tz2 = t[2] * t[2];
+        // J_T columns: (fx / tz, 0, -fx tx / tz^2), (0, fy / tz, -fy ty / tz^2), (0, 0, 0)
+        JT[0] = f.focal[0] / t[2]; JT[1] = 0.0f; JT[2] = (-f.focal[0] * t[0]) / tz2;
+        JT[3] = 0.0f; JT[4] = f.focal[1] / t[2]; JT[5] = (-f.focal[1] * t[1]) / tz2;
+        JT[6] = 0.0f; JT[7] = 0.0f; JT[8] = 0.0f;
+    }
+    float Tm[9];                        // T = transpose(view3) * J_T
+    for (int cc = 0; cc < 3; cc++)
+        for (int rr = 0; rr < 3; rr++)
+            Tm[3 * cc + rr] = (f.V[4 * rr + 0] * JT[3 * cc] + f.V[4 * rr + 1] * JT[3 * cc + 1]) + f.V[4 * rr + 2] * JT[3 * cc + 2];
+    float Am[9], C2[9];                 // cov2d = transpose(T) * Vrk * T
+    for (int cc = 0; cc < 3; cc++)
+        for (int rr = 0; rr < 3; rr++)
+            Am[3 * cc + rr] = (Tm[3 * rr + 0] * K[3 * cc] + Tm[3 * rr + 1] * K[3 * cc + 1]) + Tm[3 * rr + 2] * K[3 * cc + 2];
+    for (int cc = 0; cc < 3; cc++)
+        for (int rr = 0; rr < 3; rr++)
+            C2[3 * cc + rr] = (Am[rr] * Tm[3 * cc] + Am[3 + rr] * Tm[3 * cc + 1]) + Am[6 + rr] * Tm[3 * cc + 2];
+    const float c00 = C2[0], c01 = C2[1], c11 = C2[4];
+    const float mid = 0.5f * (c00 + c11);
+    const float hxx = 0.5f * (c00 - c11);
+    const float radius = sqrtf(hxx * hxx + c01 * c01);
+    const float l1 = mid + radius, l2 = mid - radius;
+    if (l2 < 0.0f) return false;
+    const float vx = c01, vy = l1 - c00;
+    const float vlen = sqrtf(vx * vx + vy * vy);
+    const float ex = vx / vlen, ey = vy / vlen;
+    // GSWT_OPT_ANTIALIAS (no counterpart in vs_main): the pixel filter adds s to both eigenvalues -- the rejection above and the
+    // direction stay those of the unfiltered cov2d -- and comp keeps the integrated opacity.  AA = false compiles what there was
+    float l1f = l1, l2f = l2, comp = 1.0f;
+    if (AA) {
+        l1f = l1 + f.aa_s; l2f = l2 + f.aa_s;
+        comp = clampf(sqrtf(l1 / l1f) * sqrtf(l2 / l2f), 0.0f, 1.0f);      // (fmaxf drops a NaN: 0)
+    }
+    const float smaj = fminf(sqrtf(2.0f * l1f), 1024.0f);
+    const float smin = fminf(sqrtf(2.0f * l2f), 1024.0f);
+    v.majx = smaj * ex; v.majy = smaj * ey;
+    v.minx = smin * ey; v.miny = smin * -ex;
+    // A9 :260-265, 402-410
+    v.cr = (float)(w1.w & 0xFFu) / 255.0f;
+    v.cg = (float)((w1.w >> 8) & 0xFFu) / 255.0f;
+    v.cb = (float)((w1.w >> 16) & 0xFFu) / 255.0f;
+    v.ca = (float)((w1.w >> 24) & 0xFFu) / 255.0f;
+    lod_blend_color<FULL>(f, d, w0, lod_id, m, v);
+    if (AA) v.ca = v.ca * comp;
+    v.col_word = w1.w;
+    if (ATM) {
+        // far fade: behind the LOD-transition product and the pixel filter's comp (1.0f with the fade off: exact)
+        v.ca = v.ca * m.atm_fs;
+        if (f.atm.fog_density > 0.0f && f.draw_mode == 0u) fog_requantise(f, m.atm_dist, w1.w, v);
+    }
+    // A10 :415-419
+    v.ndcx = q[0] / q[3]; v.ndcy = q[1] / q[3]; v.depth = q[2] / q[3];
+    v.fade = clampf(q[2] / q[3] + 1.0f, 0.0f, 1.0f);
+    return true;
+}
+
+// A6..A10, canonical sequence v2: dot products are fma chains, quotients are products with one correctly rounded
+// reciprocal; the CPU checker evaluates exactly the same operations.  No ORTHO, AA or ATM form.
+template <bool FULL>
+__device__ __forceinline__ bool vertex_v2(const Frame& f, const DrawDev& d, const uint4& w0, const uint4& w1, uint32_t lod_id, const Mapped& m, VertexOut& v)
+{
+    const float c0 = m.c0, c1 = m.c1, c2 = m.c2;
+    const float* const F = m.F;
+    // A6 :152-167
+    float cv[4], q[4];
+    for (int rr = 0; rr < 4; rr++) cv[rr] = fmaf(f.V[8 + rr], c2, fmaf(f.V[4 + rr], c1, f.V[rr] * c0)) + f.V[12 + rr];
+    for (int rr = 0; rr < 4; rr++)
+        q[rr] = fmaf(f.GP[12 + rr], cv[3], fmaf(f.GP[8 + rr], cv[2], fmaf(f.GP[4 + rr], cv[1], f.GP[rr] * cv[0])));
+    float clip = 1.2f * q[3];
+    if (q[2] < -clip || q[0] < -clip || q[0] > clip || q[1] < -clip || q[1] > clip) return false;
+    // A7 :169-205
+    float K[9];
+    splat_cov3(f, d, w1, K);
+    if (f.surface_type > 0u) {
+        float FK[9], R[9];
+        for (int cc = 0; cc < 3; cc++)
+            for (int rr = 0; rr < 3; rr++)
+                FK[3 * cc + rr] = fmaf(F[6 + rr], K[3 * cc + 2], fmaf(F[3 + rr], K[3 * cc + 1], F[rr] * K[3 * cc]));
+        for (int cc = 0; cc < 3; cc++)
+            for (int rr = 0; rr < 3; rr++)
+                R[3 * cc + rr] = fmaf(FK[6 + rr], F[6 + cc], fmaf(FK[3 + rr], F[3 + cc], FK[rr] * F[cc]));
+        for (int k = 0; k < 9; k++) K[k] = R[k];
+    }
+    // scene_scale_mat * Vrk * transpose(scene_scale_mat): a product with 1.0 is exact, so the usual unit scale skips 18 multiplications
+    // (uniform branch; same bits)
+    if (f.scene_scale[0] != 1.0f || f.scene_scale[1] != 1.0f || f.scene_scale[2] != 1.0f)
+        for (int cc = 0; cc < 3; cc++)
+            for (int rr = 0; rr < 3; rr++) K[3 * cc + rr] = (f.scene_scale[rr] * K[3 * cc + rr]) * f.scene_scale[cc];
+    // A8 :207-258
+    float d0 = c0 - f.cam_pos[0], d1 = c1 - f.cam_pos[1], d2 = c2 - f.cam_pos[2];
+    float t[3];
+    for (int rr = 0; rr < 3; rr++) t[rr] = fmaf(f.V[8 + rr], d2, fmaf(f.V[4 + rr], d1, f.V[rr] * d0));
+    const float rz = 1.0f / t[2];
+    float txtz = t[0] * rz, tytz = t[1] * rz;
+    float limx = 1.3f * f.htan[0], limy = 1.3f * f.htan[1];
+    t[0] = clampf(txtz, -limx, limx) * t[2];
+    t[1] = clampf(tytz, -limy, limy) * t[2];
+    const float rz2 = rz * rz;
+    float j00 = f.focal[0] * rz, j02 = -((f.focal[0] * t[0]) * rz2);
+    float j11 = f.focal[1] * rz, j12 = -((f.focal[1] * t[1]) * rz2);
+    float T0[3], T1[3];
+    for (int rr = 0; rr < 3; rr++) {
+        T0[rr] = fmaf(f.V[4 * rr + 2], j02, f.V[4 * rr + 0] * j00);
+        T1[rr] = fmaf(f.V[4 * rr + 2], j12, f.V[4 * rr + 1] * j11);
+    }
+    float A0[3], A1[3];
+    for (int k = 0; k < 3; k++) {
+        A0[k] = fmaf(T0[2], K[3 * k + 2], fmaf(T0[1], K[3 * k + 1], T0[0] * K[3 * k]));
+        A1[k] = fmaf(T1[2], K[3 * k + 2], fmaf(T1[1], K[3 * k + 1], T1[0] * K[3 * k]));
+    }
+    float c00 = fmaf(A0[2], T0[2], fmaf(A0[1], T0[1], A0[0] * T0[0]));
+    float c01 = fmaf(A1[2], T0[2], fmaf(A1[1], T0[1], A1[0] * T0[0]));
+    float c11 = fmaf(A1[2], T1[2], fmaf(A1[1], T1[1], A1[0] * T1[0]));
+    float mid = 0.5f * (c00 + c11);
+    float hxx = 0.5f * (c00 - c11);
+    float radius = sqrtf(fmaf(hxx, hxx, c01 * c01));
+    float l1 = mid + radius, l2 = mid - radius;
+    if (l2 < 0.0f) return false;
+    float vx = c01, vy = l1 - c00;
+    float vlen = sqrtf(fmaf(vx, vx, vy * vy));
+    const float rv = 1.0f / vlen;
+    float ex = vx * rv, ey = vy * rv;
+    float smaj = fminf(sqrtf(2.0f * l1), 1024.0f);
+    float smin = fminf(sqrtf(2.0f * l2), 1024.0f);
+    v.majx = smaj * ex; v.majy = smaj * ey;
+    v.minx = smin * ey; v.miny = smin * -ex;
+    // A9 :260-265, 402-410 (byte / 255 as byte * fl(1 / 255))
+    const float k255 = 1.0f / 255.0f;
+    v.cr = (float)(w1.w & 0xFFu) * k255;
+    v.cg = (float)((w1.w >> 8) & 0xFFu) * k255;
+    v.cb = (float)((w1.w >> 16) & 0xFFu) * k255;
+    v.ca = (float)((w1.w >> 24) & 0xFFu) * k255;
+    lod_blend_color<FULL>(f, d, w0, lod_id, m, v);
+    v.col_word = w1.w;
+    // A10 :415-419
+    const float rq = 1.0f / q[3];
+    v.ndcx = q[0] * rq; v.ndcy = q[1] * rq; v.depth = q[2] * rq;
+    v.fade = clampf(fmaf(q[2], rq, 1.0f), 0.0f, 1.0f);
+    return true;
+}
+
+// Fragment setup F1, F2: pixel-space centre and inverse affine map, the splat's rectangle of screen tiles, and its record.
+// visible: the splat survived the vertex stage (counted in n_visible); count: its (tile, splat) pairs, 0 with my_rect left empty
+template <bool FULL>
+__device__ __forceinline__ void fragment_setup(const Frame& f, const VertexOut& v, uint32_t slot, Rec* recs, float* depths, float4* col_f,
+                                               uint32_t& count, uint2& my_rect, bool& visible)
+{
+    float cxp = fmaf(0.5f, v.ndcx, 0.5f) * f.W;
+    float cyp = fmaf(-0.5f, v.ndcy, 0.5f) * f.H;
+    float hs = 0.5f * f.splat_scale;
+    float ux = hs * v.majx, uy = -(hs * v.majy);
+    float wx = hs * v.minx, wy = -(hs * v.miny);
+    float uu = fmaf(uy, uy, ux * ux);
+    float ww = fmaf(wy, wy, wx * wx);
+    if (!((uu > 0.0f) && (ww > 0.0f) && (uu < __builtin_inff()) && (ww < __builtin_inff()))) return;
+    visible = true;
+    // depth_compare Less against the 1.0 clear when no proxy depth is bound (renderer.rs:182,436): a vertex-stage survivor
+    // (counted in n_visible) that no fragment of can pass -- no pairs
+    if (!f.has_depth && !(v.depth < 1.0f)) return;
+    const float ruu = 1.0f / uu, rww = 1.0f / ww;
+    const float r_iux = ux * ruu, r_iuy = uy * ruu, r_ivx = wx * rww, r_ivy = wy * rww;
+    // half extents of |p| <= 2, inflated by 1e-5 relative + 1e-3 px (conservative under f32 rounding)
+    float hx = fmaf(2.0f * sqrtf(fmaf(wx, wx, ux * ux)), 1.00001f, 0.001f);
+    float hy = fmaf(2.0f * sqrtf(fmaf(wy, wy, uy * uy)), 1.00001f, 0.001f);
+    // pixels whose CENTRE lies inside the box: x in [ceil(c - h - 0.5), floor(c + h - 0.5)]
+    float fx0 = ceilf(cxp - hx - 0.5f), fx1 = floorf(cxp + hx - 0.5f);
+    float fy0 = ceilf(cyp - hy - 0.5f), fy1 = floorf(cyp + hy - 0.5f);
+    if (fx1 >= fx0 && fy1 >= fy0 && fx1 >= 0.0f && fy1 >= 0.0f && fx0 <= f.W - 1.0f && fy0 <= f.H - 1.0f) {
+        int x0 = fx0 < 0.0f ? 0 : (int)fx0, x1 = fx1 > f.W - 1.0f ? f.width - 1 : (int)fx1;
+        int y0 = fy0 < 0.0f ? 0 : (int)fy0, y1 = fy1 > f.H - 1.0f ? f.height - 1 : (int)fy1;
+        int tx0 = x0 >> 4, tx1 = x1 >> 4, ty0 = y0 >> 4, ty1 = y1 >> 4;
+        tx0 = max(tx0, f.col0); tx1 = min(tx1, f.col1 - 1);          // column band of this ctx (the whole frame when off)
+        int rows = owned_rows(ty0, ty1, f.shard_index, f.shard_count);
+        count = tx1 >= tx0 ? (uint32_t)((tx1 - tx0 + 1) * rows) : 0u;
+        if (count) {
+            my_rect = make_uint2((uint32_t)tx0 | ((uint32_t)tx1 << 16), (uint32_t)ty0 | ((uint32_t)ty1 << 16));
+            // 32-byte record: the inverse map, the centre, alpha and the packed colour (unpacked by the compositor's blend);
+            // the pixel half extents are re-derived from the inverse map by the compositor's staging lane, the depth
+            // goes to a side array that only depth-tested / depth-ordered frames read
+            Rec* dst = recs + slot;
+            reinterpret_cast<float4*>(dst)[0] = make_float4(r_iux, r_iuy, r_ivx, r_ivy);
+            // (the centre travels in NDC: the compositor takes its offset from a tile origin with one rounding, F3 of DESIGN.md section 4)
+            reinterpret_cast<float4*>(dst)[1] = make_float4(v.ndcx, v.ndcy, v.ca, __uint_as_float(v.col_word));
+            if (depths) depths[slot] = v.depth;
+            if (FULL && f.draw_mode != 0u) col_f[slot] = make_float4(v.cr, v.cg, v.cb, 0.0f);   // debug colours are not bytes
+        }
+    }
+}
+
+// The kernel itself keeps the loads (launch table, list word, record: A1, A2 and the trace stamps around them) and the workgroup's sums; per
+// splat it calls, in this order, the stages above: tile_offset (A3), map_height_surface / map_sphere_surface (A4), atmosphere_fade,
+// lod_transition (A5), vertex_strict<FULL, ORTHO, AA, ATM> or vertex_v2<FULL> (A6..A10; both over splat_cov3 and lod_blend_color, the
+// strict one over fog_requantise) and fragment_setup (F1, F2, tile rectangle, record).  A new per-splat feature goes into the stage it
+// belongs to; a new template flag into that stage's parameters.
 // k_project's stamps (tools/project_trace.py), rows 8192 + launch position: [0] entry, [1] launch-table entry known, [2] list word arrived (lane 0),
 // [3] record arrived (lane 0, when it gets that far), [4] wave 0 through the projection, [5] behind the workgroup barrier, [6] end,
 // [7] hardware id (HW_ID | XCC_ID << 32) | chunk has pairs << 63
@@ -547,405 +993,33 @@ __global__ __launch_bounds__(256) void k_project(
             { unsigned long long sink = w0.x + w1.w; asm volatile("" :: "v"(sink)); }
             GSWT_TR(3, GSWT_NOW())
 #endif
-            // A3 :52-65
-            float ox = d.off[0], oy = d.off[1], oz = d.off[2];
-            if (d.single_draw == 1u) {
-                const uint32_t map_id = map_id_m;
-                uint32_t map_wh_y = 2u * f.map_half_wh[1];
-                if (f.surface_type != 2u) map_wh_y += 1u;
-                // map_id / map_wh_y with a uniform divisor: for operands below 2^16 the quotient is the high word of map_id * (floor(2^32 / d) + 1)
-                // (three instructions instead of the ~40 of a 32-bit division); larger maps take the division
-                uint32_t mq, mr;
-                if (f.map_wh_y_magic != 0u && map_id < 65536u) {
-                    mq = __umulhi(map_id, f.map_wh_y_magic);
-                    mr = map_id - mq * map_wh_y;
-                } else { mq = map_id / map_wh_y; mr = map_id % map_wh_y; }
-                ox = (float)((int32_t)(mq - f.map_half_wh[0]) + f.center_coord[0]) * f.tile_width;
-                oy = (float)((int32_t)(mr - f.map_half_wh[1]) + f.center_coord[1]) * f.tile_width;
-                oz = 0.0f;
+            // A3: the centre in scene space
+            float ox, oy, oz;
+            tile_offset(f, d, map_id_m, ox, oy, oz);
+            Mapped m = {(u2f(w0.x) + ox) * f.scene_scale[0], (u2f(w0.y) + oy) * f.scene_scale[1], (u2f(w0.z) + oz) * f.scene_scale[2],
+                        {1, 0, 0, 0, 1, 0, 0, 0, 1}, 0.0f, -1.0f, 0u, 0.0f, 1.0f};
+            // A4: onto the surface
+            if (f.surface_type == 1u) map_height_surface(f, hmap, m);
+            else if (FULL && f.surface_type == 2u) map_sphere_surface(f, d, map_id_m, m);
+            if (f.use_clip == 1u && m.mapped_z < f.clip_height) break;
+            if (ATM && !atmosphere_fade(f, m)) break;
+            // A5
+            if (!lod_transition<ATM>(f, d, lod_id, m)) break;
+            // A6..A10
+            VertexOut v;
+            bool kept;
+            if constexpr (STRICT) kept = vertex_strict<FULL, ORTHO, AA, ATM>(f, d, w0, w1, lod_id, m, v);
+            else kept = vertex_v2<FULL>(f, d, w0, w1, lod_id, m, v);
+            if (!kept) break;
+            if (DEBUG) {
+                vout.ndc[0] = v.ndcx; vout.ndc[1] = v.ndcy; vout.depth = v.depth;
+                vout.major[0] = v.majx; vout.major[1] = v.majy; vout.minor[0] = v.minx; vout.minor[1] = v.miny;
+                vout.rgba[0] = v.cr * v.fade; vout.rgba[1] = v.cg * v.fade; vout.rgba[2] = v.cb * v.fade; vout.rgba[3] = v.ca * v.fade;
             }
-            float c0 = (u2f(w0.x) + ox) * f.scene_scale[0];
-            float c1 = (u2f(w0.y) + oy) * f.scene_scale[1];
-            float c2 = (u2f(w0.z) + oz) * f.scene_scale[2];
-            // A4 :75-87
-            float mapped_z = 0.0f;
-            float F[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-            if (f.surface_type == 1u) {
-                const float DELTA = 0.001f;
-                float xr = gswt_host::hm_axis_range(f.map_half_wh[0], f.tile_width, f.height_map_scale[0]);
-                float yr = gswt_host::hm_axis_range(f.map_half_wh[1], f.tile_width, f.height_map_scale[1]);
-                float h_u = gswt_host::hm_axis_coord(c0, f.map_half_wh[0], f.tile_width, xr);
-                float h_v = gswt_host::hm_axis_coord(c1, f.map_half_wh[1], f.tile_width, yr);
-                float hz = f.height_map_scale[2];
-                float nz = sample_height(hmap, f.hm_w, f.hm_h, h_u, h_v) * hz;
-                float dt = DELTA;
-                float h_r = sample_height(hmap, f.hm_w, f.hm_h, h_u + dt, h_v) * hz;
-                float h_l = sample_height(hmap, f.hm_w, f.hm_h, h_u - dt, h_v) * hz;
-                float h_up = sample_height(hmap, f.hm_w, f.hm_h, h_u, h_v + dt) * hz;
-                float h_d = sample_height(hmap, f.hm_w, f.hm_h, h_u, h_v - dt) * hz;
-                float lx[3] = {1.0f, 0.0f, (h_r - h_l) / (2.0f * dt * xr)};
-                float ly[3] = {0.0f, 1.0f, (h_up - h_d) / (2.0f * dt * yr)};
-                float cz0 = lx[1] * ly[2] - lx[2] * ly[1];
-                float cz1 = lx[2] * ly[0] - lx[0] * ly[2];
-                float cz2 = lx[0] * ly[1] - lx[1] * ly[0];
-                float len = sqrtf((cz0 * cz0 + cz1 * cz1) + cz2 * cz2);
-                F[0] = lx[0]; F[1] = lx[1]; F[2] = lx[2];
-                F[3] = ly[0]; F[4] = ly[1]; F[5] = ly[2];
-                F[6] = cz0 / len; F[7] = cz1 / len; F[8] = cz2 / len;
-                float z = c2;
-                c0 = c0 + F[6] * z;
-                c1 = c1 + F[7] * z;
-                c2 = nz + F[8] * z;
-                mapped_z = nz;
-            } else if (FULL && f.surface_type == 2u) {
-                // surface_mapping, gswt.wgsl:600-623 (icosahedral-strip parametrisation, 5 x 2 blocks); sphere_get_uv + sphere_uv_to_pos
-                // (gswt.wgsl:515-564) are gswt_host::sphere_point, the one the host's tile centres use
-                const float DELTA = 0.001f;
-                const float xmax = ((float)f.map_half_wh[0] * 2.0f) * f.tile_width;
-                const float ymax = ((float)f.map_half_wh[1] * 2.0f) * f.tile_width;
-                const float block_w = xmax / 5.0f;
-                const float nx = c0 - (float)(f.center_coord[0] - (int32_t)f.map_half_wh[0]) * f.tile_width;
-                const float ny = c1 - (float)(f.center_coord[1] - (int32_t)f.map_half_wh[1]) * f.tile_width;
-                float bidx = (float)(5u * d.map_coord[0] / (f.map_half_wh[0] * 2u));
-                float bidy = (float)(2u * d.map_coord[1] / (f.map_half_wh[1] * 2u));
-                if (d.single_draw == 1u) {
-                    const uint32_t map_height = 2u * f.map_half_wh[1];
-                    const uint32_t map_id = map_id_m;
-                    bidx = (float)(5u * (map_id / map_height) / (f.map_half_wh[0] * 2u));
-                    bidy = (float)(2u * (map_id % map_height) / (f.map_half_wh[1] * 2u));
-                }
-                const float bx = nx - bidx * block_w, by = ny - bidy * block_w;
-                using gswt_host::V3;
-                using gswt_host::sphere_point;
-                const V3 lzv = sphere_point(block_w, bidx, bidy, bx, by);
-                const float R = f.sphere_radius;
-                const float dt = DELTA * ymax;
-                const V3 prv = sphere_point(block_w, bidx, bidy, bx + dt, by), plv = sphere_point(block_w, bidx, bidy, bx - dt, by);
-                const V3 puv = sphere_point(block_w, bidx, bidy, bx, by + dt), pdv = sphere_point(block_w, bidx, bidy, bx, by - dt);
-                // (by component for the loop below: the nine entries written out from the V3 fields schedule k_project<FULL> differently,
-                // and the device assembly of this file is kept byte for byte)
-                const float lz[3] = {lzv.x, lzv.y, lzv.z}, pr[3] = {prv.x, prv.y, prv.z}, pl[3] = {plv.x, plv.y, plv.z};
-                const float pu[3] = {puv.x, puv.y, puv.z}, pd[3] = {pdv.x, pdv.y, pdv.z};
-                for (int k = 0; k < 3; k++) {
-                    F[k] = (pr[k] * R - pl[k] * R) / (2.0f * dt);
-                    F[3 + k] = (pu[k] * R - pd[k] * R) / (2.0f * dt);
-                    F[6 + k] = lz[k];
-                }
-                const float z = c2;
-                const float n0 = lz[0] * R, n1 = lz[1] * R, n2 = lz[2] * R;
-                c0 = n0 + F[6] * z;
-                c1 = n1 + F[7] * z;
-                c2 = n2 + F[8] * z;
-                mapped_z = n2;
-            }
-            if (f.use_clip == 1u && mapped_z < f.clip_height) break;
-            // gswt_set_atmosphere (no counterpart in vs_main): dist is A5's cam_dist expression, computed once here; a splat the far fade takes
-            // to t == 0 is discarded right away (not visible, no pairs), like A5's t_ratio discards.  A NaN dist clamps to t = 0 (fmaxf drops it).
-            float atm_dist = 0.0f, atm_fs = 1.0f;
-            if (ATM) {
-                const float dx = c0 - f.cam_pos[0], dy = c1 - f.cam_pos[1], dz = c2 - f.cam_pos[2];
-                atm_dist = sqrtf((dx * dx + dy * dy) + dz * dz);
-                if (f.atm.fade_end > 0.0f) {
-                    const float t = clampf((f.atm.fade_end - atm_dist) * f.atm.fade_inv, 0.0f, 1.0f);
-                    if (t == 0.0f) break;
-                    atm_fs = (t * t) * (3.0f - 2.0f * t);
-                }
-            }
-            // A5 :91-150
-            float t_ratio = -1.0f;
-            uint32_t higher_lod = 0u;
-            if (d.changing == 1u) {
-                float dx = c0 - f.cam_pos[0], dy = c1 - f.cam_pos[1], dz = c2 - f.cam_pos[2];
-                float cam_dist = ATM ? atm_dist : sqrtf((dx * dx + dy * dy) + dz * dz);
-                if (d.single_draw == 1u) {
-                    if (lod_id == 0u) higher_lod = 0u;
-                    else if (lod_id == f.num_lod - 1u) higher_lod = lod_id - 1u;
-                    else {
-                        float d1 = f.transition_dist[(lod_id - 1u) & 15u];
-                        float d2 = f.transition_dist[lod_id & 15u];
-                        higher_lod = (cam_dist - d1 < d2 - cam_dist) ? lod_id - 1u : lod_id;
-                    }
-                } else {
-                    higher_lod = (d.changing_to_lower == 1) ? d.tile_lod : d.tile_lod - 1u;
-                }
-                float td = f.transition_dist[higher_lod & 15u];
-                float thw = f.transition_width_ratio * td;
-                t_ratio = clampf((cam_dist - td) / thw + 0.5f, 0.0f, 1.0f);
-                if ((lod_id == higher_lod + 1u && t_ratio == 0.0f) || (lod_id == higher_lod && t_ratio == 1.0f)) break;
-            }
-            float majx, majy, minx, miny, cr, cg, cb, ca, ndcx, ndcy, depth;
-            float q[4];
-            uint32_t col_word = w1.w;       // the record's colour word: the splat's own bytes unless the fog re-quantises them
-            if (STRICT) {
-                // A6 :152-167, operator by operator
-                float cv[4];
-                for (int rr = 0; rr < 4; rr++) cv[rr] = ((f.V[rr] * c0 + f.V[4 + rr] * c1) + f.V[8 + rr] * c2) + f.V[12 + rr] * 1.0f;
-                for (int rr = 0; rr < 4; rr++)
-                    q[rr] = ((f.GP[rr] * cv[0] + f.GP[4 + rr] * cv[1]) + f.GP[8 + rr] * cv[2]) + f.GP[12 + rr] * cv[3];
-                const float clip = 1.2f * q[3];
-                if (q[2] < -clip || q[0] < -clip || q[0] > clip || q[1] < -clip || q[1] > clip) break;
-                // A7 :169-205
-                float K[9];
-                {
-                    float a = half_decode(w1.x & 0xFFFFu), b = half_decode(w1.x >> 16);
-                    float cc = half_decode(w1.y & 0xFFFFu), dd = half_decode(w1.y >> 16);
-                    float e = half_decode(w1.z & 0xFFFFu), ff = half_decode(w1.z >> 16);
-                    K[0] = a; K[1] = b; K[2] = cc; K[3] = b; K[4] = dd; K[5] = e; K[6] = cc; K[7] = e; K[8] = ff;
-                }
-                if (f.point_cloud_radius > 0.0f) {
-                    float pr = f.point_cloud_radius;
-                    if (f.draw_mode > 0u) pr *= ldexpf(1.0f, (int)d.tile_lod);
-                    K[0] = pr; K[1] = 0; K[2] = 0; K[3] = 0; K[4] = pr; K[5] = 0; K[6] = 0; K[7] = 0; K[8] = pr;
-                }
-                if (f.surface_type > 0u) {          // Vrk = transform * Vrk * transpose(transform)
-                    float FK[9], R[9];
-                    for (int cc = 0; cc < 3; cc++)
-                        for (int rr = 0; rr < 3; rr++)
-                            FK[3 * cc + rr] = (F[rr] * K[3 * cc] + F[3 + rr] * K[3 * cc + 1]) + F[6 + rr] * K[3 * cc + 2];
-                    for (int cc = 0; cc < 3; cc++)
-                        for (int rr = 0; rr < 3; rr++)
-                            R[3 * cc + rr] = (FK[rr] * F[cc] + FK[3 + rr] * F[3 + cc]) + FK[6 + rr] * F[6 + cc];
-                    for (int k = 0; k < 9; k++) K[k] = R[k];
-                }
-                {                                   // scene_scale_mat * Vrk * transpose(scene_scale_mat): the full matrix products, zeros included
-                    const float S[9] = {f.scene_scale[0], 0.0f, 0.0f, 0.0f, f.scene_scale[1], 0.0f, 0.0f, 0.0f, f.scene_scale[2]};
-                    float SK[9], R[9];
-                    for (int cc = 0; cc < 3; cc++)
-                        for (int rr = 0; rr < 3; rr++)
-                            SK[3 * cc + rr] = (S[rr] * K[3 * cc] + S[3 + rr] * K[3 * cc + 1]) + S[6 + rr] * K[3 * cc + 2];
-                    for (int cc = 0; cc < 3; cc++)
-                        for (int rr = 0; rr < 3; rr++)
-                            R[3 * cc + rr] = (SK[rr] * S[cc] + SK[3 + rr] * S[3 + cc]) + SK[6 + rr] * S[6 + cc];
-                    for (int k = 0; k < 9; k++) K[k] = R[k];
-                }
-                // A8 :207-258
-                float JT[9];
-                if (ORTHO) {
-                    // J_T columns of the affine projection: (fx, 0, 0), (0, fy, 0), (0, 0, 0)
-                    JT[0] = f.focal[0]; JT[1] = 0.0f; JT[2] = 0.0f;
-                    JT[3] = 0.0f; JT[4] = f.focal[1]; JT[5] = 0.0f;
-                    JT[6] = 0.0f; JT[7] = 0.0f; JT[8] = 0.0f;
-                } else {
-                    const float dd0 = c0 - f.cam_pos[0], dd1 = c1 - f.cam_pos[1], dd2 = c2 - f.cam_pos[2];
-                    float t[3];
-                    for (int rr = 0; rr < 3; rr++) t[rr] = (f.V[rr] * dd0 + f.V[4 + rr] * dd1) + f.V[8 + rr] * dd2;
-                    const float txtz = t[0] / t[2], tytz = t[1] / t[2];
-                    const float limx = 1.3f * f.htan[0], limy = 1.3f * f.htan[1];
-                    t[0] = clampf(txtz, -limx, limx) * t[2];
-                    t[1] = clampf(tytz, -limy, limy) * t[2];
-                    const float tz2 = t[2] * t[2];
-                    // J_T columns: (fx / tz, 0, -fx tx / tz^2), (0, fy / tz, -fy ty / tz^2), (0, 0, 0)
-                    JT[0] = f.focal[0] / t[2]; JT[1] = 0.0f; JT[2] = (-f.focal[0] * t[0]) / tz2;
-                    JT[3] = 0.0f; JT[4] = f.focal[1] / t[2]; JT[5] = (-f.focal[1] * t[1]) / tz2;
-                    JT[6] = 0.0f; JT[7] = 0.0f; JT[8] = 0.0f;
-                }
-                float Tm[9];                        // T = transpose(view3) * J_T
-                for (int cc = 0; cc < 3; cc++)
-                    for (int rr = 0; rr < 3; rr++)
-                        Tm[3 * cc + rr] = (f.V[4 * rr + 0] * JT[3 * cc] + f.V[4 * rr + 1] * JT[3 * cc + 1]) + f.V[4 * rr + 2] * JT[3 * cc + 2];
-                float Am[9], C2[9];                 // cov2d = transpose(T) * Vrk * T
-                for (int cc = 0; cc < 3; cc++)
-                    for (int rr = 0; rr < 3; rr++)
-                        Am[3 * cc + rr] = (Tm[3 * rr + 0] * K[3 * cc] + Tm[3 * rr + 1] * K[3 * cc + 1]) + Tm[3 * rr + 2] * K[3 * cc + 2];
-                for (int cc = 0; cc < 3; cc++)
-                    for (int rr = 0; rr < 3; rr++)
-                        C2[3 * cc + rr] = (Am[rr] * Tm[3 * cc] + Am[3 + rr] * Tm[3 * cc + 1]) + Am[6 + rr] * Tm[3 * cc + 2];
-                const float c00 = C2[0], c01 = C2[1], c11 = C2[4];
-                const float mid = 0.5f * (c00 + c11);
-                const float hxx = 0.5f * (c00 - c11);
-                const float radius = sqrtf(hxx * hxx + c01 * c01);
-                const float l1 = mid + radius, l2 = mid - radius;
-                if (l2 < 0.0f) break;
-                const float vx = c01, vy = l1 - c00;
-                const float vlen = sqrtf(vx * vx + vy * vy);
-                const float ex = vx / vlen, ey = vy / vlen;
-                // GSWT_OPT_ANTIALIAS (no counterpart in vs_main): the pixel filter adds s to both eigenvalues -- the rejection above and the
-                // direction stay those of the unfiltered cov2d -- and comp keeps the integrated opacity.  AA = false compiles what there was
-                float l1f = l1, l2f = l2, comp = 1.0f;
-                if (AA) {
-                    l1f = l1 + f.aa_s; l2f = l2 + f.aa_s;
-                    comp = clampf(sqrtf(l1 / l1f) * sqrtf(l2 / l2f), 0.0f, 1.0f);      // (fmaxf drops a NaN: 0)
-                }
-                const float smaj = fminf(sqrtf(2.0f * l1f), 1024.0f);
-                const float smin = fminf(sqrtf(2.0f * l2f), 1024.0f);
-                majx = smaj * ex; majy = smaj * ey;
-                minx = smin * ey; miny = smin * -ex;
-                // A9 :260-265, 402-410
-                cr = (float)(w1.w & 0xFFu) / 255.0f;
-                cg = (float)((w1.w >> 8) & 0xFFu) / 255.0f;
-                cb = (float)((w1.w >> 16) & 0xFFu) / 255.0f;
-                ca = (float)((w1.w >> 24) & 0xFFu) / 255.0f;
-                if (FULL && f.draw_mode != 0u) debug_draw_color(f, d, u2f(w0.x), u2f(w0.y), lod_id, t_ratio, cr, cg, cb);   // :268-399
-                if (d.changing == 1u) {
-                    if (lod_id != higher_lod) ca = ca * t_ratio;
-                    else ca = ca * (1.0f - t_ratio);
-                }
-                if (AA) ca = ca * comp;
-                if (ATM) {
-                    // far fade: behind the LOD-transition product and the pixel filter's comp (1.0f with the fade off: exact)
-                    ca = ca * atm_fs;
-                    // distance fog: the colour goes toward fog_color by F(dist) and back into the record's 8 bits, so that Rec and the compositors
-                    // stay what they are; the debug draw modes keep their float colours (col_f)
-                    if (f.atm.fog_density > 0.0f && f.draw_mode == 0u) {
-                        const float F = fog_amount(f.atm, atm_dist);
-                        const float fr = cr * (1.0f - F) + f.atm.fog_color[0] * F;
-                        const float fg = cg * (1.0f - F) + f.atm.fog_color[1] * F;
-                        const float fb = cb * (1.0f - F) + f.atm.fog_color[2] * F;
-                        const uint32_t br = (uint32_t)rintf(fminf(fmaxf(fr, 0.0f), 1.0f) * 255.0f);
-                        const uint32_t bg = (uint32_t)rintf(fminf(fmaxf(fg, 0.0f), 1.0f) * 255.0f);
-                        const uint32_t bb = (uint32_t)rintf(fminf(fmaxf(fb, 0.0f), 1.0f) * 255.0f);
-                        col_word = br | bg << 8 | bb << 16 | (w1.w & 0xFF000000u);
-                        cr = (float)br / 255.0f; cg = (float)bg / 255.0f; cb = (float)bb / 255.0f;     // what the compositor will read
-                    }
-                }
-                // A10 :415-419
-                ndcx = q[0] / q[3]; ndcy = q[1] / q[3]; depth = q[2] / q[3];
-                if (DEBUG) {
-                    const float fade = clampf(q[2] / q[3] + 1.0f, 0.0f, 1.0f);
-                    vout.ndc[0] = ndcx; vout.ndc[1] = ndcy; vout.depth = depth;
-                    vout.major[0] = majx; vout.major[1] = majy; vout.minor[0] = minx; vout.minor[1] = miny;
-                    vout.rgba[0] = cr * fade; vout.rgba[1] = cg * fade; vout.rgba[2] = cb * fade; vout.rgba[3] = ca * fade;
-                }
-            } else {
-                // A6 :152-167 -- canonical sequence v2: dot products are fma chains, quotients are products
-                // with one correctly rounded reciprocal; the CPU checker evaluates exactly the same operations
-                float cv[4];
-                for (int rr = 0; rr < 4; rr++) cv[rr] = fmaf(f.V[8 + rr], c2, fmaf(f.V[4 + rr], c1, f.V[rr] * c0)) + f.V[12 + rr];
-                for (int rr = 0; rr < 4; rr++)
-                    q[rr] = fmaf(f.GP[12 + rr], cv[3], fmaf(f.GP[8 + rr], cv[2], fmaf(f.GP[4 + rr], cv[1], f.GP[rr] * cv[0])));
-                float clip = 1.2f * q[3];
-                if (q[2] < -clip || q[0] < -clip || q[0] > clip || q[1] < -clip || q[1] > clip) break;
-                // A7 :169-205
-                float K[9];
-                {
-                    float a = half_decode(w1.x & 0xFFFFu), b = half_decode(w1.x >> 16);
-                    float cc = half_decode(w1.y & 0xFFFFu), dd = half_decode(w1.y >> 16);
-                    float e = half_decode(w1.z & 0xFFFFu), ff = half_decode(w1.z >> 16);
-                    K[0] = a; K[1] = b; K[2] = cc; K[3] = b; K[4] = dd; K[5] = e; K[6] = cc; K[7] = e; K[8] = ff;
-                }
-                if (f.point_cloud_radius > 0.0f) {
-                    float pr = f.point_cloud_radius;
-                    if (f.draw_mode > 0u) pr *= ldexpf(1.0f, (int)d.tile_lod);
-                    K[0] = pr; K[1] = 0; K[2] = 0; K[3] = 0; K[4] = pr; K[5] = 0; K[6] = 0; K[7] = 0; K[8] = pr;
-                }
-                if (f.surface_type > 0u) {
-                    float FK[9], R[9];
-                    for (int cc = 0; cc < 3; cc++)
-                        for (int rr = 0; rr < 3; rr++)
-                            FK[3 * cc + rr] = fmaf(F[6 + rr], K[3 * cc + 2], fmaf(F[3 + rr], K[3 * cc + 1], F[rr] * K[3 * cc]));
-                    for (int cc = 0; cc < 3; cc++)
-                        for (int rr = 0; rr < 3; rr++)
-                            R[3 * cc + rr] = fmaf(FK[6 + rr], F[6 + cc], fmaf(FK[3 + rr], F[3 + cc], FK[rr] * F[cc]));
-                    for (int k = 0; k < 9; k++) K[k] = R[k];
-                }
-                // scene_scale_mat * Vrk * transpose(scene_scale_mat): a product with 1.0 is exact, so the usual unit scale skips 18 multiplications
-                // (uniform branch; same bits)
-                if (f.scene_scale[0] != 1.0f || f.scene_scale[1] != 1.0f || f.scene_scale[2] != 1.0f)
-                    for (int cc = 0; cc < 3; cc++)
-                        for (int rr = 0; rr < 3; rr++) K[3 * cc + rr] = (f.scene_scale[rr] * K[3 * cc + rr]) * f.scene_scale[cc];
-                // A8 :207-258
-                float d0 = c0 - f.cam_pos[0], d1 = c1 - f.cam_pos[1], d2 = c2 - f.cam_pos[2];
-                float t[3];
-                for (int rr = 0; rr < 3; rr++) t[rr] = fmaf(f.V[8 + rr], d2, fmaf(f.V[4 + rr], d1, f.V[rr] * d0));
-                const float rz = 1.0f / t[2];
-                float txtz = t[0] * rz, tytz = t[1] * rz;
-                float limx = 1.3f * f.htan[0], limy = 1.3f * f.htan[1];
-                t[0] = clampf(txtz, -limx, limx) * t[2];
-                t[1] = clampf(tytz, -limy, limy) * t[2];
-                const float rz2 = rz * rz;
-                float j00 = f.focal[0] * rz, j02 = -((f.focal[0] * t[0]) * rz2);
-                float j11 = f.focal[1] * rz, j12 = -((f.focal[1] * t[1]) * rz2);
-                float T0[3], T1[3];
-                for (int rr = 0; rr < 3; rr++) {
-                    T0[rr] = fmaf(f.V[4 * rr + 2], j02, f.V[4 * rr + 0] * j00);
-                    T1[rr] = fmaf(f.V[4 * rr + 2], j12, f.V[4 * rr + 1] * j11);
-                }
-                float A0[3], A1[3];
-                for (int k = 0; k < 3; k++) {
-                    A0[k] = fmaf(T0[2], K[3 * k + 2], fmaf(T0[1], K[3 * k + 1], T0[0] * K[3 * k]));
-                    A1[k] = fmaf(T1[2], K[3 * k + 2], fmaf(T1[1], K[3 * k + 1], T1[0] * K[3 * k]));
-                }
-                float c00 = fmaf(A0[2], T0[2], fmaf(A0[1], T0[1], A0[0] * T0[0]));
-                float c01 = fmaf(A1[2], T0[2], fmaf(A1[1], T0[1], A1[0] * T0[0]));
-                float c11 = fmaf(A1[2], T1[2], fmaf(A1[1], T1[1], A1[0] * T1[0]));
-                float mid = 0.5f * (c00 + c11);
-                float hxx = 0.5f * (c00 - c11);
-                float radius = sqrtf(fmaf(hxx, hxx, c01 * c01));
-                float l1 = mid + radius, l2 = mid - radius;
-                if (l2 < 0.0f) break;
-                float vx = c01, vy = l1 - c00;
-                float vlen = sqrtf(fmaf(vx, vx, vy * vy));
-                const float rv = 1.0f / vlen;
-                float ex = vx * rv, ey = vy * rv;
-                float smaj = fminf(sqrtf(2.0f * l1), 1024.0f);
-                float smin = fminf(sqrtf(2.0f * l2), 1024.0f);
-                majx = smaj * ex; majy = smaj * ey;
-                minx = smin * ey; miny = smin * -ex;
-                // A9 :260-265, 402-410 (byte / 255 as byte * fl(1 / 255))
-                const float k255 = 1.0f / 255.0f;
-                cr = (float)(w1.w & 0xFFu) * k255;
-                cg = (float)((w1.w >> 8) & 0xFFu) * k255;
-                cb = (float)((w1.w >> 16) & 0xFFu) * k255;
-                ca = (float)((w1.w >> 24) & 0xFFu) * k255;
-                if (FULL && f.draw_mode != 0u) debug_draw_color(f, d, u2f(w0.x), u2f(w0.y), lod_id, t_ratio, cr, cg, cb);   // :268-399
-                if (d.changing == 1u) {
-                    if (lod_id != higher_lod) ca = ca * t_ratio;
-                    else ca = ca * (1.0f - t_ratio);
-                }
-                // rgba *= clamp(z/w + 1, 0, 1): identically 1 for 0 <= z/w, kept for the debug output only
-                // A10 :415-419
-                const float rq = 1.0f / q[3];
-                ndcx = q[0] * rq; ndcy = q[1] * rq; depth = q[2] * rq;
-                if (DEBUG) {
-                    float fade = clampf(fmaf(q[2], rq, 1.0f), 0.0f, 1.0f);
-                    vout.ndc[0] = ndcx; vout.ndc[1] = ndcy; vout.depth = depth;
-                    vout.major[0] = majx; vout.major[1] = majy; vout.minor[0] = minx; vout.minor[1] = miny;
-                    vout.rgba[0] = cr * fade; vout.rgba[1] = cg * fade; vout.rgba[2] = cb * fade; vout.rgba[3] = ca * fade;
-                }
-            }
-            if (!(depth >= 0.0f && depth <= 1.0f)) break;
-            // Fragment setup F1, F2: pixel-space centre and inverse affine map
-            float cxp = fmaf(0.5f, ndcx, 0.5f) * f.W;
-            float cyp = fmaf(-0.5f, ndcy, 0.5f) * f.H;
-            float hs = 0.5f * f.splat_scale;
-            float ux = hs * majx, uy = -(hs * majy);
-            float wx = hs * minx, wy = -(hs * miny);
-            float uu = fmaf(uy, uy, ux * ux);
-            float ww = fmaf(wy, wy, wx * wx);
-            if (!((uu > 0.0f) && (ww > 0.0f) && (uu < __builtin_inff()) && (ww < __builtin_inff()))) break;
-            if (DEBUG) vout.visible = 1;
-            visible = true;
-            // depth_compare Less against the 1.0 clear when no proxy depth is bound (renderer.rs:182,436): a vertex-stage survivor
-            // (counted in n_visible) that no fragment of can pass -- no pairs
-            if (!f.has_depth && !(depth < 1.0f)) break;
-            const float ruu = 1.0f / uu, rww = 1.0f / ww;
-            const float r_iux = ux * ruu, r_iuy = uy * ruu, r_ivx = wx * rww, r_ivy = wy * rww;
-            // half extents of |p| <= 2, inflated by 1e-5 relative + 1e-3 px (conservative under f32 rounding)
-            float hx = fmaf(2.0f * sqrtf(fmaf(wx, wx, ux * ux)), 1.00001f, 0.001f);
-            float hy = fmaf(2.0f * sqrtf(fmaf(wy, wy, uy * uy)), 1.00001f, 0.001f);
-            // pixels whose CENTRE lies inside the box: x in [ceil(c - h - 0.5), floor(c + h - 0.5)]
-            float fx0 = ceilf(cxp - hx - 0.5f), fx1 = floorf(cxp + hx - 0.5f);
-            float fy0 = ceilf(cyp - hy - 0.5f), fy1 = floorf(cyp + hy - 0.5f);
-            if (fx1 >= fx0 && fy1 >= fy0 && fx1 >= 0.0f && fy1 >= 0.0f && fx0 <= f.W - 1.0f && fy0 <= f.H - 1.0f) {
-                int x0 = fx0 < 0.0f ? 0 : (int)fx0, x1 = fx1 > f.W - 1.0f ? f.width - 1 : (int)fx1;
-                int y0 = fy0 < 0.0f ? 0 : (int)fy0, y1 = fy1 > f.H - 1.0f ? f.height - 1 : (int)fy1;
-                int tx0 = x0 >> 4, tx1 = x1 >> 4, ty0 = y0 >> 4, ty1 = y1 >> 4;
-                tx0 = max(tx0, f.col0); tx1 = min(tx1, f.col1 - 1);          // column band of this ctx (the whole frame when off)
-                int rows = owned_rows(ty0, ty1, f.shard_index, f.shard_count);
-                count = tx1 >= tx0 ? (uint32_t)((tx1 - tx0 + 1) * rows) : 0u;
-                if (count) {
-                    my_rect = make_uint2((uint32_t)tx0 | ((uint32_t)tx1 << 16), (uint32_t)ty0 | ((uint32_t)ty1 << 16));
-                    // 32-byte record: the inverse map, the centre, alpha and the packed colour (unpacked by the compositor's blend);
-                    // the pixel half extents are re-derived from the inverse map by the compositor's staging lane, the depth
-                    // goes to a side array that only depth-tested / depth-ordered frames read
-                    Rec* dst = recs + slot;
-                    reinterpret_cast<float4*>(dst)[0] = make_float4(r_iux, r_iuy, r_ivx, r_ivy);
-                    // (the centre travels in NDC: the compositor takes its offset from a tile origin with one rounding, F3 of DESIGN.md section 4)
-                    reinterpret_cast<float4*>(dst)[1] = make_float4(ndcx, ndcy, ca, __uint_as_float(col_word));
-                    if (depths) depths[slot] = depth;
-                    if (FULL && f.draw_mode != 0u) col_f[slot] = make_float4(cr, cg, cb, 0.0f);   // debug colours are not bytes
-                }
-            }
+            if (!(v.depth >= 0.0f && v.depth <= 1.0f)) break;
+            // F1, F2, the tile rectangle and the record
+            fragment_setup<FULL>(f, v, slot, recs, depths, col_f, count, my_rect, visible);
+            if (DEBUG) vout.visible = visible;
         } while (0);
     }
     if (DEBUG && in_list) dbg[d.entry_base + (d.count - 1u - r)] = vout;
@@ -2926,6 +3000,28 @@ __global__ void k_unshard_plane(const P* __restrict__ gathered, P* __restrict__ 
 }
 
 // ---- launch wrappers (called from gswt_api.hip) -------------------------------------
+// The one way a wrapper picks a kernel instantiation from runtime values: with_variant(fn, a, b, ...) calls the generic lambda fn with one
+// compile-time constant per selector -- a bool becomes std::bool_constant, OneOf<V0, .., Vn>{v} the std::integral_constant of the Vi that v
+// equals (the last one when it equals none) -- so that fn names its kernel as k<A, B, ...>.  fn is instantiated for every combination of the
+// selectors: where the kernel has no such form, fn guards the launch with `if constexpr` and the wrapper keeps the combination from arriving.
+template <int... Vs> struct OneOf { int v; };
+template <typename Fn>
+static void with_variant(Fn&& fn) { fn(); }
+template <typename Fn, int V0, int... Vs, typename... Rest>
+static void with_variant(Fn&& fn, OneOf<V0, Vs...> sel, Rest... rest);
+template <typename Fn, typename... Rest>
+static void with_variant(Fn&& fn, bool sel, Rest... rest)
+{
+    if (sel) with_variant([&](auto... cs) { fn(std::true_type{}, cs...); }, rest...);
+    else with_variant([&](auto... cs) { fn(std::false_type{}, cs...); }, rest...);
+}
+template <typename Fn, int V0, int... Vs, typename... Rest>
+static void with_variant(Fn&& fn, OneOf<V0, Vs...> sel, Rest... rest)
+{
+    if (sizeof...(Vs) == 0 || sel.v == V0) with_variant([&](auto... cs) { fn(std::integral_constant<int, V0>{}, cs...); }, rest...);
+    else if constexpr (sizeof...(Vs) != 0) with_variant(fn, OneOf<Vs...>{sel.v}, rest...);
+}
+
 void launch_chunk_tabs(hipStream_t s, const DrawDev* draws, const uint32_t* xcd_first, uint32_t n_draws, uint2* chunk_tab, uint2* chunk_tab_xcd,
                        const uint64_t per_xcd[8], uint64_t longest)
 {
@@ -2961,26 +3057,17 @@ void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t 
     if (b.n_chunks == 0) return;
     const uint32_t n_super = b.n_chunks / 256u + 1u;    // super_sums = [pairs x 16 n_super][visible x 16 n_super][exclusive pair prefix x n_super] (kSuperStride), zeroed by k_cull
     const bool full = f.surface_type == 2u || f.draw_mode != 0u;
-#define GSWT_LAUNCH_PROJECT_S(D, F, S, O, A, M)                                                                                  \
-    GSWT_LAUNCH((k_project<D, F, S, O, A, M>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list, \
-                b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums, \
-                b.super_sums, n_super, b.dbg, b.col_f)
     // (the orthographic stage exists in its strict form only: gswt_api.hip refuses an orthographic frame with GSWT_OPT_STRICT_VS = 0)
     // (nor has the pixel filter another: AA is a parameter of the STRICT instantiations only, and gswt_api.hip refuses a filtered v2 frame)
     // (nor has the atmosphere: ATM likewise, and a frame with gswt_set_atmosphere's block off launches the ATM = false instantiation it always did)
-    const bool aa = f.aa_s > 0.0f, atm = f.atm.fade_end > 0.0f || f.atm.fog_density > 0.0f;
-#define GSWT_LAUNCH_PROJECT_M(D, F, O, A) do { if (atm) GSWT_LAUNCH_PROJECT_S(D, F, true, O, A, true); else GSWT_LAUNCH_PROJECT_S(D, F, true, O, A, false); } while (0)
-#define GSWT_LAUNCH_PROJECT_A(D, F, O) do { if (aa) GSWT_LAUNCH_PROJECT_M(D, F, O, true); else GSWT_LAUNCH_PROJECT_M(D, F, O, false); } while (0)
-#define GSWT_LAUNCH_PROJECT(D, F) do { if (ortho) GSWT_LAUNCH_PROJECT_A(D, F, true); else if (strict) GSWT_LAUNCH_PROJECT_A(D, F, false); \
-                                       else GSWT_LAUNCH_PROJECT_S(D, F, false, false, false, false); } while (0)
-    if (debug && full) { GSWT_LAUNCH_PROJECT(true, true); }
-    else if (debug) { GSWT_LAUNCH_PROJECT(true, false); }
-    else if (full) { GSWT_LAUNCH_PROJECT(false, true); }
-    else { GSWT_LAUNCH_PROJECT(false, false); }
-#undef GSWT_LAUNCH_PROJECT
-#undef GSWT_LAUNCH_PROJECT_A
-#undef GSWT_LAUNCH_PROJECT_M
-#undef GSWT_LAUNCH_PROJECT_S
+    const bool strict_seq = strict || ortho;
+    const bool aa = strict_seq && f.aa_s > 0.0f, atm = strict_seq && (f.atm.fade_end > 0.0f || f.atm.fog_density > 0.0f);
+    with_variant([&](auto D, auto F, auto S, auto O, auto A, auto M) {
+        if constexpr (S || !(O || A || M))
+            GSWT_LAUNCH((k_project<D, F, S, O, A, M>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,
+                        b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums,
+                        b.super_sums, n_super, b.dbg, b.col_f);
+    }, debug, full, strict_seq, ortho, aa, atm);
     GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, n_super, b.counters, b.super_sums + 2u * kSuperStride * n_super, b.pair_cap, b.live_cnt, n_launch / 8u);
 }
 
@@ -2997,13 +3084,10 @@ void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* ke
     const uint32_t* const cnt2 = n_launch ? b.live_cnt + 8u * kSuperStride : nullptr;
     const uint32_t* const cid = n_launch ? b.live_cid : nullptr;
     const dim3 grid(n_launch ? ((n_launch / 8u + kEmitGroup - 1u) / kEmitGroup) * 8u : (n_chunks + kEmitGroup - 1u) / kEmitGroup);
-#define GSWT_LAUNCH_EMIT(D, L)                                                                                                 \
-    GSWT_LAUNCH((k_emit<D, L>), grid, dim3(256), s, f, b.rects, b.block_sums, excl, n_chunks, pair_cap, b.counters, keys, b.vals_a, \
-                D ? b.depths : no_f, D ? dkeys : no_u, D ? krange : no_u, cnt2, cid)
-    if (n_launch) { if (dkeys) GSWT_LAUNCH_EMIT(true, true); else GSWT_LAUNCH_EMIT(false, true); }
-    else if (dkeys) GSWT_LAUNCH_EMIT(true, false);
-    else GSWT_LAUNCH_EMIT(false, false);
-#undef GSWT_LAUNCH_EMIT
+    with_variant([&](auto L, auto D) {
+        GSWT_LAUNCH((k_emit<D, L>), grid, dim3(256), s, f, b.rects, b.block_sums, excl, n_chunks, pair_cap, b.counters, keys, b.vals_a,
+                    D ? b.depths : no_f, D ? dkeys : no_u, D ? krange : no_u, cnt2, cid);
+    }, n_launch != 0u, dkeys != nullptr);
 }
 
 // ws: per pass [ghist 256 x nblk][gsup 256 x nsup][gtot 256] (gswt_device.h: launch_sort)
@@ -3030,6 +3114,7 @@ int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* key
     if (n_cap == 0) return 0;
     const uint32_t nblk = (n_cap + kSortBlock - 1) / kSortBlock, nsup = (nblk >> kSupShift) + 1;
     const int threads = n_cap <= kSortWideMax ? 512 : 256;
+    const int aux = !aux_a ? 0 : n_cap > (12u << 20) ? 2 : 1;       // k_radix_scatter's payload forms
     int cur = 0;
     const int passes = (key_bits + 7) / 8;
     uint32_t* hist_rows = ws + (size_t)passes * ((size_t)256 * nsup + 256);      // behind the zeroed part (radix_ws_zero_words)
@@ -3043,18 +3128,12 @@ int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* key
         uint32_t* ki = cur ? keys_b : keys_a; uint32_t* vi = cur ? vals_b : vals_a;
         uint32_t* ko = cur ? keys_a : keys_b; uint32_t* vo = cur ? vals_a : vals_b;
         const uint32_t* xi = cur ? aux_b : aux_a; uint32_t* xo = cur ? aux_a : aux_b;
-#define GSWT_SORT_PASS(T)                                                                                                        \
-        GSWT_LAUNCH(k_radix_hist<T>, dim3(nblk), dim3(T), s, ki, n_ptr, n_cap, (uint32_t)shift, mask, nbits, ghist, gsup, gtot, nblk, nsup, krange); \
-        if (nsup > kSupDirect) GSWT_LAUNCH(k_radix_supscan, dim3(64), dim3(256), s, gsup, gtot, nsup);                          \
-        if (aux_a && n_cap > (12u << 20)) GSWT_LAUNCH((k_radix_scatter<T, 2>), dim3(nblk), dim3(T), s, ki, vi, ko, vo, n_ptr, n_cap, (uint32_t)shift, mask, nbits, \
-                           ghist, gsup, gtot, nblk, nsup, shift + 8 >= key_bits ? ranges : (uint2*)nullptr, krange, xi, xo);                  \
-        else if (aux_a) GSWT_LAUNCH((k_radix_scatter<T, 1>), dim3(nblk), dim3(T), s, ki, vi, ko, vo, n_ptr, n_cap, (uint32_t)shift, mask, nbits,    \
-                           ghist, gsup, gtot, nblk, nsup, shift + 8 >= key_bits ? ranges : (uint2*)nullptr, krange, xi, xo);                  \
-        else GSWT_LAUNCH((k_radix_scatter<T, 0>), dim3(nblk), dim3(T), s, ki, vi, ko, vo, n_ptr, n_cap, (uint32_t)shift, mask, nbits,    \
-                           ghist, gsup, gtot, nblk, nsup, shift + 8 >= key_bits ? ranges : (uint2*)nullptr, krange, xi, xo)
-        if (threads == 512) { GSWT_SORT_PASS(512); }
-        else { GSWT_SORT_PASS(256); }
-#undef GSWT_SORT_PASS
+        with_variant([&](auto T, auto AUX) {
+            GSWT_LAUNCH(k_radix_hist<T>, dim3(nblk), dim3(T), s, ki, n_ptr, n_cap, (uint32_t)shift, mask, nbits, ghist, gsup, gtot, nblk, nsup, krange);
+            if (nsup > kSupDirect) GSWT_LAUNCH(k_radix_supscan, dim3(64), dim3(256), s, gsup, gtot, nsup);
+            GSWT_LAUNCH((k_radix_scatter<T, AUX>), dim3(nblk), dim3(T), s, ki, vi, ko, vo, n_ptr, n_cap, (uint32_t)shift, mask, nbits,
+                        ghist, gsup, gtot, nblk, nsup, shift + 8 >= key_bits ? ranges : (uint2*)nullptr, krange, xi, xo);
+        }, OneOf<512, 256>{threads}, OneOf<2, 1, 0>{aux});
         cur ^= 1;
     }
     return cur;
@@ -3105,28 +3184,14 @@ void launch_tile_depth_sort(hipStream_t s, const uint2* ranges, uint32_t* vals, 
 }
 uint32_t tile_depth_sort_cap() { return kTileSortCap; }
 
-// Calls fn(E, D, C) with the std::bool_constant arguments of the compositor instantiation <early-out, depth test, float colours> the frame
-// needs (debug draw modes: float colours from the side buffer, no early-out).
-template <typename Fn>
-static void with_composite_edc(const Frame& f, Fn&& fn)
-{
-    const bool early = f.t_eps > 0.0f, depth = f.has_depth != 0, colf = f.draw_mode != 0u;
-    using T = std::true_type;
-    using F = std::false_type;
-    if (colf) { if (depth) fn(F{}, T{}, T{}); else fn(F{}, F{}, T{}); }
-    else if (early && depth) fn(T{}, T{}, F{});
-    else if (early) fn(T{}, F{}, F{});
-    else if (depth) fn(F{}, T{}, F{});
-    else fn(F{}, F{}, F{});
-}
-
 // ranges -> per-tile segment counts -> item_base (exclusive scan, item_base[n_tiles] = #items) ->
-// k_composite over an upper bound of items -> k_combine, storing the image in format OUTF (and with ZOUT the depth image b.out_depth).
-// PICK: the pick image b.out_pick as well -- always through k_composite (its decoupled-waves twin is a bit-identical A/B switch and has no PICK
-// instantiation) --, resolved in place by k_pick_resolve from the same `vals`.
-template <int OUTF, bool ZOUT, bool PICK>
-static void launch_composite_t(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
-                               uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end)
+// k_composite over an upper bound of items -> k_combine, storing the image in format OUTF.
+// ZOUT: the frame's depth image is written as well, when b.out_depth is set (gswt_render_depth).
+// PICK: its pick image, when b.out_pick is set (gswt_render_pick) -- always through k_composite (its decoupled-waves twin is a bit-identical
+// A/B switch and has no PICK instantiation) --, resolved in place by k_pick_resolve from the same `vals`.
+// E, D, C: the compositor's <early-out, depth test, float colours> (debug draw modes: float colours from the side buffer, no early-out).
+void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
+                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format)
 {
     const int n_tiles = (int)b.n_tiles;
     const uint32_t seg = b.seg;
@@ -3136,54 +3201,35 @@ static void launch_composite_t(hipStream_t s, const Frame& f, const FrameBufs& b
         return;
     }
     const uint32_t max_items = (uint32_t)n_tiles + b.pair_cap / seg + 1u;
-    if (heavy_first)
-        GSWT_LAUNCH(k_items<true>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, b.ranges, n_tiles, seg, b.item_base, b.item_tab, max_items, krange, depth_passes, b.counters,
+    with_variant([&](auto HEAVY) {
+        GSWT_LAUNCH(k_items<HEAVY>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, b.ranges, n_tiles, seg, b.item_base, b.item_tab, max_items, krange, depth_passes, b.counters,
                     report_max ? 1u : 0u);
-    else
-        GSWT_LAUNCH(k_items<false>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, b.ranges, n_tiles, seg, b.item_base, b.item_tab, max_items, krange, depth_passes, b.counters,
-                    report_max ? 1u : 0u);
-    // GSWT_OPT_COMPOSITE = 1: decoupled waves (k_composite_dw), same image bit for bit; 0 and 2: k_composite.  (The compositors carry
-    // ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED.)
-    with_composite_edc(f, [&](auto E, auto D, auto C) {
-        if (variant == 1 && !PICK)
-            GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C, OUTF, ZOUT>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs,
-                              b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z);
-        else
-            GSWT_LAUNCH_TIMED((k_composite<E, D, C, OUTF, ZOUT, PICK>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals,
-                              b.recs, b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z,
-                              b.out_pick, b.partials_pick);
-    });
-    GSWT_LAUNCH((k_combine<OUTF, ZOUT, PICK>), dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows,
-                (const unsigned long long*)b.counters, b.host_counters, (const float*)b.partials_z, b.bg_depth, b.out_depth,
-                (const uint2*)b.partials_pick, b.out_pick);
-    if (PICK) {
-        const uint32_t n_px = (uint32_t)out_rows * (uint32_t)f.out_w;
-        GSWT_LAUNCH_TIMED(k_pick_resolve, dim3((n_px + 255u) / 256u), dim3(256), s, b.ev_pick_begin, b.ev_pick_end, b.out_pick, n_px, vals, b.pair_cap, b.chunk_tab, b.n_chunks, b.draws,
-                    b.static_list, b.merged_list, b.merged_map, (const float*)b.depths);
-    }
-}
-
-// The frame's depth image is written when b.out_depth is set (gswt_render_depth): the ZOUT instantiations of the compositors; its pick image
-// when b.out_pick is set (gswt_render_pick): the PICK ones.
-template <int OUTF>
-static void launch_composite_z(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
-                               uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end)
-{
-    if (b.out_pick) {
-        if (b.out_depth) launch_composite_t<OUTF, true, true>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-        else launch_composite_t<OUTF, false, true>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-    } else if (b.out_depth) launch_composite_t<OUTF, true, false>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-    else launch_composite_t<OUTF, false, false>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-}
-
-void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
-                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format)
-{
-    if (out_format == kOutNV12) launch_composite_z<kOutNV12>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-    else if (out_format == kOutI420) launch_composite_z<kOutI420>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-    else if (out_format == kOutRGBA8) launch_composite_z<kOutRGBA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-    else if (out_format == kOutBGRA8) launch_composite_z<kOutBGRA8>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
-    else launch_composite_z<kOutF32>(s, f, b, vals, out_rows, variant, krange, depth_passes, report_max, heavy_first, ev_begin, ev_end);
+    }, heavy_first);
+    const bool colf = f.draw_mode != 0u;
+    with_variant([&](auto outf, auto pick, auto zout) {
+        constexpr int OUTF = outf;          // (constants of their own: the inner lambda cannot read a captured argument at compile time)
+        constexpr bool PICK = pick, ZOUT = zout;
+        with_variant([&](auto C, auto E, auto D) {
+            // GSWT_OPT_COMPOSITE = 1: decoupled waves (k_composite_dw), same image bit for bit; 0 and 2: k_composite.  (The compositors carry
+            // ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED.)
+            if constexpr (C && E) return;       // (float colours have no early-out form)
+            else if (variant == 1 && !PICK)
+                GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C, OUTF, ZOUT>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs,
+                                  b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z);
+            else
+                GSWT_LAUNCH_TIMED((k_composite<E, D, C, OUTF, ZOUT, PICK>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals,
+                                  b.recs, b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z,
+                                  b.out_pick, b.partials_pick);
+        }, colf, !colf && f.t_eps > 0.0f, f.has_depth != 0);
+        GSWT_LAUNCH((k_combine<OUTF, ZOUT, PICK>), dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows,
+                    (const unsigned long long*)b.counters, b.host_counters, (const float*)b.partials_z, b.bg_depth, b.out_depth,
+                    (const uint2*)b.partials_pick, b.out_pick);
+        if (PICK) {
+            const uint32_t n_px = (uint32_t)out_rows * (uint32_t)f.out_w;
+            GSWT_LAUNCH_TIMED(k_pick_resolve, dim3((n_px + 255u) / 256u), dim3(256), s, b.ev_pick_begin, b.ev_pick_end, b.out_pick, n_px, vals, b.pair_cap, b.chunk_tab, b.n_chunks, b.draws,
+                        b.static_list, b.merged_list, b.merged_map, (const float*)b.depths);
+        }
+    }, OneOf<kOutNV12, kOutI420, kOutRGBA8, kOutBGRA8, kOutF32>{out_format}, b.out_pick != nullptr, b.out_depth != nullptr);
 }
 
 // k_totals alone on caller-provided sums (unit test of the 64-bit pair count)
