@@ -626,6 +626,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
     const uint32_t* vals = nullptr;
     rc = emit_and_sort(c, sl, f, b, key_bits, &vals);
     if (rc != GSWT_OK) return rc;
+    sl.sorted_vals = vals; sl.sorted_final = false;
     if (c->opt.timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvSorted], s));
     if (c->opt.timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvRanges], s));
     launch_composite(s, f, b, vals, out_rows, c->opt.composite, depth_order && !sl.depth_local ? b.krange : nullptr, sl.depth_passes, depth_order,
@@ -675,6 +676,7 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
     }
     c->live_hint = (uint32_t)std::min<unsigned long long>(sl.hc[4], 0xFFFFFFFFull);
     const uint32_t P = (uint32_t)sl.hc[1];
+    sl.sorted_pairs = P; sl.sorted_final = true;
     // keep 25-50 % headroom over the running pair count without shrinking on every small dip
     if (!c->opt.fixed_pair_cap && (uint64_t)P + P / 4 > c->pair_cap) c->pair_cap = (uint32_t)std::min<uint64_t>((uint64_t)P + P / 2 + 4096, 0xFFFFFF00ull);
     if (sl.args.cfg.order_mode == GSWT_ORDER_DEPTH) {
@@ -934,6 +936,52 @@ try {
     return GSWT_OK;
 } GSWT_CATCH
 
+int gswt_debug_sort_ex(gswt_ctx* c, uint32_t* keys, uint32_t* vals, uint32_t* aux, size_t n_cap, unsigned long long n, int overflow, int key_bits,
+                       int use_krange, uint32_t krange_min, uint32_t krange_max, uint32_t* ranges_out, size_t n_range_keys, int threads, int aux_form)
+try {
+    if (!c || !keys || !vals || n_cap == 0 || n_cap >= 0xFFFFFF00ull || key_bits < 1 || key_bits > 32) return GSWT_ERR_BAD_ARG;
+    if ((threads != 0 && threads != 256 && threads != 512) || aux_form < 0 || aux_form > 2 || (aux_form != 0 && !aux)) return GSWT_ERR_BAD_ARG;
+    if (ranges_out && (n_range_keys == 0 || n_range_keys > 0x7FFFFFFFull)) return GSWT_ERR_BAD_ARG;
+    if (use_krange && (krange_max < krange_min || (key_bits < 32 && ((krange_max - krange_min) >> key_bits) != 0u)))
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_debug_sort_ex: the key range does not fit %d key bits", key_bits);
+    // what the kernels will look at: the first n items, unless the count is refused (clamped_count)
+    const size_t n_seen = (overflow || n > n_cap) ? 0 : (size_t)n;
+    for (size_t i = 0; i < n_seen; i++) {
+        if (ranges_out && keys[i] >= n_range_keys) return fail(c, GSWT_ERR_BAD_ARG, "gswt_debug_sort_ex: key %u at %zu is outside the range table", keys[i], i);
+        if (use_krange && (keys[i] < krange_min || keys[i] > krange_max)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_debug_sort_ex: key %u at %zu is outside the key range", keys[i], i);
+    }
+    hipSetDevice(c->device);
+    const uint32_t cap = (uint32_t)n_cap;
+    DevBuf<uint32_t> ka, kb, va, vb, xa, xb, ws;
+    DevBuf<uint2> rg;
+    HIP_TRY(c, ka.ensure(n_cap + 4)); HIP_TRY(c, kb.ensure(n_cap + 4)); HIP_TRY(c, va.ensure(n_cap + 1)); HIP_TRY(c, vb.ensure(n_cap + 1));
+    if (aux) { HIP_TRY(c, xa.ensure(n_cap + 1)); HIP_TRY(c, xb.ensure(n_cap + 1)); }
+    if (ranges_out) { HIP_TRY(c, rg.ensure(n_range_keys + 1)); HIP_TRY(c, hipMemset(rg.p, 0, (n_range_keys + 1) * 8)); }
+    const size_t words = radix_ws_words(cap, key_bits) + 16;
+    HIP_TRY(c, ws.ensure(words));
+    HIP_TRY(c, hipMemset(ws.p, 0, words * 4));
+    // the frame's counter block in front of the histograms: {n, -, overflow flag} as the kernels' n_ptr sees it, the key range at 64-bit word 5
+    unsigned long long hn[8] = {n, 0ull, overflow ? 1ull : 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    const uint32_t kr[2] = {~krange_min, krange_max};
+    memcpy(&hn[5], kr, 8);
+    HIP_TRY(c, hipMemcpy(ws.p, hn, 64, hipMemcpyHostToDevice));
+    for (uint32_t* p : {ka.p, kb.p}) HIP_TRY(c, hipMemcpy(p, keys, n_cap * 4, hipMemcpyHostToDevice));
+    for (uint32_t* p : {va.p, vb.p}) HIP_TRY(c, hipMemcpy(p, vals, n_cap * 4, hipMemcpyHostToDevice));
+    if (aux) for (uint32_t* p : {xa.p, xb.p}) HIP_TRY(c, hipMemcpy(p, aux, n_cap * 4, hipMemcpyHostToDevice));
+    const int where = launch_sort(c->stream, ka.p, va.p, kb.p, vb.p, cap, reinterpret_cast<const unsigned long long*>(ws.p), key_bits, ws.p + 16,
+                                  ranges_out ? rg.p : nullptr, use_krange ? ws.p + 10 : nullptr, aux ? xa.p : nullptr, aux ? xb.p : nullptr, threads, aux_form);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!ranges_out) HIP_TRY(c, hipMemcpy(keys, where ? kb.p : ka.p, n_cap * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(vals, where ? vb.p : va.p, n_cap * 4, hipMemcpyDeviceToHost));
+    if (aux) HIP_TRY(c, hipMemcpy(aux, where ? xb.p : xa.p, n_cap * 4, hipMemcpyDeviceToHost));
+    if (ranges_out) {
+        HIP_TRY(c, hipMemcpy(ranges_out, rg.p, n_range_keys * 8, hipMemcpyDeviceToHost));
+        for (size_t t = 0; t < n_range_keys; t++) ranges_out[2 * t] = ranges_out[2 * t + 1] ? ~ranges_out[2 * t] : 0u;
+    }
+    return GSWT_OK;
+} GSWT_CATCH
+
 // Test hook: k_tile_depth_sort alone.  lens[t] = length of screen tile t's slice of the (tile-sorted) pair list, the slices back to back;
 // vals / dkeys: the list's values and depth keys (n = sum of lens).  Sorts every slice's vals by its dkeys, stably, in place.  flagged_out:
 // 1 when a slice was longer than the LDS buffer holds (nothing is then guaranteed about that slice; a frame would be re-run).
@@ -1010,6 +1058,37 @@ try {
     HIP_TRY(c, hipMemcpy(out, c->slots[c->last_slot].ranges.p, (size_t)c->last_n_tiles * 8, hipMemcpyDeviceToHost));
     for (uint32_t t = 0; t < c->last_n_tiles; t++)         // the device keeps (~start, end), (0, 0) for a tile without pairs
         out[2 * (size_t)t] = out[2 * (size_t)t + 1] ? ~out[2 * (size_t)t] : 0u;
+    return GSWT_OK;
+} GSWT_CATCH
+
+int gswt_debug_read_pairs(gswt_ctx* c, uint32_t* out, size_t capacity_pairs, size_t* n_pairs)
+try {
+    if (!c || !n_pairs) return GSWT_ERR_BAD_ARG;
+    const FrameSlot& sl = c->slots[c->last_slot];
+    if (!sl.sorted_vals) return fail(c, GSWT_ERR_STATE, "gswt_debug_read_pairs: no frame yet");
+    if (!sl.sorted_final) return fail(c, GSWT_ERR_STATE, "gswt_debug_read_pairs: the last frame has not been waited for");
+    *n_pairs = sl.sorted_pairs;
+    if (!out) return GSWT_OK;
+    const size_t n = sl.sorted_pairs;
+    if (capacity_pairs < n) return fail(c, GSWT_ERR_CAPACITY, "buffer holds %zu pairs, need %zu", capacity_pairs, n);
+    hipSetDevice(c->device);
+    HIP_TRY(c, sync_all(c));
+    const DrawSet& D = c->sets[sl.set];
+    std::vector<DrawDev> draws(D.n_draws);
+    std::vector<uint2> tab(D.n_chunks);
+    if (D.n_draws) HIP_TRY(c, hipMemcpy(draws.data(), D.draws, draws.size() * sizeof(DrawDev), hipMemcpyDeviceToHost));
+    if (D.n_chunks) HIP_TRY(c, hipMemcpy(tab.data(), D.chunk_tab.p, tab.size() * sizeof(uint2), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(c, hipMemcpy(out, sl.sorted_vals, n * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {                       // slot -> draw -> list entry in draw order (k_pick_resolve's walk; k_project's dbg index)
+        const uint32_t slot = out[i];
+        uint32_t entry = 0xFFFFFFFFu;
+        if ((slot >> 8) < D.n_chunks && tab[slot >> 8].x < D.n_draws) {
+            const DrawDev& d = draws[tab[slot >> 8].x];
+            const uint32_t r = slot - d.slot_base;
+            if (r < d.count) entry = d.entry_base + (d.count - 1u - r);
+        }
+        out[i] = entry;
+    }
     return GSWT_OK;
 } GSWT_CATCH
 

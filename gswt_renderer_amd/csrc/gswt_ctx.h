@@ -218,6 +218,11 @@ struct FrameSlot {
     bool depth_local = false;              // ... or the tile-local depth sort (k_tile_depth_sort)
     bool full_grid = false;                // this (re-run) frame launches k_project / k_emit over the whole launch table, whatever the hint says
     uint32_t n_launch_eff = 0;             // positions of the launch table this frame's grids cover
+    // gswt_debug_read_pairs: the ping-pong buffer that held this slot's last frame's sorted slots (what the compositor walked), and that
+    // frame's pair count once finish_frame has seen it complete (sorted_final; a re-run enqueues again and clears it)
+    const uint32_t* sorted_vals = nullptr;
+    uint32_t sorted_pairs = 0;
+    bool sorted_final = false;
     DevBuf<float4> partials;
     DevBuf<float> partials_z;              // frames that write their depth: a segment's partial depth beside its partial colour
     DevBuf<uint2> partials_pick;           // frames that write their pick: a segment's (largest weight, pair) beside its partial colour

@@ -376,12 +376,13 @@ void launch_totals(hipStream_t s, uint32_t* super_sums, uint32_t n_super, unsign
 // LSD radix sort of (keys, vals) on key bits [0, key_bits), ping-pong between the a and b buffers; returns 0 if the result is in a, 1 if in b.
 // The item count is read on the device (*n_ptr), grids are sized for n_cap.  ws: radix_ws_words(n_cap, key_bits) words whose first
 // radix_ws_zero_words(n_cap, key_bits) are zero on entry.  ranges (zero on entry): the last pass also writes every key's (~start, end);
-// krange: the key range the passes cover (depth keys); aux: a payload carried with the vals.
+// krange: the key range the passes cover (depth keys); aux: a payload carried with the vals.  threads_override (256 / 512) and
+// aux_override (1 / 2) replace the workgroup width and payload form the capacity selects (0: they stand; gswt_debug_sort_ex).
 size_t radix_ws_words(uint32_t n_cap, int key_bits);
 size_t radix_ws_zero_words(uint32_t n_cap, int key_bits);
 int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n_cap,
                 const unsigned long long* n_ptr, int key_bits, uint32_t* ws, uint2* ranges = nullptr, const uint32_t* krange = nullptr,
-                uint32_t* aux_a = nullptr, uint32_t* aux_b = nullptr);
+                uint32_t* aux_a = nullptr, uint32_t* aux_b = nullptr, int threads_override = 0, int aux_override = 0);
 
 // GSWT_ORDER_DEPTH, tile-local path: depth-sorts every tile's slice of the tile-sorted list in place.  long_list: two lists of tiles, each
 // tile_depth_list_words(n_tiles) words ([0] count, [1 .. n_tiles] tiles), back to back; both counts zero on entry.

@@ -3109,12 +3109,14 @@ size_t radix_ws_zero_words(uint32_t n_cap, int key_bits)
 }
 
 int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n_cap,
-                const unsigned long long* n_ptr, int key_bits, uint32_t* ws, uint2* ranges, const uint32_t* krange, uint32_t* aux_a, uint32_t* aux_b)
+                const unsigned long long* n_ptr, int key_bits, uint32_t* ws, uint2* ranges, const uint32_t* krange, uint32_t* aux_a, uint32_t* aux_b,
+                int threads_override, int aux_override)
 {
     if (n_cap == 0) return 0;
     const uint32_t nblk = (n_cap + kSortBlock - 1) / kSortBlock, nsup = (nblk >> kSupShift) + 1;
-    const int threads = n_cap <= kSortWideMax ? 512 : 256;
-    const int aux = !aux_a ? 0 : n_cap > (12u << 20) ? 2 : 1;       // k_radix_scatter's payload forms
+    // (the overrides: gswt_debug_sort_ex only -- a frame takes 512 threads at every capacity and payload form 1 up to 12 M pairs, 2 above)
+    const int threads = threads_override ? threads_override : n_cap <= kSortWideMax ? 512 : 256;
+    const int aux = !aux_a ? 0 : aux_override ? aux_override : n_cap > (12u << 20) ? 2 : 1;       // k_radix_scatter's payload forms
     int cur = 0;
     const int passes = (key_bits + 7) / 8;
     uint32_t* hist_rows = ws + (size_t)passes * ((size_t)256 * nsup + 256);      // behind the zeroed part (radix_ws_zero_words)

@@ -506,3 +506,30 @@ class GSWTRenderer:
         out = np.zeros((max(1, n.value), 2), dtype=np.uint32)
         self._check(self._lib.gswt_debug_read_ranges(self._h, _ptr(out), out.shape[0], C.byref(n)))
         return out[:n.value]
+
+    def read_pairs(self) -> np.ndarray:
+        """The sorted pair list the last frame's compositor walked (read_ranges' slices index it): per pair its list entry in draw
+        order (read_projected's index; 0xFFFFFFFF for a slot that names none).  Works without GSWT_OPT_DEBUG_VARYINGS."""
+        n = C.c_size_t(0)
+        self._check(self._lib.gswt_debug_read_pairs(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), dtype=np.uint32)
+        self._check(self._lib.gswt_debug_read_pairs(self._h, _ptr(out), out.shape[0], C.byref(n)))
+        return out[:n.value]
+
+    def debug_sort_ex(self, keys, vals, aux=None, *, n=None, overflow=False, key_bits=32, krange=None, n_range_keys=0, threads=0,
+                      aux_form=0):
+        """gswt_debug_sort_ex: the frame's radix sort as frames drive it.  keys / vals / aux: n_cap words each (copies are sorted);
+        n: the device-side item count (default n_cap); krange: (min, max); n_range_keys > 0: the last pass writes the range table
+        and no keys.  Returns (keys or None, vals, aux or None, ranges [n_range_keys, 2] or None), each of all n_cap words."""
+        k = np.array(keys, dtype=np.uint32, copy=True)
+        v = np.array(vals, dtype=np.uint32, copy=True)
+        x = np.array(aux, dtype=np.uint32, copy=True) if aux is not None else None
+        n_cap = k.shape[0]
+        assert k.ndim == 1 and v.shape == k.shape and (x is None or x.shape == k.shape)
+        rg = np.full((n_range_keys, 2), 0xDEADBEEF, dtype=np.uint32) if n_range_keys else None
+        kmin, kmax = (int(krange[0]), int(krange[1])) if krange is not None else (0, 0)
+        self._check(self._lib.gswt_debug_sort_ex(self._h, _ptr(k), _ptr(v), _ptr(x) if x is not None else None, n_cap,
+                                                 n_cap if n is None else int(n), 1 if overflow else 0, key_bits,
+                                                 1 if krange is not None else 0, kmin, kmax, _ptr(rg) if rg is not None else None,
+                                                 n_range_keys, threads, aux_form))
+        return (None if rg is not None else k), v, x, rg

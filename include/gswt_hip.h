@@ -845,6 +845,20 @@ GSWT_API int gswt_debug_totals(gswt_ctx *ctx, const uint32_t *pair_sums, const u
  * Host pointers. */
 GSWT_API int gswt_debug_sort(gswt_ctx *ctx, uint32_t *keys, uint32_t *vals, size_t n, int key_bits);
 
+/* Test hook: the same sort driven the way a frame drives it.  keys, vals and (optional) aux: n_cap words each, copied in full into BOTH
+ * ping-pong buffers, so that after any number of passes every word the sort did not write is still the caller's.  n: the item count the
+ * kernels read on the device -- 0, below n_cap, or above it; overflow: the frame's overflow flag beside it (either of the last two makes
+ * the sort process nothing).  aux: a second payload carried with the vals (the tile ids of the depth passes).  use_krange: the key range
+ * {~krange_min, krange_max} is uploaded and the digits are taken from key - krange_min; the caller keeps every key inside the range and
+ * krange_max - krange_min < 2^key_bits (in a frame k_items flags a range that needs more passes).  ranges_out (n_range_keys x 2 words,
+ * optional; every key < n_range_keys): a zeroed table goes to the last pass, which leaves every key's slice of the sorted list there and
+ * writes no keys; returned decoded like gswt_debug_read_ranges, (start, end), (0, 0) for an absent key.  threads: 0 = the sort's own
+ * choice, else 256 or 512 per workgroup; aux_form: 0 = its own choice, else payload form 1 or 2 (only with aux).
+ * On return vals and aux hold all n_cap words of the final buffers, keys too unless ranges_out is set.  Host pointers. */
+GSWT_API int gswt_debug_sort_ex(gswt_ctx *ctx, uint32_t *keys, uint32_t *vals, uint32_t *aux, size_t n_cap, unsigned long long n, int overflow,
+                                int key_bits, int use_krange, uint32_t krange_min, uint32_t krange_max, uint32_t *ranges_out,
+                                size_t n_range_keys, int threads, int aux_form);
+
 /* Test hook: the tile-local depth sort of GSWT_ORDER_DEPTH alone (k_tile_depth_sort).  lens[t] = length of screen tile t's slice of the pair
  * list (the slices lie back to back, n = their sum); every slice's vals are sorted by its dkeys, stably, in place (any length: slices of
  * more than 16 384 pairs go through k_tile_depth_sort_xl).  *flagged_out: the frame-level error flag of the kernels (0).  Host pointers. */
@@ -863,6 +877,12 @@ GSWT_API int gswt_debug_merge_stats_deep(const gswt_ctx *ctx, unsigned long long
 /* Test / profiling hook: [start, end) of every screen tile in the sorted pair list of the last
  * gswt_render (2 u32 per tile, shard-local tile order). Host pointer. */
 GSWT_API int gswt_debug_read_ranges(gswt_ctx *ctx, uint32_t *out, size_t capacity_tiles, size_t *n_tiles);
+/* Test hook: the sorted pair list the compositor of the last gswt_render walked (the list gswt_debug_read_ranges' slices index), one u32
+ * per pair: the pair's list entry in draw order (gswt_debug_read_projected's index), resolved on the host from its slot as k_pick_resolve
+ * does -- draw = chunk table[slot >> 8], entry = entry_base + (count - 1 - (slot - slot_base)); 0xFFFFFFFF for a slot that names no entry.
+ * out = NULL: only *n_pairs.  Needs no GSWT_OPT_DEBUG_VARYINGS.  GSWT_ERR_STATE before any frame, and while the last frame submitted
+ * through gswt_render_async has not been waited for (an overflowed frame is only re-run by the wait).  Host pointer. */
+GSWT_API int gswt_debug_read_pairs(gswt_ctx *ctx, uint32_t *out, size_t capacity_pairs, size_t *n_pairs);
 /* GSWT_ORDER_DEPTH bookkeeping: out[0] = frames enqueued on the tile-local path (k_tile_depth_sort), [1] = on the global depth passes
  * (re-runs count), [2] = the longest screen-tile pair list of the last finished depth-ordered frame. */
 GSWT_API int gswt_debug_depth_stats(const gswt_ctx *ctx, unsigned long long out[3]);

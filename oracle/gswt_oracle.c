@@ -967,6 +967,22 @@ typedef struct {
                                for a splat of depth 1.0 without bg_depth (it cannot pass the depth test) */
 } orc_stats;
 
+/* The 16x16 pixel blocks a visible entry makes a pair with: the blocks (tx0..tx1) x (ty0..ty1), both ends included, that hold at least
+ * one pixel centre inside the entry's conservative box (frag_setup's cxp, cyp, hx, hy, clipped to the frame).  Returns 0 -- no pairs --
+ * for an empty or off-screen box and for an entry whose every fragment fails the `Less` test against the 1.0 clear (depth == 1.0, no
+ * bg_depth).  orc_render's n_pairs16 and orc_pair_rects both come from here. */
+static int pair_rect(const orc_splat *sp, const orc_frag_setup *fs, int W, int H, int has_bg_depth, int r[4])
+{
+    float fx0 = ceilf(fs->cxp - fs->hx - 0.5f), fx1 = floorf(fs->cxp + fs->hx - 0.5f);
+    float fy0 = ceilf(fs->cyp - fs->hy - 0.5f), fy1 = floorf(fs->cyp + fs->hy - 0.5f);
+    if (!(has_bg_depth || sp->depth < 1.0f)) return 0;
+    if (!(fx1 >= fx0 && fy1 >= fy0 && fx1 >= 0.0f && fy1 >= 0.0f && fx0 <= (float)(W - 1) && fy0 <= (float)(H - 1))) return 0;
+    int x0 = fx0 < 0 ? 0 : (int)fx0, x1 = fx1 > (float)(W - 1) ? W - 1 : (int)fx1;
+    int y0 = fy0 < 0 ? 0 : (int)fy0, y1 = fy1 > (float)(H - 1) ? H - 1 : (int)fy1;
+    r[0] = x0 >> 4; r[1] = x1 >> 4; r[2] = y0 >> 4; r[3] = y1 >> 4;
+    return 1;
+}
+
 /*
  * GSWTRenderer::render (renderer.rs:407-592) for an already culled draw list:
  * colour LoadOp::Load over `bg_rgba` (NULL = transparent black), depth buffer =
@@ -1013,15 +1029,9 @@ ORC_API int orc_render(const orc_camera *cam, const orc_scene *scene, const uint
             }
             if (sp[k].visible) {
                 vis_d++;
-                float fx0 = ceilf(fs[k].cxp - fs[k].hx - 0.5f), fx1 = floorf(fs[k].cxp + fs[k].hx - 0.5f);
-                float fy0 = ceilf(fs[k].cyp - fs[k].hy - 0.5f), fy1 = floorf(fs[k].cyp + fs[k].hy - 0.5f);
-                /* no pairs for a splat whose every fragment fails the `Less` test against the 1.0 clear (depth == 1.0, no bg_depth) */
-                if ((bg_depth || sp[k].depth < 1.0f) &&
-                    fx1 >= fx0 && fy1 >= fy0 && fx1 >= 0.0f && fy1 >= 0.0f && fx0 <= (float)(W - 1) && fy0 <= (float)(H - 1)) {
-                    int x0 = fx0 < 0 ? 0 : (int)fx0, x1 = fx1 > (float)(W - 1) ? W - 1 : (int)fx1;
-                    int y0 = fy0 < 0 ? 0 : (int)fy0, y1 = fy1 > (float)(H - 1) ? H - 1 : (int)fy1;
-                    pairs_d += (uint64_t)((x1 >> 4) - (x0 >> 4) + 1) * (uint64_t)((y1 >> 4) - (y0 >> 4) + 1);
-                }
+                int r[4];
+                if (pair_rect(&sp[k], &fs[k], W, H, bg_depth != NULL, r))
+                    pairs_d += (uint64_t)(r[1] - r[0] + 1) * (uint64_t)(r[3] - r[2] + 1);
             }
         }
         n_vis += vis_d; n_pairs += pairs_d;
@@ -1213,6 +1223,44 @@ ORC_API int orc_project_draws(const orc_camera *cam, const orc_scene *scene, con
             uint32_t mid = dr->map_id ? dr->map_id[j] : 0u;
             uint32_t lid = dr->lod_id ? dr->lod_id[j] : 0u;
             orc_project(cam, scene, &dr->tile, tex, dr->gs_index[j], mid, lid, hmap, hm_w, hm_h, &out[k]);
+        }
+    }
+    return 0;
+}
+
+/* One record per list entry in draw order: what orc_render's vertex stage and pair count make of it. */
+typedef struct {
+    int32_t visible;                /* survives the vertex stage and frag_setup (orc_render's n_visible counts these) */
+    float depth;
+    int32_t tx0, tx1, ty0, ty1;     /* 16x16-block rectangle, ends included; (0, -1, 0, -1) where the entry makes no pairs */
+} orc_pair_rect;
+
+/* orc_render's inputs -> per entry `visible`, `depth` and the block rectangle its pairs cover (pair_rect).  The sum of the
+ * rectangles' areas is orc_render's n_pairs16.  Follows orc_set_strict like orc_project_draws. */
+ORC_API int orc_pair_rects(const orc_camera *cam, const orc_scene *scene, const uint32_t *tex,
+                           const orc_draw *draws, int n_draws, const float *hmap, int hm_w, int hm_h,
+                           int W, int H, int has_bg_depth, orc_pair_rect *out)
+{
+    if (W <= 0 || H <= 0) return -1;
+    if ((float)W != cam->viewport[0] || (float)H != cam->viewport[1]) return -2;
+    uint64_t k = 0;
+    for (int d = 0; d < n_draws; d++) {
+        const orc_draw *dr = &draws[d];
+        for (uint32_t j = 0; j < dr->count; j++, k++) {
+            uint32_t mid = dr->map_id ? dr->map_id[j] : 0u;
+            uint32_t lid = dr->lod_id ? dr->lod_id[j] : 0u;
+            orc_splat sp;
+            orc_frag_setup fs;
+            orc_project(cam, scene, &dr->tile, tex, dr->gs_index[j], mid, lid, hmap, hm_w, hm_h, &sp);
+            fs.ok = 0;
+            if (sp.visible) {
+                frag_setup(&sp, scene->splat_scale, (float)W, (float)H, &fs);
+                if (!fs.ok) sp.visible = 0;
+            }
+            int r[4] = { 0, -1, 0, -1 };
+            if (sp.visible && !pair_rect(&sp, &fs, W, H, has_bg_depth, r)) { r[0] = 0; r[1] = -1; r[2] = 0; r[3] = -1; }
+            out[k].visible = sp.visible; out[k].depth = sp.depth;
+            out[k].tx0 = r[0]; out[k].tx1 = r[1]; out[k].ty0 = r[2]; out[k].ty1 = r[3];
         }
     }
     return 0;

@@ -130,6 +130,9 @@ def lib():
         _lib.orc_project_draws.restype = C.c_int
         _lib.orc_project_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.orc_pair_rects.restype = C.c_int
+        _lib.orc_pair_rects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib.orc_num_threads.restype = C.c_int
         _lib.orc_set_strict.restype = None
         _lib.orc_set_strict.argtypes = [C.c_int]
@@ -616,6 +619,27 @@ def project_draws(cam: Camera176, scene: Scene160, tex: np.ndarray, draws, *, he
     hm = np.ascontiguousarray(height_map, dtype=np.float32) if height_map is not None else None
     lib().orc_project_draws(C.byref(cam), C.byref(scene), _ptr(tex), arr, len(draws), _ptr(hm),
                             hm.shape[1] if hm is not None else 0, hm.shape[0] if hm is not None else 0, _ptr(out))
+    return out[:n]
+
+
+PAIR_RECT_DTYPE = np.dtype([("visible", "<i4"), ("depth", "<f4"), ("tx0", "<i4"), ("tx1", "<i4"), ("ty0", "<i4"), ("ty1", "<i4")])
+
+
+def pair_rects(cam: Camera176, scene: Scene160, tex: np.ndarray, draws, width: int, height: int, *, height_map=None,
+               bg_depth=None) -> np.ndarray:
+    """render()'s inputs -> for every list entry in draw order `visible`, `depth` and the rectangle of 16x16 pixel blocks
+    (tx0..tx1) x (ty0..ty1), ends included, the entry makes a pair with (orc_pair_rects: the statements render()'s n_pairs16 counts
+    with).  An entry without pairs has tx1 < tx0 and ty1 < ty0.  Only the presence of bg_depth matters.  Follows strict() / v2()."""
+    tex = np.ascontiguousarray(tex, dtype=np.uint32)
+    arr, keep = _pack_draws(draws)
+    n = sum(int(np.asarray(d.gs_index).shape[0]) for d in draws)
+    out = np.zeros(max(n, 1), dtype=PAIR_RECT_DTYPE)
+    hm = np.ascontiguousarray(height_map, dtype=np.float32) if height_map is not None else None
+    rc = lib().orc_pair_rects(C.byref(cam), C.byref(scene), _ptr(tex), arr, len(draws), _ptr(hm),
+                              hm.shape[1] if hm is not None else 0, hm.shape[0] if hm is not None else 0,
+                              width, height, 1 if bg_depth is not None else 0, _ptr(out))
+    if rc != 0:
+        raise RuntimeError(f"orc_pair_rects failed: {rc}")
     return out[:n]
 
 
