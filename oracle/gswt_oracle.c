@@ -532,6 +532,28 @@ static int g_strict = 2;
 ORC_API void orc_set_strict(int on) { g_strict = on == 2 ? 2 : (on ? 1 : 0); }
 ORC_API int orc_get_strict(void) { return g_strict; }
 
+/* Three stages the HIP path's strict vertex stage has beside vs_main (include/gswt_hip.h; vertex_strict<., ORTHO, AA, ATM>), all off by   */
+/* default and read by the strict branch of project_impl only (the sequence v2 has no form of any of them, in the product or here).        */
+/* Process-wide like g_strict: orc_project_draws, orc_pair_rects and orc_render follow them.                                               */
+/*   projection 1: GSWT_OPT_PROJECTION = 1 -- A8's J_T is the constant ((fx, 0, 0), (0, fy, 0), (0, 0, 0)); no t, no quotient by t.z, no   */
+/*     htan_fov clamp; T and cov2d stay the written full products.                                                                         */
+/*   antialias s > 0: GSWT_OPT_ANTIALIAS -- the pixel filter adds s (= 4 v / splat_scale^2, computed by the caller as the host does) to    */
+/*     both eigenvalues behind the rejection l2 < 0 and the direction; alpha takes comp behind the LOD-transition product.                  */
+/*   fade_end > 0: gswt_set_atmosphere's far fade -- between the clip-height test and A5, on the mapped centre's distance from cam_pos;    */
+/*     fade_inv = 1.0f / (fade_end - fade_start) comes from the caller.  (The fog changes a colour byte and no list: not restated.)        */
+static int g_ortho = 0;
+static float g_aa_s = 0.0f, g_fade_end = 0.0f, g_fade_inv = 0.0f;
+ORC_API void orc_set_projection(int ortho) { g_ortho = ortho ? 1 : 0; }
+ORC_API int orc_get_projection(void) { return g_ortho; }
+ORC_API void orc_set_antialias(float s) { g_aa_s = s > 0.0f ? s : 0.0f; }
+ORC_API float orc_get_antialias(void) { return g_aa_s; }
+ORC_API void orc_set_fade(float fade_end, float fade_inv)
+{
+    if (fade_end > 0.0f) { g_fade_end = fade_end; g_fade_inv = fade_inv; }
+    else { g_fade_end = 0.0f; g_fade_inv = 0.0f; }
+}
+ORC_API void orc_get_fade(float out[2]) { out[0] = g_fade_end; out[1] = g_fade_inv; }
+
 /* vs_main, gswt.wgsl:27-422, every draw_mode.  Canonical float sequence "A1..A10"
  * of DESIGN.md.  Returns out->visible. */
 static int project_impl(const orc_camera *cam, const orc_scene *s, const orc_tile *u,
@@ -577,6 +599,16 @@ static int project_impl(const orc_camera *cam, const orc_scene *s, const orc_til
         mapped_z = np[2];
     }
     if (s->use_clip == 1u && mapped_z < s->clip_height) return 0;
+    /* far fade (orc_set_fade; no counterpart in vs_main): a splat the fade takes to t == 0 is discarded like A5's t_ratio discards; a NaN
+     * distance clamps to t = 0 (fmaxf drops it) */
+    float atm_fs = 1.0f;
+    if (strict_mode && g_fade_end > 0.0f) {
+        float dx = c[0] - cam->cam_pos[0], dy = c[1] - cam->cam_pos[1], dz = c[2] - cam->cam_pos[2];
+        float dist = sqrtf((dx * dx + dy * dy) + dz * dz);
+        float tf = clampf((g_fade_end - dist) * g_fade_inv, 0.0f, 1.0f);
+        if (tf == 0.0f) return 0;
+        atm_fs = (tf * tf) * (3.0f - 2.0f * tf);
+    }
     /* A5 :91-150 */
     float t_ratio = -1.0f;
     uint32_t higher_lod = 0u;
@@ -648,18 +680,24 @@ static int project_impl(const orc_camera *cam, const orc_scene *s, const orc_til
                     R[3 * cc + r] = (SK[r] * S[cc] + SK[3 + r] * S[3 + cc]) + SK[6 + r] * S[6 + cc];
             memcpy(K, R, sizeof(K));
         }
-        float dd[3] = { c[0] - cam->cam_pos[0], c[1] - cam->cam_pos[1], c[2] - cam->cam_pos[2] };
-        float t[3];
-        for (int r = 0; r < 3; r++) t[r] = (V[r] * dd[0] + V[4 + r] * dd[1]) + V[8 + r] * dd[2];
-        float txtz = t[0] / t[2], tytz = t[1] / t[2];
-        float limx = 1.3f * cam->htan_fov[0], limy = 1.3f * cam->htan_fov[1];
-        t[0] = clampf(txtz, -limx, limx) * t[2];
-        t[1] = clampf(tytz, -limy, limy) * t[2];
-        float tz2 = t[2] * t[2];
-        /* J_T columns: (fx/tz, 0, -fx*tx/tz2), (0, fy/tz, -fy*ty/tz2), (0, 0, 0) */
-        float JT[9] = { cam->focal[0] / t[2], 0.0f, (-cam->focal[0] * t[0]) / tz2,
-                        0.0f, cam->focal[1] / t[2], (-cam->focal[1] * t[1]) / tz2,
-                        0.0f, 0.0f, 0.0f };
+        float JT[9] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+        if (g_ortho) {
+            /* the affine projection's J_T columns: (fx, 0, 0), (0, fy, 0), (0, 0, 0) */
+            JT[0] = cam->focal[0];
+            JT[4] = cam->focal[1];
+        } else {
+            float dd[3] = { c[0] - cam->cam_pos[0], c[1] - cam->cam_pos[1], c[2] - cam->cam_pos[2] };
+            float t[3];
+            for (int r = 0; r < 3; r++) t[r] = (V[r] * dd[0] + V[4 + r] * dd[1]) + V[8 + r] * dd[2];
+            float txtz = t[0] / t[2], tytz = t[1] / t[2];
+            float limx = 1.3f * cam->htan_fov[0], limy = 1.3f * cam->htan_fov[1];
+            t[0] = clampf(txtz, -limx, limx) * t[2];
+            t[1] = clampf(tytz, -limy, limy) * t[2];
+            float tz2 = t[2] * t[2];
+            /* J_T columns: (fx/tz, 0, -fx*tx/tz2), (0, fy/tz, -fy*ty/tz2), (0, 0, 0) */
+            JT[0] = cam->focal[0] / t[2]; JT[2] = (-cam->focal[0] * t[0]) / tz2;
+            JT[4] = cam->focal[1] / t[2]; JT[5] = (-cam->focal[1] * t[1]) / tz2;
+        }
         /* T = transpose(view3) * J_T: T[c][r] = sum_k view3T[k][r] * JT[c][k], view3T[k][r] = V[4 r + k] */
         float Tm[9];
         for (int cc = 0; cc < 3; cc++)
@@ -682,8 +720,14 @@ static int project_impl(const orc_camera *cam, const orc_scene *s, const orc_til
         float vx = c01, vy = l1 - c00;
         float vlen = sqrtf(vx * vx + vy * vy);
         float ex = vx / vlen, ey = vy / vlen;               /* normalize(): 0/0 -> NaN -> nothing drawn */
-        float smaj = fminf(sqrtf(2.0f * l1), 1024.0f);
-        float smin = fminf(sqrtf(2.0f * l2), 1024.0f);
+        /* pixel filter (orc_set_antialias; no counterpart in vs_main): behind the rejection and the direction, which stay the unfiltered cov2d's */
+        float l1f = l1, l2f = l2, comp = 1.0f;
+        if (g_aa_s > 0.0f) {
+            l1f = l1 + g_aa_s; l2f = l2 + g_aa_s;
+            comp = clampf(sqrtf(l1 / l1f) * sqrtf(l2 / l2f), 0.0f, 1.0f);      /* (fmaxf drops a NaN: 0) */
+        }
+        float smaj = fminf(sqrtf(2.0f * l1f), 1024.0f);
+        float smin = fminf(sqrtf(2.0f * l2f), 1024.0f);
         out->major[0] = smaj * ex; out->major[1] = smaj * ey;
         out->minor[0] = smin * ey; out->minor[1] = smin * -ex;
         uint32_t cw = rec[7];
@@ -696,6 +740,8 @@ static int project_impl(const orc_camera *cam, const orc_scene *s, const orc_til
             if (lod_id != higher_lod) out->rgba[3] = out->rgba[3] * t_ratio;
             else out->rgba[3] = out->rgba[3] * (1.0f - t_ratio);
         }
+        if (g_aa_s > 0.0f) out->rgba[3] = out->rgba[3] * comp;
+        if (g_fade_end > 0.0f) out->rgba[3] = out->rgba[3] * atm_fs;
         float fade = clampf(q[2] / q[3] + 1.0f, 0.0f, 1.0f);
         for (int k = 0; k < 4; k++) out->rgba[k] = out->rgba[k] * fade;
         out->ndc[0] = q[0] / q[3];

@@ -100,50 +100,87 @@ assert C.sizeof(Camera176) == 176 and C.sizeof(Scene160) == 160 and C.sizeof(Til
 assert C.sizeof(OrcSplat) == SPLAT_DTYPE.itemsize == 48
 
 
+def _load(name: str):
+    """One of the two builds of gswt_oracle.c (oracle/Makefile), with its prototypes declared."""
+    build()
+    _lib = C.CDLL(os.path.join(_HERE, "_build", name))
+    _lib.orc_half_to_float.restype = C.c_float
+    _lib.orc_half_to_float.argtypes = [C.c_uint32]
+    _lib.orc_float_to_half.restype = C.c_uint32
+    _lib.orc_float_to_half.argtypes = [C.c_float]
+    _lib.orc_pack_half_2x16.restype = C.c_uint32
+    _lib.orc_pack_half_2x16.argtypes = [C.c_float, C.c_float]
+    _lib.orc_generate_texture.restype = None
+    _lib.orc_generate_texture.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    _lib.orc_sort_raw_depth.restype = None
+    _lib.orc_sort_raw_depth.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    _lib.orc_raw_depth.restype = None
+    _lib.orc_raw_depth.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    _lib.orc_scene_load.restype = None
+    _lib.orc_scene_load.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    _lib.orc_project.restype = C.c_int
+    _lib.orc_project.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                 C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    _lib.orc_render.restype = C.c_int
+    _lib.orc_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                C.c_int, C.c_void_p, C.c_void_p]
+    _lib.orc_project_draws.restype = C.c_int
+    _lib.orc_project_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    _lib.orc_pair_rects.restype = C.c_int
+    _lib.orc_pair_rects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_void_p]
+    _lib.orc_num_threads.restype = C.c_int
+    _lib.orc_set_strict.restype = None
+    _lib.orc_set_strict.argtypes = [C.c_int]
+    _lib.orc_get_strict.restype = C.c_int
+    _lib.orc_compare_modes.restype = C.c_int
+    _lib.orc_compare_modes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    _lib.orc_compare_modes2.restype = C.c_int
+    _lib.orc_compare_modes2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    _lib.orc_set_projection.restype = None
+    _lib.orc_set_projection.argtypes = [C.c_int]
+    _lib.orc_get_projection.restype = C.c_int
+    _lib.orc_set_antialias.restype = None
+    _lib.orc_set_antialias.argtypes = [C.c_float]
+    _lib.orc_get_antialias.restype = C.c_float
+    _lib.orc_set_fade.restype = None
+    _lib.orc_set_fade.argtypes = [C.c_float, C.c_float]
+    _lib.orc_get_fade.restype = None
+    _lib.orc_get_fade.argtypes = [C.c_void_p]
+    return _lib
+
+
 def lib():
     global _lib
     if _lib is None:
-        build()
-        name = "libgswt_oracle_fma.so" if _cpu_has_fma() else "libgswt_oracle.so"
-        _lib = C.CDLL(os.path.join(_HERE, "_build", name))
-        _lib.orc_half_to_float.restype = C.c_float
-        _lib.orc_half_to_float.argtypes = [C.c_uint32]
-        _lib.orc_float_to_half.restype = C.c_uint32
-        _lib.orc_float_to_half.argtypes = [C.c_float]
-        _lib.orc_pack_half_2x16.restype = C.c_uint32
-        _lib.orc_pack_half_2x16.argtypes = [C.c_float, C.c_float]
-        _lib.orc_generate_texture.restype = None
-        _lib.orc_generate_texture.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-        _lib.orc_sort_raw_depth.restype = None
-        _lib.orc_sort_raw_depth.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-        _lib.orc_raw_depth.restype = None
-        _lib.orc_raw_depth.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        _lib.orc_scene_load.restype = None
-        _lib.orc_scene_load.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-        _lib.orc_project.restype = C.c_int
-        _lib.orc_project.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                     C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        _lib.orc_render.restype = C.c_int
-        _lib.orc_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                    C.c_int, C.c_void_p, C.c_void_p]
-        _lib.orc_project_draws.restype = C.c_int
-        _lib.orc_project_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        _lib.orc_pair_rects.restype = C.c_int
-        _lib.orc_pair_rects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                        C.c_int, C.c_int, C.c_int, C.c_void_p]
-        _lib.orc_num_threads.restype = C.c_int
-        _lib.orc_set_strict.restype = None
-        _lib.orc_set_strict.argtypes = [C.c_int]
-        _lib.orc_get_strict.restype = C.c_int
-        _lib.orc_compare_modes.restype = C.c_int
-        _lib.orc_compare_modes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                           C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        _lib.orc_compare_modes2.restype = C.c_int
-        _lib.orc_compare_modes2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                            C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib = _load("libgswt_oracle_fma.so" if _cpu_has_fma() else "libgswt_oracle.so")
     return _lib
+
+
+class use_build:
+    """Context manager: every call of this module goes to the named build for the block -- fma=False the generic one, fma=True the
+    -mfma one (only on a CPU that has the unit: check cpu_has_fma()).  Each build has its own process-wide mode switches."""
+
+    def __init__(self, fma: bool):
+        self.name = "libgswt_oracle_fma.so" if fma else "libgswt_oracle.so"
+
+    def __enter__(self):
+        global _lib
+        self.prev = lib()
+        _lib = _load(self.name)
+        return self
+
+    def __exit__(self, *exc):
+        global _lib
+        _lib = self.prev
+        return False
+
+
+cpu_has_fma = _cpu_has_fma
 
 
 class strict:
@@ -172,6 +209,43 @@ class v2(strict):
 
     def __init__(self):
         self.mode = 0
+
+
+class frame_mode:
+    """Context manager, process-wide like strict(): the three stages the HIP path's strict vertex stage has beside vs_main
+    (gswt_oracle.c, orc_set_projection / orc_set_antialias / orc_set_fade), the defaults -- all off -- restored on exit.
+    ortho: GSWT_OPT_PROJECTION = 1, the camera block is an orthographic one;
+    aa_s: the pixel filter's s = 4 v / splat_scale^2 as the host computes it in binary32 (tests/antialias_ref.py: aa_s), 0 = off;
+    fade: (fade_end, fade_inv) with fade_inv = 1.0f / (fade_end - fade_start) in binary32, None = off.
+    Only the strict vertex stage (modes 1 and 2) reads them; v2() ignores them, as the product refuses such frames."""
+
+    def __init__(self, ortho=0, aa_s=0.0, fade=None):
+        self.ortho, self.aa_s = 1 if ortho else 0, float(aa_s)
+        self.fade = (0.0, 0.0) if fade is None else (float(fade[0]), float(fade[1]))
+
+    def __enter__(self):
+        l = self.lib = lib()
+        got = (C.c_float * 2)()
+        l.orc_get_fade(got)
+        self.prev = (l.orc_get_projection(), l.orc_get_antialias(), (got[0], got[1]))
+        l.orc_set_projection(self.ortho)
+        l.orc_set_antialias(self.aa_s)
+        l.orc_set_fade(*self.fade)
+        return self
+
+    def __exit__(self, *exc):
+        l = self.lib
+        l.orc_set_projection(self.prev[0])
+        l.orc_set_antialias(self.prev[1])
+        l.orc_set_fade(*self.prev[2])
+        return False
+
+
+def frame_mode_is_default() -> bool:
+    l = lib()
+    got = (C.c_float * 2)()
+    l.orc_get_fade(got)
+    return l.orc_get_projection() == 0 and l.orc_get_antialias() == 0.0 and got[0] == 0.0 and got[1] == 0.0
 
 
 def _ptr(a):

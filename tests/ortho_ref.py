@@ -2,8 +2,9 @@
 
 (a) project_ortho_f32: vs_main (gswt.wgsl:27-422) on the plain surface with the affine Jacobian in place of gswt.wgsl:213-232,
     restated operator by operator in np.float32 -- one rounding per written `*` `+` `-` `/` and sqrt, products and sums in the written
-    order, no fused multiply-add (numpy's element-wise float32 operations are single IEEE operations).  The CPU oracle has no
-    orthographic mode, so this restatement is what the GPU's per-splat outputs are compared with bit for bit.
+    order, no fused multiply-add (numpy's element-wise float32 operations are single IEEE operations).  The GPU's per-splat outputs
+    are compared with it bit for bit, and so is the C oracle's orthographic mode (oracle.frame_mode(ortho=1), which came later and
+    also covers the mapped surfaces: tests/test_pair_list_modes_cpu.py).
 (b) cov2d_f64: the same 2 x 2 covariance from the analytic J Sigma J^T in float64, with a per-entry bound of the float32 chain's
     rounding error.  It anchors (a): a slip in (a)'s index juggling shows there, not only as "GPU differs".
 (c) composite_f64: the blend of tests/depth_ref.py evaluated in float64 from the same records.
@@ -214,10 +215,13 @@ def _covariance3(scene, rec):
     return R
 
 
-def project_ortho_f32(cam, scene, tex, draws) -> np.ndarray:
+def project_ortho_f32(cam, scene, tex, draws, aa_s=None) -> np.ndarray:
     """The orthographic vertex stage of every instance of `draws` (orc.Draw, draw order) -> orc.SPLAT_DTYPE records.  Plain surface,
     draw_mode 0, no point-cloud radius.  `visible` carries the product's meaning: a vertex-stage survivor whose fragment setup F1 / F2
-    (|major|^2, |minor|^2 in (0, inf), as tests/depth_ref.py evaluates them) also passes."""
+    (|major|^2, |minor|^2 in (0, inf), as tests/depth_ref.py evaluates them) also passes.
+    aa_s (a binary32 number > 0, tests/antialias_ref.py: aa_s): GSWT_OPT_ANTIALIAS' pixel filter on this stage's own eigenvalues --
+    antialias_ref.filter_f32 behind the rejection l2 < 0 and the direction, comp on alpha behind the LOD-transition product."""
+    from tests import antialias_ref as AA
     assert scene.surface_type == 0 and scene.draw_mode == 0 and not scene.point_cloud_radius > 0.0
     V, P = _f32a(cam.view), _f32a(cam.projection)
     GP = np.zeros(16, F32)                           # opengl_to_wgpu * projection, gswt.wgsl:152-160
@@ -288,8 +292,12 @@ def project_ortho_f32(cam, scene, tex, draws) -> np.ndarray:
             vx, vy = c01, l1 - c00
             vlen = np.sqrt(vx * vx + vy * vy)
             ex, ey = vx / vlen, vy / vlen
-            smaj = np.fmin(np.sqrt(F32(2.0) * l1), F32(1024.0))
-            smin = np.fmin(np.sqrt(F32(2.0) * l2), F32(1024.0))
+            comp = None
+            if aa_s is not None and float(aa_s) > 0.0:
+                smaj, smin, comp = AA.filter_f32(l1, l2, F32(aa_s))
+            else:
+                smaj = np.fmin(np.sqrt(F32(2.0) * l1), F32(1024.0))
+                smin = np.fmin(np.sqrt(F32(2.0) * l2), F32(1024.0))
             sp["major"][:, 0], sp["major"][:, 1] = smaj * ex, smaj * ey
             sp["minor"][:, 0], sp["minor"][:, 1] = smin * ey, smin * -ex
             # A9 :260-265, 402-410
@@ -297,6 +305,8 @@ def project_ortho_f32(cam, scene, tex, draws) -> np.ndarray:
             col = [((cw >> np.uint32(8 * k)) & np.uint32(0xFF)).astype(F32) / F32(255.0) for k in range(4)]
             if t.changing == 1:
                 col[3] = np.where(lod != higher, col[3] * t_ratio, col[3] * (F32(1.0) - t_ratio))
+            if comp is not None:
+                col[3] = col[3] * comp
             # A10 :415-419
             fade = _clamp(q[2] / q[3] + F32(1.0), F32(0.0), F32(1.0))
             for k in range(4):

@@ -131,6 +131,28 @@ def test_surfaces_agree_with_the_oracle_where_the_jacobian_plays_no_part(rendere
     assert (np.hypot(maj[:, 0], maj[:, 1]) >= np.hypot(mnr[:, 0], mnr[:, 1])).all()
 
 
+@pytest.mark.parametrize("which", OR.CAMERAS)
+@pytest.mark.parametrize("name", ["case_hmap", "case_sphere"])
+def test_surfaces_equal_the_oracle_bit_for_bit(renderer, name, which):
+    """The same frames against the oracle's own orthographic stage (oracle.frame_mode(ortho=1); tests/test_pair_list_modes_cpu.py pins it to
+    the float32 restatement on the plane): every output, the axes included, bit for bit, and the same `visible`."""
+    g = OR.golden(name)
+    _bind(renderer, g)
+    su = OR.scene_of(g)
+    cu = _cam(which, g, name).uniforms()
+    got = _varyings(renderer, cu, su)
+    block = orc.Camera176.from_buffer_copy(bytes(cu))
+    with orc.frame_mode(ortho=1):
+        want = orc.project_draws(block, su, g["pp"].tex, g["draws"], height_map=g["hm"])
+        rects = orc.pair_rects(block, su, g["pp"].tex, g["draws"], W, Hh, height_map=g["hm"])
+    assert got.shape == want.shape
+    assert np.array_equal(got["visible"], rects["visible"])           # (the product's `visible`: the fragment setup passed too)
+    vis = rects["visible"] == 1
+    assert vis.sum() > 150
+    for fld in ("ndc", "depth", "major", "minor", "rgba"):
+        assert _bits_equal(got[fld][vis], want[fld][vis]), fld
+
+
 # ---- 3. image, depth and pick against the CPU references over the GPU's own records --------------------------------------------------
 def _image_case(renderer, which, order_mode, bg, splat_scale):
     g = OR.golden()

@@ -4,7 +4,10 @@ sequence reversed, restricted to the entries whose rectangle holds the tile).  k
 paths of GSWT_ORDER_DEPTH are checked pair by pair: a pair filed under the neighbouring tile, two neighbours swapped, a pair behind
 opaque content lost -- none of which the total pair count or the 1e-4 image can see.  All comparisons are between integers.
 
-Orthographic and anti-aliased frames are not covered: the C oracle's frag_setup has neither path (their numpy references do)."""
+The frames here are perspective ones with the pixel filter and the atmosphere off.  Orthographic, anti-aliased and faded frames, alone
+and combined, are in tests/test_pair_list_modes_gpu.py, which reuses _options / _frame / _check.  Not covered by either file: the fog's
+colours (a colour byte, no list), the sequence v2 in those modes (it has no form of them) and orthographic column bands (the API refuses
+them)."""
 import contextlib
 
 import numpy as np
