@@ -165,8 +165,15 @@ class Pick(C.Structure):
 
 PICK_NONE = 0xFFFFFFFF        # map_index and entry of a pixel no splat covers
 
+
+class TileStyle(C.Structure):
+    """gswt_tile_style: one map cell's entry of gswt_set_tile_styles' table (8 B; all zero: neutral)."""
+    _fields_ = [("tint", C.c_uint8 * 3), ("tint_strength", C.c_uint8), ("dim", C.c_uint8), ("_pad", C.c_uint8 * 3)]
+
+
 assert C.sizeof(Cell) == 260 and C.sizeof(CellState) == 20
 assert C.sizeof(Pick) == 16
+assert C.sizeof(TileStyle) == 8
 
 assert C.sizeof(CameraUniforms) == 176 and C.sizeof(SceneUniforms) == 160 and C.sizeof(TileUniforms) == 80
 
@@ -188,6 +195,7 @@ SYMBOLS = {
     "gswt_set_stream": (C.c_int, [_P, _P]),
     "gswt_set_option": (C.c_int, [_P, C.c_int, C.c_int]),
     "gswt_set_atmosphere": (C.c_int, [_P, _P]),
+    "gswt_set_tile_styles": (C.c_int, [_P, _P, C.c_size_t]),
     "gswt_upload_scene": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int]),
     "gswt_configure": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "gswt_set_draws": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_size_t]),

@@ -62,6 +62,8 @@ gswt_ctx::~gswt_ctx()
     if (ev_unshard) hipEventDestroy(ev_unshard);
     for (auto& ds : sets)
         if (ds.ev_up) hipEventDestroy(ds.ev_up);
+    for (auto& sv : sty_pool)
+        if (sv.ev_copied) hipEventDestroy(sv.ev_copied);
     for (auto& sl : slots) {
         sl.release_graph();
         for (auto& e : sl.ev) if (e) hipEventDestroy(e);
@@ -224,6 +226,48 @@ try {
     return GSWT_OK;
 } GSWT_CATCH
 
+int gswt_set_tile_styles(gswt_ctx* c, const gswt_tile_style* styles, size_t n_styles)
+try {
+    static_assert(sizeof(gswt_tile_style) == 8 && sizeof(uint2) == 8, "k_project reads an entry as one uint2: (tint | tint_strength << 24, dim)");
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!styles && n_styles > 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_tile_styles: styles is NULL with n_styles = %zu", n_styles);
+    if (n_styles > ((size_t)1 << 20)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_tile_styles: n_styles = %zu, more than 1 << 20 map cells", n_styles);
+    bool on = false;
+    for (size_t i = 0; i < n_styles; i++) {
+        const gswt_tile_style& e = styles[i];
+        if (e._pad[0] | e._pad[1] | e._pad[2])
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_tile_styles: styles[%zu]._pad = (%u, %u, %u), must be zero", i, e._pad[0], e._pad[1], e._pad[2]);
+        on = on || e.tint_strength != 0 || e.dim != 0;
+    }
+    if (!on) { c->sty_cur = -1; return GSWT_OK; }
+    // a version that is neither the current one nor the one a frame slot was last submitted with (frames in flight, re-runs): there is
+    // always one, kStyleVersions.  Nothing here waits for a frame: the staging of a free version is only waited for if its own earlier
+    // copy (of a table no frame ever used) is still queued on the ctx stream.
+    int v = -1;
+    for (int k = 0; k < kStyleVersions && v < 0; k++) {
+        bool used = k == c->sty_cur;
+        for (const auto& sl : c->slots) used = used || sl.args.sty_ver == k;
+        if (!used) v = k;
+    }
+    if (v < 0) return fail(c, GSWT_ERR_STATE, "gswt_set_tile_styles: no free table version");
+    StyleVersion& sv = c->sty_pool[v];
+    hipSetDevice(c->device);
+    if (sv.copy_pending) { HIP_TRY(c, hipEventSynchronize(sv.ev_copied)); sv.copy_pending = false; }
+    if (!sv.ev_copied) HIP_TRY(c, hipEventCreateWithFlags(&sv.ev_copied, hipEventDisableTiming));
+    // (buffers grow to twice the request: a host that sets a table per frame allocates once per version)
+    if (n_styles > sv.h.cap) HIP_TRY(c, sv.h.ensure(2 * n_styles));
+    HIP_TRY(c, sv.d.ensure_roomy(n_styles));
+    memcpy(sv.h.p, styles, n_styles * sizeof(gswt_tile_style));
+    // (on the ctx stream: a copy on the null stream would synchronise with every blocking stream; a frame submitted from now on starts
+    // behind everything queued on the ctx stream, enqueue_frame)
+    HIP_TRY(c, hipMemcpyAsync(sv.d.p, sv.h.p, n_styles * sizeof(gswt_tile_style), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(sv.ev_copied, c->stream));
+    sv.copy_pending = true;
+    sv.n = (uint32_t)n_styles;
+    c->sty_cur = v;
+    return GSWT_OK;
+} GSWT_CATCH
+
 int gswt_configure(gswt_ctx* c, const float* height_map, int hm_w, int hm_h)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;
@@ -319,6 +363,9 @@ static int validate_frame(gswt_ctx* c, const gswt_camera_uniforms* cam, const gs
     // a frame with the far fade or the fog on (gswt_set_atmosphere): only the strict vertex stage has an atmospheric form
     if ((c->atm.fade_end > 0.0f || c->atm.fog_density > 0.0f) && !c->opt.strict_vs)
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: gswt_set_atmosphere's fade or fog needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no atmospheric form)");
+    // nor a styled one (gswt_set_tile_styles with a table on)
+    if (c->sty_cur >= 0 && !c->opt.strict_vs)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: gswt_set_tile_styles' table needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no styled form)");
     return GSWT_OK;
 }
 
@@ -492,6 +539,8 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     b.draws = D.draws; b.n_chunks = D.n_chunks; b.chunk_tab = D.chunk_tab.p; b.chunk_tab_xcd = D.chunk_tab_xcd.p;
     b.static_list = c->static_list.p; b.merged_list = D.merged_list.p; b.merged_map = D.merged_map.p;
     b.tex = c->tex.p; b.hmap = c->hmap.p; b.boxes = c->static_boxes.p;
+    // (the version the frame was submitted with: no gswt_set_tile_styles refills it while this slot names it)
+    b.styles = a.sty_ver >= 0 ? c->sty_pool[a.sty_ver].d.p : nullptr; b.n_styles = a.sty_ver >= 0 ? c->sty_pool[a.sty_ver].n : 0u;
     b.bg_rgba = a.d_bg; b.bg_depth = a.d_bgd; b.out = a.d_out; b.out_depth = a.d_out_depth; b.host_counters = sl.hc_dev;
     b.out_pick = reinterpret_cast<uint4*>(a.d_out_pick);
     b.n_tiles = (uint32_t)n_tiles; b.pair_cap = cap; b.seg = seg;
@@ -722,6 +771,7 @@ static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* 
     // (validate_frame refused a splat_scale with which s is not a finite positive number)
     a.aa_s = c->opt.antialias > 0 ? antialias_s(c->opt.antialias, su->splat_scale) : 0.0f;
     a.atm = atmo_constants(c->atm);
+    a.sty_ver = c->sty_cur;
     return enqueue_frame(c, sl);
 }
 

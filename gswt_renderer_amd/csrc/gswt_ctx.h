@@ -176,7 +176,21 @@ struct FrameArgs {
     bool ortho = false;                    // GSWT_OPT_PROJECTION likewise: k_project<.,.,true,ORTHO> (frames in flight and re-runs keep their own)
     float aa_s = 0.0f;                     // GSWT_OPT_ANTIALIAS as it stood when the frame was submitted: s = 4 v / splat_scale^2 (a re-run keeps it)
     Atmo atm = {};                         // gswt_set_atmosphere's block likewise, with its derived constants (all zero: off)
+    int sty_ver = -1;                      // gswt_set_tile_styles' table likewise: its version in gswt_ctx::sty_pool (-1: styles off)
 };
+
+// One version of gswt_set_tile_styles' table: pinned staging (the host's entries, copied inside the call) and the device copy k_project
+// reads, filled by one asynchronous copy on the ctx stream.  A version is in use while it is the current one or a frame slot was last
+// submitted with it (FrameArgs::sty_ver: frames in flight and re-runs); any other one may be refilled.
+struct StyleVersion {
+    HostBuf<uint2> h;
+    DevBuf<uint2> d;
+    uint32_t n = 0;
+    hipEvent_t ev_copied = nullptr;        // behind the copy: the staging may be refilled once it has fired
+    bool copy_pending = false;
+};
+// the frame slots' versions and the current one can all differ: one more is always free
+constexpr int kStyleVersions = kFrameSlots + 2;
 
 // A frame's events on its slot's stream.  GSWT_OPT_TIMING >= 1 records kEvStart, kEvEnd and the compositor kernel's pair, 2 also the
 // stage boundaries in between (nothing runs between kEvSorted and kEvRanges); kEvDone follows the frame's last command in any case.
@@ -244,8 +258,8 @@ struct FrameSlot {
     }
 };
 
-// gswt_set_option's values with their defaults.  strict_vs, projection and antialias (and gswt_set_atmosphere's block, gswt_ctx::atm) are
-// snapshotted into FrameArgs when a frame is submitted; every other one is read when the frame (or the sort event) is enqueued.
+// gswt_set_option's values with their defaults.  strict_vs, projection and antialias (and gswt_set_atmosphere's block, gswt_ctx::atm, and
+// gswt_set_tile_styles' table version, gswt_ctx::sty_cur) are snapshotted into FrameArgs when a frame is submitted; every other one is read when the frame (or the sort event) is enqueued.
 struct Options {
     int no_prefilter = 0;                  // GSWT_OPT_NO_LOD_PREFILTER
     int debug_varyings = 0;
@@ -292,6 +306,9 @@ struct gswt_ctx {
     gswt::Options opt;
     // gswt_set_atmosphere: the block in force, validated (all zero: off).  Read when a frame is submitted and when gswt_proxy_render is called.
     gswt_atmosphere atm = {};
+    // gswt_set_tile_styles: the table versions and the one in force (-1: styles off).  Read when a frame is submitted.
+    gswt::StyleVersion sty_pool[gswt::kStyleVersions];
+    int sty_cur = -1;
     // scene
     gswt::DevBuf<uint4> tex;
     size_t n_splats = 0;

@@ -311,6 +311,9 @@ struct FrameBufs {
     const uint32_t *static_list, *merged_list, *merged_map;
     const uint4* tex;
     const float *hmap, *boxes;                 // boxes: tile-local bounds of every chunk of the static lists (k_cull's chunk cull)
+    // gswt_set_tile_styles' table as the frame was submitted with it, per map cell (tint r | g << 8 | b << 16 | tint_strength << 24, dim);
+    // null: styles off (k_project<.., STY = false>)
+    const uint2* styles; uint32_t n_styles;
     const float4* bg_rgba; const float* bg_depth; float4* out;
     float* out_depth;                          // the frame's depth image (f32, the colour's geometry); null: none (gswt_render_depth)
     uint4* out_pick;                           // the frame's pick image (gswt_pick records, the colour's geometry); null: none (gswt_render_pick)
@@ -363,7 +366,8 @@ void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks
 // (keys -> `keys`, slots -> b.vals_a; depth-ordered frames also the depth bits -> dkeys and, with krange, the frame's key range; n_launch 0:
 // over every chunk instead of the live table), k_items + the compositor over the sorted slots `vals`.
 void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_cull);
-// (the atmosphere is on when f.atm.fade_end > 0 or f.atm.fog_density > 0: strict frames only, gswt_api.hip refuses the others)
+// (the atmosphere is on when f.atm.fade_end > 0 or f.atm.fog_density > 0: strict frames only, gswt_api.hip refuses the others;
+// the tile styles are on when b.styles is set, likewise)
 void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict, bool ortho);
 void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
 // b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer, the video formats

@@ -468,6 +468,32 @@ struct VertexOut {
     float fade;                             // clamp(z/w + 1, 0, 1) on rgba: identically 1 for 0 <= z/w, kept for the debug output only
 };
 
+// gswt_set_tile_styles (no counterpart in vs_main), directly behind A1: the style of the map cell the entry belongs to -- the map_index the
+// pick image reports for it, k_pick_resolve's expression -- as (tint r | g << 8 | b << 16 | tint_strength << 24, dim); a cell past the table
+// reads as neutral.  A static draw's index is uniform (one scalar load per chunk), a merged draw's is the map id already loaded beside the
+// list word.  A hidden cell (dim == 255) discards the splat before its record is fetched: not visible, no pairs.
+__device__ __forceinline__ bool tile_style(const DrawDev& d, bool mrg, uint32_t map_id_m, const uint2* __restrict__ styles, uint32_t n_styles, uint2& sty)
+{
+    sty = make_uint2(0u, 0u);
+    if (mrg) { if (map_id_m < n_styles) sty = styles[map_id_m]; }
+    else if (d.map_index < n_styles) sty = styles[d.map_index];
+    return (sty.y & 0xFFu) != 255u;
+}
+
+// tile_style's dim, behind the LOD-transition product, the pixel filter's comp and the far fade's factor, and its tint, in front of the fog:
+// every written operator one binary32 operation (include/gswt_hip.h).  Returns whether the colour was tinted (the debug draw modes keep theirs).
+__device__ __forceinline__ bool tile_style_shade(const Frame& f, const uint2& sty, VertexOut& v)
+{
+    const uint32_t dim = sty.y & 0xFFu, strength = sty.x >> 24;
+    if (dim != 0u) v.ca = v.ca * ((float)(255u - dim) / 255.0f);
+    if (strength == 0u || f.draw_mode != 0u) return false;
+    const float k = (float)strength / 255.0f;
+    v.cr = v.cr * (1.0f - k) + ((float)(sty.x & 0xFFu) / 255.0f) * k;
+    v.cg = v.cg * (1.0f - k) + ((float)((sty.x >> 8) & 0xFFu) / 255.0f) * k;
+    v.cb = v.cb * (1.0f - k) + ((float)((sty.x >> 16) & 0xFFu) / 255.0f) * k;
+    return true;
+}
+
 // A3 :52-65 -- the offset of the entry's tile: the draw's own, or that of the member tile map_id of a merged group
 __device__ __forceinline__ void tile_offset(const Frame& f, const DrawDev& d, uint32_t map_id, float& ox, float& oy, float& oz)
 {
@@ -650,9 +676,20 @@ __device__ __forceinline__ void fog_requantise(const Frame& f, float atm_dist, u
     v.cr = (float)br / 255.0f; v.cg = (float)bg / 255.0f; v.cb = (float)bb / 255.0f;     // what the compositor will read
 }
 
+// a tinted colour the fog does not touch goes back into the record's 8 bits by the fog's own expression (with the fog on, fog_requantise
+// takes the tinted floats and this is not called: one quantisation either way)
+__device__ __forceinline__ void tint_requantise(uint32_t rgba8, VertexOut& v)
+{
+    const uint32_t br = (uint32_t)rintf(fminf(fmaxf(v.cr, 0.0f), 1.0f) * 255.0f);
+    const uint32_t bg = (uint32_t)rintf(fminf(fmaxf(v.cg, 0.0f), 1.0f) * 255.0f);
+    const uint32_t bb = (uint32_t)rintf(fminf(fmaxf(v.cb, 0.0f), 1.0f) * 255.0f);
+    v.col_word = br | bg << 8 | bb << 16 | (rgba8 & 0xFF000000u);
+    v.cr = (float)br / 255.0f; v.cg = (float)bg / 255.0f; v.cb = (float)bb / 255.0f;     // what the compositor will read
+}
+
 // A6..A10, STRICT: operator by operator as the shader text writes them (the comment above k_project)
-template <bool FULL, bool ORTHO, bool AA, bool ATM>
-__device__ __forceinline__ bool vertex_strict(const Frame& f, const DrawDev& d, const uint4& w0, const uint4& w1, uint32_t lod_id, const Mapped& m, VertexOut& v)
+template <bool FULL, bool ORTHO, bool AA, bool ATM, bool STY>
+__device__ __forceinline__ bool vertex_strict(const Frame& f, const DrawDev& d, const uint4& w0, const uint4& w1, uint32_t lod_id, const Mapped& m, const uint2& sty, VertexOut& v)
 {
     const float c0 = m.c0, c1 = m.c1, c2 = m.c2;
     const float* const F = m.F;
@@ -750,8 +787,12 @@ __device__ __forceinline__ bool vertex_strict(const Frame& f, const DrawDev& d, 
     if (ATM) {
         // far fade: behind the LOD-transition product and the pixel filter's comp (1.0f with the fade off: exact)
         v.ca = v.ca * m.atm_fs;
-        if (f.atm.fog_density > 0.0f && f.draw_mode == 0u) fog_requantise(f, m.atm_dist, w1.w, v);
     }
+    // gswt_set_tile_styles: dim behind the three alpha products above, tint in front of the fog, which then mixes the tinted floats
+    bool tinted = false;
+    if (STY) tinted = tile_style_shade(f, sty, v);
+    if (ATM && f.atm.fog_density > 0.0f && f.draw_mode == 0u) fog_requantise(f, m.atm_dist, w1.w, v);
+    else if (STY && tinted) tint_requantise(w1.w, v);
     // A10 :415-419
     v.ndcx = q[0] / q[3]; v.ndcy = q[1] / q[3]; v.depth = q[2] / q[3];
     v.fade = clampf(q[2] / q[3] + 1.0f, 0.0f, 1.0f);
@@ -893,8 +934,9 @@ __device__ __forceinline__ void fragment_setup(const Frame& f, const VertexOut& 
 
 // The kernel itself keeps the loads (launch table, list word, record: A1, A2 and the trace stamps around them) and the workgroup's sums; per
 // splat it calls, in this order, the stages above: tile_offset (A3), map_height_surface / map_sphere_surface (A4), atmosphere_fade,
-// lod_transition (A5), vertex_strict<FULL, ORTHO, AA, ATM> or vertex_v2<FULL> (A6..A10; both over splat_cov3 and lod_blend_color, the
-// strict one over fog_requantise) and fragment_setup (F1, F2, tile rectangle, record).  A new per-splat feature goes into the stage it
+// lod_transition (A5), vertex_strict<FULL, ORTHO, AA, ATM, STY> or vertex_v2<FULL> (A6..A10; both over splat_cov3 and lod_blend_color, the
+// strict one over tile_style_shade, fog_requantise and tint_requantise) and fragment_setup (F1, F2, tile rectangle, record); with STY,
+// tile_style runs directly behind A1, in front of the record's loads.  A new per-splat feature goes into the stage it
 // belongs to; a new template flag into that stage's parameters.
 // k_project's stamps (tools/project_trace.py), rows 8192 + launch position: [0] entry, [1] launch-table entry known, [2] list word arrived (lane 0),
 // [3] record arrived (lane 0, when it gets that far), [4] wave 0 through the projection, [5] behind the workgroup barrier, [6] end,
@@ -915,7 +957,10 @@ __device__ __forceinline__ void fragment_setup(const Frame& f, const VertexOut& 
 // ATM (gswt_set_atmosphere with either part on, STRICT only): the per-splat far fade and distance fog of include/gswt_hip.h, both functions of
 // A5's camera distance.  A template parameter like AA, so that a frame with the block off launches the instantiation it always did; which
 // of the two parts is on is a uniform branch on f.atm inside the ATM instantiations only.
-template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO, bool AA, bool ATM>
+// STY (gswt_set_tile_styles with a table on, STRICT only): the per-cell hide, dim and tint of include/gswt_hip.h.  A template parameter like
+// ATM: a frame with styles off launches the instantiation it always did and never reads `styles`; which parts of a style are on for a splat
+// is a branch on the loaded entry inside the STY instantiations only.
+template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO, bool AA, bool ATM, bool STY>
 __global__ __launch_bounds__(256) void k_project(
     const Frame f, const DrawDev* __restrict__ draws, const uint2* __restrict__ chunk_tab,
     const uint32_t* __restrict__ static_list, const uint32_t* __restrict__ merged_list,
@@ -923,7 +968,7 @@ __global__ __launch_bounds__(256) void k_project(
     const float* __restrict__ hmap, const uint32_t* __restrict__ draw_culled, const uint32_t* __restrict__ cell_culled,
     const uint32_t* __restrict__ live_cnt, const uint4* __restrict__ live_tab, uint2* __restrict__ rects,
     Rec* __restrict__ recs, float* __restrict__ depths, uint32_t* __restrict__ block_sums, uint32_t* __restrict__ super_sums, uint32_t n_super,
-    Varyings* __restrict__ dbg, float4* __restrict__ col_f)
+    Varyings* __restrict__ dbg, float4* __restrict__ col_f, const uint2* __restrict__ styles, uint32_t n_styles)
 {
     __shared__ uint32_t s_wsum[4], s_wvis[4];
     // chunk_tab is in LAUNCH order, which is not slot order: workgroup b runs on XCD b % 8, and the table is laid out so
@@ -986,6 +1031,8 @@ __global__ __launch_bounds__(256) void k_project(
             if (f.band_cull && d.single_draw == 1u && cell_culled[map_id_m] != 0u) break;
             // A1 gswt.wgsl:38-42
             if (d.valid_lod_id >= 0 && d.valid_lod_id != (int32_t)lod_id) break;
+            uint2 sty = make_uint2(0u, 0u);
+            if (STY && !tile_style(d, mrg, map_id_m, styles, n_styles, sty)) break;
             // A2 :45-49
             const uint4 w0 = tex[2 * (size_t)gs_index];
             const uint4 w1 = tex[2 * (size_t)gs_index + 1];
@@ -1008,7 +1055,7 @@ __global__ __launch_bounds__(256) void k_project(
             // A6..A10
             VertexOut v;
             bool kept;
-            if constexpr (STRICT) kept = vertex_strict<FULL, ORTHO, AA, ATM>(f, d, w0, w1, lod_id, m, v);
+            if constexpr (STRICT) kept = vertex_strict<FULL, ORTHO, AA, ATM, STY>(f, d, w0, w1, lod_id, m, sty, v);
             else kept = vertex_v2<FULL>(f, d, w0, w1, lod_id, m, v);
             if (!kept) break;
             if (DEBUG) {
@@ -3060,14 +3107,16 @@ void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t 
     // (the orthographic stage exists in its strict form only: gswt_api.hip refuses an orthographic frame with GSWT_OPT_STRICT_VS = 0)
     // (nor has the pixel filter another: AA is a parameter of the STRICT instantiations only, and gswt_api.hip refuses a filtered v2 frame)
     // (nor has the atmosphere: ATM likewise, and a frame with gswt_set_atmosphere's block off launches the ATM = false instantiation it always did)
+    // (nor have the tile styles: STY likewise, on when the frame was submitted with a table, b.styles)
     const bool strict_seq = strict || ortho;
     const bool aa = strict_seq && f.aa_s > 0.0f, atm = strict_seq && (f.atm.fade_end > 0.0f || f.atm.fog_density > 0.0f);
-    with_variant([&](auto D, auto F, auto S, auto O, auto A, auto M) {
-        if constexpr (S || !(O || A || M))
-            GSWT_LAUNCH((k_project<D, F, S, O, A, M>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,
+    const bool sty = strict_seq && b.styles != nullptr;
+    with_variant([&](auto D, auto F, auto S, auto O, auto A, auto M, auto Y) {
+        if constexpr (S || !(O || A || M || Y))
+            GSWT_LAUNCH((k_project<D, F, S, O, A, M, Y>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,
                         b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums,
-                        b.super_sums, n_super, b.dbg, b.col_f);
-    }, debug, full, strict_seq, ortho, aa, atm);
+                        b.super_sums, n_super, b.dbg, b.col_f, b.styles, b.n_styles);
+    }, debug, full, strict_seq, ortho, aa, atm, sty);
     GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, n_super, b.counters, b.super_sums + 2u * kSuperStride * n_super, b.pair_cap, b.live_cnt, n_launch / 8u);
 }
 

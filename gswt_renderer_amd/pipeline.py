@@ -32,6 +32,7 @@ class GSWTPipeline:
         self.configure(user)
         self.sort = None
         self._last_vp = None
+        self.tile_styles = None
 
     def configure(self, user: host.UserData, height_tex=None):
         self.conf = self.wang.configure(user, height_tex)  # worker configure, then renderer configure
@@ -39,12 +40,28 @@ class GSWTPipeline:
         self.sort = None
         self._last_vp = None
 
+    def set_tile_styles(self, styles):
+        """styles: a styles.TileStyles (world cell (cx, cy) -> TileStyle) or None.  Kept, packed for the current map window and handed
+        to the renderer at once, and packed again after every build event in update(): a styled world cell stays styled while the
+        map window shifts under it; a cell outside the window has no entry."""
+        self.tile_styles = styles
+        self._pack_tile_styles()
+
+    def _pack_tile_styles(self):
+        if not self.tile_styles:
+            self.renderer.set_tile_styles(None)
+            return
+        su = self.wang.scene_uniforms()
+        self.renderer.set_tile_styles(self.tile_styles.table(tuple(su.center_coord), tuple(su.map_half_wh), int(su.surface_type)))
+
     def update(self, cam_pos, view_proj, force_sort: bool = False) -> bool:
         """Worker half of a frame (state.rs:483-560).  Returns True when a new SortData was swapped in."""
         rebuilt = False
         if self.wang.check_update(cam_pos):
             self.wang.build_tiles(cam_pos)
             rebuilt = True
+            if self.tile_styles:                       # a build event moves the map window: the same world cells, new map indices
+                self._pack_tile_styles()
         vp = np.asarray(view_proj, dtype=np.float32)
         moved = self._last_vp is None or float(np.abs(vp - self._last_vp).sum()) >= 0.01   # state.rs:527-548
         if rebuilt or moved or force_sort or self.wang.user.always_sort or self.sort is None:
@@ -64,7 +81,7 @@ class GSWTPipeline:
 
     def render(self, camera_uniforms, width, height, **kw):
         """GSWTRenderer.render with the scene uniforms of the current configuration; every other keyword (order_mode, bg_rgba, depth,
-        pick, projection, antialias, atmosphere, ...) is passed through."""
+        pick, projection, antialias, atmosphere, tile_styles, ...) is passed through."""
         su = self.wang.scene_uniforms(splat_scale=kw.pop("splat_scale", 1.0), scene_scale=kw.pop("scene_scale", (1.0, 1.0, 1.0)),
                                       height_map_scale_v=kw.pop("height_map_scale_v", 1.0))
         # the other RenderConfig fields of SceneUniforms::from_data (renderer.rs:631-672)

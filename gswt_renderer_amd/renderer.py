@@ -113,6 +113,24 @@ class GSWTRenderer:
         blk = (C.c_char * 32).from_buffer_copy(bytes(a))
         self._check(self._lib.gswt_set_atmosphere(self._h, blk))
 
+    def set_tile_styles(self, table):
+        """gswt_set_tile_styles: table is the packed table of a styles.TileStyles (``.table(...)``), bytes of 8-byte gswt_tile_style
+        entries indexed by map cell, or a sequence of styles.TileStyle; None, empty or all neutral switches styles off.  The library
+        copies it inside the call; the frames submitted afterwards use it, frames in flight keep theirs."""
+        if table is None:
+            self._check(self._lib.gswt_set_tile_styles(self._h, None, 0))
+            return
+        if not isinstance(table, (bytes, bytearray, memoryview)):
+            table = b"".join(bytes(e) for e in table)
+        raw = bytes(table)
+        if len(raw) % 8:
+            raise ValueError("set_tile_styles: the table is a whole number of 8-byte entries")
+        if not raw:
+            self._check(self._lib.gswt_set_tile_styles(self._h, None, 0))
+            return
+        buf = (C.c_char * len(raw)).from_buffer_copy(raw)
+        self._check(self._lib.gswt_set_tile_styles(self._h, buf, len(raw) // 8))
+
     def set_stream(self, hip_stream: int):
         self._check(self._lib.gswt_set_stream(self._h, C.c_void_p(hip_stream)))
 
@@ -212,7 +230,7 @@ class GSWTRenderer:
                out_device_ptr: int | None = None, bg_on_device: bool = False, out_format: int = L.GSWT_OUT_RGBA32F,
                depth: bool = False, out_depth_device_ptr: int | None = None, pick: bool = False,
                out_pick_device_ptr: int | None = None, projection: int | None = None, antialias: float | None = None,
-               atmosphere=None):
+               atmosphere=None, tile_styles=None):
         """camera / scene: 176 / 160-byte uniform blocks (any ctypes struct or bytes of that layout).
         Returns the image [rows, W, 4] on the host -- f32 for GSWT_OUT_RGBA32F, uint8 in the channel order of
         GSWT_OUT_RGBA8_UNORM / GSWT_OUT_BGRA8_UNORM --, or None when out_device_ptr is given.
@@ -232,13 +250,17 @@ class GSWTRenderer:
         antialias: when given, sets GSWT_OPT_ANTIALIAS first: the variance of the screen-space pixel filter in px^2 (0.3 is the
         usual 3DGS constant, 0.1 Mip-Splatting's, 0 switches it off; rounded to 1/1024 px^2); omitted, the context keeps its value.
         atmosphere: when given, an atmosphere.Atmosphere set first with set_atmosphere (atmosphere.OFF switches the far fade and the
-        fog off); omitted, the context keeps the block it has."""
+        fog off); omitted, the context keeps the block it has.
+        tile_styles: when given, a table set first with set_tile_styles (b"" switches styles off); omitted, the context keeps the
+        table it has."""
         if projection is not None:
             self.set_option(L.GSWT_OPT_PROJECTION, int(projection))
         if antialias is not None:
             self.set_option(L.GSWT_OPT_ANTIALIAS, int(round(float(antialias) * 1024)))
         if atmosphere is not None:
             self.set_atmosphere(atmosphere)
+        if tile_styles is not None:
+            self.set_tile_styles(tile_styles)
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()
@@ -285,18 +307,21 @@ class GSWTRenderer:
                      lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
                      transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba_ptr: int = 0, bg_depth_ptr: int = 0,
                      out_format: int = L.GSWT_OUT_RGBA32F, out_depth_ptr: int = 0, out_pick_ptr: int = 0,
-                     projection: int | None = None, antialias: float | None = None, atmosphere=None) -> int:
+                     projection: int | None = None, antialias: float | None = None, atmosphere=None,
+                     tile_styles=None) -> int:
         """Queues a frame (device pointers only) and returns a ticket for render_wait.  out_device_ptr holds rows x out_w x 4
         f32, or bytes for the 8-bit out_format values, or the planes of a GSWT_VIDEO_* format (gswt_out_image_bytes(out_format,
         rows, out_w) bytes, width and height even; see video_planes); out_depth_ptr (optional) receives the depth image, rows x out_w f32
         (gswt_render_async_depth); out_pick_ptr (optional) the pick image, rows x out_w records of PICK_DTYPE (gswt_render_async_pick).
-        projection, antialias, atmosphere: as in render (the frame keeps the values it was submitted with, whatever is set afterwards)."""
+        projection, antialias, atmosphere, tile_styles: as in render (the frame keeps the values it was submitted with, whatever is set afterwards)."""
         if projection is not None:
             self.set_option(L.GSWT_OPT_PROJECTION, int(projection))
         if antialias is not None:
             self.set_option(L.GSWT_OPT_ANTIALIAS, int(round(float(antialias) * 1024)))
         if atmosphere is not None:
             self.set_atmosphere(atmosphere)
+        if tile_styles is not None:
+            self.set_tile_styles(tile_styles)
         cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
         sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
         cfg = L.RenderConfig()

@@ -368,6 +368,59 @@ typedef struct {
 } gswt_atmosphere;                /* 32 bytes */
 GSWT_API int gswt_set_atmosphere(gswt_ctx *ctx, const gswt_atmosphere *a);   /* NULL or an all-zero block: off (the default) */
 
+/* ---- tile-instance styles: hide, dim and tint map cells per splat ---------------------------------
+ * The pick image (gswt_render_pick) names the tile instance a pixel shows, its map_index.  This table lets the host act on it:
+ * highlight the picked instance, ghost a tile, cut a hole into the splat layer, mark a region of a minimap -- also for a member of a
+ * merged draw, which cannot be left out of the draw list on its own.  The reference has no per-instance appearance.
+ *
+ * Key.  The table is indexed by map cell: a splat's style is styles[id] with id the map_index the pick image reports for it --
+ * gswt_tile_uniforms.map_index of a static draw, the member's map_index for an entry of a merged draw.  id >= n_styles reads as
+ * neutral.  Map indices move with the map window at a build event; keeping a world cell styled across build events is the
+ * caller's job (the Python layer does it: styles.TileStyles, GSWTPipeline.set_tile_styles).
+ *
+ * Off.  NULL, n_styles == 0 or a table whose entries are all neutral (tint_strength == 0 and dim == 0; the call scans it): styles
+ * off, the default.  A frame with styles off launches exactly the kernels it launches without this call and is bit for bit the
+ * same frame.
+ *
+ * Vertex stage (strict sequence).  Every written operator is one correctly rounded binary32 operation, nothing fused; s = styles[id]:
+ *   Hide (s.dim == 255): the splat is discarded directly behind A1 (the valid_lod_id test), before its record is fetched: it is not
+ *     visible (not in n_visible), makes no pairs and cannot appear in the colour, depth or pick image.
+ *   Dim (0 < s.dim < 255):
+ *     a_s = (float)(255 - s.dim) / 255.0f;   alpha = alpha * a_s
+ *     with the product after the LOD-transition product, after the pixel filter's comp and after the far fade's fs.
+ *   Tint (s.tint_strength > 0 and draw_mode == 0):
+ *     k = (float)s.tint_strength / 255.0f;   tc = (float)s.tint[c] / 255.0f
+ *     per channel  c_t = c * (1.0f - k) + tc * k      on the float colour of the record's bytes
+ *     With the fog on, the fog's formula takes c_t in place of c.  The colour is re-quantised once, at the end, by the fog's own
+ *     expression: byte' = (uint32_t)rintf(fminf(fmaxf(c', 0), 1) * 255.0f), and the record's colour word becomes
+ *     byte'_r | byte'_g << 8 | byte'_b << 16 | (word & 0xFF000000).  At strength 255 the bytes are the tint's.
+ *   The debug draw modes (draw_mode != 0) keep their colours; hide and dim still apply to them.
+ *   A neutral entry of a table that is on leaves the splat's record bit-identical to the unstyled frame's.
+ * gswt_debug_read_projected reports what the compositor will read: (float)byte' / 255.0f and the dimmed alpha.
+ * Untouched: pair rectangles, the tile / chunk / column-band culls (styles only remove splats), the sorts, every compositor form, the
+ * pick resolve, every output format, both order modes and both shard modes, GSWT_OPT_PROJECTION = 1, GSWT_OPT_ANTIALIAS and the
+ * atmosphere.  The projected record stays 32 bytes.
+ *
+ * Lifetime.  The table is copied by the call (the host pointer is borrowed for the call only) into a device buffer of the library's:
+ * one of a small pool of table versions, each kept while it is the current one or a frame slot was last submitted with it.  A frame
+ * uses the table that was in force when it was submitted; frames in flight keep theirs, and so does a frame re-run after a
+ * pair-buffer overflow, whatever is set afterwards.  Setting a table does not wait for frames in flight: the copy goes through a
+ * pinned staging buffer on the ctx stream, and the frames submitted afterwards are ordered behind it (only a version whose buffers
+ * must grow past the largest table seen so far allocates).  Under GSWT_OPT_GRAPH the table's pointer and length are arguments of
+ * the k_project node; switching styles on or off selects another k_project instantiation and the slot's graph is rebuilt.
+ *
+ * Refused with GSWT_ERR_BAD_ARG, the reason in gswt_last_error and the table in force unchanged: styles == NULL with n_styles > 0;
+ * n_styles > 1 << 20; an entry with a nonzero _pad byte (the message names the entry).  With styles on, a submit returns
+ * GSWT_ERR_BAD_ARG before anything is enqueued when GSWT_OPT_STRICT_VS = 0 (sequence v2 has no styled form).
+ * Out of scope: styles for gswt_proxy_render / gswt_skybox_render, outlines, per-splat styles, the CPU oracle. */
+typedef struct {
+    uint8_t tint[3];        /* R, G, B of the tint colour */
+    uint8_t tint_strength;  /* 0: no tint ... 255: the tint colour replaces the splat's */
+    uint8_t dim;            /* 0: opacity unchanged ... 254; 255: the cell is hidden */
+    uint8_t _pad[3];        /* must be zero */
+} gswt_tile_style;          /* 8 bytes; all-zero = neutral */
+GSWT_API int gswt_set_tile_styles(gswt_ctx *ctx, const gswt_tile_style *styles, size_t n_styles);
+
 /* GSWTRenderer::new (renderer.rs:31-349): uploads PreloadData.tile_splats_merged.tex_data
  * (8 u32 per splat, renderer.rs:236-248) and all static base lists (renderer.rs:290-327).
  * lists is [n_lod][n_tile][n_view] row-major. */
