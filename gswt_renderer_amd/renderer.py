@@ -30,10 +30,26 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _shard_mode(mode) -> int:
+    """"cols", "columns" or GSWT_SHARD_COLUMNS -> contiguous tile-column bands; anything else -> interleaved tile rows."""
+    return L.GSWT_SHARD_COLUMNS if mode in ("cols", "columns", L.GSWT_SHARD_COLUMNS) and mode != 0 else L.GSWT_SHARD_ROWS
+
+
 def _shard_args(shard):
     """shard = (index, count) -> interleaved tile rows; (index, count, "cols") -> contiguous tile-column bands."""
-    mode = L.GSWT_SHARD_COLUMNS if len(shard) > 2 and shard[2] in ("cols", "columns", L.GSWT_SHARD_COLUMNS) and shard[2] != 0 else L.GSWT_SHARD_ROWS
-    return int(shard[0]), int(shard[1]), mode
+    return int(shard[0]), int(shard[1]), _shard_mode(shard[2]) if len(shard) > 2 else L.GSWT_SHARD_ROWS
+
+
+def _frame_blocks(camera, scene, culling_dist, lod_enable_mask, order_mode, transmittance_eps, shard, out_format):
+    """(camera block, scene block, RenderConfig) of a frame, as the gswt_render* entry points take them."""
+    cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
+    sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
+    cfg = L.RenderConfig()
+    cfg.culling_dist, cfg.lod_enable_mask, cfg.order_mode = culling_dist, lod_enable_mask & 0xFFFFFFFF, order_mode
+    cfg.transmittance_eps = transmittance_eps
+    cfg.shard_index, cfg.shard_count, cfg.shard_mode = _shard_args(shard)
+    cfg.out_format = out_format & 0xFFFFFFFF
+    return cam, sc, cfg
 
 
 def _out_dtype(out_format: int):
@@ -223,6 +239,17 @@ class GSWTRenderer:
         self._check(self._lib.gswt_debug_read_merged(self._h, _ptr(a), _ptr(b), a.shape[0], C.byref(n)))
         return a[:n.value], b[:n.value]
 
+    def _set_frame_modes(self, projection, antialias, atmosphere, tile_styles):
+        """The per-frame modes that render and render_async take as keywords: each one given is set on the context, in this order."""
+        if projection is not None:
+            self.set_option(L.GSWT_OPT_PROJECTION, int(projection))
+        if antialias is not None:
+            self.set_option(L.GSWT_OPT_ANTIALIAS, int(round(float(antialias) * 1024)))
+        if atmosphere is not None:
+            self.set_atmosphere(atmosphere)
+        if tile_styles is not None:
+            self.set_tile_styles(tile_styles)
+
     # -- GSWTRenderer::render (renderer.rs:407) ---------------------------------------
     def render(self, camera, scene, width: int, height: int, *, culling_dist: float = 1.0,
                lod_enable_mask: int = 0xFFFFFFFF, order_mode: int = L.GSWT_ORDER_REFERENCE,
@@ -253,21 +280,8 @@ class GSWTRenderer:
         fog off); omitted, the context keeps the block it has.
         tile_styles: when given, a table set first with set_tile_styles (b"" switches styles off); omitted, the context keeps the
         table it has."""
-        if projection is not None:
-            self.set_option(L.GSWT_OPT_PROJECTION, int(projection))
-        if antialias is not None:
-            self.set_option(L.GSWT_OPT_ANTIALIAS, int(round(float(antialias) * 1024)))
-        if atmosphere is not None:
-            self.set_atmosphere(atmosphere)
-        if tile_styles is not None:
-            self.set_tile_styles(tile_styles)
-        cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
-        sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
-        cfg = L.RenderConfig()
-        cfg.culling_dist, cfg.lod_enable_mask, cfg.order_mode = culling_dist, lod_enable_mask & 0xFFFFFFFF, order_mode
-        cfg.transmittance_eps = transmittance_eps
-        cfg.shard_index, cfg.shard_count, cfg.shard_mode = _shard_args(shard)
-        cfg.out_format = out_format & 0xFFFFFFFF
+        self._set_frame_modes(projection, antialias, atmosphere, tile_styles)
+        cam, sc, cfg = _frame_blocks(camera, scene, culling_dist, lod_enable_mask, order_mode, transmittance_eps, shard, out_format)
         rows, out_w = height, width
         if cfg.shard_count > 1 and cfg.shard_mode == L.GSWT_SHARD_COLUMNS:
             out_w = self._lib.gswt_shard_cols_padded(width, cfg.shard_count)
@@ -314,21 +328,8 @@ class GSWTRenderer:
         rows, out_w) bytes, width and height even; see video_planes); out_depth_ptr (optional) receives the depth image, rows x out_w f32
         (gswt_render_async_depth); out_pick_ptr (optional) the pick image, rows x out_w records of PICK_DTYPE (gswt_render_async_pick).
         projection, antialias, atmosphere, tile_styles: as in render (the frame keeps the values it was submitted with, whatever is set afterwards)."""
-        if projection is not None:
-            self.set_option(L.GSWT_OPT_PROJECTION, int(projection))
-        if antialias is not None:
-            self.set_option(L.GSWT_OPT_ANTIALIAS, int(round(float(antialias) * 1024)))
-        if atmosphere is not None:
-            self.set_atmosphere(atmosphere)
-        if tile_styles is not None:
-            self.set_tile_styles(tile_styles)
-        cam = (C.c_char * 176).from_buffer_copy(bytes(camera))
-        sc = (C.c_char * 160).from_buffer_copy(bytes(scene))
-        cfg = L.RenderConfig()
-        cfg.culling_dist, cfg.lod_enable_mask, cfg.order_mode = culling_dist, lod_enable_mask & 0xFFFFFFFF, order_mode
-        cfg.transmittance_eps = transmittance_eps
-        cfg.shard_index, cfg.shard_count, cfg.shard_mode = _shard_args(shard)
-        cfg.out_format = out_format & 0xFFFFFFFF
+        self._set_frame_modes(projection, antialias, atmosphere, tile_styles)
+        cam, sc, cfg = _frame_blocks(camera, scene, culling_dist, lod_enable_mask, order_mode, transmittance_eps, shard, out_format)
         ticket = C.c_int(-1)
         self._check(self._lib.gswt_render_async_pick(self._h, cam, sc, C.byref(cfg), width, height,
                                                      C.c_void_p(bg_rgba_ptr) if bg_rgba_ptr else None,
@@ -440,16 +441,14 @@ class GSWTRenderer:
         return int(self._lib.gswt_shard_cols_padded(width, shard_count))
 
     def unshard_mode(self, gathered_device_ptr: int, width: int, height: int, shard_count: int, mode, out_device_ptr: int):
-        m = L.GSWT_SHARD_COLUMNS if mode in ("cols", "columns", L.GSWT_SHARD_COLUMNS) and mode != 0 else L.GSWT_SHARD_ROWS
-        self._check(self._lib.gswt_unshard_mode(self._h, C.c_void_p(gathered_device_ptr), width, height, shard_count, m,
+        self._check(self._lib.gswt_unshard_mode(self._h, C.c_void_p(gathered_device_ptr), width, height, shard_count, _shard_mode(mode),
                                                 C.c_void_p(out_device_ptr)))
 
     def unshard_format(self, gathered_device_ptr: int, width: int, height: int, shard_count: int, mode, out_format: int,
                        out_device_ptr: int):
         """unshard_mode for any output format (GSWT_OUT_*: 16- or 4-byte pixels; GSWT_VIDEO_*: every gathered shard is a complete
         image of planes, the frame is reassembled plane by plane)."""
-        m = L.GSWT_SHARD_COLUMNS if mode in ("cols", "columns", L.GSWT_SHARD_COLUMNS) and mode != 0 else L.GSWT_SHARD_ROWS
-        self._check(self._lib.gswt_unshard_format(self._h, C.c_void_p(gathered_device_ptr), width, height, shard_count, m, out_format,
+        self._check(self._lib.gswt_unshard_format(self._h, C.c_void_p(gathered_device_ptr), width, height, shard_count, _shard_mode(mode), out_format,
                                                   C.c_void_p(out_device_ptr)))
 
     def unshard(self, gathered_device_ptr: int, width: int, height: int, shard_count: int, out_device_ptr: int):

@@ -6,7 +6,6 @@ perspective, tests/ortho_ref.py's under the orthographic cameras); image, depth 
 own filtered records; a known-answer minification; the same bits through graphs, frames in flight, compositor and cull variants, a
 pair-buffer overflow, output formats and shards (column bands included: their cull must know the filter); the option off leaves
 every output as it was; the refusals."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -14,17 +13,12 @@ import pytest
 
 from gswt_renderer_amd import _lib as L
 from gswt_renderer_amd import ortho
-from gswt_renderer_amd.renderer import PICK_DTYPE, GSWTError, GSWTRenderer
+from gswt_renderer_amd.renderer import GSWTError
 from oracle import gswt_oracle as orc
 from tests import antialias_ref as AA
-from tests import depth_ref as DR
+from tests import frame_modes as FM
 from tests import ortho_ref as OR
-from tests import pick_ref as PR
 from tests import special_splats as S
-from tests import unorm8_ref as U8
-from tests import yuv_ref as YUV
-from tests.test_depth_out_gpu import TOL, ZTOL, _check_against_ref
-from tests.test_ortho_gpu import _bind, _bits_equal, _cam, _persp, _same
 
 pytestmark = pytest.mark.gpu
 W, Hh = OR.W, OR.H
@@ -35,42 +29,12 @@ VALUES = (102, 307, 2048)
 
 @pytest.fixture(autouse=True)
 def _defaults(renderer):
-    """Every test leaves the shared context as it found it: perspective, no filter, default options."""
     yield
-    for key, value in ((AA_OPT, 0), (L.GSWT_OPT_PROJECTION, PERSP), (L.GSWT_OPT_STRICT_VS, 1), (L.GSWT_OPT_GRAPH, 0), (L.GSWT_OPT_TIMING, 2),
-                       (L.GSWT_OPT_SEGMENT, L.GSWT_DEFAULT_SEGMENT), (L.GSWT_OPT_COMPOSITE, 0), (L.GSWT_OPT_NO_CHUNK_CULL, 0),
-                       (L.GSWT_OPT_ITEM_ORDER, 0), (L.GSWT_OPT_PAIR_CAP, 0), (L.GSWT_OPT_DEBUG_VARYINGS, 0), (L.GSWT_OPT_NO_LOD_PREFILTER, 0)):
-        renderer.set_option(key, value)
-    renderer.configure(None)
+    FM.restore_defaults(renderer)
 
 
 def _varyings(renderer, cu, su, projection, value):
-    renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-    try:
-        renderer.render(cu, su, W, Hh, projection=projection, antialias=value / 1024.0)
-        return renderer.read_projected().view(orc.SPLAT_DTYPE)
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
-
-
-_UNFILTERED = {}
-
-
-def _view(name, cam, splat_scale=OR.SPLAT_SCALE):
-    """(golden case, camera block, scene block, projection, UNFILTERED reference records) of case `name` under camera `cam`: "persp"
-    (the oracle's vertex stage) or one of OR.CAMERAS (tests/ortho_ref.py's restatement, plane case only); computed once."""
-    k = (name, cam, splat_scale)
-    if k not in _UNFILTERED:
-        g = OR.golden(name)
-        if cam == "persp":
-            cu, su = _persp(g), OR.scene_of(g, splat_scale)
-            sp = orc.project_draws(orc.Camera176.from_buffer_copy(bytes(cu)), su, g["pp"].tex, g["draws"], height_map=g["hm"])
-            _UNFILTERED[k] = (g, cu, su, PERSP, sp)
-        else:
-            assert name == "case_plane"
-            _, su, sp = OR.plane_records(cam, splat_scale)
-            _UNFILTERED[k] = (g, _cam(cam, g).uniforms(), su, ORTHO, sp)
-    return _UNFILTERED[k]
+    return FM.varyings(renderer, cu, su, projection=projection, antialias=value / 1024.0)[0]
 
 
 def _check_filtered(got, unf, value, splat_scale, label):
@@ -81,8 +45,8 @@ def _check_filtered(got, unf, value, splat_scale, label):
     assert not (vis_u & ~vis_g).any(), label                              # the visible set can only grow
     assert n_masked <= 0.01 * vis_u.sum(), (label, n_masked)
     both = vis_u & vis_g
-    assert _bits_equal(got["ndc"][both], unf["ndc"][both]) and _bits_equal(got["depth"][both], unf["depth"][both]), label
-    assert _bits_equal(np.ascontiguousarray(got["rgba"][both][:, :3]), np.ascontiguousarray(unf["rgba"][both][:, :3])), label
+    assert FM.bits_equal(got["ndc"][both], unf["ndc"][both]) and FM.bits_equal(got["depth"][both], unf["depth"][both]), label
+    assert FM.bits_equal(np.ascontiguousarray(got["rgba"][both][:, :3]), np.ascontiguousarray(unf["rgba"][both][:, :3])), label
     ok = both & ~masked
     gm, gn = got["major"][ok].astype(np.float64), got["minor"][ok].astype(np.float64)
     lm, ln = np.hypot(gm[:, 0], gm[:, 1]), np.hypot(gn[:, 0], gn[:, 1])
@@ -103,8 +67,8 @@ def _check_filtered(got, unf, value, splat_scale, label):
 @pytest.mark.parametrize("name,cam", [("case_plane", "persp"), ("case_plane", "top"), ("case_plane", "oblique"), ("case_hmap", "persp"),
                                       ("case_sphere", "persp")])
 def test_filtered_varyings(renderer, name, cam, value):
-    g, cu, su, proj, unf = _view(name, cam)
-    _bind(renderer, g)
+    g, cu, su, proj, unf = FM.view(name, cam)
+    FM.bind(renderer, g)
     got = _varyings(renderer, cu, su, proj, value)
     assert _check_filtered(got, unf, value, OR.SPLAT_SCALE, f"{name} {cam} value {value}") > 100
 
@@ -114,16 +78,16 @@ def test_s_carries_the_square_of_splat_scale(renderer):
     times as large at 12), while the unfiltered axes do not depend on splat_scale at all."""
     recs = {}
     for scale in (12.0, 24.0):
-        g, cu, su, proj, unf = _view("case_plane", "oblique", scale)
-        _bind(renderer, g)
+        g, cu, su, proj, unf = FM.view("case_plane", "oblique", scale)
+        FM.bind(renderer, g)
         recs[scale] = _varyings(renderer, cu, su, proj, 307)
         _check_filtered(recs[scale], unf, 307, scale, f"oblique scale {scale}")
         seen = unf["visible"] == 1
-        assert _bits_equal(_varyings(renderer, cu, su, proj, 0)["major"][seen], unf["major"][seen])
+        assert FM.bits_equal(_varyings(renderer, cu, su, proj, 0)["major"][seen], unf["major"][seen])
     vis = (recs[12.0]["visible"] == 1) & (recs[24.0]["visible"] == 1)
     l12, l24 = (np.hypot(*recs[k]["minor"][vis].astype(np.float64).T) for k in (12.0, 24.0))
     assert (l12 > l24).all()
-    unf = _view("case_plane", "oblique", 12.0)[4]
+    unf = FM.view("case_plane", "oblique", 12.0)[4]
     s12, s24 = float(AA.aa_s(307, 12.0)), float(AA.aa_s(307, 24.0))
     assert s12 == 4.0 * s24
     # |minor|^2 / 2 - l2 is s: the ratio of the two increments is 4 to rounding of the small differences
@@ -134,28 +98,11 @@ def test_s_carries_the_square_of_splat_scale(renderer):
 
 # ---- 2. image, depth and pick over the GPU's own filtered records ------------------------------------------------------------------------
 def _image_case(renderer, cam, order_mode, bg, splat_scale, value=307):
-    g, cu, su, proj, _ = _view("case_plane", cam, splat_scale)
-    _bind(renderer, g)
-    sp = _varyings(renderer, cu, su, proj, value)
-    bgc, bgd = DR.bg_images(W, Hh) if bg else (None, None)
-    kw = dict(order_mode=order_mode, bg_rgba=bgc, bg_depth=bgd)
-    img, z, pick = renderer.render(cu, su, W, Hh, projection=proj, depth=True, pick=True, **kw)      # (the context keeps `value`)
-    t = renderer.timings()
-    assert z.shape == (Hh, W) and pick.shape == (Hh, W) and pick.dtype == PICK_DTYPE
-    ref_img, ref_z, n_cover = DR.composite(sp, W, Hh, splat_scale=splat_scale, with_cover=True, **kw)
-    assert (n_cover > 0).mean() > 0.5 and ref_img[..., 3].max() > 0.5
-    dz = _check_against_ref(img, z, ref_img, ref_z)
-    ev = PR.composite(sp, W, Hh, splat_scale=splat_scale, **kw)
-    mi, en = PR.identities(g["draws"])
-    label = f"antialias {value} {cam} order={order_mode} bg={bg} scale={splat_scale}"
-    dw = PR.check_pick(pick, ev, sp, mi, en, label=label)
-    print(f"{label}: visible {t['n_visible']} pairs {t['n_pairs']} max|dz| {dz:.3e} max|dw| {dw:.3e}")
-    assert t["n_visible"] == int((sp["visible"] == 1).sum())
-    assert _same(img, renderer.render(cu, su, W, Hh, projection=proj, **kw))
+    c = FM.image_case(renderer, cam, order_mode, bg, splat_scale, dict(antialias=value / 1024.0), f"antialias {value}", min_cover=0.5)
     # ... and it is not the unfiltered frame
-    off = renderer.render(cu, su, W, Hh, projection=proj, antialias=0.0, **kw)
-    assert not _same(img, off) and renderer.timings()["n_pairs"] <= t["n_pairs"]
-    return t
+    off = c["again"](antialias=0.0)
+    assert not FM.same(c["img"], off) and renderer.timings()["n_pairs"] <= c["t"]["n_pairs"]
+    return c["t"]
 
 
 @pytest.mark.parametrize("bg", [False, True], ids=["clear", "bg"])
@@ -182,7 +129,7 @@ def test_known_answer_minification(renderer):
     """Five isolated opaque splats under a top_down camera of 4 px per world unit, world variances 0.002 (x) and 0.003 (y) -- on-screen
     0.032 and 0.048 px^2, a footprint of about one pixel --, clear background, splat_scale 1.  A splat's summed output alpha over its
     neighbourhood is its integrated opacity; the analytic value is antialias_ref.analytic_mass of cov2d's eigenvalues, 16 x the stored
-    (binary16) covariance entries.  With value = 512 every sum is within antialias_ref.lattice_bound (4.3 % here) of it, plus TOL per
+    (binary16) covariance entries.  With value = 512 every sum is within antialias_ref.lattice_bound (4.3 % here) of it, plus FM.TOL per
     covered pixel; with value = 0 it depends on the sub-pixel position of the centre: 4.1 x at a pixel centre, nothing at a corner.
     (The splats are longer in y than in x: tests/test_ortho_gpu.py's height-field test explains why.)"""
     z_top, z_bottom = 3.0, -1.0
@@ -224,129 +171,66 @@ def test_known_answer_minification(renderer):
     for k, ((m, n), (rm, rn)) in enumerate(zip(sums[512], ref_on)):
         print(f"splat {k}: filtered mass {m:.6f} over {n} px (float64 lattice {rm:.6f} over {rn}), analytic {want:.6f}, ratio {m / want:.4f} "
               f"(bound {bound:.4f}); unfiltered {sums[0][k][0]:.6f} (float64 {ref_off[k]:.6f}), ratio {sums[0][k][0] / want:.3f}")
-        assert n > 0 and abs(m - want) <= bound * want + TOL * n
-        assert abs(m - rm) <= TOL * max(n, rn)
+        assert n > 0 and abs(m - want) <= bound * want + FM.TOL * n
+        assert abs(m - rm) <= FM.TOL * max(n, rn)
     assert sum(1 for m, _ in sums[0] if not 0.5 <= m / want <= 2.0) >= 2
     assert renderer.timings()["n_visible"] == len(px)
 
 
 # ---- 4. the same bits every way ---------------------------------------------------------------------------------------------------------
+def _set_value(renderer, value):
+    renderer.set_option(AA_OPT, value)
+
+
+MODE = FM.Mode({value: (None, dict(antialias=value / 1024.0)) for value in (0, 102, 307, 2048)}, _set_value, on=307)
+
+
 @pytest.fixture()
 def plain(renderer):
     """The plane case bound under its perspective camera, depth order over a background, and the plain synchronous frames (colour,
     depth, pick) at each filter value."""
-    g, cu, su, proj, _ = _view("case_plane", "persp")
-    _bind(renderer, g)
-    bgc, bgd = DR.bg_images(W, Hh)
-    kw = dict(order_mode=L.GSWT_ORDER_DEPTH, bg_rgba=bgc, bg_depth=bgd)
-    frames, pairs = {}, {}
-    for value in (0, 102, 307, 2048):
-        frames[value] = renderer.render(cu, su, W, Hh, projection=PERSP, antialias=value / 1024.0, depth=True, pick=True, **kw)
-        pairs[value] = renderer.timings()["n_pairs"]
+    g, cu, su, proj, _ = FM.view("case_plane", "persp")
+    s = FM.plain_frames(renderer, MODE, g, su, cu)
     renderer.set_option(AA_OPT, 0)
+    frames, pairs = s["frames"], s["pairs"]
     assert len({bytes(np.ascontiguousarray(f[0])) for f in frames.values()}) == 4
     assert pairs[0] <= pairs[102] <= pairs[307] <= pairs[2048] and pairs[2048] > pairs[0]
-    return dict(g=g, cu=cu, su=su, kw=kw, bgc=bgc, bgd=bgd, frames=frames, pairs=pairs)
-
-
-def _device_frames(renderer, s, seq, *, waves, then=None):
-    """Submits frames at the filter values in `seq` with render_async, `waves` at a time in flight, into buffers of their own; sets the
-    option to `then` before waiting; returns (colour, depth, pick) as numpy arrays."""
-    import torch
-    bgc, bgd = torch.from_numpy(s["bgc"]).cuda(), torch.from_numpy(s["bgd"]).cuda()
-    outs = [(torch.zeros((Hh, W, 4), dtype=torch.float32, device="cuda"), torch.full((Hh, W), -1.0, dtype=torch.float32, device="cuda"),
-             torch.full((Hh, W, 4), -1, dtype=torch.int32, device="cuda")) for _ in seq]
-    torch.cuda.synchronize()
-    for i in range(0, len(seq), waves):
-        tickets = []
-        for value, (o, z, p) in zip(seq[i:i + waves], outs[i:i + waves]):
-            tickets.append(renderer.render_async(s["cu"], s["su"], W, Hh, o.data_ptr(), order_mode=L.GSWT_ORDER_DEPTH, bg_rgba_ptr=bgc.data_ptr(),
-                                                 bg_depth_ptr=bgd.data_ptr(), out_depth_ptr=z.data_ptr(), out_pick_ptr=p.data_ptr(),
-                                                 antialias=value / 1024.0))
-        assert len(set(tickets)) == len(tickets)
-        if then is not None:                                                 # must not reach the frames already submitted
-            renderer.set_option(AA_OPT, then)
-        for t in tickets:
-            renderer.render_wait(t)
-    torch.cuda.synchronize()
-    return [(o.cpu().numpy(), z.cpu().numpy(), p.cpu().numpy()) for o, z, p in outs]
-
-
-def _assert_frames(got, seq, s, what):
-    for k, (value, f) in enumerate(zip(seq, got)):
-        want = s["frames"][value]
-        assert _same(f[0], want[0]) and _same(f[1], want[1]) and _same(f[2], want[2]), (what, k, value)
+    return s
 
 
 def test_graph_replay_with_alternating_values(renderer, plain):
-    renderer.set_option(L.GSWT_OPT_TIMING, 0)
-    renderer.set_option(L.GSWT_OPT_GRAPH, 1)
-    launches0, _, updates0 = renderer.graph_stats()
     seq1 = [0, 307, 2048, 307, 0, 307]
-    _assert_frames(_device_frames(renderer, plain, seq1, waves=1), seq1, plain, "graph, one slot")
     seq2 = [307, 0, 2048, 307, 0, 2048]
-    _assert_frames(_device_frames(renderer, plain, seq2, waves=2), seq2, plain, "graph, two slots")
-    launches, _, updates = renderer.graph_stats()
-    assert launches - launches0 == len(seq1) + len(seq2)
-    assert updates - updates0 >= len(seq1) - 1                # a changed aa_s reaches the kernel nodes that take the frame constants
+    _, _, updates = FM.check_graph_replay(renderer, plain, MODE, seq1, seq2)
+    assert updates >= len(seq1) - 1                           # a changed aa_s reaches the kernel nodes that take the frame constants
 
 
 def test_async_frames_in_flight_keep_their_value(renderer, plain):
     assert renderer.frame_slots() >= 4
     seq = [307, 0, 2048, 102]                                 # four frames in flight, each with a value of its own
-    _assert_frames(_device_frames(renderer, plain, seq, waves=4, then=4096), seq, plain, "async")
+    FM.check_in_flight(renderer, plain, MODE, seq, waves=4, then=4096)
 
 
 @pytest.mark.parametrize("opt", [L.GSWT_OPT_COMPOSITE, L.GSWT_OPT_ITEM_ORDER, L.GSWT_OPT_NO_CHUNK_CULL], ids=["composite_dw", "item_order", "no_chunk_cull"])
 def test_compositor_and_cull_variants(renderer, plain, opt):
-    renderer.set_option(opt, 1)
-    got = renderer.render(plain["cu"], plain["su"], W, Hh, antialias=307 / 1024.0, depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], [307], plain, opt)
+    FM.check_compositor_and_cull_variant(renderer, plain, MODE, opt, [MODE.on])
 
 
 def test_pair_buffer_overflow_rerun_keeps_the_value(renderer, plain):
-    assert plain["pairs"][307] > 256
-    renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)             # the next frame overflows and is re-run with grown buffers
-    got = renderer.render(plain["cu"], plain["su"], W, Hh, antialias=307 / 1024.0, depth=True, pick=True, **plain["kw"])
-    assert renderer.timings()["n_pairs"] == plain["pairs"][307]
-    _assert_frames([got], [307], plain, "overflow, synchronous")
-    # ... and in flight, with the option changed between submit and the wait that re-runs the frame
-    renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)
-    _assert_frames(_device_frames(renderer, plain, [307], waves=1, then=2048), [307], plain, "overflow, in flight")
-    assert renderer.timings()["n_pairs"] == plain["pairs"][307]
+    FM.check_overflow_rerun(renderer, plain, MODE, MODE.on, then=2048)
 
 
 def test_output_formats(renderer, plain):
-    f32 = plain["frames"][307][0]
-    kw = dict(antialias=307 / 1024.0, **plain["kw"])
-    assert np.array_equal(renderer.render(plain["cu"], plain["su"], W, Hh, out_format=L.GSWT_OUT_RGBA8_UNORM, **kw), U8.rgba8(f32))
-    y, cbcr = renderer.render(plain["cu"], plain["su"], W, Hh, out_format=L.GSWT_VIDEO_NV12, **kw)
-    wy, wc = YUV.nv12(f32)
-    assert np.array_equal(y, wy) and np.array_equal(cbcr, wc)
+    FM.check_output_formats(renderer, plain, MODE, [MODE.on])
 
 
 # ---- 5. shards -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [2, 3])
 @pytest.mark.parametrize("cam", ["persp", "top"])
 def test_row_shards_tile_the_frame(renderer, cam, n):
-    g, cu, su, proj, _ = _view("case_plane", cam)
-    _bind(renderer, g)
-    bgc, bgd = DR.bg_images(W, Hh)
-    kw = dict(order_mode=L.GSWT_ORDER_DEPTH, bg_rgba=bgc, bg_depth=bgd, projection=proj, antialias=307 / 1024.0, depth=True, pick=True)
-    full = renderer.render(cu, su, W, Hh, **kw)
-    rows = renderer.shard_rows_padded(Hh, n)
-    parts = [np.zeros((Hh, W, 4), np.float32), np.zeros((Hh, W), np.float32), np.zeros((Hh, W), PICK_DTYPE)]
-    for r in range(n):
-        got = renderer.render(cu, su, W, Hh, shard=(r, n), **kw)
-        assert got[0].shape == (rows, W, 4)
-        k = 0
-        for ty in range(r, (Hh + 15) // 16, n):
-            y0, y1 = ty * 16, min(Hh, ty * 16 + 16)
-            for dst, src in zip(parts, got):
-                dst[y0:y1] = src[k * 16:k * 16 + (y1 - y0)]
-            k += 1
-    for a, b in zip(parts, full):
-        assert _same(a, b), (cam, n)
+    g, cu, su, proj, _ = FM.view("case_plane", cam)
+    mode = FM.Mode({307: (None, dict(projection=proj, antialias=307 / 1024.0))}, _set_value)
+    FM.check_row_shards(renderer, FM.plain_frames(renderer, mode, g, su, cu), mode, n, [307])
 
 
 BAND_SPLAT_SCALE = 0.15
@@ -361,24 +245,20 @@ def test_column_bands_unite_to_the_frame(renderer, value, n):
     a build without that term, this scene, scales 0.05 .. 0.25: at 4096 the union of two and of five bands differs from the unsharded
     frame in one to four pixels (summed n_visible 306 against 336 with the term at two bands); at 2048 its 2 px pad still covers the
     4 px, and at scales of 0.5 and more every case passes without the term.  The 4096 cases are what pins the term."""
-    g, cu, su, proj, _ = _view("case_plane", "persp", BAND_SPLAT_SCALE)
-    _bind(renderer, g)
+    g, cu, su, proj, _ = FM.view("case_plane", "persp", BAND_SPLAT_SCALE)
+    FM.bind(renderer, g)
     kw = dict(order_mode=L.GSWT_ORDER_DEPTH, projection=PERSP, antialias=value / 1024.0, depth=True, pick=True)
     full = renderer.render(cu, su, W, Hh, **kw)
     n_vis = renderer.timings()["n_visible"]
     assert n_vis > 150 and (full[0][..., 3] > 0).mean() > 0.2
     bw = renderer.shard_cols_padded(W, n)
-    parts = [np.zeros((Hh, W, 4), np.float32), np.zeros((Hh, W), np.float32), np.zeros((Hh, W), PICK_DTYPE)]
-    total = 0
+    parts, total = [], 0
     for r in range(n):
-        got = renderer.render(cu, su, W, Hh, shard=(r, n, "cols"), **kw)
+        parts.append(renderer.render(cu, su, W, Hh, shard=(r, n, "cols"), **kw))
         total += renderer.timings()["n_visible"]
-        x0, x1 = r * bw, min(W, (r + 1) * bw)
-        assert got[0].shape == (Hh, bw, 4)
-        for dst, src in zip(parts, got):
-            dst[:, x0:x1] = src[:, :x1 - x0]
-    for a, b in zip(parts, full):
-        assert _same(a, b), (value, n)
+        assert parts[r][0].shape == (Hh, bw, 4)
+    for a, b in zip(FM.assemble_column_bands(parts, W, bw), full):
+        assert FM.same(a, b), (value, n)
     print(f"{n} column bands at value {value}: visible {total} summed over the bands, {n_vis} unsharded")
     assert total < n * n_vis                                  # the band cull did engage
 
@@ -386,49 +266,21 @@ def test_column_bands_unite_to_the_frame(renderer, value, n):
 # ---- 6. off is untouched ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cam", ["persp", "oblique"])
 def test_off_is_untouched(cam):
-    """A context on which the option was never set, then frames at 307, then 0 again: byte-identical colour, depth, pick and counts."""
-    g, cu, su, proj, unf = _view("case_plane", cam)
-    r = GSWTRenderer(0)
-    try:
-        _bind(r, g)
-        bgc, bgd = DR.bg_images(W, Hh)
-        kw = dict(order_mode=L.GSWT_ORDER_DEPTH, bg_rgba=bgc, bg_depth=bgd, projection=proj, depth=True, pick=True)
-        before = r.render(cu, su, W, Hh, **kw)
-        t0 = r.timings()
-        on = r.render(cu, su, W, Hh, antialias=307 / 1024.0, **kw)
-        r.render(cu, su, W, Hh, **kw)                          # (no argument: the context keeps 307)
-        assert _same(r.render(cu, su, W, Hh, **kw)[0], on[0]) and not _same(on[0], before[0])
-        after = r.render(cu, su, W, Hh, antialias=0.0, **kw)
-        t1 = r.timings()
-        for a, b in zip(before, after):
-            assert _same(a, b)
-        assert (t0["n_visible"], t0["n_pairs"]) == (t1["n_visible"], t1["n_pairs"])
-        assert (before[2]["weight"] > 0).mean() > 0.3
-        # ... and the unfiltered vertex stage is still the reference's, bit for bit
-        r.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-        r.render(cu, su, W, Hh, projection=proj)
-        got = r.read_projected().view(orc.SPLAT_DTYPE)
-        vis = unf["visible"] == 1
-        for fld in ("ndc", "depth", "major", "minor", "rgba"):
-            assert _bits_equal(got[fld][vis], unf[fld][vis]), fld
-    finally:
-        r.close()
+    """A context on which the option was never set, then frames at 307, then 0 again: byte-identical colour, depth, pick and counts,
+    and the unfiltered vertex stage is still the reference's, bit for bit."""
+    FM.check_off_is_untouched(cam, dict(antialias=307 / 1024.0), [("0", lambda r: dict(antialias=0.0))])
 
 
 # ---- 7. refusals --------------------------------------------------------------------------------------------------------------------------
 def test_refusals(renderer, plain):
-    import torch
     lib, h = renderer._lib, renderer._h
-    cam = (C.c_char * 176).from_buffer_copy(bytes(plain["cu"]))
 
     def scene(splat_scale=None):
         su = orc.Scene160.from_buffer_copy(bytes(plain["su"]))
         if splat_scale is not None:
             su.splat_scale = splat_scale
-        return (C.c_char * 160).from_buffer_copy(bytes(su))
+        return su
 
-    cfg = L.RenderConfig()
-    cfg.culling_dist, cfg.lod_enable_mask, cfg.order_mode = 1.0, 0xFFFFFFFF, L.GSWT_ORDER_DEPTH
     # option values: refused, and the value in force stays
     renderer.set_option(AA_OPT, 307)
     for bad in (-1, 4097):
@@ -437,7 +289,7 @@ def test_refusals(renderer, plain):
     with pytest.raises(GSWTError):
         renderer.render(plain["cu"], plain["su"], W, Hh, antialias=4.5)
     got = renderer.render(plain["cu"], plain["su"], W, Hh, depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], [307], plain, "after refused option values")
+    FM.assert_frames([got], [307], plain, "after refused option values")
     for ok in (1, 4096):
         assert lib.gswt_set_option(h, AA_OPT, ok) == L.GSWT_OK
     renderer.set_option(AA_OPT, 307)
@@ -449,39 +301,18 @@ def test_refusals(renderer, plain):
              # finite, but s = 4 v / splat_scale^2 is not a finite positive binary32 number: the square overflows (s = 0) or underflows (s = inf)
              ("splat_scale 1e20", scene(1e20), None, b"splat_scale"),
              ("splat_scale 1e-20", scene(1e-20), None, b"splat_scale")]
-    out = np.full((Hh, W, 4), 7.0, np.float32)
-    z = np.full((Hh, W), -1.0, np.float32)
-    pk = np.full((Hh, W, 4), 0x55555555, np.uint32)
-    o_d = torch.full((Hh, W, 4), 7.0, dtype=torch.float32, device="cuda")
-    z_d = torch.full((Hh, W), -1.0, dtype=torch.float32, device="cuda")
-    p_d = torch.full((Hh, W, 4), 0x55555555, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    for what, sc, opt, word in cases:
-        if opt:
-            renderer.set_option(*opt)
-        try:
-            assert lib.gswt_render_pick(h, cam, sc, C.byref(cfg), W, Hh, None, None, 0, vp(out), vp(z), vp(pk), 0) == L.GSWT_ERR_BAD_ARG, what
-            assert word in lib.gswt_last_error(h), (what, lib.gswt_last_error(h))
-            ticket = C.c_int(-7)
-            assert lib.gswt_render_async_pick(h, cam, sc, C.byref(cfg), W, Hh, None, None, C.c_void_p(o_d.data_ptr()), C.c_void_p(z_d.data_ptr()),
-                                              C.c_void_p(p_d.data_ptr()), C.byref(ticket)) == L.GSWT_ERR_BAD_ARG, what
-            assert ticket.value == -7
-        finally:
-            if opt:
-                renderer.set_option(opt[0], 1)
-        torch.cuda.synchronize()
-        assert (out == 7.0).all() and (z == -1.0).all() and (pk == 0x55555555).all(), what
-        assert bool((o_d == 7.0).all()) and bool((z_d == -1.0).all()) and bool((p_d == 0x55555555).all()), what
+    refused, rendered = FM.refusal_probe(renderer)
+    for what, su, opt, word in cases:
+        FM.check_refused(renderer, refused, *FM.frame_blocks(plain["cu"], su), (word,), what, opt=opt)
         # the next valid frame renders
         got = renderer.render(plain["cu"], plain["su"], W, Hh, depth=True, pick=True, **plain["kw"])
-        _assert_frames([got], [307], plain, "after " + what)
+        FM.assert_frames([got], [307], plain, "after " + what)
     # with the filter off neither is refused: sequence v2 runs, and a zero splat_scale draws nothing
     renderer.set_option(AA_OPT, 0)
     renderer.set_option(L.GSWT_OPT_STRICT_VS, 0)
     renderer.render(plain["cu"], plain["su"], W, Hh)
     renderer.set_option(L.GSWT_OPT_STRICT_VS, 1)
-    assert lib.gswt_render_pick(h, cam, scene(0.0), C.byref(cfg), W, Hh, None, None, 0, vp(out), vp(z), vp(pk), 0) == L.GSWT_OK
+    rendered(*FM.frame_blocks(plain["cu"], scene(0.0)))
 
 
 # ---- 8. through the frame harness -----------------------------------------------------------------------------------------------------------
@@ -498,8 +329,8 @@ def test_pipeline_passes_antialias_through(renderer):
     off = pipe.render(cu, W, Hh)
     pairs_off = renderer.timings()["n_pairs"]
     on = pipe.render(cu, W, Hh, antialias=307 / 1024.0)
-    assert renderer.timings()["n_pairs"] > pairs_off > 0 and not _same(on, off)
+    assert renderer.timings()["n_pairs"] > pairs_off > 0 and not FM.same(on, off)
     renderer.set_option(AA_OPT, 0)
-    assert _same(renderer.render(cu, pipe.wang.scene_uniforms(), W, Hh, antialias=307 / 1024.0), on)
-    assert _same(pipe.render(cu, W, Hh), on)                  # (no argument: the context keeps 307)
-    assert _same(pipe.render(cu, W, Hh, antialias=0.0), off)
+    assert FM.same(renderer.render(cu, pipe.wang.scene_uniforms(), W, Hh, antialias=307 / 1024.0), on)
+    assert FM.same(pipe.render(cu, W, Hh), on)                  # (no argument: the context keeps 307)
+    assert FM.same(pipe.render(cu, W, Hh, antialias=0.0), off)

@@ -15,18 +15,13 @@ import pytest
 
 from gswt_renderer_amd import _lib as L
 from gswt_renderer_amd import atmosphere as A
-from gswt_renderer_amd.renderer import PICK_DTYPE, GSWTError, GSWTRenderer
+from gswt_renderer_amd.renderer import GSWTError
 from oracle import gswt_oracle as orc
 from tests import atmosphere_ref as AR
-from tests import depth_ref as DR
+from tests import frame_modes as FM
 from tests import ortho_ref as OR
-from tests import pick_ref as PR
 from tests import proxy_raster_ref as R
 from tests import special_splats as S
-from tests import unorm8_ref as U8
-from tests import yuv_ref as YUV
-from tests.test_depth_out_gpu import _check_against_ref
-from tests.test_ortho_gpu import _bind, _bits_equal, _cam, _persp, _same
 
 pytestmark = pytest.mark.gpu
 W, Hh = OR.W, OR.H
@@ -41,43 +36,12 @@ AA = 307 / 1024.0
 
 @pytest.fixture(autouse=True)
 def _defaults(renderer):
-    """Every test leaves the shared context as it found it: no atmosphere, perspective, no filter, default options."""
     yield
-    renderer.set_atmosphere(A.OFF)
-    for key, value in ((L.GSWT_OPT_ANTIALIAS, 0), (L.GSWT_OPT_PROJECTION, PERSP), (L.GSWT_OPT_STRICT_VS, 1), (L.GSWT_OPT_GRAPH, 0), (L.GSWT_OPT_TIMING, 2),
-                       (L.GSWT_OPT_SEGMENT, L.GSWT_DEFAULT_SEGMENT), (L.GSWT_OPT_COMPOSITE, 0), (L.GSWT_OPT_NO_CHUNK_CULL, 0),
-                       (L.GSWT_OPT_ITEM_ORDER, 0), (L.GSWT_OPT_PAIR_CAP, 0), (L.GSWT_OPT_DEBUG_VARYINGS, 0), (L.GSWT_OPT_NO_LOD_PREFILTER, 0)):
-        renderer.set_option(key, value)
-    renderer.configure(None)
+    FM.restore_defaults(renderer)
 
 
 def _varyings(renderer, cu, su, projection, atm, antialias=0.0):
-    renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-    try:
-        renderer.render(cu, su, W, Hh, projection=projection, antialias=antialias, atmosphere=atm)
-        return renderer.read_projected().view(orc.SPLAT_DTYPE), renderer.timings()
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
-
-
-_VIEWS = {}
-
-
-def _view(name, cam, splat_scale=OR.SPLAT_SCALE):
-    """(golden case, camera block, scene block, projection, reference records WITHOUT atmosphere) of case `name` under camera `cam`:
-    "persp" (the oracle's vertex stage) or one of OR.CAMERAS (tests/ortho_ref.py's restatement, plane case only); computed once."""
-    k = (name, cam, splat_scale)
-    if k not in _VIEWS:
-        g = OR.golden(name)
-        if cam == "persp":
-            cu, su = _persp(g), OR.scene_of(g, splat_scale)
-            sp = orc.project_draws(orc.Camera176.from_buffer_copy(bytes(cu)), su, g["pp"].tex, g["draws"], height_map=g["hm"])
-            _VIEWS[k] = (g, cu, su, PERSP, sp)
-        else:
-            assert name == "case_plane"
-            _, su, sp = OR.plane_records(cam, splat_scale)
-            _VIEWS[k] = (g, _cam(cam, g).uniforms(), su, ORTHO, sp)
-    return _VIEWS[k]
+    return FM.varyings(renderer, cu, su, projection=projection, antialias=antialias, atmosphere=atm)
 
 
 def _block(cu):
@@ -86,14 +50,14 @@ def _block(cu):
 
 def _unchanged(got, base, m, fields, label):
     for fld in fields:
-        assert _bits_equal(np.ascontiguousarray(got[fld][m]), np.ascontiguousarray(base[fld][m])), (label, fld)
+        assert FM.bits_equal(np.ascontiguousarray(got[fld][m]), np.ascontiguousarray(base[fld][m])), (label, fld)
 
 
 # ---- 1. the fade, bit for bit --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cam", ["persp", "top", "oblique"])
 def test_fade_is_bit_exact_on_the_plain_surface(renderer, cam):
-    g, cu, su, proj, unf = _view("case_plane", cam)
-    _bind(renderer, g)
+    g, cu, su, proj, unf = FM.view("case_plane", cam)
+    FM.bind(renderer, g)
     p = AR.params(BLOCKS["fade"])
     dist = AR.dist_f32(_block(cu).cam_pos, su, g["pp"].tex, g["draws"])
     t, fs = AR.fade_f32(dist, p)
@@ -107,9 +71,9 @@ def test_fade_is_bit_exact_on_the_plain_surface(renderer, cam):
         assert np.array_equal(got["visible"] == 1, want_vis), (cam, label)
         assert tm["n_visible"] == int(want_vis.sum()) and 0 < want_vis.sum() < (base["visible"] == 1).sum()
         _unchanged(got, base, want_vis, ("ndc", "depth", "major", "minor"), (cam, label))
-        assert _bits_equal(np.ascontiguousarray(got["rgba"][want_vis][:, :3]), np.ascontiguousarray(base["rgba"][want_vis][:, :3])), (cam, label)
+        assert FM.bits_equal(np.ascontiguousarray(got["rgba"][want_vis][:, :3]), np.ascontiguousarray(base["rgba"][want_vis][:, :3])), (cam, label)
         alpha = (base["rgba"][:, 3].astype(F32) * fs).astype(F32)
-        assert _bits_equal(got["rgba"][want_vis][:, 3].copy(), alpha[want_vis]), (cam, label)
+        assert FM.bits_equal(got["rgba"][want_vis][:, 3].copy(), alpha[want_vis]), (cam, label)
         ramp = want_vis & (t < 1)
         assert ramp.sum() > 50 and (got["rgba"][ramp][:, 3] < base["rgba"][ramp][:, 3]).all()
         print(f"{cam} {label}: visible {int(want_vis.sum())} of {int((base['visible'] == 1).sum())}, {int(ramp.sum())} inside the ramp")
@@ -118,8 +82,8 @@ def test_fade_is_bit_exact_on_the_plain_surface(renderer, cam):
 # ---- 2. the fade on the surfaces ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["case_hmap", "case_sphere"])
 def test_fade_on_the_surfaces(renderer, name):
-    g, cu, su, proj, unf = _view(name, "persp")
-    _bind(renderer, g)
+    g, cu, su, proj, unf = FM.view(name, "persp")
+    FM.bind(renderer, g)
     cam = _block(cu)
     vis = unf["visible"] == 1
     dist, z = AR.dist_f64(cam, unf["ndc"][vis], unf["depth"][vis])
@@ -153,8 +117,8 @@ def test_fade_on_the_surfaces(renderer, name):
 # ---- 3. the fog's bytes ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["case_plane", "case_hmap", "case_sphere"])
 def test_fog_bytes(renderer, name):
-    g, cu, su, proj, unf = _view(name, "persp")
-    _bind(renderer, g)
+    g, cu, su, proj, unf = FM.view(name, "persp")
+    FM.bind(renderer, g)
     cam = _block(cu)
     vis = unf["visible"] == 1
     if name == "case_plane":
@@ -164,7 +128,7 @@ def test_fog_bytes(renderer, name):
     got, tm = _varyings(renderer, cu, su, proj, BLOCKS["fog"])
     assert np.array_equal(got["visible"] == 1, vis) and tm["n_visible"] == int(vis.sum())
     _unchanged(got, unf, vis, ("ndc", "depth", "major", "minor"), name)
-    assert _bits_equal(got["rgba"][vis][:, 3].copy(), unf["rgba"][vis][:, 3].copy()), name
+    assert FM.bits_equal(got["rgba"][vis][:, 3].copy(), unf["rgba"][vis][:, 3].copy()), name
     want, near_half = AR.fog_bytes(AR.fog_codes_f64(unf["rgba"][vis][:, :3], dist, AR.params(BLOCKS["fog"])))
     codes = got["rgba"][vis][:, :3].astype(np.float64) * 255.0
     have = np.rint(codes)
@@ -200,43 +164,26 @@ def test_known_answers(renderer):
     assert np.array_equal(base_bytes, np.array([[200, 100 + 20 * k, 50] for k in range(5)], np.float64))
     got, tm = _varyings(renderer, cu, su, PERSP, A.Atmosphere(fade=(5.0, 10.0)))
     assert list(got["visible"]) == [1, 1, 0, 1, 0] and tm["n_visible"] == 3
-    assert _bits_equal(got["rgba"][[0, 3]][:, 3].copy(), base["rgba"][[0, 3]][:, 3].copy())             # distances 5 and 2.5: t = 1
+    assert FM.bits_equal(got["rgba"][[0, 3]][:, 3].copy(), base["rgba"][[0, 3]][:, 3].copy())             # distances 5 and 2.5: t = 1
     assert got["rgba"][1, 3] == F32(0.5) * base["rgba"][1, 3]                                            # distance 7.5: exactly half
     assert np.array_equal(AR.bytes_of(got["rgba"][[0, 1, 3]]), base_bytes[[0, 1, 3]])                    # the fade leaves the colours alone
     # fog that begins behind every splat changes nothing; a saturated fog leaves the fog colour alone
     got, tm = _varyings(renderer, cu, su, PERSP, A.Atmosphere(fog=(0.15, 20.0, 0.9, FOG[3])))
     assert tm["n_visible"] == 5 and np.array_equal(AR.bytes_of(got["rgba"]), base_bytes)
-    assert _bits_equal(got["rgba"].copy(), base["rgba"].copy())
+    assert FM.bits_equal(got["rgba"].copy(), base["rgba"].copy())
     got, tm = _varyings(renderer, cu, su, PERSP, A.Atmosphere(fog=(1e6, 0.0, 1.0, FOG[3])))
     want = np.rint(255.0 * np.array(FOG[3], F32).astype(np.float64))
     assert tm["n_visible"] == 5 and (AR.bytes_of(got["rgba"]) == want[None, :]).all()
-    assert _bits_equal(got["rgba"][:, 3].copy(), base["rgba"][:, 3].copy())
+    assert FM.bits_equal(got["rgba"][:, 3].copy(), base["rgba"][:, 3].copy())
 
 
 # ---- 5. image, depth and pick over the GPU's own records ----------------------------------------------------------------------------------
 def _image_case(renderer, cam, order_mode, bg, splat_scale, atm=BLOCKS["both"]):
-    g, cu, su, proj, _ = _view("case_plane", cam, splat_scale)
-    _bind(renderer, g)
-    sp, _ = _varyings(renderer, cu, su, proj, atm)
-    bgc, bgd = DR.bg_images(W, Hh) if bg else (None, None)
-    kw = dict(order_mode=order_mode, bg_rgba=bgc, bg_depth=bgd)
-    img, z, pick = renderer.render(cu, su, W, Hh, projection=proj, depth=True, pick=True, **kw)          # (the context keeps the block)
-    t = renderer.timings()
-    assert z.shape == (Hh, W) and pick.shape == (Hh, W) and pick.dtype == PICK_DTYPE
-    ref_img, ref_z, n_cover = DR.composite(sp, W, Hh, splat_scale=splat_scale, with_cover=True, **kw)
-    assert (n_cover > 0).mean() > 0.3 and ref_img[..., 3].max() > 0.5
-    dz = _check_against_ref(img, z, ref_img, ref_z)
-    ev = PR.composite(sp, W, Hh, splat_scale=splat_scale, **kw)
-    mi, en = PR.identities(g["draws"])
-    label = f"atmosphere {cam} order={order_mode} bg={bg} scale={splat_scale}"
-    dw = PR.check_pick(pick, ev, sp, mi, en, label=label)
-    print(f"{label}: visible {t['n_visible']} pairs {t['n_pairs']} max|dz| {dz:.3e} max|dw| {dw:.3e}")
-    assert t["n_visible"] == int((sp["visible"] == 1).sum())
-    assert _same(img, renderer.render(cu, su, W, Hh, projection=proj, **kw))
+    c = FM.image_case(renderer, cam, order_mode, bg, splat_scale, dict(antialias=0.0, atmosphere=atm), "atmosphere")
     # ... it is not the frame without the atmosphere, and the fade did not add pairs
-    off = renderer.render(cu, su, W, Hh, projection=proj, atmosphere=A.OFF, **kw)
-    assert not _same(img, off) and renderer.timings()["n_pairs"] >= t["n_pairs"] > 0
-    return t
+    off = c["again"](atmosphere=A.OFF)
+    assert not FM.same(c["img"], off) and renderer.timings()["n_pairs"] >= c["t"]["n_pairs"] > 0
+    return c["t"]
 
 
 @pytest.mark.parametrize("bg", [False, True], ids=["clear", "bg"])
@@ -254,166 +201,72 @@ def test_image_depth_and_pick_with_several_segments_per_tile(renderer):
 
 
 # ---- 6. the same bits every way ------------------------------------------------------------------------------------------------------------
+def _set_block(renderer, name):
+    renderer.set_atmosphere(BLOCKS[name])
+
+
+MODE = FM.Mode({name: (None, dict(atmosphere=blk)) for name, blk in BLOCKS.items()}, _set_block, on="both")
+
+
 @pytest.fixture()
 def plain(renderer):
     """The plane case bound under its perspective camera, depth order over a background, and the plain synchronous frames (colour,
     depth, pick) under each block of BLOCKS."""
-    g, cu, su, proj, _ = _view("case_plane", "persp")
-    _bind(renderer, g)
-    bgc, bgd = DR.bg_images(W, Hh)
-    kw = dict(order_mode=L.GSWT_ORDER_DEPTH, bg_rgba=bgc, bg_depth=bgd)
-    frames, pairs = {}, {}
-    for name, blk in BLOCKS.items():
-        frames[name] = renderer.render(cu, su, W, Hh, projection=PERSP, atmosphere=blk, depth=True, pick=True, **kw)
-        pairs[name] = renderer.timings()["n_pairs"]
+    g, cu, su, proj, _ = FM.view("case_plane", "persp")
+    s = FM.plain_frames(renderer, MODE, g, su, cu)
     renderer.set_atmosphere(A.OFF)
-    assert len({bytes(np.ascontiguousarray(f[0])) for f in frames.values()}) == len(BLOCKS)
+    pairs = s["pairs"]
+    assert len({bytes(np.ascontiguousarray(f[0])) for f in s["frames"].values()}) == len(BLOCKS)
     assert pairs["fog"] == pairs["off"] and pairs["both"] == pairs["fade"] < pairs["off"] and pairs["near"] < pairs["fade"]
-    return dict(g=g, cu=cu, su=su, kw=kw, bgc=bgc, bgd=bgd, frames=frames, pairs=pairs)
-
-
-def _device_frames(renderer, s, seq, *, waves, then=None):
-    """Submits frames under the blocks named in `seq` with render_async, `waves` at a time in flight, into buffers of their own; sets
-    the context's block to `then` before waiting; returns (colour, depth, pick) as numpy arrays."""
-    import torch
-    bgc, bgd = torch.from_numpy(s["bgc"]).cuda(), torch.from_numpy(s["bgd"]).cuda()
-    outs = [(torch.zeros((Hh, W, 4), dtype=torch.float32, device="cuda"), torch.full((Hh, W), -1.0, dtype=torch.float32, device="cuda"),
-             torch.full((Hh, W, 4), -1, dtype=torch.int32, device="cuda")) for _ in seq]
-    torch.cuda.synchronize()
-    for i in range(0, len(seq), waves):
-        tickets = []
-        for name, (o, z, p) in zip(seq[i:i + waves], outs[i:i + waves]):
-            tickets.append(renderer.render_async(s["cu"], s["su"], W, Hh, o.data_ptr(), order_mode=L.GSWT_ORDER_DEPTH, bg_rgba_ptr=bgc.data_ptr(),
-                                                 bg_depth_ptr=bgd.data_ptr(), out_depth_ptr=z.data_ptr(), out_pick_ptr=p.data_ptr(),
-                                                 atmosphere=BLOCKS[name]))
-        assert len(set(tickets)) == len(tickets)
-        if then is not None:                                                 # must not reach the frames already submitted
-            renderer.set_atmosphere(BLOCKS[then])
-        for t in tickets:
-            renderer.render_wait(t)
-    torch.cuda.synchronize()
-    return [(o.cpu().numpy(), z.cpu().numpy(), p.cpu().numpy()) for o, z, p in outs]
-
-
-def _assert_frames(got, seq, s, what):
-    for k, (name, f) in enumerate(zip(seq, got)):
-        want = s["frames"][name]
-        assert _same(f[0], want[0]) and _same(f[1], want[1]) and _same(f[2], want[2]), (what, k, name)
+    return s
 
 
 def test_graph_replay_with_alternating_blocks(renderer, plain):
-    renderer.set_option(L.GSWT_OPT_TIMING, 0)
-    renderer.set_option(L.GSWT_OPT_GRAPH, 1)
-    launches0, _, _ = renderer.graph_stats()
     seq1 = ["off", "both", "fade", "both", "off", "fog"]
-    _assert_frames(_device_frames(renderer, plain, seq1, waves=1), seq1, plain, "graph, one slot")
     seq2 = ["both", "off", "near", "fog", "off", "fade"]
-    _assert_frames(_device_frames(renderer, plain, seq2, waves=2), seq2, plain, "graph, two slots")
-    launches, _, _ = renderer.graph_stats()
-    assert launches - launches0 == len(seq1) + len(seq2)
+    FM.check_graph_replay(renderer, plain, MODE, seq1, seq2)
 
 
 def test_async_frames_in_flight_keep_their_block(renderer, plain):
     assert renderer.frame_slots() >= 4
     seq = ["both", "off", "near", "fade"]                      # four frames in flight, each with a block of its own
-    _assert_frames(_device_frames(renderer, plain, seq, waves=4, then="fog"), seq, plain, "async")
+    FM.check_in_flight(renderer, plain, MODE, seq, waves=4, then="fog")
 
 
 @pytest.mark.parametrize("opt", [L.GSWT_OPT_COMPOSITE, L.GSWT_OPT_ITEM_ORDER, L.GSWT_OPT_NO_CHUNK_CULL], ids=["composite_dw", "item_order", "no_chunk_cull"])
 def test_compositor_and_cull_variants(renderer, plain, opt):
-    renderer.set_option(opt, 1)
-    got = renderer.render(plain["cu"], plain["su"], W, Hh, atmosphere=BLOCKS["both"], depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], ["both"], plain, opt)
+    FM.check_compositor_and_cull_variant(renderer, plain, MODE, opt, [MODE.on])
 
 
 def test_pair_buffer_overflow_rerun_keeps_the_block(renderer, plain):
-    assert plain["pairs"]["both"] > 256
-    renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)             # the next frame overflows and is re-run with grown buffers
-    got = renderer.render(plain["cu"], plain["su"], W, Hh, atmosphere=BLOCKS["both"], depth=True, pick=True, **plain["kw"])
-    assert renderer.timings()["n_pairs"] == plain["pairs"]["both"]
-    _assert_frames([got], ["both"], plain, "overflow, synchronous")
-    # ... and in flight, with the block changed between submit and the wait that re-runs the frame
-    renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)
-    _assert_frames(_device_frames(renderer, plain, ["both"], waves=1, then="near"), ["both"], plain, "overflow, in flight")
-    assert renderer.timings()["n_pairs"] == plain["pairs"]["both"]
+    FM.check_overflow_rerun(renderer, plain, MODE, MODE.on, then="near")
 
 
 def test_output_formats(renderer, plain):
-    f32 = plain["frames"]["both"][0]
-    kw = dict(atmosphere=BLOCKS["both"], **plain["kw"])
-    assert np.array_equal(renderer.render(plain["cu"], plain["su"], W, Hh, out_format=L.GSWT_OUT_RGBA8_UNORM, **kw), U8.rgba8(f32))
-    y, cbcr = renderer.render(plain["cu"], plain["su"], W, Hh, out_format=L.GSWT_VIDEO_NV12, **kw)
-    wy, wc = YUV.nv12(f32)
-    assert np.array_equal(y, wy) and np.array_equal(cbcr, wc)
+    FM.check_output_formats(renderer, plain, MODE, [MODE.on])
 
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_row_shards_tile_the_frame(renderer, plain, n):
-    kw = dict(atmosphere=BLOCKS["both"], depth=True, pick=True, **plain["kw"])
-    full = plain["frames"]["both"]
-    rows = renderer.shard_rows_padded(Hh, n)
-    parts = [np.zeros((Hh, W, 4), np.float32), np.zeros((Hh, W), np.float32), np.zeros((Hh, W), PICK_DTYPE)]
-    for r in range(n):
-        got = renderer.render(plain["cu"], plain["su"], W, Hh, shard=(r, n), **kw)
-        assert got[0].shape == (rows, W, 4)
-        k = 0
-        for ty in range(r, (Hh + 15) // 16, n):
-            y0, y1 = ty * 16, min(Hh, ty * 16 + 16)
-            for dst, src in zip(parts, got):
-                dst[y0:y1] = src[k * 16:k * 16 + (y1 - y0)]
-            k += 1
-    for a, b in zip(parts, full):
-        assert _same(a, b), n
+    FM.check_row_shards(renderer, plain, MODE, n, [MODE.on])
 
 
 @pytest.mark.parametrize("n", [2, 3, 5])
 def test_column_bands_unite_to_the_frame(renderer, plain, n):
-    kw = dict(atmosphere=BLOCKS["both"], depth=True, pick=True, **plain["kw"])
-    full = plain["frames"]["both"]
-    bw = renderer.shard_cols_padded(W, n)
-    parts = [np.zeros((Hh, W, 4), np.float32), np.zeros((Hh, W), np.float32), np.zeros((Hh, W), PICK_DTYPE)]
-    for r in range(n):
-        got = renderer.render(plain["cu"], plain["su"], W, Hh, shard=(r, n, "cols"), **kw)
-        x0, x1 = r * bw, min(W, (r + 1) * bw)
-        assert got[0].shape == (Hh, bw, 4)
-        for dst, src in zip(parts, got):
-            dst[:, x0:x1] = src[:, :x1 - x0]
-    for a, b in zip(parts, full):
-        assert _same(a, b), n
+    FM.check_column_bands(renderer, plain, MODE, n, [MODE.on])
 
 
 # ---- 7. off is untouched --------------------------------------------------------------------------------------------------------------------
+def _null_block(r):
+    r.set_atmosphere(None)
+    return {}
+
+
 @pytest.mark.parametrize("cam", ["persp", "oblique"])
 def test_off_is_untouched(cam):
-    """A context on which the block was never set, then frames with it, then NULL: byte-identical colour, depth, pick and counts."""
-    g, cu, su, proj, unf = _view("case_plane", cam)
-    r = GSWTRenderer(0)
-    try:
-        _bind(r, g)
-        bgc, bgd = DR.bg_images(W, Hh)
-        kw = dict(order_mode=L.GSWT_ORDER_DEPTH, bg_rgba=bgc, bg_depth=bgd, projection=proj, depth=True, pick=True)
-        before = r.render(cu, su, W, Hh, **kw)
-        t0 = r.timings()
-        on = r.render(cu, su, W, Hh, atmosphere=BLOCKS["both"], **kw)
-        assert _same(r.render(cu, su, W, Hh, **kw)[0], on[0]) and not _same(on[0], before[0])     # (no argument: the context keeps the block)
-        r.set_atmosphere(None)
-        after = r.render(cu, su, W, Hh, **kw)
-        t1 = r.timings()
-        for a, b in zip(before, after):
-            assert _same(a, b)
-        assert (t0["n_visible"], t0["n_pairs"]) == (t1["n_visible"], t1["n_pairs"])
-        assert _same(r.render(cu, su, W, Hh, atmosphere=A.OFF, **kw)[0], before[0])
-        assert (before[2]["weight"] > 0).mean() > 0.3
-        # ... and the vertex stage with the block off is still the reference's, bit for bit
-        r.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-        r.render(cu, su, W, Hh, projection=proj)
-        got = r.read_projected().view(orc.SPLAT_DTYPE)
-        vis = unf["visible"] == 1
-        assert np.array_equal(got["visible"] == 1, vis)
-        for fld in ("ndc", "depth", "major", "minor", "rgba"):
-            assert _bits_equal(got[fld][vis], unf[fld][vis]), fld
-    finally:
-        r.close()
+    """A context on which the block was never set, then frames with it, then NULL, then OFF: byte-identical colour, depth, pick and
+    counts, and the vertex stage with the block off is still the reference's, bit for bit, the visible mask included."""
+    FM.check_off_is_untouched(cam, dict(atmosphere=BLOCKS["both"]), [("NULL", _null_block), ("OFF", lambda r: dict(atmosphere=A.OFF))])
 
 
 # ---- 8. refusals ----------------------------------------------------------------------------------------------------------------------------
@@ -440,53 +293,17 @@ def test_refused_blocks_leave_the_block_in_force(renderer, plain):
     with pytest.raises(GSWTError):
         renderer.set_atmosphere(A.Atmosphere(fade=(8.0, 4.0)))
     got = renderer.render(plain["cu"], plain["su"], W, Hh, depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], ["both"], plain, "after refused blocks")
+    FM.assert_frames([got], ["both"], plain, "after refused blocks")
     # the edges of the ranges are accepted
     for kw in (dict(fade_start=0.0), dict(fog_max=1.0), dict(fog_start=0.0), dict(r=0.0, g=1.0), dict(fade_start=0.0, fade_end=0.0), dict(fog_density=0.0, fog_max=0.0)):
         assert lib.gswt_set_atmosphere(h, _raw_block(**kw)) == L.GSWT_OK, kw
     assert lib.gswt_set_atmosphere(h, None) == L.GSWT_OK
     got = renderer.render(plain["cu"], plain["su"], W, Hh, depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], ["off"], plain, "after NULL")
+    FM.assert_frames([got], ["off"], plain, "after NULL")
 
 
 def test_sequence_v2_is_refused_at_submit(renderer, plain):
-    import torch
-    lib, h = renderer._lib, renderer._h
-    cam = (C.c_char * 176).from_buffer_copy(bytes(plain["cu"]))
-    sc = (C.c_char * 160).from_buffer_copy(bytes(plain["su"]))
-    cfg = L.RenderConfig()
-    cfg.culling_dist, cfg.lod_enable_mask, cfg.order_mode = 1.0, 0xFFFFFFFF, L.GSWT_ORDER_DEPTH
-    out = np.full((Hh, W, 4), 7.0, np.float32)
-    z = np.full((Hh, W), -1.0, np.float32)
-    pk = np.full((Hh, W, 4), 0x55555555, np.uint32)
-    o_d = torch.full((Hh, W, 4), 7.0, dtype=torch.float32, device="cuda")
-    z_d = torch.full((Hh, W), -1.0, dtype=torch.float32, device="cuda")
-    p_d = torch.full((Hh, W, 4), 0x55555555, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    for name in ("fade", "fog", "both"):
-        renderer.set_atmosphere(BLOCKS[name])
-        renderer.set_option(L.GSWT_OPT_STRICT_VS, 0)
-        try:
-            assert lib.gswt_render_pick(h, cam, sc, C.byref(cfg), W, Hh, None, None, 0, vp(out), vp(z), vp(pk), 0) == L.GSWT_ERR_BAD_ARG, name
-            assert b"GSWT_OPT_STRICT_VS" in lib.gswt_last_error(h) and b"gswt_set_atmosphere" in lib.gswt_last_error(h)
-            ticket = C.c_int(-7)
-            assert lib.gswt_render_async_pick(h, cam, sc, C.byref(cfg), W, Hh, None, None, C.c_void_p(o_d.data_ptr()), C.c_void_p(z_d.data_ptr()),
-                                              C.c_void_p(p_d.data_ptr()), C.byref(ticket)) == L.GSWT_ERR_BAD_ARG, name
-            assert ticket.value == -7
-        finally:
-            renderer.set_option(L.GSWT_OPT_STRICT_VS, 1)
-        torch.cuda.synchronize()
-        assert (out == 7.0).all() and (z == -1.0).all() and (pk == 0x55555555).all(), name
-        assert bool((o_d == 7.0).all()) and bool((z_d == -1.0).all()) and bool((p_d == 0x55555555).all()), name
-        # the next valid frame renders, with the block still in force
-        got = renderer.render(plain["cu"], plain["su"], W, Hh, depth=True, pick=True, **plain["kw"])
-        _assert_frames([got], [name], plain, "after the refused v2 frame, " + name)
-    # with the block off sequence v2 renders
-    renderer.set_atmosphere(A.OFF)
-    renderer.set_option(L.GSWT_OPT_STRICT_VS, 0)
-    assert lib.gswt_render_pick(h, cam, sc, C.byref(cfg), W, Hh, None, None, 0, vp(out), vp(z), vp(pk), 0) == L.GSWT_OK
-    assert not (out == 7.0).all()
+    FM.check_v2_refused_at_submit(renderer, plain, MODE, ("fade", "fog", "both"), (b"GSWT_OPT_STRICT_VS", b"gswt_set_atmosphere"))
 
 
 # ---- 9. the proxy pass ------------------------------------------------------------------------------------------------------------------------
@@ -515,13 +332,13 @@ def test_proxy_is_fogged(renderer, name):
     d0, c0 = _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, A.OFF)
     d1, c1 = _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, atm)
     d2, c2 = _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, A.Atmosphere(fade=(1.0, 2.0)))
-    assert _same(d0, d1) and _same(d0, d2) and _same(c0, c2)
+    assert FM.same(d0, d1) and FM.same(d0, d2) and FM.same(c0, c2)
     written = d0 < 1.0
     assert written.mean() > 0.05
     sky = R.sky(Wp, Hp)
-    assert _same(c1[~written], sky[~written]) and _same(c0[~written], sky[~written])
+    assert FM.same(c1[~written], sky[~written]) and FM.same(c0[~written], sky[~written])
     if name == "black_background":
-        assert _same(c0, c1) and (c0[written] == np.array([0, 0, 0, 1], F32)).all()
+        assert FM.same(c0, c1) and (c0[written] == np.array([0, 0, 0, 1], F32)).all()
         return
     # the hit distance from the float64 unprojection of the proxy's own depth
     cu = cam.uniforms()
@@ -537,7 +354,7 @@ def test_proxy_is_fogged(renderer, name):
     print(f"{name}: {int(written.sum())} proxy pixels, F {F.min():.3f} .. {F.max():.3f}, max |colour error| / tolerance {np.max(err / tol):.3f}, largest tolerance {tol.max():.2e}")
     assert (err <= tol).all()
     assert (c1[written][:, 3] == 1.0).all()
-    assert F.max() > 0.3 and not _same(c0, c1)
+    assert F.max() > 0.3 and not FM.same(c0, c1)
 
 
 # ---- 10. through the frame harness -----------------------------------------------------------------------------------------------------------
@@ -555,8 +372,8 @@ def test_pipeline_passes_atmosphere_through(renderer):
     pairs_off = renderer.timings()["n_pairs"]
     atm = A.Atmosphere(fade=(3.0, 9.0), fog=FOG)
     on = pipe.render(cu, W, Hh, atmosphere=atm)
-    assert 0 < renderer.timings()["n_pairs"] < pairs_off and not _same(on, off)
+    assert 0 < renderer.timings()["n_pairs"] < pairs_off and not FM.same(on, off)
     renderer.set_atmosphere(A.OFF)
-    assert _same(renderer.render(cu, pipe.wang.scene_uniforms(), W, Hh, atmosphere=atm), on)
-    assert _same(pipe.render(cu, W, Hh), on)                   # (no argument: the context keeps the block)
-    assert _same(pipe.render(cu, W, Hh, atmosphere=A.OFF), off)
+    assert FM.same(renderer.render(cu, pipe.wang.scene_uniforms(), W, Hh, atmosphere=atm), on)
+    assert FM.same(pipe.render(cu, W, Hh), on)                   # (no argument: the context keeps the block)
+    assert FM.same(pipe.render(cu, W, Hh, atmosphere=A.OFF), off)

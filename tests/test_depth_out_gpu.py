@@ -13,21 +13,11 @@ import pytest
 from gswt_renderer_amd import _lib as L
 from oracle import gswt_oracle as orc
 from tests import depth_ref as DR
+from tests import frame_modes as FM
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-4          # colour parity tolerance of the image tests
-ZTOL = 1e-5         # depth against the reference, outside pixels whose colour already differs beyond TOL
 FORMATS = [L.GSWT_OUT_RGBA32F, L.GSWT_OUT_RGBA8_UNORM, L.GSWT_OUT_BGRA8_UNORM]
-
-
-def _check_against_ref(img, z, ref_img, ref_z):
-    n = ref_z.size
-    bad = (np.abs(img.astype(np.float64) - ref_img.astype(np.float64)) > TOL).any(axis=-1)
-    assert bad.sum() <= 2e-3 * n, int(bad.sum())
-    dz = np.abs(z.astype(np.float64) - ref_z.astype(np.float64))
-    assert dz[~bad].max() <= ZTOL, float(dz[~bad].max())
-    return float(dz.max())
 
 
 @pytest.mark.parametrize("bg", [False, True], ids=["clear", "bg_depth"])
@@ -46,13 +36,13 @@ def test_depth_matches_reference_golden_cases(renderer, name, order_mode, bg):
     pipe.update(g["pos"], vp)
     img, z = pipe.render(cu, W, Hh, bg_rgba=bgc, bg_depth=bgd, order_mode=order_mode, depth=True)
     assert z.shape == (Hh, W) and z.dtype == np.float32
-    _check_against_ref(img, z, ref_img, ref_z)
+    FM.check_against_ref(img, z, ref_img, ref_z)
     # colour and depth from the same frame: the colour is the image a frame without depth output writes
     assert np.array_equal(img, pipe.render(cu, W, Hh, bg_rgba=bgc, bg_depth=bgd, order_mode=order_mode))
     zbg = np.ones((Hh, W), np.float32) if bgd is None else bgd
     free = n_cover == 0
     assert free.any() and (~free).any()
-    assert np.abs(z[free] - zbg[free]).max() <= ZTOL
+    assert np.abs(z[free] - zbg[free]).max() <= FM.ZTOL
 
 
 @pytest.mark.parametrize("order_mode,bg", [(0, False), (1, True)], ids=["reference-clear", "depth-bg_depth"])
@@ -68,7 +58,7 @@ def test_depth_matches_reference_mid_size(renderer, order_mode, bg):
     ref_img, ref_z = DR.composite(sp, W, Hh, splat_scale=su.splat_scale, order_mode=order_mode, bg_rgba=bgc, bg_depth=bgd)
     img, z = renderer.render(cam, su, W, Hh, order_mode=order_mode, bg_rgba=bgc, bg_depth=bgd, depth=True)
     assert ref_img[..., 3].max() > 0.5
-    _check_against_ref(img, z, ref_img, ref_z)
+    FM.check_against_ref(img, z, ref_img, ref_z)
 
 
 # ---- full frames against themselves (c3) ----------------------------------------------------------------------------------------------

@@ -6,23 +6,16 @@ The vertex stage against the float32 restatement bit for bit; the surface mappin
 does not touch; image, depth and pick against the CPU references over the GPU's own projected records; a known-answer height field;
 the same bits through graphs, frames in flight, compositor and cull variants, output formats and row shards; the refusals; and the
 perspective path untouched by switching the option on and off."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from gswt_renderer_amd import _lib as L
 from gswt_renderer_amd import ortho
-from gswt_renderer_amd.renderer import PICK_DTYPE, PICK_NONE, GSWTError, make_draw
+from gswt_renderer_amd.renderer import PICK_NONE, GSWTError
 from oracle import gswt_oracle as orc
-from tests import depth_ref as DR
-from tests import helpers as H
+from tests import frame_modes as FM
 from tests import ortho_ref as OR
-from tests import pick_ref as PR
 from tests import special_splats as S
-from tests import unorm8_ref as U8
-from tests import yuv_ref as YUV
-from tests.test_depth_out_gpu import TOL, ZTOL, _check_against_ref
 
 pytestmark = pytest.mark.gpu
 W, Hh = OR.W, OR.H
@@ -31,76 +24,21 @@ ORTHO, PERSP = L.GSWT_PROJECTION_ORTHO, L.GSWT_PROJECTION_PERSPECTIVE
 
 @pytest.fixture(autouse=True)
 def _defaults(renderer):
-    """Every test leaves the shared context as it found it: perspective, default options."""
     yield
-    for key, value in ((L.GSWT_OPT_PROJECTION, PERSP), (L.GSWT_OPT_STRICT_VS, 1), (L.GSWT_OPT_GRAPH, 0), (L.GSWT_OPT_TIMING, 2),
-                       (L.GSWT_OPT_SEGMENT, L.GSWT_DEFAULT_SEGMENT), (L.GSWT_OPT_COMPOSITE, 0), (L.GSWT_OPT_NO_CHUNK_CULL, 0),
-                       (L.GSWT_OPT_DEBUG_VARYINGS, 0), (L.GSWT_OPT_NO_LOD_PREFILTER, 0)):
-        renderer.set_option(key, value)
-    renderer.configure(None)
-
-
-def _bind(renderer, g):
-    """The case's scene and the oracle's draw list through gswt_upload_scene / gswt_set_draws, list for list (no LOD pre-filter), so that
-    gswt_debug_read_projected is in the order of the oracle's instances."""
-    pp = g["pp"]
-    renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 1)
-    renderer.configure(g["hm"])
-    renderer.upload_scene(pp.tex, pp.gs_index, pp.gs_lod_id)
-    draws, m_gs, m_map, m_lod, off = [], [], [], [], 0
-    for d in g["draws"]:
-        tile = H.to_product_tile(d.tile)
-        if d.base is not None:
-            draws.append(make_draw(tile, base=d.base, lod=int(d.tile.tile_id[0])))
-        else:
-            n = len(d.gs_index)
-            draws.append(make_draw(tile, merged_range=(off, n), merged_has_lod=d.lod_id is not None, lod=int(d.tile.tile_id[0])))
-            m_gs.append(np.asarray(d.gs_index, np.uint32))
-            m_map.append(np.asarray(d.map_id, np.uint32))
-            m_lod.append(np.asarray(d.lod_id, np.uint32) if d.lod_id is not None else np.zeros(n, np.uint32))
-            off += n
-    cat = lambda a: np.concatenate(a) if a else None
-    renderer.set_draws(draws, cat(m_gs), cat(m_map), cat(m_lod))
+    FM.restore_defaults(renderer)
 
 
 def _varyings(renderer, cu, su, projection=ORTHO):
-    renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-    try:
-        renderer.render(cu, su, W, Hh, projection=projection)
-        return renderer.read_projected().view(orc.SPLAT_DTYPE)
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
-
-
-def _cam(which, g, name="case_plane"):
-    args = OR.camera_args(which, lod_pos=g["pos"]) if name == "case_plane" else OR.surface_camera_args(name, which, lod_pos=g["pos"])
-    return OR.ortho_camera_of(args)
-
-
-def _persp(g):
-    from gswt_renderer_amd import host
-    return host.camera_uniforms(g["pos"], g["tgt"], (0, 0, 1), 45.0, 0.1, 2400.0, W, Hh)[0]
-
-
-def _raw(a):
-    return np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-
-
-def _same(a, b):
-    return np.array_equal(_raw(a), _raw(b))
-
-
-def _bits_equal(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+    return FM.varyings(renderer, cu, su, projection=projection)[0]
 
 
 # ---- 1. the vertex stage, bit for bit ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("which", OR.CAMERAS)
 def test_vertex_stage_is_bit_exact(renderer, which):
     g = OR.golden()
-    _bind(renderer, g)
+    FM.bind(renderer, g)
     cu, su, want = OR.plane_records(which)
-    cam = _cam(which, g)
+    cam = FM.ortho_cam(which, g)
     assert bytes(cam.uniforms()) == bytes(cu)
     got = _varyings(renderer, cam.uniforms(), su)
     assert got.shape == want.shape
@@ -108,7 +46,7 @@ def test_vertex_stage_is_bit_exact(renderer, which):
     vis = want["visible"] == 1
     assert vis.sum() > 300
     for fld in ("ndc", "depth", "major", "minor", "rgba"):
-        assert _bits_equal(got[fld][vis], want[fld][vis]), fld
+        assert FM.bits_equal(got[fld][vis], want[fld][vis]), fld
 
 
 # ---- 2. the surface mappings inside the FULL x ORTHO instantiations ------------------------------------------------------------------
@@ -116,16 +54,16 @@ def test_vertex_stage_is_bit_exact(renderer, which):
 @pytest.mark.parametrize("name", ["case_hmap", "case_sphere"])
 def test_surfaces_agree_with_the_oracle_where_the_jacobian_plays_no_part(renderer, name, which):
     g = OR.golden(name)
-    _bind(renderer, g)
+    FM.bind(renderer, g)
     su = OR.scene_of(g)
-    cu = _cam(which, g, name).uniforms()
+    cu = FM.ortho_cam(which, g, name).uniforms()
     got = _varyings(renderer, cu, su)
     want = orc.project_draws(orc.Camera176.from_buffer_copy(bytes(cu)), su, g["pp"].tex, g["draws"], height_map=g["hm"])
     assert got.shape == want.shape
     both = (got["visible"] == 1) & (want["visible"] == 1)
     assert both.sum() > 150 and not ((got["visible"] == 1) & (want["visible"] == 0)).any()
     for fld in ("ndc", "depth", "rgba"):
-        assert _bits_equal(got[fld][both], want[fld][both]), fld
+        assert FM.bits_equal(got[fld][both], want[fld][both]), fld
     maj, mnr = got["major"][got["visible"] == 1].astype(np.float64), got["minor"][got["visible"] == 1].astype(np.float64)
     assert np.isfinite(maj).all() and np.isfinite(mnr).all()
     assert (np.hypot(maj[:, 0], maj[:, 1]) >= np.hypot(mnr[:, 0], mnr[:, 1])).all()
@@ -137,9 +75,9 @@ def test_surfaces_equal_the_oracle_bit_for_bit(renderer, name, which):
     """The same frames against the oracle's own orthographic stage (oracle.frame_mode(ortho=1); tests/test_pair_list_modes_cpu.py pins it to
     the float32 restatement on the plane): every output, the axes included, bit for bit, and the same `visible`."""
     g = OR.golden(name)
-    _bind(renderer, g)
+    FM.bind(renderer, g)
     su = OR.scene_of(g)
-    cu = _cam(which, g, name).uniforms()
+    cu = FM.ortho_cam(which, g, name).uniforms()
     got = _varyings(renderer, cu, su)
     block = orc.Camera176.from_buffer_copy(bytes(cu))
     with orc.frame_mode(ortho=1):
@@ -150,32 +88,12 @@ def test_surfaces_equal_the_oracle_bit_for_bit(renderer, name, which):
     vis = rects["visible"] == 1
     assert vis.sum() > 150
     for fld in ("ndc", "depth", "major", "minor", "rgba"):
-        assert _bits_equal(got[fld][vis], want[fld][vis]), fld
+        assert FM.bits_equal(got[fld][vis], want[fld][vis]), fld
 
 
 # ---- 3. image, depth and pick against the CPU references over the GPU's own records --------------------------------------------------
 def _image_case(renderer, which, order_mode, bg, splat_scale):
-    g = OR.golden()
-    _bind(renderer, g)
-    su = OR.scene_of(g, splat_scale)
-    cu = _cam(which, g).uniforms()
-    sp = _varyings(renderer, cu, su)
-    bgc, bgd = DR.bg_images(W, Hh) if bg else (None, None)
-    kw = dict(order_mode=order_mode, bg_rgba=bgc, bg_depth=bgd)
-    img, z, pick = renderer.render(cu, su, W, Hh, projection=ORTHO, depth=True, pick=True, **kw)
-    t = renderer.timings()
-    assert z.shape == (Hh, W) and pick.shape == (Hh, W) and pick.dtype == PICK_DTYPE
-    ref_img, ref_z, n_cover = DR.composite(sp, W, Hh, splat_scale=splat_scale, with_cover=True, **kw)
-    assert (n_cover > 0).mean() > 0.5 and ref_img[..., 3].max() > 0.5
-    dz = _check_against_ref(img, z, ref_img, ref_z)
-    ev = PR.composite(sp, W, Hh, splat_scale=splat_scale, **kw)
-    mi, en = PR.identities(g["draws"])
-    dw = PR.check_pick(pick, ev, sp, mi, en, label=f"ortho {which} order={order_mode} bg={bg} scale={splat_scale}")
-    print(f"ortho {which} order={order_mode} bg={bg} scale={splat_scale}: visible {t['n_visible']} pairs {t['n_pairs']} max|dz| {dz:.3e} max|dw| {dw:.3e}")
-    assert t["n_visible"] == int((sp["visible"] == 1).sum())
-    # colour and depth are what frames without the other outputs write
-    assert _same(img, renderer.render(cu, su, W, Hh, projection=ORTHO, **kw))
-    return t
+    return FM.image_case(renderer, which, order_mode, bg, splat_scale, {}, "ortho", min_cover=0.5)["t"]
 
 
 @pytest.mark.parametrize("bg", [False, True], ids=["clear", "bg"])
@@ -225,13 +143,13 @@ def test_known_answer_height_field(renderer):
         rng = z_top - z_bottom
         for k, (x, y, h) in enumerate(px):
             p = pick[y, x]
-            assert p["map_index"] == 7 and p["entry"] == k and 1.0 - TOL <= p["weight"] <= 1.0
+            assert p["map_index"] == 7 and p["entry"] == k and 1.0 - FM.TOL <= p["weight"] <= 1.0
             d = (z_top - h) / rng
             bound = 3 * OR.U * (1 + 2 * OR.U) * d * rng + 2.0 ** -50
             got = float(ortho.height_from_depth(cam, p["depth"]))
             print(f"splat {k}: height {h} from depth {p['depth']!r} -> {got!r} (bound {bound:.3e})")
             assert abs(got - h) <= bound
-            assert abs(float(z[y, x]) - float(p["depth"])) <= ZTOL      # an opaque splat's centre: weight 1, the depth image holds the same value
+            assert abs(float(z[y, x]) - float(p["depth"])) <= FM.ZTOL      # an opaque splat's centre: weight 1, the depth image holds the same value
         free = pick["weight"] == 0
         assert free.sum() > 0.9 * W * Hh and (~free).sum() >= len(px)
         assert (pick["depth"][free] == 1.0).all() and (z[free] == 1.0).all()
@@ -240,133 +158,69 @@ def test_known_answer_height_field(renderer):
 
 
 # ---- 5. the same bits every way ------------------------------------------------------------------------------------------------------
+def _set_projection(renderer, name):
+    renderer.set_option(L.GSWT_OPT_PROJECTION, PERSP if name == "persp" else ORTHO)
+
+
+def _opposite(wave):
+    """The state whose projection is not that of the wave's first frame: the option as it stands must not reach the frames submitted."""
+    return "persp" if wave[0] != "persp" else "top"
+
+
 @pytest.fixture()
 def plain(renderer):
     """The plane case bound, and the plain synchronous frames (colour, depth, pick) of the two orthographic cameras and the case's
-    perspective camera, depth order, over a background."""
+    perspective camera, depth order, over a background; under "mode" the three cameras as states."""
     g = OR.golden()
-    _bind(renderer, g)
-    su = OR.scene_of(g)
-    bgc, bgd = DR.bg_images(W, Hh)
-    kw = dict(order_mode=L.GSWT_ORDER_DEPTH, bg_rgba=bgc, bg_depth=bgd)
-    cams = {"top": (_cam("top", g).uniforms(), ORTHO), "oblique": (_cam("oblique", g).uniforms(), ORTHO), "persp": (_persp(g), PERSP)}
-    frames = {k: renderer.render(cu, su, W, Hh, projection=pr, depth=True, pick=True, **kw) for k, (cu, pr) in cams.items()}
+    mode = FM.Mode({"top": (FM.ortho_cam("top", g).uniforms(), dict(projection=ORTHO)), "oblique": (FM.ortho_cam("oblique", g).uniforms(), dict(projection=ORTHO)),
+                    "persp": (FM.persp_cam(g), dict(projection=PERSP))}, _set_projection)
+    s = FM.plain_frames(renderer, mode, g, OR.scene_of(g))
     renderer.set_option(L.GSWT_OPT_PROJECTION, PERSP)
-    assert not _same(frames["top"][0], frames["oblique"][0]) and not _same(frames["top"][0], frames["persp"][0])
+    frames = s["frames"]
+    assert not FM.same(frames["top"][0], frames["oblique"][0]) and not FM.same(frames["top"][0], frames["persp"][0])
     for f in frames.values():
         assert (f[2]["weight"] > 0).mean() > 0.3
-    return dict(g=g, su=su, kw=kw, bgc=bgc, bgd=bgd, cams=cams, frames=frames)
-
-
-def _device_frames(renderer, s, seq, *, waves):
-    """Submits the frames named in `seq` with render_async, `waves` at a time in flight, into buffers of their own; returns their
-    (colour, depth, pick) as numpy arrays."""
-    import torch
-    bgc, bgd = torch.from_numpy(s["bgc"]).cuda(), torch.from_numpy(s["bgd"]).cuda()
-    outs = [(torch.zeros((Hh, W, 4), dtype=torch.float32, device="cuda"), torch.full((Hh, W), -1.0, dtype=torch.float32, device="cuda"),
-             torch.full((Hh, W, 4), -1, dtype=torch.int32, device="cuda")) for _ in seq]
-    torch.cuda.synchronize()
-    for i in range(0, len(seq), waves):
-        tickets = []
-        for name, (o, z, p) in zip(seq[i:i + waves], outs[i:i + waves]):
-            cu, pr = s["cams"][name]
-            tickets.append(renderer.render_async(cu, s["su"], W, Hh, o.data_ptr(), order_mode=L.GSWT_ORDER_DEPTH, bg_rgba_ptr=bgc.data_ptr(),
-                                                 bg_depth_ptr=bgd.data_ptr(), out_depth_ptr=z.data_ptr(), out_pick_ptr=p.data_ptr(), projection=pr))
-        assert len(set(tickets)) == len(tickets)
-        # the option as it stands now must not reach the frames already submitted
-        renderer.set_option(L.GSWT_OPT_PROJECTION, PERSP if seq[i] != "persp" else ORTHO)
-        for t in tickets:
-            renderer.render_wait(t)
-    torch.cuda.synchronize()
-    return [(o.cpu().numpy(), z.cpu().numpy(), p.cpu().numpy()) for o, z, p in outs]
-
-
-def _assert_frames(got, seq, s, what):
-    for k, (name, f) in enumerate(zip(seq, got)):
-        want = s["frames"][name]
-        assert _same(f[0], want[0]) and _same(f[1], want[1]) and _same(f[2], want[2]), (what, k, name)
+    return dict(s, mode=mode)
 
 
 def test_graph_replay_with_alternating_projections(renderer, plain):
-    renderer.set_option(L.GSWT_OPT_TIMING, 0)
-    renderer.set_option(L.GSWT_OPT_GRAPH, 1)
-    launches0, rebuilds0, _ = renderer.graph_stats()
     # one frame at a time: slot 0 alternates; then two in flight: slots 0 and 1 each alternate from wave to wave
     seq1 = ["top", "persp", "oblique", "persp", "top"]
-    _assert_frames(_device_frames(renderer, plain, seq1, waves=1), seq1, plain, "graph, one slot")
     seq2 = ["top", "persp", "persp", "oblique", "top", "persp"]
-    _assert_frames(_device_frames(renderer, plain, seq2, waves=2), seq2, plain, "graph, two slots")
-    launches, rebuilds, _ = renderer.graph_stats()
-    assert launches - launches0 == len(seq1) + len(seq2)
-    assert rebuilds - rebuilds0 >= 4                        # another k_project instantiation: the slot's graph is rebuilt
+    _, rebuilds, _ = FM.check_graph_replay(renderer, plain, plain["mode"], seq1, seq2, then=_opposite)
+    assert rebuilds >= 4                                    # another k_project instantiation: the slot's graph is rebuilt
 
 
 def test_async_frames_in_flight_keep_their_projection(renderer, plain):
     slots = renderer.frame_slots()
     seq = [("top", "persp", "oblique", "persp")[k % 4] for k in range(slots)]
-    _assert_frames(_device_frames(renderer, plain, seq, waves=slots), seq, plain, "async")
+    FM.check_in_flight(renderer, plain, plain["mode"], seq, waves=slots, then=_opposite)
 
 
 @pytest.mark.parametrize("opt", [L.GSWT_OPT_NO_CHUNK_CULL, L.GSWT_OPT_COMPOSITE], ids=["no_chunk_cull", "composite_dw"])
 def test_cull_and_compositor_variants(renderer, plain, opt):
-    renderer.set_option(opt, 1)
-    for name in ("top", "oblique"):
-        cu, pr = plain["cams"][name]
-        got = renderer.render(cu, plain["su"], W, Hh, projection=pr, depth=True, pick=True, **plain["kw"])
-        _assert_frames([got], [name], plain, opt)
+    FM.check_compositor_and_cull_variant(renderer, plain, plain["mode"], opt, ("top", "oblique"))
 
 
 def test_output_formats(renderer, plain):
-    for name in ("top", "oblique"):
-        cu, pr = plain["cams"][name]
-        f32 = plain["frames"][name][0]
-        kw = dict(projection=pr, **plain["kw"])
-        assert np.array_equal(renderer.render(cu, plain["su"], W, Hh, out_format=L.GSWT_OUT_RGBA8_UNORM, **kw), U8.rgba8(f32))
-        assert np.array_equal(renderer.render(cu, plain["su"], W, Hh, out_format=L.GSWT_OUT_BGRA8_UNORM, **kw), U8.bgra8(f32))
-        y, cbcr = renderer.render(cu, plain["su"], W, Hh, out_format=L.GSWT_VIDEO_NV12, **kw)
-        wy, wc = YUV.nv12(f32)
-        assert np.array_equal(y, wy) and np.array_equal(cbcr, wc)
+    FM.check_output_formats(renderer, plain, plain["mode"], ("top", "oblique"), bgra=True)
 
 
 def test_two_row_shards_tile_the_frame(renderer, plain):
-    for name in ("top", "oblique"):
-        cu, pr = plain["cams"][name]
-        full = plain["frames"][name]
-        rows = renderer.shard_rows_padded(Hh, 2)
-        parts = [np.zeros((Hh, W, 4), np.float32), np.zeros((Hh, W), np.float32), np.zeros((Hh, W), PICK_DTYPE)]
-        for r in range(2):
-            got = renderer.render(cu, plain["su"], W, Hh, projection=pr, depth=True, pick=True, shard=(r, 2), **plain["kw"])
-            assert got[0].shape == (rows, W, 4)
-            k = 0
-            for ty in range(r, (Hh + 15) // 16, 2):
-                y0, y1 = ty * 16, min(Hh, ty * 16 + 16)
-                for dst, src in zip(parts, got):
-                    dst[y0:y1] = src[k * 16:k * 16 + (y1 - y0)]
-                k += 1
-        for a, b in zip(parts, full):
-            assert _same(a, b), name
+    FM.check_row_shards(renderer, plain, plain["mode"], 2, ("top", "oblique"))
 
 
 # ---- 6. refusals ------------------------------------------------------------------------------------------------------------------------
 def test_refusals(renderer, plain):
-    import torch
     lib, h = renderer._lib, renderer._h
-    su = plain["su"]
-    sc = (C.c_char * 160).from_buffer_copy(bytes(su))
-    good = plain["cams"]["top"][0]
+    su, mode = plain["su"], plain["mode"]
+    good, persp = mode.states["top"][0], mode.states["persp"][0]
 
     def block(edit=None, base=good):
         cu = L.CameraUniforms.from_buffer_copy(bytes(base))
         if edit:
             edit(cu)
-        return (C.c_char * 176).from_buffer_copy(bytes(cu))
-
-    def cfg(**kw):
-        c = L.RenderConfig()
-        c.culling_dist, c.lod_enable_mask, c.order_mode = 1.0, 0xFFFFFFFF, L.GSWT_ORDER_DEPTH
-        for k, v in kw.items():
-            setattr(c, k, v)
-        return c
+        return cu
 
     # option values
     for bad in (2, -1):
@@ -380,63 +234,40 @@ def test_refusals(renderer, plain):
             cu.focal[k] = v
         return f
 
-    cases = [("perspective matrix", block(base=plain["cams"]["persp"][0]), cfg(), None, b"affine"),
-             ("focal 0", block(setfocal(0, 0.0)), cfg(), None, b"focal"),
-             ("focal NaN", block(setfocal(1, float("nan"))), cfg(), None, b"focal"),
-             ("focal inf", block(setfocal(0, float("inf"))), cfg(), None, b"focal"),
-             ("sequence v2", block(), cfg(), (L.GSWT_OPT_STRICT_VS, 0), b"GSWT_OPT_STRICT_VS"),
-             ("column shards", block(), cfg(shard_index=1, shard_count=2, shard_mode=L.GSWT_SHARD_COLUMNS), None, b"column")]
-    out = np.full((Hh, W, 4), 7.0, np.float32)
-    z = np.full((Hh, W), -1.0, np.float32)
-    pk = np.full((Hh, W, 4), 0x55555555, np.uint32)
-    o_d = torch.full((Hh, W, 4), 7.0, dtype=torch.float32, device="cuda")
-    z_d = torch.full((Hh, W), -1.0, dtype=torch.float32, device="cuda")
-    p_d = torch.full((Hh, W, 4), 0x55555555, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    cases = [("perspective matrix", block(base=persp), {}, None, b"affine"),
+             ("focal 0", block(setfocal(0, 0.0)), {}, None, b"focal"),
+             ("focal NaN", block(setfocal(1, float("nan"))), {}, None, b"focal"),
+             ("focal inf", block(setfocal(0, float("inf"))), {}, None, b"focal"),
+             ("sequence v2", block(), {}, (L.GSWT_OPT_STRICT_VS, 0), b"GSWT_OPT_STRICT_VS"),
+             ("column shards", block(), dict(shard_index=1, shard_count=2, shard_mode=L.GSWT_SHARD_COLUMNS), None, b"column")]
+    refused, _ = FM.refusal_probe(renderer)
     renderer.set_option(L.GSWT_OPT_PROJECTION, ORTHO)
-    for what, cam, c, opt, word in cases:
-        if opt:
-            renderer.set_option(*opt)
-        try:
-            assert lib.gswt_render_pick(h, cam, sc, C.byref(c), W, Hh, None, None, 0, vp(out), vp(z), vp(pk), 0) == L.GSWT_ERR_BAD_ARG, what
-            assert word in lib.gswt_last_error(h), (what, lib.gswt_last_error(h))
-            ticket = C.c_int(-7)
-            assert lib.gswt_render_async_pick(h, cam, sc, C.byref(c), W, Hh, None, None, C.c_void_p(o_d.data_ptr()), C.c_void_p(z_d.data_ptr()),
-                                              C.c_void_p(p_d.data_ptr()), C.byref(ticket)) == L.GSWT_ERR_BAD_ARG, what
-            assert ticket.value == -7
-        finally:
-            if opt:
-                renderer.set_option(opt[0], 1)
-        torch.cuda.synchronize()
-        assert (out == 7.0).all() and (z == -1.0).all() and (pk == 0x55555555).all(), what
-        assert bool((o_d == 7.0).all()) and bool((z_d == -1.0).all()) and bool((p_d == 0x55555555).all()), what
+    for what, cu, cfg_kw, opt, word in cases:
+        FM.check_refused(renderer, refused, *FM.frame_blocks(cu, su, **cfg_kw), (word,), what, opt=opt)
         # the next valid frame renders
-        cu, pr = plain["cams"]["top"]
-        got = renderer.render(cu, su, W, Hh, projection=pr, depth=True, pick=True, **plain["kw"])
-        _assert_frames([got], ["top"], plain, "after " + what)
+        FM.assert_frames([FM.render_state(renderer, plain, mode, "top")], ["top"], plain, "after " + what)
     # row shards are not refused, and the perspective path takes its usual matrix with the option off
     renderer.render(good, su, W, Hh, projection=ORTHO, shard=(0, 2))
-    renderer.render(plain["cams"]["persp"][0], su, W, Hh, projection=PERSP, shard=(1, 2, "cols"))
+    renderer.render(persp, su, W, Hh, projection=PERSP, shard=(1, 2, "cols"))
 
 
 # ---- 7. perspective is untouched --------------------------------------------------------------------------------------------------------
 def test_perspective_untouched_by_the_switch(renderer):
     g = OR.golden()
-    _bind(renderer, g)
-    su, cu = OR.scene_of(g), _persp(g)
+    FM.bind(renderer, g)
+    su, cu = OR.scene_of(g), FM.persp_cam(g)
     before = renderer.render(cu, su, W, Hh, depth=True, pick=True)
     v_before = _varyings(renderer, cu, su, projection=PERSP)
-    renderer.render(_cam("top", g).uniforms(), su, W, Hh, projection=ORTHO)
+    renderer.render(FM.ortho_cam("top", g).uniforms(), su, W, Hh, projection=ORTHO)
     renderer.set_option(L.GSWT_OPT_PROJECTION, PERSP)
     after = renderer.render(cu, su, W, Hh, depth=True, pick=True)           # (no projection argument: the context is left as it is)
     for a, b in zip(before, after):
-        assert _same(a, b)
-    assert _same(v_before, _varyings(renderer, cu, su, projection=PERSP))
+        assert FM.same(a, b)
+    assert FM.same(v_before, _varyings(renderer, cu, su, projection=PERSP))
     assert (before[2]["weight"] > 0).mean() > 0.1
     # the perspective vertex stage still equals the oracle's
     want = orc.project_draws(orc.Camera176.from_buffer_copy(bytes(cu)), su, g["pp"].tex, g["draws"])
     vis = want["visible"] == 1
     assert np.array_equal(v_before["visible"][vis], want["visible"][vis])
     for fld in ("ndc", "depth", "major", "minor", "rgba"):
-        assert _bits_equal(v_before[fld][vis], want[fld][vis]), fld
+        assert FM.bits_equal(v_before[fld][vis], want[fld][vis]), fld

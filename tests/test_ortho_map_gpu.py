@@ -10,7 +10,7 @@ from gswt_renderer_amd import ortho
 from oracle import gswt_oracle as orc
 from tests import ortho_ref as OR
 from tests import proxy_raster_ref as R
-from tests.test_ortho_gpu import _bind, _cam, _same
+from tests import frame_modes as FM
 
 pytestmark = pytest.mark.gpu
 W, Hh = OR.W, OR.H
@@ -43,21 +43,21 @@ def _ground(renderer, cam, height_offset, **kw):
 @pytest.mark.parametrize("which", OR.CAMERAS)
 def test_ground_above_every_splat_hides_them(renderer, which):
     g = OR.golden()
-    _bind(renderer, g)
-    su, cam = OR.scene_of(g), _cam(which, g)
+    FM.bind(renderer, g)
+    su, cam = OR.scene_of(g), FM.ortho_cam(which, g)
     rgba_d, depth_d, rgba, depth = _ground(renderer, cam, 5.0)
     assert (depth < 1.0).all() and (depth > 0.0).all()
     img, z = renderer.render(cam.uniforms(), su, W, Hh, projection=ORTHO, order_mode=L.GSWT_ORDER_DEPTH, bg_rgba=rgba_d.data_ptr(),
                              bg_depth=depth_d.data_ptr(), bg_on_device=True, depth=True)
     assert renderer.timings()["n_visible"] > 300          # the splats are there, behind the ground
-    assert _same(img, rgba) and _same(z, depth)
+    assert FM.same(img, rgba) and FM.same(z, depth)
 
 
 @pytest.mark.parametrize("order_mode", [L.GSWT_ORDER_REFERENCE, L.GSWT_ORDER_DEPTH], ids=["reference", "depth"])
 def test_ground_below_the_splats(renderer, order_mode):
     g = OR.golden()
-    _bind(renderer, g)
-    su, cam = OR.scene_of(g), _cam("top", g)
+    FM.bind(renderer, g)
+    su, cam = OR.scene_of(g), FM.ortho_cam("top", g)
     h = -0.45                                               # z_bottom is -0.5: depth ~0.998, behind nearly every splat
     rgba_d, depth_d, rgba, depth = _ground(renderer, cam, h)
     assert (depth < 1.0).all()
@@ -65,11 +65,11 @@ def test_ground_below_the_splats(renderer, order_mode):
     chained = renderer.render(cam.uniforms(), su, W, Hh, bg_rgba=rgba_d.data_ptr(), bg_depth=depth_d.data_ptr(), bg_on_device=True, **kw)
     plain = renderer.render(cam.uniforms(), su, W, Hh, bg_rgba=rgba, bg_depth=depth, **kw)
     for a, b in zip(chained, plain):
-        assert _same(a, b)
+        assert FM.same(a, b)
     img, z, pick = chained
     free, covered = pick["weight"] == 0, pick["weight"] > 0
     assert free.sum() > 20 and covered.mean() > 0.3
-    assert _same(z[free], depth[free]) and _same(img[free], rgba[free])
+    assert FM.same(z[free], depth[free]) and FM.same(img[free], rgba[free])
     # where no splat reaches, the height field holds the ground instead of z_bottom
     got = ortho.height_from_depth(cam, z[free])
     # (the bound: 16 roundings of 2^-24 at the magnitude of the range, 25.5 -- the ray's origin and hit, the view and the projection)
@@ -83,13 +83,13 @@ def test_ground_below_the_splats(renderer, order_mode):
 def test_option_left_at_ortho_does_not_reach_the_perspective_proxy(renderer):
     import torch
     g = OR.golden()
-    _bind(renderer, g)
+    FM.bind(renderer, g)
     renderer.proxy_configure(R.mip_chain(), grid_dim=GRID)
     pc = orc.Camera(W, Hh, g["pos"], g["tgt"], [0, 0, 1])
     u = orc.proxy_uniforms(pc, map_proxy=0, surface_type=0, height_offset=-0.45, tile_width=4.0, width_scale=4.0)
     out = []
     for opt in (PERSP, ORTHO, PERSP):
-        renderer.render(_cam("top", g).uniforms(), OR.scene_of(g), W, Hh, projection=ORTHO)      # leaves the option at 1 ...
+        renderer.render(FM.ortho_cam("top", g).uniforms(), OR.scene_of(g), W, Hh, projection=ORTHO)      # leaves the option at 1 ...
         renderer.set_option(L.GSWT_OPT_PROJECTION, opt)                                           # ... or puts it back
         rgba = torch.from_numpy(R.sky(W, Hh)).cuda()
         depth = torch.zeros((Hh, W), dtype=torch.float32, device="cuda")
@@ -99,4 +99,4 @@ def test_option_left_at_ortho_does_not_reach_the_perspective_proxy(renderer):
         out.append((rgba.cpu().numpy(), depth.cpu().numpy()))
     assert (out[0][1] < 1.0).mean() > 0.2
     for o in out[1:]:
-        assert _same(o[0], out[0][0]) and _same(o[1], out[0][1])
+        assert FM.same(o[0], out[0][0]) and FM.same(o[1], out[0][1])

@@ -14,18 +14,14 @@ import pytest
 from gswt_renderer_amd import _lib as L
 from gswt_renderer_amd import atmosphere as A
 from gswt_renderer_amd import styles as ST
-from gswt_renderer_amd.renderer import PICK_DTYPE, GSWTError, GSWTRenderer
+from gswt_renderer_amd.renderer import GSWTError
 from oracle import gswt_oracle as orc
 from tests import atmosphere_ref as AR
-from tests import depth_ref as DR
+from tests import frame_modes as FM
 from tests import ortho_ref as OR
 from tests import pick_ref as PR
 from tests import special_splats as S
 from tests import tile_style_ref as TR
-from tests import unorm8_ref as U8
-from tests import yuv_ref as YUV
-from tests.test_depth_out_gpu import _check_against_ref
-from tests.test_ortho_gpu import _bind, _bits_equal, _cam, _persp, _same
 
 pytestmark = pytest.mark.gpu
 W, Hh = OR.W, OR.H
@@ -45,43 +41,18 @@ SURFACE_TABLES = {"case_hmap": ({9: TR.HIDE, 14: TR.entry((20, 200, 90), 180), 1
 
 @pytest.fixture(autouse=True)
 def _defaults(renderer):
-    """Every test leaves the shared context as it found it: styles off, no atmosphere, perspective, no filter, default options."""
     yield
-    renderer.set_tile_styles(None)
-    renderer.set_atmosphere(A.OFF)
-    for key, value in ((L.GSWT_OPT_ANTIALIAS, 0), (L.GSWT_OPT_PROJECTION, PERSP), (L.GSWT_OPT_STRICT_VS, 1), (L.GSWT_OPT_GRAPH, 0), (L.GSWT_OPT_TIMING, 2),
-                       (L.GSWT_OPT_SEGMENT, L.GSWT_DEFAULT_SEGMENT), (L.GSWT_OPT_COMPOSITE, 0), (L.GSWT_OPT_NO_CHUNK_CULL, 0),
-                       (L.GSWT_OPT_ITEM_ORDER, 0), (L.GSWT_OPT_PAIR_CAP, 0), (L.GSWT_OPT_DEBUG_VARYINGS, 0), (L.GSWT_OPT_NO_LOD_PREFILTER, 0)):
-        renderer.set_option(key, value)
-    renderer.configure(None)
+    FM.restore_defaults(renderer)
 
 
 def _varyings(renderer, cu, su, projection, table, antialias=0.0, atmosphere=A.OFF):
-    renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-    try:
-        renderer.render(cu, su, W, Hh, projection=projection, antialias=antialias, atmosphere=atmosphere, tile_styles=table if table is not None else b"")
-        return renderer.read_projected().view(orc.SPLAT_DTYPE), renderer.timings()
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
-
-
-_VIEWS = {}
+    return FM.varyings(renderer, cu, su, projection=projection, antialias=antialias, atmosphere=atmosphere, tile_styles=table if table is not None else b"")
 
 
 def _view(name, cam, splat_scale=OR.SPLAT_SCALE):
-    """(golden case, camera block, scene block, projection, per-instance cell ids) of case `name` under the perspective camera or one of
-    OR.CAMERAS (plane case only); computed once."""
-    k = (name, cam, splat_scale)
-    if k not in _VIEWS:
-        g = OR.golden(name)
-        ids, _ = PR.identities(g["draws"])
-        if cam == "persp":
-            _VIEWS[k] = (g, _persp(g), OR.scene_of(g, splat_scale), PERSP, ids)
-        else:
-            assert name == "case_plane"
-            _, su, _ = OR.plane_records(cam, splat_scale)
-            _VIEWS[k] = (g, _cam(cam, g).uniforms(), su, ORTHO, ids)
-    return _VIEWS[k]
+    """FM.view with the per-instance cell ids in the place of the reference records."""
+    g, cu, su, proj, _ = FM.view(name, cam, splat_scale)
+    return g, cu, su, proj, PR.identities(g["draws"])[0]
 
 
 def _check_records(got, tm, base, sty, label):
@@ -90,11 +61,11 @@ def _check_records(got, tm, base, sty, label):
     assert np.array_equal(got["visible"] == 1, want_vis), label
     assert tm["n_visible"] == int(want_vis.sum()), label
     for fld in ("ndc", "depth", "major", "minor"):
-        assert _bits_equal(np.ascontiguousarray(got[fld][want_vis]), np.ascontiguousarray(base[fld][want_vis])), (label, fld)
-    assert _bits_equal(np.ascontiguousarray(got["rgba"][want_vis]), np.ascontiguousarray(want_rgba[want_vis])), label
+        assert FM.bits_equal(np.ascontiguousarray(got[fld][want_vis]), np.ascontiguousarray(base[fld][want_vis])), (label, fld)
+    assert FM.bits_equal(np.ascontiguousarray(got["rgba"][want_vis]), np.ascontiguousarray(want_rgba[want_vis])), label
     neutral = want_vis & TR.classes(sty)[3]
     for fld in ("ndc", "depth", "major", "minor", "rgba"):
-        assert _bits_equal(np.ascontiguousarray(got[fld][neutral]), np.ascontiguousarray(base[fld][neutral])), (label, fld, "neutral")
+        assert FM.bits_equal(np.ascontiguousarray(got[fld][neutral]), np.ascontiguousarray(base[fld][neutral])), (label, fld, "neutral")
     return want_vis
 
 
@@ -103,7 +74,7 @@ def _check_records(got, tm, base, sty, label):
 @pytest.mark.parametrize("cam", ["persp", "oblique"])
 def test_records_are_bit_exact_on_the_plain_surface(renderer, cam, aa):
     g, cu, su, proj, ids = _view("case_plane", cam)
-    _bind(renderer, g)
+    FM.bind(renderer, g)
     sty = TR.lookup(MAIN, ids)
     base, tm0 = _varyings(renderer, cu, su, proj, None, aa)
     if aa == 0.0:                               # the unstyled records are the oracle's / the orthographic restatement's, bit for bit
@@ -111,7 +82,7 @@ def test_records_are_bit_exact_on_the_plain_surface(renderer, cam, aa):
             else OR.plane_records(cam)[2]
         assert np.array_equal(base["visible"], ref["visible"])
         for fld in ("ndc", "depth", "major", "minor", "rgba"):
-            assert _bits_equal(np.ascontiguousarray(base[fld][ref["visible"] == 1]), np.ascontiguousarray(ref[fld][ref["visible"] == 1])), fld
+            assert FM.bits_equal(np.ascontiguousarray(base[fld][ref["visible"] == 1]), np.ascontiguousarray(ref[fld][ref["visible"] == 1])), fld
     got, tm = _varyings(renderer, cu, su, proj, TABLES["main"], aa)
     assert got.shape == base.shape == (510,)
     vis0 = base["visible"] == 1
@@ -136,7 +107,7 @@ def test_records_are_bit_exact_on_the_plain_surface(renderer, cam, aa):
 @pytest.mark.parametrize("name", ["case_hmap", "case_sphere"])
 def test_records_on_the_surfaces(renderer, name):
     g, cu, su, proj, ids = _view(name, "persp")
-    _bind(renderer, g)
+    FM.bind(renderer, g)
     cells, n = SURFACE_TABLES[name]
     e = TR.entries(cells, n)
     sty = TR.lookup(e, ids)
@@ -155,7 +126,7 @@ def test_records_on_the_surfaces(renderer, name):
 # ---- 3. tint, then fog ------------------------------------------------------------------------------------------------------------------
 def test_tint_then_fog(renderer):
     g, cu, su, proj, ids = _view("case_plane", "persp")
-    _bind(renderer, g)
+    FM.bind(renderer, g)
     atm = A.Atmosphere(fog=FOG)
     sty = TR.lookup(MAIN, ids)
     base, _ = _varyings(renderer, cu, su, proj, None)
@@ -163,9 +134,9 @@ def test_tint_then_fog(renderer):
     keep = (base["visible"] == 1) & ~TR.classes(sty)[0]
     assert np.array_equal(got["visible"] == 1, keep) and tm["n_visible"] == int(keep.sum()) == 147
     for fld in ("ndc", "depth", "major", "minor"):
-        assert _bits_equal(np.ascontiguousarray(got[fld][keep]), np.ascontiguousarray(base[fld][keep])), fld
+        assert FM.bits_equal(np.ascontiguousarray(got[fld][keep]), np.ascontiguousarray(base[fld][keep])), fld
     # alpha: the dim-only reference, nothing else
-    assert _bits_equal(got["rgba"][keep][:, 3].copy(), TR.dimmed_alpha(base["rgba"][:, 3], sty)[keep].copy())
+    assert FM.bits_equal(got["rgba"][keep][:, 3].copy(), TR.dimmed_alpha(base["rgba"][:, 3], sty)[keep].copy())
     dist = AR.dist_f32(orc.Camera176.from_buffer_copy(bytes(cu)).cam_pos, su, g["pp"].tex, g["draws"]).astype(np.float64)[keep]
     ct = TR.tinted_rgb(base["rgba"][:, :3], sty)[keep]
     want, near_half = AR.fog_bytes(AR.fog_codes_f64(ct, dist, AR.params(atm)))
@@ -205,12 +176,12 @@ def test_known_answers(renderer):
     got, tm = _varyings(renderer, cu, su, PERSP, table)
     assert list(got["visible"]) == [0, 1, 1] and tm["n_visible"] == 2
     assert got["rgba"][1, 3] == (F32(127) / F32(255)) * base["rgba"][1, 3]
-    assert _bits_equal(got["rgba"][1, :3].copy(), base["rgba"][1, :3].copy())
+    assert FM.bits_equal(got["rgba"][1, :3].copy(), base["rgba"][1, :3].copy())
     for fld in ("ndc", "depth", "major", "minor", "rgba"):
-        assert _bits_equal(np.ascontiguousarray(got[fld][2]), np.ascontiguousarray(base[fld][2])), fld
+        assert FM.bits_equal(np.ascontiguousarray(got[fld][2]), np.ascontiguousarray(base[fld][2])), fld
     got, tm = _varyings(renderer, cu, su, PERSP, TR.pack(TR.entries({5: TR.entry((10, 20, 250), 255)}, 6)))
     assert tm["n_visible"] == 3 and (AR.bytes_of(got["rgba"][2:3]) == np.array([10.0, 20.0, 250.0])).all()
-    assert _bits_equal(got["rgba"][:, 3].copy(), base["rgba"][:, 3].copy()) and _bits_equal(got["rgba"][:2].copy(), base["rgba"][:2].copy())
+    assert FM.bits_equal(got["rgba"][:, 3].copy(), base["rgba"][:, 3].copy()) and FM.bits_equal(got["rgba"][:2].copy(), base["rgba"][:2].copy())
     # a table of length 4 does not reach cells 4 and 5
     got, tm = _varyings(renderer, cu, su, PERSP, TR.pack(TR.entries({3: TR.HIDE}, 6))[:32])
     assert list(got["visible"]) == [0, 1, 1] and tm["n_visible"] == 2
@@ -218,32 +189,17 @@ def test_known_answers(renderer):
     got, tm = _varyings(renderer, cu, su, PERSP, short)
     assert list(got["visible"]) == [0, 1, 1]
     for fld in ("ndc", "depth", "major", "minor", "rgba"):
-        assert _bits_equal(np.ascontiguousarray(got[fld][1:]), np.ascontiguousarray(base[fld][1:])), fld
+        assert FM.bits_equal(np.ascontiguousarray(got[fld][1:]), np.ascontiguousarray(base[fld][1:])), fld
 
 
 # ---- 5. image, depth and pick over the GPU's own styled records ---------------------------------------------------------------------------
 def _image_case(renderer, cam, order_mode, bg, splat_scale):
-    g, cu, su, proj, ids = _view("case_plane", cam, splat_scale)
-    _bind(renderer, g)
-    sp, _ = _varyings(renderer, cu, su, proj, TABLES["main"])
-    bgc, bgd = DR.bg_images(W, Hh) if bg else (None, None)
-    kw = dict(order_mode=order_mode, bg_rgba=bgc, bg_depth=bgd)
-    img, z, pick = renderer.render(cu, su, W, Hh, projection=proj, depth=True, pick=True, **kw)           # (the context keeps the table)
-    t = renderer.timings()
-    assert z.shape == (Hh, W) and pick.shape == (Hh, W) and pick.dtype == PICK_DTYPE
-    ref_img, ref_z, n_cover = DR.composite(sp, W, Hh, splat_scale=splat_scale, with_cover=True, **kw)
-    assert (n_cover > 0).mean() > 0.3 and ref_img[..., 3].max() > 0.5
-    dz = _check_against_ref(img, z, ref_img, ref_z)
-    ev = PR.composite(sp, W, Hh, splat_scale=splat_scale, **kw)
-    mi, en = PR.identities(g["draws"])
-    label = f"styles {cam} order={order_mode} bg={bg} scale={splat_scale}"
-    dw = PR.check_pick(pick, ev, sp, mi, en, label=label)
-    print(f"{label}: visible {t['n_visible']} pairs {t['n_pairs']} max|dz| {dz:.3e} max|dw| {dw:.3e}")
-    assert t["n_visible"] == int((sp["visible"] == 1).sum())
+    c = FM.image_case(renderer, cam, order_mode, bg, splat_scale, dict(antialias=0.0, atmosphere=A.OFF, tile_styles=TABLES["main"]), "styles")
+    t, pick = c["t"], c["pick"]
     hit = pick["weight"] > 0
     assert hit.mean() > 0.3 and not np.isin(pick["map_index"][hit], [8, 9]).any()
-    off = renderer.render(cu, su, W, Hh, projection=proj, tile_styles=b"", depth=True, pick=True, **kw)
-    assert not _same(img, off[0]) and renderer.timings()["n_pairs"] > t["n_pairs"] > 0
+    off = c["again"](tile_styles=b"", depth=True, pick=True)
+    assert not FM.same(c["img"], off[0]) and renderer.timings()["n_pairs"] > t["n_pairs"] > 0
     assert np.isin(off[2]["map_index"][off[2]["weight"] > 0], [8, 9]).any()           # (the hidden cells are on screen without the table)
     return t
 
@@ -266,179 +222,81 @@ def _styles_arg(name):
     return TABLES[name] if TABLES[name] is not None else b""
 
 
+def _set_table(renderer, name):
+    renderer.set_tile_styles(_styles_arg(name))
+
+
+MODE = FM.Mode({name: (None, dict(tile_styles=_styles_arg(name))) for name in TABLES}, _set_table, on="main")
+
+
 @pytest.fixture()
 def plain(renderer):
     """The plane case bound under its perspective camera, depth order over a background, and the plain synchronous frames (colour,
     depth, pick) under each table of TABLES."""
     g, cu, su, proj, _ = _view("case_plane", "persp")
-    _bind(renderer, g)
-    bgc, bgd = DR.bg_images(W, Hh)
-    kw = dict(order_mode=L.GSWT_ORDER_DEPTH, bg_rgba=bgc, bg_depth=bgd)
-    frames, pairs = {}, {}
-    for name in TABLES:
-        frames[name] = renderer.render(cu, su, W, Hh, projection=PERSP, tile_styles=_styles_arg(name), depth=True, pick=True, **kw)
-        pairs[name] = renderer.timings()["n_pairs"]
+    s = FM.plain_frames(renderer, MODE, g, su, cu)
     renderer.set_tile_styles(None)
-    assert len({bytes(np.ascontiguousarray(f[0])) for f in frames.values()}) == len(TABLES)
+    pairs = s["pairs"]
+    assert len({bytes(np.ascontiguousarray(f[0])) for f in s["frames"].values()}) == len(TABLES)
     assert pairs["tint_only"] == pairs["off"] and pairs["main"] < pairs["off"] and pairs["hide_only"] < pairs["off"]
-    return dict(g=g, cu=cu, su=su, kw=kw, bgc=bgc, bgd=bgd, frames=frames, pairs=pairs)
-
-
-def _device_frames(renderer, s, seq, *, waves, then=None):
-    """Submits frames under the tables named in `seq` with render_async, `waves` at a time in flight, into buffers of their own; sets
-    the context's table to `then` before waiting; returns (colour, depth, pick) as numpy arrays."""
-    import torch
-    bgc, bgd = torch.from_numpy(s["bgc"]).cuda(), torch.from_numpy(s["bgd"]).cuda()
-    outs = [(torch.zeros((Hh, W, 4), dtype=torch.float32, device="cuda"), torch.full((Hh, W), -1.0, dtype=torch.float32, device="cuda"),
-             torch.full((Hh, W, 4), -1, dtype=torch.int32, device="cuda")) for _ in seq]
-    torch.cuda.synchronize()
-    for i in range(0, len(seq), waves):
-        tickets = []
-        for name, (o, z, p) in zip(seq[i:i + waves], outs[i:i + waves]):
-            tickets.append(renderer.render_async(s["cu"], s["su"], W, Hh, o.data_ptr(), order_mode=L.GSWT_ORDER_DEPTH, bg_rgba_ptr=bgc.data_ptr(),
-                                                 bg_depth_ptr=bgd.data_ptr(), out_depth_ptr=z.data_ptr(), out_pick_ptr=p.data_ptr(),
-                                                 tile_styles=_styles_arg(name)))
-        assert len(set(tickets)) == len(tickets)
-        if then is not None:                                                 # must not reach the frames already submitted
-            renderer.set_tile_styles(_styles_arg(then))
-        for t in tickets:
-            renderer.render_wait(t)
-    torch.cuda.synchronize()
-    return [(o.cpu().numpy(), z.cpu().numpy(), p.cpu().numpy()) for o, z, p in outs]
-
-
-def _assert_frames(got, seq, s, what):
-    for k, (name, f) in enumerate(zip(seq, got)):
-        want = s["frames"][name]
-        assert _same(f[0], want[0]) and _same(f[1], want[1]) and _same(f[2], want[2]), (what, k, name)
+    return s
 
 
 def test_graph_replay_with_alternating_tables(renderer, plain):
-    renderer.set_option(L.GSWT_OPT_TIMING, 0)
-    renderer.set_option(L.GSWT_OPT_GRAPH, 1)
-    launches0, rebuilds0, _ = renderer.graph_stats()
     seq1 = ["off", "main", "hide_only", "main", "off", "tint_only"]
-    _assert_frames(_device_frames(renderer, plain, seq1, waves=1), seq1, plain, "graph, one slot")
     seq2 = ["main", "off", "tint_only", "hide_only", "off", "main"]
-    _assert_frames(_device_frames(renderer, plain, seq2, waves=2), seq2, plain, "graph, two slots")
-    launches, rebuilds, _ = renderer.graph_stats()
-    assert launches - launches0 == len(seq1) + len(seq2)
-    assert rebuilds - rebuilds0 >= 4                       # on <-> off is another k_project instantiation: the slot's graph is rebuilt
+    _, rebuilds, _ = FM.check_graph_replay(renderer, plain, MODE, seq1, seq2)
+    assert rebuilds >= 4                                   # on <-> off is another k_project instantiation: the slot's graph is rebuilt
 
 
 def test_async_frames_in_flight_keep_their_table(renderer, plain):
     assert renderer.frame_slots() >= 4
     seq = ["main", "off", "tint_only", "hide_only"]          # four frames in flight, each with a table of its own
-    _assert_frames(_device_frames(renderer, plain, seq, waves=4, then="tint_only"), seq, plain, "async")
+    FM.check_in_flight(renderer, plain, MODE, seq, waves=4, then="tint_only")
     seq = ["hide_only", "main", "main", "tint_only"]
-    _assert_frames(_device_frames(renderer, plain, seq, waves=4, then="off"), seq, plain, "async, then off")
+    FM.check_in_flight(renderer, plain, MODE, seq, waves=4, then="off", what="async, then off")
 
 
 @pytest.mark.parametrize("opt", [L.GSWT_OPT_COMPOSITE, L.GSWT_OPT_ITEM_ORDER, L.GSWT_OPT_NO_CHUNK_CULL], ids=["composite_dw", "item_order", "no_chunk_cull"])
 def test_compositor_and_cull_variants(renderer, plain, opt):
-    renderer.set_option(opt, 1)
-    got = renderer.render(plain["cu"], plain["su"], W, Hh, tile_styles=TABLES["main"], depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], ["main"], plain, opt)
+    FM.check_compositor_and_cull_variant(renderer, plain, MODE, opt, [MODE.on])
 
 
 def test_pair_buffer_overflow_rerun_keeps_the_table(renderer, plain):
-    assert plain["pairs"]["main"] > 256
-    renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)             # the next frame overflows and is re-run with grown buffers
-    got = renderer.render(plain["cu"], plain["su"], W, Hh, tile_styles=TABLES["main"], depth=True, pick=True, **plain["kw"])
-    assert renderer.timings()["n_pairs"] == plain["pairs"]["main"]
-    _assert_frames([got], ["main"], plain, "overflow, synchronous")
-    # ... and in flight, with the table changed between submit and the wait that re-runs the frame
-    renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)
-    _assert_frames(_device_frames(renderer, plain, ["main"], waves=1, then="hide_only"), ["main"], plain, "overflow, in flight")
-    assert renderer.timings()["n_pairs"] == plain["pairs"]["main"]
+    FM.check_overflow_rerun(renderer, plain, MODE, MODE.on, then="hide_only")
 
 
 def test_output_formats(renderer, plain):
-    f32 = plain["frames"]["main"][0]
-    kw = dict(tile_styles=TABLES["main"], **plain["kw"])
-    assert np.array_equal(renderer.render(plain["cu"], plain["su"], W, Hh, out_format=L.GSWT_OUT_RGBA8_UNORM, **kw), U8.rgba8(f32))
-    y, cbcr = renderer.render(plain["cu"], plain["su"], W, Hh, out_format=L.GSWT_VIDEO_NV12, **kw)
-    wy, wc = YUV.nv12(f32)
-    assert np.array_equal(y, wy) and np.array_equal(cbcr, wc)
+    FM.check_output_formats(renderer, plain, MODE, [MODE.on])
 
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_row_shards_tile_the_frame(renderer, plain, n):
-    kw = dict(tile_styles=TABLES["main"], depth=True, pick=True, **plain["kw"])
-    full = plain["frames"]["main"]
-    rows = renderer.shard_rows_padded(Hh, n)
-    parts = [np.zeros((Hh, W, 4), np.float32), np.zeros((Hh, W), np.float32), np.zeros((Hh, W), PICK_DTYPE)]
-    for r in range(n):
-        got = renderer.render(plain["cu"], plain["su"], W, Hh, shard=(r, n), **kw)
-        assert got[0].shape == (rows, W, 4)
-        k = 0
-        for ty in range(r, (Hh + 15) // 16, n):
-            y0, y1 = ty * 16, min(Hh, ty * 16 + 16)
-            for dst, src in zip(parts, got):
-                dst[y0:y1] = src[k * 16:k * 16 + (y1 - y0)]
-            k += 1
-    for a, b in zip(parts, full):
-        assert _same(a, b), n
+    FM.check_row_shards(renderer, plain, MODE, n, [MODE.on])
 
 
 @pytest.mark.parametrize("n", [2, 3, 5])
 def test_column_bands_unite_to_the_frame(renderer, plain, n):
-    kw = dict(tile_styles=TABLES["main"], depth=True, pick=True, **plain["kw"])
-    full = plain["frames"]["main"]
-    bw = renderer.shard_cols_padded(W, n)
-    parts = [np.zeros((Hh, W, 4), np.float32), np.zeros((Hh, W), np.float32), np.zeros((Hh, W), PICK_DTYPE)]
-    for r in range(n):
-        got = renderer.render(plain["cu"], plain["su"], W, Hh, shard=(r, n, "cols"), **kw)
-        x0, x1 = r * bw, min(W, (r + 1) * bw)
-        assert got[0].shape == (Hh, bw, 4)
-        for dst, src in zip(parts, got):
-            dst[:, x0:x1] = src[:, :x1 - x0]
-    for a, b in zip(parts, full):
-        assert _same(a, b), n
+    FM.check_column_bands(renderer, plain, MODE, n, [MODE.on])
 
 
 # ---- 7. off is untouched ----------------------------------------------------------------------------------------------------------------------
+def _null_table(r):
+    r.set_tile_styles(TABLES["main"])
+    r.set_tile_styles(None)
+    return {}
+
+
 def test_off_is_untouched():
     """A context on which no table was ever set; then NULL, an all-neutral table, and a table that is on (one hidden cell) but too short
-    to reach any drawn cell, so that the STY instantiation runs: byte-identical colour, depth, pick and counts every time."""
-    g, cu, su, proj, ids = _view("case_plane", "persp")
-    unf = orc.project_draws(orc.Camera176.from_buffer_copy(bytes(cu)), su, g["pp"].tex, g["draws"], height_map=g["hm"])
-    r = GSWTRenderer(0)
-    try:
-        _bind(r, g)
-        bgc, bgd = DR.bg_images(W, Hh)
-        kw = dict(order_mode=L.GSWT_ORDER_DEPTH, bg_rgba=bgc, bg_depth=bgd, projection=proj, depth=True, pick=True)
-        before = r.render(cu, su, W, Hh, **kw)
-        t0 = r.timings()
-        assert (before[2]["weight"] > 0).mean() > 0.3
-        n_short = int(ids.min())
-        assert n_short >= 1
-        neutral = TR.pack(TR.entries({3: TR.entry((9, 9, 9), 0, 0)}, TR.MAIN_N))           # a tint colour without strength is neutral
-        short = TR.pack(TR.entries({0: TR.HIDE}, n_short))
-        on = r.render(cu, su, W, Hh, tile_styles=TABLES["main"], **kw)
-        assert not _same(on[0], before[0]) and _same(r.render(cu, su, W, Hh, **kw)[0], on[0])        # (no argument: the context keeps the table)
-        for label, table in (("NULL", None), ("all neutral", neutral), ("too short", short)):
-            if table is None:
-                r.set_tile_styles(TABLES["main"])
-                r.set_tile_styles(None)
-                after = r.render(cu, su, W, Hh, **kw)
-            else:
-                after = r.render(cu, su, W, Hh, tile_styles=table, **kw)
-            t1 = r.timings()
-            for a, b in zip(before, after):
-                assert _same(a, b), label
-            assert (t0["n_visible"], t0["n_pairs"]) == (t1["n_visible"], t1["n_pairs"]), label
-            # ... and the vertex stage is still the oracle's, bit for bit
-            r.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-            r.render(cu, su, W, Hh, projection=proj)
-            got = r.read_projected().view(orc.SPLAT_DTYPE)
-            r.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
-            vis = unf["visible"] == 1
-            assert np.array_equal(got["visible"] == 1, vis), label
-            for fld in ("ndc", "depth", "major", "minor", "rgba"):
-                assert _bits_equal(np.ascontiguousarray(got[fld][vis]), np.ascontiguousarray(unf[fld][vis])), (label, fld)
-    finally:
-        r.close()
+    to reach any drawn cell, so that the STY instantiation runs: byte-identical colour, depth, pick and counts every time, and the vertex
+    stage is still the oracle's, bit for bit."""
+    n_short = int(_view("case_plane", "persp")[4].min())
+    assert n_short >= 1
+    neutral = TR.pack(TR.entries({3: TR.entry((9, 9, 9), 0, 0)}, TR.MAIN_N))           # a tint colour without strength is neutral
+    short = TR.pack(TR.entries({0: TR.HIDE}, n_short))
+    FM.check_off_is_untouched("persp", dict(tile_styles=TABLES["main"]), [("NULL", _null_table), ("all neutral", lambda r: dict(tile_styles=neutral)),
+                                                                        ("too short", lambda r: dict(tile_styles=short))])
 
 
 # ---- 8. refusals --------------------------------------------------------------------------------------------------------------------------------
@@ -460,54 +318,19 @@ def test_refused_tables_leave_the_table_in_force(renderer, plain):
     with pytest.raises(ValueError):
         renderer.set_tile_styles(b"\0" * 12)
     got = renderer.render(plain["cu"], plain["su"], W, Hh, depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], ["main"], plain, "after refused tables")
+    FM.assert_frames([got], ["main"], plain, "after refused tables")
     # the largest table is accepted; a table and n_styles = 0 switches styles off
     assert lib.gswt_set_tile_styles(h, big.ctypes.data_as(C.c_void_p), 1 << 20) == L.GSWT_OK
     got = renderer.render(plain["cu"], plain["su"], W, Hh, depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], ["off"], plain, "a hidden cell no draw names")
+    FM.assert_frames([got], ["off"], plain, "a hidden cell no draw names")
     renderer.set_tile_styles(TABLES["main"])
     assert lib.gswt_set_tile_styles(h, one, 0) == L.GSWT_OK
     got = renderer.render(plain["cu"], plain["su"], W, Hh, depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], ["off"], plain, "after n_styles = 0")
+    FM.assert_frames([got], ["off"], plain, "after n_styles = 0")
 
 
 def test_sequence_v2_is_refused_at_submit(renderer, plain):
-    import torch
-    lib, h = renderer._lib, renderer._h
-    cam = (C.c_char * 176).from_buffer_copy(bytes(plain["cu"]))
-    sc = (C.c_char * 160).from_buffer_copy(bytes(plain["su"]))
-    cfg = L.RenderConfig()
-    cfg.culling_dist, cfg.lod_enable_mask, cfg.order_mode = 1.0, 0xFFFFFFFF, L.GSWT_ORDER_DEPTH
-    out = np.full((Hh, W, 4), 7.0, np.float32)
-    z = np.full((Hh, W), -1.0, np.float32)
-    pk = np.full((Hh, W, 4), 0x55555555, np.uint32)
-    o_d = torch.full((Hh, W, 4), 7.0, dtype=torch.float32, device="cuda")
-    z_d = torch.full((Hh, W), -1.0, dtype=torch.float32, device="cuda")
-    p_d = torch.full((Hh, W, 4), 0x55555555, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    renderer.set_tile_styles(TABLES["main"])
-    renderer.set_option(L.GSWT_OPT_STRICT_VS, 0)
-    try:
-        assert lib.gswt_render_pick(h, cam, sc, C.byref(cfg), W, Hh, None, None, 0, vp(out), vp(z), vp(pk), 0) == L.GSWT_ERR_BAD_ARG
-        assert b"GSWT_OPT_STRICT_VS" in lib.gswt_last_error(h) and b"gswt_set_tile_styles" in lib.gswt_last_error(h)
-        ticket = C.c_int(-7)
-        assert lib.gswt_render_async_pick(h, cam, sc, C.byref(cfg), W, Hh, None, None, C.c_void_p(o_d.data_ptr()), C.c_void_p(z_d.data_ptr()),
-                                          C.c_void_p(p_d.data_ptr()), C.byref(ticket)) == L.GSWT_ERR_BAD_ARG
-        assert ticket.value == -7
-    finally:
-        renderer.set_option(L.GSWT_OPT_STRICT_VS, 1)
-    torch.cuda.synchronize()
-    assert (out == 7.0).all() and (z == -1.0).all() and (pk == 0x55555555).all()
-    assert bool((o_d == 7.0).all()) and bool((z_d == -1.0).all()) and bool((p_d == 0x55555555).all())
-    # the next valid frame renders, with the table still in force
-    got = renderer.render(plain["cu"], plain["su"], W, Hh, depth=True, pick=True, **plain["kw"])
-    _assert_frames([got], ["main"], plain, "after the refused v2 frame")
-    # after NULL sequence v2 renders again
-    renderer.set_tile_styles(None)
-    renderer.set_option(L.GSWT_OPT_STRICT_VS, 0)
-    assert lib.gswt_render_pick(h, cam, sc, C.byref(cfg), W, Hh, None, None, 0, vp(out), vp(z), vp(pk), 0) == L.GSWT_OK
-    assert not (out == 7.0).all()
+    FM.check_v2_refused_at_submit(renderer, plain, MODE, ("main",), (b"GSWT_OPT_STRICT_VS", b"gswt_set_tile_styles"))
 
 
 # ---- 9. through the frame harness: world-keyed styles across a build event ---------------------------------------------------------------------
@@ -548,7 +371,7 @@ def test_pipeline_keeps_a_world_cell_styled_across_a_build_event(renderer):
     # hidden through the pipeline: no pixel picks it, and the frame differs
     pipe.set_tile_styles(ST.TileStyles({cell: ST.HIDE}))
     on2, pk = pipe.render(cu2, W, Hh, pick=True)
-    assert not _same(on2, off2) and cell not in owners(pk, win2) and (pk["weight"] > 0).any()
+    assert not FM.same(on2, off2) and cell not in owners(pk, win2) and (pk["weight"] > 0).any()
     # the camera goes back one tile: another build event, the map index of the cell changes, the cell stays hidden
     cu1, swapped = visit(pos1)
     assert swapped and window()[0] == win1[0]
@@ -557,6 +380,6 @@ def test_pipeline_keeps_a_world_cell_styled_across_a_build_event(renderer):
     # with None the frame is the unstyled one again, and the cell is back
     pipe.set_tile_styles(None)
     off1, pk = pipe.render(cu1, W, Hh, pick=True)
-    assert cell in owners(pk, win1) and not _same(on1, off1)
-    assert _same(renderer.render(cu1, pipe.wang.scene_uniforms(), W, Hh, tile_styles=ST.TileStyles({cell: ST.HIDE}).table(*win1[:3])), on1)
-    assert _same(pipe.render(cu1, W, Hh, tile_styles=b""), off1)
+    assert cell in owners(pk, win1) and not FM.same(on1, off1)
+    assert FM.same(renderer.render(cu1, pipe.wang.scene_uniforms(), W, Hh, tile_styles=ST.TileStyles({cell: ST.HIDE}).table(*win1[:3])), on1)
+    assert FM.same(pipe.render(cu1, W, Hh, tile_styles=b""), off1)
