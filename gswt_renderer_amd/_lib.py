@@ -24,7 +24,6 @@ GSWT_ORDER_DEPTH = 1
 GSWT_OPT_NO_LOD_PREFILTER = 1
 GSWT_OPT_DEBUG_VARYINGS = 2
 GSWT_OPT_SEGMENT = 3
-GSWT_DEFAULT_SEGMENT = 1536      # the library's default for GSWT_OPT_SEGMENT (tests that change it put this back)
 GSWT_OPT_DEBUG_FLAGS = 4
 GSWT_OPT_TIMING = 5
 GSWT_OPT_PAIR_CAP = 6
@@ -40,6 +39,14 @@ GSWT_OPT_ITEM_ORDER = 16
 GSWT_OPT_PROJECTION = 17            # 0 perspective (default), 1 orthographic (gswt_renderer_amd/ortho.py)
 GSWT_PROJECTION_PERSPECTIVE, GSWT_PROJECTION_ORTHO = 0, 1
 GSWT_OPT_ANTIALIAS = 18             # variance of the screen-space pixel filter in 1/1024 px^2: 0 off (default), 1..4096
+# The library's default of every option that gswt_set_option stores as a plain value (struct Options, csrc/gswt_ctx.h; pinned against
+# the header by tests/test_option_defaults_cpu.py).  GSWT_OPT_DEPTH_PASSES and GSWT_OPT_DEBUG_FLAGS are not plain values.
+OPTION_DEFAULTS = {
+    GSWT_OPT_NO_LOD_PREFILTER: 0, GSWT_OPT_DEBUG_VARYINGS: 0, GSWT_OPT_SEGMENT: 1536, GSWT_OPT_TIMING: 2, GSWT_OPT_PAIR_CAP: 0,
+    GSWT_OPT_NO_MERGE_REUSE: 0, GSWT_OPT_DEFER_SWAP: 0, GSWT_OPT_GRAPH: 0, GSWT_OPT_STRICT_VS: 1, GSWT_OPT_COMPOSITE: 0,
+    GSWT_OPT_DEPTH_SORT: 0, GSWT_OPT_NO_CHUNK_CULL: 0, GSWT_OPT_ITEM_ORDER: 0, GSWT_OPT_PROJECTION: 0, GSWT_OPT_ANTIALIAS: 0,
+}
+GSWT_DEFAULT_SEGMENT = OPTION_DEFAULTS[GSWT_OPT_SEGMENT]
 # gswt_debug_read_scene items
 GSWT_SCENE_TEX = 0
 GSWT_SCENE_RAW_DEPTH = 1

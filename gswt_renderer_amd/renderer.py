@@ -6,6 +6,7 @@ CPU fallback: constructing a renderer without the HIP library or a GPU raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -100,6 +101,7 @@ class GSWTRenderer:
             raise GSWTError(rc, "gswt_create failed (no HIP device?)")
         self._h = h
         self.n_lists = (0, 0, 0)
+        self._options = dict(L.OPTION_DEFAULTS)      # the value last set through set_option, per plain option
 
     # -- lifecycle ---------------------------------------------------------------
     def close(self):
@@ -119,6 +121,27 @@ class GSWTRenderer:
 
     def set_option(self, key: int, value: int):
         self._check(self._lib.gswt_set_option(self._h, key, value))
+        if key in self._options:
+            self._options[key] = value
+
+    @contextlib.contextmanager
+    def options(self, **by_name):
+        """``with r.options(GRAPH=1, TIMING=0):`` sets the named plain options (GSWT_OPT_<name>, the keys of _lib.OPTION_DEFAULTS) in
+        the order given and on the way out, also when the body raises, puts back in reverse order what set_option had last set when
+        the block was entered: blocks nest.  An unknown name raises KeyError before anything is set.  The body may call set_option on
+        the same keys (GSWT_OPT_PAIR_CAP clears itself inside the library once a frame overflows it); the exit restores all the same."""
+        keys = [getattr(L, "GSWT_OPT_" + name, None) for name in by_name]
+        for name, key in zip(by_name, keys):
+            if key not in L.OPTION_DEFAULTS:
+                raise KeyError(name)
+        before = [self._options[key] for key in keys]
+        try:
+            for key, value in zip(keys, by_name.values()):
+                self.set_option(key, value)
+            yield self
+        finally:
+            for key, value in zip(reversed(keys), reversed(before)):
+                self.set_option(key, value)
 
     def set_atmosphere(self, a):
         """gswt_set_atmosphere: a is an atmosphere.Atmosphere (or 32 bytes of that layout); atmosphere.OFF or None switches the far

@@ -89,21 +89,16 @@ def restore_defaults(renderer):
     """The shared context as every test has to leave it: no table, no atmosphere, no filter, perspective, default options."""
     renderer.set_tile_styles(None)
     renderer.set_atmosphere(atmosphere.OFF)
-    for key, value in ((L.GSWT_OPT_ANTIALIAS, 0), (L.GSWT_OPT_PROJECTION, PERSP), (L.GSWT_OPT_STRICT_VS, 1), (L.GSWT_OPT_GRAPH, 0), (L.GSWT_OPT_TIMING, 2),
-                       (L.GSWT_OPT_SEGMENT, L.GSWT_DEFAULT_SEGMENT), (L.GSWT_OPT_COMPOSITE, 0), (L.GSWT_OPT_NO_CHUNK_CULL, 0),
-                       (L.GSWT_OPT_ITEM_ORDER, 0), (L.GSWT_OPT_PAIR_CAP, 0), (L.GSWT_OPT_DEBUG_VARYINGS, 0), (L.GSWT_OPT_NO_LOD_PREFILTER, 0)):
+    for key, value in L.OPTION_DEFAULTS.items():
         renderer.set_option(key, value)
     renderer.configure(None)
 
 
 def varyings(renderer, cu, su, **mode_kw):
     """(projected records, timings) of one debug-varyings frame under the mode keywords of GSWTRenderer.render."""
-    renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-    try:
+    with renderer.options(DEBUG_VARYINGS=1):
         renderer.render(cu, su, W, Hh, **mode_kw)
         return renderer.read_projected().view(orc.SPLAT_DTYPE), renderer.timings()
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
 
 
 _VIEWS = {}
@@ -134,9 +129,9 @@ def new_outputs(H_, W_):
 
 
 def assemble_row_shards(parts_per_rank, H_, n):
-    """The frame's (colour, depth, pick) out of those of its n row shards: rank r holds the 16-row screen tile rows r, r + n, ... one
-    below the other, the frame's last one with the rows it has."""
-    out = new_outputs(H_, parts_per_rank[0][0].shape[1])
+    """The frame's outputs (colour, depth, pick, or the ones a rank's tuple holds) out of those of its n row shards: rank r holds the
+    16-row screen tile rows r, r + n, ... one below the other, the frame's last one with the rows it has."""
+    out = [np.zeros((H_,) + p.shape[1:], p.dtype) for p in parts_per_rank[0]]
     for r, got in enumerate(parts_per_rank):
         for k, ty in enumerate(range(r, (H_ + 15) // 16, n)):
             y0, y1 = ty * 16, min(H_, ty * 16 + 16)
@@ -146,9 +141,9 @@ def assemble_row_shards(parts_per_rank, H_, n):
 
 
 def assemble_column_bands(parts_per_rank, W_, band_w):
-    """The frame's (colour, depth, pick) out of those of its column bands: rank r holds columns r band_w ... of the frame, the last
-    band as many as are left."""
-    out = new_outputs(parts_per_rank[0][0].shape[0], W_)
+    """The frame's outputs (as in assemble_row_shards) out of those of its column bands: rank r holds columns r band_w ... of the
+    frame, the last band as many as are left."""
+    out = [np.zeros(p.shape[:1] + (W_,) + p.shape[2:], p.dtype) for p in parts_per_rank[0]]
     for r, got in enumerate(parts_per_rank):
         x0, x1 = r * band_w, min(W_, (r + 1) * band_w)
         for dst, src in zip(out, got):
@@ -363,14 +358,9 @@ def refusal_probe(renderer):
 
 
 def check_refused(renderer, refused, cam, sc, cfg, needles, what, opt=None):
-    """refused(...) with option `opt` = (key, value) set for the two calls and back at 1 whatever they do."""
-    if opt:
-        renderer.set_option(*opt)
-    try:
+    """refused(...) with the options `opt` (keywords of GSWTRenderer.options) set for the two calls and put back whatever they do."""
+    with renderer.options(**(opt or {})):
         refused(cam, sc, cfg, needles, what)
-    finally:
-        if opt:
-            renderer.set_option(opt[0], 1)
 
 
 def check_v2_refused_at_submit(renderer, s, mode, names, needles, off="off"):
@@ -380,7 +370,7 @@ def check_v2_refused_at_submit(renderer, s, mode, names, needles, off="off"):
     cam, sc, cfg = frame_blocks(s["cu"], s["su"])
     for name in names:
         mode.set_state(renderer, name)
-        check_refused(renderer, refused, cam, sc, cfg, needles, name, opt=(L.GSWT_OPT_STRICT_VS, 0))
+        check_refused(renderer, refused, cam, sc, cfg, needles, name, opt=dict(STRICT_VS=0))
         got = renderer.render(s["cu"], s["su"], W, Hh, depth=True, pick=True, **s["kw"])
         assert_frames([got], [name], s, ("after the refused v2 frame", name))
     mode.set_state(renderer, off)

@@ -294,7 +294,7 @@ def test_refusals(renderer, plain):
         assert lib.gswt_set_option(h, AA_OPT, ok) == L.GSWT_OK
     renderer.set_option(AA_OPT, 307)
 
-    cases = [("sequence v2", scene(), (L.GSWT_OPT_STRICT_VS, 0), b"GSWT_OPT_STRICT_VS"),
+    cases = [("sequence v2", scene(), dict(STRICT_VS=0), b"GSWT_OPT_STRICT_VS"),
              ("splat_scale 0", scene(0.0), None, b"splat_scale"),
              ("splat_scale inf", scene(float("inf")), None, b"splat_scale"),
              ("splat_scale NaN", scene(float("nan")), None, b"splat_scale"),

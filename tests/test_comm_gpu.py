@@ -7,6 +7,7 @@ import pytest
 from gswt_renderer_amd import _lib as L
 from gswt_renderer_amd.renderer import GSWTRenderer, GSWTError
 from oracle import gswt_oracle as orc
+from tests import frame_outputs as FO
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -133,11 +134,9 @@ def test_frames_overlap_the_previous_frames_gather():
     timestamps from the device (gswt_debug_frame_times): on every rank frame i + 1 STARTS before gather i has finished, for every i,
     and the gathered frames are the unsharded renders bit for bit."""
     import torch
-    import bench
     from gswt_renderer_amd import host, workloads
-    w, wang, cu0, vp0, sort = bench.build_workload("c3")
-    W, Hh = w["width"], w["height"]
-    su = wang.scene_uniforms()
+    c3 = FO.workload("c3")
+    W, Hh, su = c3["W"], c3["H"], c3["su"]
     cam = workloads.camera_for("c3")
     n, n_frames = 3, 6
     cams = [host.camera_uniforms((cam["pos"][0] + 0.2 * k, cam["pos"][1] + 0.3 * k, cam["pos"][2]),
@@ -146,9 +145,7 @@ def test_frames_overlap_the_previous_frames_gather():
     rs = [GSWTRenderer(0) for _ in range(n)]
     try:
         for r in rs:
-            wang.upload_to(r)
-            r.configure(None)
-            r.set_draws(sort.draws, sort.merged_gs_index, sort.merged_map_id, sort.merged_lod_id)
+            FO.bind_workload(r, c3)
             r.set_option(L.GSWT_OPT_TIMING, 1)
         wants = [rs[0].render(c, su, W, Hh, transmittance_eps=1e-5) for c in cams]
         GSWTRenderer.group_init(rs)

@@ -10,6 +10,7 @@ import pytest
 
 from gswt_renderer_amd import _lib as L
 from oracle import gswt_oracle as orc
+from tests import frame_outputs as FO
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -18,18 +19,12 @@ TOL = 1e-4
 
 def _setup(renderer, name):
     import bench
-    w, wang, cu, vp, sort = bench.build_workload(name)
-    W, Hh = w["width"], w["height"]
-    su = wang.scene_uniforms()
-    hm = wang.height_map() if int(wang.user.surface_type) == 1 else None
-    wang.upload_to(renderer)
-    renderer.configure(hm)
-    renderer.set_draws(sort.draws, sort.merged_gs_index, sort.merged_map_id, sort.merged_lod_id)
-    tex, draws = bench.oracle_draws(wang, sort, vp)
-    ocu = orc.Camera176.from_buffer_copy(bytes(cu))
-    osu = orc.Scene160.from_buffer_copy(bytes(su))
-    # (wang owns the memory tex and the draws' index arrays are views of: it has to outlive them)
-    return dict(W=W, H=Hh, cu=cu, su=su, hm=hm, tex=tex, draws=draws, ocu=ocu, osu=osu, wang=wang, sort=sort)
+    s = dict(FO.workload(name))                            # (a copy: one test below puts other cameras into it)
+    FO.bind_workload(renderer, s)
+    # (s["wang"] owns the memory tex and the draws' index arrays are views of: it has to outlive them)
+    s["tex"], s["draws"] = bench.oracle_draws(s["wang"], s["sort"], s["vp"])
+    s["ocu"], s["osu"] = orc.Camera176.from_buffer_copy(bytes(s["cu"])), orc.Scene160.from_buffer_copy(bytes(s["su"]))
+    return s
 
 
 @pytest.mark.parametrize("name", ["c3", "c3d"])
@@ -49,20 +44,17 @@ def test_depth_order_at_baseline_size(renderer, name):
     # the two ways to get there -- global radix passes on the depth bits in front of the tile passes (the default), or tile passes first and
     # every tile's slice depth-sorted in LDS (the default; GSWT_OPT_DEPTH_SORT = 0 / 2; lists beyond 16 384 pairs through global memory, see
     # the test below) -- give the same bits
-    try:
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 1)
+    with renderer.options(DEPTH_SORT=1):
         l0, g0, _ = renderer.depth_stats()
         img_g = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH)
         l1, g1, max_len = renderer.depth_stats()
         assert (l1 - l0, g1 - g0) == (0, 1) and max_len > 256
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 2)
+    with renderer.options(DEPTH_SORT=2):
         img_l = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH)
         l2, g2, _ = renderer.depth_stats()
         print(f"{name}: longest tile list {max_len} pairs; tile-local frames {l2 - l1}, global {g2 - g1}")
         assert (l2 - l1, g2 - g1) == (1, 0)
-        assert np.array_equal(img_g, img) and np.array_equal(img_l, img)
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
+    assert np.array_equal(img_g, img) and np.array_equal(img_l, img)
     # the mode is not a no-op: neighbouring Wang tiles interpenetrate, and a tile's presorted list is only ordered along one of nine
     # directions, so the reference order and the true depth order give different images
     d = H.max_abs_diff(ref_d, ref_r)
@@ -101,15 +93,14 @@ def test_tile_local_depth_sort_long_lists(renderer):
     from gswt_renderer_amd import host, workloads
     s = _setup(renderer, "c3")
     cam = workloads.camera_for("c3")
-    try:
-        for (W, Hh), lo, hi in (((800, 448), 4096, 16384), ((256, 144), 16384, 1 << 30)):
-            cu, vp = host.camera_uniforms(cam["pos"], cam["target"], cam["up"], cam["fovy"], cam["near"], cam["far"], W, Hh)
-            s["cu"], s["ocu"] = cu, orc.Camera176.from_buffer_copy(bytes(cu))
-            s["tex"], s["draws"] = bench.oracle_draws(s["wang"], s["sort"], vp)
-            renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 1)
+    for (W, Hh), lo, hi in (((800, 448), 4096, 16384), ((256, 144), 16384, 1 << 30)):
+        cu, vp = host.camera_uniforms(cam["pos"], cam["target"], cam["up"], cam["fovy"], cam["near"], cam["far"], W, Hh)
+        s["cu"], s["ocu"] = cu, orc.Camera176.from_buffer_copy(bytes(cu))
+        s["tex"], s["draws"] = bench.oracle_draws(s["wang"], s["sort"], vp)
+        with renderer.options(DEPTH_SORT=1):
             img_g = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH)
             _, _, max_len = renderer.depth_stats()
-            renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
+        with renderer.options(DEPTH_SORT=0):
             l0, g0, _ = renderer.depth_stats()
             img_l = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH)
             l1, g1, _ = renderer.depth_stats()
@@ -120,17 +111,10 @@ def test_tile_local_depth_sort_long_lists(renderer):
             ref_d, st = orc.render(s["ocu"], s["osu"], s["tex"], s["draws"], W, Hh, height_map=s["hm"], order_mode=1)
             assert renderer.timings()["n_pairs"] == st["n_pairs16"]
             assert H.max_abs_diff(img_l, ref_d) <= TOL
-            renderer.set_option(L.GSWT_OPT_GRAPH, 1)
-            renderer.set_option(L.GSWT_OPT_TIMING, 0)
-            try:
+            with renderer.options(GRAPH=1, TIMING=0):
                 img_q = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH)
                 img_q2 = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH, transmittance_eps=1e-5)
-            finally:
-                renderer.set_option(L.GSWT_OPT_GRAPH, 0)
-                renderer.set_option(L.GSWT_OPT_TIMING, 2)
             assert np.array_equal(img_q, img_g) and H.max_abs_diff(img_q2, ref_d) <= TOL
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
 
 
 @pytest.mark.parametrize("depth_sort", [0, 1])
@@ -149,30 +133,24 @@ def test_depth_order_frames_replay_as_one_graph(renderer, depth_sort):
         tgt = (cam["target"][0] + 0.15 * k, cam["target"][1] + 0.4 * k, cam["target"][2] - 0.05 * k)
         cams.append(host.camera_uniforms(pos, tgt, cam["up"], cam["fovy"], cam["near"], cam["far"], W, Hh)[0])
     outs = [torch.empty((Hh, W, 4), dtype=torch.float32, device="cuda") for _ in cams]
-    renderer.set_option(L.GSWT_OPT_TIMING, 0)
-    renderer.set_option(L.GSWT_OPT_DEPTH_SORT, depth_sort)
-    try:
+    with renderer.options(TIMING=0, DEPTH_SORT=depth_sort):
         want = []
         for cu, o in zip(cams, outs):
             renderer.render_wait(renderer.render_async(cu, s["su"], W, Hh, o.data_ptr(), order_mode=L.GSWT_ORDER_DEPTH, transmittance_eps=1e-5))
             want.append(o.cpu().numpy().copy())
         g0 = renderer.graph_stats()
-        renderer.set_option(L.GSWT_OPT_GRAPH, 1)
-        tickets = []
-        for o in outs:
-            o.zero_()
-        torch.cuda.synchronize()                        # (torch's fills run on ITS stream: nothing orders them against the frame slots' streams)
-        for cu, o in zip(cams, outs):
-            if len(tickets) >= renderer.frame_slots():
-                renderer.render_wait(tickets.pop(0))
-            tickets.append(renderer.render_async(cu, s["su"], W, Hh, o.data_ptr(), order_mode=L.GSWT_ORDER_DEPTH, transmittance_eps=1e-5))
-        for tk in tickets:
-            renderer.render_wait(tk)
-        g1 = renderer.graph_stats()
-    finally:
-        renderer.set_option(L.GSWT_OPT_GRAPH, 0)
-        renderer.set_option(L.GSWT_OPT_TIMING, 2)
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
+        with renderer.options(GRAPH=1):
+            tickets = []
+            for o in outs:
+                o.zero_()
+            torch.cuda.synchronize()                    # (torch's fills run on ITS stream: nothing orders them against the frame slots' streams)
+            for cu, o in zip(cams, outs):
+                if len(tickets) >= renderer.frame_slots():
+                    renderer.render_wait(tickets.pop(0))
+                tickets.append(renderer.render_async(cu, s["su"], W, Hh, o.data_ptr(), order_mode=L.GSWT_ORDER_DEPTH, transmittance_eps=1e-5))
+            for tk in tickets:
+                renderer.render_wait(tk)
+            g1 = renderer.graph_stats()
     assert g1[0] - g0[0] == len(cams)                   # every frame went through hipGraphLaunch
     for i, (a, o) in enumerate(zip(want, outs)):
         b = o.cpu().numpy()
@@ -194,18 +172,17 @@ def test_depth_sort_pass_count_follows_the_depth_range(renderer):
     t = renderer.timings()
     assert st["n_visible"] > 10000 and t["n_visible"] == st["n_visible"] and t["n_pairs"] == st["n_pairs16"]
     assert H.max_abs_diff(img, ref_d) <= TOL
-    try:
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 1)
-        l0, g0, _ = renderer.depth_stats()
-        for passes in (1, 2, 4):
-            renderer.set_option(L.GSWT_OPT_DEPTH_PASSES, passes)
-            img_p = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH)
-            assert np.array_equal(img, img_p), passes
-        l1, g1, _ = renderer.depth_stats()
-        assert l1 == l0 and g1 - g0 >= 3
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEPTH_PASSES, 3)
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
+    with renderer.options(DEPTH_SORT=1):
+        try:
+            l0, g0, _ = renderer.depth_stats()
+            for passes in (1, 2, 4):
+                renderer.set_option(L.GSWT_OPT_DEPTH_PASSES, passes)         # (not a plain value: the library adapts it)
+                img_p = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH)
+                assert np.array_equal(img, img_p), passes
+            l1, g1, _ = renderer.depth_stats()
+            assert l1 == l0 and g1 - g0 >= 3
+        finally:
+            renderer.set_option(L.GSWT_OPT_DEPTH_PASSES, 3)
 
 
 @pytest.mark.parametrize("depth_sort", [0, 1])
@@ -218,17 +195,9 @@ def test_depth_order_survives_a_pair_overflow_with_and_without_the_graph(rendere
     want = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH)
     n_pairs = renderer.timings()["n_pairs"]
     assert n_pairs > 10000
-    try:
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, depth_sort)
-        for graph in (0, 1):
-            renderer.set_option(L.GSWT_OPT_GRAPH, graph)
-            renderer.set_option(L.GSWT_OPT_TIMING, 0 if graph else 2)
-            renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)         # the next frame overflows; the capacity then grows
+    for graph in (0, 1):
+        # PAIR_CAP: the next frame overflows; the capacity then grows
+        with renderer.options(DEPTH_SORT=depth_sort, GRAPH=graph, TIMING=0 if graph else 2, PAIR_CAP=256):
             img = renderer.render(s["cu"], s["su"], W, Hh, order_mode=L.GSWT_ORDER_DEPTH)
             assert renderer.timings()["n_pairs"] == n_pairs
             assert np.array_equal(img, want), graph
-    finally:
-        renderer.set_option(L.GSWT_OPT_PAIR_CAP, 0)
-        renderer.set_option(L.GSWT_OPT_GRAPH, 0)
-        renderer.set_option(L.GSWT_OPT_TIMING, 2)
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)

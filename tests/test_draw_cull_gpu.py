@@ -29,19 +29,7 @@ TOL = 1e-4
 W, Hh = R.W, R.H
 ALL = 0xFFFFFFFF
 PATHS = ("set_draws", "merge_groups", "worker")
-DEBUG = ((L.GSWT_OPT_NO_LOD_PREFILTER, 1, 0), (L.GSWT_OPT_DEBUG_VARYINGS, 1, 0))
-
-
-@contextlib.contextmanager
-def _options(renderer, *triples):
-    """(key, value, value to put back): set on entry, put back in a finally -- the renderer is shared by the whole session."""
-    try:
-        for key, value, _ in triples:
-            renderer.set_option(key, value)
-        yield
-    finally:
-        for key, _, back in triples:
-            renderer.set_option(key, back)
+DEBUG = dict(NO_LOD_PREFILTER=1, DEBUG_VARYINGS=1)
 
 
 def _c_float(x):
@@ -152,7 +140,7 @@ def sweep(renderer):
                 img = pipe.render(cu, W, Hh, culling_dist=_c_float(cd), lod_enable_mask=mask)
                 t = renderer.timings()
                 plain.append((img, {k: t[k] for k in ("n_draws", "n_instanced", "n_visible", "n_pairs")}))
-        with _options(renderer, *DEBUG):
+        with renderer.options(**DEBUG):
             with _bound(renderer, path) as pipe:
                 flags = [_debug_visible(renderer, pipe, cu, None, W, Hh, _c_float(cd), mask) for cd, mask in SWEEP]
         out[path] = (flags, plain)
@@ -255,7 +243,7 @@ def _check_hand_frames(renderer, case, cam_u, su, vp, frames, w, h, keep_of, pro
     for cd, mask in frames:
         img = renderer.render(cam_u, su, w, h, culling_dist=_c_float(cd), lod_enable_mask=mask, **kw)
         plain.append((img, renderer.timings()))
-    with _options(renderer, *DEBUG):
+    with renderer.options(**DEBUG):
         case.upload(renderer)
         got = [_debug_visible(renderer, None, cam_u, su, w, h, _c_float(cd), mask, **kw) for cd, mask in frames]
         if projection is None:
@@ -438,7 +426,7 @@ def test_knife_edges(renderer, path):
     assert len(observable) == 10 and seen_axes == {"x", "y"} and {sc.kind[i] for i in observable} == {"plain", "blend"}
     cu, _ = _camera()
     flipped_visible = 0
-    with _options(renderer, *DEBUG):
+    with renderer.options(**DEBUG):
         with _bound(renderer, path) as pipe:
             for i in chosen:
                 g = sc.g(i)
@@ -494,7 +482,7 @@ def _variant_graph(renderer, pipe, cu):
     want = _sync_frames(renderer, pipe, cu, values[:2])
     _check_sync_against_oracle(want, values[:2])
     assert not np.array_equal(want[0][0], want[1][0])
-    with _options(renderer, (L.GSWT_OPT_TIMING, 0, 2), (L.GSWT_OPT_GRAPH, 1, 0)):
+    with renderer.options(TIMING=0, GRAPH=1):
         _sync_frames(renderer, pipe, cu, values[:2])                       # the slot's graph exists from here on
         s0 = renderer.graph_stats()
         got = _sync_frames(renderer, pipe, cu, values)
@@ -534,7 +522,7 @@ def _variant_overflow(renderer, pipe, cu):
     _check_sync_against_oracle(want, values)
     for (cd, mask), w in zip(values, want):
         assert w[2] > 256
-        with _options(renderer, (L.GSWT_OPT_PAIR_CAP, 256, 0)):
+        with renderer.options(PAIR_CAP=256):
             got = _sync_frames(renderer, pipe, cu, [(cd, mask)])[0]
         assert np.array_equal(got[0], w[0]) and got[1:] == w[1:], (cd, mask)
 
@@ -544,7 +532,7 @@ def _variant_depth_order(renderer, pipe, cu):
     values = VALUES[:4]
     want = None
     for depth_sort in (0, 1):
-        with _options(renderer, (L.GSWT_OPT_DEPTH_SORT, depth_sort, 0)):
+        with renderer.options(DEPTH_SORT=depth_sort):
             got = _sync_frames(renderer, pipe, cu, values, order_mode=L.GSWT_ORDER_DEPTH)
         if want is None:
             want = got
@@ -611,7 +599,7 @@ def _variant_chunk_cull(renderer, pipe, cu):
     values = [VALUES[0], (0.5, ALL)]
     want = _sync_frames(renderer, pipe, cu, values)
     _check_sync_against_oracle(want, values)
-    with _options(renderer, (L.GSWT_OPT_NO_CHUNK_CULL, 1, 0)):
+    with renderer.options(NO_CHUNK_CULL=1):
         got = _sync_frames(renderer, pipe, cu, values)
     for g, w in zip(got, want):
         assert np.array_equal(g[0], w[0]) and g[1:] == w[1:]
@@ -664,11 +652,9 @@ def _variant_ortho(renderer):
     su = orc.scene_uniforms(num_lod=pp.n_lod, map_half_wh=(2, 2))
     frames = [(0.0, ALL), (0.25, ALL), (0.5, ALL), (1.0, ALL), (1.0, 0), (float("nan"), ALL)]
     lods = [0] * len(names)
-    try:
+    with renderer.options(PROJECTION=L.GSWT_PROJECTION_ORTHO):     # (the frames set it themselves; the block puts it back)
         seen = _check_hand_frames(renderer, case, cam.uniforms(), su, vp, frames, W2, H2,
                                   lambda i, cd, mask: R.keeps(terms[i], cd) and R.lod_kept(mask, lods[i]), projection=L.GSWT_PROJECTION_ORTHO)
-    finally:
-        renderer.set_option(L.GSWT_OPT_PROJECTION, L.GSWT_PROJECTION_PERSPECTIVE)
     nvis = seen[0][1]
     assert all(n > 0 for n in nvis), dict(zip(names, nvis))
     by_cd = {repr(cd) + ("" if mask else "/0"): dict(zip(names, keep)) for (cd, mask), (keep, _) in zip(frames, seen)}

@@ -7,6 +7,7 @@ import pytest
 from gswt_renderer_amd import _lib as L
 from gswt_renderer_amd.renderer import GSWTError, make_draw
 from oracle import gswt_oracle as orc
+from tests import frame_outputs as FO
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -77,13 +78,12 @@ def test_huge_splats_cover_many_tiles(renderer):
     su = orc.scene_uniforms(num_lod=pp.n_lod, map_half_wh=(1, 2), splat_scale=80.0)
     ref, st = orc.render(cam, su, pp.tex, case.orc_draws, W, Hh)
     for seg in (256, 512, 1536, 4096):
-        renderer.set_option(L.GSWT_OPT_SEGMENT, seg)
-        img = renderer.render(cam, su, W, Hh)
-        assert renderer.timings()["n_pairs"] == st["n_pairs16"] > 100000
-        assert H.max_abs_diff(img, ref) <= TOL
-        img = renderer.render(cam, su, W, Hh, transmittance_eps=1e-5)
-        assert H.max_abs_diff(img, ref) <= TOL
-    renderer.set_option(L.GSWT_OPT_SEGMENT, L.GSWT_DEFAULT_SEGMENT)
+        with renderer.options(SEGMENT=seg):
+            img = renderer.render(cam, su, W, Hh)
+            assert renderer.timings()["n_pairs"] == st["n_pairs16"] > 100000
+            assert H.max_abs_diff(img, ref) <= TOL
+            img = renderer.render(cam, su, W, Hh, transmittance_eps=1e-5)
+            assert H.max_abs_diff(img, ref) <= TOL
 
 
 def test_point_cloud_clip_and_scene_scale(renderer):
@@ -175,29 +175,28 @@ def test_fenced_consumer_never_sees_an_overflowed_frame(renderer):
     stream = torch.cuda.Stream()
     renderer.set_stream(stream.cuda_stream)
     try:
-        out = torch.zeros((Hh, W, 4), dtype=torch.float32, device="cuda")
-        seen = torch.zeros_like(out)
-        torch.cuda.synchronize()
-        renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)             # every frame overflows until the capacity has grown
-        ticket = renderer.render_async(cu, su, W, Hh, out.data_ptr())
-        renderer.render_fence(ticket)
-        with torch.cuda.stream(stream):
-            seen.copy_(out, non_blocking=True)                     # the fenced consumer
-        renderer.render_wait(ticket)
-        stream.synchronize()
-        assert renderer.timings()["n_pairs"] == n_pairs
-        assert np.array_equal(seen.cpu().numpy(), want)
-        # the same with a sort event between submit and wait: the pending frame finishes against ITS draw list
-        renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)
-        out.zero_()
-        torch.cuda.synchronize()
-        ticket = renderer.render_async(cu, su, W, Hh, out.data_ptr())
-        renderer.set_draws([])
-        renderer.render_wait(ticket)
-        torch.cuda.synchronize()
-        assert np.array_equal(out.cpu().numpy(), want)
+        with renderer.options(PAIR_CAP=256):                      # every frame overflows until the capacity has grown
+            out = torch.zeros((Hh, W, 4), dtype=torch.float32, device="cuda")
+            seen = torch.zeros_like(out)
+            torch.cuda.synchronize()
+            ticket = renderer.render_async(cu, su, W, Hh, out.data_ptr())
+            renderer.render_fence(ticket)
+            with torch.cuda.stream(stream):
+                seen.copy_(out, non_blocking=True)                     # the fenced consumer
+            renderer.render_wait(ticket)
+            stream.synchronize()
+            assert renderer.timings()["n_pairs"] == n_pairs
+            assert np.array_equal(seen.cpu().numpy(), want)
+            # the same with a sort event between submit and wait: the pending frame finishes against ITS draw list
+            renderer.set_option(L.GSWT_OPT_PAIR_CAP, 256)
+            out.zero_()
+            torch.cuda.synchronize()
+            ticket = renderer.render_async(cu, su, W, Hh, out.data_ptr())
+            renderer.set_draws([])
+            renderer.render_wait(ticket)
+            torch.cuda.synchronize()
+            assert np.array_equal(out.cpu().numpy(), want)
     finally:
-        renderer.set_option(L.GSWT_OPT_PAIR_CAP, 0)
         renderer.set_stream(0)
 
 
@@ -215,27 +214,26 @@ def test_more_shards_than_tile_columns_or_rows(renderer):
     n = 8
     bw = renderer.shard_cols_padded(W, n)
     for level in (2, 1, 0):
-        renderer.set_option(L.GSWT_OPT_TIMING, level)
-        uni = np.zeros_like(full)
-        for _ in range(2):                              # twice: a sticky error of the first frame would fail the second
+        with renderer.options(TIMING=level):
+            uni = np.zeros_like(full)
+            for _ in range(2):                              # twice: a sticky error of the first frame would fail the second
+                for r in range(n):
+                    part = renderer.render(cam, su, W, Hh, shard=(r, n, "cols"))
+                    x0, x1 = r * bw, min(W, (r + 1) * bw)
+                    if x1 > x0:
+                        uni[:, x0:x1] = part[:, :x1 - x0]
+                    else:
+                        assert renderer.timings()["n_tiles"] == 0 and not part.any()
+            assert np.array_equal(uni, full)
+            rows_p = renderer.shard_rows_padded(Hh, n)
+            uni = np.zeros_like(full)
             for r in range(n):
-                part = renderer.render(cam, su, W, Hh, shard=(r, n, "cols"))
-                x0, x1 = r * bw, min(W, (r + 1) * bw)
-                if x1 > x0:
-                    uni[:, x0:x1] = part[:, :x1 - x0]
-                else:
-                    assert renderer.timings()["n_tiles"] == 0 and not part.any()
-        assert np.array_equal(uni, full)
-        rows_p = renderer.shard_rows_padded(Hh, n)
-        uni = np.zeros_like(full)
-        for r in range(n):
-            part = renderer.render(cam, su, W, Hh, shard=(r, n))
-            assert part.shape == (rows_p, W, 4)
-            for y in range(Hh):
-                if (y // 16) % n == r:
-                    uni[y] = part[((y // 16) // n) * 16 + (y % 16)]
-        assert np.array_equal(uni, full)
-    renderer.set_option(L.GSWT_OPT_TIMING, 2)
+                part = renderer.render(cam, su, W, Hh, shard=(r, n))
+                assert part.shape == (rows_p, W, 4)
+                for y in range(Hh):
+                    if (y // 16) % n == r:
+                        uni[y] = part[((y // 16) // n) * 16 + (y % 16)]
+            assert np.array_equal(uni, full)
 
 
 def test_pair_total_is_carried_in_64_bits(renderer):
@@ -346,14 +344,8 @@ def test_frame_whose_live_chunks_outgrow_its_launch_grid_is_rerun(renderer):
     """The launch grids of k_project / k_emit follow the longest live-chunk list of the last finished frame (+ 50 % + 256, and only where that
     removes at least half of the launch table).  A camera that sees almost nothing, then one that sees the scene: the second frame's lists
     outgrow its grid, k_totals flags it, the host re-runs it over the whole table -- the image and the counts are the full frame's."""
-    import bench
     from gswt_renderer_amd import host, workloads
-    w, wang, cu, vp, sort = bench.build_workload("c3")
-    W, Hh = w["width"], w["height"]
-    su = wang.scene_uniforms()
-    wang.upload_to(renderer)
-    renderer.configure(None)
-    renderer.set_draws(sort.draws, sort.merged_gs_index, sort.merged_map_id, sort.merged_lod_id)
+    W, Hh, cu, su = FO.bind_workload(renderer, FO.workload("c3"))
     cam = workloads.camera_for("c3")
     pos = cam["pos"]
     up_cu, _ = host.camera_uniforms(pos, (pos[0] + 0.3, pos[1] + 0.2, pos[2] + 10.0), cam["up"], cam["fovy"], cam["near"], cam["far"], W, Hh)      # at the sky

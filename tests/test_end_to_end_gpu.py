@@ -96,11 +96,8 @@ def test_more_than_8192_screen_tiles(renderer):
     first one's tiles itself; a small segment size gives many tiles several work items (k_combine)."""
     from gswt_renderer_amd import _lib as L
     cfg = dict(tile_map_half_wh=(3, 3), surface_type=0, lod_max_dist=20.0, tile_sort_type=3, merge_type=2)
-    renderer.set_option(L.GSWT_OPT_SEGMENT, 256)
-    try:
+    with renderer.options(SEGMENT=256):
         img, ref, kinds, st = _run_case(renderer, cfg, ((4.2, 1.0, 3.0), (5.0, 3.0, 2.5)), 2304, 1296, bg=True)
-    finally:
-        renderer.set_option(L.GSWT_OPT_SEGMENT, L.GSWT_DEFAULT_SEGMENT)
     assert st["n_visible"] > 500
     assert H.max_abs_diff(img, ref) <= TOL
 
@@ -401,19 +398,18 @@ def test_merged_group_reuse_across_sort_events(renderer):
     path = [((4.2 + 0.35 * k, 1.0 + 0.5 * k, 1.5), (5.0 + 0.3 * k, 4.0 + 0.55 * k, 1.0)) for k in range(9)]
     results = {}
     for reuse in (False, True):
-        renderer.set_option(L.GSWT_OPT_NO_MERGE_REUSE, 0 if reuse else 1)
-        pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)
-        built0, reused0 = renderer.merge_stats()
-        out = []
-        for pos, tgt in path:
-            cu, vp = host.camera_uniforms(pos, tgt, (0, 0, 1), 45.0, 0.1, 2400.0, W, Hh)
-            pipe.update(pos, vp, force_sort=True)
-            img = pipe.render(cu, W, Hh)
-            lst, mp = renderer.read_merged()
-            out.append((img, lst.copy(), mp.copy()))
-        built, reused = renderer.merge_stats()
-        results[reuse] = (out, built - built0, reused - reused0)
-    renderer.set_option(L.GSWT_OPT_NO_MERGE_REUSE, 0)
+        with renderer.options(NO_MERGE_REUSE=0 if reuse else 1):
+            pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)
+            built0, reused0 = renderer.merge_stats()
+            out = []
+            for pos, tgt in path:
+                cu, vp = host.camera_uniforms(pos, tgt, (0, 0, 1), 45.0, 0.1, 2400.0, W, Hh)
+                pipe.update(pos, vp, force_sort=True)
+                img = pipe.render(cu, W, Hh)
+                lst, mp = renderer.read_merged()
+                out.append((img, lst.copy(), mp.copy()))
+            built, reused = renderer.merge_stats()
+            results[reuse] = (out, built - built0, reused - reused0)
     assert results[False][2] == 0 and results[True][2] > 0                       # groups were reused
     assert results[True][1] + results[True][2] == results[False][1]              # ... instead of being sorted
     for (img_a, l_a, m_a), (img_b, l_b, m_b) in zip(results[False][0], results[True][0]):
@@ -436,22 +432,21 @@ def test_merged_group_reuse_reaches_back_several_events(renderer):
     path = [places[k % 3] for k in range(12)]
     results = {}
     for reuse in (False, True):
-        renderer.set_option(L.GSWT_OPT_NO_MERGE_REUSE, 0 if reuse else 1)
-        pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)
-        built0, reused0 = renderer.merge_stats()
-        deep0 = renderer.merge_stats_deep()
-        out, built_after_first_lap = [], None
-        for k, (pos, tgt) in enumerate(path):
-            cu, vp = host.camera_uniforms(pos, tgt, (0, 0, 1), 45.0, 0.1, 2400.0, W, Hh)
-            pipe.update(pos, vp, force_sort=True)
-            img = pipe.render(cu, W, Hh)
-            lst, mp = renderer.read_merged()
-            out.append((img, lst.copy(), mp.copy()))
-            if k == 2:
-                built_after_first_lap = renderer.merge_stats()[0] - built0
-        built, reused = renderer.merge_stats()
-        results[reuse] = (out, built - built0, reused - reused0, renderer.merge_stats_deep() - deep0, built_after_first_lap)
-    renderer.set_option(L.GSWT_OPT_NO_MERGE_REUSE, 0)
+        with renderer.options(NO_MERGE_REUSE=0 if reuse else 1):
+            pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)
+            built0, reused0 = renderer.merge_stats()
+            deep0 = renderer.merge_stats_deep()
+            out, built_after_first_lap = [], None
+            for k, (pos, tgt) in enumerate(path):
+                cu, vp = host.camera_uniforms(pos, tgt, (0, 0, 1), 45.0, 0.1, 2400.0, W, Hh)
+                pipe.update(pos, vp, force_sort=True)
+                img = pipe.render(cu, W, Hh)
+                lst, mp = renderer.read_merged()
+                out.append((img, lst.copy(), mp.copy()))
+                if k == 2:
+                    built_after_first_lap = renderer.merge_stats()[0] - built0
+            built, reused = renderer.merge_stats()
+            results[reuse] = (out, built - built0, reused - reused0, renderer.merge_stats_deep() - deep0, built_after_first_lap)
     out_a, built_a, reused_a, deep_a, _ = results[False]
     out_b, built_b, reused_b, deep_b, first_lap_b = results[True]
     assert reused_a == 0 and deep_a == 0
@@ -472,24 +467,21 @@ def test_merged_group_reuse_does_not_survive_a_scene_upload(renderer):
     path = [((4.2 + 0.35 * k, 1.0 + 0.5 * k, 1.5), (5.0 + 0.3 * k, 4.0 + 0.55 * k, 1.0)) for k in range(4)]
 
     def run(seed, reuse):
-        renderer.set_option(L.GSWT_OPT_NO_MERGE_REUSE, 0 if reuse else 1)
-        verts = synth.make_tileset(n_lod=3, n_tile=16, lod0_count=900, seed_offset=seed)
-        pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)      # uploads the scene + its raw depths
-        out = []
-        for pos, tgt in path:
-            cu, vp = host.camera_uniforms(pos, tgt, (0, 0, 1), 45.0, 0.1, 2400.0, W, Hh)
-            pipe.update(pos, vp, force_sort=True)
-            img = pipe.render(cu, W, Hh)
-            lst, mp = renderer.read_merged()
-            out.append((img, lst.copy(), mp.copy()))
+        with renderer.options(NO_MERGE_REUSE=0 if reuse else 1):
+            verts = synth.make_tileset(n_lod=3, n_tile=16, lod0_count=900, seed_offset=seed)
+            pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)      # uploads the scene + its raw depths
+            out = []
+            for pos, tgt in path:
+                cu, vp = host.camera_uniforms(pos, tgt, (0, 0, 1), 45.0, 0.1, 2400.0, W, Hh)
+                pipe.update(pos, vp, force_sort=True)
+                img = pipe.render(cu, W, Hh)
+                lst, mp = renderer.read_merged()
+                out.append((img, lst.copy(), mp.copy()))
         return out
 
-    try:
-        want = run(7, False)                 # scene B alone, every group sorted
-        run(0, True)                         # scene A fills the retained draw sets ...
-        got = run(7, True)                   # ... then scene B of the same shape on the same ctx, reuse on
-    finally:
-        renderer.set_option(L.GSWT_OPT_NO_MERGE_REUSE, 0)
+    want = run(7, False)                     # scene B alone, every group sorted
+    run(0, True)                             # scene A fills the retained draw sets ...
+    got = run(7, True)                       # ... then scene B of the same shape on the same ctx, reuse on
     assert not np.array_equal(run(0, True)[0][1], want[0][1])                    # the two scenes really sort differently
     for (img_a, l_a, m_a), (img_b, l_b, m_b) in zip(want, got):
         assert np.array_equal(l_a, l_b) and np.array_equal(m_a, m_b)
@@ -518,18 +510,17 @@ def test_deferred_swap_in_takes_effect_once_built(renderer):
     cams = [host.camera_uniforms(pos, tgt, (0, 0, 1), 45.0, 0.1, 2400.0, W, Hh) for pos, tgt in path]
     cu_fix = cams[3][0]                                  # one camera for every image: only the draw list changes
     ref = []
-    renderer.set_option(L.GSWT_OPT_DEFER_SWAP, 0)
-    pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)
-    for (pos, _), (cu, vp) in zip(path, cams):
-        pipe.update(pos, vp, force_sort=True)
-        ref.append(pipe.render(cu_fix, W, Hh))
-    pipe.update(path[1][0], cams[1][1], force_sort=True)
-    pipe.update(path[5][0], cams[5][1], force_sort=True)
-    ref_bb = pipe.render(cu_fix, W, Hh)
+    with renderer.options(DEFER_SWAP=0):
+        pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)
+        for (pos, _), (cu, vp) in zip(path, cams):
+            pipe.update(pos, vp, force_sort=True)
+            ref.append(pipe.render(cu_fix, W, Hh))
+        pipe.update(path[1][0], cams[1][1], force_sort=True)
+        pipe.update(path[5][0], cams[5][1], force_sort=True)
+        ref_bb = pipe.render(cu_fix, W, Hh)
     assert any(not np.array_equal(ref[0], r) for r in ref[1:])          # the events do change the image
-    renderer.set_option(L.GSWT_OPT_DEFER_SWAP, 1)
-    pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)
-    try:
+    with renderer.options(DEFER_SWAP=1):
+        pipe = GSWTPipeline(verts, host.user_data(**cfg), renderer=renderer, device_merge=True)
         for k, ((pos, _), (cu, vp)) in enumerate(zip(path, cams)):
             pipe.update(pos, vp, force_sort=True)
             early = pipe.render(cu_fix, W, Hh)          # may still be the previous event's list (never anything else)
@@ -542,17 +533,15 @@ def test_deferred_swap_in_takes_effect_once_built(renderer):
         renderer.synchronize()
         assert np.array_equal(pipe.render(cu_fix, W, Hh), ref_bb)
         # value n >= 2: the n-th frame submitted after the call reads the new list, whatever the device is doing
-        renderer.set_option(L.GSWT_OPT_DEFER_SWAP, 3)
-        pipe.update(path[2][0], cams[2][1], force_sort=True)
-        before = pipe.render(cu_fix, W, Hh)
-        assert np.array_equal(before, ref_bb) and np.array_equal(pipe.render(cu_fix, W, Hh), ref_bb)
-        third = pipe.render(cu_fix, W, Hh)
-        assert not np.array_equal(third, ref_bb)
-        renderer.set_option(L.GSWT_OPT_DEFER_SWAP, 0)
-        pipe.update(path[2][0], cams[2][1], force_sort=True)
-        assert np.array_equal(pipe.render(cu_fix, W, Hh), third)
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEFER_SWAP, 0)
+        with renderer.options(DEFER_SWAP=3):
+            pipe.update(path[2][0], cams[2][1], force_sort=True)
+            before = pipe.render(cu_fix, W, Hh)
+            assert np.array_equal(before, ref_bb) and np.array_equal(pipe.render(cu_fix, W, Hh), ref_bb)
+            third = pipe.render(cu_fix, W, Hh)
+            assert not np.array_equal(third, ref_bb)
+        with renderer.options(DEFER_SWAP=0):
+            pipe.update(path[2][0], cams[2][1], force_sort=True)
+            assert np.array_equal(pipe.render(cu_fix, W, Hh), third)
 
 
 def test_first_frames_of_fresh_contexts_fill_every_slot():

@@ -30,11 +30,8 @@ def _cam(scale, sx, sy, grazing):
 
 
 def _render(renderer, cfg, cam, order_mode, no_cull):
-    renderer.set_option(L.GSWT_OPT_NO_CHUNK_CULL, no_cull)
-    try:
+    with renderer.options(NO_CHUNK_CULL=no_cull):
         img, ref, kinds, st = _run_case(renderer, cfg, cam, W, HH, lod0=500, order_mode=order_mode)
-    finally:
-        renderer.set_option(L.GSWT_OPT_NO_CHUNK_CULL, 0)
     t = renderer.timings()
     return img, ref, kinds, st, (t["n_visible"], t["n_pairs"])
 
@@ -144,11 +141,8 @@ def test_negative_zero_depth_ties_with_positive_zero(renderer, depth_sort):
     renderer.upload_scene(pp.tex, pp.gs_index, pp.gs_lod_id)
     renderer.configure(None)
     renderer.set_draws(case.draws)
-    renderer.set_option(L.GSWT_OPT_DEPTH_SORT, depth_sort)
-    try:
+    with renderer.options(DEPTH_SORT=depth_sort):
         img = renderer.render(cu, su, W_, Hh, order_mode=L.GSWT_ORDER_DEPTH)
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
     t = renderer.timings()
     assert t["n_visible"] == st["n_visible"] and t["n_pairs"] == st["n_pairs16"]
     assert H.max_abs_diff(img, ref) <= TOL

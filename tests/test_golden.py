@@ -99,7 +99,6 @@ def test_host_library_reproduces_golden_order(path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p) for p in GOLD])
 def test_gpu_matches_golden_image(renderer, path):
-    from gswt_renderer_amd import _lib as L
     g, cfg, rows = _load(path)
     rc = cfg.pop("__rc")
     W, H = [int(x) for x in g["size"]]
@@ -116,11 +115,8 @@ def test_gpu_matches_golden_image(renderer, path):
     assert np.max(np.abs(img.astype(np.float64) - g["image_default"].astype(np.float64))) <= 1e-4
     t = renderer.timings()
     assert [t["n_visible"], t["n_pairs"]] == g["stats_default"].tolist()[1:]
-    renderer.set_option(L.GSWT_OPT_STRICT_VS, 0)           # the rounding sequence v2
-    try:
+    with renderer.options(STRICT_VS=0):    # the rounding sequence v2
         img2 = renderer.render(cu, su, W, H)
-    finally:
-        renderer.set_option(L.GSWT_OPT_STRICT_VS, 1)
     assert np.max(np.abs(img2.astype(np.float64) - g["image"].astype(np.float64))) <= 1e-4
     t = renderer.timings()
     assert [t["n_visible"], t["n_pairs"]] == g["stats"].tolist()[1:]

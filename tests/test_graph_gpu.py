@@ -22,11 +22,9 @@ def _graph_stats(renderer):
 
 @pytest.fixture()
 def graph_mode(renderer):
-    renderer.set_option(L.GSWT_OPT_TIMING, 0)          # frames that carry timing events do not go through the graph
-    yield renderer
-    renderer.set_option(L.GSWT_OPT_GRAPH, 0)
-    renderer.set_option(L.GSWT_OPT_TIMING, 2)
-    renderer.set_option(L.GSWT_OPT_PAIR_CAP, 0)
+    # TIMING: frames that carry timing events do not go through the graph.  GRAPH, PAIR_CAP: what the tests set is put back with it
+    with renderer.options(TIMING=0, GRAPH=0, PAIR_CAP=0):
+        yield renderer
 
 
 def test_graph_replay_is_bit_identical_over_a_moving_camera_and_sort_events(graph_mode):

@@ -238,7 +238,7 @@ def test_refusals(renderer, plain):
              ("focal 0", block(setfocal(0, 0.0)), {}, None, b"focal"),
              ("focal NaN", block(setfocal(1, float("nan"))), {}, None, b"focal"),
              ("focal inf", block(setfocal(0, float("inf"))), {}, None, b"focal"),
-             ("sequence v2", block(), {}, (L.GSWT_OPT_STRICT_VS, 0), b"GSWT_OPT_STRICT_VS"),
+             ("sequence v2", block(), {}, dict(STRICT_VS=0), b"GSWT_OPT_STRICT_VS"),
              ("column shards", block(), dict(shard_index=1, shard_count=2, shard_mode=L.GSWT_SHARD_COLUMNS), None, b"column")]
     refused, _ = FM.refusal_probe(renderer)
     renderer.set_option(L.GSWT_OPT_PROJECTION, ORTHO)

@@ -28,15 +28,11 @@ ORDERS = {"reference": (L.GSWT_ORDER_REFERENCE, 0), "depth-local": (L.GSWT_ORDER
 
 @contextlib.contextmanager
 def _options(renderer, **opts):
-    """GSWT_OPT_<NAME> = value for the block, the defaults afterwards."""
-    defaults = dict(DEBUG_VARYINGS=0, NO_LOD_PREFILTER=0, STRICT_VS=1, DEPTH_SORT=0, PAIR_CAP=0)
+    """renderer.options(**opts) for the block, and no height map afterwards."""
     try:
-        for k, v in opts.items():
-            renderer.set_option(getattr(L, "GSWT_OPT_" + k), v)
-        yield
+        with renderer.options(**opts):
+            yield
     finally:
-        for k in opts:
-            renderer.set_option(getattr(L, "GSWT_OPT_" + k), defaults[k])
         renderer.configure(None)
 
 
@@ -44,8 +40,7 @@ def _frame(renderer, sc, order, *, shard=None, prefilter=True, **render_kw):
     """Uploads the scene, renders one frame and reads its lists back, the pairs translated to the oracle's entry numbers.
     Returns (image, PairLists, timings).  Call inside _options (the LOD prefilter is read when the draws are set)."""
     order_mode, depth_sort = ORDERS[order]
-    renderer.set_option(L.GSWT_OPT_DEPTH_SORT, depth_sort)
-    try:
+    with renderer.options(DEPTH_SORT=depth_sort):
         renderer.configure(sc.hm)
         sc.case.upload(renderer)
         l0, g0, _ = renderer.depth_stats()
@@ -53,8 +48,6 @@ def _frame(renderer, sc, order, *, shard=None, prefilter=True, **render_kw):
         l1, g1, _ = renderer.depth_stats()
         t = renderer.timings()
         ranges, pairs = renderer.read_ranges(), renderer.read_pairs()
-    finally:
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
     # the frame took the path the test names (re-runs count too)
     assert (l1 > l0, g1 > g0) == (order == "depth-local", order == "depth-global")
     emap = PL.product_entry_map(sc.case.draws, sc.case.orc_draws, prefilter=prefilter)

@@ -56,17 +56,9 @@ def _cases():
 
 @pytest.mark.parametrize("cfg,cam,rc,bg,mode", _cases())
 def test_random_sweep(renderer, cfg, cam, rc, bg, mode):
-    from gswt_renderer_amd import _lib as L
     W, Hh = (272, 176)
     t_eps = 1e-5 if cfg["surface_type"] == 0 else 0.0
-    renderer.set_option(L.GSWT_OPT_COMPOSITE, mode["composite"])
-    renderer.set_option(L.GSWT_OPT_DEPTH_SORT, mode["depth_sort"])     # (depth-ordered cases: global passes / tile-local LDS sort)
-    renderer.set_option(L.GSWT_OPT_ITEM_ORDER, mode["item_order"])
-    try:
+    with renderer.options(COMPOSITE=mode["composite"], DEPTH_SORT=mode["depth_sort"], ITEM_ORDER=mode["item_order"]):    # (depth-ordered cases: global passes / tile-local LDS sort)
         with np.errstate(all="ignore"):
             img, ref, kinds, st = _run_case(renderer, cfg, cam, W, Hh, lod0=500, bg=bg, render_config=rc, t_eps=t_eps, order_mode=mode["order_mode"])
-    finally:
-        renderer.set_option(L.GSWT_OPT_COMPOSITE, 0)
-        renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
-        renderer.set_option(L.GSWT_OPT_ITEM_ORDER, 0)
     assert H.max_abs_diff(img, ref) <= TOL + t_eps, (cfg, cam, rc, mode, kinds, st)

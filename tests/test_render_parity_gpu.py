@@ -6,7 +6,6 @@ import pytest
 
 from tests import helpers as H
 from oracle import gswt_oracle as orc
-from gswt_renderer_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -38,15 +37,10 @@ def test_vertex_stage_bit_exact(renderer):
     cam = orc.default_camera(W, Hh).uniforms()
     su = _scene(pp)
     case = H.grid_case(pp)
-    renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 1)
-    renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-    try:
+    with renderer.options(NO_LOD_PREFILTER=1, DEBUG_VARYINGS=1):
         case.upload(renderer)
         renderer.render(cam, su, W, Hh)
         got = renderer.read_projected()
-    finally:
-        renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 0)
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
     want = orc.project_draws(cam, su, pp.tex, case.orc_draws)
     assert got.shape == want.shape
     assert np.array_equal(got["visible"], want["visible"])
@@ -82,20 +76,15 @@ def test_both_vertex_stage_sequences_bit_exact(renderer, surface):
         cam = orc.default_camera(W, Hh).uniforms()
     wants = {}
     for strict_vs in (1, 0):
-        renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 1)
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-        renderer.set_option(L.GSWT_OPT_STRICT_VS, strict_vs)
-        try:
-            renderer.configure(hm)
-            case.upload(renderer)
-            img = renderer.render(cam, su, W, Hh)
-            got = renderer.read_projected()
-            t = renderer.timings()
-        finally:
-            renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 0)
-            renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
-            renderer.set_option(L.GSWT_OPT_STRICT_VS, 1)
-            renderer.configure(None)
+        with renderer.options(NO_LOD_PREFILTER=1, DEBUG_VARYINGS=1, STRICT_VS=strict_vs):
+            try:
+                renderer.configure(hm)
+                case.upload(renderer)
+                img = renderer.render(cam, su, W, Hh)
+                got = renderer.read_projected()
+                t = renderer.timings()
+            finally:
+                renderer.configure(None)
         with (orc.strict(fragment=False) if strict_vs else orc.v2()):
             want = orc.project_draws(cam, su, pp.tex, case.orc_draws, height_map=hm)
             ref, st = orc.render(cam, su, pp.tex, case.orc_draws, W, Hh, height_map=hm)
@@ -141,15 +130,10 @@ def test_sphere_surface_vertex_stage_and_image(renderer, draw_mode):
     case = _sphere_case(pp)
     for pos, tgt in (((3.0, -19.0, 6.0), (0.0, 0.0, 0.0)), ((-14.0, 9.0, -8.0), (0.0, 0.0, 1.0))):
         cam = orc.Camera(W, Hh, pos, tgt, [0, 0, 1]).uniforms()
-        renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 1)
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-        try:
+        with renderer.options(NO_LOD_PREFILTER=1, DEBUG_VARYINGS=1):
             case.upload(renderer)
             img = renderer.render(cam, su, W, Hh)
             got = renderer.read_projected()
-        finally:
-            renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 0)
-            renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
         want = orc.project_draws(cam, su, pp.tex, case.orc_draws)
         assert np.array_equal(got["visible"], want["visible"])
         vis = want["visible"] == 1

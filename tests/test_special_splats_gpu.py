@@ -38,14 +38,9 @@ def _parity(renderer, scene, cu, su, W, Hh, order_mode, *, view=0, bg_rgba=None,
 
 
 def _varyings(renderer, scene, pdraws, cu, su, W, Hh):
-    renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 1)
-    renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-    try:
+    with renderer.options(NO_LOD_PREFILTER=1, DEBUG_VARYINGS=1):
         _frame(renderer, scene, pdraws, cu, su, W, Hh)
         return renderer.read_projected()
-    finally:
-        renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 0)
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
 
 
 def _assert_varyings_equal(got, want, what=""):
@@ -244,15 +239,12 @@ def test_hostile_tileset_end_to_end(renderer, surface, cam_name):
     for order_mode in ORDERS:
         sorts = (0, 1) if order_mode == L.GSWT_ORDER_DEPTH else (0,)
         for ds in sorts:
-            renderer.set_option(L.GSWT_OPT_DEPTH_SORT, ds)
-            try:
+            with renderer.options(DEPTH_SORT=ds):
                 for eps in (0.0, 1e-5):
                     img, ref, _, st = _run_case(renderer, cfg, cam, W, Hh, verts=verts, order_mode=order_mode, t_eps=eps, max_pairs=MAX_PAIRS)
                     assert np.isfinite(img).all(), (order_mode, ds, eps)
                     assert st["n_visible"] > 200, st
                     assert H.max_abs_diff(img, ref) <= TOL + eps, (order_mode, ds, eps, H.max_abs_diff(img, ref))
-            finally:
-                renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
 
 
 @pytest.mark.parametrize("surface", ["plane", "hmap"])
@@ -269,14 +261,11 @@ def test_hostile_tileset_variants_bitwise(renderer, surface):
             full, ref, _, st = _run_case(renderer, cfg, cam, W, Hh, verts=verts, order_mode=order_mode, max_pairs=MAX_PAIRS)
             assert H.max_abs_diff(full, ref) <= TOL
             t_full = renderer.timings()
-            for key, vals in ((L.GSWT_OPT_COMPOSITE, (1, 2)), (L.GSWT_OPT_NO_CHUNK_CULL, (1,))):
+            for key, vals in (("COMPOSITE", (1, 2)), ("NO_CHUNK_CULL", (1,))):
                 for v in vals:
-                    renderer.set_option(key, v)
-                    try:
+                    with renderer.options(**{key: v}):
                         img, _, _, _ = _run_case(renderer, cfg, cam, W, Hh, verts=verts, order_mode=order_mode, max_pairs=MAX_PAIRS)
                         t = renderer.timings()
-                    finally:
-                        renderer.set_option(key, 0)
                     assert np.array_equal(img, full), (cam_name, order_mode, key, v, float(np.abs(img - full).max()))
                     assert (t["n_visible"], t["n_pairs"]) == (t_full["n_visible"], t_full["n_pairs"]), (cam_name, key, v)
             img, _, _, _ = _run_case(renderer, cfg, cam, W, Hh, verts=verts, order_mode=order_mode, shard=3, shard_cols=True)
@@ -297,17 +286,14 @@ def test_hostile_presort_vertex_stage_bit_exact(renderer, surface):
     su = orc.scene_uniforms(num_lod=pp.n_lod, map_half_wh=(1, 2), **kw)
     case = H.grid_case(pp, lod_of=lambda ix, iy: (ix + iy) % 3)
     cu = orc.default_camera(W, Hh).uniforms()
-    renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 1)
-    renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 1)
-    try:
-        renderer.configure(hm)
-        case.upload(renderer)
-        renderer.render(cu, su, W, Hh)
-        got = renderer.read_projected()
-    finally:
-        renderer.set_option(L.GSWT_OPT_NO_LOD_PREFILTER, 0)
-        renderer.set_option(L.GSWT_OPT_DEBUG_VARYINGS, 0)
-        renderer.configure(None)
+    with renderer.options(NO_LOD_PREFILTER=1, DEBUG_VARYINGS=1):
+        try:
+            renderer.configure(hm)
+            case.upload(renderer)
+            renderer.render(cu, su, W, Hh)
+            got = renderer.read_projected()
+        finally:
+            renderer.configure(None)
     want = orc.project_draws(cu, su, pp.tex, case.orc_draws, height_map=hm)
     assert _assert_varyings_equal(got, want, surface) > 300
 
@@ -331,11 +317,8 @@ def test_exact_depth_ties_follow_the_oracle(renderer):
     sc = S.raw_scene(rows, lists=[(np.arange(len(rows)), np.zeros(len(rows))), (perm, np.zeros(len(rows)))])
     for view in (0, 1):
         for ds in (0, 1):
-            renderer.set_option(L.GSWT_OPT_DEPTH_SORT, ds)
-            try:
+            with renderer.options(DEPTH_SORT=ds):
                 img, ref, st = _parity(renderer, sc, cu, su, W, Hh, L.GSWT_ORDER_DEPTH, view=view, valid_lod_id=0)
-            finally:
-                renderer.set_option(L.GSWT_OPT_DEPTH_SORT, 0)
             assert st["n_visible"] == len(rows)
     swapped = list(rows)
     swapped[0], swapped[1] = swapped[1], swapped[0]

@@ -15,8 +15,8 @@ table above lists.  The reference's src/gswt.wgsl:152-258,402-435."""
 import numpy as np
 import pytest
 
-from gswt_renderer_amd import _lib as L
 from oracle import gswt_oracle as orc
+from tests import frame_outputs as FO
 from tests.test_strict_oracle import both_modes, check_bounds
 
 pytestmark = pytest.mark.gpu
@@ -24,22 +24,13 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("name", ["c3", "c3h", "c5"])
 def test_gpu_v2_option_vs_strict_full_error_stack(renderer, name):
-    import bench
     import torch
     d = both_modes(name, varyings=False)
-    w, wang, cu, vp, sort = bench.build_workload(name)
-    W, H = w["width"], w["height"]
-    su = wang.scene_uniforms()
-    wang.upload_to(renderer)
-    renderer.configure(wang.height_map() if int(wang.user.surface_type) == 1 else None)
-    renderer.set_draws(sort.draws, sort.merged_gs_index, sort.merged_map_id, sort.merged_lod_id)
+    W, H, cu, su = FO.bind_workload(renderer, FO.workload(name))
     out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
-    renderer.set_option(L.GSWT_OPT_STRICT_VS, 0)           # this test is about the rounding sequence v2 (the default until round 3)
-    try:
+    with renderer.options(STRICT_VS=0):                    # this test is about the rounding sequence v2 (the default until round 3)
         renderer.render_wait(renderer.render_async(cu, su, W, H, out.data_ptr(), transmittance_eps=1e-5))
         t = renderer.timings()
-    finally:
-        renderer.set_option(L.GSWT_OPT_STRICT_VS, 1)
     img = out.cpu().numpy()
     del out
     torch.cuda.empty_cache()
@@ -64,20 +55,16 @@ def test_gpu_strict_vertex_stage_meets_1e4_off_the_ellipse_borders(renderer, nam
     the thin-ellipse term of the default sequence v2 (2.8e-4 / 4.6e-4 / 1.5e-3) came from the vertex stage."""
     import bench
     import torch
-    w, wang, cu, vp, sort = bench.build_workload(name)
-    W, H = w["width"], w["height"]
-    su = wang.scene_uniforms()
-    hm = wang.height_map() if int(wang.user.surface_type) == 1 else None
-    tex, draws = bench.oracle_draws(wang, sort, vp)
+    wl = FO.workload(name)
+    W, H, cu, su, hm = wl["W"], wl["H"], wl["cu"], wl["su"], wl["hm"]
+    tex, draws = bench.oracle_draws(wl["wang"], wl["sort"], wl["vp"])
     ocu = orc.Camera176.from_buffer_copy(bytes(cu))
     osu = orc.Scene160.from_buffer_copy(bytes(su))
     with orc.strict():
         strict_img, sts = orc.render(ocu, osu, tex, draws, W, H, height_map=hm)
     mixed_img, stm = orc.render(ocu, osu, tex, draws, W, H, height_map=hm)          # the checker's default: strict vertex stage + F1..F4
     mask, counts = orc.compare_modes(ocu, osu, tex, draws, W, H, height_map=hm, strict_vs=True)
-    wang.upload_to(renderer)
-    renderer.configure(hm)
-    renderer.set_draws(sort.draws, sort.merged_gs_index, sort.merged_map_id, sort.merged_lod_id)
+    FO.bind_workload(renderer, wl)
     out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
     renderer.render_wait(renderer.render_async(cu, su, W, H, out.data_ptr(), transmittance_eps=1e-5))
     t = renderer.timings()
