@@ -9,9 +9,11 @@
 // contract is the reference's exact draw list), so they run on one lane of a single workgroup out of LDS, with every
 // data-parallel part around them (edge numbering, adjacency lists, group finalisation) spread over the workgroup.
 //
-// Float discipline: the vector / matrix helpers and surface_mapping are the SAME sources libgswt_host compiles
-// (host/gswt_math.h, host/gswt_surface.h under GSWT_HD, which gswt_device_fn.h sets), built with -ffp-contract=off: one rounding
-// per operator, IEEE division and square root (hipcc's default for fp32), so every stage is bit-identical to gswt_wang_sort_tiles.
+// Float discipline: the vector / matrix helpers, surface_mapping and the per-cell / per-edge / per-record arithmetic of every stage
+// are the SAME sources libgswt_host compiles (host/gswt_math.h, host/gswt_surface.h, host/gswt_sort_event.h under GSWT_HD, which
+// gswt_device_fn.h sets), built with -ffp-contract=off: one rounding per operator, IEEE division and square root (hipcc's default
+// for fp32), so every stage is bit-identical to gswt_wang_sort_tiles.  The kernels here are the adapters (gswt_cell /
+// gswt_cell_state in, one thread per cell, side or record) and the order-defined sequential algorithms.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -22,16 +24,13 @@
 
 #include "gswt_device_fn.h"      // (first: it makes host/gswt_math.h and host/gswt_surface.h __host__ __device__)
 #include "gswt_ctx.h"
+#include "host/gswt_sort_event.h"      // (behind gswt_device_fn.h, for the same reason)
 
 using namespace gswt_host;
 
 namespace {
 
-enum { SORT_DISTANCE = 0, SORT_VIEWPORT = 1, SORT_OBJECT = 2, SORT_GRAPH = 3 };
-enum { MERGE_NONE = 0, MERGE_AXIS = 1, MERGE_EDGE = 2 };
-enum { TR_NONE = 0, TR_SPAWNING = 1, TR_CHANGING_HIGHER = 2, TR_CHANGING_LOWER = 3 };
-enum { MS_NONE = 0, MS_FROM = 1, MS_TO = 2 };
-enum { ERR_LOD0_HIGHER = 1, ERR_NO_CORNERS = 2, ERR_AXIS_UNWRAP = 4 };
+enum { ERR_AXIS_UNWRAP = 4 };                        // C_ERR bits: beside ERR_LOD0_HIGHER | ERR_NO_CORNERS of draw_from_tile
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 constexpr uint16_t kNone16 = 0xFFFFu;
 // Map size limits (gswt_worker_create returns GSWT_ERR_CAPACITY beyond them, include/gswt_hip.h).  Every map table is u16 with
@@ -71,6 +70,7 @@ struct WDev {
 struct Mat4 { float m[16]; };
 
 __device__ __forceinline__ V3 v3(const float* p) { return V3{p[0], p[1], p[2]}; }
+__device__ __forceinline__ M3 m3(const float* p) { M3 r; for (int i = 0; i < 9; i++) r.m[i] = p[i]; return r; }
 
 // neighbour of cell c on side s: map index << 2 | the slot c occupies for it, or -1 (wangtile.rs:257-338; the planar case inline)
 __device__ __forceinline__ int nbr(const WDev& w, int c, int s)
@@ -89,46 +89,13 @@ __global__ __launch_bounds__(256) void k_w_lod(const WDev w, const V3 cam)
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= w.cells) return;
     const int x = idx / w.sp.map_h, y = idx - x * w.sp.map_h;
-    int ccx, ccy;
-    sp_map_to_coord(w.sp, x, y, ccx, ccy);
-    const V3 pos_offset = sp_coord_to_pos(w.sp, ccx, ccy);
     const gswt_cell& c = w.cell[idx];
-    const float* D = w.lod_dist;
-    const int nD = w.n_lod;
-    const float center_dist = distance(v3(c.tile_center), cam);
-    int sel = nD - 1;
-    for (int l = 0; l < nD; l++)
-        if (center_dist <= D[l]) { sel = l; break; }
-    int status = TR_NONE;
-    if (w.lod_blending) {
-        const V3 lo = v3(w.tile_aabb + 6 * c.tile), hi = v3(w.tile_aabb + 6 * c.tile + 3);
-        float mn = -1.0f, mx = -1.0f;
-        const int npts = w.lod_bbox_check ? 8 : 1;
-        for (int k = 0; k < npts; k++) {
-            V3 p;
-            if (w.lod_bbox_check) p = V3{(k & 4) ? hi.x : lo.x, (k & 2) ? hi.y : lo.y, (k & 1) ? hi.z : lo.z};
-            else p = v3(w.tile_center + 3 * c.tile);
-            V3 q; M3 tr;
-            surface_mapping(w.sp, x, y, p + pos_offset, true, q, tr);
-            const float d = distance(q, cam);
-            if (mn < 0.0f || d < mn) mn = d;
-            if (mx < 0.0f || d > mx) mx = d;
-        }
-        const float r = w.lod_ratio, tol = w.lod_tol;
-        if (sel > 0 && mn < D[sel - 1] * (1.0f + r) + tol) status = TR_CHANGING_HIGHER;
-        if (sel < nD - 1 && mx > D[sel] * (1.0f - r) - tol) status = TR_CHANGING_LOWER;
-    }
-    float spawning = 0.0f;
-    if (w.lod_blending && w.sp.surface_type != 2) {
-        const V3 cc = sp_coord_to_pos(w.sp, w.sp.center_x, w.sp.center_y);
-        const float cam_u = (cam.x - cc.x) / w.sp.tile_width, cam_v = (cam.y - cc.y) / w.sp.tile_width;
-        float bf = 1.0f;
-        if (x == 0) bf *= 1.0f - cam_u;
-        else if (x == w.sp.map_w - 1) bf *= cam_u;
-        if (y == 0) bf *= 1.0f - cam_v;
-        else if (y == w.sp.map_h - 1) bf *= cam_v;
-        if (bf != 1.0f) { status = TR_SPAWNING; spawning = bf; }
-    }
+    int sel, status;
+    lod_select(w.sp, x, y, v3(c.tile_center), w.lod_dist, w.n_lod, w.lod_blending, w.lod_bbox_check, v3(w.tile_aabb + 6 * c.tile), v3(w.tile_aabb + 6 * c.tile + 3),
+               v3(w.tile_center + 3 * c.tile), w.lod_ratio, w.lod_tol, cam, sel, status);
+    float cam_u, cam_v, spawning;
+    spawning_cam_uv(w.sp, cam, cam_u, cam_v);
+    if (spawning_factor(w.sp, w.lod_blending, x, y, cam_u, cam_v, spawning)) status = TR_SPAWNING;
     gswt_cell_state& s = w.st[idx];
     s.lod = (uint32_t)sel; s.transition = status; s.spawning_factor = spawning;
 }
@@ -148,32 +115,15 @@ __global__ __launch_bounds__(256) void k_w_edges(const WDev w, const V3 cam, con
     if (nbv >= 0 && (nbv >> 2) > c) {
         const gswt_cell& cl = w.cell[c];
         const V3 epos = v3(cl.edge_pos + 3 * s), enormal = v3(cl.edge_normal + 3 * s);
-        const V3 vd = epos - cam;
-        if (!is_zero(vd)) {
-            const float dr = dot(enormal, vd);
-            dir = dr > 0.0f ? 1 : (dr < 0.0f ? -1 : 0);
-            if (w.merge_type == MERGE_EDGE) {
-                const float vlen = magnitude(vd);
-                const int s2 = (s + 1) & 3;
-                const V3 u1 = v3(cl.corner_up + 3 * s), u2 = v3(cl.corner_up + 3 * s2);
-                if (!(dot(vd, u1) > 0.0f || dot(vd, u2) > 0.0f)) {
-                    const float a4[4] = {cl.corner_pos[3 * s], cl.corner_pos[3 * s + 1], cl.corner_pos[3 * s + 2], 1.0f};
-                    const float b4[4] = {cl.corner_pos[3 * s2], cl.corner_pos[3 * s2 + 1], cl.corner_pos[3 * s2 + 2], 1.0f};
-                    float p1[4], p2[4];
-                    mat4_vec(vp.m, a4, p1);
-                    mat4_vec(vp.m, b4, p2);
-                    const V3 q1 = V3{p1[0], p1[1], p1[2]} / p1[3], q2 = V3{p2[0], p2[1], p2[2]} / p2[3];
-                    const float clip = 1.0f;
-                    const bool o1 = q1.z < -clip || q1.x < -clip || q1.x > clip || q1.y < -clip || q1.y > clip;
-                    const bool o2 = q2.z < -clip || q2.x < -clip || q2.x > clip || q2.y < -clip || q2.y > clip;
-                    if (!(o1 && o2)) {
-                        const float dabs = fabsf(dot(enormal, vd));
-                        const float ndot = dabs / vlen;
-                        // the reference skips edges over the threshold without counting them towards top-k: dropping them here is the same
-                        if (!(ndot > w.merge_dot_thr)) key = __float_as_uint(dabs);
-                    }
-                }
-            }
+        dir = edge_direction(epos, enormal, cam);
+        if (w.merge_type == MERGE_EDGE) {
+            const int s2 = (s + 1) & 3;
+            float dabs, ndot;
+            // the reference skips edges over the threshold without counting them towards top-k: dropping them here is the same
+            if (edge_candidate(epos, enormal, v3(cl.corner_pos + 3 * s), v3(cl.corner_pos + 3 * s2), v3(cl.corner_up + 3 * s), v3(cl.corner_up + 3 * s2), cam, vp.m, dabs,
+                               ndot) &&
+                !(ndot > w.merge_dot_thr))
+                key = __float_as_uint(dabs);
         }
     }
     keys[t] = key;
@@ -367,8 +317,7 @@ __global__ __launch_bounds__(256) void k_w_order_keys(const WDev w, const V3 cam
     if (idx >= w.cells) return;
     uint32_t key = kNoKey;
     if (w.st[idx].merge != MS_TO) {
-        const V3 p = v3(w.cell[idx].tile_center);
-        float k = w.sort_type == SORT_DISTANCE ? distance2(cam, p) : (vp.m[2] * p.x + vp.m[6] * p.y) + vp.m[10] * p.z;
+        float k = order_key(w.sort_type, cam, vp.m, v3(w.cell[idx].tile_center));
         k = k + 0.0f;                                    // -0 and +0 compare equal in the reference's partial_cmp
         const uint32_t u = __float_as_uint(k);
         key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -730,20 +679,6 @@ __global__ __launch_bounds__(1024) void k_w_scan(const WDev w, const uint32_t* _
     }
 }
 
-__device__ inline uint32_t choose_presort_view(const WDev& w, const M3& transform, V3 pos, V3 cam)      // :700-716
-{
-    const V3 dl = transform * normalize(pos - cam);
-    uint32_t best = 0;
-    float best_err = 1000.0f;
-    for (int i = 0; i < w.n_view; i++) {
-        const V3 pd = v3(w.presort_dirs + 3 * i);
-        const float ex = dl.x - pd.x, ey = dl.y - pd.y, ez = dl.z - pd.z;
-        const float err = (ex * ex + ey * ey) + ez * ez;
-        if (err < best_err) { best = (uint32_t)i; best_err = err; }
-    }
-    return best;
-}
-
 // one thread per ordered tile: the record (:500-690), its group description, and the draw the render loop makes of it
 // (renderer.rs:466-591 host half)
 __global__ __launch_bounds__(256) void k_w_records(const WDev w, const V3 cam, const uint32_t* __restrict__ order, const uint32_t* __restrict__ pre_group,
@@ -762,89 +697,32 @@ __global__ __launch_bounds__(256) void k_w_records(const WDev w, const V3 cam, c
     if (s.merge == MS_FROM) {
         const uint32_t len = w.head_len[mi];
         const uint32_t* mem = w.pool + w.head_off[mi];
-        bool merge_x = true, merge_y = true;
-        V3 avg_c;
-        Quat avg_q;
+        GroupView gv;
         gswt_merge_member* mo = members + pre_member[k];
         for (uint32_t m = 0; m < len; m++) {
             const uint32_t m_mi = mem[m];
             const int ax = (int)m_mi / w.sp.map_h, ay = (int)m_mi - ax * w.sp.map_h;
-            if (ax != mx) merge_x = false;
-            if (ay != my) merge_y = false;
             const gswt_cell& mc = w.cell[m_mi];
             const gswt_cell_state& ms = w.st[m_mi];
-            avg_c = avg_c + v3(mc.tile_center);
-            M3 tl;
-            for (int i = 0; i < 9; i++) tl.m[i] = mc.to_local[i];
-            const Quat q = quat_from_mat3(tl);
-            avg_q.s += q.s; avg_q.x += q.x; avg_q.y += q.y; avg_q.z += q.z;
-            gswt_merge_member mm;
-            mm.map_index = m_mi; mm.lod = ms.lod; mm.tile = mc.tile; mm.other_lod = -1;
-            if (ms.transition == TR_CHANGING_LOWER) mm.other_lod = (int32_t)ms.lod + 1;
-            else if (ms.transition == TR_CHANGING_HIGHER) mm.other_lod = (int32_t)ms.lod - 1;
-            if (ms.transition != TR_NONE) do_transition = true;
-            mo[m] = mm;
+            group_view_add(gv, mx, my, ax, ay, v3(mc.tile_center), m3(mc.to_local));
+            mo[m] = merge_member_of(m_mi, ms.lod, mc.tile, ms.transition, do_transition);
         }
-        if (!merge_x && !merge_y) view_id = (uint32_t)w.n_view - 1u;
-        else {
-            const float n = (float)len;
-            const Quat q{avg_q.s / n, avg_q.x / n, avg_q.y / n, avg_q.z / n};
-            view_id = choose_presort_view(w, mat3_from_quat(q), avg_c / n, cam);
-        }
+        view_id = group_view_finish(gv, len, w.presort_dirs, w.n_view, cam);
         key_len = len;
         gswt_merge_group g;
         g.view_id = view_id; g.first_member = pre_member[k]; g.n_members = len; g._pad = 0;
         groups[pre_group[k]] = g;
-    } else {
-        M3 tl;
-        for (int i = 0; i < 9; i++) tl.m[i] = c.to_local[i];
-        view_id = choose_presort_view(w, tl, v3(c.tile_center), cam);
-    }
-    gswt_sorted_tile st;
-    memset(&st, 0, sizeof(st));
-    st.lod = s.lod; st.tile = c.tile; st.view_id = view_id;
-    for (int i = 0; i < 3; i++) { st.tile_offset[i] = c.tile_offset[i]; st.tile_center[i] = c.tile_center[i]; }
-    st.map_index = mi; st.map_coord[0] = (uint32_t)mx; st.map_coord[1] = (uint32_t)my;
-    st.transition = s.transition; st.spawning_factor = s.spawning_factor;
-    st.has_corners = c.has_corner;
-    for (int i = 0; i < 12; i++) st.corners[i] = c.has_corner ? c.corner_pos[i] : 0.0f;
-    st.key_len = key_len;
-    st.single_lod_id = -1;
+    } else view_id = choose_presort_view(w.presort_dirs, w.n_view, m3(c.to_local), v3(c.tile_center), cam);
+    gswt_sorted_tile st = sorted_tile_of(s.lod, c.tile, view_id, v3(c.tile_offset), mi, mx, my, v3(c.tile_center), s.transition, s.spawning_factor, c.has_corner,
+                                         c.corner_pos, key_len);
     if (s.merge == MS_FROM) {
         st.merged = 1; st.merged_group = pre_group[k]; st.merged_offset = pre_len[k]; st.merged_count = ent_len[k];
         st.single_lod_id = do_transition ? -1 : (int32_t)s.lod;
     }
     tiles[k] = st;
-    // the draw, renderer.rs:499-590
     gswt_draw d;
-    memset(&d, 0, sizeof(d));
-    gswt_tile_uniforms& u = d.tile;
-    u.single_draw = 0; u.map_index = mi; u.single_lod_id = -1; u.valid_lod_id = -1; u.changing = 0; u.changing_to_lower = -1;
-    u.tile_id[0] = s.lod; u.tile_id[1] = c.tile; u.tile_id[2] = view_id; u.tile_id[3] = 0;
-    u.offset[0] = c.tile_offset[0]; u.offset[1] = c.tile_offset[1]; u.offset[2] = c.tile_offset[2]; u.offset[3] = 0.0f;
-    u.map_coord[0] = (uint32_t)mx; u.map_coord[1] = (uint32_t)my;
-    d.lod = s.lod;
-    if (st.merged) {
-        u.single_draw = 1;
-        u.single_lod_id = st.single_lod_id;
-        u.changing = st.single_lod_id == -1 ? 1u : 0u;
-        d.merged = 1; d.merged_offset = st.merged_offset; d.merged_count = st.merged_count; d.merged_group = st.merged_group;
-        d.merged_has_lod = st.single_lod_id == -1 ? 1u : 0u;
-    } else {
-        d.base_lod = s.lod;
-        if (s.transition == TR_CHANGING_LOWER) { u.changing = 1; u.changing_to_lower = 1; }
-        else if (s.transition == TR_CHANGING_HIGHER) {
-            u.changing = 1; u.changing_to_lower = 0;
-            if (s.lod == 0) atomicOr(&w.counts[C_ERR], ERR_LOD0_HIGHER);
-            d.base_lod = s.lod - 1;
-        } else u.valid_lod_id = (int32_t)s.lod;
-        d.base_tile = c.tile; d.base_view = view_id;
-    }
-    if (key_len == 1) {
-        if (!c.has_corner) atomicOr(&w.counts[C_ERR], ERR_NO_CORNERS);
-        d.cull_enable = 1;
-        for (int i = 0; i < 12; i++) d.corners[i] = st.corners[i];
-    }
+    const uint32_t err = draw_from_tile(st, d);
+    if (err) atomicOr(&w.counts[C_ERR], err);
     draws[k] = d;
 }
 

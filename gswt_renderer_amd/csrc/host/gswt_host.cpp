@@ -26,6 +26,7 @@
 
 #include "gswt_math.h"
 #include "gswt_surface.h"
+#include "gswt_sort_event.h"
 
 using namespace gswt_host;
 
@@ -367,14 +368,10 @@ struct DiGraph {
 };
 
 // ------------------------------------------------------------------------------------------
-// structure.rs data contracts
+// structure.rs data contracts (SORT_*, MERGE_*, TR_*, MS_*: gswt_sort_event.h, shared with the device worker)
 // ------------------------------------------------------------------------------------------
-enum { SORT_DISTANCE = 0, SORT_VIEWPORT = 1, SORT_OBJECT = 2, SORT_GRAPH = 3 };
-enum { MERGE_NONE = 0, MERGE_AXIS = 1, MERGE_EDGE = 2 };
 enum { SURFACE_NONE = 0, SURFACE_HEIGHTMAP = 1, SURFACE_SPHERE = 2 };
 enum { HMAP_TEXTURE = 0, HMAP_RANDOM = 1, HMAP_SLOPEX = 2, HMAP_SLOPEY = 3, HMAP_DUALSLOPE = 4 };
-enum { TR_NONE = 0, TR_SPAWNING = 1, TR_CHANGING_HIGHER = 2, TR_CHANGING_LOWER = 3 };   // Changing(false) / Changing(true)
-enum { MS_NONE = 0, MS_FROM = 1, MS_TO = 2 };
 
 struct TileBaseData {   // structure.rs:545-554
     size_t splat_count = 0;
@@ -722,65 +719,21 @@ bool compute_corner_edge(const gswt_wang& w, int x, int y, float tile_center_z, 
     return true;
 }
 
-// ---- lod_select_spatial + update_lod, wangtile.rs:1496-1607 -------------------------------
-void lod_select_spatial(const gswt_wang& w, int x, int y, V3 cam, size_t& lod_out, int& status_out)
-{
-    int cx, cy;
-    w.map_to_coord(x, y, cx, cy);
-    V3 pos_offset = w.coord_to_pos(cx, cy);
-    const TileInstance* ti = w.at(x, y);
-    const std::vector<float>& D = w.lod_transition_dist;
-    float center_dist = distance(ti->tile_center, cam);
-    size_t sel = D.size() - 1;
-    for (size_t l = 0; l < D.size(); l++)
-        if (center_dist <= D[l]) { sel = l; break; }
-    int status = TR_NONE;
-    if (w.user.lod_blending) {
-        V3 lo = w.aabb_lo[ti->tile], hi = w.aabb_hi[ti->tile];
-        V3 pts[8];
-        int npts = 0;
-        if (w.user.lod_bbox_check) {
-            pts[0] = lo; pts[1] = {lo.x, lo.y, hi.z}; pts[2] = {lo.x, hi.y, lo.z}; pts[3] = {lo.x, hi.y, hi.z};
-            pts[4] = {hi.x, lo.y, lo.z}; pts[5] = {hi.x, lo.y, hi.z}; pts[6] = {hi.x, hi.y, lo.z}; pts[7] = hi;
-            npts = 8;
-        } else { pts[0] = w.tile_center[ti->tile]; npts = 1; }
-        float mn = -1.0f, mx = -1.0f;
-        for (int k = 0; k < npts; k++) {
-            V3 q; M3 tr;
-            surface_mapping(w, x, y, pts[k] + pos_offset, true, q, tr);
-            float d = distance(q, cam);
-            if (mn < 0.0f || d < mn) mn = d;
-            if (mx < 0.0f || d > mx) mx = d;
-        }
-        const float r = w.user.lod_transition_width_ratio, tol = w.user.lod_dist_tolerance;
-        if (sel > 0 && mn < D[sel - 1] * (1.0f + r) + tol) status = TR_CHANGING_HIGHER;
-        if (sel < D.size() - 1 && mx > D[sel] * (1.0f - r) - tol) status = TR_CHANGING_LOWER;
-    }
-    lod_out = sel;
-    status_out = status;
-}
-
+// ---- update_lod, wangtile.rs:1496-1607 (lod_select_spatial and the spawning factor: gswt_sort_event.h) ----
 void update_lod(gswt_wang& w, V3 cam)
 {
-    V3 cc = w.coord_to_pos(w.center_x, w.center_y);
-    float cam_u = (cam.x - cc.x) / w.user.tile_width;
-    float cam_v = (cam.y - cc.y) / w.user.tile_width;
+    const SurfaceParams sp = surface_params(w);
+    const std::vector<float>& D = w.lod_transition_dist;
+    float cam_u, cam_v;
+    spawning_cam_uv(sp, cam, cam_u, cam_v);
     for (int i = 0; i < w.map_w; i++)
         for (int j = 0; j < w.map_h; j++) {
-            size_t lod; int st;
-            lod_select_spatial(w, i, j, cam, lod, st);
             TileInstance* ti = w.at(i, j);
-            ti->lod = lod;
-            ti->transition = st;
-            ti->spawning = 0.0f;
-            if (w.user.lod_blending && w.user.surface_type != SURFACE_SPHERE) {
-                float bf = 1.0f;
-                if (i == 0) bf *= 1.0f - cam_u;
-                else if (i == w.map_w - 1) bf *= cam_u;
-                if (j == 0) bf *= 1.0f - cam_v;
-                else if (j == w.map_h - 1) bf *= cam_v;
-                if (bf != 1.0f) { ti->transition = TR_SPAWNING; ti->spawning = bf; }
-            }
+            int lod;
+            lod_select(sp, i, j, ti->tile_center, D.data(), (int)D.size(), w.user.lod_blending, w.user.lod_bbox_check, w.aabb_lo[ti->tile], w.aabb_hi[ti->tile],
+                       w.tile_center[ti->tile], w.user.lod_transition_width_ratio, w.user.lod_dist_tolerance, cam, lod, ti->transition);
+            ti->lod = (size_t)lod;
+            if (spawning_factor(sp, w.user.lod_blending, i, j, cam_u, cam_v, ti->spawning)) ti->transition = TR_SPAWNING;
         }
 }
 
@@ -868,19 +821,8 @@ void selective_merge_edge(gswt_wang& w, V3 cam, const float* vp)
                 const Edge& e = ti->edge[n_i];
                 const Corner& c1 = ti->corner[n_i];
                 const Corner& c2 = ti->corner[(n_i + 1) % 4];
-                V3 vd = e.pos - cam;
-                float vlen = magnitude(vd);
-                if (is_zero(vd)) continue;
-                if (dot(vd, c1.to_world.col(2)) > 0.0f || dot(vd, c2.to_world.col(2)) > 0.0f) continue;
-                float a4[4] = {c1.pos.x, c1.pos.y, c1.pos.z, 1.0f}, b4[4] = {c2.pos.x, c2.pos.y, c2.pos.z, 1.0f}, p1[4], p2[4];
-                mat4_vec(vp, a4, p1);
-                mat4_vec(vp, b4, p2);
-                V3 q1 = V3{p1[0], p1[1], p1[2]} / p1[3], q2 = V3{p2[0], p2[1], p2[2]} / p2[3];
-                const float clip = 1.0f;
-                auto outside = [&](V3 p) { return p.z < -clip || p.x < -clip || p.x > clip || p.y < -clip || p.y > clip; };
-                if (outside(q1) && outside(q2)) continue;
-                float dabs = std::fabs(dot(e.normal, vd));
-                edges.push_back({mi, n_i, dabs, dabs / vlen});
+                float dabs, ndot;
+                if (edge_candidate(e.pos, e.normal, c1.pos, c2.pos, c1.to_world.col(2), c2.to_world.col(2), cam, vp, dabs, ndot)) edges.push_back({mi, n_i, dabs, ndot});
             }
         }
     std::stable_sort(edges.begin(), edges.end(), [](const E& a, const E& b) { return a.dabs < b.dabs; });
@@ -1015,25 +957,13 @@ std::vector<size_t> sort_by_key_desc(std::vector<std::pair<size_t, float>>& sv)
     return out;
 }
 
-std::vector<size_t> sort_tiles_object_pos(const gswt_wang& w, V3 cam)
+std::vector<size_t> sort_tiles_object_key(const gswt_wang& w, int sort_type, V3 cam, const float* vp)      // sort_tiles_object_pos / _vp
 {
     std::vector<std::pair<size_t, float>> sv;
     for (size_t idx = 0; idx < (size_t)w.map_w * w.map_h; idx++) {
         const TileInstance* ti = w.tile_map[idx].get();
         if (ti->merge == MS_TO) continue;
-        sv.emplace_back(idx, distance2(cam, ti->tile_center));
-    }
-    return sort_by_key_desc(sv);
-}
-
-std::vector<size_t> sort_tiles_object_vp(const gswt_wang& w, const float* vp)
-{
-    std::vector<std::pair<size_t, float>> sv;
-    for (size_t idx = 0; idx < (size_t)w.map_w * w.map_h; idx++) {
-        const TileInstance* ti = w.tile_map[idx].get();
-        if (ti->merge == MS_TO) continue;
-        V3 p = ti->tile_center;
-        sv.emplace_back(idx, (vp[2] * p.x + vp[6] * p.y) + vp[10] * p.z);
+        sv.emplace_back(idx, order_key(sort_type, cam, vp, ti->tile_center));
     }
     return sort_by_key_desc(sv);
 }
@@ -1089,11 +1019,9 @@ std::vector<size_t> sort_tiles_object_graph(const gswt_wang& w, V3 cam)
                 if (!n.some || check[w.map_to_index(n.x, n.y)]) continue;
                 int nnode = node_of(n.x, n.y);
                 if (this_node == nnode) continue;
-                V3 vd = ti->edge[s].pos - cam;
-                if (is_zero(vd)) continue;
-                float dr = dot(ti->edge[s].normal, vd);
-                if (dr > 0.0f) g.add_edge(this_node, nnode);
-                else if (dr < 0.0f) g.add_edge(nnode, this_node);
+                const int dir = edge_direction(ti->edge[s].pos, ti->edge[s].normal, cam);
+                if (dir > 0) g.add_edge(this_node, nnode);
+                else if (dir < 0) g.add_edge(nnode, this_node);
             }
         }
     std::vector<size_t> out, removed;
@@ -1111,20 +1039,6 @@ std::vector<size_t> sort_tiles_object_graph(const gswt_wang& w, V3 cam)
     out.insert(out.end(), removed.begin(), removed.end());
     std::reverse(out.begin(), out.end());
     return out;
-}
-
-size_t choose_presort_view(const gswt_wang& w, const M3& transform, V3 pos, V3 cam)
-{
-    V3 dl = transform * normalize(pos - cam);
-    size_t best = 0;
-    float best_err = 1000.0f;
-    for (size_t i = 0; i < w.presort_dirs.size(); i++) {
-        V3 pd = w.presort_dirs[i];
-        float ex = dl.x - pd.x, ey = dl.y - pd.y, ez = dl.z - pd.z;
-        float err = (ex * ex + ey * ey) + ez * ez;
-        if (err < best_err) { best = i; best_err = err; }
-    }
-    return best;
 }
 
 // merged-group list, wangtile.rs:595-670
@@ -1175,6 +1089,54 @@ std::string cache_key(size_t view_id, const std::vector<std::pair<size_t, size_t
     for (auto& t : tid) { put(t.first); put(t.second); }
     for (int s : st) put((uint64_t)status_hash(s));
     return k;
+}
+
+// The host-built lists of one merged group (no device merge), wangtile.rs:562-593,672-675: from the LRU cache, with its map ids
+// moved to this group's members, or built and cached.  Appends them to the wang's merged arrays and sets the record's
+// merged_count / single_lod_id / cache_hit.
+void append_host_merged(gswt_wang& w, const TileInstance& head, size_t view_id, gswt_sorted_tile& st)
+{
+    std::vector<std::pair<size_t, size_t>> tids;
+    std::vector<int> sts;
+    for (size_t m_mi : head.merged_from) {
+        const TileInstance* mt = w.tile_map[m_mi].get();
+        tids.emplace_back(mt->lod, mt->tile);
+        sts.push_back(mt->transition);
+    }
+    const std::string key = cache_key(view_id, tids, sts);
+    const RenderDataValue* val = nullptr;
+    RenderDataValue fresh;
+    std::vector<uint32_t> remapped;
+    if (w.user.use_cache) {
+        auto it = w.lru_index.find(key);
+        if (it != w.lru_index.end()) {
+            w.lru.splice(w.lru.begin(), w.lru, it->second);     // LruCache::get promotes
+            val = &it->second->second;
+            st.cache_hit = 1;
+            // update map index, :578-589: first matching member wins
+            remapped = val->gs_map_id;
+            const auto& old = val->merge_from_vec;
+            for (size_t i = 0; i < val->splat_count; i++)
+                for (size_t j = 0; j < old.size(); j++)
+                    if (remapped[i] == (uint32_t)old[j]) { remapped[i] = (uint32_t)head.merged_from[j]; break; }
+        }
+    }
+    if (!val) {
+        build_merged_value(w, head.merged_from, view_id, head.lod, fresh);
+        if (w.user.use_cache) {
+            w.lru.emplace_front(key, fresh);                       // LruCache::put
+            w.lru_index[key] = w.lru.begin();
+            while (w.lru.size() > w.user.cache_size) { w.lru_index.erase(w.lru.back().first); w.lru.pop_back(); }
+        }
+        val = &fresh;
+        remapped = fresh.gs_map_id;
+    }
+    st.merged_count = (uint32_t)val->splat_count;
+    st.single_lod_id = val->single_lod_id;
+    w.m_gs.insert(w.m_gs.end(), val->gs_index.begin(), val->gs_index.end());
+    w.m_map.insert(w.m_map.end(), remapped.begin(), remapped.end());
+    if (val->has_lod) w.m_lod.insert(w.m_lod.end(), val->gs_lod_id.begin(), val->gs_lod_id.end());
+    else w.m_lod.insert(w.m_lod.end(), val->splat_count, 0u);
 }
 
 int check_user(const gswt_user_data& u)
@@ -1696,83 +1658,52 @@ try {
     if (!w->initialized) return fail(GSWT_ERR_STATE, "WangTile::sort_tiles before build_tiles");
     if (w->rows_only && !w->device_merge)
         return fail(GSWT_ERR_STATE, "gswt_wang_sort_tiles: a rows-only wang has no host base lists; merged lists need device merge");
-    const bool need_corner = w->user.tile_sort_type == SORT_GRAPH || w->user.merge_type == MERGE_EDGE;
-    (void)need_corner;
     V3 cam{cam_pos[0], cam_pos[1], cam_pos[2]};
     if (w->user.merge_type == MERGE_AXIS) selective_merge_axis(*w, cam, vp);
     else if (w->user.merge_type == MERGE_EDGE) selective_merge_edge(*w, cam, vp);
     std::vector<size_t> order;
     switch (w->user.tile_sort_type) {
-    case SORT_DISTANCE: order = sort_tiles_object_pos(*w, cam); break;
-    case SORT_VIEWPORT: order = sort_tiles_object_vp(*w, vp); break;
+    case SORT_DISTANCE:
+    case SORT_VIEWPORT: order = sort_tiles_object_key(*w, (int)w->user.tile_sort_type, cam, vp); break;
     case SORT_OBJECT: order = sort_tiles_object_bfs(*w, cam); break;
     default: order = sort_tiles_object_graph(*w, cam); break;
     }
     w->sorted.clear();
     w->m_gs.clear(); w->m_map.clear(); w->m_lod.clear();
     w->m_groups.clear(); w->m_members.clear();
+    static_assert(sizeof(V3) == 3 * sizeof(float), "presort_dirs is read as a flat float table");
+    const float* dirs = reinterpret_cast<const float*>(w->presort_dirs.data());
+    const int n_view = (int)w->presort_dirs.size();
     size_t merged_total = 0;
     for (size_t mi : order) {
         const TileInstance* ti = w->tile_map[mi].get();
-        size_t view_id;
-        std::vector<std::pair<size_t, size_t>> tids;
-        std::vector<int> sts;
-        if (ti->merge == MS_FROM) {
-            bool merge_x = true, merge_y = true;
-            V3 avg_c;
-            Quat avg_q;
+        const bool grouped = ti->merge == MS_FROM;
+        // the view; of a group also its description (what gswt_set_draws_merge_groups consumes)
+        uint32_t view_id;
+        gswt_merge_group grp{0, (uint32_t)w->m_members.size(), (uint32_t)ti->merged_from.size(), 0};
+        size_t group_len = 0;
+        bool do_transition = false;
+        if (grouped) {
+            GroupView gv;
             for (size_t m_mi : ti->merged_from) {
+                const TileInstance* mt = w->tile_map[m_mi].get();
                 int mx, my;
                 w->index_to_map(m_mi, mx, my);
-                if (mx != ti->mx) merge_x = false;
-                if (my != ti->my) merge_y = false;
-                const TileInstance* mt = w->tile_map[m_mi].get();
-                tids.emplace_back(mt->lod, mt->tile);
-                sts.push_back(mt->transition);
-                avg_c = avg_c + mt->tile_center;
-                Quat q = quat_from_mat3(mt->to_local);
-                avg_q.s += q.s; avg_q.x += q.x; avg_q.y += q.y; avg_q.z += q.z;
-            }
-            if (!merge_x && !merge_y) view_id = w->presort_dirs.size() - 1;
-            else {
-                float n = (float)ti->merged_from.size();
-                Quat q{avg_q.s / n, avg_q.x / n, avg_q.y / n, avg_q.z / n};
-                view_id = choose_presort_view(*w, mat3_from_quat(q), avg_c / n, cam);
-            }
-        } else {
-            view_id = choose_presort_view(*w, ti->to_local, ti->tile_center, cam);
-            tids.emplace_back(ti->lod, ti->tile);
-            sts.push_back(ti->transition);
-        }
-        gswt_sorted_tile st;
-        memset(&st, 0, sizeof(st));
-        st.lod = (uint32_t)ti->lod; st.tile = (uint32_t)ti->tile; st.view_id = (uint32_t)view_id;
-        st.tile_offset[0] = ti->tile_offset.x; st.tile_offset[1] = ti->tile_offset.y; st.tile_offset[2] = ti->tile_offset.z;
-        st.map_index = (uint32_t)ti->map_index;
-        st.map_coord[0] = (uint32_t)ti->mx; st.map_coord[1] = (uint32_t)ti->my;
-        st.tile_center[0] = ti->tile_center.x; st.tile_center[1] = ti->tile_center.y; st.tile_center[2] = ti->tile_center.z;
-        st.transition = ti->transition; st.spawning_factor = ti->spawning;
-        st.has_corners = ti->has_corner ? 1 : 0;
-        for (int ci = 0; ci < 4; ci++) { st.corners[3 * ci] = ti->corner[ci].pos.x; st.corners[3 * ci + 1] = ti->corner[ci].pos.y; st.corners[3 * ci + 2] = ti->corner[ci].pos.z; }
-        st.key_len = (uint32_t)tids.size();
-        st.single_lod_id = -1;
-        if (ti->merge == MS_FROM) {
-            // group description (what gswt_set_draws_merge_groups consumes)
-            gswt_merge_group grp;
-            grp.view_id = (uint32_t)view_id; grp.first_member = (uint32_t)w->m_members.size(); grp.n_members = (uint32_t)ti->merged_from.size(); grp._pad = 0;
-            size_t group_len = 0;
-            bool do_transition = false;
-            for (size_t m_mi : ti->merged_from) {
-                const TileInstance* mt = w->tile_map[m_mi].get();
-                gswt_merge_member mm;
-                mm.map_index = (uint32_t)m_mi; mm.lod = (uint32_t)mt->lod; mm.tile = (uint32_t)mt->tile; mm.other_lod = -1;
-                if (mt->transition == TR_CHANGING_LOWER) mm.other_lod = (int32_t)mt->lod + 1;
-                else if (mt->transition == TR_CHANGING_HIGHER) mm.other_lod = (int32_t)mt->lod - 1;
-                if (mt->transition != TR_NONE) do_transition = true;
+                group_view_add(gv, ti->mx, ti->my, mx, my, mt->tile_center, mt->to_local);
+                const gswt_merge_member mm = merge_member_of((uint32_t)m_mi, (uint32_t)mt->lod, (uint32_t)mt->tile, mt->transition, do_transition);
                 group_len += w->cnt(mt->lod, mt->tile);
                 if (mm.other_lod >= 0) group_len += w->cnt((size_t)mm.other_lod, mt->tile);
                 w->m_members.push_back(mm);
             }
+            view_id = group_view_finish(gv, grp.n_members, dirs, n_view, cam);
+        } else view_id = choose_presort_view(dirs, n_view, ti->to_local, ti->tile_center, cam);
+        // the record
+        float corners[12];
+        for (int ci = 0; ci < 4; ci++) { corners[3 * ci] = ti->corner[ci].pos.x; corners[3 * ci + 1] = ti->corner[ci].pos.y; corners[3 * ci + 2] = ti->corner[ci].pos.z; }
+        gswt_sorted_tile st = sorted_tile_of((uint32_t)ti->lod, (uint32_t)ti->tile, view_id, ti->tile_offset, (uint32_t)ti->map_index, ti->mx, ti->my, ti->tile_center,
+                                             ti->transition, ti->spawning, ti->has_corner ? 1 : 0, corners, grouped ? grp.n_members : 1u);
+        if (grouped) {
+            grp.view_id = view_id;
             st.merged = 1;
             st.merged_group = (uint32_t)w->m_groups.size();
             st.merged_offset = (uint32_t)merged_total;
@@ -1780,42 +1711,7 @@ try {
             st.single_lod_id = do_transition ? -1 : (int32_t)ti->lod;
             w->m_groups.push_back(grp);
             merged_total += group_len;
-            if (!w->device_merge) {
-            std::string key = cache_key(view_id, tids, sts);
-            const RenderDataValue* val = nullptr;
-            RenderDataValue fresh;
-            std::vector<uint32_t> remapped;
-            if (w->user.use_cache) {
-                auto it = w->lru_index.find(key);
-                if (it != w->lru_index.end()) {
-                    w->lru.splice(w->lru.begin(), w->lru, it->second);     // LruCache::get promotes
-                    val = &it->second->second;
-                    st.cache_hit = 1;
-                    // update map index, :578-589: first matching member wins
-                    remapped = val->gs_map_id;
-                    const auto& old = val->merge_from_vec;
-                    for (size_t i = 0; i < val->splat_count; i++)
-                        for (size_t j = 0; j < old.size(); j++)
-                            if (remapped[i] == (uint32_t)old[j]) { remapped[i] = (uint32_t)ti->merged_from[j]; break; }
-                }
-            }
-            if (!val) {
-                build_merged_value(*w, ti->merged_from, view_id, ti->lod, fresh);
-                if (w->user.use_cache) {
-                    w->lru.emplace_front(key, fresh);                       // LruCache::put
-                    w->lru_index[key] = w->lru.begin();
-                    while (w->lru.size() > w->user.cache_size) { w->lru_index.erase(w->lru.back().first); w->lru.pop_back(); }
-                }
-                val = &fresh;
-                remapped = fresh.gs_map_id;
-            }
-            st.merged_count = (uint32_t)val->splat_count;
-            st.single_lod_id = val->single_lod_id;
-            w->m_gs.insert(w->m_gs.end(), val->gs_index.begin(), val->gs_index.end());
-            w->m_map.insert(w->m_map.end(), remapped.begin(), remapped.end());
-            if (val->has_lod) w->m_lod.insert(w->m_lod.end(), val->gs_lod_id.begin(), val->gs_lod_id.end());
-            else w->m_lod.insert(w->m_lod.end(), val->splat_count, 0u);
-            }
+            if (!w->device_merge) append_host_merged(*w, *ti, view_id, st);
         }
         w->sorted.push_back(st);
     }
@@ -1836,36 +1732,9 @@ int gswt_renderer_build_draws(const gswt_sort_data* sort, gswt_draw* draws_out)
 try {
     if (!sort || (!draws_out && sort->n_tiles)) return fail(GSWT_ERR_BAD_ARG, "gswt_renderer_build_draws: null argument");
     for (uint32_t i = 0; i < sort->n_tiles; i++) {
-        const gswt_sorted_tile& t = sort->tiles[i];
-        gswt_draw& d = draws_out[i];
-        memset(&d, 0, sizeof(d));
-        gswt_tile_uniforms& u = d.tile;
-        u.single_draw = 0; u.map_index = t.map_index; u.single_lod_id = -1; u.valid_lod_id = -1; u.changing = 0; u.changing_to_lower = -1;
-        u.tile_id[0] = t.lod; u.tile_id[1] = t.tile; u.tile_id[2] = t.view_id; u.tile_id[3] = 0;
-        u.offset[0] = t.tile_offset[0]; u.offset[1] = t.tile_offset[1]; u.offset[2] = t.tile_offset[2]; u.offset[3] = 0.0f;
-        u.map_coord[0] = t.map_coord[0]; u.map_coord[1] = t.map_coord[1];
-        d.lod = t.lod;
-        if (t.merged) {
-            u.single_draw = 1;
-            u.single_lod_id = t.single_lod_id;
-            u.changing = t.single_lod_id == -1 ? 1u : 0u;
-            d.merged = 1; d.merged_offset = t.merged_offset; d.merged_count = t.merged_count; d.merged_group = t.merged_group;
-            d.merged_has_lod = t.single_lod_id == -1 ? 1u : 0u;
-        } else {
-            d.base_lod = t.lod;
-            if (t.transition == TR_CHANGING_LOWER) { u.changing = 1; u.changing_to_lower = 1; }
-            else if (t.transition == TR_CHANGING_HIGHER) {
-                u.changing = 1; u.changing_to_lower = 0;
-                if (t.lod == 0) return fail(GSWT_ERR_BAD_ARG, "render: Changing(false) on lod 0 (index underflow in the reference)");
-                d.base_lod = t.lod - 1;
-            } else u.valid_lod_id = (int32_t)t.lod;
-            d.base_tile = t.tile; d.base_view = t.view_id;
-        }
-        if (t.key_len == 1) {                          // viewport culling only for non-merged tiles, :472
-            if (!t.has_corners) return fail(GSWT_ERR_STATE, "render: corner_data is None (called `Option::unwrap()` on a `None` value, renderer.rs:476)");
-            d.cull_enable = 1;
-            memcpy(d.corners, t.corners, sizeof(d.corners));
-        }
+        const uint32_t err = draw_from_tile(sort->tiles[i], draws_out[i]);
+        if (err & ERR_LOD0_HIGHER) return fail(GSWT_ERR_BAD_ARG, "render: Changing(false) on lod 0 (index underflow in the reference)");
+        if (err & ERR_NO_CORNERS) return fail(GSWT_ERR_STATE, "render: corner_data is None (called `Option::unwrap()` on a `None` value, renderer.rs:476)");
     }
     return GSWT_OK;
 } GSWT_CATCH("gswt_renderer_build_draws")

@@ -20,6 +20,19 @@ def _pipe(half, user_kw, n_lod=3, lod0=600, height_tex=None, seed=3):
     return pipe, verts
 
 
+def _build_draws(wang, tiles, n_tiles):
+    """gswt_renderer_build_draws of n_tiles records given as bytes -> the draws' bytes"""
+    from gswt_renderer_amd import _lib as L
+    from gswt_renderer_amd.host import SortDataC, _check
+    buf = C.create_string_buffer(tiles, max(1, len(tiles)))
+    sd = SortDataC()
+    sd.n_tiles = n_tiles
+    sd.tiles = C.cast(buf, C.POINTER(L.SortedTile))
+    draws = (L.Draw * max(1, n_tiles))()
+    _check(wang._lib.gswt_renderer_build_draws(C.byref(sd), draws))
+    return bytes(draws)[:n_tiles * C.sizeof(L.Draw)]
+
+
 def _host_event(pipe, pos, vp, rebuild):
     from gswt_renderer_amd import _lib as L
     w = pipe.wang
@@ -62,6 +75,8 @@ def _compare(pipe, dw, pos, vp, rebuild, tag):
     assert np.array_equal(a[:, 2], b[:, 2]), f"{tag}: view ids differ"
     assert tiles == ref["tiles"], f"{tag}: records differ in columns {sorted(set(np.argwhere(a != b)[:, 1].tolist()))}"
     assert groups == ref["groups"] and members == ref["members"], tag
+    # the host's draw function is a pure function of the records (the device builds its draws with the same one)
+    assert _build_draws(pipe.wang, tiles, nt) == ref["draws"], f"{tag}: draws built from the worker's records differ from the host's"
     return ref
 
 
@@ -86,6 +101,28 @@ def test_orders_and_merges_match_host(sort_type, merge_type):
     for k, (pos, tgt) in enumerate(CAMS):
         cu, vp = _cam(pos, tgt)
         _compare(pipe, dw, pos, vp, rebuild=(k % 2 == 0), tag=f"sort {sort_type} merge {merge_type} cam {k}")
+    dw.close()
+
+
+@pytest.mark.parametrize("sort_type,merge_type", [(3, 0), (3, 1), (0, 2), (1, 2), (2, 2), (3, 2)])
+def test_frames_from_worker_draws_match_host_draws(sort_type, merge_type):
+    """The draws the worker builds are read back by no ABI: a frame rendered from them (gswt_set_draws_from_worker) must equal
+    the frame rendered from the host's draw list bit for bit.  11 x 9 cells: merged and unmerged tiles, both Changing
+    directions and Spawning border cells on these cameras."""
+    from gswt_renderer_amd import host
+    from gswt_renderer_amd.worker import DeviceWorker
+    W, H = 320, 180
+    pipe, _ = _pipe((5, 4), dict(surface_type=host.SURFACE_NONE, tile_sort_type=sort_type, merge_type=merge_type, lod_blending=True,
+                                 lod_transition_width_ratio=0.1, merge_topk=12, merge_dot_threshold=0.6, merge_tile_dist=(1, 4), lod_max_dist=6.0))
+    dw = DeviceWorker(pipe.renderer, pipe.wang)
+    for k, (pos, tgt) in enumerate(CAMS[:2]):
+        cu, vp = _cam(pos, tgt, W, H)
+        _compare(pipe, dw, pos, vp, rebuild=True, tag=f"sort {sort_type} merge {merge_type} cam {k}")
+        pipe.update(pos, vp, force_sort=True)
+        img_host = pipe.render(cu, W, H)
+        dw.swap_in()
+        img_dev = pipe.render(cu, W, H)
+        assert np.array_equal(img_host, img_dev), f"sort {sort_type} merge {merge_type} cam {k}"
     dw.close()
 
 
