@@ -178,9 +178,16 @@ class TileStyle(C.Structure):
     _fields_ = [("tint", C.c_uint8 * 3), ("tint_strength", C.c_uint8), ("dim", C.c_uint8), ("_pad", C.c_uint8 * 3)]
 
 
+class ShadowParams(C.Structure):
+    """gswt_shadow_params: gswt_set_shadow_map's block (96 B; shadows.ShadowMap packs it)."""
+    _fields_ = [("world_to_light", C.c_float * 16), ("bias", C.c_float), ("strength", C.c_float), ("shade_color", C.c_float * 3),
+                ("_pad", C.c_uint32 * 3)]
+
+
 assert C.sizeof(Cell) == 260 and C.sizeof(CellState) == 20
 assert C.sizeof(Pick) == 16
 assert C.sizeof(TileStyle) == 8
+assert C.sizeof(ShadowParams) == 96 and ShadowParams.bias.offset == 64 and ShadowParams.shade_color.offset == 72
 
 assert C.sizeof(CameraUniforms) == 176 and C.sizeof(SceneUniforms) == 160 and C.sizeof(TileUniforms) == 80
 
@@ -203,6 +210,7 @@ SYMBOLS = {
     "gswt_set_option": (C.c_int, [_P, C.c_int, C.c_int]),
     "gswt_set_atmosphere": (C.c_int, [_P, _P]),
     "gswt_set_tile_styles": (C.c_int, [_P, _P, C.c_size_t]),
+    "gswt_set_shadow_map": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "gswt_upload_scene": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int]),
     "gswt_configure": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "gswt_set_draws": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_size_t]),

@@ -64,6 +64,8 @@ gswt_ctx::~gswt_ctx()
         if (ds.ev_up) hipEventDestroy(ds.ev_up);
     for (auto& sv : sty_pool)
         if (sv.ev_copied) hipEventDestroy(sv.ev_copied);
+    for (auto& sv : shd_pool)
+        if (sv.ev_copied) hipEventDestroy(sv.ev_copied);
     for (auto& sl : slots) {
         sl.release_graph();
         for (auto& e : sl.ev) if (e) hipEventDestroy(e);
@@ -268,6 +270,70 @@ try {
     return GSWT_OK;
 } GSWT_CATCH
 
+int gswt_set_shadow_map(gswt_ctx* c, const gswt_shadow_params* p, const float* depth, int width, int height, int depth_on_device)
+try {
+    static_assert(sizeof(gswt_shadow_params) == 96, "gswt_shadow_params layout");
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!p || !depth) { c->shd_cur = -1; return GSWT_OK; }
+    const float inf = std::numeric_limits<float>::infinity();
+    const float* M = p->world_to_light;
+    for (int k = 0; k < 16; k++)
+        if (!(std::fabs(M[k]) < inf)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: world_to_light[%d] = %g is not finite", k, M[k]);
+    const struct { const char* name; float v; } fields[] = {
+        {"bias", p->bias}, {"strength", p->strength}, {"shade_color[0]", p->shade_color[0]}, {"shade_color[1]", p->shade_color[1]},
+        {"shade_color[2]", p->shade_color[2]}};
+    for (const auto& fd : fields)
+        if (!(std::fabs(fd.v) < inf)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: %s = %g is not finite", fd.name, fd.v);
+    if (!(M[3] == 0.0f && M[7] == 0.0f && M[11] == 0.0f && M[15] == 1.0f))
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: world_to_light needs the bottom row (0, 0, 0, 1), not (%g, %g, %g, %g)", M[3], M[7], M[11], M[15]);
+    if (!(p->bias >= 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: bias = %g, not >= 0", p->bias);
+    if (!(p->strength > 0.0f && p->strength <= 1.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: strength = %g, not in (0, 1]", p->strength);
+    for (int k = 0; k < 3; k++)
+        if (!(p->shade_color[k] >= 0.0f && p->shade_color[k] <= 1.0f))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: shade_color[%d] = %g, not in [0, 1]", k, p->shade_color[k]);
+    if (p->_pad[0] | p->_pad[1] | p->_pad[2])
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: _pad = (%u, %u, %u), must be zero", p->_pad[0], p->_pad[1], p->_pad[2]);
+    if (width < 1 || width > 4096) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: width = %d, not in 1..4096", width);
+    if (height < 1 || height > 4096) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: height = %d, not in 1..4096", height);
+    // a version that is neither the current one nor the one a frame slot was last submitted with, as gswt_set_tile_styles picks its own:
+    // nothing here waits for a frame
+    int v = -1;
+    for (int k = 0; k < kShadowVersions && v < 0; k++) {
+        bool used = k == c->shd_cur;
+        for (const auto& sl : c->slots) used = used || sl.args.shd_ver == k;
+        if (!used) v = k;
+    }
+    if (v < 0) return fail(c, GSWT_ERR_STATE, "gswt_set_shadow_map: no free map version");
+    ShadowVersion& sv = c->shd_pool[v];
+    const size_t n = (size_t)width * height;
+    hipSetDevice(c->device);
+    if (sv.copy_pending) { HIP_TRY(c, hipEventSynchronize(sv.ev_copied)); sv.copy_pending = false; }
+    if (!sv.ev_copied) HIP_TRY(c, hipEventCreateWithFlags(&sv.ev_copied, hipEventDisableTiming));
+    // (buffers grow to twice the request, like the styles': growing frees the old buffer, which waits for the device, so a host whose image
+    // sizes creep upwards stalls once per version and doubling, not at every set)
+    HIP_TRY(c, sv.d.ensure_roomy(n));
+    // (on the ctx stream, like the styles' copy: the frames and proxy passes submitted from now on are ordered behind it; an earlier proxy
+    // pass that read this version is on the same stream, in front of the copy)
+    if (depth_on_device)
+        HIP_TRY(c, hipMemcpyAsync(sv.d.p, depth, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    else {
+        if (n > sv.h.cap) HIP_TRY(c, sv.h.ensure(2 * n));
+        memcpy(sv.h.p, depth, n * sizeof(float));
+        HIP_TRY(c, hipMemcpyAsync(sv.d.p, sv.h.p, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipEventRecord(sv.ev_copied, c->stream));
+    sv.copy_pending = true;
+    Shadow& k = sv.p;
+    k = Shadow{};
+    for (int r = 0; r < 3; r++)
+        for (int j = 0; j < 4; j++) k.row[r][j] = M[4 * j + r];
+    k.bias = p->bias; k.strength = p->strength;
+    for (int j = 0; j < 3; j++) k.shade[j] = p->shade_color[j];
+    k.w = width; k.h = height; k.z = sv.d.p;
+    c->shd_cur = v;
+    return GSWT_OK;
+} GSWT_CATCH
+
 int gswt_configure(gswt_ctx* c, const float* height_map, int hm_w, int hm_h)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;
@@ -366,6 +432,9 @@ static int validate_frame(gswt_ctx* c, const gswt_camera_uniforms* cam, const gs
     // nor a styled one (gswt_set_tile_styles with a table on)
     if (c->sty_cur >= 0 && !c->opt.strict_vs)
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: gswt_set_tile_styles' table needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no styled form)");
+    // nor a shadowed one (gswt_set_shadow_map with a map on)
+    if (c->shd_cur >= 0 && !c->opt.strict_vs)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: gswt_set_shadow_map's map needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no shadowed form)");
     return GSWT_OK;
 }
 
@@ -541,6 +610,7 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     b.tex = c->tex.p; b.hmap = c->hmap.p; b.boxes = c->static_boxes.p;
     // (the version the frame was submitted with: no gswt_set_tile_styles refills it while this slot names it)
     b.styles = a.sty_ver >= 0 ? c->sty_pool[a.sty_ver].d.p : nullptr; b.n_styles = a.sty_ver >= 0 ? c->sty_pool[a.sty_ver].n : 0u;
+    b.shadow = shadow_version(c, a.shd_ver);
     b.bg_rgba = a.d_bg; b.bg_depth = a.d_bgd; b.out = a.d_out; b.out_depth = a.d_out_depth; b.host_counters = sl.hc_dev;
     b.out_pick = reinterpret_cast<uint4*>(a.d_out_pick);
     b.n_tiles = (uint32_t)n_tiles; b.pair_cap = cap; b.seg = seg;
@@ -772,6 +842,7 @@ static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* 
     a.aa_s = c->opt.antialias > 0 ? antialias_s(c->opt.antialias, su->splat_scale) : 0.0f;
     a.atm = atmo_constants(c->atm);
     a.sty_ver = c->sty_cur;
+    a.shd_ver = c->shd_cur;
     return enqueue_frame(c, sl);
 }
 

@@ -221,7 +221,7 @@ try {
     ProxyArgs a;
     proxy_args(c, u, width, height, a);
     if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
-    launch_proxy(c->stream, a, c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
+    launch_proxy(c->stream, a, shadow_version(c, c->shd_cur), c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
     HIP_TRY(c, hipGetLastError());
     return GSWT_OK;
 } GSWT_CATCH
@@ -276,7 +276,7 @@ try {
     a.ortho_d[0] = sz * V[2]; a.ortho_d[1] = sz * V[6]; a.ortho_d[2] = sz * V[10];
     hipSetDevice(c->device);
     if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
-    launch_proxy_ortho(c->stream, a, c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
+    launch_proxy_ortho(c->stream, a, shadow_version(c, c->shd_cur), c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
     HIP_TRY(c, hipGetLastError());
     return GSWT_OK;
 } GSWT_CATCH

@@ -177,6 +177,7 @@ struct FrameArgs {
     float aa_s = 0.0f;                     // GSWT_OPT_ANTIALIAS as it stood when the frame was submitted: s = 4 v / splat_scale^2 (a re-run keeps it)
     Atmo atm = {};                         // gswt_set_atmosphere's block likewise, with its derived constants (all zero: off)
     int sty_ver = -1;                      // gswt_set_tile_styles' table likewise: its version in gswt_ctx::sty_pool (-1: styles off)
+    int shd_ver = -1;                      // gswt_set_shadow_map's block and image likewise: their version in gswt_ctx::shd_pool (-1: shadows off)
 };
 
 // One version of gswt_set_tile_styles' table: pinned staging (the host's entries, copied inside the call) and the device copy k_project
@@ -191,6 +192,18 @@ struct StyleVersion {
 };
 // the frame slots' versions and the current one can all differ: one more is always free
 constexpr int kStyleVersions = kFrameSlots + 2;
+
+// One version of gswt_set_shadow_map's map, held like a StyleVersion: the validated block as the kernels read it (p.z: the device image),
+// pinned staging for an image that comes from a host pointer (a device image is copied device to device, no staging), and the copy's
+// event.  In use while it is the current one or a frame slot was last submitted with it (FrameArgs::shd_ver); any other one may be refilled.
+struct ShadowVersion {
+    HostBuf<float> h;
+    DevBuf<float> d;
+    Shadow p = {};
+    hipEvent_t ev_copied = nullptr;        // behind the copy: the staging may be refilled once it has fired
+    bool copy_pending = false;
+};
+constexpr int kShadowVersions = kFrameSlots + 2;
 
 // A frame's events on its slot's stream.  GSWT_OPT_TIMING >= 1 records kEvStart, kEvEnd and the compositor kernel's pair, 2 also the
 // stage boundaries in between (nothing runs between kEvSorted and kEvRanges); kEvDone follows the frame's last command in any case.
@@ -259,7 +272,7 @@ struct FrameSlot {
 };
 
 // gswt_set_option's values with their defaults.  strict_vs, projection and antialias (and gswt_set_atmosphere's block, gswt_ctx::atm, and
-// gswt_set_tile_styles' table version, gswt_ctx::sty_cur) are snapshotted into FrameArgs when a frame is submitted; every other one is read when the frame (or the sort event) is enqueued.
+// gswt_set_tile_styles' table version, gswt_ctx::sty_cur, and gswt_set_shadow_map's version, gswt_ctx::shd_cur) are snapshotted into FrameArgs when a frame is submitted; every other one is read when the frame (or the sort event) is enqueued.
 struct Options {
     int no_prefilter = 0;                  // GSWT_OPT_NO_LOD_PREFILTER
     int debug_varyings = 0;
@@ -309,6 +322,9 @@ struct gswt_ctx {
     // gswt_set_tile_styles: the table versions and the one in force (-1: styles off).  Read when a frame is submitted.
     gswt::StyleVersion sty_pool[gswt::kStyleVersions];
     int sty_cur = -1;
+    // gswt_set_shadow_map: the map versions and the one in force (-1: shadows off).  Read when a frame is submitted and when a proxy pass is called.
+    gswt::ShadowVersion shd_pool[gswt::kShadowVersions];
+    int shd_cur = -1;
     // scene
     gswt::DevBuf<uint4> tex;
     size_t n_splats = 0;
@@ -453,6 +469,9 @@ inline Atmo atmo_constants(const gswt_atmosphere& a)
     }
     return m;
 }
+
+// gswt_set_shadow_map's version v as a kernel argument (-1: off, all zero)
+inline Shadow shadow_version(const gswt_ctx* c, int v) { return v >= 0 ? c->shd_pool[v].p : Shadow{}; }
 
 // opengl_to_wgpu * projection (gswt.wgsl:152-160, proxy.wgsl:84-91): clip z = (z + w) / 2, the other rows as they are
 inline void gl_to_wgpu_projection(const float* P, float* GP)

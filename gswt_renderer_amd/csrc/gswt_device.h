@@ -73,6 +73,18 @@ struct Atmo {
     float fog_color[3];
 };
 
+// gswt_set_shadow_map's block and image as the kernels read them (include/gswt_hip.h): a kernel argument of its own beside Frame / ProxyArgs,
+// so that neither struct grows and the instantiations without SHD stay the code they were.  z null: shadows off (all zero).
+struct Shadow {
+    float row[3][4];                       // rows 0..2 of world_to_light: light NDC x, y and the depth image's depth of a world point
+    float bias, strength;
+    float shade[3];
+    int32_t w, h;                          // the depth image, row 0 at the top
+    uint32_t _pad;                         // (no implicit padding: a recorded graph node compares its argument bytes)
+    const float* z;
+};
+static_assert(sizeof(Shadow) == 88, "Shadow has no implicit padding");
+
 // Per-frame constants (kernel argument, by value).
 struct Frame {
     float V[16];       // view
@@ -314,6 +326,8 @@ struct FrameBufs {
     // gswt_set_tile_styles' table as the frame was submitted with it, per map cell (tint r | g << 8 | b << 16 | tint_strength << 24, dim);
     // null: styles off (k_project<.., STY = false>)
     const uint2* styles; uint32_t n_styles;
+    // gswt_set_shadow_map's block and image version as the frame was submitted with them; shadow.z null: shadows off (k_project<.., SHD = false>)
+    Shadow shadow;
     const float4* bg_rgba; const float* bg_depth; float4* out;
     float* out_depth;                          // the frame's depth image (f32, the colour's geometry); null: none (gswt_render_depth)
     uint4* out_pick;                           // the frame's pick image (gswt_pick records, the colour's geometry); null: none (gswt_render_pick)
@@ -367,7 +381,7 @@ void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks
 // over every chunk instead of the live table), k_items + the compositor over the sorted slots `vals`.
 void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_cull);
 // (the atmosphere is on when f.atm.fade_end > 0 or f.atm.fog_density > 0: strict frames only, gswt_api.hip refuses the others;
-// the tile styles are on when b.styles is set, likewise)
+// the tile styles are on when b.styles is set, the sun shadows when b.shadow.z is, likewise)
 void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict, bool ortho);
 void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
 // b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer, the video formats
@@ -401,8 +415,9 @@ void launch_unshard(hipStream_t s, const void* gathered, void* out, int width, i
 void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int width, int height, int face_size, int equirect,
                    const float4* faces, float4* out);
 void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi, float4* faces);
-void launch_proxy(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth);
-void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth);
+// (shd.z set: the pass shades the ground by gswt_set_shadow_map's image, k_proxy<., ., SHD>)
+void launch_proxy(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth);
+void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth);
 // One level of the proxy mip build into dst (n x n float4).  src: the staged source, a.pitch bytes per row.  ranges: 2 n int2,
 // wv / wh: the tap weights, tmp: the intermediate, part: the partial sums (sizes: proxy_mip_* above; unused on a copy level).
 void launch_proxy_mip(hipStream_t s, const ProxyMipArgs& a, const uint8_t* src, int2* ranges, float* wv, float* wh, float4* tmp,

@@ -36,6 +36,46 @@ __device__ __forceinline__ float fog_amount(const Atmo& a, float dist)
     return a.fog_max * (1.0f - e);
 }
 
+// gswt_set_shadow_map's lookup (include/gswt_hip.h), shared by k_project<.., SHD> and k_proxy<.., SHD>, in two halves so that a caller can
+// put work between the texel loads and their use.  Every written operator is one binary32 operation.
+// shadow_fetch: the world point into the light's image and the 2 x 2 texels around it.  The four loads are UNCONDITIONAL, from clamped
+// indices, and nothing here reads what they return: which of them count is the tap's `ok` mask (bit k: texel k lies inside the image and
+// the point inside the image and the depth range), applied by shadow_amount.  Loads under a lane condition, or a select on their result
+// here, would make the wait for whatever the caller still has in flight an uncounted vmcnt(0) directly behind them.
+// Bounds: for a point outside (NaN included) u and v are replaced by 0; otherwise u is in (-1, w) and v in (-1, h), so i0 is in
+// [-1, w - 1] and i1 in [0, w] (rows likewise).  Every index is clamped to [0, w - 1] x [0, h - 1] (w, h >= 1), and j * w + i <
+// 4096 * 4096 fits an int.
+struct ShadowTap { float z00, z10, z01, z11, wx, wy, r; uint32_t ok; };
+__device__ __forceinline__ ShadowTap shadow_fetch(const Shadow& s, float c0, float c1, float c2)
+{
+    const float lx = ((s.row[0][0] * c0 + s.row[0][1] * c1) + s.row[0][2] * c2) + s.row[0][3];
+    const float ly = ((s.row[1][0] * c0 + s.row[1][1] * c1) + s.row[1][2] * c2) + s.row[1][3];
+    const float ld = ((s.row[2][0] * c0 + s.row[2][1] * c1) + s.row[2][2] * c2) + s.row[2][3];
+    const float W = (float)s.w, H = (float)s.h;
+    const float u = (lx * 0.5f + 0.5f) * W - 0.5f;
+    const float v = (0.5f - ly * 0.5f) * H - 0.5f;
+    const bool inside = (ld >= 0.0f && ld <= 1.0f) && (u > -1.0f && u < W) && (v > -1.0f && v < H);
+    const float us = inside ? u : 0.0f, vs = inside ? v : 0.0f;
+    const float x0 = floorf(us), y0 = floorf(vs);
+    ShadowTap t;
+    t.wx = us - x0; t.wy = vs - y0; t.r = ld - s.bias;
+    const int i0 = (int)x0, j0 = (int)y0, i1 = i0 + 1, j1 = j0 + 1;
+    const bool xa = i0 >= 0, xb = i1 < s.w, ya = j0 >= 0, yb = j1 < s.h;          // (i0 <= w - 1 and i1 >= 0 always, rows likewise)
+    t.ok = inside ? (uint32_t)(xa && ya) | (uint32_t)(xb && ya) << 1 | (uint32_t)(xa && yb) << 2 | (uint32_t)(xb && yb) << 3 : 0u;
+    const int ia = max(i0, 0), ib = min(i1, s.w - 1), ja = max(j0, 0) * s.w, jb = min(j1, s.h - 1) * s.w;
+    t.z00 = s.z[ja + ia]; t.z10 = s.z[ja + ib]; t.z01 = s.z[jb + ia]; t.z11 = s.z[jb + ib];
+    return t;
+}
+// shadow_amount: sh = strength * (1 - lit), lit the bilinear mix of the four depth compares; a texel that does not count (shadow_fetch's
+// mask) and a NaN texel are lit, and a point outside has weights 0 and every texel lit: lit = 1 exactly
+__device__ __forceinline__ float shadow_amount(const Shadow& s, const ShadowTap& t)
+{
+    const float t00 = (t.ok & 1u) && t.r > t.z00 ? 0.0f : 1.0f, t10 = (t.ok & 2u) && t.r > t.z10 ? 0.0f : 1.0f;
+    const float t01 = (t.ok & 4u) && t.r > t.z01 ? 0.0f : 1.0f, t11 = (t.ok & 8u) && t.r > t.z11 ? 0.0f : 1.0f;
+    const float lit = (t00 * (1.0f - t.wx) + t10 * t.wx) * (1.0f - t.wy) + (t01 * (1.0f - t.wx) + t11 * t.wx) * t.wy;
+    return s.strength * (1.0f - lit);
+}
+
 // halfToFloat, gswt.wgsl:478-494: normals as IEEE; subnormals scale 2^-15 (f * 2^-25);
 // Inf/NaN -> 0.  The definition is gswt_host::half_to_float (host/gswt_math.h, the shader's arithmetic): this is the hot path's form of
 // it and must equal it on all 65536 bit patterns, signs of zero included.

@@ -494,6 +494,20 @@ __device__ __forceinline__ bool tile_style_shade(const Frame& f, const uint2& st
     return true;
 }
 
+// gswt_set_shadow_map (no counterpart in vs_main), behind A9 and the tint, in front of the fog: the float colour goes toward shade_color by
+// sh = strength * (1 - lit) of the texels shadow_fetch loaded behind the frustum rejection (gswt_device_fn.h).  Returns whether the colour
+// changed: sh == 0 (fully lit, outside the image or the depth range) leaves the record's colour word alone; the debug draw modes keep theirs.
+__device__ __forceinline__ bool sun_shadow(const Frame& f, const Shadow& shd, const ShadowTap& tap, VertexOut& v)
+{
+    if (f.draw_mode != 0u) return false;
+    const float sh = shadow_amount(shd, tap);
+    if (sh == 0.0f) return false;
+    v.cr = v.cr * (1.0f - sh) + shd.shade[0] * sh;
+    v.cg = v.cg * (1.0f - sh) + shd.shade[1] * sh;
+    v.cb = v.cb * (1.0f - sh) + shd.shade[2] * sh;
+    return true;
+}
+
 // A3 :52-65 -- the offset of the entry's tile: the draw's own, or that of the member tile map_id of a merged group
 __device__ __forceinline__ void tile_offset(const Frame& f, const DrawDev& d, uint32_t map_id, float& ox, float& oy, float& oz)
 {
@@ -676,7 +690,7 @@ __device__ __forceinline__ void fog_requantise(const Frame& f, float atm_dist, u
     v.cr = (float)br / 255.0f; v.cg = (float)bg / 255.0f; v.cb = (float)bb / 255.0f;     // what the compositor will read
 }
 
-// a tinted colour the fog does not touch goes back into the record's 8 bits by the fog's own expression (with the fog on, fog_requantise
+// a tinted or shaded colour the fog does not touch goes back into the record's 8 bits by the fog's own expression (with the fog on, fog_requantise
 // takes the tinted floats and this is not called: one quantisation either way)
 __device__ __forceinline__ void tint_requantise(uint32_t rgba8, VertexOut& v)
 {
@@ -688,8 +702,9 @@ __device__ __forceinline__ void tint_requantise(uint32_t rgba8, VertexOut& v)
 }
 
 // A6..A10, STRICT: operator by operator as the shader text writes them (the comment above k_project)
-template <bool FULL, bool ORTHO, bool AA, bool ATM, bool STY>
-__device__ __forceinline__ bool vertex_strict(const Frame& f, const DrawDev& d, const uint4& w0, const uint4& w1, uint32_t lod_id, const Mapped& m, const uint2& sty, VertexOut& v)
+template <bool FULL, bool ORTHO, bool AA, bool ATM, bool STY, bool SHD>
+__device__ __forceinline__ bool vertex_strict(const Frame& f, const DrawDev& d, const uint4& w0, const uint4& w1, uint32_t lod_id, const Mapped& m, const uint2& sty,
+                                              const Shadow& shd, VertexOut& v)
 {
     const float c0 = m.c0, c1 = m.c1, c2 = m.c2;
     const float* const F = m.F;
@@ -700,6 +715,11 @@ __device__ __forceinline__ bool vertex_strict(const Frame& f, const DrawDev& d, 
         q[rr] = ((f.GP[rr] * cv[0] + f.GP[4 + rr] * cv[1]) + f.GP[8 + rr] * cv[2]) + f.GP[12 + rr] * cv[3];
     const float clip = 1.2f * q[3];
     if (q[2] < -clip || q[0] < -clip || q[0] > clip || q[1] < -clip || q[1] > clip) return false;
+    // gswt_set_shadow_map: the centre into the light's image and its four texel loads, issued here, behind the frustum rejection, so that
+    // their round trip passes under A7 and A8; sun_shadow reads them behind A9.  (The loads are unconditional, gswt_device_fn.h: the wait for w1
+    // in front of A7 is then a counted vmcnt(4) that leaves them in flight, not a vmcnt(0).)
+    ShadowTap tap = {};
+    if (SHD) tap = shadow_fetch(shd, c0, c1, c2);
     // A7 :169-205
     float K[9];
     splat_cov3(f, d, w1, K);
@@ -791,8 +811,10 @@ __device__ __forceinline__ bool vertex_strict(const Frame& f, const DrawDev& d, 
     // gswt_set_tile_styles: dim behind the three alpha products above, tint in front of the fog, which then mixes the tinted floats
     bool tinted = false;
     if (STY) tinted = tile_style_shade(f, sty, v);
+    // gswt_set_shadow_map: behind the tint, in front of the fog
+    if (SHD) tinted = sun_shadow(f, shd, tap, v) || tinted;
     if (ATM && f.atm.fog_density > 0.0f && f.draw_mode == 0u) fog_requantise(f, m.atm_dist, w1.w, v);
-    else if (STY && tinted) tint_requantise(w1.w, v);
+    else if ((STY || SHD) && tinted) tint_requantise(w1.w, v);
     // A10 :415-419
     v.ndcx = q[0] / q[3]; v.ndcy = q[1] / q[3]; v.depth = q[2] / q[3];
     v.fade = clampf(q[2] / q[3] + 1.0f, 0.0f, 1.0f);
@@ -934,8 +956,8 @@ __device__ __forceinline__ void fragment_setup(const Frame& f, const VertexOut& 
 
 // The kernel itself keeps the loads (launch table, list word, record: A1, A2 and the trace stamps around them) and the workgroup's sums; per
 // splat it calls, in this order, the stages above: tile_offset (A3), map_height_surface / map_sphere_surface (A4), atmosphere_fade,
-// lod_transition (A5), vertex_strict<FULL, ORTHO, AA, ATM, STY> or vertex_v2<FULL> (A6..A10; both over splat_cov3 and lod_blend_color, the
-// strict one over tile_style_shade, fog_requantise and tint_requantise) and fragment_setup (F1, F2, tile rectangle, record); with STY,
+// lod_transition (A5), vertex_strict<FULL, ORTHO, AA, ATM, STY, SHD> or vertex_v2<FULL> (A6..A10; both over splat_cov3 and lod_blend_color, the
+// strict one over shadow_fetch, tile_style_shade, sun_shadow, fog_requantise and tint_requantise) and fragment_setup (F1, F2, tile rectangle, record); with STY,
 // tile_style runs directly behind A1, in front of the record's loads.  A new per-splat feature goes into the stage it
 // belongs to; a new template flag into that stage's parameters.
 // k_project's stamps (tools/project_trace.py), rows 8192 + launch position: [0] entry, [1] launch-table entry known, [2] list word arrived (lane 0),
@@ -960,7 +982,10 @@ __device__ __forceinline__ void fragment_setup(const Frame& f, const VertexOut& 
 // STY (gswt_set_tile_styles with a table on, STRICT only): the per-cell hide, dim and tint of include/gswt_hip.h.  A template parameter like
 // ATM: a frame with styles off launches the instantiation it always did and never reads `styles`; which parts of a style are on for a splat
 // is a branch on the loaded entry inside the STY instantiations only.
-template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO, bool AA, bool ATM, bool STY>
+// SHD (gswt_set_shadow_map with a map on, STRICT only): the sun shadow of include/gswt_hip.h, a 2 x 2 depth compare in the light's image per
+// splat that passed the frustum test.  A template parameter like STY: a frame with shadows off launches the instantiation it always did and
+// never reads `shd`, which is a kernel argument of its own so that Frame stays what it was.
+template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO, bool AA, bool ATM, bool STY, bool SHD>
 __global__ __launch_bounds__(256) void k_project(
     const Frame f, const DrawDev* __restrict__ draws, const uint2* __restrict__ chunk_tab,
     const uint32_t* __restrict__ static_list, const uint32_t* __restrict__ merged_list,
@@ -968,7 +993,7 @@ __global__ __launch_bounds__(256) void k_project(
     const float* __restrict__ hmap, const uint32_t* __restrict__ draw_culled, const uint32_t* __restrict__ cell_culled,
     const uint32_t* __restrict__ live_cnt, const uint4* __restrict__ live_tab, uint2* __restrict__ rects,
     Rec* __restrict__ recs, float* __restrict__ depths, uint32_t* __restrict__ block_sums, uint32_t* __restrict__ super_sums, uint32_t n_super,
-    Varyings* __restrict__ dbg, float4* __restrict__ col_f, const uint2* __restrict__ styles, uint32_t n_styles)
+    Varyings* __restrict__ dbg, float4* __restrict__ col_f, const uint2* __restrict__ styles, uint32_t n_styles, const Shadow shd)
 {
     __shared__ uint32_t s_wsum[4], s_wvis[4];
     // chunk_tab is in LAUNCH order, which is not slot order: workgroup b runs on XCD b % 8, and the table is laid out so
@@ -1055,7 +1080,7 @@ __global__ __launch_bounds__(256) void k_project(
             // A6..A10
             VertexOut v;
             bool kept;
-            if constexpr (STRICT) kept = vertex_strict<FULL, ORTHO, AA, ATM, STY>(f, d, w0, w1, lod_id, m, sty, v);
+            if constexpr (STRICT) kept = vertex_strict<FULL, ORTHO, AA, ATM, STY, SHD>(f, d, w0, w1, lod_id, m, sty, shd, v);
             else kept = vertex_v2<FULL>(f, d, w0, w1, lod_id, m, v);
             if (!kept) break;
             if (DEBUG) {
@@ -3110,13 +3135,14 @@ void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t 
     // (nor have the tile styles: STY likewise, on when the frame was submitted with a table, b.styles)
     const bool strict_seq = strict || ortho;
     const bool aa = strict_seq && f.aa_s > 0.0f, atm = strict_seq && (f.atm.fade_end > 0.0f || f.atm.fog_density > 0.0f);
-    const bool sty = strict_seq && b.styles != nullptr;
-    with_variant([&](auto D, auto F, auto S, auto O, auto A, auto M, auto Y) {
-        if constexpr (S || !(O || A || M || Y))
-            GSWT_LAUNCH((k_project<D, F, S, O, A, M, Y>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,
+    // (nor have the sun shadows: SHD likewise, on when the frame was submitted with a map, b.shadow.z)
+    const bool sty = strict_seq && b.styles != nullptr, shd = strict_seq && b.shadow.z != nullptr;
+    with_variant([&](auto D, auto F, auto S, auto O, auto A, auto M, auto Y, auto Z) {
+        if constexpr (S || !(O || A || M || Y || Z))
+            GSWT_LAUNCH((k_project<D, F, S, O, A, M, Y, Z>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,
                         b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums,
-                        b.super_sums, n_super, b.dbg, b.col_f, b.styles, b.n_styles);
-    }, debug, full, strict_seq, ortho, aa, atm, sty);
+                        b.super_sums, n_super, b.dbg, b.col_f, b.styles, b.n_styles, b.shadow);
+    }, debug, full, strict_seq, ortho, aa, atm, sty, shd);
     GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, n_super, b.counters, b.super_sums + 2u * kSuperStride * n_super, b.pair_cap, b.live_cnt, n_launch / 8u);
 }
 

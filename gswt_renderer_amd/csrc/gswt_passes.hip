@@ -182,9 +182,13 @@ __device__ __forceinline__ void proxy_tex_bilinear(const float4* __restrict__ lv
 // the lower pixel differ from the pixel's own by their origin instead of their direction.  Rays, vertices, a.cam and the view's translation
 // are in the grid frame, whose lattice starts at (0, 0): far from the world origin nothing here is rounded at the world coordinates'
 // magnitude but the lattice itself (rx, ry: the reference's f32 vertices).
-template <bool FOG, bool ORTHO = false>
+// SHD (gswt_set_shadow_map with a map on when the pass is called): a pixel the proxy writes goes toward shade_color by the splats' own
+// sh = strength * (1 - lit) (shadow_fetch / shadow_amount, gswt_device_fn.h) at the ray's hit point in WORLD coordinates -- the orthographic
+// pass brings its grid-frame point back by (gx0, gy0) --, behind `brightness` and in front of the fog.  Depth, unwritten pixels and the
+// black_background output are what they are without it.
+template <bool FOG, bool ORTHO = false, bool SHD = false>
 __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* __restrict__ hm, const float4* __restrict__ tex,
-                                               float4* __restrict__ rgba, float* __restrict__ depth_buf)
+                                               float4* __restrict__ rgba, float* __restrict__ depth_buf, const Shadow shd)
 {
     const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= a.width || y >= a.height) return;
@@ -255,6 +259,12 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
     if (!hit || !(dep < depth_buf[pi])) return;                  // CompareFunction::Less, depth write on
     depth_buf[pi] = dep;
     if (a.black_background == 1u) { rgba[pi] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
+    // (the texels' round trip passes under the texturing below)
+    ShadowTap tap = {};
+    if (SHD) {
+        const float hx = o[0] + best_t * d[0], hy = o[1] + best_t * d[1], hz = o[2] + best_t * d[2];
+        tap = shadow_fetch(shd, ORTHO ? hx + a.gx0 : hx, ORTHO ? hy + a.gy0 : hy, hz);
+    }
     float uv[2], uvx[2], uvy[2], dxr[3], dyr[3];
     proxy_plane_uv(a, o, d, pa, nrm, uv);
     if (ORTHO) {                                                 // (dxr, dyr: the neighbours' origins)
@@ -282,6 +292,14 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
     proxy_tex_bilinear(tex + a.mip_off[l1], a.tex_size >> l1, uv[0], uv[1], c1);
     float4 px = make_float4((c0[0] * (1.0f - fl) + c1[0] * fl) * a.brightness, (c0[1] * (1.0f - fl) + c1[1] * fl) * a.brightness,
                             (c0[2] * (1.0f - fl) + c1[2] * fl) * a.brightness, 1.0f);
+    if (SHD) {
+        const float sh = shadow_amount(shd, tap);
+        if (sh != 0.0f) {
+            px.x = px.x * (1.0f - sh) + shd.shade[0] * sh;
+            px.y = px.y * (1.0f - sh) + shd.shade[1] * sh;
+            px.z = px.z * (1.0f - sh) + shd.shade[2] * sh;
+        }
+    }
     if (FOG) {
         float dist;
         if (ORTHO) {
@@ -582,18 +600,26 @@ void launch_fill_f32(hipStream_t s, float* p, size_t n, float v)
     if (n) hipLaunchKernelGGL(k_fill_f32, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, p, n, v);
 }
 
-void launch_proxy(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth)
+// the pass's instantiation from the fog part of a.atm and the shadow map in force (both read when the pass is called)
+template <bool ORTHO>
+static void launch_proxy_variant(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth)
 {
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-    if (a.atm.fog_density > 0.0f) hipLaunchKernelGGL(k_proxy<true>, grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
-    else hipLaunchKernelGGL(k_proxy<false>, grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
+    const bool fog = a.atm.fog_density > 0.0f, shade = shd.z != nullptr;
+    if (fog && shade) hipLaunchKernelGGL((k_proxy<true, ORTHO, true>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
+    else if (fog) hipLaunchKernelGGL((k_proxy<true, ORTHO, false>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
+    else if (shade) hipLaunchKernelGGL((k_proxy<false, ORTHO, true>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
+    else hipLaunchKernelGGL((k_proxy<false, ORTHO, false>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
 }
 
-void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const float* hm, const float4* tex, float4* rgba, float* depth)
+void launch_proxy(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth)
 {
-    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-    if (a.atm.fog_density > 0.0f) hipLaunchKernelGGL((k_proxy<true, true>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
-    else hipLaunchKernelGGL((k_proxy<false, true>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth);
+    launch_proxy_variant<false>(s, a, shd, hm, tex, rgba, depth);
+}
+
+void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth)
+{
+    launch_proxy_variant<true>(s, a, shd, hm, tex, rgba, depth);
 }
 
 }  // namespace gswt

@@ -11,8 +11,8 @@ depth = (d - near) / (far - near), so under a `top_down` camera the depth and pi
 The matrices are evaluated in float64 and rounded to float32 once per element.  The ground under an orthographic frame is
 the proxy pass's orthographic form: ``GSWTRenderer.proxy_render(cam.proxy_uniforms(...), W, H, rgba, depth, clear, projection=1)``
 (gswt_proxy_render_ortho) writes the colour and depth images the frame then takes as bg_rgba / bg_depth, so a height field
-holds the terrain where no splat covers it and a sun-direction depth map contains the ground.  The skybox has no orthographic
-form.
+holds the terrain where no splat covers it and a sun-direction depth map contains the ground (``shadows.from_ortho_camera``
+turns such a frame's depth image into the shadow map of gswt_set_shadow_map).  The skybox has no orthographic form.
 """
 from __future__ import annotations
 

@@ -81,7 +81,7 @@ class GSWTPipeline:
 
     def render(self, camera_uniforms, width, height, **kw):
         """GSWTRenderer.render with the scene uniforms of the current configuration; every other keyword (order_mode, bg_rgba, depth,
-        pick, projection, antialias, atmosphere, tile_styles, ...) is passed through."""
+        pick, projection, antialias, atmosphere, tile_styles, shadow, ...) is passed through."""
         su = self.wang.scene_uniforms(splat_scale=kw.pop("splat_scale", 1.0), scene_scale=kw.pop("scene_scale", (1.0, 1.0, 1.0)),
                                       height_map_scale_v=kw.pop("height_map_scale_v", 1.0))
         # the other RenderConfig fields of SceneUniforms::from_data (renderer.rs:631-672)

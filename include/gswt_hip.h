@@ -421,6 +421,78 @@ typedef struct {
 } gswt_tile_style;          /* 8 bytes; all-zero = neutral */
 GSWT_API int gswt_set_tile_styles(gswt_ctx *ctx, const gswt_tile_style *styles, size_t n_styles);
 
+/* ---- sun shadows: shade splats and proxy ground by a light-space depth map -------------------------
+ * An orthographic frame along the sun's direction (GSWT_OPT_PROJECTION = 1 with gswt_render_depth, over gswt_proxy_render_ortho's
+ * ground) is a shadow map: the depth of the first surface the light meets.  This call is its consumer: every splat of the frames
+ * submitted afterwards, and every ground pixel of the proxy passes called afterwards, is tested against the map and, where something
+ * lies between it and the light, goes toward shade_color.  The host may equally pass a map of its own occluders (a building placed
+ * on the terrain) in the same convention, or the minimum of both.  The reference has no shadows.
+ *
+ * Input image.  depth is width x height f32, row 0 at the top, 0 near .. 1 far: exactly what gswt_render_depth writes for an
+ * orthographic frame of that size.  depth_on_device != 0: a device pointer, copied device to device on the ctx stream (the caller
+ * orders later writes to it behind that stream, as for every device pointer the library reads); otherwise a host pointer, copied
+ * inside the call.  p == NULL or depth == NULL: shadows off, the default.  A frame with shadows off launches exactly the kernels it
+ * launches without this call and is bit for bit the same frame.
+ *
+ * world_to_light (M, column-major, affine) takes a world point to the light's image: row 0 and 1 light NDC x, y (+y up, -1..1 over
+ * the image), row 2 the depth in the image's convention.  For a map rendered by this library, M = opengl_to_wgpu * projection * view
+ * of the orthographic camera (shadows.from_ortho_camera in the Python layer evaluates it in float64 and rounds once).
+ *
+ * Definition.  Every written operator is one correctly rounded binary32 operation, nothing fused.  c is the surface-mapped,
+ * scene-scaled centre A6 feeds to the view matrix; W, H = width, height; Z the image:
+ *     lx = ((M[0]*c0 + M[4]*c1) + M[8]*c2) + M[12]        ly, ld likewise from rows 1, 2
+ *     u  = (lx * 0.5f + 0.5f) * (float)W - 0.5f           v = (0.5f - ly * 0.5f) * (float)H - 0.5f
+ *     outside:  !(ld >= 0 && ld <= 1) || !(u > -1 && u < W) || !(v > -1 && v < H)   (NaN included)  ->  lit = 1
+ *     x0 = floorf(u); y0 = floorf(v); wx = u - x0; wy = v - y0;   r = ld - bias
+ *     t(i, j) = texel in range ? (r > Z[j*W + i] ? 0.0f : 1.0f) : 1.0f            (a NaN texel is lit)
+ *     lit = (t00*(1.0f - wx) + t10*wx)*(1.0f - wy) + (t01*(1.0f - wx) + t11*wx)*wy
+ *     sh  = strength * (1.0f - lit)
+ *     sh == 0: the colour word stays as it is.  Otherwise per channel  c' = c*(1.0f - sh) + shade_c*sh
+ * Pixel centres sit at integers: pixel x of the orthographic frame that produced the map is u = x.  The 2 x 2 compare is the usual
+ * percentage-closer filter: a shadow's edge is a ramp one texel wide.
+ * Order: tile-style tint, then the shadow, then the fog.  The colour is quantised once at the end, by the fog's expression (or, with
+ * the fog off, by the same expression on the shaded floats): byte' = (uint32_t)rintf(fminf(fmaxf(c', 0), 1) * 255.0f), and the
+ * record's colour word becomes byte'_r | byte'_g << 8 | byte'_b << 16 | (word & 0xFF000000).  The debug draw modes (draw_mode != 0)
+ * keep their colours.  The shadow changes the colour word only: visibility, n_visible, pairs, axes, alpha, depth and the pick
+ * identity are those of the frame without it, the record stays 32 bytes and the compositors are untouched.
+ * gswt_debug_read_projected reports the shaded bytes, (float)byte' / 255.0f.
+ * M * c is evaluated in binary32 at the world coordinates' magnitude: far from the world origin the lookup loses the bits the
+ * coordinates have lost (at |c| = 2^17 and 1 world unit per texel, about 2^-6 texel); exactness there is out of scope.
+ *
+ * Vertex stage.  k_project gains an eighth template flag SHD on its strict instantiations; the image pointer, its size and the block
+ * are a kernel argument of their own (under GSWT_OPT_GRAPH a node argument: another map updates one node, switching shadows on or off
+ * selects another instantiation and the slot's graph is rebuilt).  The four texel loads are issued behind the frustum rejection, in
+ * front of A7 / A8, unconditionally from indices clamped into the image, and read behind A9.
+ *
+ * Proxy pass.  gswt_proxy_render and gswt_proxy_render_ortho read the map in force when they are called and apply the same function
+ * at the ray's hit point in world coordinates (the orthographic pass works in its grid frame and adds the grid's origin back):
+ *     rgb' = rgb*(1.0f - sh) + shade_color*sh        behind `brightness`, in front of the fog, alpha 1
+ * The depth they write, the pixels they leave alone and the black_background output are unchanged.
+ *
+ * Copy and lifetime.  The image is copied by the call into a buffer of the library's: one of a small pool of map versions (frame
+ * slots + 2, allocated when first used), each kept while it is the current one or a frame slot was last submitted with it.  A frame
+ * uses the version in force when it was submitted; frames in flight and a frame re-run after a pair-buffer overflow keep theirs.
+ * Setting a map waits for no frame: the copy is queued on the ctx stream (through pinned staging from a host pointer) and the frames
+ * and proxy passes submitted afterwards are ordered behind it.  The one exception: a version that meets an image larger than its buffers
+ * (they are allocated at twice the first image's size) frees and reallocates them, and freeing device memory waits for the device, frames in
+ * flight included.  A host that keeps its map's size, or halves and doubles it, never meets it after each version's first use.
+ *
+ * Refused with GSWT_ERR_BAD_ARG, the field named in gswt_last_error and the map in force unchanged: any non-finite field; a bottom
+ * row of world_to_light other than (0, 0, 0, 1); bias < 0; strength outside (0, 1]; a shade_color component outside [0, 1]; a
+ * nonzero _pad; width or height outside 1..4096.  With a map on, a submit returns GSWT_ERR_BAD_ARG before anything is enqueued when
+ * GSWT_OPT_STRICT_VS = 0 (sequence v2 has no shadowed form).
+ * Out of scope: filters wider than 2 x 2, slope-scaled bias, cascades, perspective (spot) lights, shadows on the skybox, the CPU
+ * oracle. */
+typedef struct {
+    float world_to_light[16]; /* column-major, affine: bottom row exactly (0,0,0,1).  Row 0, 1: light NDC x, y (+y up, -1..1 over the
+                                 image); row 2: depth in the depth image's convention, 0 near .. 1 far */
+    float bias;               /* >= 0, depth units */
+    float strength;           /* in (0, 1] */
+    float shade_color[3];     /* each in [0, 1]: what a fully shadowed colour goes toward at strength 1 */
+    uint32_t _pad[3];         /* zero */
+} gswt_shadow_params;         /* 96 bytes */
+GSWT_API int gswt_set_shadow_map(gswt_ctx *ctx, const gswt_shadow_params *p, const float *depth, int width, int height, int depth_on_device);
+
 /* GSWTRenderer::new (renderer.rs:31-349): uploads PreloadData.tile_splats_merged.tex_data
  * (8 u32 per splat, renderer.rs:236-248) and all static base lists (renderer.rs:290-327).
  * lists is [n_lod][n_tile][n_view] row-major. */
