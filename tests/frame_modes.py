@@ -1,5 +1,6 @@
 """What the GPU tests of the per-frame modes share (orthographic projection, the anti-aliasing filter, the atmosphere block, the
-tile-style table: tests/test_ortho_gpu.py, test_antialias_gpu.py, test_atmosphere_gpu.py, test_tile_style_gpu.py).  A mode is a
+tile-style table, the sun shadow: tests/test_ortho_gpu.py, test_antialias_gpu.py, test_atmosphere_gpu.py, test_tile_style_gpu.py,
+test_shadow_gpu.py, and all of them stacked, test_mode_stack_gpu.py).  A mode is a
 setting that a frame takes when it is submitted and keeps however it is run: the battery below renders a handful of named states of
 one mode synchronously (`plain_frames`) and wants the same bytes back through graphs, frames in flight, compositor and cull
 variants, a pair-buffer overflow, output formats and shards.  Frames are 72 x 40 (tests/ortho_ref.py) on the golden cases.
@@ -106,7 +107,8 @@ _VIEWS = {}
 
 def view(name, cam, splat_scale=OR.SPLAT_SCALE):
     """(golden case, camera block, scene block, projection, reference records WITHOUT any mode but the projection) of case `name` under
-    camera `cam`: "persp" (the oracle's vertex stage) or one of OR.CAMERAS (tests/ortho_ref.py's restatement, plane case only);
+    camera `cam`: "persp" (the oracle's vertex stage) or one of OR.CAMERAS (on the plane case tests/ortho_ref.py's restatement, on the
+    HeightMap and Sphere cases the oracle's own orthographic stage with the `visible` of its pair rectangles, the product's);
     computed once."""
     k = (name, cam, splat_scale)
     if k not in _VIEWS:
@@ -115,10 +117,16 @@ def view(name, cam, splat_scale=OR.SPLAT_SCALE):
             cu, su = persp_cam(g), OR.scene_of(g, splat_scale)
             sp = orc.project_draws(orc.Camera176.from_buffer_copy(bytes(cu)), su, g["pp"].tex, g["draws"], height_map=g["hm"])
             _VIEWS[k] = (g, cu, su, PERSP, sp)
-        else:
-            assert name == "case_plane"
+        elif name == "case_plane":
             _, su, sp = OR.plane_records(cam, splat_scale)
             _VIEWS[k] = (g, ortho_cam(cam, g).uniforms(), su, ORTHO, sp)
+        else:
+            cu, su = ortho_cam(cam, g, name).uniforms(), OR.scene_of(g, splat_scale)
+            block = orc.Camera176.from_buffer_copy(bytes(cu))
+            with orc.frame_mode(ortho=1):
+                sp = orc.project_draws(block, su, g["pp"].tex, g["draws"], height_map=g["hm"]).copy()
+                sp["visible"] = orc.pair_rects(block, su, g["pp"].tex, g["draws"], W, Hh, height_map=g["hm"])["visible"]
+            _VIEWS[k] = (g, cu, su, ORTHO, sp)
     return _VIEWS[k]
 
 
@@ -378,13 +386,14 @@ def check_v2_refused_at_submit(renderer, s, mode, names, needles, off="off"):
     assert rendered(cam, sc, cfg)
 
 
-def image_case(renderer, cam, order_mode, bg, splat_scale, mode_kw, label, min_cover=0.3):
-    """Image, depth and pick of the plane case under `cam` and the mode keywords against tests/depth_ref.py and tests/pick_ref.py over
-    the GPU's own projected records; the context keeps the mode from the debug-varyings frame on.  Returns what the caller's own
-    checks need: timings `t`, the frame's `img` and `pick`, and `again(**kw)`, the same view and background rendered once more."""
-    g, cu, su, proj, _ = view("case_plane", cam, splat_scale)
+def image_case(renderer, cam, order_mode, bg, splat_scale, mode_kw, label, min_cover=0.3, name="case_plane"):
+    """Image, depth and pick of case `name` (the plane case unless said otherwise) under `cam` and the mode keywords against
+    tests/depth_ref.py and tests/pick_ref.py over the GPU's own projected records; the context keeps the mode from the debug-varyings
+    frame on.  Returns what the caller's own checks need: timings `t`, the frame's `img` and `pick`, `again(**kw)`, the same view and
+    background rendered once more, and the debug-varyings frame's records `sp` and timings `t_debug`."""
+    g, cu, su, proj, _ = view(name, cam, splat_scale)
     bind(renderer, g)
-    sp, _ = varyings(renderer, cu, su, projection=proj, **mode_kw)
+    sp, t_debug = varyings(renderer, cu, su, projection=proj, **mode_kw)
     bgc, bgd = DR.bg_images(W, Hh) if bg else (None, None)
     kw = dict(order_mode=order_mode, bg_rgba=bgc, bg_depth=bgd)
     again = lambda **more: renderer.render(cu, su, W, Hh, projection=proj, **kw, **more)
@@ -401,4 +410,4 @@ def image_case(renderer, cam, order_mode, bg, splat_scale, mode_kw, label, min_c
     print(f"{label}: visible {t['n_visible']} pairs {t['n_pairs']} max|dz| {dz:.3e} max|dw| {dw:.3e}")
     assert t["n_visible"] == int((sp["visible"] == 1).sum())
     assert same(img, again())                                   # colour is what a frame without the other outputs writes, twice the same
-    return dict(t=t, img=img, pick=pick, again=again)
+    return dict(t=t, img=img, pick=pick, again=again, sp=sp, t_debug=t_debug)

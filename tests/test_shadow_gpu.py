@@ -426,11 +426,12 @@ def test_refused_maps_leave_the_map_in_force(renderer, plain):
 PROXY_SHADE = dict(bias=0.0, strength=0.8, shade_color=(0.05, 0.1, 0.3))
 
 
-def _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, shadow, projection=PERSP):
+def _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, shadow, projection=PERSP, atm=A.OFF):
     import torch
     renderer.configure(hm)
     renderer.proxy_configure(mips, grid_dim=grid_dim)
     renderer.set_shadow_map(shadow)
+    renderer.set_atmosphere(atm)
     rgba = torch.from_numpy(R.sky(Wp, Hp)).cuda()
     depth = torch.zeros((Hp, Wp), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
@@ -440,11 +441,9 @@ def _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, shadow, projection=PERSP):
     return depth.cpu().numpy(), rgba.cpu().numpy()
 
 
-def _proxy_case(renderer, name, us, cam_block, grid_dim, hm, mips, projection, delta_of):
-    """The pass without a map, then with a two-region map of a top-down light over the middle of what the pass drew: depth and unwritten
-    pixels byte for byte, shaded pixels against the float64 lookup at the float64 unprojection of the proxy's own depth."""
-    Wp, Hp = R.W0, R.H0
-    d0, c0 = _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, shadows.OFF, projection)
+def _proxy_points_and_map(d0, cam_block, Wp, Hp):
+    """(written pixels, their float64 unprojection pos and view depth z, a two-region map of a top-down light over the middle of what
+    the pass drew) of the plain pass's depth image d0."""
     written = d0 < 1.0
     assert written.mean() > 0.05
     ys, xs = np.nonzero(written)
@@ -453,7 +452,15 @@ def _proxy_case(renderer, name, us, cam_block, grid_dim, hm, mips, projection, d
     lo, hi = np.percentile(pos, 10, axis=0), np.percentile(pos, 90, axis=0)
     light = ortho.top_down(((lo[0] + hi[0]) / 2, (lo[1] + hi[1]) / 2), max(hi[1] - lo[1], (hi[0] - lo[0]) * 24 / 32) / 2,
                            float(pos[:, 2].max()) + 5.0, float(pos[:, 2].min()) - 5.0, 32, 24)
-    m = shadows.from_ortho_camera(light, SR.two_region_map(32, 24), **PROXY_SHADE)
+    return written, pos, z, shadows.from_ortho_camera(light, SR.two_region_map(32, 24), **PROXY_SHADE)
+
+
+def _proxy_case(renderer, name, us, cam_block, grid_dim, hm, mips, projection, delta_of):
+    """The pass without a map, then with a two-region map of a top-down light over the middle of what the pass drew: depth and unwritten
+    pixels byte for byte, shaded pixels against the float64 lookup at the float64 unprojection of the proxy's own depth."""
+    Wp, Hp = R.W0, R.H0
+    d0, c0 = _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, shadows.OFF, projection)
+    written, pos, z, m = _proxy_points_and_map(d0, cam_block, Wp, Hp)
     p = SR.params(m)
     d1, c1 = _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, m, projection)
     sky = R.sky(Wp, Hp)
@@ -476,23 +483,79 @@ def _proxy_case(renderer, name, us, cam_block, grid_dim, hm, mips, projection, d
     assert FM.same(c1[written][sh == 0], c0[written][sh == 0])
 
 
-@pytest.mark.parametrize("name", ["oblique", "flat_two_draws", "clip_two_draws", "black_background"])
-def test_proxy_is_shaded(renderer, name):
+def _persp_scene(name):
+    """What _proxy_case takes of the perspective scene `name` (tests/proxy_raster_ref.py) behind the test's own name."""
     cam_kw, draws, grid_dim, _ = R.SCENES[name]
     cam = R.scene_camera(cam_kw, R.W0, R.H0)
     cu = cam.uniforms()
     near = AR.near_of(cu)
     # (the kernel's own hit point o + t d, rounded at the world coordinates' magnitude, on top of the depth's share)
-    _proxy_case(renderer, name, R.scene_uniforms(cam, draws), cu, grid_dim, R.height_map(), R.mip_chain(), PERSP,
-                lambda pos, z: SR.persp_delta(z, near) + 8.0 * SR.U * np.abs(pos).max(1))
+    return (R.scene_uniforms(cam, draws), cu, grid_dim, R.height_map(), R.mip_chain(), PERSP,
+            lambda pos, z: SR.persp_delta(z, near) + 8.0 * SR.U * np.abs(pos).max(1))
+
+
+def _ortho_scene(name):
+    spec, draws, grid_dim, hm_n, _ = O.SCENES[name]
+    cam = O.make_camera(spec, R.W0, R.H0)
+    span = 2.0 / abs(float(cam.projection[10]))                      # far - near: the depth image's binary32 rounding times it, along the rays
+    return (O.scene_uniforms(cam, draws), cam.uniforms(), grid_dim, R.height_map(n=hm_n), R.mip_chain(), ORTHO,
+            lambda pos, z: AR.DEPTH_ROUNDINGS * SR.U * (span + np.abs(pos).max(1)))
+
+
+@pytest.mark.parametrize("name", ["oblique", "flat_two_draws", "clip_two_draws", "black_background"])
+def test_proxy_is_shaded(renderer, name):
+    _proxy_case(renderer, name, *_persp_scene(name))
 
 
 def test_orthographic_proxy_is_shaded(renderer):
-    spec, draws, grid_dim, hm_n, _ = O.SCENES["isometric"]
-    cam = O.make_camera(spec, R.W0, R.H0)
-    span = 2.0 / abs(float(cam.projection[10]))                      # far - near: the depth image's binary32 rounding times it, along the rays
-    _proxy_case(renderer, "isometric (orthographic)", O.scene_uniforms(cam, draws), cam.uniforms(), grid_dim, R.height_map(n=hm_n), R.mip_chain(), ORTHO,
-                lambda pos, z: AR.DEPTH_ROUNDINGS * SR.U * (span + np.abs(pos).max(1)))
+    _proxy_case(renderer, "isometric (orthographic)", *_ortho_scene("isometric"))
+
+
+# k_proxy<FOG = true, ., SHD = true>: the shadow, then the fog (the fogs of the two passes' own fog tests)
+PROXY_FOGS = {"oblique": (_persp_scene, (0.15, 2.0, 0.9, (0.62, 0.71, 0.80))), "isometric": (_ortho_scene, (0.03, 5.0, 0.9, (0.6, 0.7, 0.8)))}
+
+
+@pytest.mark.parametrize("name", list(PROXY_FOGS))
+def test_proxy_is_shaded_then_fogged(renderer, name):
+    """Both on: depth and unwritten pixels are the plain pass's byte for byte; a written pixel is (c0 (1 - sh) + shade sh) (1 - F) + fog F
+    in float64, c0 the plain pass's own pixel, sh and F at the float64 unprojection of the proxy's depth.  The tolerance is the shaded
+    pass's 2e-6 + tol_sh plus a fog term built the same way: |dc / dF| <= 1, |dF / d dist| <= fog_max density and the hit point is off by
+    at most the same delta, so fog_max density delta."""
+    scene, fog = PROXY_FOGS[name]
+    us, cam_block, grid_dim, hm, mips, projection, delta_of = scene(name)
+    Wp, Hp = R.W0, R.H0
+    atm = A.Atmosphere(fog=fog)
+    fp = AR.params(atm)
+    d0, c0 = _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, shadows.OFF, projection)
+    written, pos, z, m = _proxy_points_and_map(d0, cam_block, Wp, Hp)
+    p = SR.params(m)
+    d1, c1 = _proxy(renderer, us, Wp, Hp, grid_dim, hm, mips, m, projection, atm)
+    sky = R.sky(Wp, Hp)
+    assert FM.same(d0, d1) and FM.same(c1[~written], sky[~written]) and FM.same(c0[~written], sky[~written])
+    sh, _, _, (_, _, ld) = SR.lookup_f64([pos[:, 0], pos[:, 1], pos[:, 2]], p)
+    delta = delta_of(pos, z)
+    tol_sh, tol_ld = SR.surface_tols(pos, delta, p)
+    assert not ((np.abs(ld) <= tol_ld) | (np.abs(ld - 1.0) <= tol_ld)).any()
+    cp = np.array([float(_block(cam_block).cam_pos[k]) for k in range(3)])
+    F = AR.fog_amount_f64(np.sqrt(((pos - cp) ** 2).sum(1)), fp)[:, None]
+    base = c0[written][:, :3].astype(np.float64)
+    shade, fogc, s = p["shade"].astype(np.float64)[None], fp["fog_color"].astype(np.float64)[None], sh[:, None]
+    want = (base * (1.0 - s) + shade * s) * (1.0 - F) + fogc * F
+    have = c1[written][:, :3].astype(np.float64)
+    err = np.abs(have - want).max(1)
+    tol = 2e-6 + tol_sh + float(fp["fog_max"]) * float(fp["fog_density"]) * delta
+    lit, dark, between = SR.shares(sh, p)
+    print(f"{name}: {int(written.sum())} proxy pixels, lit {lit:.3f} shadowed {dark:.3f} between {between:.3f}, F {F.min():.3f} .. {F.max():.3f}, "
+          f"max |colour error| / tolerance {np.max(err / tol):.3f}, largest tolerance {tol.max():.2e}")
+    assert (err <= tol).all()
+    assert (c1[written][:, 3] == 1.0).all()
+    assert lit > 0.1 and dark > 0.1 and F.max() > 0.1
+    # the order shows: the shadow behind the fog would be another colour on a good share of the shaded pixels
+    wrong = (base * (1.0 - F) + fogc * F) * (1.0 - s) + shade * s
+    shaded = sh > 0
+    other = (np.abs(wrong - want).max(1) > tol)[shaded].mean()
+    print(f"{name}: the shadow behind the fog differs beyond the tolerance on {other:.3f} of the {int(shaded.sum())} shaded pixels")
+    assert other >= 0.1
 
 
 # ---- 10. through the frame harness ---------------------------------------------------------------------------------------------------------
