@@ -237,6 +237,7 @@ SYMBOLS = {
     "gswt_proxy_download": (C.c_int, [_P, _P]),
     "gswt_proxy_render": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
     "gswt_proxy_render_ortho": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int]),
+    "gswt_proxy_render_sphere": (C.c_int, [_P, _P, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int]),
     "gswt_shard_rows": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "gswt_shard_rows_padded": (C.c_int, [C.c_int, C.c_int]),
     "gswt_unshard": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),

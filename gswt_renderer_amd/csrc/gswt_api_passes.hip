@@ -226,29 +226,29 @@ try {
     return GSWT_OK;
 } GSWT_CATCH
 
-// The orthographic form (include/gswt_hip.h, "orthographic proxy pass"): the same block under an affine projection, k_proxy<., ORTHO>.
-int gswt_proxy_render_ortho(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, float* rgba_dev, float* depth_dev, int clear_depth)
-try {
-    if (!c) return GSWT_ERR_BAD_ARG;
-    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: bad argument");
-    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_ortho before gswt_proxy_configure");
-    if (u->surface_type == 1u && (c->hm_w == 0 || c->hm_h == 0)) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_ortho: HeightMap surface without gswt_configure height map");
-    if (!(u->tile_width > 0.0f) || (!u->map_proxy && !(u->width_scale > 0.0f))) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: tile_width / width_scale: cell size must be positive");
+// The checks gswt_proxy_render_ortho makes on the block's projection (fn: the entry point the refusal names); GSWT_OK or the refusal.
+static int ortho_projection_check(gswt_ctx* c, const gswt_proxy_uniforms* u, const char* fn)
+{
     const float* P = u->projection;
     if (!(P[3] == 0.0f && P[7] == 0.0f && P[11] == 0.0f && P[15] == 1.0f))
-        return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: projection must be affine, bottom row (0, 0, 0, 1), not (%g, %g, %g, %g)", P[3], P[7], P[11], P[15]);
+        return fail(c, GSWT_ERR_BAD_ARG, "%s: projection must be affine, bottom row (0, 0, 0, 1), not (%g, %g, %g, %g)", fn, P[3], P[7], P[11], P[15]);
     for (int k : {1, 2, 4, 6, 8, 9})
-        if (!(P[k] == 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: projection[%d] = %g: not of ortho() form (no shear or rotation)", k, P[k]);
+        if (!(P[k] == 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "%s: projection[%d] = %g: not of ortho() form (no shear or rotation)", fn, k, P[k]);
     for (int k : {0, 5, 10})
-        if (!std::isfinite(P[k]) || P[k] == 0.0f) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: projection[%d] = %g: singular projection", k, P[k]);
+        if (!std::isfinite(P[k]) || P[k] == 0.0f) return fail(c, GSWT_ERR_BAD_ARG, "%s: projection[%d] = %g: singular projection", fn, k, P[k]);
     for (int k : {12, 13, 14})
-        if (!std::isfinite(P[k])) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: projection[%d] = %g is not finite", k, P[k]);
-    ProxyArgs a;
-    proxy_args(c, u, width, height, a);
-    // The rays run the way depth grows (depth = GP[10] z + GP[14]: along -z of the camera for an ortho() matrix with near < far, sz = -1) and
-    // start at z0, an eighth of the depth range before the depth-0 plane.  The kernel works in the grid frame, world - g, g = (gx0, gy0, 0):
-    // ortho_o = R^-1 ((0, 0, z0) - t) - g, the view's translation becomes t + R g, cam_pos becomes cam_pos - g, and the texture coordinate the
-    // frame lacks, g / tile_width / 4, is reduced to its fraction (Repeat addressing).  Binary64, each rounded once.
+        if (!std::isfinite(P[k])) return fail(c, GSWT_ERR_BAD_ARG, "%s: projection[%d] = %g is not finite", fn, k, P[k]);
+    return GSWT_OK;
+}
+
+// The orthographic pass's host set-up in the frame world - g (g[2] = 0): a.ortho_*, and a.V[12..14] / a.cam moved into that frame.
+// The rays run the way depth grows (depth = GP[10] z + GP[14]: along -z of the camera for an ortho() matrix with near < far, sz = -1) and
+// start at z0, an eighth of the depth range before the depth-0 plane.  ortho_o = R^-1 ((0, 0, z0) - t) - g, the view's translation becomes
+// t + R g, cam_pos becomes cam_pos - g, and the texture coordinate the frame lacks, g / tile_width / 4, is reduced to its fraction (Repeat
+// addressing).  Binary64, each rounded once.
+static int ortho_frame(gswt_ctx* c, const gswt_proxy_uniforms* u, ProxyArgs& a, const double g[3], const char* fn)
+{
+    const float* P = u->projection;
     const double g10 = a.GP[10], g14 = a.GP[14];
     const double zn = (0.0 - g14) / g10, zf = (1.0 - g14) / g10;
     const float sz = g10 < 0.0 ? -1.0f : 1.0f;
@@ -260,11 +260,10 @@ try {
                              {r[0][2] * r[2][1] - r[0][1] * r[2][2], r[0][0] * r[2][2] - r[0][2] * r[2][0], r[0][1] * r[2][0] - r[0][0] * r[2][1]},
                              {r[0][1] * r[1][2] - r[0][2] * r[1][1], r[0][2] * r[1][0] - r[0][0] * r[1][2], r[0][0] * r[1][1] - r[0][1] * r[1][0]}};
     const double det = r[0][0] * co[0][0] + r[0][1] * co[0][1] + r[0][2] * co[0][2];
-    const double g[3] = {a.gx0, a.gy0, 0.0};
     for (int k = 0; k < 3; k++) {             // R^-1 = cofactor^T / det
         const double w = (co[0][k] * b[0] + co[1][k] * b[1] + co[2][k] * b[2]) / det;
         a.ortho_o[k] = (float)(w - g[k]);
-        if (!std::isfinite(a.ortho_o[k])) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: view is singular or not finite");
+        if (!std::isfinite(a.ortho_o[k])) return fail(c, GSWT_ERR_BAD_ARG, "%s: view is singular or not finite", fn);
         a.V[12 + k] = (float)((double)V[12 + k] + (r[k][0] * g[0] + r[k][1] * g[1]));
         a.cam[k] = (float)((double)u->cam_pos[k] - g[k]);
     }
@@ -274,9 +273,67 @@ try {
     }
     a.ortho_t[0] = P[12]; a.ortho_t[1] = P[13];
     a.ortho_d[0] = sz * V[2]; a.ortho_d[1] = sz * V[6]; a.ortho_d[2] = sz * V[10];
+    return GSWT_OK;
+}
+
+// The orthographic form (include/gswt_hip.h, "orthographic proxy pass"): the same block under an affine projection, k_proxy<., ORTHO>, in the
+// grid frame g = (gx0, gy0, 0).
+int gswt_proxy_render_ortho(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, float* rgba_dev, float* depth_dev, int clear_depth)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: bad argument");
+    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_ortho before gswt_proxy_configure");
+    if (u->surface_type == 1u && (c->hm_w == 0 || c->hm_h == 0)) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_ortho: HeightMap surface without gswt_configure height map");
+    if (!(u->tile_width > 0.0f) || (!u->map_proxy && !(u->width_scale > 0.0f))) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: tile_width / width_scale: cell size must be positive");
+    if (int e = ortho_projection_check(c, u, "gswt_proxy_render_ortho")) return e;
+    ProxyArgs a;
+    proxy_args(c, u, width, height, a);
+    const double g[3] = {a.gx0, a.gy0, 0.0};
+    if (int e = ortho_frame(c, u, a, g, "gswt_proxy_render_ortho")) return e;
     hipSetDevice(c->device);
     if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
     launch_proxy_ortho(c->stream, a, shadow_version(c, c->shd_cur), c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
+    HIP_TRY(c, hipGetLastError());
+    return GSWT_OK;
+} GSWT_CATCH
+
+// The ground under the Sphere surface (include/gswt_hip.h, "sphere proxy pass"): k_proxy_sphere, an entry point of its own -- gswt_proxy_render
+// and gswt_proxy_render_ortho with surface_type == 2 keep drawing the plane.  The sphere is centred at the world origin, so the orthographic
+// set-up runs with g = 0.
+int gswt_proxy_render_sphere(gswt_ctx* c, const gswt_proxy_uniforms* u, float sphere_radius, int projection, int width, int height, float* rgba_dev,
+                             float* depth_dev, int clear_depth)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: bad argument");
+    if (projection != 0 && projection != 1) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: projection %d is neither 0 (perspective) nor 1 (orthographic)", projection);
+    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_sphere before gswt_proxy_configure");
+    if (!(u->tile_width > 0.0f) || !std::isfinite(u->tile_width)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: tile_width must be positive and finite");
+    if (!std::isfinite(sphere_radius) || !(sphere_radius > 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: sphere_radius %g must be positive and finite", sphere_radius);
+    const float r = sphere_radius + u->height_offset;
+    if (!std::isfinite(r) || !(r > 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: sphere_radius + height_offset = %g must be positive and finite", r);
+    if (u->map_half_wh[0] == 0u) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: map_half_wh[0] is 0: the unfolding has no width");
+    if (projection == 0) {
+        if (u->projection[0] == 0.0f || u->projection[5] == 0.0f) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: singular projection");
+    } else if (int e = ortho_projection_check(c, u, "gswt_proxy_render_sphere")) return e;
+    // the block with the grid the pass never reads pinned to the map grid (no division by width_scale, whatever the caller left there)
+    gswt_proxy_uniforms v = *u;
+    v.map_proxy = 1u;
+    ProxyArgs a;
+    proxy_args(c, &v, width, height, a);
+    if (projection == 1) {
+        const double g[3] = {0.0, 0.0, 0.0};
+        if (int e = ortho_frame(c, u, a, g, "gswt_proxy_render_sphere")) return e;
+    }
+    const float PI = 3.14159265358979323846f;
+    SphereProxyArgs sp;
+    sp.r = r; sp.sphere_radius = sphere_radius;
+    sp.block_w = (2.0f * (float)u->map_half_wh[0] * u->tile_width) / 5.0f;
+    sp.org[0] = (float)((long)u->center_coord[0] - (long)u->map_half_wh[0]) * u->tile_width;
+    sp.org[1] = (float)((long)u->center_coord[1] - (long)u->map_half_wh[1]) * u->tile_width;
+    sp.lod_k = ((float)u->map_half_wh[0] * (float)a.tex_size) / ((4.0f * PI) * r);
+    hipSetDevice(c->device);
+    if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
+    launch_proxy_sphere(c->stream, a, sp, projection == 1, shadow_version(c, c->shd_cur), c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
     HIP_TRY(c, hipGetLastError());
     return GSWT_OK;
 } GSWT_CATCH

@@ -238,6 +238,16 @@ struct ProxyArgs {
     float ortho_uv0[2];            // frac((gx0, gy0) / tile_width / 4): what the grid frame's uv lacks, up to whole texture periods
 };
 
+// gswt_proxy_render_sphere only (k_proxy_sphere, beside a ProxyArgs whose grid fields it does not read; the orthographic form runs with
+// g = 0: the sphere is centred at the world origin, the rays are of the planet's size there)
+struct SphereProxyArgs {
+    float r;                       // sphere_radius + height_offset: the ground sphere
+    float sphere_radius;           // the splats' sphere: mapped_z = (hit.z / r) * sphere_radius is what use_clip tests
+    float block_w;                 // (2 half_w tile_width) / 5
+    float org[2];                  // (center_coord - half) tile_width: the plane origin map_sphere_surface subtracts
+    float lod_k;                   // half_w tex_size / (4 PI r): texels per world unit at the equator
+};
+
 // ---- hipGraph replay of a frame's launch sequence (GSWT_OPT_GRAPH) -------------------------------------------------------------
 // The frame is a fixed chain of kernel launches whose grids follow capacities; what changes from frame to frame is a handful of
 // kernel arguments (the camera block, the output pointer).  With a recorder set, the launch sites of the frame path do not
@@ -418,6 +428,9 @@ void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi,
 // (shd.z set: the pass shades the ground by gswt_set_shadow_map's image, k_proxy<., ., SHD>)
 void launch_proxy(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth);
 void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth);
+// gswt_proxy_render_sphere: ortho != 0 reads a's ortho_* fields (set up with g = 0)
+void launch_proxy_sphere(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, bool ortho, const Shadow& shd, const float4* tex, float4* rgba,
+                         float* depth);
 // One level of the proxy mip build into dst (n x n float4).  src: the staged source, a.pitch bytes per row.  ranges: 2 n int2,
 // wv / wh: the tap weights, tmp: the intermediate, part: the partial sums (sizes: proxy_mip_* above; unused on a copy level).
 void launch_proxy_mip(hipStream_t s, const ProxyMipArgs& a, const uint8_t* src, int2* ranges, float* wv, float* wh, float4* tmp,

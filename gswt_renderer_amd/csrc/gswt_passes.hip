@@ -13,6 +13,9 @@
 //              right / lower pixel on the fragment's plane.  The height map is read through sample_height, the splat path's
 //              sampler (gswt_device_fn.h: one definition, the padded buffer of gswt_configure); the repeat wraps of the proxy
 //              texture and of the panorama are its wrap_repeat.
+//   k_proxy_sphere : gswt_proxy_render_sphere (no counterpart in the reference, whose proxy draws the plane under every surface): the
+//              ground of the Sphere surface, the pixel's ray against the sphere about the world origin, textured through the inverse of
+//              the sphere unfolding (host/gswt_surface.h: sphere_plane_pos)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (same flags as gswt_kernels.hip).
 #include "gswt_device_fn.h"
@@ -313,6 +316,119 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
         px.z = px.z * (1.0f - F) + a.atm.fog_color[2] * F;
     }
     rgba[pi] = px;
+}
+
+// ---- sphere proxy ------------------------------------------------------------------------------------
+// gswt_proxy_render_sphere (include/gswt_hip.h, "sphere proxy pass"): the ground under the Sphere surface.  The pixel's ray against the
+// sphere |x| = r about the world origin, r = sphere_radius + height_offset; no grid, no walk: one pixel per lane, two candidate roots.
+// The ray's closest point c to the centre comes first and the half chord from r r - c.c, so that a grazing ray cancels at the size of
+// r^2 and not of |o|^2.  clamp: a neighbour ray of the LOD differences that misses at the silhouette takes its closest point.
+__device__ __forceinline__ bool sphere_cut(const float o[3], const float d[3], float r, bool clamp, float& tc, float& h, float& dd)
+{
+    dd = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+    tc = -((o[0] * d[0] + o[1] * d[1]) + o[2] * d[2]) / dd;
+    const float c[3] = {o[0] + tc * d[0], o[1] + tc * d[1], o[2] + tc * d[2]};
+    float disc = r * r - ((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+    if (disc < 0.0f) {
+        if (!clamp) return false;
+        disc = 0.0f;
+    }
+    h = sqrtf(disc / dd);
+    return true;
+}
+
+// the neighbour pixel's ray cut with the same sphere at the same root (second: tc + h), and its distance from the pixel's own hit
+__device__ __forceinline__ float sphere_neighbour_dist(const float o[3], const float d[3], float r, bool second, const float hit[3])
+{
+    float tc, h, dd;
+    sphere_cut(o, d, r, true, tc, h, dd);
+    const float t = second ? tc + h : tc - h;
+    const float ex = (o[0] + t * d[0]) - hit[0], ey = (o[1] + t * d[1]) - hit[1], ez = (o[2] + t * d[2]) - hit[2];
+    return sqrtf((ex * ex + ey * ey) + ez * ez);
+}
+
+// FOG / ORTHO / SHD as k_proxy's; the ORTHO host set-up runs with g = 0, so origin, a.cam, the view's translation and the hit are in world
+// coordinates.  The grid fields of a (nx, ny, cs, gx0, gy0), map_proxy, width_scale, surface_type and the height map are not read.
+// Every store goes to pixel (x, y) of the frame, inside width x height by the first test; the texture reads are proxy_tex_bilinear's wrapped
+// indices at levels clamped to [0, n_mips - 1].
+template <bool FOG, bool ORTHO, bool SHD>
+__global__ __launch_bounds__(256) void k_proxy_sphere(const ProxyArgs a, const SphereProxyArgs sp, const float4* __restrict__ tex,
+                                                      float4* __restrict__ rgba, float* __restrict__ depth_buf, const Shadow shd)
+{
+    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= a.width || y >= a.height) return;
+    float o[3] = {a.cam[0], a.cam[1], a.cam[2]};
+    float d[3];
+    if (ORTHO) {
+        ortho_origin(a, x, y, o);
+        d[0] = a.ortho_d[0]; d[1] = a.ortho_d[1]; d[2] = a.ortho_d[2];
+    } else
+        pixel_ray(a.V, a.p00, a.p11, x, y, a.width, a.height, d);
+    float tc, h, dd;
+    if (!sphere_cut(o, d, sp.r, false, tc, h, dd)) return;
+    bool hit = false, second = false;
+    float t = 0.0f, dep = 1.0f, hp[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < 2 && !hit; k++) {                        // t1 = tc - h, then t2 = tc + h: the first kept candidate is the fragment
+        const float tk = k == 0 ? tc - h : tc + h;
+        const float p[3] = {o[0] + tk * d[0], o[1] + tk * d[1], o[2] + tk * d[2]};
+        float dz;
+        if (!(tk > 0.0f) || !proxy_depth(a, p, dz)) continue;
+        if (a.use_clip == 1u && (p[2] / sp.r) * sp.sphere_radius < a.clip_height) continue;
+        hit = true; second = k == 1; t = tk; dep = dz;
+        hp[0] = p[0]; hp[1] = p[1]; hp[2] = p[2];
+    }
+    const size_t pi = (size_t)y * a.width + x;
+    if (!hit || !(dep < depth_buf[pi])) return;                  // CompareFunction::Less, depth write on
+    depth_buf[pi] = dep;
+    if (a.black_background == 1u) { rgba[pi] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
+    ShadowTap tap = {};
+    if (SHD) tap = shadow_fetch(shd, hp[0], hp[1], hp[2]);
+    float px, py;
+    gswt_host::sphere_plane_pos(sp.block_w, gswt_host::V3{hp[0] / sp.r, hp[1] / sp.r, hp[2] / sp.r}, px, py);
+    float uv[2] = {(sp.org[0] + px) / a.tile_width / 4.0f, (sp.org[1] + py) / a.tile_width / 4.0f};
+    if (!(fabsf(uv[0]) < 3.0e38f)) uv[0] = 0.0f;                 // (a finite hit gives finite coordinates; nothing else reaches the sampler)
+    if (!(fabsf(uv[1]) < 3.0e38f)) uv[1] = 0.0f;
+    // LOD from the world distance to the neighbour pixels' hits: free of the unfolding's seams and of the pinch at the poles
+    float ex, ey;
+    {
+        float on[3] = {o[0], o[1], o[2]}, dn[3] = {d[0], d[1], d[2]};
+        if (ORTHO) ortho_origin(a, x + 1, y, on); else pixel_ray(a.V, a.p00, a.p11, x + 1, y, a.width, a.height, dn);
+        ex = sphere_neighbour_dist(on, dn, sp.r, second, hp);
+        if (ORTHO) ortho_origin(a, x, y + 1, on); else pixel_ray(a.V, a.p00, a.p11, x, y + 1, a.width, a.height, dn);
+        ey = sphere_neighbour_dist(on, dn, sp.r, second, hp);
+    }
+    const float rho = fmaxf(ex, ey) * sp.lod_k;
+    float lod = log2f(rho);
+    if (!(lod > 0.0f)) lod = 0.0f;
+    if (lod > (float)(a.n_mips - 1)) lod = (float)(a.n_mips - 1);
+    const int l0 = (int)floorf(lod), l1 = l0 + 1 > a.n_mips - 1 ? a.n_mips - 1 : l0 + 1;
+    const float fl = lod - (float)l0;
+    float c0[3], c1[3];
+    proxy_tex_bilinear(tex + a.mip_off[l0], a.tex_size >> l0, uv[0], uv[1], c0);
+    proxy_tex_bilinear(tex + a.mip_off[l1], a.tex_size >> l1, uv[0], uv[1], c1);
+    float4 out = make_float4((c0[0] * (1.0f - fl) + c1[0] * fl) * a.brightness, (c0[1] * (1.0f - fl) + c1[1] * fl) * a.brightness,
+                             (c0[2] * (1.0f - fl) + c1[2] * fl) * a.brightness, 1.0f);
+    if (SHD) {
+        const float sh = shadow_amount(shd, tap);
+        if (sh != 0.0f) {
+            out.x = out.x * (1.0f - sh) + shd.shade[0] * sh;
+            out.y = out.y * (1.0f - sh) + shd.shade[1] * sh;
+            out.z = out.z * (1.0f - sh) + shd.shade[2] * sh;
+        }
+    }
+    if (FOG) {
+        float dist;
+        if (ORTHO) {
+            const float fx = hp[0] - a.cam[0], fy = hp[1] - a.cam[1], fz = hp[2] - a.cam[2];
+            dist = sqrtf((fx * fx + fy * fy) + fz * fz);
+        } else
+            dist = t * sqrtf(dd);
+        const float F = fog_amount(a.atm, dist);
+        out.x = out.x * (1.0f - F) + a.atm.fog_color[0] * F;
+        out.y = out.y * (1.0f - F) + a.atm.fog_color[1] * F;
+        out.z = out.z * (1.0f - F) + a.atm.fog_color[2] * F;
+    }
+    rgba[pi] = out;
 }
 
 // ---- skybox bake -----------------------------------------------------------------------------------
@@ -620,6 +736,25 @@ void launch_proxy(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const fl
 void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth)
 {
     launch_proxy_variant<true>(s, a, shd, hm, tex, rgba, depth);
+}
+
+template <bool ORTHO>
+static void launch_proxy_sphere_variant(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, const Shadow& shd, const float4* tex,
+                                        float4* rgba, float* depth)
+{
+    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+    const bool fog = a.atm.fog_density > 0.0f, shade = shd.z != nullptr;
+    if (fog && shade) hipLaunchKernelGGL((k_proxy_sphere<true, ORTHO, true>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
+    else if (fog) hipLaunchKernelGGL((k_proxy_sphere<true, ORTHO, false>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
+    else if (shade) hipLaunchKernelGGL((k_proxy_sphere<false, ORTHO, true>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
+    else hipLaunchKernelGGL((k_proxy_sphere<false, ORTHO, false>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
+}
+
+void launch_proxy_sphere(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, bool ortho, const Shadow& shd, const float4* tex,
+                         float4* rgba, float* depth)
+{
+    if (ortho) launch_proxy_sphere_variant<true>(s, a, sp, shd, tex, rgba, depth);
+    else launch_proxy_sphere_variant<false>(s, a, sp, shd, tex, rgba, depth);
 }
 
 }  // namespace gswt

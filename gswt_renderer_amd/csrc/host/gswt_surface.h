@@ -108,6 +108,55 @@ GSWT_HD inline V3 sphere_point(float block_w, float bidx, float bidy, float bx, 
     return V3{cv * cu, cv * su, sv};
 }
 
+// The inverse of sphere_point (include/gswt_hip.h, "sphere proxy pass"; k_proxy_sphere textures the planet through it): a unit direction n ->
+// the plane position relative to the unfolding's origin, px = bidx block_w + bx and py = bidy block_w + by, of the point sphere_point sends
+// to n.  v in [0, 1] runs south pole -> north pole, u in [0, 1) is the longitude in turns; the bands v < 1/3 (south caps), 1/3 <= v < 2/3 (the
+// two mid bands, split by the blocks' diagonal f = 1 - w) and v >= 2/3 (north caps) undo sphere_point's four branches.  One binary32
+// operation per written operator; atan2 is the platform's (atan2f on the device, within 2 ulp).  A modulus that rounds up
+// to 5 wraps to 0: the same meridian.
+GSWT_HD inline float sphere_mod5(float x)
+{
+    const float t = x - 5.0f * std::floor(x / 5.0f);
+    return (t >= 5.0f || t < 0.0f) ? 0.0f : t;
+}
+GSWT_HD inline void sphere_plane_pos(float block_w, V3 n, float& px, float& py)
+{
+    const float PI = 3.14159265358979323846f;
+    // the latitude as atan2(z, |xy|), not asin(z): asin loses half the digits at the poles (d asin / dz = 1 / |xy|), and a binary32 hit
+    // point next to a pole then lands texels away
+    const float v = std::atan2(n.z, std::sqrt(n.x * n.x + n.y * n.y)) / PI + 0.5f;
+    float u = std::atan2(n.y, n.x) / (2.0f * PI);
+    u = u - std::floor(u);
+    if (u >= 1.0f) u = 0.0f;
+    float t, bx, by, bidy;
+    if (v < 1.0f / 3.0f) {
+        const float s = 3.0f * v;
+        t = sphere_mod5(5.0f * u);
+        const float bidx = std::fmin(std::floor(t), 4.0f), f = t - bidx;
+        bidy = 0.0f;
+        by = f * block_w * s;
+        bx = by + block_w * (1.0f - s);
+        px = bidx * block_w + bx;
+    } else if (v < 2.0f / 3.0f) {
+        const float w = 3.0f * v - 1.0f;
+        t = sphere_mod5(5.0f * u - 0.5f * w);
+        const float bidx = std::fmin(std::floor(t), 4.0f), f = t - bidx;
+        bx = f * block_w;
+        if (f <= 1.0f - w) { bidy = 0.0f; by = bx + w * block_w; }
+        else { bidy = 1.0f; by = bx - block_w * (1.0f - w); }
+        px = bidx * block_w + bx;
+    } else {
+        const float s = 3.0f * v - 2.0f;
+        t = sphere_mod5(5.0f * u - 0.5f);
+        const float bidx = std::fmin(std::floor(t), 4.0f), f = t - bidx;
+        bidy = 1.0f;
+        bx = f * block_w * (1.0f - s);
+        by = bx + s * block_w;
+        px = bidx * block_w + bx;
+    }
+    py = bidy * block_w + by;
+}
+
 // The shader's height-map coordinates (gswt.wgsl:565-599; k_proxy's grid and the band cull's slope bound use the same): the world
 // range the map spans along one axis, (2 map_half + 1) tiles scaled, and a world coordinate's place in it.  One rounding per operator.
 GSWT_HD inline float hm_axis_range(uint32_t map_half, float tile_width, float scale) { return (2.0f * (float)map_half + 1.0f) * tile_width * scale; }

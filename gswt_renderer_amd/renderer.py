@@ -471,6 +471,17 @@ class GSWTRenderer:
         fn = self._lib.gswt_proxy_render_ortho if projection == 1 else self._lib.gswt_proxy_render
         self._check(fn(self._h, u, width, height, C.c_void_p(rgba_device_ptr), C.c_void_p(depth_device_ptr), 1 if clear_depth else 0))
 
+    def proxy_render_sphere(self, uniforms, sphere_radius: float, width: int, height: int, rgba_device_ptr: int, depth_device_ptr: int,
+                            clear_depth: bool, projection: int = 0):
+        """The ground under the Sphere surface (gswt_proxy_render_sphere): the sphere of radius sphere_radius + height_offset about the
+        world origin, textured through the inverse of the sphere unfolding; uniforms: the 224-byte proxy block (map_proxy, width_scale,
+        surface_type and height_map_scale are not read).  projection = 1: an orthographic block, as `proxy_render(..., projection=1)`."""
+        if projection not in (0, 1):
+            raise ValueError(f"proxy_render_sphere: projection must be 0 (perspective) or 1 (orthographic), not {projection!r}")
+        u = (C.c_char * 224).from_buffer_copy(bytes(uniforms))
+        self._check(self._lib.gswt_proxy_render_sphere(self._h, u, float(sphere_radius), int(projection), width, height, C.c_void_p(rgba_device_ptr),
+                                                       C.c_void_p(depth_device_ptr), 1 if clear_depth else 0))
+
     def shard_rows_padded(self, height: int, shard_count: int) -> int:
         return int(self._lib.gswt_shard_rows_padded(height, shard_count))
 

@@ -797,6 +797,54 @@ GSWT_API int gswt_proxy_render(gswt_ctx *ctx, const gswt_proxy_uniforms *u, int 
  *   The depth written, the pixels not written and the black_background output do not depend on the fog. */
 GSWT_API int gswt_proxy_render_ortho(gswt_ctx *ctx, const gswt_proxy_uniforms *u, int width, int height, float *rgba_dev, float *depth_dev,
                                      int clear_depth);
+/* ---- sphere proxy pass: the ground under the Sphere surface (planets), with depth and sun shade ----
+ * ONE draw of the ground sphere |x| = r about the world origin, r = sphere_radius + height_offset, where WangTile::surface_mapping puts the
+ * Sphere surface: the same 224-byte block and buffers as gswt_proxy_render (colour loaded, depth tested Less and written, clear_depth != 0
+ * fills depth_dev with 1.0 first), on the ctx stream.  projection 0: perspective, the fields as in gswt_proxy_render; projection 1:
+ * orthographic, the fields and the host-side binary64 set-up of gswt_proxy_render_ortho with g = 0 (the rays are of the planet's size at the
+ * origin; cam_pos is the fog's reference point).  map_proxy, width_scale, surface_type and height_map_scale of the block are NOT read.
+ * It is an entry point of its own: gswt_proxy_render and gswt_proxy_render_ortho with surface_type == 2 keep drawing the plane
+ * z = height_offset, as the reference does, bit for bit.  Its depth image is what hides the far hemisphere's splats (bg_depth of
+ * gswt_render), what the atmosphere's far fade dissolves into, and, drawn orthographically along the sun with black_background, the
+ * occluder of a sun map (gswt_set_shadow_map): the planet shades its own night side.
+ *
+ * Returns GSWT_ERR_BAD_ARG with the reason in gswt_last_error, nothing enqueued and clear_depth not performed, for: what gswt_proxy_render
+ * refuses (null pointers, width / height <= 0, tile_width <= 0 or not finite, with projection 0 a singular projection); projection not 0 or 1;
+ * with projection 1 everything gswt_proxy_render_ortho refuses of the projection and the view; sphere_radius not finite or not positive;
+ * sphere_radius + height_offset not finite or not positive; map_half_wh[0] == 0.  GSWT_ERR_STATE without a proxy texture, unless
+ * black_background.
+ *
+ * The definition.  Every written operator is one binary32 operation, nothing fused; sqrtf, atan2f and log2f are named as such.
+ *   Ray: o = cam_pos, d = the perspective pass's pixel ray (projection 0); o, d = the orthographic pass's origin and direction (projection 1).
+ *   d is not normalised.  Dot products are (x x' + y y') + z z'.
+ *   Intersection, written so that a grazing ray does not cancel at the size of |o|^2:
+ *     dd = d.d;  tc = -(o.d) / dd;  c = o + tc d;  disc = r * r - c.c;  disc < 0: the ray misses;  h = sqrtf(disc / dd)
+ *     candidates t1 = tc - h, then t2 = tc + h; hit = o + t d per component.  A candidate is kept if t > 0, the depth test of the plane
+ *     passes accepts it (V then GP applied to hit: q.w > 0, q.z / q.w in [0, 1]) and it is not clipped: with use_clip == 1 a candidate with
+ *     (hit.z / r) * sphere_radius < clip_height is dropped -- the splats' mapped_z of the same ground point.  The first kept candidate is
+ *     the fragment: a camera inside the sphere, or a clipped cap, shows the inside of the far surface, as an unculled mesh would.
+ *   Depth: the fragment's q.z / q.w, tested Less against depth_dev, then written.  black_background == 1 writes (0, 0, 0, 1) and is done.
+ *   Texture coordinate, the inverse of the sphere unfolding (host/gswt_surface.h: sphere_plane_pos beside sphere_point):
+ *     n = hit / r;  v = atan2f(n.z, sqrtf(n.x * n.x + n.y * n.y)) / PI + 0.5f;  u = atan2f(n.y, n.x) / (2 PI), u = u - floorf(u), 1 -> 0
+ *       (v is asin(n.z) / PI + 0.5 written so that it keeps its digits at the poles: d asin / dz = 1 / |n.xy| turns the binary32 rounding of a
+ *       hit point one pixel from a pole into 1e-3 texels or more; atan2 of the two legs is conditioned like the angle itself)
+ *     bw = (2 half_w tile_width) / 5;  x mod 5 = x - 5 floorf(x / 5), a result outside [0, 5) -> 0;  bidx = min(floorf(t), 4), f = t - bidx
+ *     v < 1/3  (south caps):  s = 3 v;      t = 5 u mod 5;              bidy = 0;  by = f bw s;  bx = by + bw (1 - s)
+ *     v < 2/3  (mid bands):   w = 3 v - 1;  t = (5 u - 0.5 w) mod 5;    bx = f bw;  f <= 1 - w: bidy = 0, by = bx + w bw;
+ *                                                                                   else:       bidy = 1, by = bx - bw (1 - w)
+ *     else     (north caps):  s = 3 v - 2;  t = (5 u - 0.5) mod 5;      bidy = 1;  bx = f bw (1 - s);  by = bx + s bw
+ *     p = ((center_coord - map_half_wh) tile_width) + (bidx bw + bx, bidy bw + by)      the origin map_sphere_surface subtracts
+ *     uv = p / tile_width / 4, as in the plane pass.
+ *   Texture LOD, free of the unfolding's seams and of the pinch at the poles: the rays of pixels (x + 1, y) and (x, y + 1) are cut with the
+ *     same sphere at the same root, disc clamped at 0 (a neighbour that misses at the silhouette takes its closest point) -> hx, hy;
+ *     rho = max(|hx - hit|, |hy - hit|) * k,  k = (half_w * tex_size) / ((4 PI) * r): texels per world unit at the equator;
+ *     lod = clamp(log2f(rho), 0, n_mips - 1); trilinear Repeat taps and `brightness` as in gswt_proxy_render.
+ *   Shade and fog: gswt_set_shadow_map's lookup at the world hit point, then gswt_set_atmosphere's fog, order and formulas as in the plane
+ *     passes; dist = t * sqrtf(dd) (projection 0) or |hit - cam_pos| (projection 1).  The depth written does not depend on either.
+ * Out of scope: a height-mapped sphere (the Sphere surface has no height map); a sphere mode of the CPU oracle's proxy_render; any change to
+ * what gswt_proxy_render does with surface_type == 2; the bench workloads. */
+GSWT_API int gswt_proxy_render_sphere(gswt_ctx *ctx, const gswt_proxy_uniforms *u, float sphere_radius, int projection, int width, int height,
+                                      float *rgba_dev, float *depth_dev, int clear_depth);
 
 
 /* Number of pixel rows the shard (index, count) owns for a frame of `height` rows. */
