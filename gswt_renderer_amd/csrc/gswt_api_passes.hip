@@ -209,22 +209,31 @@ static void proxy_args(const gswt_ctx* c, const gswt_proxy_uniforms* u, int widt
     a.atm = atmo_constants(c->atm);           // the block in force now: the fog part (the fade does not apply: the proxy is what the splats fade into)
 }
 
-int gswt_proxy_render(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, float* rgba_dev, float* depth_dev, int clear_depth)
-try {
-    if (!c) return GSWT_ERR_BAD_ARG;
-    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: bad argument");
-    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render before gswt_proxy_configure");
-    if (u->surface_type == 1u && (c->hm_w == 0 || c->hm_h == 0)) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render: HeightMap surface without gswt_configure height map");
-    if (!(u->tile_width > 0.0f) || (!u->map_proxy && !(u->width_scale > 0.0f))) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: cell size must be positive");
-    if (u->projection[0] == 0.0f || u->projection[5] == 0.0f) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: singular projection");
+// What the proxy passes check in common before anything is launched or written (fn: the entry point the refusal names); GSWT_OK or the
+// refusal.  grid: the pass reads the block's grid (the plane passes), so the HeightMap surface needs its map and both cell sizes count.
+static int proxy_call_check(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, const float* rgba_dev, const float* depth_dev, bool grid,
+                            const char* fn)
+{
+    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "%s: bad argument", fn);
+    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "%s before gswt_proxy_configure", fn);
+    if (!grid) return GSWT_OK;
+    if (u->surface_type == 1u && (c->hm_w == 0 || c->hm_h == 0)) return fail(c, GSWT_ERR_STATE, "%s: HeightMap surface without gswt_configure height map", fn);
+    if (!(u->tile_width > 0.0f) || (!u->map_proxy && !(u->width_scale > 0.0f)))
+        return fail(c, GSWT_ERR_BAD_ARG, "%s: tile_width / width_scale: cell size must be positive", fn);
+    return GSWT_OK;
+}
+
+// The common end of the proxy passes: the optional depth fill, the launch (sp set: k_proxy_sphere) with the shadow map in force, its status.
+static int proxy_draw(gswt_ctx* c, const ProxyArgs& a, const SphereProxyArgs* sp, bool ortho, float* rgba_dev, float* depth_dev, int clear_depth)
+{
     hipSetDevice(c->device);
-    ProxyArgs a;
-    proxy_args(c, u, width, height, a);
-    if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
-    launch_proxy(c->stream, a, shadow_version(c, c->shd_cur), c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
+    if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)a.width * a.height, 1.0f);
+    const Shadow shd = shadow_version(c, c->shd_cur);
+    if (sp) launch_proxy_sphere(c->stream, a, *sp, ortho, shd, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
+    else launch_proxy(c->stream, a, ortho, shd, c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
     HIP_TRY(c, hipGetLastError());
     return GSWT_OK;
-} GSWT_CATCH
+}
 
 // The checks gswt_proxy_render_ortho makes on the block's projection (fn: the entry point the refusal names); GSWT_OK or the refusal.
 static int ortho_projection_check(gswt_ctx* c, const gswt_proxy_uniforms* u, const char* fn)
@@ -276,25 +285,28 @@ static int ortho_frame(gswt_ctx* c, const gswt_proxy_uniforms* u, ProxyArgs& a, 
     return GSWT_OK;
 }
 
+int gswt_proxy_render(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, float* rgba_dev, float* depth_dev, int clear_depth)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (int e = proxy_call_check(c, u, width, height, rgba_dev, depth_dev, true, "gswt_proxy_render")) return e;
+    if (u->projection[0] == 0.0f || u->projection[5] == 0.0f) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render: singular projection");
+    ProxyArgs a;
+    proxy_args(c, u, width, height, a);
+    return proxy_draw(c, a, nullptr, false, rgba_dev, depth_dev, clear_depth);
+} GSWT_CATCH
+
 // The orthographic form (include/gswt_hip.h, "orthographic proxy pass"): the same block under an affine projection, k_proxy<., ORTHO>, in the
 // grid frame g = (gx0, gy0, 0).
 int gswt_proxy_render_ortho(gswt_ctx* c, const gswt_proxy_uniforms* u, int width, int height, float* rgba_dev, float* depth_dev, int clear_depth)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;
-    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: bad argument");
-    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_ortho before gswt_proxy_configure");
-    if (u->surface_type == 1u && (c->hm_w == 0 || c->hm_h == 0)) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_ortho: HeightMap surface without gswt_configure height map");
-    if (!(u->tile_width > 0.0f) || (!u->map_proxy && !(u->width_scale > 0.0f))) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_ortho: tile_width / width_scale: cell size must be positive");
+    if (int e = proxy_call_check(c, u, width, height, rgba_dev, depth_dev, true, "gswt_proxy_render_ortho")) return e;
     if (int e = ortho_projection_check(c, u, "gswt_proxy_render_ortho")) return e;
     ProxyArgs a;
     proxy_args(c, u, width, height, a);
     const double g[3] = {a.gx0, a.gy0, 0.0};
     if (int e = ortho_frame(c, u, a, g, "gswt_proxy_render_ortho")) return e;
-    hipSetDevice(c->device);
-    if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
-    launch_proxy_ortho(c->stream, a, shadow_version(c, c->shd_cur), c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
-    HIP_TRY(c, hipGetLastError());
-    return GSWT_OK;
+    return proxy_draw(c, a, nullptr, true, rgba_dev, depth_dev, clear_depth);
 } GSWT_CATCH
 
 // The ground under the Sphere surface (include/gswt_hip.h, "sphere proxy pass"): k_proxy_sphere, an entry point of its own -- gswt_proxy_render
@@ -304,9 +316,8 @@ int gswt_proxy_render_sphere(gswt_ctx* c, const gswt_proxy_uniforms* u, float sp
                              float* depth_dev, int clear_depth)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;
-    if (!u || !rgba_dev || !depth_dev || width <= 0 || height <= 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: bad argument");
     if (projection != 0 && projection != 1) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: projection %d is neither 0 (perspective) nor 1 (orthographic)", projection);
-    if (c->proxy_size == 0 && !u->black_background) return fail(c, GSWT_ERR_STATE, "gswt_proxy_render_sphere before gswt_proxy_configure");
+    if (int e = proxy_call_check(c, u, width, height, rgba_dev, depth_dev, false, "gswt_proxy_render_sphere")) return e;
     if (!(u->tile_width > 0.0f) || !std::isfinite(u->tile_width)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: tile_width must be positive and finite");
     if (!std::isfinite(sphere_radius) || !(sphere_radius > 0.0f)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_proxy_render_sphere: sphere_radius %g must be positive and finite", sphere_radius);
     const float r = sphere_radius + u->height_offset;
@@ -331,11 +342,7 @@ try {
     sp.org[0] = (float)((long)u->center_coord[0] - (long)u->map_half_wh[0]) * u->tile_width;
     sp.org[1] = (float)((long)u->center_coord[1] - (long)u->map_half_wh[1]) * u->tile_width;
     sp.lod_k = ((float)u->map_half_wh[0] * (float)a.tex_size) / ((4.0f * PI) * r);
-    hipSetDevice(c->device);
-    if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)width * height, 1.0f);
-    launch_proxy_sphere(c->stream, a, sp, projection == 1, shadow_version(c, c->shd_cur), c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
-    HIP_TRY(c, hipGetLastError());
-    return GSWT_OK;
+    return proxy_draw(c, a, &sp, projection == 1, rgba_dev, depth_dev, clear_depth);
 } GSWT_CATCH
 
 }  // extern "C"

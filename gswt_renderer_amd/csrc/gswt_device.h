@@ -229,17 +229,19 @@ struct ProxyArgs {
     int hm_w, hm_h, tex_size, n_mips;
     uint32_t mip_off[16];          // float4 offsets of the mip levels
     int width, height;
-    Atmo atm;                      // gswt_set_atmosphere as it stands when the pass is called: k_proxy<FOG> reads the fog part
-    // gswt_proxy_render_ortho only (k_proxy<., true>; zero for the perspective pass, which never reads them).  That kernel works in the
-    // GRID FRAME, world - (gx0, gy0, 0): V[12..14] and cam are given in it, so that no sum cancels at the magnitude of the world coordinates.
+    Atmo atm;                      // gswt_set_atmosphere as it stands when the pass is called: proxy_colour<FOG> reads the fog part
+    // The orthographic passes only (proxy_ray<ORTHO> of either kernel; zero for a perspective pass, which never reads them).  k_proxy<., ORTHO>
+    // works in the GRID FRAME, world - (gx0, gy0, 0): V[12..14] and cam are given in it, so that no sum cancels at the magnitude of the world
+    // coordinates; k_proxy_sphere<., ORTHO> in the world frame (g = 0).
     float ortho_t[2];              // projection[12], projection[13]
     float ortho_o[3];              // grid-frame point of camera-space (0, 0, z0): the ray origin of ndc (p[12], p[13])
     float ortho_d[3];              // the rays' direction: -(V[2], V[6], V[10]), or its negative where depth falls along the view axis
     float ortho_uv0[2];            // frac((gx0, gy0) / tile_width / 4): what the grid frame's uv lacks, up to whole texture periods
 };
 
-// gswt_proxy_render_sphere only (k_proxy_sphere, beside a ProxyArgs whose grid fields it does not read; the orthographic form runs with
-// g = 0: the sphere is centred at the world origin, the rays are of the planet's size there)
+// gswt_proxy_render_sphere only: what k_proxy_sphere's own part (the sphere roots, the unfolding's uv, the LOD) reads beside a ProxyArgs whose
+// grid fields it leaves alone; the shared stages (proxy_ray, proxy_write, proxy_colour) read the ProxyArgs.  The orthographic form runs with
+// g = 0: the sphere is centred at the world origin, the rays are of the planet's size there.
 struct SphereProxyArgs {
     float r;                       // sphere_radius + height_offset: the ground sphere
     float sphere_radius;           // the splats' sphere: mapped_z = (hit.z / r) * sphere_radius is what use_clip tests
@@ -425,10 +427,9 @@ void launch_unshard(hipStream_t s, const void* gathered, void* out, int width, i
 void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int width, int height, int face_size, int equirect,
                    const float4* faces, float4* out);
 void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi, float4* faces);
-// (shd.z set: the pass shades the ground by gswt_set_shadow_map's image, k_proxy<., ., SHD>)
-void launch_proxy(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth);
-void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth);
-// gswt_proxy_render_sphere: ortho != 0 reads a's ortho_* fields (set up with g = 0)
+// The proxy passes, k_proxy / k_proxy_sphere<FOG, ORTHO, SHD>.  ortho: the pass reads a's ortho_* fields (gswt_proxy_render_ortho: set up in
+// the grid frame; gswt_proxy_render_sphere: with g = 0); shd.z set: it shades the ground by gswt_set_shadow_map's image.
+void launch_proxy(hipStream_t s, const ProxyArgs& a, bool ortho, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth);
 void launch_proxy_sphere(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, bool ortho, const Shadow& shd, const float4* tex, float4* rgba,
                          float* depth);
 // One level of the proxy mip build into dst (n x n float4).  src: the staged source, a.pitch bytes per row.  ranges: 2 n int2,

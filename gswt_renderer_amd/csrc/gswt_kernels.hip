@@ -21,6 +21,7 @@
 // What other kernel files use too (lane masks, half decode, the height map's sampler) is in gswt_device_fn.h; what the host computes
 // as well (canonical sin / cos, the sphere unfolding, the height-map coordinates) is gswt_host:: of host/gswt_surface.h, one source.
 #include "gswt_device_fn.h"
+#include "gswt_variant.h"
 
 namespace gswt {
 
@@ -3072,28 +3073,7 @@ __global__ void k_unshard_plane(const P* __restrict__ gathered, P* __restrict__ 
 }
 
 // ---- launch wrappers (called from gswt_api.hip) -------------------------------------
-// The one way a wrapper picks a kernel instantiation from runtime values: with_variant(fn, a, b, ...) calls the generic lambda fn with one
-// compile-time constant per selector -- a bool becomes std::bool_constant, OneOf<V0, .., Vn>{v} the std::integral_constant of the Vi that v
-// equals (the last one when it equals none) -- so that fn names its kernel as k<A, B, ...>.  fn is instantiated for every combination of the
-// selectors: where the kernel has no such form, fn guards the launch with `if constexpr` and the wrapper keeps the combination from arriving.
-template <int... Vs> struct OneOf { int v; };
-template <typename Fn>
-static void with_variant(Fn&& fn) { fn(); }
-template <typename Fn, int V0, int... Vs, typename... Rest>
-static void with_variant(Fn&& fn, OneOf<V0, Vs...> sel, Rest... rest);
-template <typename Fn, typename... Rest>
-static void with_variant(Fn&& fn, bool sel, Rest... rest)
-{
-    if (sel) with_variant([&](auto... cs) { fn(std::true_type{}, cs...); }, rest...);
-    else with_variant([&](auto... cs) { fn(std::false_type{}, cs...); }, rest...);
-}
-template <typename Fn, int V0, int... Vs, typename... Rest>
-static void with_variant(Fn&& fn, OneOf<V0, Vs...> sel, Rest... rest)
-{
-    if (sizeof...(Vs) == 0 || sel.v == V0) with_variant([&](auto... cs) { fn(std::integral_constant<int, V0>{}, cs...); }, rest...);
-    else if constexpr (sizeof...(Vs) != 0) with_variant(fn, OneOf<Vs...>{sel.v}, rest...);
-}
-
+// Every wrapper picks its kernel instantiation from runtime values through with_variant (gswt_variant.h).
 void launch_chunk_tabs(hipStream_t s, const DrawDev* draws, const uint32_t* xcd_first, uint32_t n_draws, uint2* chunk_tab, uint2* chunk_tab_xcd,
                        const uint64_t per_xcd[8], uint64_t longest)
 {

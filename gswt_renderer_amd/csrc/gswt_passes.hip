@@ -16,13 +16,37 @@
 //   k_proxy_sphere : gswt_proxy_render_sphere (no counterpart in the reference, whose proxy draws the plane under every surface): the
 //              ground of the Sphere surface, the pixel's ray against the sphere about the world origin, textured through the inverse of
 //              the sphere unfolding (host/gswt_surface.h: sphere_plane_pos)
+// k_proxy and k_proxy_sphere differ in how a pixel finds its hit, its texture coordinate and its LOD.  The rest is one definition each:
+// proxy_ray (pixel -> ray, perspective or orthographic, also of the neighbour pixels), proxy_write (depth test and store, black_background,
+// the shadow map's loads), proxy_colour (trilinear texture, brightness, shade, fog), and with_proxy_variant behind both launch wrappers.
+// bilerp is the one bilinear blend of the cube map, the proxy texture and the panorama.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (same flags as gswt_kernels.hip).
 #include "gswt_device_fn.h"
+#include "gswt_variant.h"
 
 #include <algorithm>
 
 namespace gswt {
+
+// The bilinear blend of four taps, every channel (a caller that wants rgb drops w): the filter of sample_cube, proxy_tex_bilinear and
+// k_skybox_bake, each with its own addressing (clamp to edge, repeat).
+__device__ __forceinline__ float4 bilerp(const float4 c00, const float4 c10, const float4 c01, const float4 c11, float wx, float wy)
+{
+    const auto mix = [wx, wy](float a, float b, float c, float d) { return (a * (1.0f - wx) + b * wx) * (1.0f - wy) + (c * (1.0f - wx) + d * wx) * wy; };
+    return make_float4(mix(c00.x, c10.x, c01.x, c11.x), mix(c00.y, c10.y, c01.y, c11.y), mix(c00.z, c10.z, c01.z, c11.z), mix(c00.w, c10.w, c01.w, c11.w));
+}
+
+// Direction of the perspective view ray of pixel (x, y): d = R^T v, R = upper 3x3 of the view V (column-major), v = (ndc / (p00, p11), -1)
+__device__ __forceinline__ void pixel_ray(const float* V, float p00, float p11, int x, int y, int W, int H, float d[3])
+{
+    const float nx = ((float)x + 0.5f) / (float)W * 2.0f - 1.0f;
+    const float ny = 1.0f - ((float)y + 0.5f) / (float)H * 2.0f;
+    const float vx = nx / p00, vy = ny / p11, vz = -1.0f;
+    d[0] = (V[0] * vx + V[1] * vy) + V[2] * vz;
+    d[1] = (V[4] * vx + V[5] * vy) + V[6] * vz;
+    d[2] = (V[8] * vx + V[9] * vy) + V[10] * vz;
+}
 
 // Cube-map face selection (WebGPU / Vulkan major-axis rule) + bilinear filter inside the face, clamp to edge
 // (skybox.rs:420-426: ClampToEdge, Linear, level 0).  faces: [6][n][n] float4, +X -X +Y -Y +Z -Z.
@@ -42,17 +66,9 @@ __device__ __forceinline__ float4 sample_cube(const float4* __restrict__ faces, 
     x0 = min(max(x0, 0), n - 1); x1 = min(max(x1, 0), n - 1);
     y0 = min(max(y0, 0), n - 1); y1 = min(max(y1, 0), n - 1);
     const float4* f = faces + (size_t)face * n * n;
-    const float4 c00 = f[(size_t)y0 * n + x0], c10 = f[(size_t)y0 * n + x1];
-    const float4 c01 = f[(size_t)y1 * n + x0], c11 = f[(size_t)y1 * n + x1];
-    float4 o;
-    o.x = (c00.x * (1.0f - wx) + c10.x * wx) * (1.0f - wy) + (c01.x * (1.0f - wx) + c11.x * wx) * wy;
-    o.y = (c00.y * (1.0f - wx) + c10.y * wx) * (1.0f - wy) + (c01.y * (1.0f - wx) + c11.y * wx) * wy;
-    o.z = (c00.z * (1.0f - wx) + c10.z * wx) * (1.0f - wy) + (c01.z * (1.0f - wx) + c11.z * wx) * wy;
-    o.w = 1.0f;
-    return o;
+    const float4 o = bilerp(f[(size_t)y0 * n + x0], f[(size_t)y0 * n + x1], f[(size_t)y1 * n + x0], f[(size_t)y1 * n + x1], wx, wy);
+    return make_float4(o.x, o.y, o.z, 1.0f);
 }
-
-
 
 // One thread per pixel.  The rasterised cube's interpolated attribute `position` at a pixel is a positive multiple
 // of the pixel's world-space view direction, so the lookup vector is that direction, re-ordered as the vertex
@@ -61,14 +77,9 @@ __global__ __launch_bounds__(256) void k_skybox(const SkyArgs a, const float4* _
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= a.width || y >= a.height) return;
-    const float nx = ((float)x + 0.5f) / (float)a.width * 2.0f - 1.0f;
-    const float ny = 1.0f - ((float)y + 0.5f) / (float)a.height * 2.0f;
-    const float vx = nx / a.p00, vy = ny / a.p11, vz = -1.0f;
-    // d = R^T v, R = upper 3x3 of view (column-major)
-    const float dx = (a.V[0] * vx + a.V[1] * vy) + a.V[2] * vz;
-    const float dy = (a.V[4] * vx + a.V[5] * vy) + a.V[6] * vz;
-    const float dz = (a.V[8] * vx + a.V[9] * vy) + a.V[10] * vz;
-    float tx = dx, ty = -dz, tz = dy;
+    float d[3];
+    pixel_ray(a.V, a.p00, a.p11, x, y, a.width, a.height, d);
+    float tx = d[0], ty = -d[2], tz = d[1];
     if (a.equirectangular == 0) ty = -ty;
     out[(size_t)y * a.width + x] = sample_cube(faces, a.face_size, tx, ty, tz);
 }
@@ -85,17 +96,6 @@ void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int
 
 // ---- proxy -----------------------------------------------------------------------------------------
 
-
-__device__ __forceinline__ void pixel_ray(const float* V, float p00, float p11, int x, int y, int W, int H, float d[3])
-{
-    const float nx = ((float)x + 0.5f) / (float)W * 2.0f - 1.0f;
-    const float ny = 1.0f - ((float)y + 0.5f) / (float)H * 2.0f;
-    const float vx = nx / p00, vy = ny / p11, vz = -1.0f;
-    d[0] = (V[0] * vx + V[1] * vy) + V[2] * vz;
-    d[1] = (V[4] * vx + V[5] * vy) + V[6] * vz;
-    d[2] = (V[8] * vx + V[9] * vy) + V[10] * vz;
-}
-
 // gswt_proxy_render_ortho (include/gswt_hip.h, "Ray of pixel (x, y)"): the origin of the pixel's ray, in the grid frame (world - (gx0, gy0, 0)).
 // All rays share the direction ortho_d, -(V[2], V[6], V[10]); ortho_o is the point of camera-space (0, 0, z0), inverted in binary64 by the host.
 __device__ __forceinline__ void ortho_origin(const ProxyArgs& a, int x, int y, float o[3])
@@ -106,6 +106,20 @@ __device__ __forceinline__ void ortho_origin(const ProxyArgs& a, int x, int y, f
     o[0] = (a.V[0] * cx + a.V[1] * cy) + a.ortho_o[0];
     o[1] = (a.V[4] * cx + a.V[5] * cy) + a.ortho_o[1];
     o[2] = (a.V[8] * cx + a.V[9] * cy) + a.ortho_o[2];
+}
+
+// Origin and direction of the ray of pixel (x, y), of both proxy kernels: the pixel's own and those of its right and lower neighbour.
+// Perspective: the eye a.cam and pixel_ray; ORTHO: ortho_origin and the one direction a.ortho_d.
+template <bool ORTHO>
+__device__ __forceinline__ void proxy_ray(const ProxyArgs& a, int x, int y, float o[3], float d[3])
+{
+    if (ORTHO) {
+        ortho_origin(a, x, y, o);
+        d[0] = a.ortho_d[0]; d[1] = a.ortho_d[1]; d[2] = a.ortho_d[2];
+    } else {
+        o[0] = a.cam[0]; o[1] = a.cam[1]; o[2] = a.cam[2];
+        pixel_ray(a.V, a.p00, a.p11, x, y, a.width, a.height, d);
+    }
 }
 
 __device__ __forceinline__ float proxy_mapped_height(const ProxyArgs& a, const float* __restrict__ hm, float rx, float ry)
@@ -165,43 +179,90 @@ __device__ __forceinline__ void proxy_plane_uv(const ProxyArgs& a, const float o
     uv[1] = (o[1] + t * d[1]) / a.tile_width / 4.0f;
 }
 
-__device__ __forceinline__ void proxy_tex_bilinear(const float4* __restrict__ lvl, int n, float u, float v, float out[3])
+__device__ __forceinline__ float4 proxy_tex_bilinear(const float4* __restrict__ lvl, int n, float u, float v)
 {
     const float x = u * (float)n - 0.5f, y = v * (float)n - 0.5f;
     const float fx0 = floorf(x), fy0 = floorf(y);
     const float wx = x - fx0, wy = y - fy0;
     const int xa = wrap_repeat(fx0, n), ya = wrap_repeat(fy0, n);
     const int xb = xa + 1 == n ? 0 : xa + 1, yb = ya + 1 == n ? 0 : ya + 1;
-    const float4 c00 = lvl[ya * n + xa], c10 = lvl[ya * n + xb], c01 = lvl[yb * n + xa], c11 = lvl[yb * n + xb];
-    out[0] = (c00.x * (1.0f - wx) + c10.x * wx) * (1.0f - wy) + (c01.x * (1.0f - wx) + c11.x * wx) * wy;
-    out[1] = (c00.y * (1.0f - wx) + c10.y * wx) * (1.0f - wy) + (c01.y * (1.0f - wx) + c11.y * wx) * wy;
-    out[2] = (c00.z * (1.0f - wx) + c10.z * wx) * (1.0f - wy) + (c01.z * (1.0f - wx) + c11.z * wx) * wy;
+    return bilerp(lvl[ya * n + xa], lvl[ya * n + xb], lvl[yb * n + xa], lvl[yb * n + xb], wx, wy);
 }
 
-// FOG (gswt_set_atmosphere's fog part on when the pass is called): a pixel the proxy writes goes toward fog_color by F of the ray's hit distance
-// from the eye, behind `brightness`; the depth, the pixels left alone and the black_background output are what they are without it.
-// ORTHO (gswt_proxy_render_ortho): parallel rays, one origin per pixel (ortho_origin); a.cam is the reference point the fog distance is
-// measured from, not the origin.  The grid walk, the hit and depth tests and the texturing are the same code; the rays of the right and
-// the lower pixel differ from the pixel's own by their origin instead of their direction.  Rays, vertices, a.cam and the view's translation
-// are in the grid frame, whose lattice starts at (0, 0): far from the world origin nothing here is rounded at the world coordinates'
-// magnitude but the lattice itself (rx, ry: the reference's f32 vertices).
-// SHD (gswt_set_shadow_map with a map on when the pass is called): a pixel the proxy writes goes toward shade_color by the splats' own
-// sh = strength * (1 - lit) (shadow_fetch / shadow_amount, gswt_device_fn.h) at the ray's hit point in WORLD coordinates -- the orthographic
-// pass brings its grid-frame point back by (gx0, gy0) --, behind `brightness` and in front of the fog.  Depth, unwritten pixels and the
-// black_background output are what they are without it.
-template <bool FOG, bool ORTHO = false, bool SHD = false>
+// The two stages k_proxy and k_proxy_sphere share behind their own hit search.  What a kernel brings: the fragment's depth `dep`, its point
+// hp = o + t d in the rays' frame with t and dd = |d|^2, the same point in WORLD coordinates hw, and (for the colour stage) the texture
+// coordinate uv and the LOD's texels per pixel rho.
+//
+// proxy_write -- a fragment's depth state and what needs no texture: CompareFunction::Less against the depth buffer with depth write on, the
+// black_background output, and (SHD) the shadow map's texel loads at hw, issued here so that the kernel's texturing arithmetic and the
+// colour stage's own loads pass over their latency (shadow_fetch, gswt_device_fn.h).  false: the pixel is done.  Every store of either
+// stage goes to pixel pi of the frame.
+template <bool SHD>
+__device__ __forceinline__ bool proxy_write(const ProxyArgs& a, const Shadow& shd, size_t pi, float dep, const float hw[3],
+                                            float4* __restrict__ rgba, float* __restrict__ depth_buf, ShadowTap& tap)
+{
+    if (!(dep < depth_buf[pi])) return false;                     // CompareFunction::Less, depth write on
+    depth_buf[pi] = dep;
+    if (a.black_background == 1u) { rgba[pi] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return false; }
+    if (SHD) tap = shadow_fetch(shd, hw[0], hw[1], hw[2]);
+    return true;
+}
+
+// proxy_colour -- implicit-LOD trilinear texturing (levels clamped to [0, n_mips - 1], proxy_tex_bilinear's wrapped indices), `brightness`,
+// then SHD: toward shade_color by the splats' own sh = strength * (1 - lit) (shadow_amount on proxy_write's tap), then FOG: toward fog_color
+// by F of the hit's distance from the eye -- t |d| under the perspective camera, |hp - a.cam| under ORTHO, where a.cam is the reference
+// point and not the rays' origin.
+template <bool FOG, bool ORTHO, bool SHD>
+__device__ __forceinline__ float4 proxy_colour(const ProxyArgs& a, const Shadow& shd, const ShadowTap& tap, const float4* __restrict__ tex,
+                                               const float uv[2], float rho, const float hp[3], float t, float dd)
+{
+    float lod = log2f(rho);
+    if (!(lod > 0.0f)) lod = 0.0f;
+    if (lod > (float)(a.n_mips - 1)) lod = (float)(a.n_mips - 1);
+    const int l0 = (int)floorf(lod), l1 = l0 + 1 > a.n_mips - 1 ? a.n_mips - 1 : l0 + 1;
+    const float fl = lod - (float)l0;
+    const float4 c0 = proxy_tex_bilinear(tex + a.mip_off[l0], a.tex_size >> l0, uv[0], uv[1]);
+    const float4 c1 = proxy_tex_bilinear(tex + a.mip_off[l1], a.tex_size >> l1, uv[0], uv[1]);
+    float4 px = make_float4((c0.x * (1.0f - fl) + c1.x * fl) * a.brightness, (c0.y * (1.0f - fl) + c1.y * fl) * a.brightness,
+                            (c0.z * (1.0f - fl) + c1.z * fl) * a.brightness, 1.0f);
+    if (SHD) {
+        const float sh = shadow_amount(shd, tap);
+        if (sh != 0.0f) {
+            px.x = px.x * (1.0f - sh) + shd.shade[0] * sh;
+            px.y = px.y * (1.0f - sh) + shd.shade[1] * sh;
+            px.z = px.z * (1.0f - sh) + shd.shade[2] * sh;
+        }
+    }
+    if (FOG) {
+        float dist;
+        if (ORTHO) {
+            const float fx = hp[0] - a.cam[0], fy = hp[1] - a.cam[1], fz = hp[2] - a.cam[2];
+            dist = sqrtf((fx * fx + fy * fy) + fz * fz);
+        } else
+            dist = t * sqrtf(dd);
+        const float F = fog_amount(a.atm, dist);
+        px.x = px.x * (1.0f - F) + a.atm.fog_color[0] * F;
+        px.y = px.y * (1.0f - F) + a.atm.fog_color[1] * F;
+        px.z = px.z * (1.0f - F) + a.atm.fog_color[2] * F;
+    }
+    return px;
+}
+
+// FOG (gswt_set_atmosphere's fog part on when the pass is called), SHD (gswt_set_shadow_map with a map on when the pass is called): the
+// colour stage above; the depth, the pixels left alone and the black_background output are what they are without them.
+// ORTHO (gswt_proxy_render_ortho): parallel rays, one origin per pixel (proxy_ray).  The grid walk, the hit and depth tests and the
+// texturing are the same code; the rays of the right and the lower pixel differ from the pixel's own by their origin instead of their
+// direction.  Rays, vertices, a.cam and the view's translation are in the grid frame, whose lattice starts at (0, 0): far from the world
+// origin nothing here is rounded at the world coordinates' magnitude but the lattice itself (rx, ry: the reference's f32 vertices); the
+// hit point goes back to WORLD coordinates by (gx0, gy0) for the shadow map.
+template <bool FOG, bool ORTHO, bool SHD>
 __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* __restrict__ hm, const float4* __restrict__ tex,
                                                float4* __restrict__ rgba, float* __restrict__ depth_buf, const Shadow shd)
 {
     const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= a.width || y >= a.height) return;
-    float o[3] = {a.cam[0], a.cam[1], a.cam[2]};
-    float d[3];
-    if (ORTHO) {
-        ortho_origin(a, x, y, o);
-        d[0] = a.ortho_d[0]; d[1] = a.ortho_d[1]; d[2] = a.ortho_d[2];
-    } else
-        pixel_ray(a.V, a.p00, a.p11, x, y, a.width, a.height, d);
+    float o[3], d[3];
+    proxy_ray<ORTHO>(a, x, y, o, d);
     float best_t = 3.0e38f, dep = 1.0f, nrm[3] = {0.0f, 0.0f, 1.0f}, pa[3] = {0.0f, 0.0f, 0.0f};
     bool hit = false;
     const float fx0 = ORTHO ? 0.0f : a.gx0, fy0 = ORTHO ? 0.0f : a.gy0;      // the lattice's origin in the rays' frame
@@ -258,64 +319,29 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
             }
         }
     }
+    if (!hit) return;
     const size_t pi = (size_t)y * a.width + x;
-    if (!hit || !(dep < depth_buf[pi])) return;                  // CompareFunction::Less, depth write on
-    depth_buf[pi] = dep;
-    if (a.black_background == 1u) { rgba[pi] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
-    // (the texels' round trip passes under the texturing below)
-    ShadowTap tap = {};
-    if (SHD) {
+    float hw[3] = {0.0f, 0.0f, 0.0f};
+    if (SHD) {                                                   // the hit point back in WORLD coordinates
         const float hx = o[0] + best_t * d[0], hy = o[1] + best_t * d[1], hz = o[2] + best_t * d[2];
-        tap = shadow_fetch(shd, ORTHO ? hx + a.gx0 : hx, ORTHO ? hy + a.gy0 : hy, hz);
+        hw[0] = ORTHO ? hx + a.gx0 : hx; hw[1] = ORTHO ? hy + a.gy0 : hy; hw[2] = hz;
     }
-    float uv[2], uvx[2], uvy[2], dxr[3], dyr[3];
+    ShadowTap tap;                                               // (SHD only: proxy_write sets it, proxy_colour reads it)
+    if (!proxy_write<SHD>(a, shd, pi, dep, hw, rgba, depth_buf, tap)) return;
+    float uv[2], uvx[2], uvy[2], on[3], dn[3];
     proxy_plane_uv(a, o, d, pa, nrm, uv);
-    if (ORTHO) {                                                 // (dxr, dyr: the neighbours' origins)
-        ortho_origin(a, x + 1, y, dxr);
-        ortho_origin(a, x, y + 1, dyr);
-        proxy_plane_uv(a, dxr, d, pa, nrm, uvx);
-        proxy_plane_uv(a, dyr, d, pa, nrm, uvy);
-    } else {
-        pixel_ray(a.V, a.p00, a.p11, x + 1, y, a.width, a.height, dxr);
-        pixel_ray(a.V, a.p00, a.p11, x, y + 1, a.width, a.height, dyr);
-        proxy_plane_uv(a, o, dxr, pa, nrm, uvx);
-        proxy_plane_uv(a, o, dyr, pa, nrm, uvy);
-    }
+    proxy_ray<ORTHO>(a, x + 1, y, on, dn);
+    proxy_plane_uv(a, on, dn, pa, nrm, uvx);
+    proxy_ray<ORTHO>(a, x, y + 1, on, dn);
+    proxy_plane_uv(a, on, dn, pa, nrm, uvy);
     const float sz = (float)a.tex_size;
     const float ax = (uvx[0] - uv[0]) * sz, ay = (uvx[1] - uv[1]) * sz, bx = (uvy[0] - uv[0]) * sz, by = (uvy[1] - uv[1]) * sz;
     const float rho = fmaxf(sqrtf(ax * ax + ay * ay), sqrtf(bx * bx + by * by));
     if (ORTHO) { uv[0] = uv[0] + a.ortho_uv0[0]; uv[1] = uv[1] + a.ortho_uv0[1]; }      // grid frame -> world, modulo the texture's period
-    float lod = log2f(rho);
-    if (!(lod > 0.0f)) lod = 0.0f;
-    if (lod > (float)(a.n_mips - 1)) lod = (float)(a.n_mips - 1);
-    const int l0 = (int)floorf(lod), l1 = l0 + 1 > a.n_mips - 1 ? a.n_mips - 1 : l0 + 1;
-    const float fl = lod - (float)l0;
-    float c0[3], c1[3];
-    proxy_tex_bilinear(tex + a.mip_off[l0], a.tex_size >> l0, uv[0], uv[1], c0);
-    proxy_tex_bilinear(tex + a.mip_off[l1], a.tex_size >> l1, uv[0], uv[1], c1);
-    float4 px = make_float4((c0[0] * (1.0f - fl) + c1[0] * fl) * a.brightness, (c0[1] * (1.0f - fl) + c1[1] * fl) * a.brightness,
-                            (c0[2] * (1.0f - fl) + c1[2] * fl) * a.brightness, 1.0f);
-    if (SHD) {
-        const float sh = shadow_amount(shd, tap);
-        if (sh != 0.0f) {
-            px.x = px.x * (1.0f - sh) + shd.shade[0] * sh;
-            px.y = px.y * (1.0f - sh) + shd.shade[1] * sh;
-            px.z = px.z * (1.0f - sh) + shd.shade[2] * sh;
-        }
-    }
-    if (FOG) {
-        float dist;
-        if (ORTHO) {
-            const float fx = (o[0] + best_t * d[0]) - a.cam[0], fy = (o[1] + best_t * d[1]) - a.cam[1], fz = (o[2] + best_t * d[2]) - a.cam[2];
-            dist = sqrtf((fx * fx + fy * fy) + fz * fz);
-        } else
-            dist = best_t * sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-        const float F = fog_amount(a.atm, dist);
-        px.x = px.x * (1.0f - F) + a.atm.fog_color[0] * F;
-        px.y = px.y * (1.0f - F) + a.atm.fog_color[1] * F;
-        px.z = px.z * (1.0f - F) + a.atm.fog_color[2] * F;
-    }
-    rgba[pi] = px;
+    // ... and in the rays' frame, for the fog: the same sums, written where they are used (in front of the depth test they stay live across the
+    // texturing, 2 % more instructions in k_proxy<FOG, ORTHO>)
+    const float hp[3] = {o[0] + best_t * d[0], o[1] + best_t * d[1], o[2] + best_t * d[2]};
+    rgba[pi] = proxy_colour<FOG, ORTHO, SHD>(a, shd, tap, tex, uv, rho, hp, best_t, (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
 }
 
 // ---- sphere proxy ------------------------------------------------------------------------------------
@@ -347,23 +373,17 @@ __device__ __forceinline__ float sphere_neighbour_dist(const float o[3], const f
     return sqrtf((ex * ex + ey * ey) + ez * ez);
 }
 
-// FOG / ORTHO / SHD as k_proxy's; the ORTHO host set-up runs with g = 0, so origin, a.cam, the view's translation and the hit are in world
-// coordinates.  The grid fields of a (nx, ny, cs, gx0, gy0), map_proxy, width_scale, surface_type and the height map are not read.
-// Every store goes to pixel (x, y) of the frame, inside width x height by the first test; the texture reads are proxy_tex_bilinear's wrapped
-// indices at levels clamped to [0, n_mips - 1].
+// FOG / ORTHO / SHD: proxy_ray, proxy_write and proxy_colour, the stages k_proxy runs; the ORTHO host set-up runs with g = 0, so origin,
+// a.cam, the view's translation and the hit are in world coordinates.  The grid fields of a (nx, ny, cs, gx0, gy0), map_proxy, width_scale,
+// surface_type and the height map are not read.  Every store goes to pixel (x, y) of the frame, inside width x height by the first test.
 template <bool FOG, bool ORTHO, bool SHD>
 __global__ __launch_bounds__(256) void k_proxy_sphere(const ProxyArgs a, const SphereProxyArgs sp, const float4* __restrict__ tex,
                                                       float4* __restrict__ rgba, float* __restrict__ depth_buf, const Shadow shd)
 {
     const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= a.width || y >= a.height) return;
-    float o[3] = {a.cam[0], a.cam[1], a.cam[2]};
-    float d[3];
-    if (ORTHO) {
-        ortho_origin(a, x, y, o);
-        d[0] = a.ortho_d[0]; d[1] = a.ortho_d[1]; d[2] = a.ortho_d[2];
-    } else
-        pixel_ray(a.V, a.p00, a.p11, x, y, a.width, a.height, d);
+    float o[3], d[3];
+    proxy_ray<ORTHO>(a, x, y, o, d);
     float tc, h, dd;
     if (!sphere_cut(o, d, sp.r, false, tc, h, dd)) return;
     bool hit = false, second = false;
@@ -378,57 +398,21 @@ __global__ __launch_bounds__(256) void k_proxy_sphere(const ProxyArgs a, const S
         hp[0] = p[0]; hp[1] = p[1]; hp[2] = p[2];
     }
     const size_t pi = (size_t)y * a.width + x;
-    if (!hit || !(dep < depth_buf[pi])) return;                  // CompareFunction::Less, depth write on
-    depth_buf[pi] = dep;
-    if (a.black_background == 1u) { rgba[pi] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
-    ShadowTap tap = {};
-    if (SHD) tap = shadow_fetch(shd, hp[0], hp[1], hp[2]);
+    ShadowTap tap;                                               // (SHD only: proxy_write sets it, proxy_colour reads it)
+    if (!hit) return;
+    if (!proxy_write<SHD>(a, shd, pi, dep, hp, rgba, depth_buf, tap)) return;          // (g = 0: the rays' frame is the world)
     float px, py;
     gswt_host::sphere_plane_pos(sp.block_w, gswt_host::V3{hp[0] / sp.r, hp[1] / sp.r, hp[2] / sp.r}, px, py);
     float uv[2] = {(sp.org[0] + px) / a.tile_width / 4.0f, (sp.org[1] + py) / a.tile_width / 4.0f};
     if (!(fabsf(uv[0]) < 3.0e38f)) uv[0] = 0.0f;                 // (a finite hit gives finite coordinates; nothing else reaches the sampler)
     if (!(fabsf(uv[1]) < 3.0e38f)) uv[1] = 0.0f;
     // LOD from the world distance to the neighbour pixels' hits: free of the unfolding's seams and of the pinch at the poles
-    float ex, ey;
-    {
-        float on[3] = {o[0], o[1], o[2]}, dn[3] = {d[0], d[1], d[2]};
-        if (ORTHO) ortho_origin(a, x + 1, y, on); else pixel_ray(a.V, a.p00, a.p11, x + 1, y, a.width, a.height, dn);
-        ex = sphere_neighbour_dist(on, dn, sp.r, second, hp);
-        if (ORTHO) ortho_origin(a, x, y + 1, on); else pixel_ray(a.V, a.p00, a.p11, x, y + 1, a.width, a.height, dn);
-        ey = sphere_neighbour_dist(on, dn, sp.r, second, hp);
-    }
-    const float rho = fmaxf(ex, ey) * sp.lod_k;
-    float lod = log2f(rho);
-    if (!(lod > 0.0f)) lod = 0.0f;
-    if (lod > (float)(a.n_mips - 1)) lod = (float)(a.n_mips - 1);
-    const int l0 = (int)floorf(lod), l1 = l0 + 1 > a.n_mips - 1 ? a.n_mips - 1 : l0 + 1;
-    const float fl = lod - (float)l0;
-    float c0[3], c1[3];
-    proxy_tex_bilinear(tex + a.mip_off[l0], a.tex_size >> l0, uv[0], uv[1], c0);
-    proxy_tex_bilinear(tex + a.mip_off[l1], a.tex_size >> l1, uv[0], uv[1], c1);
-    float4 out = make_float4((c0[0] * (1.0f - fl) + c1[0] * fl) * a.brightness, (c0[1] * (1.0f - fl) + c1[1] * fl) * a.brightness,
-                             (c0[2] * (1.0f - fl) + c1[2] * fl) * a.brightness, 1.0f);
-    if (SHD) {
-        const float sh = shadow_amount(shd, tap);
-        if (sh != 0.0f) {
-            out.x = out.x * (1.0f - sh) + shd.shade[0] * sh;
-            out.y = out.y * (1.0f - sh) + shd.shade[1] * sh;
-            out.z = out.z * (1.0f - sh) + shd.shade[2] * sh;
-        }
-    }
-    if (FOG) {
-        float dist;
-        if (ORTHO) {
-            const float fx = hp[0] - a.cam[0], fy = hp[1] - a.cam[1], fz = hp[2] - a.cam[2];
-            dist = sqrtf((fx * fx + fy * fy) + fz * fz);
-        } else
-            dist = t * sqrtf(dd);
-        const float F = fog_amount(a.atm, dist);
-        out.x = out.x * (1.0f - F) + a.atm.fog_color[0] * F;
-        out.y = out.y * (1.0f - F) + a.atm.fog_color[1] * F;
-        out.z = out.z * (1.0f - F) + a.atm.fog_color[2] * F;
-    }
-    rgba[pi] = out;
+    float on[3], dn[3];
+    proxy_ray<ORTHO>(a, x + 1, y, on, dn);
+    const float ex = sphere_neighbour_dist(on, dn, sp.r, second, hp);
+    proxy_ray<ORTHO>(a, x, y + 1, on, dn);
+    const float ey = sphere_neighbour_dist(on, dn, sp.r, second, hp);
+    rgba[pi] = proxy_colour<FOG, ORTHO, SHD>(a, shd, tap, tex, uv, fmaxf(ex, ey) * sp.lod_k, hp, t, dd);
 }
 
 // ---- skybox bake -----------------------------------------------------------------------------------
@@ -458,12 +442,8 @@ __global__ __launch_bounds__(256) void k_skybox_bake(const SkyBakeArgs a, const 
     const float tx = sx - fx0, ty = sy - fy0;
     const int xa = wrap_repeat(fx0, w), ya = wrap_repeat(fy0, h);
     const int xb = xa + 1 == w ? 0 : xa + 1, yb = ya + 1 == h ? 0 : ya + 1;
-    const float4 c00 = equi[(size_t)ya * w + xa], c10 = equi[(size_t)ya * w + xb];
-    const float4 c01 = equi[(size_t)yb * w + xa], c11 = equi[(size_t)yb * w + xb];
-    float c[3];
-    c[0] = (c00.x * (1.0f - tx) + c10.x * tx) * (1.0f - ty) + (c01.x * (1.0f - tx) + c11.x * tx) * ty;
-    c[1] = (c00.y * (1.0f - tx) + c10.y * tx) * (1.0f - ty) + (c01.y * (1.0f - tx) + c11.y * tx) * ty;
-    c[2] = (c00.z * (1.0f - tx) + c10.z * tx) * (1.0f - ty) + (c01.z * (1.0f - tx) + c11.z * tx) * ty;
+    const float4 tap = bilerp(equi[(size_t)ya * w + xa], equi[(size_t)ya * w + xb], equi[(size_t)yb * w + xa], equi[(size_t)yb * w + xb], tx, ty);
+    float c[3] = {tap.x, tap.y, tap.z};
     const float gamma = (float)(1.0 / 2.2);          // the f32 constant of pow(color, vec3(1.0/2.2))
     for (int k = 0; k < 3; k++) {
         const float r = c[k] / (c[k] + 1.0f);
@@ -716,45 +696,29 @@ void launch_fill_f32(hipStream_t s, float* p, size_t n, float v)
     if (n) hipLaunchKernelGGL(k_fill_f32, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, p, n, v);
 }
 
-// the pass's instantiation from the fog part of a.atm and the shadow map in force (both read when the pass is called)
-template <bool ORTHO>
-static void launch_proxy_variant(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth)
+// A proxy pass's instantiation, for both kernels: fn(FOG, ORTHO, SHD, grid), the constants in the kernels' template order <FOG, ORTHO, SHD>.
+// FOG from the fog part of a.atm, SHD from the shadow map in force (both read when the pass is called), ORTHO from the entry point.
+template <typename Fn>
+static void with_proxy_variant(const ProxyArgs& a, bool ortho, const Shadow& shd, Fn&& fn)
 {
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
     const bool fog = a.atm.fog_density > 0.0f, shade = shd.z != nullptr;
-    if (fog && shade) hipLaunchKernelGGL((k_proxy<true, ORTHO, true>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
-    else if (fog) hipLaunchKernelGGL((k_proxy<true, ORTHO, false>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
-    else if (shade) hipLaunchKernelGGL((k_proxy<false, ORTHO, true>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
-    else hipLaunchKernelGGL((k_proxy<false, ORTHO, false>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
+    with_variant([&](auto FOG, auto ORTHO, auto SHD) { fn(FOG, ORTHO, SHD, grid); }, fog, ortho, shade);
 }
 
-void launch_proxy(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth)
+void launch_proxy(hipStream_t s, const ProxyArgs& a, bool ortho, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth)
 {
-    launch_proxy_variant<false>(s, a, shd, hm, tex, rgba, depth);
-}
-
-void launch_proxy_ortho(hipStream_t s, const ProxyArgs& a, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth)
-{
-    launch_proxy_variant<true>(s, a, shd, hm, tex, rgba, depth);
-}
-
-template <bool ORTHO>
-static void launch_proxy_sphere_variant(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, const Shadow& shd, const float4* tex,
-                                        float4* rgba, float* depth)
-{
-    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-    const bool fog = a.atm.fog_density > 0.0f, shade = shd.z != nullptr;
-    if (fog && shade) hipLaunchKernelGGL((k_proxy_sphere<true, ORTHO, true>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
-    else if (fog) hipLaunchKernelGGL((k_proxy_sphere<true, ORTHO, false>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
-    else if (shade) hipLaunchKernelGGL((k_proxy_sphere<false, ORTHO, true>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
-    else hipLaunchKernelGGL((k_proxy_sphere<false, ORTHO, false>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
+    with_proxy_variant(a, ortho, shd, [&](auto FOG, auto ORTHO, auto SHD, dim3 grid) {
+        hipLaunchKernelGGL((k_proxy<FOG, ORTHO, SHD>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
+    });
 }
 
 void launch_proxy_sphere(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, bool ortho, const Shadow& shd, const float4* tex,
                          float4* rgba, float* depth)
 {
-    if (ortho) launch_proxy_sphere_variant<true>(s, a, sp, shd, tex, rgba, depth);
-    else launch_proxy_sphere_variant<false>(s, a, sp, shd, tex, rgba, depth);
+    with_proxy_variant(a, ortho, shd, [&](auto FOG, auto ORTHO, auto SHD, dim3 grid) {
+        hipLaunchKernelGGL((k_proxy_sphere<FOG, ORTHO, SHD>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
+    });
 }
 
 }  // namespace gswt

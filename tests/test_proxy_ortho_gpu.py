@@ -13,6 +13,7 @@ import pytest
 from gswt_renderer_amd import _lib as L
 from gswt_renderer_amd import atmosphere as A
 from gswt_renderer_amd import ortho
+from tests import frame_modes as FM
 from tests import proxy_ortho_ref as O
 from tests import proxy_raster_ref as R
 
@@ -47,10 +48,6 @@ def _draw(r, us, Wp, Hp, grid_dim, hm, mips, fog=A.OFF, projection=1):
     return depth.cpu().numpy(), rgba.cpu().numpy()
 
 
-def _same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
 def _check(name, got_d, got_c, us, opt, ref, label=None, factor=O.DEPTH_FACTOR):
     ref_d, ref_c, amb, res, ctol = ref
     tol, emu = O.depth_tol(us, W, H, res, amb, factor)
@@ -74,10 +71,10 @@ def test_kernel_matches_rasterised_mesh(renderer, name):
     _check(name, got_d, got_c, us, opt, ref)
     if name == "black_background":
         wr = got_d < 1.0
-        assert (got_c[wr] == np.array([0.0, 0.0, 0.0, 1.0], np.float32)).all() and _same(got_c[~wr], R.sky(W, H)[~wr])
+        assert (got_c[wr] == np.array([0.0, 0.0, 0.0, 1.0], np.float32)).all() and FM.same(got_c[~wr], R.sky(W, H)[~wr])
     if name == "top_down":          # wider than the map: the pixels off the footprint keep the incoming colour and depth 1
         off = ref[0] == 1.0
-        assert 0.1 < off.mean() < 0.15 and (got_d[off] == 1.0).all() and _same(got_c[off], R.sky(W, H)[off])
+        assert 0.1 < off.mean() < 0.15 and (got_d[off] == 1.0).all() and FM.same(got_c[off], R.sky(W, H)[off])
 
 
 def test_pixel_centres_on_lattice_lines_and_vertices(renderer):
@@ -162,7 +159,7 @@ def test_fog(renderer, name):
     d0, c0 = _draw(renderer, us, W, H, grid_dim, hm, mips)
     d1, c1 = _draw(renderer, us, W, H, grid_dim, hm, mips, fog=FOG)
     wr = d0 < 1.0
-    assert _same(d0, d1) and _same(c0[~wr], c1[~wr]) and not _same(c0[wr], c1[wr])
+    assert FM.same(d0, d1) and FM.same(c0[~wr], c1[~wr]) and not FM.same(c0[wr], c1[wr])
     moved = np.abs(ref[1] - ref0[1]).max(-1)[wr]
     assert moved.max() > 0.1                                           # the fog is not a detail of this frame
     _check(name, d0, c0, us, opt, ref0, label=name + " unfogged")
@@ -202,12 +199,12 @@ def test_perspective_pass_untouched(renderer):
     renderer.set_option(L.GSWT_OPT_PROJECTION, L.GSWT_PROJECTION_PERSPECTIVE)
     without = _draw(renderer, us, W, H, grid_dim, hm, mips, projection=0)
     for other in (after, with_opt, without):
-        assert _same(before[0], other[0]) and _same(before[1], other[1])
+        assert FM.same(before[0], other[0]) and FM.same(before[1], other[1])
     # ... and the orthographic pass does not read the option either
     a = _draw(renderer, ous, W, H, grid_dim, hm, mips)
     renderer.set_option(L.GSWT_OPT_PROJECTION, L.GSWT_PROJECTION_ORTHO)
     b = _draw(renderer, ous, W, H, grid_dim, hm, mips)
-    assert _same(a[0], b[0]) and _same(a[1], b[1])
+    assert FM.same(a[0], b[0]) and FM.same(a[1], b[1])
 
 
 def test_refusals(renderer):
@@ -255,7 +252,7 @@ def test_refusals(renderer):
         assert word in lib.gswt_last_error(h) and b"gswt_proxy_render_ortho" in lib.gswt_last_error(h), (what, lib.gswt_last_error(h))
     renderer.synchronize()
     torch.cuda.synchronize()
-    assert bool((depth == 0.25).all()) and _same(rgba.cpu().numpy(), R.sky(W, H))          # nothing enqueued, clear_depth not performed
+    assert bool((depth == 0.25).all()) and FM.same(rgba.cpu().numpy(), R.sky(W, H))          # nothing enqueued, clear_depth not performed
     # a HeightMap surface without a height map is a state error, as in the perspective call
     renderer.configure(None)
     assert lib.gswt_proxy_render_ortho(h, block(), W, H, rp, dp, 1) == L.GSWT_ERR_STATE
@@ -264,6 +261,6 @@ def test_refusals(renderer):
     assert bool((depth == 0.25).all())
     # the next valid call works
     again = _draw(renderer, us, W, H, grid_dim, hm, mips)
-    assert _same(good[0], again[0]) and _same(good[1], again[1])
+    assert FM.same(good[0], again[0]) and FM.same(good[1], again[1])
     with pytest.raises(ValueError):
         renderer.proxy_render(us[0], W, H, rgba.data_ptr(), depth.data_ptr(), True, projection=2)

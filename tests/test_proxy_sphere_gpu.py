@@ -11,6 +11,7 @@ import pytest
 
 from gswt_renderer_amd import _lib as L
 from gswt_renderer_amd import atmosphere as A
+from tests import frame_modes as FM
 from tests import proxy_raster_ref as R
 from tests import proxy_sphere_ref as S
 
@@ -23,10 +24,6 @@ def _defaults(renderer):
     yield
     renderer.set_atmosphere(A.OFF)
     renderer.set_shadow_map(None)
-
-
-def _same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
 def _draw(r, u, projection, W, H, mips, fog=None, shadow=None, depth_in=None, radius=S.RADIUS):
@@ -57,14 +54,14 @@ def test_kernel_matches_reference(renderer, name):
           f"colour error {raw_c:.3e} (allowance 1e-4 + up to {res['col_tol'].max():.2e})")
     S.compare(got_d, got_c, res, depth_in)
     unwritten = ~res["written"] & off
-    assert _same(got_c[unwritten], R.sky(W, H)[unwritten])                        # the colour is loaded, not cleared
+    assert FM.same(got_c[unwritten], R.sky(W, H)[unwritten])                        # the colour is loaded, not cleared
     if name == "black_background":
         wr = res["written"] & off
         assert (got_c[wr] == np.array([0.0, 0.0, 0.0, 1.0], np.float32)).all()
     if name == "incoming_depth":
         left = np.zeros((H, W), bool)
         left[:, :W // 2] = True
-        assert _same(got_d[left], depth_in[left]) and (got_d[~left & res["written"]] < 1.0).all()
+        assert FM.same(got_d[left], depth_in[left]) and (got_d[~left & res["written"]] < 1.0).all()
 
 
 def test_depth_does_not_depend_on_fog_or_shade(renderer):
@@ -72,7 +69,56 @@ def test_depth_does_not_depend_on_fog_or_shade(renderer):
     d0, c0 = _draw(renderer, u, projection, W, H, mips)
     d1, c1 = _draw(renderer, u, projection, W, H, mips, fog=S.fog_block(), shadow=S.shadow_block())
     wr = d0 < 1.0
-    assert _same(d0, d1) and _same(c0[~wr], c1[~wr]) and not _same(c0[wr], c1[wr])
+    assert FM.same(d0, d1) and FM.same(c0[~wr], c1[~wr]) and not FM.same(c0[wr], c1[wr])
+
+
+_MODE_REFS = {}
+
+
+def _mode_reference(name, fog, shade):
+    """The float64 reference of scene `name` under S.fog_block() / S.shadow_block(), computed once per process; nobody writes into it."""
+    if (name, fog, shade) not in _MODE_REFS:
+        u, projection, W, H, mips, _, _, _, plain = S.scene_reference(name)
+        _MODE_REFS[name, fog, shade] = plain if not (fog or shade) else S.render(
+            u, S.RADIUS, W, H, projection=projection, mips=mips, rgba_in=R.sky(W, H), fog=S.fog_block() if fog else None,
+            shadow=S.shadow_block() if shade else None)
+    return _MODE_REFS[name, fog, shade]
+
+
+@pytest.mark.parametrize("name", ["oblique", "ortho_planet"])
+def test_every_fog_and_shade_instantiation(renderer, name):
+    """k_proxy_sphere<FOG, ORTHO, SHD> for all four (fog, shade) settings under each camera -- the scenes above launch five of the eight:
+    each against the reference by S.compare; depth bit-equal across the four and unwritten pixels the incoming sky; and each switch moves
+    the colour of at least MOVED (10 %) of the written pixels by more than 0.01, so that one instantiation cannot stand in for another
+    (the float64 reference alone moves 18 % / 81 % of them with the shade and 99.9 % with the fog)."""
+    MOVED = 0.10
+    u, projection, W, H, mips, _, _, _, _ = S.scene_reference(name)
+    sky = R.sky(W, H)
+    got = {}
+    for fog in (False, True):
+        for shade in (False, True):
+            res = _mode_reference(name, fog, shade)
+            d, c = _draw(renderer, u, projection, W, H, mips, S.fog_block() if fog else None, S.shadow_block() if shade else None)
+            off = ~res["amb"]
+            raw_c = float(np.abs(c.astype(np.float64) - res["rgba"]).max(-1)[off].max())
+            share, cover = S.conditions(res)
+            derr, tol, cerr = S.compare(d, c, res)
+            print(f"{name} fog {int(fog)} shade {int(shade)}: cover {cover:.3f} mask {share:.3%} depth error {derr:.3e} (bound {tol:.3e}) "
+                  f"colour error {raw_c:.3e} (allowance 1e-4 + up to {res['col_tol'].max():.2e}; beyond it by {cerr:.3e}, bound 0)")
+            unwritten = ~res["written"] & off
+            assert FM.same(c[unwritten], sky[unwritten])
+            got[fog, shade] = (d, c)
+    d0, c0 = got[False, False]
+    assert all(FM.same(d, d0) for d, _ in got.values())
+    wr = d0 < 1.0
+
+    def moved(a, b):
+        return float((np.abs(got[a][1][wr].astype(np.float64) - got[b][1][wr])[:, :3].max(-1) > 0.01).mean())
+
+    switches = {"shade, fog off": moved((False, False), (False, True)), "shade, fog on": moved((True, False), (True, True)),
+                "fog, shade off": moved((False, False), (True, False)), "fog, shade on": moved((False, True), (True, True))}
+    print(f"{name}: written pixels moved by more than 0.01 (floor {MOVED:.0%}): " + ", ".join(f"{k} {v:.1%}" for k, v in switches.items()))
+    assert min(switches.values()) >= MOVED, switches
 
 
 def test_depth_only_ground_on_a_fresh_context():
@@ -148,7 +194,7 @@ def test_refusals(renderer):
         assert word in err and b"gswt_proxy_render_sphere" in err, (what, err)
         renderer.synchronize()
         torch.cuda.synchronize()
-        assert bool((depth == 0.25).all()) and _same(rgba.cpu().numpy(), R.sky(W, H)), what       # nothing enqueued, clear_depth not performed
+        assert bool((depth == 0.25).all()) and FM.same(rgba.cpu().numpy(), R.sky(W, H)), what       # nothing enqueued, clear_depth not performed
     with pytest.raises(ValueError):
         renderer.proxy_render_sphere(u0, Rr, W, H, rgba.data_ptr(), depth.data_ptr(), True, projection=2)
     # the fields the pass does not read may hold anything
@@ -159,7 +205,7 @@ def test_refusals(renderer):
     torch.cuda.synchronize()
     assert lib.gswt_proxy_render_sphere(h, junk, Rr, 0, W, H, C.c_void_p(c2.data_ptr()), C.c_void_p(d2.data_ptr()), 1) == L.GSWT_OK
     renderer.synchronize()
-    assert _same(d2.cpu().numpy(), good[0]) and _same(c2.cpu().numpy(), good[1])
+    assert FM.same(d2.cpu().numpy(), good[0]) and FM.same(c2.cpu().numpy(), good[1])
 
 
 def test_plane_passes_still_draw_the_plane_on_a_sphere_block(renderer):
@@ -194,4 +240,4 @@ def test_plane_passes_still_draw_the_plane_on_a_sphere_block(renderer):
         su, sp, sw, sh, smips, _, _, _, _ = S.scene_reference("oblique")
         _draw(renderer, su, sp, sw, sh, None)
         d2b, c2b = plane(blocks, 2, projection)
-        assert _same(d0, d2) and _same(c0, c2) and _same(d0, d2b) and _same(c0, c2b)
+        assert FM.same(d0, d2) and FM.same(c0, c2) and FM.same(d0, d2b) and FM.same(c0, c2b)
