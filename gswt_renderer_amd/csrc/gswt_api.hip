@@ -122,8 +122,8 @@ try {
         if (hipEventCreate(&sl.ev_gather) != hipSuccess) return GSWT_ERR_HIP;
         for (auto& e : sl.ev)
             if (hipEventCreate(&e) != hipSuccess) return GSWT_ERR_HIP;
-        if (hipHostMalloc(reinterpret_cast<void**>(&sl.hc), 8 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess) return GSWT_ERR_HIP;
-        memset(sl.hc, 0, 8 * sizeof(unsigned long long));
+        if (hipHostMalloc(reinterpret_cast<void**>(&sl.hc), sizeof(FrameResult), hipHostMallocMapped) != hipSuccess) return GSWT_ERR_HIP;
+        memset(sl.hc, 0, sizeof(FrameResult));
         if (hipHostGetDevicePointer(reinterpret_cast<void**>(&sl.hc_dev), sl.hc, 0) != hipSuccess) sl.hc_dev = nullptr;   // then the copy stays
     }
     *out = c.release();
@@ -575,27 +575,25 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     // (cleared ON THE SLOT'S STREAM: the slot streams are non-blocking, so a null-stream hipMemset -- asynchronous to the host for
     // device memory -- could land after this frame's k_cull had filled the counts: the slot's FIRST frame then projected nothing
     // and came back as background.  Seen once five slots made test_async_all_slots_in_flight_and_slot_reuse the first user of slot 4.)
-    if (!sl.live_cnt.p) { HIP_TRY(c, sl.live_cnt.ensure(16 * kSuperStride)); HIP_TRY(c, hipMemsetAsync(sl.live_cnt.p, 0, sl.live_cnt.cap * 4, sl.stream)); }
+    if (!sl.live_cnt.p) { HIP_TRY(c, sl.live_cnt.ensure(kLiveTableWords)); HIP_TRY(c, hipMemsetAsync(sl.live_cnt.p, 0, sl.live_cnt.cap * 4, sl.stream)); }
     HIP_TRY(c, sl.draw_culled.ensure_roomy((size_t)D.n_draws + 1));
     HIP_TRY(c, sl.cell_culled.ensure((size_t)b.n_cells + 1));
     if (a.su.draw_mode != 0u) HIP_TRY(c, sl.col_f.ensure(n_slots_all + 1));
     if (need_depths) HIP_TRY(c, sl.depths.ensure(n_slots_all + 1));
     if (c->opt.debug_varyings) HIP_TRY(c, c->dbg.ensure((size_t)D.n_entries + 1));
-    // the `ranges` region (uint2 units): every tile's (~start, end) and one more, then the tile-local depth sort's two lists of long tiles;
+    // the `ranges` region (uint2 units): every tile's range words (encode_tile_range) and one more, then the tile-local depth sort's two lists of long tiles;
     // the list parts are padded to whole uint2s plus one.  k_cull clears the ranges, the first list and the second list's count.
     const size_t range_words = 2 * (nt + 1), list_words = tile_depth_list_words(nt);
     auto uint2s = [](size_t words) { return (words + 1) / 2 + 1; };
     HIP_TRY(c, sl.ranges.ensure(range_words / 2 + 2 * uint2s(list_words)));
     b.n_zero_ranges = (uint32_t)(range_words + list_words + 1);
-    // the `ghist` region (u32): [counters][super-group sums][pair sort workspace][depth sort workspace]; each workspace has its zeroed part
-    // (group rows, digit totals) in front of its per-workgroup rows (written in full).  k_cull clears the head up to the end of the pair
-    // sort's zeroed part, and the depth sort's zeroed part.
-    const size_t counter_words = 16, n_super = (size_t)D.n_chunks / 256 + 1;
-    const size_t super_words = (2 * (size_t)kSuperStride + 1) * n_super;     // pair sums, visible sums (a cache line per word), exclusive pair prefix (k_totals)
-    const size_t rw_pair = radix_ws_words(cap, key_bits), rw_depth = depth_bits ? radix_ws_words(cap, depth_bits) : 0;
-    HIP_TRY(c, sl.ghist.ensure_roomy(counter_words + super_words + rw_pair + rw_depth + 16));
-    b.n_zero_head = (uint32_t)(counter_words + super_words + radix_ws_zero_words(cap, key_bits));
-    b.n_zero_depth = depth_bits ? (uint32_t)radix_ws_zero_words(cap, depth_bits) : 0u;
+    // the `ghist` region (u32): [FrameCounters][SuperSums][pair sort's RadixWs][depth sort's RadixWs] (gswt_frame_layout.h); a workspace has
+    // its zeroed part in front.  k_cull clears the head up to the end of the pair sort's zeroed part, and the depth sort's zeroed part.
+    const size_t counter_words = kFrameCounterWords, super_words = super_sums_of(D.n_chunks).words();
+    const RadixWs ws_pair = radix_ws_of(cap, key_bits), ws_depth = radix_ws_of(cap, depth_bits);       // (depth_bits 0: no passes, no words)
+    HIP_TRY(c, sl.ghist.ensure_roomy(counter_words + super_words + ws_pair.words() + ws_depth.words() + 16));
+    b.n_zero_head = (uint32_t)(counter_words + super_words + ws_pair.zero_words());
+    b.n_zero_depth = (uint32_t)ws_depth.zero_words();
     HIP_TRY(c, sl.keys_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.keys_b.ensure_roomy((size_t)cap + 1));
     HIP_TRY(c, sl.vals_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.vals_b.ensure_roomy((size_t)cap + 1));
     if (depth_order) { HIP_TRY(c, sl.aux_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.aux_b.ensure_roomy((size_t)cap + 1)); }
@@ -617,11 +615,11 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     b.rects = sl.rects.p; b.recs = sl.recs.p; b.depths = need_depths ? sl.depths.p : nullptr; b.col_f = sl.col_f.p; b.dbg = c->dbg.p;
     b.draw_culled = sl.draw_culled.p; b.cell_culled = sl.cell_culled.p;
     b.live_cnt = sl.live_cnt.p; b.live_cid = sl.live_cid.p; b.live_tab = sl.live_tab.p; b.block_sums = sl.block_sums.p;
-    b.counters = reinterpret_cast<unsigned long long*>(sl.ghist.p);
-    b.krange = reinterpret_cast<uint32_t*>(b.counters + 5);
-    b.super_sums = sl.ghist.p + counter_words;
+    b.ghist = sl.ghist.p;
+    b.counters = reinterpret_cast<FrameCounters*>(b.ghist);
+    b.super_sums = b.ghist + counter_words;
     b.radix_pair = b.super_sums + super_words;
-    b.radix_depth = b.radix_pair + rw_pair;
+    b.radix_depth = b.radix_pair + ws_pair.words();
     b.keys_a = sl.keys_a.p; b.keys_b = sl.keys_b.p; b.vals_a = sl.vals_a.p; b.vals_b = sl.vals_b.p; b.aux_a = sl.aux_a.p; b.aux_b = sl.aux_b.p;
     b.ranges = sl.ranges.p;
     b.long_tiles = reinterpret_cast<uint32_t*>(sl.ranges.p) + range_words;
@@ -642,7 +640,7 @@ static int emit_and_sort(gswt_ctx* c, const FrameSlot& sl, const Frame& f, const
 {
     hipStream_t s = sl.stream;
     const uint32_t n_launch = c->opt.debug_varyings ? 0u : sl.n_launch_eff;       // (the debug-varyings frame emits from every chunk)
-    const unsigned long long* const n_pairs = b.counters + 1;
+    const SortCount* const n_pairs = sort_count_of(b.counters);      // the pair count, refused while the frame is flagged for a re-run
     const uint32_t cap = b.pair_cap;
     if (sl.args.cfg.order_mode != GSWT_ORDER_DEPTH) {
         launch_emit(s, f, b, b.keys_a, nullptr, nullptr, n_launch);
@@ -658,9 +656,9 @@ static int emit_and_sort(gswt_ctx* c, const FrameSlot& sl, const Frame& f, const
                                b.long_tiles, b.counters);
         *sorted = vals;
     } else {
-        launch_emit(s, f, b, b.aux_a, b.keys_a, b.krange, n_launch);
+        launch_emit(s, f, b, b.aux_a, b.keys_a, b.krange(), n_launch);
         if (c->opt.timing >= 2) HIP_TRY(c, hipEventRecord(sl.ev[kEvEmitted], s));
-        const int wd = launch_sort(s, b.keys_a, b.vals_a, b.keys_b, b.vals_b, cap, n_pairs, 8 * (int)sl.depth_passes, b.radix_depth, nullptr, b.krange,
+        const int wd = launch_sort(s, b.keys_a, b.vals_a, b.keys_b, b.vals_b, cap, n_pairs, 8 * (int)sl.depth_passes, b.radix_depth, nullptr, b.krange(),
                                    b.aux_a, b.aux_b);
         // (the depth keys are dead now: keys_a serves as the other half of the tile-key ping-pong)
         uint32_t* const tiles_in = wd ? b.aux_b : b.aux_a;
@@ -748,7 +746,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
     sl.sorted_vals = vals; sl.sorted_final = false;
     if (c->opt.timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvSorted], s));
     if (c->opt.timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvRanges], s));
-    launch_composite(s, f, b, vals, out_rows, c->opt.composite, depth_order && !sl.depth_local ? b.krange : nullptr, sl.depth_passes, depth_order,
+    launch_composite(s, f, b, vals, out_rows, c->opt.composite, depth_order && !sl.depth_local ? b.krange() : nullptr, sl.depth_passes, depth_order,
                      c->opt.item_order != 0, c->opt.timing >= 1 ? ev[kEvCompositeBegin] : nullptr, c->opt.timing >= 1 ? ev[kEvCompositeEnd] : nullptr,
                      (int)a.cfg.out_format);
     c->last_n_tiles = (uint32_t)n_tiles;
@@ -762,7 +760,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
     HIP_TRY(c, hipGetLastError());
     // k_combine (the last kernel of the frame, or the last but k_pick_resolve) stores the result counters into the pinned host words itself; only a frame
     // without screen tiles has no such launch
-    if (n_tiles == 0 || !sl.hc_dev) HIP_TRY(c, hipMemcpyAsync(sl.hc, b.counters, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (n_tiles == 0 || !sl.hc_dev) HIP_TRY(c, hipMemcpyAsync(sl.hc, &b.counters->res, kFrameResultWords64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipEventRecord(ev[kEvDone], s));
     sl.timing_level = c->opt.timing;
     return GSWT_OK;
@@ -773,14 +771,14 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
 {
     for (int attempt = 0;; attempt++) {
         HIP_TRY(c, hipEventSynchronize(sl.ev[kEvDone]));
-        const unsigned long long P64 = sl.hc[1];
+        const unsigned long long P64 = sl.hc->n_pairs;
         if (P64 >= 0xFFFFFF00ull) return fail(c, GSWT_ERR_CAPACITY, "gswt_render: %llu pairs exceed 2^32", P64);
-        if (sl.hc[3] == 0 && P64 <= sl.cap) break;
+        if (sl.hc->rerun == 0 && P64 <= sl.cap) break;
         if (attempt >= 3) return fail(c, GSWT_ERR_CAPACITY, "gswt_render: pair capacity did not converge");      // (a short launch grid, a pair overflow and a depth-pass shortfall can each cost one re-run)
         if (P64 > sl.cap || sl.args.cfg.order_mode != GSWT_ORDER_DEPTH)
             c->pair_cap = std::max<uint32_t>(c->pair_cap, (uint32_t)std::min<uint64_t>(P64 + P64 / 2 + 4096, 0xFFFFFF00ull));
         if (sl.args.cfg.order_mode == GSWT_ORDER_DEPTH) {
-            const uint32_t need = (uint32_t)(sl.hc[2] & 0xFFFFFFFFull), max_len = (uint32_t)(sl.hc[2] >> 32);
+            const uint32_t need = sl.hc->depth_passes_needed, max_len = sl.hc->max_tile_len;
             if (!sl.depth_local && need > sl.depth_passes) { c->depth_passes = std::min<uint32_t>(need, 4u); c->depth_passes_low_run = 0; }
             // a re-run tile-local frame (pair overflow, short launch grid: lists of any length fit k_tile_depth_sort) keeps the same path;
             // gswt_debug_depth_stats reports at least one list past the LDS buffer (k_items may not have seen the whole frame's lengths yet
@@ -788,19 +786,19 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
             if (sl.depth_local) c->depth_max_tile_len = std::max<uint32_t>(std::max<uint32_t>(max_len, c->depth_max_tile_len), tile_depth_sort_cap() + 1u);
         }
         sl.full_grid = true;                                   // (whatever flagged it: the re-run covers the whole launch table)
-        c->live_hint = std::max<uint32_t>(c->live_hint, (uint32_t)std::min<unsigned long long>(sl.hc[4], 0xFFFFFFFFull));
+        c->live_hint = std::max<uint32_t>(c->live_hint, (uint32_t)std::min<unsigned long long>(sl.hc->live_longest, 0xFFFFFFFFull));
         int rc = enqueue_frame(c, sl);
         sl.full_grid = false;
         if (rc != GSWT_OK) return rc;
     }
-    c->live_hint = (uint32_t)std::min<unsigned long long>(sl.hc[4], 0xFFFFFFFFull);
-    const uint32_t P = (uint32_t)sl.hc[1];
+    c->live_hint = (uint32_t)std::min<unsigned long long>(sl.hc->live_longest, 0xFFFFFFFFull);
+    const uint32_t P = (uint32_t)sl.hc->n_pairs;
     sl.sorted_pairs = P; sl.sorted_final = true;
     // keep 25-50 % headroom over the running pair count without shrinking on every small dip
     if (!c->opt.fixed_pair_cap && (uint64_t)P + P / 4 > c->pair_cap) c->pair_cap = (uint32_t)std::min<uint64_t>((uint64_t)P + P / 2 + 4096, 0xFFFFFF00ull);
     if (sl.args.cfg.order_mode == GSWT_ORDER_DEPTH) {
-        const uint32_t need = std::min<uint32_t>(std::max<uint32_t>((uint32_t)(sl.hc[2] & 0xFFFFFFFFull), 1u), 4u);
-        c->depth_max_tile_len = (uint32_t)(sl.hc[2] >> 32);        // (every depth-ordered frame reports it: gswt_debug_depth_stats)
+        const uint32_t need = std::min<uint32_t>(std::max<uint32_t>(sl.hc->depth_passes_needed, 1u), 4u);
+        c->depth_max_tile_len = sl.hc->max_tile_len;       // (every depth-ordered frame reports it: gswt_debug_depth_stats)
         if (sl.depth_local) { /* the pass count is the kernel's own business there */ }
         else if (need < c->depth_passes && sl.depth_passes == c->depth_passes) {
             c->depth_passes_low_max = c->depth_passes_low_run ? std::max(c->depth_passes_low_max, need) : need;
@@ -822,7 +820,7 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
         HIP_TRY(c, hipEventElapsedTime(&t.ms_composite_kernel, ev[kEvCompositeBegin], ev[kEvCompositeEnd]));
         if (sl.pick_timed) HIP_TRY(c, hipEventElapsedTime(&t.ms_pick_resolve, ev[kEvPickBegin], ev[kEvPickEnd]));
     }
-    t.n_draws = c->sets[sl.set].n_draws; t.n_instanced = c->sets[sl.set].n_entries; t.n_visible = sl.hc[0]; t.n_pairs = P; t.n_tiles = (uint32_t)sl.n_tiles;
+    t.n_draws = c->sets[sl.set].n_draws; t.n_instanced = c->sets[sl.set].n_entries; t.n_visible = sl.hc->n_visible; t.n_pairs = P; t.n_tiles = (uint32_t)sl.n_tiles;
     return GSWT_OK;
 }
 
@@ -1020,41 +1018,67 @@ try {
     if (!c || !pair_sums || !visible_sums || n_super == 0 || !counters_out) return GSWT_ERR_BAD_ARG;
     hipSetDevice(c->device);
     DevBuf<uint32_t> buf;
-    const size_t S = kSuperStride, words = (2 * S + 1) * (size_t)n_super;
-    HIP_TRY(c, buf.ensure(words + 16));
-    unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(buf.p + words + (words & 1));
-    HIP_TRY(c, hipMemset(buf.p, 0, (words + 16) * 4));
-    HIP_TRY(c, hipMemcpy2D(buf.p, S * 4, pair_sums, 4, 4, n_super, hipMemcpyHostToDevice));                 // one word per cache line
-    HIP_TRY(c, hipMemcpy2D(buf.p + S * n_super, S * 4, visible_sums, 4, 4, n_super, hipMemcpyHostToDevice));
-    launch_totals(c->stream, buf.p, n_super, d_cnt, pair_cap);
+    DevBuf<FrameCounters> d_cnt;
+    const SuperSums ss{n_super};
+    HIP_TRY(c, buf.ensure(ss.words())); HIP_TRY(c, d_cnt.ensure(1));
+    HIP_TRY(c, hipMemset(buf.p, 0, ss.words() * 4));
+    HIP_TRY(c, hipMemset(d_cnt.p, 0, sizeof(FrameCounters)));
+    // one word per super-group, each at its place in the region (a cache line apart)
+    const size_t pitch = (size_t)(ss.pair_word(1) - ss.pair_word(0)) * 4;
+    HIP_TRY(c, hipMemcpy2D(buf.p + ss.pair_word(0), pitch, pair_sums, 4, 4, n_super, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy2D(buf.p + ss.visible_word(0), pitch, visible_sums, 4, 4, n_super, hipMemcpyHostToDevice));
+    launch_totals(c->stream, buf.p, ss, d_cnt.p, pair_cap);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(counters_out, d_cnt, 32, hipMemcpyDeviceToHost));
-    if (super_excl_out) HIP_TRY(c, hipMemcpy(super_excl_out, buf.p + 2 * S * (size_t)n_super, (size_t)n_super * 4, hipMemcpyDeviceToHost));
+    // (the hook's four words: the block's first four 64-bit words, up to the re-run flag)
+    static_assert(offsetof(FrameResult, rerun) + sizeof(unsigned long long) == 4 * sizeof(unsigned long long), "gswt_debug_totals' counters_out");
+    HIP_TRY(c, hipMemcpy(counters_out, &d_cnt.p->res, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (super_excl_out) HIP_TRY(c, hipMemcpy(super_excl_out, buf.p + ss.prefix_word(0), (size_t)n_super * 4, hipMemcpyDeviceToHost));
     return GSWT_OK;
 } GSWT_CATCH
+
+// launch_sort alone (gswt_debug_sort, gswt_debug_sort_ex; arguments as the latter's, checked there): the sort reads its count through the
+// SortCount view of a counter block staged as a frame's would be -- n pairs, flagged for a re-run when `refused` -- and, with krange
+// ({smallest, largest} key; null: none), the key range from the same block.
+static int debug_sort(gswt_ctx* c, uint32_t* keys, uint32_t* vals, uint32_t* aux, size_t n_cap, unsigned long long n, bool refused, int key_bits,
+                      const uint32_t* krange, uint32_t* ranges_out, size_t n_range_keys, int threads, int aux_form)
+{
+    hipSetDevice(c->device);
+    const uint32_t cap = (uint32_t)n_cap;
+    DevBuf<uint32_t> ka, kb, va, vb, xa, xb, ws;
+    DevBuf<uint2> rg;
+    DevBuf<FrameCounters> blk;
+    HIP_TRY(c, ka.ensure(n_cap + 4)); HIP_TRY(c, kb.ensure(n_cap + 4)); HIP_TRY(c, va.ensure(n_cap + 1)); HIP_TRY(c, vb.ensure(n_cap + 1));
+    if (aux) { HIP_TRY(c, xa.ensure(n_cap + 1)); HIP_TRY(c, xb.ensure(n_cap + 1)); }
+    if (ranges_out) { HIP_TRY(c, rg.ensure(n_range_keys + 1)); HIP_TRY(c, hipMemset(rg.p, 0, (n_range_keys + 1) * 8)); }
+    const size_t words = radix_ws_words(cap, key_bits);
+    HIP_TRY(c, ws.ensure(words)); HIP_TRY(c, blk.ensure(1));
+    HIP_TRY(c, hipMemset(ws.p, 0, words * 4));
+    FrameCounters h{};
+    h.res.n_pairs = n; h.res.rerun = refused ? 1ull : 0ull;
+    if (krange) { h.krange[0] = krange_min_word(krange[0]); h.krange[1] = krange[1]; }       // as k_emit<DEPTH>'s atomicMax pair leaves it
+    HIP_TRY(c, hipMemcpy(blk.p, &h, sizeof(h), hipMemcpyHostToDevice));
+    for (uint32_t* p : {ka.p, kb.p}) HIP_TRY(c, hipMemcpy(p, keys, n_cap * 4, hipMemcpyHostToDevice));
+    for (uint32_t* p : {va.p, vb.p}) HIP_TRY(c, hipMemcpy(p, vals, n_cap * 4, hipMemcpyHostToDevice));
+    if (aux) for (uint32_t* p : {xa.p, xb.p}) HIP_TRY(c, hipMemcpy(p, aux, n_cap * 4, hipMemcpyHostToDevice));
+    const int where = launch_sort(c->stream, ka.p, va.p, kb.p, vb.p, cap, sort_count_of(blk.p), key_bits, ws.p, ranges_out ? rg.p : nullptr,
+                                  krange ? blk.p->krange : nullptr, aux ? xa.p : nullptr, aux ? xb.p : nullptr, threads, aux_form);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!ranges_out) HIP_TRY(c, hipMemcpy(keys, where ? kb.p : ka.p, n_cap * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(vals, where ? vb.p : va.p, n_cap * 4, hipMemcpyDeviceToHost));
+    if (aux) HIP_TRY(c, hipMemcpy(aux, where ? xb.p : xa.p, n_cap * 4, hipMemcpyDeviceToHost));
+    if (ranges_out) {
+        HIP_TRY(c, hipMemcpy(ranges_out, rg.p, n_range_keys * 8, hipMemcpyDeviceToHost));
+        for (size_t t = 0; t < n_range_keys; t++) decode_tile_range(ranges_out[2 * t], ranges_out[2 * t + 1], ranges_out[2 * t], ranges_out[2 * t + 1]);
+    }
+    return GSWT_OK;
+}
 
 int gswt_debug_sort(gswt_ctx* c, uint32_t* keys, uint32_t* vals, size_t n, int key_bits)
 try {
     if (!c || !keys || !vals || n == 0 || n >= 0xFFFFFF00ull || key_bits < 1 || key_bits > 32) return GSWT_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    const uint32_t cap = (uint32_t)n;
-    DevBuf<uint32_t> ka, kb, va, vb, ws;
-    HIP_TRY(c, ka.ensure(n + 4)); HIP_TRY(c, kb.ensure(n + 4)); HIP_TRY(c, va.ensure(n + 1)); HIP_TRY(c, vb.ensure(n + 1));
-    const size_t words = radix_ws_words(cap, key_bits) + 16;
-    HIP_TRY(c, ws.ensure(words));
-    HIP_TRY(c, hipMemset(ws.p, 0, words * 4));
-    // the item count lives in device memory, as in a frame: {n, -, overflow flag = 0} in front of the histograms
-    unsigned long long hn[4] = {(unsigned long long)n, 0ull, 0ull, 0ull};
-    HIP_TRY(c, hipMemcpy(ws.p, hn, 32, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(ka.p, keys, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(va.p, vals, n * 4, hipMemcpyHostToDevice));
-    const int where = launch_sort(c->stream, ka.p, va.p, kb.p, vb.p, cap, reinterpret_cast<const unsigned long long*>(ws.p), key_bits, ws.p + 16);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(keys, where ? kb.p : ka.p, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(vals, where ? vb.p : va.p, n * 4, hipMemcpyDeviceToHost));
-    return GSWT_OK;
+    return debug_sort(c, keys, vals, nullptr, n, n, false, key_bits, nullptr, nullptr, 0, 0, 0);
 } GSWT_CATCH
 
 int gswt_debug_sort_ex(gswt_ctx* c, uint32_t* keys, uint32_t* vals, uint32_t* aux, size_t n_cap, unsigned long long n, int overflow, int key_bits,
@@ -1071,36 +1095,8 @@ try {
         if (ranges_out && keys[i] >= n_range_keys) return fail(c, GSWT_ERR_BAD_ARG, "gswt_debug_sort_ex: key %u at %zu is outside the range table", keys[i], i);
         if (use_krange && (keys[i] < krange_min || keys[i] > krange_max)) return fail(c, GSWT_ERR_BAD_ARG, "gswt_debug_sort_ex: key %u at %zu is outside the key range", keys[i], i);
     }
-    hipSetDevice(c->device);
-    const uint32_t cap = (uint32_t)n_cap;
-    DevBuf<uint32_t> ka, kb, va, vb, xa, xb, ws;
-    DevBuf<uint2> rg;
-    HIP_TRY(c, ka.ensure(n_cap + 4)); HIP_TRY(c, kb.ensure(n_cap + 4)); HIP_TRY(c, va.ensure(n_cap + 1)); HIP_TRY(c, vb.ensure(n_cap + 1));
-    if (aux) { HIP_TRY(c, xa.ensure(n_cap + 1)); HIP_TRY(c, xb.ensure(n_cap + 1)); }
-    if (ranges_out) { HIP_TRY(c, rg.ensure(n_range_keys + 1)); HIP_TRY(c, hipMemset(rg.p, 0, (n_range_keys + 1) * 8)); }
-    const size_t words = radix_ws_words(cap, key_bits) + 16;
-    HIP_TRY(c, ws.ensure(words));
-    HIP_TRY(c, hipMemset(ws.p, 0, words * 4));
-    // the frame's counter block in front of the histograms: {n, -, overflow flag} as the kernels' n_ptr sees it, the key range at 64-bit word 5
-    unsigned long long hn[8] = {n, 0ull, overflow ? 1ull : 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
-    const uint32_t kr[2] = {~krange_min, krange_max};
-    memcpy(&hn[5], kr, 8);
-    HIP_TRY(c, hipMemcpy(ws.p, hn, 64, hipMemcpyHostToDevice));
-    for (uint32_t* p : {ka.p, kb.p}) HIP_TRY(c, hipMemcpy(p, keys, n_cap * 4, hipMemcpyHostToDevice));
-    for (uint32_t* p : {va.p, vb.p}) HIP_TRY(c, hipMemcpy(p, vals, n_cap * 4, hipMemcpyHostToDevice));
-    if (aux) for (uint32_t* p : {xa.p, xb.p}) HIP_TRY(c, hipMemcpy(p, aux, n_cap * 4, hipMemcpyHostToDevice));
-    const int where = launch_sort(c->stream, ka.p, va.p, kb.p, vb.p, cap, reinterpret_cast<const unsigned long long*>(ws.p), key_bits, ws.p + 16,
-                                  ranges_out ? rg.p : nullptr, use_krange ? ws.p + 10 : nullptr, aux ? xa.p : nullptr, aux ? xb.p : nullptr, threads, aux_form);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (!ranges_out) HIP_TRY(c, hipMemcpy(keys, where ? kb.p : ka.p, n_cap * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(vals, where ? vb.p : va.p, n_cap * 4, hipMemcpyDeviceToHost));
-    if (aux) HIP_TRY(c, hipMemcpy(aux, where ? xb.p : xa.p, n_cap * 4, hipMemcpyDeviceToHost));
-    if (ranges_out) {
-        HIP_TRY(c, hipMemcpy(ranges_out, rg.p, n_range_keys * 8, hipMemcpyDeviceToHost));
-        for (size_t t = 0; t < n_range_keys; t++) ranges_out[2 * t] = ranges_out[2 * t + 1] ? ~ranges_out[2 * t] : 0u;
-    }
-    return GSWT_OK;
+    const uint32_t kr[2] = {krange_min, krange_max};
+    return debug_sort(c, keys, vals, aux, n_cap, n, overflow != 0, key_bits, use_krange ? kr : nullptr, ranges_out, n_range_keys, threads, aux_form);
 } GSWT_CATCH
 
 // Test hook: k_tile_depth_sort alone.  lens[t] = length of screen tile t's slice of the (tile-sorted) pair list, the slices back to back;
@@ -1112,27 +1108,27 @@ try {
     hipSetDevice(c->device);
     std::vector<uint2> rg(n_tiles);
     size_t at = 0;
-    for (size_t t = 0; t < n_tiles; t++) {                 // the device's encoding: (~start, end), (0, 0) for a tile without pairs
-        rg[t] = lens[t] ? make_uint2(~(uint32_t)at, (uint32_t)(at + lens[t])) : make_uint2(0u, 0u);
+    for (size_t t = 0; t < n_tiles; t++) {                 // the range words the last sort pass would leave
+        encode_tile_range((uint32_t)at, (uint32_t)(at + lens[t]), rg[t].x, rg[t].y);
         at += lens[t];
     }
     if (at != n) return fail(c, GSWT_ERR_BAD_ARG, "gswt_debug_tile_depth_sort: the lengths sum to %zu, not %zu", at, n);
-    DevBuf<uint2> d_rg; DevBuf<uint32_t> d_vals, d_keys, d_vals2, d_keys2, d_long; DevBuf<unsigned long long> d_cnt;
+    DevBuf<uint2> d_rg; DevBuf<uint32_t> d_vals, d_keys, d_vals2, d_keys2, d_long; DevBuf<FrameCounters> d_cnt;
     HIP_TRY(c, d_rg.ensure(n_tiles)); HIP_TRY(c, d_vals.ensure(n + 1)); HIP_TRY(c, d_keys.ensure(n + 1)); HIP_TRY(c, d_vals2.ensure(n + 1)); HIP_TRY(c, d_keys2.ensure(n + 1));
     const size_t long_words = 2 * tile_depth_list_words(n_tiles);
-    HIP_TRY(c, d_long.ensure(long_words)); HIP_TRY(c, d_cnt.ensure(8));
+    HIP_TRY(c, d_long.ensure(long_words)); HIP_TRY(c, d_cnt.ensure(1));
     HIP_TRY(c, hipMemcpy(d_rg.p, rg.data(), n_tiles * 8, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d_vals.p, vals, n * 4, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d_keys.p, dkeys, n * 4, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(d_long.p, 0, long_words * 4));
-    HIP_TRY(c, hipMemset(d_cnt.p, 0, 64));
+    HIP_TRY(c, hipMemset(d_cnt.p, 0, sizeof(FrameCounters)));
     launch_tile_depth_sort(c->stream, d_rg.p, d_vals.p, d_keys.p, d_vals2.p, d_keys2.p, (int)n_tiles, d_long.p, d_cnt.p);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    unsigned long long cnt[4];
-    HIP_TRY(c, hipMemcpy(cnt, d_cnt.p, 32, hipMemcpyDeviceToHost));
+    FrameResult res;
+    HIP_TRY(c, hipMemcpy(&res, &d_cnt.p->res, sizeof(res), hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(vals, d_vals.p, n * 4, hipMemcpyDeviceToHost));
-    if (flagged_out) *flagged_out = cnt[3] != 0ull;
+    if (flagged_out) *flagged_out = res.rerun != 0ull;
     return GSWT_OK;
 } GSWT_CATCH
 
@@ -1177,8 +1173,8 @@ try {
     hipSetDevice(c->device);
     HIP_TRY(c, sync_all(c));
     HIP_TRY(c, hipMemcpy(out, c->slots[c->last_slot].ranges.p, (size_t)c->last_n_tiles * 8, hipMemcpyDeviceToHost));
-    for (uint32_t t = 0; t < c->last_n_tiles; t++)         // the device keeps (~start, end), (0, 0) for a tile without pairs
-        out[2 * (size_t)t] = out[2 * (size_t)t + 1] ? ~out[2 * (size_t)t] : 0u;
+    for (uint32_t t = 0; t < c->last_n_tiles; t++)         // the device keeps range words; (0, 0) for a tile without pairs
+        decode_tile_range(out[2 * (size_t)t], out[2 * (size_t)t + 1], out[2 * (size_t)t], out[2 * (size_t)t + 1]);
     return GSWT_OK;
 } GSWT_CATCH
 

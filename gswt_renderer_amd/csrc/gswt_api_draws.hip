@@ -342,8 +342,7 @@ static int match_groups(gswt_ctx* c, DrawSet& D, const std::vector<int>& sources
         for (uint32_t off = 0; off < jobs[q].len; off += 1024u) h_cblocks[P.n_cblocks++] = make_uint2((uint32_t)q, off);
     for (size_t q = 0; q < P.n_segs; q++)
         for (uint32_t off = 0; off < segs[q].len; off += 1024u) h_blocks[P.n_blocks++] = make_uint2((uint32_t)q, off);
-    memset(D.hp<uint8_t>(D.off_n64), 0, 64);              // the sort reads its item count and an overflow word 16 bytes behind it
-    *D.hp<unsigned long long>(D.off_n64) = (uint32_t)build_total;
+    *D.hp<SortCount>(D.off_count) = sort_count((uint32_t)build_total);       // the sort's item count, as its kernels read it
     P.total = total; P.build_total = build_total;
     return GSWT_OK;
 }
@@ -468,7 +467,7 @@ try {
         uint32_t* radix = w + 4 * (size_t)n_total;
         HIP_TRY(c, hipMemsetAsync(radix, 0, (radix_words + 16) * 4, s));
         launch_merge_build(s, D.dp<MergeSeg>(D.off_segs), (uint32_t)P.n_segs, D.dp<uint2>(D.off_blocks), (uint32_t)P.n_blocks, D.dp<MergeGroup>(D.off_groups),
-                           (uint32_t)P.n_build, c->raw_depth.p, n_total, D.dp<unsigned long long>(D.off_n64), w, w + n_total, w + 2 * (size_t)n_total,
+                           (uint32_t)P.n_build, c->raw_depth.p, n_total, D.dp<SortCount>(D.off_count), w, w + n_total, w + 2 * (size_t)n_total,
                            w + 3 * (size_t)n_total, radix, gbits, D.merged_list.p, D.merged_map.p);
     }
     GSWT_TRY(record_upload(c, D));

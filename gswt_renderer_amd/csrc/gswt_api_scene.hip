@@ -207,7 +207,8 @@ try {
     const size_t seg_words = segs.size() * sizeof(MergeSeg) / 4, grp_words = groups.size() * sizeof(MergeGroup) / 4;
     const size_t blk_words = 2 * blocks.size(), list_words = nl * sizeof(ListRef) / 4;
     HIP_TRY(c, tabs.ensure(2 * n_lt + seg_words + grp_words + blk_words + list_words));
-    HIP_TRY(c, sortbuf.ensure(4 * n_total + 16 + radix_words + 16));
+    const size_t count_words = 2 * sizeof(SortCount) / 4;       // the sort's count record, on a 64-byte line of its own
+    HIP_TRY(c, sortbuf.ensure(4 * n_total + count_words + radix_words + 16));
     HIP_TRY(c, bounds_d.ensure(8));
     HIP_TRY(c, c->tex.ensure(2 * n_splats));
     HIP_TRY(c, c->raw_depth.ensure(nv * n_splats + 1));
@@ -236,14 +237,14 @@ try {
     uint32_t* const va = ka + n_total;
     uint32_t* const kb = va + n_total;
     uint32_t* const vb = kb + n_total;
-    uint32_t* const hdr = vb + n_total;               // the sort's item count {n, -, overflow word = 0, -} (read only)
-    uint32_t* const ws = hdr + 16;
-    const unsigned long long n64[4] = {(unsigned long long)n_total, 0ull, 0ull, 0ull};
-    HIP_TRY(c, hipMemcpyAsync(hdr, n64, sizeof(n64), hipMemcpyHostToDevice, s));
+    SortCount* const d_count = reinterpret_cast<SortCount*>(vb + n_total);      // the sort's item count (read only)
+    uint32_t* const ws = vb + n_total + count_words;
+    const SortCount n_items = sort_count(n_total);
+    HIP_TRY(c, hipMemcpyAsync(d_count, &n_items, sizeof(n_items), hipMemcpyHostToDevice, s));
     for (size_t v = 0; v < nv; v++) {
         HIP_TRY(c, hipMemsetAsync(ws, 0, radix_words * 4, s));
         const int where = launch_scene_sort(s, d_segs + seg_first[v], d_blocks + blk_first[v], (uint32_t)(blk_first[v + 1] - blk_first[v]),
-                                            d_groups + v * n_lt, c->raw_depth.p, (uint32_t)n_total, reinterpret_cast<const unsigned long long*>(hdr),
+                                            d_groups + v * n_lt, c->raw_depth.p, (uint32_t)n_total, d_count,
                                             ka, va, kb, vb, ws, gbits);
         launch_scene_scatter(s, d_segs + seg_first[v], (uint32_t)(seg_first[v + 1] - seg_first[v]), d_groups + v * n_lt, where ? kb : ka,
                              where ? vb : va, (uint32_t)n_total, c->static_list.p, (uint32_t)arena_n);

@@ -119,7 +119,7 @@ struct DrawSet {
     HostBuf<uint8_t> h_blob;
     DevBuf<uint8_t> d_blob;
     size_t blob_bytes = 0;
-    size_t off_draws = 0, off_xcd = 0, off_groups = 0, off_jobs = 0, off_remap = 0, off_segs = 0, off_blocks = 0, off_cblocks = 0, off_n64 = 0;
+    size_t off_draws = 0, off_xcd = 0, off_groups = 0, off_jobs = 0, off_remap = 0, off_segs = 0, off_blocks = 0, off_cblocks = 0, off_count = 0;
     template <typename T> T* hp(size_t off) { return reinterpret_cast<T*>(h_blob.p + off); }
     template <typename T> T* dp(size_t off) { return reinterpret_cast<T*>(d_blob.p + off); }
     hipError_t plan(size_t n_draws, size_t n_groups, size_t n_members, size_t total_entries)
@@ -130,7 +130,7 @@ struct DrawSet {
         off_draws = take((n_draws + 1) * sizeof(DrawDev)); off_xcd = take((n_draws + 1) * 4);
         off_groups = take((n_groups + 1) * sizeof(MergeGroup)); off_jobs = take((n_groups + 1) * sizeof(MergeCopy));
         off_remap = take((n_members + 1) * sizeof(uint2)); off_segs = take((2 * n_members + 1) * sizeof(MergeSeg));
-        off_blocks = take(n_blk * sizeof(uint2)); off_cblocks = take(n_blk * sizeof(uint2)); off_n64 = take(64);
+        off_blocks = take(n_blk * sizeof(uint2)); off_cblocks = take(n_blk * sizeof(uint2)); off_count = take(sizeof(SortCount));
         blob_bytes = o;
         hipError_t e = o <= h_blob.cap ? hipSuccess : h_blob.ensure(2 * o);      // (grows to twice the request, like DevBuf::ensure_roomy)
         if (e != hipSuccess) return e;
@@ -218,8 +218,8 @@ struct FrameSlot {
     hipEvent_t ev_gather = nullptr;        // recorded on the ctx stream behind the frame's gather + re-assembly (gswt_render_gather / gswt_group_render_gather)
     bool gather_recorded = false;
     unsigned long long seq = 0;            // submission order of the frame in this slot
-    unsigned long long* hc = nullptr;      // pinned host: [0] visible [1] pairs [2] scratch [3] overflow ... [7] staging
-    unsigned long long* hc_dev = nullptr;  // the same words as the device sees them (k_combine writes [0..3] at the end of a frame)
+    FrameResult* hc = nullptr;             // pinned host: the result part of the frame's counter block (gswt_frame_layout.h)
+    FrameResult* hc_dev = nullptr;         // the same words as the device sees them (k_combine writes them at the end of a frame)
     bool pending = false;                  // submitted through gswt_render_async, ticket not yet handed back by gswt_render_wait
     bool collected = false;                // finish_frame already ran for the pending frame (fence / gswt_set_draws*): its status and
     int collected_rc = 0;                  // timings wait here for gswt_render_wait

@@ -7,6 +7,15 @@
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
+// the frame's bookkeeping layouts (counter block, sort count and workspace, super-group sums, live table, tile ranges): free of HIP,
+// __host__ __device__ here.  (GSWT_HD is left as it was found: gswt_device_fn.h sets it for host/gswt_math.h and its like.)
+#ifndef GSWT_HD
+#define GSWT_HD __host__ __device__
+#include "gswt_frame_layout.h"
+#undef GSWT_HD
+#else
+#include "gswt_frame_layout.h"
+#endif
 
 namespace gswt {
 
@@ -277,10 +286,6 @@ struct GraphNodeRec {
                n_bytes == o.n_bytes && memcmp(args, o.args, n_bytes) == 0;
     }
 };
-// k_project's two-level sums: one word per super-group (256 chunks) for the pairs and one for the visible splats, each on a cache line of its
-// own (16 words apart).  Device-scope atomics on one 64-byte line retire at ~10 ns each whichever XCD they come from (measured: 43 k atomics
-// on 4 lines = +125 us), and side by side the 64 super-group words of c3 were 4 + 4 lines taking 2.7 k atomics each.
-constexpr uint32_t kSuperStride = 16;
 constexpr uint32_t kGraphMaxNodes = 32;          // reference order: 10-12 kernels per frame; GSWT_ORDER_DEPTH: 19-23
 struct GraphRec {
     GraphNodeRec nodes[kGraphMaxNodes];
@@ -328,6 +333,7 @@ bool kernel_events_enabled();
     } while (0)
 
 // ---- host side: what one frame's kernels read and write (gswt_api.hip: plan_frame_buffers) ------------------------------------------
+// The layouts of the bookkeeping regions (counters, super_sums, live_cnt, radix_*, ranges) are gswt_frame_layout.h's.
 struct FrameBufs {
     // inputs: the frame's draw set, the scene, the caller's images (bg_rgba / bg_depth null: none) and the slot's pinned result words
     const DrawDev* draws;
@@ -343,16 +349,18 @@ struct FrameBufs {
     const float4* bg_rgba; const float* bg_depth; float4* out;
     float* out_depth;                          // the frame's depth image (f32, the colour's geometry); null: none (gswt_render_depth)
     uint4* out_pick;                           // the frame's pick image (gswt_pick records, the colour's geometry); null: none (gswt_render_pick)
-    unsigned long long* host_counters;         // as the device sees them (null: copied behind the frame)
+    FrameResult* host_counters;                // as the device sees them (null: copied behind the frame)
     // the sizes the buffers were planned for
     uint32_t n_chunks, n_cells, n_tiles, pair_cap, seg;
     // per slot (= composite order), per draw, per map cell (the band cull), per chunk
     uint2* rects; Rec* recs; float4* col_f; Varyings* dbg;
     float* depths;                             // null unless the frame is depth-tested, depth-ordered or writes its depth or pick image
     uint32_t *draw_culled, *cell_culled, *live_cnt, *live_cid, *block_sums; uint4* live_tab;
-    // the `ghist` region: counters (krange = counters[5], k_emit<DEPTH>), k_project's super-group sums, the two sorts' radix workspaces
-    unsigned long long* counters;
-    uint32_t *krange, *super_sums, *radix_pair, *radix_depth;
+    // the `ghist` region: the counter block, k_project's super-group sums (SuperSums of n_chunks), the two sorts' radix workspaces (RadixWs)
+    uint32_t* ghist;                           // the region's first word: where k_cull's clear of n_zero_head words starts
+    FrameCounters* counters;
+    uint32_t* krange() const { return counters->krange; }      // the depth key range (k_emit<DEPTH>); address arithmetic on a device pointer
+    uint32_t *super_sums, *radix_pair, *radix_depth;
     // per pair: tile keys, slots, and the depth order's tile ids / depth bits
     uint32_t *keys_a, *keys_b, *vals_a, *vals_b, *aux_a, *aux_b;
     // the `ranges` region: per tile (~start, end), the tile-local depth sort's lists of long tiles
@@ -369,12 +377,12 @@ struct FrameBufs {
 void launch_chunk_tabs(hipStream_t s, const DrawDev* draws, const uint32_t* xcd_first, uint32_t n_draws, uint2* chunk_tab, uint2* chunk_tab_xcd,
                        const uint64_t per_xcd[8], uint64_t longest);
 void launch_merge_build(hipStream_t s, const MergeSeg* segs, uint32_t n_segs, const uint2* blocks, uint32_t n_blocks, MergeGroup* groups, uint32_t n_groups,
-                        const int32_t* raw, uint32_t n_total, const unsigned long long* n_total_dev, uint32_t* ka, uint32_t* va,
+                        const int32_t* raw, uint32_t n_total, const SortCount* n_total_dev, uint32_t* ka, uint32_t* va,
                         uint32_t* kb, uint32_t* vb, uint32_t* radix_ws, int group_bits, uint32_t* merged_list, uint32_t* merged_map);
 // Base lists of one presort view: the k_mg_* keys of gswt_upload_scene_rows' groups (one per (lod, tile)) and the stable radix sort;
 // returns launch_sort's 0 / 1 (sorted keys / vals in ka, va or kb, vb).  Arguments as launch_merge_build.
 int launch_scene_sort(hipStream_t s, const MergeSeg* segs, const uint2* blocks, uint32_t n_blocks, MergeGroup* groups, const int32_t* raw,
-                      uint32_t n_total, const unsigned long long* n_total_dev, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb,
+                      uint32_t n_total, const SortCount* n_total_dev, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb,
                       uint32_t* radix_ws, int group_bits);
 // gswt_scene.hip.  bounds: 8 words, {INT_MAX x3, INT_MIN x3, 0, 0} on entry (k_scene_tex).
 void launch_scene_tex(hipStream_t s, const uint4* rows, uint32_t n, uint4* tex, int32_t* bounds);
@@ -401,23 +409,24 @@ void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* ke
 // (gswt_pick records; then `vals` is also what k_pick_resolve reads behind the compositors).
 void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
                       uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format);
-void launch_totals(hipStream_t s, uint32_t* super_sums, uint32_t n_super, unsigned long long* counters, uint32_t pair_cap);
+void launch_totals(hipStream_t s, uint32_t* super_sums, SuperSums ss, FrameCounters* counters, uint32_t pair_cap);
 
 // LSD radix sort of (keys, vals) on key bits [0, key_bits), ping-pong between the a and b buffers; returns 0 if the result is in a, 1 if in b.
-// The item count is read on the device (*n_ptr), grids are sized for n_cap.  ws: radix_ws_words(n_cap, key_bits) words whose first
-// radix_ws_zero_words(n_cap, key_bits) are zero on entry.  ranges (zero on entry): the last pass also writes every key's (~start, end);
+// The item count is read on the device (count: a SortCount record, a frame's own through sort_count_of), grids are sized for n_cap.  ws: the
+// RadixWs of (n_cap, key_bits) in gswt_frame_layout.h -- radix_ws_words words whose first radix_ws_zero_words are zero on entry.  ranges
+// (zero on entry): the last pass also writes every key's range words (encode_tile_range);
 // krange: the key range the passes cover (depth keys); aux: a payload carried with the vals.  threads_override (256 / 512) and
 // aux_override (1 / 2) replace the workgroup width and payload form the capacity selects (0: they stand; gswt_debug_sort_ex).
-size_t radix_ws_words(uint32_t n_cap, int key_bits);
-size_t radix_ws_zero_words(uint32_t n_cap, int key_bits);
+inline size_t radix_ws_words(uint32_t n_cap, int key_bits) { return radix_ws_of(n_cap, key_bits).words(); }
+inline size_t radix_ws_zero_words(uint32_t n_cap, int key_bits) { return radix_ws_of(n_cap, key_bits).zero_words(); }
 int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n_cap,
-                const unsigned long long* n_ptr, int key_bits, uint32_t* ws, uint2* ranges = nullptr, const uint32_t* krange = nullptr,
+                const SortCount* count, int key_bits, uint32_t* ws, uint2* ranges = nullptr, const uint32_t* krange = nullptr,
                 uint32_t* aux_a = nullptr, uint32_t* aux_b = nullptr, int threads_override = 0, int aux_override = 0);
 
 // GSWT_ORDER_DEPTH, tile-local path: depth-sorts every tile's slice of the tile-sorted list in place.  long_list: two lists of tiles, each
 // tile_depth_list_words(n_tiles) words ([0] count, [1 .. n_tiles] tiles), back to back; both counts zero on entry.
 void launch_tile_depth_sort(hipStream_t s, const uint2* ranges, uint32_t* vals, uint32_t* dkeys, uint32_t* vals_scratch, uint32_t* dkeys_scratch, int n_tiles,
-                            uint32_t* long_list, unsigned long long* counters);
+                            uint32_t* long_list, FrameCounters* counters);
 inline size_t tile_depth_list_words(size_t n_tiles) { return n_tiles + 1; }
 uint32_t tile_depth_sort_cap();
 

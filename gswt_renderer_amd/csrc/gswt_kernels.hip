@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void k_cull(const Frame f, const DrawDev* __re
         }
     }
     __syncthreads();
-    if (threadIdx.x < 8u && s_cnt[threadIdx.x] != 0u) s_base[threadIdx.x] = atomicAdd(&live_cnt[threadIdx.x * kSuperStride], s_cnt[threadIdx.x]);      // (a cache line per XCD's count: gswt_device.h)
+    if (threadIdx.x < 8u && s_cnt[threadIdx.x] != 0u) s_base[threadIdx.x] = atomicAdd(&live_cnt[live_count_word(threadIdx.x)], s_cnt[threadIdx.x]);      // (a cache line per XCD's count: gswt_frame_layout.h)
     __syncthreads();
     if (live) {
         live_tab[(size_t)(s_base[x] + rank) * 8u + x] = e;
@@ -1014,7 +1014,7 @@ __global__ __launch_bounds__(256) void k_project(
         if (ct.y == 0xFFFFFFFFu) return;    // padding of a short per-XCD list
     } else {
         const uint32_t x = blockIdx.x & 7u, k = blockIdx.x >> 3;
-        if (k >= live_cnt[x * kSuperStride]) return;
+        if (k >= live_cnt[live_count_word(x)]) return;
         const uint4 lt = live_tab[(size_t)k * 8u + x];
         ct = make_uint2(lt.x, lt.y);
         list_top = lt.z; list_cnt = lt.w;
@@ -1116,38 +1116,40 @@ __global__ __launch_bounds__(256) void k_project(
     if (tid == 0) {
         block_sums[cid] = bsum;
         // two-level sums, spread over n_chunks / 256 addresses (a single hot counter serialises the whole grid);
-        // k_totals folds them into counters[0] (visible splats) and counters[1] (pairs)
-        if (bsum) atomicAdd(&super_sums[(cid >> 8) * kSuperStride], bsum);
+        // k_totals folds them into the frame's visible-splat and pair counts
+        const SuperSums ss{n_super};
+        if (bsum) atomicAdd(&super_sums[ss.pair_word(super_of_chunk(cid))], bsum);
         uint32_t v = s_wvis[0] + s_wvis[1] + s_wvis[2] + s_wvis[3];
-        if (v) atomicAdd(&super_sums[(n_super + (cid >> 8)) * kSuperStride], v);
+        if (v) atomicAdd(&super_sums[ss.visible_word(super_of_chunk(cid))], v);
     }
     GSWT_TR(6, GSWT_NOW())
 }
 
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, uint32_t* total);
 
-// counters[0] = visible splats, counters[1] = pairs; super_excl[j] = pairs of all chunks before super-group j (exclusive
-// scan of the pair half of super_sums), so that k_emit reads one word instead of summing up to n_chunks / 256 of them
+// The frame's visible-splat and pair counts (FrameCounters); super_excl[j] = pairs of all chunks before super-group j (exclusive
+// scan of the pair half of super_sums: SuperSums' prefix words), so that k_emit reads one word instead of summing up to n_chunks / 256 of them
 // (c5: 1 430 per workgroup).  Single workgroup.  (Folding it into k_emit -- every workgroup sums the super-group counts
 // in front of it, workgroup 0 leaves the totals -- was measured: k_emit +6 us for the 4.6 us saved, 4015 -> 3881 frames/s.)
 __global__ __launch_bounds__(256) void k_totals(const uint32_t* __restrict__ super_sums, uint32_t n_super,
-                                                unsigned long long* __restrict__ counters, uint32_t* __restrict__ super_excl, uint32_t pair_cap,
+                                                FrameCounters* __restrict__ counters, uint32_t* __restrict__ super_excl, uint32_t pair_cap,
                                                 uint32_t* __restrict__ live_cnt, uint32_t launched_per_xcd)
 {
+    const SuperSums ss{n_super};
     // k_project is done with this frame's live-chunk counts: cleared here for the slot's next frame (k_cull both clears
     // buffers and adds to these counters, so it cannot clear them itself)
     if (live_cnt && threadIdx.x < 64u) {
-        // the longest of the eight live lists: the host sizes the next frames' launch grids by it (counters[4]); a frame whose grid was cut
+        // the longest of the eight live lists: the host sizes the next frames' launch grids by it (live_longest); a frame whose grid was cut
         // shorter than its own lists has chunks that nobody projected: flagged, the host re-runs it with the full grid (gswt_api.hip, live_hint)
-        uint32_t v = threadIdx.x < 8u ? live_cnt[threadIdx.x * kSuperStride] : 0u;
-        if (threadIdx.x < 8u) {
-            live_cnt[(8u + threadIdx.x) * kSuperStride] = v;      // (k_emit runs behind this kernel and walks the same table)
-            live_cnt[threadIdx.x * kSuperStride] = 0u;
+        uint32_t v = threadIdx.x < kLiveLists ? live_cnt[live_count_word(threadIdx.x)] : 0u;
+        if (threadIdx.x < kLiveLists) {
+            live_cnt[live_copy_word(threadIdx.x)] = v;            // (k_emit runs behind this kernel and walks the same table)
+            live_cnt[live_count_word(threadIdx.x)] = 0u;
         }
         for (int o = 4; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
         if (threadIdx.x == 0u) {
-            counters[4] = v;
-            if (v > launched_per_xcd) counters[3] = 1ull;
+            counters->res.live_longest = v;
+            if (v > launched_per_xcd) counters->res.rerun = 1ull;
         }
     }
     __shared__ unsigned long long s_v[4];
@@ -1164,7 +1166,7 @@ __global__ __launch_bounds__(256) void k_totals(const uint32_t* __restrict__ sup
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const uint32_t idx = min(i + (uint32_t)k, n_super - 1u);              // clamped, unmasked loads
-            const uint32_t pv = super_sums[idx * kSuperStride], vv = super_sums[(n_super + idx) * kSuperStride];
+            const uint32_t pv = super_sums[ss.pair_word(idx)], vv = super_sums[ss.visible_word(idx)];
             p[k] = i + k < n_super ? pv : 0u;
             v += i + k < n_super ? vv : 0u;
             sum += p[k];
@@ -1186,8 +1188,8 @@ __global__ __launch_bounds__(256) void k_totals(const uint32_t* __restrict__ sup
     if ((threadIdx.x & 63u) == 0) s_v[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
-        counters[1] = carry; counters[0] = s_v[0] + s_v[1] + s_v[2] + s_v[3];
-        if (carry > (unsigned long long)pair_cap) counters[3] = 1ull;       // pair buffers too small: the host re-runs the frame
+        counters->res.n_pairs = carry; counters->res.n_visible = s_v[0] + s_v[1] + s_v[2] + s_v[3];
+        if (carry > (unsigned long long)pair_cap) counters->res.rerun = 1ull;       // pair buffers too small: the host re-runs the frame
     }
 }
 
@@ -1263,7 +1265,7 @@ __device__ __forceinline__ uint32_t block_scan_and_sum(uint32_t v, uint32_t r, u
 template <bool DEPTH, bool TAB>
 __global__ __launch_bounds__(256) void k_emit(const Frame f, const uint2* __restrict__ rects,
                                               const uint32_t* __restrict__ block_sums, const uint32_t* __restrict__ super_excl,
-                                              uint32_t n_chunks, uint32_t pair_cap, unsigned long long* __restrict__ counters,
+                                              uint32_t n_chunks, uint32_t pair_cap, FrameCounters* __restrict__ counters,
                                               uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                               const float* __restrict__ depths, uint32_t* __restrict__ dkeys, uint32_t* __restrict__ krange,
                                               const uint32_t* __restrict__ live_cnt2, const uint32_t* __restrict__ live_cid)
@@ -1285,7 +1287,7 @@ __global__ __launch_bounds__(256) void k_emit(const Frame f, const uint2* __rest
     uint32_t n_mine;
     if (TAB) {
         const uint32_t x = blockIdx.x & 7u, k0 = (blockIdx.x >> 3) * kEmitGroup;
-        const uint32_t n_live = live_cnt2[x * kSuperStride];
+        const uint32_t n_live = live_cnt2[live_count_word(x)];      // (live_cnt2: the table's copy rows, from live_copy_word(0))
         if (k0 >= n_live) return;
         n_mine = min(kEmitGroup, n_live - k0);
 #pragma unroll
@@ -1303,7 +1305,7 @@ __global__ __launch_bounds__(256) void k_emit(const Frame f, const uint2* __rest
     for (uint32_t k = 0; k < kEmitGroup; k++) {
         sums[k] = block_sums[cid[k]];
         bs[k] = block_sums[min((cid[k] & ~255u) + threadIdx.x, cid[k])];
-        sbase[k] = super_excl[cid[k] >> 8];                          // pairs of all chunks before the chunk's super-group (k_totals)
+        sbase[k] = super_excl[super_of_chunk(cid[k])];                         // pairs of all chunks before the chunk's super-group (k_totals)
         rcs[k] = rects[(size_t)cid[k] * 256u + threadIdx.x];         // only meaningful when sums[k] != 0 (k_project wrote it then)
         dep[k] = DEPTH ? depths[(size_t)cid[k] * 256u + threadIdx.x] : 0.0f;      // likewise (k_project stores a slot's depth beside its record)
     }
@@ -1335,7 +1337,7 @@ __global__ __launch_bounds__(256) void k_emit(const Frame f, const uint2* __rest
         chunk_base += sbase[k];
         off += chunk_base;
         if ((unsigned long long)chunk_base + tot > (unsigned long long)pair_cap) {   // pair buffers too small: host re-runs the frame
-            if (threadIdx.x == 0) atomicOr(&counters[3], 1ull);
+            if (threadIdx.x == 0) atomicOr(&counters->res.rerun, 1ull);
             return;
         }
         if (count == 0) continue;
@@ -1379,7 +1381,7 @@ __global__ __launch_bounds__(256) void k_emit(const Frame f, const uint2* __rest
             kmn = min(min(s_mn[0], s_mn[DEPTH ? 1 : 0]), min(s_mn[DEPTH ? 2 : 0], s_mn[DEPTH ? 3 : 0]));
             kmx = max(max(s_mx[0], s_mx[DEPTH ? 1 : 0]), max(s_mx[DEPTH ? 2 : 0], s_mx[DEPTH ? 3 : 0]));
             if (kmn <= kmx) {
-                if (~kmn > __builtin_nontemporal_load(&krange[0])) atomicMax(&krange[0], ~kmn);                     // (load_krange)
+                if (krange_min_word(kmn) > __builtin_nontemporal_load(&krange[0])) atomicMax(&krange[0], krange_min_word(kmn));     // (load_krange)
                 if (kmx > __builtin_nontemporal_load(&krange[1])) atomicMax(&krange[1], kmx);
             }
         }
@@ -1392,12 +1394,12 @@ __global__ __launch_bounds__(256) void k_emit(const Frame f, const uint2* __rest
 // them 64 at a time with ballot match-any, so in-wave order == memory order.
 // ------------------------------------------------------------------------------------
 // pair count as seen by the kernels downstream of k_emit: never more than the buffers hold
-// (n_ptr = &counters[1]; counters[3] = overflow flag set by k_emit).  On overflow part of the pair buffer is
-// unwritten, so the whole downstream chain processes nothing and the host re-runs the frame with larger buffers.
-__device__ __forceinline__ uint32_t clamped_count(const unsigned long long* n_ptr, uint32_t n_cap)
+// (a frame's SortCount is the view of its counter block: n = the pair count, refused = the re-run flag k_emit sets).  On overflow part of
+// the pair buffer is unwritten, so the whole downstream chain processes nothing and the host re-runs the frame with larger buffers.
+__device__ __forceinline__ uint32_t clamped_count(const SortCount* count, uint32_t n_cap)
 {
-    const unsigned long long n = n_ptr[0];
-    if (n_ptr[2] != 0ull || n > (unsigned long long)n_cap) return 0u;
+    const unsigned long long n = count->n;
+    if (count->refused != 0ull || n > (unsigned long long)n_cap) return 0u;
     return (uint32_t)n;
 }
 
@@ -1405,22 +1407,21 @@ __device__ __forceinline__ uint32_t clamped_count(const unsigned long long* n_pt
 // its share 64 at a time.  Sweeps, frames/s with two frames in flight (bench.py, 300 steps): c3 (2.66 M pairs) 256 threads
 // 3733, 512 3925, 1024 3899; c3h 3105 / 3578 / 3589; c5 (21 M pairs) 537.5 / 531.6 / 506.2.  The sort stage alone at c3:
 // 77 / 69 / 76 us (other splits of the block: 1024x8 78, 512x16 82, 1024x2 95, 512x4 84).  launch_sort picks 512 threads up
-// to kSortWideMax pairs of capacity and 256 above.
-constexpr int kSortBlock = 4096;
+// to kSortWideMax pairs of capacity and 256 above.  (kSortBlock: gswt_frame_layout.h, with the workspace the block size shapes.)
 constexpr uint32_t kSortWideMax = 0xFFFFFFFFu;  // pair capacities up to this use 512-thread workgroups (every size since k_radix_supscan: the 256-thread build only won at c5 while each workgroup summed ~100 group rows)
 
 // Per pass: k_radix_hist leaves, for every digit d, the per-workgroup counts ghist[d][blk], the sums over
 // groups of 32 workgroups gsup[d][blk >> 5] and the digit totals gtot[d] (integer atomics, spread over
 // 256 x nblk/32 addresses).  k_radix_scatter derives its global offsets from those directly -- digit d's
-// base = sum of gtot[< d] + gsup[d][< blk >> 5] + ghist[d][same group, < blk] -- so no scan kernel runs.
-constexpr uint32_t kSupShift = 5;
+// base = sum of gtot[< d] + gsup[d][< blk >> 5] + ghist[d][same group, < blk] -- so no scan kernel runs.  (kSupShift and where the
+// three lie in the workspace: RadixWs, gswt_frame_layout.h.)
 constexpr uint32_t kSupDirect = 32;             // up to this many groups the scatter kernel reads every group row instead of digit totals
 
 // Key range of the depth sort as k_emit<DEPTH> leaves it: [0] = ~smallest key, [1] = largest (both through atomicMax, so the frame's zeroed
 // scratch words are the neutral start); no keys at all reads as (0, 0).
 __device__ __forceinline__ void load_krange(const uint32_t* __restrict__ krange, uint32_t& kmin, uint32_t& kmax)
 {
-    kmin = ~krange[0]; kmax = krange[1];
+    kmin = krange_min_word(krange[0]); kmax = krange[1];
     if (kmax < kmin) { kmin = 0u; kmax = 0u; }
 }
 // Number of radix passes the keys in [kmin, kmax] need (see k_radix_hist): pass p covers bits 8p .. 8p+7 of key - kmin.  The host
@@ -1463,7 +1464,7 @@ __device__ __forceinline__ unsigned long long match_digit(uint32_t dgt, bool val
 }
 
 template <int kSortThreads>
-__global__ __launch_bounds__(kSortThreads) void k_radix_hist(const uint32_t* __restrict__ keys, const unsigned long long* __restrict__ n_ptr,
+__global__ __launch_bounds__(kSortThreads) void k_radix_hist(const uint32_t* __restrict__ keys, const SortCount* __restrict__ count,
                                                     uint32_t n_cap, uint32_t shift, uint32_t mask, uint32_t nbits, uint32_t* __restrict__ ghist,
                                                     uint32_t* __restrict__ gsup, uint32_t* __restrict__ gtot, uint32_t nblk,
                                                     uint32_t nsup, const uint32_t* __restrict__ krange)
@@ -1474,7 +1475,7 @@ __global__ __launch_bounds__(kSortThreads) void k_radix_hist(const uint32_t* __r
     // (sort_passes_needed; a frame that needs more than were launched is flagged by k_items and re-run).
     uint32_t kmin = 0;
     if (krange) { uint32_t kmax; load_krange(krange, kmin, kmax); }
-    const uint32_t n = clamped_count(n_ptr, n_cap);
+    const uint32_t n = clamped_count(count, n_cap);
     __shared__ uint32_t s_h[256];
     if (threadIdx.x < 256u) s_h[threadIdx.x] = 0;
     __syncthreads();
@@ -1561,7 +1562,7 @@ __global__ __launch_bounds__(256) void k_radix_supscan(uint32_t* __restrict__ gs
 template <int kSortThreads, int AUX>
 __global__ __launch_bounds__(kSortThreads) __attribute__((amdgpu_waves_per_eu((kSortThreads == 512 && AUX != 2) ? 6 : 1, 8))) void k_radix_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                                                        uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
-                                                       const unsigned long long* __restrict__ n_ptr, uint32_t n_cap, uint32_t shift,
+                                                       const SortCount* __restrict__ count, uint32_t n_cap, uint32_t shift,
                                                        uint32_t mask, uint32_t nbits, const uint32_t* __restrict__ ghist,
                                                        const uint32_t* __restrict__ gsup, const uint32_t* __restrict__ gtot,
                                                        uint32_t nblk, uint32_t nsup, uint2* __restrict__ ranges, const uint32_t* __restrict__ krange,
@@ -1570,7 +1571,7 @@ __global__ __launch_bounds__(kSortThreads) __attribute__((amdgpu_waves_per_eu((k
     constexpr int kSortItems = kSortBlock / kSortThreads, kSortWaves = kSortThreads / 64;
     uint32_t kmin = 0;                                  // (see k_radix_hist)
     if (krange) { uint32_t kmax; load_krange(krange, kmin, kmax); }
-    const uint32_t n = clamped_count(n_ptr, n_cap);
+    const uint32_t n = clamped_count(count, n_cap);
     if (blockIdx.x * kSortBlock >= n) return;
 #ifdef GSWT_TRACE
     // phase stamps of the scatter pass (tools/sort_trace.py): rows kTraceItems / 2 + (shift ? 4096 : 0) + block
@@ -1721,11 +1722,11 @@ __global__ __launch_bounds__(kSortThreads) __attribute__((amdgpu_waves_per_eu((k
             else {
                 // LAST pass of the frame's pair sort: the block in LDS is sorted by the whole key (the passes before ordered the
                 // input by the lower digits, stably), so the first and last item of every run of equal keys are neighbours' business --
-                // they leave the tile's [start, end) in the sorted pair list: start as ~start, both through atomicMax on the zeroed
-                // table, because a tile's run can continue in the next block.  This replaces a pass over the sorted keys (k_ranges,
+                // they leave the tile's [start, end) in the sorted pair list: the range words of encode_tile_range, both through atomicMax on
+                // the zeroed table, because a tile's run can continue in the next block.  This replaces a pass over the sorted keys (k_ranges,
                 // 5 us + a launch at c3), and the sorted keys themselves are not written any more: nothing reads them.
                 const uint32_t kp = s_kv[i == 0u ? 0u : i - 1u].x, kn = s_kv[min(i + 1u, n_blk - 1u)].x;
-                if (i == 0u || kp != kv.x) atomicMax(&ranges[kv.x].x, ~gp);
+                if (i == 0u || kp != kv.x) atomicMax(&ranges[kv.x].x, tile_range_start_word(gp));
                 if (i == n_blk - 1u || kn != kv.x) atomicMax(&ranges[kv.x].y, gp + 1u);
             }
         }
@@ -1879,21 +1880,21 @@ __device__ __forceinline__ void tls_sync()
 }
 template <int THREADS, int ROUNDS, bool LONG, bool WAVE = false>
 __device__ __forceinline__ void tile_depth_sort_one(uint32_t tile, const uint2* __restrict__ ranges, uint32_t* __restrict__ vals, const uint32_t* __restrict__ dkeys,
-                                                    uint32_t* __restrict__ long_list, uint32_t* __restrict__ xl_list, unsigned long long* __restrict__ counters,
+                                                    uint32_t* __restrict__ long_list, uint32_t* __restrict__ xl_list, FrameCounters* __restrict__ counters,
                                                     uint32_t n_lo, bool push, uint2* s_kv, uint32_t (*s_h)[256], uint32_t* s_w, uint32_t* s_mn, uint32_t* s_mx)
 {
     constexpr uint32_t CAP = (uint32_t)(THREADS * ROUNDS);
     constexpr int NW = THREADS / 64;
     // (everything the control flow hangs on is read through v_readfirstlane: a value loaded from memory sits in a vector register, and the
     // compiler then predicates every "uniform" branch below with exec-mask nests instead of scalar branches)
-    const uint2 rgv = ranges[__builtin_amdgcn_readfirstlane(tile)];  // (~start, end); (0, 0): no pairs
+    const uint2 rgv = ranges[__builtin_amdgcn_readfirstlane(tile)];  // the tile's range words; (0, 0): no pairs
     const uint32_t rg_x = __builtin_amdgcn_readfirstlane(rgv.x), rg_y = __builtin_amdgcn_readfirstlane(rgv.y);
     if (rg_y == 0u) return;
-    const uint32_t start = ~rg_x, n = rg_y - start;
+    const uint32_t start = tile_range_start_word(rg_x), n = rg_y - start;
     if (n <= max(n_lo, 1u)) return;                               // (a shorter list: the class below's)
     if (n > CAP) {                                                // workgroup-uniform
         if ((WAVE ? (threadIdx.x & 63u) : threadIdx.x) == 0u && (LONG || push)) {
-            if (LONG) counters[3] = 1ull;                         // (cannot happen: the list only holds what fits)
+            if (LONG) counters->res.rerun = 1ull;                 // (cannot happen: the list only holds what fits)
             else {
                 uint32_t* const lst = n > kTileSortCap ? xl_list : long_list;      // beyond the LDS buffer: k_tile_depth_sort_xl
                 lst[1u + atomicAdd(&lst[0], 1u)] = tile;
@@ -2008,7 +2009,8 @@ __device__ __forceinline__ void tile_depth_sort_xl(const uint2* __restrict__ ran
     const uint32_t lane = threadIdx.x & 63u, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (uint32_t t = blockIdx.x; t < n_xl; t += gridDim.x) {
         const uint2 rgv = ranges[__builtin_amdgcn_readfirstlane(xl_list[1u + t])];
-        const uint32_t start = ~(uint32_t)__builtin_amdgcn_readfirstlane(rgv.x), n = (uint32_t)__builtin_amdgcn_readfirstlane(rgv.y) - start;
+        // (a listed tile has pairs: its start word decodes without the empty case)
+        const uint32_t start = tile_range_start_word((uint32_t)__builtin_amdgcn_readfirstlane(rgv.x)), n = (uint32_t)__builtin_amdgcn_readfirstlane(rgv.y) - start;
         const uint32_t per = ((n + NW * 64u - 1u) / (NW * 64u)) * 64u;            // items per wave: whole 64-item rounds
         const uint32_t lo = min(w * per, n), hi = min(lo + per, n);
         // the list's key range
@@ -2079,7 +2081,7 @@ __device__ __forceinline__ void tile_depth_sort_xl(const uint2* __restrict__ ran
 
 template <int THREADS, int ROUNDS, bool LONG>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS == 256 ? 4 : 1, 8))) void k_tile_depth_sort(const uint2* __restrict__ ranges, uint32_t* vals, uint32_t* dkeys,      // (no __restrict__: the last class writes both)
-                                                             uint32_t n_tiles, uint32_t* __restrict__ long_list, unsigned long long* __restrict__ counters,
+                                                             uint32_t n_tiles, uint32_t* __restrict__ long_list, FrameCounters* __restrict__ counters,
                                                              uint32_t n_lo, uint32_t push, uint32_t* vals_scratch, uint32_t* dkeys_scratch)
 {
     constexpr int NW = THREADS / 64;
@@ -2118,18 +2120,18 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
 // item_base[t] = exclusive scan of seg_count, item_base[n_tiles] = number of items; item_tab[item] =
 // (tile, segment << 1 | tile has several segments, first pair, end pair): everything k_composite needs in one load.  Single workgroup (n_tiles is a few thousand to a few
 // tens of thousands): one launch instead of count + 3 scan launches.
-// GSWT_ORDER_DEPTH (krange != nullptr): also the depth sort's pass check -- counters[2] = 8-bit passes this frame's depth range needs; more
-// than were launched = the pair list is not in depth order: the frame is flagged (counters[3]) and the host re-runs it with more passes.
+// GSWT_ORDER_DEPTH (krange != nullptr): also the depth sort's pass check -- depth_passes_needed = 8-bit passes this frame's depth range needs;
+// more than were launched = the pair list is not in depth order: the frame is flagged (rerun) and the host re-runs it with more passes.
 template <bool HEAVY>
 __global__ __launch_bounds__(1024) void k_items(const uint2* __restrict__ ranges, int n_tiles, uint32_t seg,
                                                 uint32_t* __restrict__ item_base, uint4* __restrict__ item_tab, uint32_t max_items,
-                                                const uint32_t* __restrict__ krange, uint32_t n_launched, unsigned long long* __restrict__ counters,
+                                                const uint32_t* __restrict__ krange, uint32_t n_launched, FrameCounters* __restrict__ counters,
                                                 uint32_t report_max)
 {
     if (krange && blockIdx.x == 0u && threadIdx.x == 0u) {
         const uint32_t need = sort_passes_needed(krange);
-        *reinterpret_cast<uint32_t*>(counters + 2) = need;                   // (the low half: the high one takes the longest tile list)
-        if (need > n_launched) counters[3] = 1ull;
+        counters->res.depth_passes_needed = need;
+        if (need > n_launched) counters->res.rerun = 1ull;
     }
     // One workgroup per 8192 tiles (c3: one workgroup, c5: four).  Thread t owns tiles base + j * 1024 + t, j = 0..7: every
     // load and store of a wave is contiguous (eight tiles per thread SIDE BY SIDE made each of them 64 separate 8-byte
@@ -2146,9 +2148,9 @@ __global__ __launch_bounds__(1024) void k_items(const uint2* __restrict__ ranges
     const uint32_t seg_sh = (uint32_t)__ffs((int)seg) - 1u;
     const int base = (int)blockIdx.x * 1024 * kPer;
     uint2 r[kPer];
-    // (ranges[t] = (~start, end) as the last sort pass leaves it, (0, 0) for a tile without pairs)
+    // (ranges[t] = the range words the last sort pass leaves, decoded in place: r[j] = (start, end), (0, 0) for a tile without pairs)
 #pragma unroll
-    for (int j = 0; j < kPer; j++) { r[j] = ranges[min(base + j * 1024 + (int)threadIdx.x, last)]; r[j].x = r[j].y ? ~r[j].x : 0u; }
+    for (int j = 0; j < kPer; j++) { r[j] = ranges[min(base + j * 1024 + (int)threadIdx.x, last)]; r[j].x = tile_range_start(r[j].x, r[j].y); }
     // segments of the tiles in front of this workgroup
     uint32_t carry = 0;
     if (base > 0) {
@@ -2156,7 +2158,7 @@ __global__ __launch_bounds__(1024) void k_items(const uint2* __restrict__ ranges
         for (int t0 = 0; t0 < base; t0 += 1024 * kPer) {
             uint2 e[kPer];
 #pragma unroll
-            for (int j = 0; j < kPer; j++) { e[j] = ranges[t0 + j * 1024 + (int)threadIdx.x]; e[j].x = e[j].y ? ~e[j].x : 0u; }      // t0 + 8191 < base <= n_tiles
+            for (int j = 0; j < kPer; j++) { e[j] = ranges[t0 + j * 1024 + (int)threadIdx.x]; e[j].x = tile_range_start(e[j].x, e[j].y); }      // t0 + 8191 < base <= n_tiles
 #pragma unroll
             for (int j = 0; j < kPer; j++) {
                 const uint32_t len = e[j].y - e[j].x;
@@ -2169,13 +2171,13 @@ __global__ __launch_bounds__(1024) void k_items(const uint2* __restrict__ ranges
         for (uint32_t i = 0; i < 16u; i++) carry += s_carry[i];
     }
     if (report_max) {
-        // GSWT_ORDER_DEPTH: the longest tile list of the frame -> high half of counters[2]: the host picks the tile-local depth sort (lists that
+        // GSWT_ORDER_DEPTH: the longest tile list of the frame -> max_tile_len: the host picks the tile-local depth sort (lists that
         // fit its LDS buffer) or the global depth passes for the next frames by it
         uint32_t mx = 0;
 #pragma unroll
         for (int j = 0; j < kPer; j++) mx = max(mx, base + j * 1024 + (int)threadIdx.x < n_tiles ? r[j].y - r[j].x : 0u);
         mx = wave_max(mx);
-        if (lane == 0u && mx) atomicMax(reinterpret_cast<uint32_t*>(counters + 2) + 1, mx);        // <= 16 per workgroup, <= 4 workgroups
+        if (lane == 0u && mx) atomicMax(&counters->res.max_tile_len, mx);     // <= 16 per workgroup, <= 4 workgroups
     }
     uint32_t cnt[kPer], inc[kPer];
 #pragma unroll
@@ -2946,15 +2948,15 @@ template <int OUTF, bool ZOUT, bool PICK>
 __global__ __launch_bounds__(256) void k_combine(const Frame f, const uint32_t* __restrict__ item_base,
                                                  const float4* __restrict__ partials, const float4* __restrict__ bg_rgba,
                                                  float4* __restrict__ out, int n_tiles, int out_rows,
-                                                 const unsigned long long* __restrict__ counters, unsigned long long* __restrict__ host_counters,
+                                                 const FrameCounters* __restrict__ counters, FrameResult* __restrict__ host_counters,
                                                  const float* __restrict__ partials_z, const float* __restrict__ bg_depth, float* __restrict__ out_depth,
                                                  const uint2* __restrict__ partials_pick, uint4* __restrict__ out_pick)
 {
     const int tile = blockIdx.x;
     // last kernel of a frame without a pick image (k_pick_resolve follows otherwise; the host reads the words behind the frame's final event
-    // either way): the four result counters go straight into the slot's pinned host words (instead of a
-    // separate 32-byte device-to-host copy, ~4 us of stream time and one more API call per frame)
-    if (tile == 0 && threadIdx.x < 5u && host_counters) host_counters[threadIdx.x] = counters[threadIdx.x];
+    // either way): the frame's result (FrameResult) goes straight into the slot's pinned host words (instead of a
+    // separate device-to-host copy, ~4 us of stream time and one more API call per frame)
+    if (tile == 0 && threadIdx.x < kFrameResultWords64 && host_counters) copy_frame_result_word(host_counters, counters, threadIdx.x);
     const uint32_t i0 = item_base[tile], n_seg = item_base[tile + 1] - i0;
     if (n_seg == 1u) return;                      // the tile's only work item wrote the pixels itself; n_seg == 0: no pairs, background only
     const auto [tyl, bx, by] = comp_tile(f, (uint32_t)tile);
@@ -3099,7 +3101,7 @@ void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_c
 {
     uint32_t grid = (b.n_chunks + 255u) / 256u;            // one thread per chunk; the clears and the cell table stride over the grid
     if (grid < 32) grid = 32;
-    GSWT_LAUNCH(k_cull, dim3(grid), dim3(256), s, f, b.draws, b.draw_culled, b.cell_culled, b.n_cells, reinterpret_cast<uint32_t*>(b.counters), b.n_zero_head,
+    GSWT_LAUNCH(k_cull, dim3(grid), dim3(256), s, f, b.draws, b.draw_culled, b.cell_culled, b.n_cells, b.ghist, b.n_zero_head,
                 reinterpret_cast<uint32_t*>(b.ranges), b.n_zero_ranges, b.block_sums, b.n_chunks, b.radix_depth, b.n_zero_depth,
                 b.chunk_tab, b.n_chunks, b.boxes, chunk_cull && b.boxes ? 1u : 0u, b.live_cnt, b.live_tab, b.live_cid);
 }
@@ -3107,7 +3109,7 @@ void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_c
 void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict, bool ortho)
 {
     if (b.n_chunks == 0) return;
-    const uint32_t n_super = b.n_chunks / 256u + 1u;    // super_sums = [pairs x 16 n_super][visible x 16 n_super][exclusive pair prefix x n_super] (kSuperStride), zeroed by k_cull
+    const SuperSums ss = super_sums_of(b.n_chunks);     // (zeroed by k_cull)
     const bool full = f.surface_type == 2u || f.draw_mode != 0u;
     // (the orthographic stage exists in its strict form only: gswt_api.hip refuses an orthographic frame with GSWT_OPT_STRICT_VS = 0)
     // (nor has the pixel filter another: AA is a parameter of the STRICT instantiations only, and gswt_api.hip refuses a filtered v2 frame)
@@ -3121,9 +3123,9 @@ void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t 
         if constexpr (S || !(O || A || M || Y || Z))
             GSWT_LAUNCH((k_project<D, F, S, O, A, M, Y, Z>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,
                         b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums,
-                        b.super_sums, n_super, b.dbg, b.col_f, b.styles, b.n_styles, b.shadow);
+                        b.super_sums, ss.n_super, b.dbg, b.col_f, b.styles, b.n_styles, b.shadow);
     }, debug, full, strict_seq, ortho, aa, atm, sty, shd);
-    GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, n_super, b.counters, b.super_sums + 2u * kSuperStride * n_super, b.pair_cap, b.live_cnt, n_launch / 8u);
+    GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, ss.n_super, b.counters, b.super_sums + ss.prefix_word(0), b.pair_cap, b.live_cnt, n_launch / kLiveLists);
 }
 
 // keys: tile ids, vals: slots.  GSWT_ORDER_DEPTH (dkeys != nullptr): also each pair's depth bits -> dkeys and the frame's key range -> krange.
@@ -3131,12 +3133,11 @@ void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* ke
 {
     const uint32_t n_chunks = b.n_chunks, pair_cap = b.pair_cap;
     if (n_chunks == 0) return;
-    const uint32_t n_super = n_chunks / 256u + 1u;      // [pairs x n_super][visible x n_super][exclusive pair prefix x n_super]
-    const uint32_t* const excl = b.super_sums + 2u * kSuperStride * n_super;
+    const uint32_t* const excl = b.super_sums + super_sums_of(n_chunks).prefix_word(0);
     const float* const no_f = nullptr; uint32_t* const no_u = nullptr;
     // over k_cull's table of live chunks (k_totals' copy of its counts); without one (n_launch 0: the debug-varyings frame) over every chunk of
     // the frame, four consecutive ones per workgroup
-    const uint32_t* const cnt2 = n_launch ? b.live_cnt + 8u * kSuperStride : nullptr;
+    const uint32_t* const cnt2 = n_launch ? b.live_cnt + live_copy_word(0) : nullptr;
     const uint32_t* const cid = n_launch ? b.live_cid : nullptr;
     const dim3 grid(n_launch ? ((n_launch / 8u + kEmitGroup - 1u) / kEmitGroup) * 8u : (n_chunks + kEmitGroup - 1u) / kEmitGroup);
     with_variant([&](auto L, auto D) {
@@ -3145,50 +3146,31 @@ void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* ke
     }, n_launch != 0u, dkeys != nullptr);
 }
 
-// ws: per pass [ghist 256 x nblk][gsup 256 x nsup][gtot 256] (gswt_device.h: launch_sort)
-size_t radix_ws_words(uint32_t n_cap, int key_bits)
-{
-    const uint32_t nblk = (n_cap + kSortBlock - 1) / kSortBlock, nsup = (nblk >> kSupShift) + 1;
-    const int passes = (key_bits + 7) / 8;
-    return (size_t)passes * ((size_t)256 * nblk + (size_t)256 * nsup + 256);
-}
-// The part of the workspace that has to be zero when a sort starts: the group rows and digit totals of every pass (targets of
-// atomic adds), which come first.  The per-workgroup rows behind them are written in full by k_radix_hist (every launched
-// workgroup stores its 256 counts, zeros past the item count) -- a frame used to clear them too: 2 MB at c3, 13.6 MB at c5, by
-// k_cull's 32 workgroups.
-size_t radix_ws_zero_words(uint32_t n_cap, int key_bits)
-{
-    const uint32_t nblk = (n_cap + kSortBlock - 1) / kSortBlock, nsup = (nblk >> kSupShift) + 1;
-    const int passes = (key_bits + 7) / 8;
-    return (size_t)passes * ((size_t)256 * nsup + 256);
-}
-
+// ws: the RadixWs of (n_cap, key_bits), gswt_frame_layout.h.  Its zeroed part -- the group rows and digit totals of every pass, targets of
+// atomic adds -- comes first; the per-workgroup rows behind it are written in full by k_radix_hist (every launched workgroup stores its
+// 256 counts, zeros past the item count) -- a frame used to clear them too: 2 MB at c3, 13.6 MB at c5, by k_cull's 32 workgroups.
 int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n_cap,
-                const unsigned long long* n_ptr, int key_bits, uint32_t* ws, uint2* ranges, const uint32_t* krange, uint32_t* aux_a, uint32_t* aux_b,
+                const SortCount* count, int key_bits, uint32_t* ws, uint2* ranges, const uint32_t* krange, uint32_t* aux_a, uint32_t* aux_b,
                 int threads_override, int aux_override)
 {
     if (n_cap == 0) return 0;
-    const uint32_t nblk = (n_cap + kSortBlock - 1) / kSortBlock, nsup = (nblk >> kSupShift) + 1;
+    const RadixWs lay = radix_ws_of(n_cap, key_bits);
+    const uint32_t nblk = lay.nblk, nsup = lay.nsup;
     // (the overrides: gswt_debug_sort_ex only -- a frame takes 512 threads at every capacity and payload form 1 up to 12 M pairs, 2 above)
     const int threads = threads_override ? threads_override : n_cap <= kSortWideMax ? 512 : 256;
     const int aux = !aux_a ? 0 : aux_override ? aux_override : n_cap > (12u << 20) ? 2 : 1;       // k_radix_scatter's payload forms
     int cur = 0;
-    const int passes = (key_bits + 7) / 8;
-    uint32_t* hist_rows = ws + (size_t)passes * ((size_t)256 * nsup + 256);      // behind the zeroed part (radix_ws_zero_words)
-    for (int shift = 0; shift < key_bits; shift += 8) {
+    for (int shift = 0, pass = 0; shift < key_bits; shift += 8, pass++) {
         uint32_t nbits = (uint32_t)((key_bits - shift) < 8 ? (key_bits - shift) : 8);
         uint32_t mask = (1u << nbits) - 1u;
-        uint32_t* gsup = ws; uint32_t* gtot = gsup + (size_t)256 * nsup;
-        ws = gtot + 256;
-        uint32_t* ghist = hist_rows;
-        hist_rows += (size_t)256 * nblk;
+        uint32_t* const gsup = ws + lay.gsup(pass); uint32_t* const gtot = ws + lay.gtot(pass); uint32_t* const ghist = ws + lay.ghist(pass);
         uint32_t* ki = cur ? keys_b : keys_a; uint32_t* vi = cur ? vals_b : vals_a;
         uint32_t* ko = cur ? keys_a : keys_b; uint32_t* vo = cur ? vals_a : vals_b;
         const uint32_t* xi = cur ? aux_b : aux_a; uint32_t* xo = cur ? aux_a : aux_b;
         with_variant([&](auto T, auto AUX) {
-            GSWT_LAUNCH(k_radix_hist<T>, dim3(nblk), dim3(T), s, ki, n_ptr, n_cap, (uint32_t)shift, mask, nbits, ghist, gsup, gtot, nblk, nsup, krange);
+            GSWT_LAUNCH(k_radix_hist<T>, dim3(nblk), dim3(T), s, ki, count, n_cap, (uint32_t)shift, mask, nbits, ghist, gsup, gtot, nblk, nsup, krange);
             if (nsup > kSupDirect) GSWT_LAUNCH(k_radix_supscan, dim3(64), dim3(256), s, gsup, gtot, nsup);
-            GSWT_LAUNCH((k_radix_scatter<T, AUX>), dim3(nblk), dim3(T), s, ki, vi, ko, vo, n_ptr, n_cap, (uint32_t)shift, mask, nbits,
+            GSWT_LAUNCH((k_radix_scatter<T, AUX>), dim3(nblk), dim3(T), s, ki, vi, ko, vo, count, n_cap, (uint32_t)shift, mask, nbits,
                         ghist, gsup, gtot, nblk, nsup, shift + 8 >= key_bits ? ranges : (uint2*)nullptr, krange, xi, xo);
         }, OneOf<512, 256>{threads}, OneOf<2, 1, 0>{aux});
         cur ^= 1;
@@ -3197,9 +3179,9 @@ int launch_sort(hipStream_t s, uint32_t* keys_a, uint32_t* vals_a, uint32_t* key
 }
 
 // Builds every merged group's (gs_index | lod, map_id) list on the device.  keys/vals a,b: n_total u32 each;
-// ws: radix_ws_words(n_total, 16 + group_bits) zeroed words; n_total_dev: device u64 = n_total (+ two zero words after it).
+// ws: radix_ws_words(n_total, 16 + group_bits) zeroed words; n_total_dev: the device's SortCount record of n_total.
 void launch_merge_build(hipStream_t s, const MergeSeg* segs, uint32_t n_segs, const uint2* blocks, uint32_t n_blocks, MergeGroup* groups, uint32_t n_groups,
-                        const int32_t* raw, uint32_t n_total, const unsigned long long* n_total_dev, uint32_t* ka, uint32_t* va,
+                        const int32_t* raw, uint32_t n_total, const SortCount* n_total_dev, uint32_t* ka, uint32_t* va,
                         uint32_t* kb, uint32_t* vb, uint32_t* radix_ws, int group_bits, uint32_t* merged_list, uint32_t* merged_map)
 {
     if (n_total == 0 || n_groups == 0 || n_blocks == 0) return;
@@ -3211,7 +3193,7 @@ void launch_merge_build(hipStream_t s, const MergeSeg* segs, uint32_t n_segs, co
 }
 
 int launch_scene_sort(hipStream_t s, const MergeSeg* segs, const uint2* blocks, uint32_t n_blocks, MergeGroup* groups, const int32_t* raw,
-                      uint32_t n_total, const unsigned long long* n_total_dev, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb,
+                      uint32_t n_total, const SortCount* n_total_dev, uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb,
                       uint32_t* radix_ws, int group_bits)
 {
     if (n_total == 0 || n_blocks == 0) return 0;
@@ -3228,7 +3210,7 @@ void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks
 
 // dkeys = the pairs' depth bits in the order of vals (the tile sort's payload)
 void launch_tile_depth_sort(hipStream_t s, const uint2* ranges, uint32_t* vals, uint32_t* dkeys, uint32_t* vals_scratch, uint32_t* dkeys_scratch, int n_tiles,
-                            uint32_t* long_list, unsigned long long* counters)
+                            uint32_t* long_list, FrameCounters* counters)
 {
     if (n_tiles <= 0) return;
     // four size classes in three launches: a wave per tile, a 256-thread workgroup per tile, a fixed grid over the list of still longer ones
@@ -3279,7 +3261,7 @@ void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const u
                                   b.out_pick, b.partials_pick);
         }, colf, !colf && f.t_eps > 0.0f, f.has_depth != 0);
         GSWT_LAUNCH((k_combine<OUTF, ZOUT, PICK>), dim3(n_tiles), dim3(256), s, f, b.item_base, b.partials, b.bg_rgba, b.out, n_tiles, out_rows,
-                    (const unsigned long long*)b.counters, b.host_counters, (const float*)b.partials_z, b.bg_depth, b.out_depth,
+                    (const FrameCounters*)b.counters, b.host_counters, (const float*)b.partials_z, b.bg_depth, b.out_depth,
                     (const uint2*)b.partials_pick, b.out_pick);
         if (PICK) {
             const uint32_t n_px = (uint32_t)out_rows * (uint32_t)f.out_w;
@@ -3290,9 +3272,9 @@ void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const u
 }
 
 // k_totals alone on caller-provided sums (unit test of the 64-bit pair count)
-void launch_totals(hipStream_t s, uint32_t* super_sums, uint32_t n_super, unsigned long long* counters, uint32_t pair_cap)
+void launch_totals(hipStream_t s, uint32_t* super_sums, SuperSums ss, FrameCounters* counters, uint32_t pair_cap)
 {
-    hipLaunchKernelGGL(k_totals, dim3(1), dim3(256), 0, s, super_sums, n_super, counters, super_sums + 2u * kSuperStride * n_super, pair_cap, (uint32_t*)nullptr, 0xFFFFFFFFu);
+    hipLaunchKernelGGL(k_totals, dim3(1), dim3(256), 0, s, super_sums, ss.n_super, counters, super_sums + ss.prefix_word(0), pair_cap, (uint32_t*)nullptr, 0xFFFFFFFFu);
 }
 
 void launch_unshard(hipStream_t s, const void* gathered, void* out, int width, int height, int shard_count, int rows_padded, int band_px,

@@ -739,6 +739,8 @@ struct Pinned {
     hipError_t alloc(size_t count) { release(); return hipHostMalloc(reinterpret_cast<void**>(&p), (count ? count : 1) * sizeof(T), hipHostMallocDefault); }
     void release() { if (p) hipHostFree(p); p = nullptr; }
 };
+// gswt_worker::sort_counts: the record of the edge candidates' sort and of the cells'
+enum { kCountCand = 0, kCountCells = 1, kSortCounts = 2 };
 
 }  // namespace
 
@@ -759,7 +761,7 @@ struct gswt_worker {
     Dev<gswt_cell_state> st;
     Dev<int8_t> gdir;
     Dev<unsigned long long> gtab;
-    Dev<unsigned long long> n64;
+    Dev<gswt::SortCount> sort_counts;      // the item counts of the two sorts of an event: kCountCand, kCountCells
     Dev<gswt_sorted_tile> tiles;
     Dev<gswt_merge_group> groups;
     Dev<gswt_merge_member> members;
@@ -874,7 +876,7 @@ try {
     A(w->cell.alloc(cells)); A(w->st.alloc(cells)); A(w->head_off.alloc(cells)); A(w->head_len.alloc(cells)); A(w->pool.alloc(cells + 8));
     A(w->counts.alloc(C_COUNT)); A(w->order.alloc(cells)); A(w->keys_a.alloc(n_cand)); A(w->vals_a.alloc(n_cand)); A(w->keys_b.alloc(n_cand));
     A(w->vals_b.alloc(n_cand)); A(w->radix_ws.alloc(w->radix_words)); A(w->pre_group.alloc(cells)); A(w->pre_member.alloc(cells)); A(w->pre_len.alloc(cells));
-    A(w->ent_len.alloc(cells)); A(w->gdir.alloc(n_cand)); A(w->gtab.alloc(graph_tab_bytes((int)cells) / 8 + 8)); A(w->n64.alloc(8));
+    A(w->ent_len.alloc(cells)); A(w->gdir.alloc(n_cand)); A(w->gtab.alloc(graph_tab_bytes((int)cells) / 8 + 8)); A(w->sort_counts.alloc(kSortCounts));
     A(w->tiles.alloc(cells)); A(w->groups.alloc(cells)); A(w->members.alloc(cells)); A(w->draws.alloc(cells));
     for (auto& h : w->hs) { A(h.tiles.alloc(cells)); A(h.groups.alloc(cells)); A(h.members.alloc(cells)); A(h.draws.alloc(cells)); }
     A(w->h_counts.alloc(C_COUNT));
@@ -886,12 +888,11 @@ try {
         // item counts of the two sorts a sort event may run (edge candidates, cells): fixed for the worker's life, so they are
         // written here, once, from pinned memory and before the synchronize -- not per event from a stack array that an
         // asynchronous copy could outlive
-        Pinned<unsigned long long> h;
-        A(h.alloc(8));
+        Pinned<gswt::SortCount> h;
+        A(h.alloc(kSortCounts));
         if (e == hipSuccess) {
-            for (int k = 0; k < 8; k++) h.p[k] = 0ull;
-            h.p[0] = n_cand; h.p[4] = cells;
-            A(hipMemcpyAsync(w->n64.p, h.p, 8 * sizeof(unsigned long long), hipMemcpyHostToDevice, w->stream));
+            h.p[kCountCand] = gswt::sort_count(n_cand); h.p[kCountCells] = gswt::sort_count(cells);
+            A(hipMemcpyAsync(w->sort_counts.p, h.p, kSortCounts * sizeof(gswt::SortCount), hipMemcpyHostToDevice, w->stream));
             A(hipStreamSynchronize(w->stream));
         }
         h.release();
@@ -933,7 +934,7 @@ void gswt_worker_destroy(gswt_worker* w)
     w->splat_count.release(); w->head_off.release(); w->head_len.release(); w->pool.release(); w->counts.release(); w->order.release();
     w->keys_a.release(); w->vals_a.release(); w->keys_b.release(); w->vals_b.release(); w->radix_ws.release(); w->pre_group.release();
     w->pre_member.release(); w->pre_len.release(); w->ent_len.release(); w->nb.release(); w->cell.release(); w->st.release(); w->gdir.release();
-    w->gtab.release(); w->n64.release(); w->tiles.release(); w->groups.release(); w->members.release(); w->draws.release();
+    w->gtab.release(); w->sort_counts.release(); w->tiles.release(); w->groups.release(); w->members.release(); w->draws.release();
     for (auto& h : w->hs) { h.tiles.release(); h.groups.release(); h.members.release(); h.draws.release(); }
     w->h_counts.release();
     delete w;
@@ -993,16 +994,16 @@ try {
     if (need_edges) hipLaunchKernelGGL(k_w_edges, dim3((n_cand + 255) / 256), dim3(256), 0, s, d, cam, vp, w->keys_a.p, w->vals_a.p, w->gdir.p);
     const uint32_t* sk = w->keys_a.p; const uint32_t* sv = w->vals_a.p;
     if (d.merge_type == MERGE_EDGE) {
-        // (w->n64[0] = n_cand, w->n64[4] = cells: written once by gswt_worker_create)
+        // (the sorts' item counts, n_cand and cells: written once by gswt_worker_create)
         WHIP(hipMemsetAsync(w->radix_ws.p, 0, w->radix_words * sizeof(uint32_t), s));
-        const int where = gswt::launch_sort(s, w->keys_a.p, w->vals_a.p, w->keys_b.p, w->vals_b.p, n_cand, w->n64.p, 32, w->radix_ws.p);
+        const int where = gswt::launch_sort(s, w->keys_a.p, w->vals_a.p, w->keys_b.p, w->vals_b.p, n_cand, w->sort_counts.p + kCountCand, 32, w->radix_ws.p);
         if (where) { sk = w->keys_b.p; sv = w->vals_b.p; }
     }
     if (d.merge_type != MERGE_NONE) hipLaunchKernelGGL(k_w_merge, dim3(1), dim3(64), w->lds_merge, s, d, cam, vp, sk, sv);
     if (d.sort_type == SORT_DISTANCE || d.sort_type == SORT_VIEWPORT) {
         hipLaunchKernelGGL(k_w_order_keys, dim3((cells + 255) / 256), dim3(256), 0, s, d, cam, vp, w->keys_a.p, w->vals_a.p);
         WHIP(hipMemsetAsync(w->radix_ws.p, 0, w->radix_words * sizeof(uint32_t), s));
-        const int where = gswt::launch_sort(s, w->keys_a.p, w->vals_a.p, w->keys_b.p, w->vals_b.p, cells, w->n64.p + 4, 32, w->radix_ws.p);
+        const int where = gswt::launch_sort(s, w->keys_a.p, w->vals_a.p, w->keys_b.p, w->vals_b.p, cells, w->sort_counts.p + kCountCells, 32, w->radix_ws.p);
         hipLaunchKernelGGL(k_w_order_reverse, dim3((cells + 255) / 256), dim3(256), 0, s, d, where ? w->vals_b.p : w->vals_a.p, w->order.p);
     } else {
         if (w->graph_in_lds) hipLaunchKernelGGL(k_w_order_seq<true>, dim3(1), dim3(kSeqThreads), w->lds_graph, s, d, cam, w->gdir.p, w->gtab.p, w->order.p);

@@ -208,6 +208,28 @@ def test_group_prefix_path(renderer, large_input, threads):
     assert np.array_equal(k[n:], g["keys"][n:]) and np.array_equal(v[n:], g["vals"][n:]) and np.array_equal(x[n:], g["aux"][n:])
 
 
+@pytest.mark.parametrize("n", [1, BLOCK, BLOCK + 1, 32 * BLOCK + 1])
+def test_plain_hook_is_the_ex_hook(renderer, n):
+    """gswt_debug_sort and gswt_debug_sort_ex (no payload, no key range, n = n_cap) run one helper: identical keys and values on the same
+    random 32-bit keys, both numpy's stable order of the keys masked to key_bits (the bits above travel with their key).  Sizes: one item, a
+    full block, a block and one item, and 33 workgroups -- two group rows of the workspace.  key_bits: one partial pass, two passes, four."""
+    from gswt_renderer_amd import _lib as L
+    lib = L.load()
+    assert (32 * BLOCK + 1 + BLOCK - 1) // BLOCK == 33 and (33 >> 5) + 1 == 2
+    rng = np.random.default_rng(2100 + n)
+    keys = rng.integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
+    vals = np.arange(n, dtype=np.uint32) | np.uint32(0x40000000)
+    for key_bits in (1, 9, 32):
+        masked = keys & np.uint32((1 << key_bits) - 1)
+        order = np.argsort(masked, kind="stable")
+        k1, v1 = keys.copy(), vals.copy()
+        assert lib.gswt_debug_sort(renderer._h, k1.ctypes.data, v1.ctypes.data, n, key_bits) == 0
+        k2, v2, _, _ = renderer.debug_sort_ex(keys, vals, key_bits=key_bits)
+        assert np.array_equal(k1, keys[order]) and np.array_equal(v1, vals[order]), f"gswt_debug_sort, n {n} bits {key_bits}"
+        assert np.array_equal(k2, keys[order]) and np.array_equal(v2, vals[order]), f"gswt_debug_sort_ex, n {n} bits {key_bits}"
+        assert np.array_equal(k1, k2) and np.array_equal(v1, v2)
+
+
 def test_hook_refuses_inputs_it_cannot_run(renderer):
     """A key outside the range table or the key range, a range that needs more bits than the passes cover, an unknown workgroup width."""
     from gswt_renderer_amd.renderer import GSWTError
