@@ -62,10 +62,6 @@ gswt_ctx::~gswt_ctx()
     if (ev_unshard) hipEventDestroy(ev_unshard);
     for (auto& ds : sets)
         if (ds.ev_up) hipEventDestroy(ds.ev_up);
-    for (auto& sv : sty_pool)
-        if (sv.ev_copied) hipEventDestroy(sv.ev_copied);
-    for (auto& sv : shd_pool)
-        if (sv.ev_copied) hipEventDestroy(sv.ev_copied);
     for (auto& sl : slots) {
         sl.release_graph();
         for (auto& e : sl.ev) if (e) hipEventDestroy(e);
@@ -241,32 +237,20 @@ try {
             return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_tile_styles: styles[%zu]._pad = (%u, %u, %u), must be zero", i, e._pad[0], e._pad[1], e._pad[2]);
         on = on || e.tint_strength != 0 || e.dim != 0;
     }
-    if (!on) { c->sty_cur = -1; return GSWT_OK; }
-    // a version that is neither the current one nor the one a frame slot was last submitted with (frames in flight, re-runs): there is
-    // always one, kStyleVersions.  Nothing here waits for a frame: the staging of a free version is only waited for if its own earlier
-    // copy (of a table no frame ever used) is still queued on the ctx stream.
-    int v = -1;
-    for (int k = 0; k < kStyleVersions && v < 0; k++) {
-        bool used = k == c->sty_cur;
-        for (const auto& sl : c->slots) used = used || sl.args.sty_ver == k;
-        if (!used) v = k;
-    }
+    if (!on) { c->styles.off(); return GSWT_OK; }
+    const int v = c->styles.free_version(c->slots, &FrameModes::sty_ver);
     if (v < 0) return fail(c, GSWT_ERR_STATE, "gswt_set_tile_styles: no free table version");
-    StyleVersion& sv = c->sty_pool[v];
     hipSetDevice(c->device);
-    if (sv.copy_pending) { HIP_TRY(c, hipEventSynchronize(sv.ev_copied)); sv.copy_pending = false; }
-    if (!sv.ev_copied) HIP_TRY(c, hipEventCreateWithFlags(&sv.ev_copied, hipEventDisableTiming));
+    StyleVersion* sv = nullptr;
+    HIP_TRY(c, c->styles.begin_fill(v, &sv));
     // (buffers grow to twice the request: a host that sets a table per frame allocates once per version)
-    if (n_styles > sv.h.cap) HIP_TRY(c, sv.h.ensure(2 * n_styles));
-    HIP_TRY(c, sv.d.ensure_roomy(n_styles));
-    memcpy(sv.h.p, styles, n_styles * sizeof(gswt_tile_style));
-    // (on the ctx stream: a copy on the null stream would synchronise with every blocking stream; a frame submitted from now on starts
-    // behind everything queued on the ctx stream, enqueue_frame)
-    HIP_TRY(c, hipMemcpyAsync(sv.d.p, sv.h.p, n_styles * sizeof(gswt_tile_style), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(sv.ev_copied, c->stream));
-    sv.copy_pending = true;
-    sv.n = (uint32_t)n_styles;
-    c->sty_cur = v;
+    if (n_styles > sv->h.cap) HIP_TRY(c, sv->h.ensure(2 * n_styles));
+    HIP_TRY(c, sv->d.ensure_roomy(n_styles));
+    memcpy(sv->h.p, styles, n_styles * sizeof(gswt_tile_style));
+    // (on the ctx stream: a copy on the null stream would synchronise with every blocking stream)
+    HIP_TRY(c, hipMemcpyAsync(sv->d.p, sv->h.p, n_styles * sizeof(gswt_tile_style), hipMemcpyHostToDevice, c->stream));
+    sv->n = (uint32_t)n_styles;
+    HIP_TRY(c, c->styles.commit(v, c->stream));
     return GSWT_OK;
 } GSWT_CATCH
 
@@ -274,7 +258,7 @@ int gswt_set_shadow_map(gswt_ctx* c, const gswt_shadow_params* p, const float* d
 try {
     static_assert(sizeof(gswt_shadow_params) == 96, "gswt_shadow_params layout");
     if (!c) return GSWT_ERR_BAD_ARG;
-    if (!p || !depth) { c->shd_cur = -1; return GSWT_OK; }
+    if (!p || !depth) { c->shadows.off(); return GSWT_OK; }
     const float inf = std::numeric_limits<float>::infinity();
     const float* M = p->world_to_light;
     for (int k = 0; k < 16; k++)
@@ -295,42 +279,31 @@ try {
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: _pad = (%u, %u, %u), must be zero", p->_pad[0], p->_pad[1], p->_pad[2]);
     if (width < 1 || width > 4096) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: width = %d, not in 1..4096", width);
     if (height < 1 || height > 4096) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_shadow_map: height = %d, not in 1..4096", height);
-    // a version that is neither the current one nor the one a frame slot was last submitted with, as gswt_set_tile_styles picks its own:
-    // nothing here waits for a frame
-    int v = -1;
-    for (int k = 0; k < kShadowVersions && v < 0; k++) {
-        bool used = k == c->shd_cur;
-        for (const auto& sl : c->slots) used = used || sl.args.shd_ver == k;
-        if (!used) v = k;
-    }
+    const int v = c->shadows.free_version(c->slots, &FrameModes::shd_ver);
     if (v < 0) return fail(c, GSWT_ERR_STATE, "gswt_set_shadow_map: no free map version");
-    ShadowVersion& sv = c->shd_pool[v];
     const size_t n = (size_t)width * height;
     hipSetDevice(c->device);
-    if (sv.copy_pending) { HIP_TRY(c, hipEventSynchronize(sv.ev_copied)); sv.copy_pending = false; }
-    if (!sv.ev_copied) HIP_TRY(c, hipEventCreateWithFlags(&sv.ev_copied, hipEventDisableTiming));
+    ShadowVersion* sv = nullptr;
+    HIP_TRY(c, c->shadows.begin_fill(v, &sv));
     // (buffers grow to twice the request, like the styles': growing frees the old buffer, which waits for the device, so a host whose image
     // sizes creep upwards stalls once per version and doubling, not at every set)
-    HIP_TRY(c, sv.d.ensure_roomy(n));
-    // (on the ctx stream, like the styles' copy: the frames and proxy passes submitted from now on are ordered behind it; an earlier proxy
-    // pass that read this version is on the same stream, in front of the copy)
+    HIP_TRY(c, sv->d.ensure_roomy(n));
+    // (on the ctx stream, like the styles' copy: an earlier proxy pass that read this version is on the same stream, in front of the copy)
     if (depth_on_device)
-        HIP_TRY(c, hipMemcpyAsync(sv.d.p, depth, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(sv->d.p, depth, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     else {
-        if (n > sv.h.cap) HIP_TRY(c, sv.h.ensure(2 * n));
-        memcpy(sv.h.p, depth, n * sizeof(float));
-        HIP_TRY(c, hipMemcpyAsync(sv.d.p, sv.h.p, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (n > sv->h.cap) HIP_TRY(c, sv->h.ensure(2 * n));
+        memcpy(sv->h.p, depth, n * sizeof(float));
+        HIP_TRY(c, hipMemcpyAsync(sv->d.p, sv->h.p, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     }
-    HIP_TRY(c, hipEventRecord(sv.ev_copied, c->stream));
-    sv.copy_pending = true;
-    Shadow& k = sv.p;
+    Shadow& k = sv->p;
     k = Shadow{};
     for (int r = 0; r < 3; r++)
         for (int j = 0; j < 4; j++) k.row[r][j] = M[4 * j + r];
     k.bias = p->bias; k.strength = p->strength;
     for (int j = 0; j < 3; j++) k.shade[j] = p->shade_color[j];
-    k.w = width; k.h = height; k.z = sv.d.p;
-    c->shd_cur = v;
+    k.w = width; k.h = height; k.z = sv->d.p;
+    HIP_TRY(c, c->shadows.commit(v, c->stream));
     return GSWT_OK;
 } GSWT_CATCH
 
@@ -366,10 +339,54 @@ try {
 
 // ---- frame machinery ------------------------------------------------------------------------------
 // GSWT_OPT_ANTIALIAS: s = 4 v / splat_scale^2 with v = value / 1024 (exact), one binary32 operation per operator (include/gswt_hip.h)
-static float antialias_s(int value, float splat_scale)
+static float antialias_s(int value, float splat_scale) { return (4.0f * ((float)value / 1024.0f)) / (splat_scale * splat_scale); }
+
+// What a frame submitted now keeps from the context (submit_frame; validate_frame_modes has accepted it, so s is a finite positive number).
+static FrameModes frame_modes(const gswt_ctx& c, const gswt_scene_uniforms& su)
 {
-    const float v = (float)value / 1024.0f;
-    return (4.0f * v) / (splat_scale * splat_scale);
+    const float aa_s = c.opt.antialias > 0 ? antialias_s(c.opt.antialias, su.splat_scale) : 0.0f;
+    return FrameModes{c.opt.strict_vs != 0, c.opt.projection == 1, aa_s, atmo_constants(c.atm), c.styles.cur, c.shadows.cur};
+}
+
+// The preconditions of the modes a frame submitted now would run with.  Every mode exists in the strict vertex stage only (project_modes,
+// gswt_frame_modes.h); the orthographic projection and the pixel filter also constrain the frame's uniforms.
+static int validate_frame_modes(gswt_ctx* c, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const ShardGeom& g)
+{
+    const float inf = std::numeric_limits<float>::infinity();
+    const bool ortho = c->opt.projection == 1, aa = c->opt.antialias > 0;
+    if (ortho) {
+        // the projection must be affine (clip w = 1 exactly) and focal is pixels per world unit
+        const float* P = cam->projection;
+        if (!(P[3] == 0.0f && P[7] == 0.0f && P[11] == 0.0f && P[15] == 1.0f))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 needs an affine projection, bottom row (0, 0, 0, 1), not (%g, %g, %g, %g)",
+                        P[3], P[7], P[11], P[15]);
+        for (int k = 0; k < 2; k++)
+            if (!(cam->focal[k] > 0.0f) || !(cam->focal[k] < inf))
+                return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 needs a finite focal > 0 (pixels per world unit), not focal[%d] = %g", k, cam->focal[k]);
+    }
+    // (mode is on, who needs the strict sequence, which form the v2 sequence lacks); the first one on is refused, so what follows checks a strict frame
+    const struct { bool on; const char* who; const char* form; } modes[] = {
+        {ortho, "GSWT_OPT_PROJECTION = 1", "orthographic"},
+        {aa, "GSWT_OPT_ANTIALIAS > 0", "filtered"},
+        {c->atm.fade_end > 0.0f || c->atm.fog_density > 0.0f, "gswt_set_atmosphere's fade or fog", "atmospheric"},
+        {c->styles.cur >= 0, "gswt_set_tile_styles' table", "styled"},
+        {c->shadows.cur >= 0, "gswt_set_shadow_map's map", "shadowed"}};
+    for (const auto& m : modes)
+        if (m.on && !c->opt.strict_vs)
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: %s needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no %s form)", m.who, m.form);
+    if (ortho && g.cols)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 does not take column-band shards (their band cull is perspective-only); use GSWT_SHARD_ROWS");
+    if (aa) {
+        // s = 4 v / splat_scale^2 needs a splat_scale, and one whose square neither overflows (s = 0: the filter would switch off silently)
+        // nor underflows (s = inf: every alpha 0)
+        if (su->splat_scale == 0.0f || !(std::fabs(su->splat_scale) < inf))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_ANTIALIAS > 0 needs a finite splat_scale != 0, not %g", su->splat_scale);
+        const float s = antialias_s(c->opt.antialias, su->splat_scale);
+        if (!(s > 0.0f && s < inf))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_ANTIALIAS = %d with splat_scale %g gives s = 4 v / splat_scale^2 = %g, not a finite positive number",
+                        c->opt.antialias, su->splat_scale, s);
+    }
+    return GSWT_OK;
 }
 
 // A frame is enqueued without any host round trip (enqueue_frame) and collected later (finish_frame).
@@ -399,43 +416,7 @@ static int validate_frame(gswt_ctx* c, const gswt_camera_uniforms* cam, const gs
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: unknown out_format %u", cfg->out_format);
     if (out_is_video((int)cfg->out_format) && ((width | height) & 1))
         return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: the video formats need an even target size, not %dx%d", width, height);
-    if (c->opt.projection == 1) {
-        // an orthographic frame (GSWT_OPT_PROJECTION = 1): the projection must be affine (clip w = 1 exactly), focal is pixels per world unit,
-        // and only the strict vertex stage and row shards have an orthographic form
-        const float* P = cam->projection;
-        if (!(P[3] == 0.0f && P[7] == 0.0f && P[11] == 0.0f && P[15] == 1.0f))
-            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 needs an affine projection, bottom row (0, 0, 0, 1), not (%g, %g, %g, %g)",
-                        P[3], P[7], P[11], P[15]);
-        for (int k = 0; k < 2; k++)
-            if (!(cam->focal[k] > 0.0f) || !(cam->focal[k] < std::numeric_limits<float>::infinity()))
-                return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 needs a finite focal > 0 (pixels per world unit), not focal[%d] = %g", k, cam->focal[k]);
-        if (!c->opt.strict_vs)
-            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no orthographic form)");
-        if (g.cols)
-            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_PROJECTION = 1 does not take column-band shards (their band cull is perspective-only); use GSWT_SHARD_ROWS");
-    }
-    if (c->opt.antialias > 0) {
-        // a filtered frame (GSWT_OPT_ANTIALIAS > 0): only the strict vertex stage has a filtered form, and s = 4 v / splat_scale^2 needs a splat_scale
-        if (!c->opt.strict_vs)
-            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_ANTIALIAS > 0 needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no filtered form)");
-        if (su->splat_scale == 0.0f || !(std::fabs(su->splat_scale) < std::numeric_limits<float>::infinity()))
-            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_ANTIALIAS > 0 needs a finite splat_scale != 0, not %g", su->splat_scale);
-        // ... and one whose square neither overflows (s = 0: the filter would switch off silently) nor underflows (s = inf: every alpha 0)
-        const float s = antialias_s(c->opt.antialias, su->splat_scale);
-        if (!(s > 0.0f && s < std::numeric_limits<float>::infinity()))
-            return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: GSWT_OPT_ANTIALIAS = %d with splat_scale %g gives s = 4 v / splat_scale^2 = %g, not a finite positive number",
-                        c->opt.antialias, su->splat_scale, s);
-    }
-    // a frame with the far fade or the fog on (gswt_set_atmosphere): only the strict vertex stage has an atmospheric form
-    if ((c->atm.fade_end > 0.0f || c->atm.fog_density > 0.0f) && !c->opt.strict_vs)
-        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: gswt_set_atmosphere's fade or fog needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no atmospheric form)");
-    // nor a styled one (gswt_set_tile_styles with a table on)
-    if (c->sty_cur >= 0 && !c->opt.strict_vs)
-        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: gswt_set_tile_styles' table needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no styled form)");
-    // nor a shadowed one (gswt_set_shadow_map with a map on)
-    if (c->shd_cur >= 0 && !c->opt.strict_vs)
-        return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: gswt_set_shadow_map's map needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no shadowed form)");
-    return GSWT_OK;
+    return validate_frame_modes(c, cam, su, g);
 }
 
 // GSWT_OPT_GRAPH: the frame's launch sequence was recorded, not launched (gswt_device.h); replay it as one hipGraphLaunch on the
@@ -510,7 +491,7 @@ static Frame make_frame(const gswt_ctx& c, const FrameArgs& a, const ShardGeom& 
     memcpy(f.transition_dist, su->transition_dist_vec, 64);
     for (int k = 0; k < 3; k++) { f.height_map_scale[k] = su->height_map_scale[k]; f.scene_scale[k] = su->scene_scale[k]; }
     f.culling_dist = cfg->culling_dist; f.lod_enable_mask = cfg->lod_enable_mask; f.t_eps = cfg->transmittance_eps;
-    f.has_depth = a.d_bgd ? 1 : 0;
+    f.has_depth = a.img.d_bgd ? 1 : 0;
     f.width = width; f.height = height;
     // the shard's screen tiles: every column of the interleaved tile rows, or (column mode) a contiguous band of tile columns
     f.tiles_x = g.col1 - g.col0; f.tiles_y = (height + kTile - 1) / kTile;
@@ -552,8 +533,8 @@ static Frame make_frame(const gswt_ctx& c, const FrameArgs& a, const ShardGeom& 
     // (0 = "divide": a one-row map, map_wh_y == 1, would wrap the magic to 0 and the multiply-high quotient to 0 -- ADVICE r3)
     f.map_wh_y_magic = f.map_wh_y >= 2u && f.map_wh_y < 65536u ? 0xFFFFFFFFu / f.map_wh_y + 1u : 0u;
     f.tiles_x_magic = f.tiles_x > 0 && f.tiles_x < 65536 ? 0xFFFFFFFFu / (uint32_t)f.tiles_x + 1u : 0u;
-    f.aa_s = a.aa_s;
-    f.atm = a.atm;
+    f.aa_s = a.modes.aa_s;
+    f.atm = a.modes.atm;
     return f;
 }
 
@@ -563,8 +544,9 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
                               FrameBufs& b)
 {
     const FrameArgs& a = sl.args;
+    const FrameImages& im = a.img;
     const size_t nt = (size_t)n_tiles, n_slots_all = (size_t)D.n_chunks * kChunk;
-    const bool depth_order = a.cfg.order_mode == GSWT_ORDER_DEPTH, need_depths = a.d_bgd != nullptr || depth_order || a.d_out_depth != nullptr || a.d_out_pick != nullptr;
+    const bool depth_order = a.cfg.order_mode == GSWT_ORDER_DEPTH, need_depths = im.d_bgd != nullptr || depth_order || im.d_out_depth != nullptr || im.d_out_pick != nullptr;
     const uint32_t seg = (uint32_t)c->opt.segment;      // (opt_segment: the measured segment sizes are at Options::segment, gswt_ctx.h)
     b.n_cells = f.band_cull ? (2u * f.map_half_wh[0] + 1u) * (2u * f.map_half_wh[1] + 1u) : 0u;
     HIP_TRY(c, sl.rects.ensure(n_slots_all + 1));
@@ -599,18 +581,19 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     if (depth_order) { HIP_TRY(c, sl.aux_a.ensure_roomy((size_t)cap + 1)); HIP_TRY(c, sl.aux_b.ensure_roomy((size_t)cap + 1)); }
     HIP_TRY(c, sl.item_base.ensure_roomy(nt + 2));
     HIP_TRY(c, sl.partials.ensure_roomy((nt + cap / seg + 1) * 256));
-    if (a.d_out_depth) HIP_TRY(c, sl.partials_z.ensure_roomy((nt + cap / seg + 1) * 256));
-    if (a.d_out_pick) HIP_TRY(c, sl.partials_pick.ensure_roomy((nt + cap / seg + 1) * 256));
+    if (im.d_out_depth) HIP_TRY(c, sl.partials_z.ensure_roomy((nt + cap / seg + 1) * 256));
+    if (im.d_out_pick) HIP_TRY(c, sl.partials_pick.ensure_roomy((nt + cap / seg + 1) * 256));
     HIP_TRY(c, sl.item_tab.ensure_roomy(nt + cap / seg + 2));
 
     b.draws = D.draws; b.n_chunks = D.n_chunks; b.chunk_tab = D.chunk_tab.p; b.chunk_tab_xcd = D.chunk_tab_xcd.p;
     b.static_list = c->static_list.p; b.merged_list = D.merged_list.p; b.merged_map = D.merged_map.p;
     b.tex = c->tex.p; b.hmap = c->hmap.p; b.boxes = c->static_boxes.p;
-    // (the version the frame was submitted with: no gswt_set_tile_styles refills it while this slot names it)
-    b.styles = a.sty_ver >= 0 ? c->sty_pool[a.sty_ver].d.p : nullptr; b.n_styles = a.sty_ver >= 0 ? c->sty_pool[a.sty_ver].n : 0u;
-    b.shadow = shadow_version(c, a.shd_ver);
-    b.bg_rgba = a.d_bg; b.bg_depth = a.d_bgd; b.out = a.d_out; b.out_depth = a.d_out_depth; b.host_counters = sl.hc_dev;
-    b.out_pick = reinterpret_cast<uint4*>(a.d_out_pick);
+    // (the versions the frame was submitted with: no setter refills them while this slot names them)
+    const StyleVersion* const sty = c->styles.get(a.modes.sty_ver);
+    b.styles = sty ? sty->d.p : nullptr; b.n_styles = sty ? sty->n : 0u;
+    b.shadow = shadow_version(c, a.modes.shd_ver);
+    b.bg_rgba = im.d_bg; b.bg_depth = im.d_bgd; b.out = im.d_out; b.out_depth = im.d_out_depth; b.host_counters = sl.hc_dev;
+    b.out_pick = reinterpret_cast<uint4*>(im.d_out_pick);
     b.n_tiles = (uint32_t)n_tiles; b.pair_cap = cap; b.seg = seg;
     b.rects = sl.rects.p; b.recs = sl.recs.p; b.depths = need_depths ? sl.depths.p : nullptr; b.col_f = sl.col_f.p; b.dbg = c->dbg.p;
     b.draw_culled = sl.draw_culled.p; b.cell_culled = sl.cell_culled.p;
@@ -623,9 +606,9 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     b.keys_a = sl.keys_a.p; b.keys_b = sl.keys_b.p; b.vals_a = sl.vals_a.p; b.vals_b = sl.vals_b.p; b.aux_a = sl.aux_a.p; b.aux_b = sl.aux_b.p;
     b.ranges = sl.ranges.p;
     b.long_tiles = reinterpret_cast<uint32_t*>(sl.ranges.p) + range_words;
-    b.item_base = sl.item_base.p; b.item_tab = sl.item_tab.p; b.partials = sl.partials.p; b.partials_z = a.d_out_depth ? sl.partials_z.p : nullptr;
-    b.partials_pick = a.d_out_pick ? sl.partials_pick.p : nullptr;
-    const bool time_pick = a.d_out_pick != nullptr && c->opt.timing >= 1;
+    b.item_base = sl.item_base.p; b.item_tab = sl.item_tab.p; b.partials = sl.partials.p; b.partials_z = im.d_out_depth ? sl.partials_z.p : nullptr;
+    b.partials_pick = im.d_out_pick ? sl.partials_pick.p : nullptr;
+    const bool time_pick = im.d_out_pick != nullptr && c->opt.timing >= 1;
     b.ev_pick_begin = time_pick ? sl.ev[kEvPickBegin] : nullptr; b.ev_pick_end = time_pick ? sl.ev[kEvPickEnd] : nullptr;
     sl.pick_timed = time_pick && n_tiles > 0;
     return GSWT_OK;
@@ -715,9 +698,9 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         if (hipEventQuery(D.ev_up) == hipSuccess) D.built = true;
         else HIP_TRY(c, hipStreamWaitEvent(s, D.ev_up, 0));
     }
-    if (g.world > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(a.d_out, 0, g.bytes, s));
-    if (g.world > 1 && out_px > 0 && a.d_out_depth) HIP_TRY(c, hipMemsetAsync(a.d_out_depth, 0, out_px * sizeof(float), s));
-    if (g.world > 1 && out_px > 0 && a.d_out_pick) HIP_TRY(c, hipMemsetAsync(a.d_out_pick, 0, out_px * sizeof(gswt_pick), s));
+    if (g.world > 1 && out_px > 0) HIP_TRY(c, hipMemsetAsync(a.img.d_out, 0, g.bytes, s));
+    if (g.world > 1 && out_px > 0 && a.img.d_out_depth) HIP_TRY(c, hipMemsetAsync(a.img.d_out_depth, 0, out_px * sizeof(float), s));
+    if (g.world > 1 && out_px > 0 && a.img.d_out_pick) HIP_TRY(c, hipMemsetAsync(a.img.d_out_pick, 0, out_px * sizeof(gswt_pick), s));
     // GSWT_OPT_GRAPH: from here to the end of the frame the launch sites record instead of launching (frames that carry timing
     // events, debug varyings and shards without tiles launch as before)
     const bool use_graph = c->opt.graph != 0 && c->opt.timing == 0 && !dbg && n_tiles > 0 && sl.hc_dev != nullptr;
@@ -737,7 +720,7 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
         }
         sl.n_launch_eff = (uint32_t)eff;
     }
-    launch_project(s, f, b, sl.n_launch_eff, dbg, a.strict_vs, a.ortho);
+    launch_project(s, f, b, sl.n_launch_eff, dbg, project_modes(a.modes));
     if (c->opt.timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvProjected], s));
     // ---- emit + sort, ranges, composite
     const uint32_t* vals = nullptr;
@@ -826,21 +809,12 @@ static int finish_frame(gswt_ctx* c, FrameSlot& sl)
 
 // Submits a frame in slot `sl` (gswt_render, gswt_render_async): the slot's stream on first use, the draw set current now, the arguments.
 static int submit_frame(gswt_ctx* c, FrameSlot& sl, const gswt_camera_uniforms* cam, const gswt_scene_uniforms* su, const gswt_render_config* cfg,
-                        int width, int height, const float4* d_bg, const float* d_bgd, float4* d_out, float* d_out_depth, gswt_pick* d_out_pick)
+                        int width, int height, const FrameImages& img)
 {
     if (!sl.stream) HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));      // a slot past the fourth: first use
     activate_pending(c, false);
     sl.set = c->cur_set;
-    FrameArgs& a = sl.args;
-    a.cam = *cam; a.su = *su; a.cfg = *cfg; a.width = width; a.height = height; a.d_bg = d_bg; a.d_bgd = d_bgd; a.d_out = d_out;
-    a.d_out_depth = d_out_depth; a.d_out_pick = d_out_pick;
-    a.strict_vs = c->opt.strict_vs != 0;
-    a.ortho = c->opt.projection == 1;
-    // (validate_frame refused a splat_scale with which s is not a finite positive number)
-    a.aa_s = c->opt.antialias > 0 ? antialias_s(c->opt.antialias, su->splat_scale) : 0.0f;
-    a.atm = atmo_constants(c->atm);
-    a.sty_ver = c->sty_cur;
-    a.shd_ver = c->shd_cur;
+    sl.args = FrameArgs{*cam, *su, *cfg, width, height, img, frame_modes(*c, *su)};
     return enqueue_frame(c, sl);
 }
 
@@ -864,6 +838,29 @@ static int select_slot(const gswt_ctx* c, bool reuse_oldest)
     int si = 0;
     for (int k = 1; k < kFrameSlots; k++) if (c->slots[k].seq < c->slots[si].seq) si = k;
     return si;
+}
+
+// gswt_render's images (null: none).  An input of n elements: read in place on the device, or copied from the host into the context's
+// staging on the ctx stream.
+template <typename T>
+static int stage_input(gswt_ctx* c, DevBuf<T>& staging, const float* src, size_t n, bool on_device, const T** d)
+{
+    if (!src || on_device) { *d = reinterpret_cast<const T*>(src); return GSWT_OK; }
+    HIP_TRY(c, staging.ensure(n));
+    HIP_TRY(c, hipMemcpyAsync(staging.p, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    *d = staging.p;
+    return GSWT_OK;
+}
+// An output of `bytes` bytes: written in place on the device, or into the context's staging and copied to the host behind the frame (`back`).
+struct HostOutput { void* host = nullptr; const void* dev = nullptr; size_t bytes = 0; };
+template <typename T, typename U, typename H>
+static int stage_output(gswt_ctx* c, DevBuf<U>& staging, H* out, size_t bytes, bool on_device, T** d, HostOutput* back)
+{
+    if (!out || on_device) { *d = reinterpret_cast<T*>(out); return GSWT_OK; }
+    HIP_TRY(c, staging.ensure((bytes + sizeof(U) - 1) / sizeof(U)));
+    *d = reinterpret_cast<T*>(staging.p);
+    *back = HostOutput{out, staging.p, bytes};
+    return GSWT_OK;
 }
 
 extern "C" {
@@ -892,42 +889,24 @@ try {
     rc = check_frame_outputs(c, "gswt_render", "", out_rgba, out_depth, out_pick);
     if (rc != GSWT_OK) return rc;
     hipSetDevice(c->device);
-    hipStream_t s = c->stream;
     HIP_TRY(c, collect_pending(c));                // frames still in flight from the async API keep their tickets
     const ShardGeom g = shard_geom(*cfg, width, height);
-    const size_t out_px = g.px, out_bytes = g.bytes, npx = (size_t)width * height;
-    const float4* d_bg = nullptr; const float* d_bgd = nullptr; float4* d_out = nullptr; float* d_outz = nullptr; gswt_pick* d_outp = nullptr;
-    if (bg_rgba) {
-        if (bg_on_device) d_bg = reinterpret_cast<const float4*>(bg_rgba);
-        else { HIP_TRY(c, c->bg_rgba.ensure(npx)); HIP_TRY(c, hipMemcpyAsync(c->bg_rgba.p, bg_rgba, npx * 16, hipMemcpyHostToDevice, s)); d_bg = c->bg_rgba.p; }
-    }
-    if (bg_depth) {
-        if (bg_on_device) d_bgd = bg_depth;
-        else { HIP_TRY(c, c->bg_depth.ensure(npx)); HIP_TRY(c, hipMemcpyAsync(c->bg_depth.p, bg_depth, npx * 4, hipMemcpyHostToDevice, s)); d_bgd = c->bg_depth.p; }
-    }
-    if (out_on_device) d_out = reinterpret_cast<float4*>(out_rgba);
-    else { HIP_TRY(c, c->out_img.ensure((out_bytes + 15) / 16)); d_out = c->out_img.p; }
-    if (out_depth) {
-        if (out_on_device) d_outz = out_depth;
-        else { HIP_TRY(c, c->out_depth_img.ensure(out_px)); d_outz = c->out_depth_img.p; }
-    }
-    if (out_pick) {
-        if (out_on_device) d_outp = out_pick;
-        else { HIP_TRY(c, c->out_pick_img.ensure(out_px)); d_outp = reinterpret_cast<gswt_pick*>(c->out_pick_img.p); }
-    }
+    const size_t out_px = g.px, npx = (size_t)width * height;
+    FrameImages img;
+    HostOutput back[3];
+    if ((rc = stage_input(c, c->bg_rgba, bg_rgba, npx, bg_on_device != 0, &img.d_bg)) != GSWT_OK) return rc;
+    if ((rc = stage_input(c, c->bg_depth, bg_depth, npx, bg_on_device != 0, &img.d_bgd)) != GSWT_OK) return rc;
+    if ((rc = stage_output(c, c->out_img, out_rgba, g.bytes, out_on_device != 0, &img.d_out, &back[0])) != GSWT_OK) return rc;
+    if ((rc = stage_output(c, c->out_depth_img, out_depth, out_px * sizeof(float), out_on_device != 0, &img.d_out_depth, &back[1])) != GSWT_OK) return rc;
+    if ((rc = stage_output(c, c->out_pick_img, out_pick, out_px * sizeof(gswt_pick), out_on_device != 0, &img.d_out_pick, &back[2])) != GSWT_OK) return rc;
     const int si = select_slot(c, false);
     if (si < 0) return fail(c, GSWT_ERR_STATE, "gswt_render: every frame slot holds an uncollected gswt_render_async ticket");
     FrameSlot& sl = c->slots[si];
-    rc = submit_frame(c, sl, cam, su, cfg, width, height, d_bg, d_bgd, d_out, d_outz, d_outp);
-    if (rc != GSWT_OK) return rc;
-    rc = finish_frame(c, sl);
-    if (rc != GSWT_OK) return rc;
-    if (!out_on_device) {
-        HIP_TRY(c, hipMemcpyAsync(out_rgba, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-        if (out_depth) HIP_TRY(c, hipMemcpyAsync(out_depth, d_outz, out_px * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (out_pick) HIP_TRY(c, hipMemcpyAsync(out_pick, d_outp, out_px * sizeof(gswt_pick), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-    }
+    if ((rc = submit_frame(c, sl, cam, su, cfg, width, height, img)) != GSWT_OK) return rc;
+    if ((rc = finish_frame(c, sl)) != GSWT_OK) return rc;
+    for (const HostOutput& o : back)
+        if (o.host) HIP_TRY(c, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (!out_on_device) HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GSWT_OK;
 } GSWT_CATCH
 
@@ -962,8 +941,8 @@ try {
     }
     sl.seq = ++c->frame_seq;
     sl.gather_recorded = false;
-    rc = submit_frame(c, sl, cam, su, cfg, width, height, reinterpret_cast<const float4*>(bg_rgba_dev), bg_depth_dev,
-                      reinterpret_cast<float4*>(out_rgba_dev), out_depth_dev, out_pick_dev);
+    rc = submit_frame(c, sl, cam, su, cfg, width, height, FrameImages{reinterpret_cast<const float4*>(bg_rgba_dev), bg_depth_dev,
+                                                                      reinterpret_cast<float4*>(out_rgba_dev), out_depth_dev, out_pick_dev});
     if (rc != GSWT_OK) return rc;
     sl.pending = true; sl.collected = false;
     *ticket = si;

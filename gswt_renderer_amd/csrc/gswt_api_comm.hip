@@ -202,13 +202,13 @@ try {
                     sl.args.cfg.shard_index, g.world, c->comm_rank, c->comm_world);
     hipSetDevice(c->device);
     if (g.world == 1) {                                   // nothing to gather: the shard is the frame
-        if (reinterpret_cast<float4*>(frame_out_dev) != sl.args.d_out)
-            HIP_TRY(c, hipMemcpyAsync(frame_out_dev, sl.args.d_out, g.bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (reinterpret_cast<float4*>(frame_out_dev) != sl.args.img.d_out)
+            HIP_TRY(c, hipMemcpyAsync(frame_out_dev, sl.args.img.d_out, g.bytes, hipMemcpyDeviceToDevice, c->stream));
         return GSWT_OK;
     }
     HIP_TRY(c, c->gather_buf.ensure(((size_t)g.world * g.bytes + 15) / 16));
     // (the shard moves as 4-byte words whatever its format: g.bytes is a multiple of 4)
-    const int nrc = g_rccl.AllGather(sl.args.d_out, c->gather_buf.p, g.bytes / 4, kNcclFloat, c->comm, c->stream);
+    const int nrc = g_rccl.AllGather(sl.args.img.d_out, c->gather_buf.p, g.bytes / 4, kNcclFloat, c->comm, c->stream);
     if (nrc != 0) return fail(c, GSWT_ERR_RCCL, "ncclAllGather: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nrc) : "error");
     launch_unshard(c->stream, c->gather_buf.p, frame_out_dev, sl.args.width, sl.args.height, g.world, g.rows_padded, g.band_px,
                    (int)sl.args.cfg.out_format);
@@ -253,7 +253,7 @@ try {
         for (int p = 0; p < n; p++)
             if (p != r && ctxs[p]->unshard_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, ctxs[p]->ev_unshard, 0));
         for (int p = 0; p < n; p++)
-            HIP_TRY(c, hipMemcpyPeerAsync(reinterpret_cast<char*>(ctxs[p]->gather_buf.p) + (size_t)r * g0.bytes, ctxs[p]->device, sl.args.d_out, c->device,
+            HIP_TRY(c, hipMemcpyPeerAsync(reinterpret_cast<char*>(ctxs[p]->gather_buf.p) + (size_t)r * g0.bytes, ctxs[p]->device, sl.args.img.d_out, c->device,
                                           g0.bytes, c->stream));
         HIP_TRY(c, hipEventRecord(c->ev_push, c->stream));
     }
@@ -264,7 +264,7 @@ try {
         const FrameSlot& sl = c->slots[tickets[p]];
         for (int r = 0; r < n; r++) HIP_TRY(c, hipStreamWaitEvent(c->stream, ctxs[r]->ev_push, 0));
         if (n == 1) {
-            if (reinterpret_cast<float4*>(frames_out_dev[p]) != sl.args.d_out)
+            if (reinterpret_cast<float4*>(frames_out_dev[p]) != sl.args.img.d_out)
                 HIP_TRY(c, hipMemcpyAsync(frames_out_dev[p], c->gather_buf.p, g0.bytes, hipMemcpyDeviceToDevice, c->stream));
         } else {
             launch_unshard(c->stream, c->gather_buf.p, frames_out_dev[p], sl.args.width, sl.args.height, n, g0.rows_padded, g0.band_px, fmt0);

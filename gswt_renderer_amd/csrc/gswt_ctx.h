@@ -161,49 +161,46 @@ struct DrawSet {
     uint64_t n_entries = 0;
 };
 
+struct FrameImages {                       // the frame's images, all on the device (null: none; d_out is never null)
+    const float4* d_bg = nullptr;          // the background's colour ...
+    const float* d_bgd = nullptr;          // ... and depth
+    float4* d_out = nullptr;
+    float* d_out_depth = nullptr;          // gswt_render_depth / gswt_render_async_depth: the frame's depth image
+    gswt_pick* d_out_pick = nullptr;       // gswt_render_pick / gswt_render_async_pick: the frame's pick image
+};
+
+// What a frame keeps from its submission: the state in force when it was submitted, which frames in flight and re-runs keep whatever is set
+// meanwhile.  frame_modes (gswt_api.hip) takes the snapshot, project_modes (gswt_frame_modes.h) reads k_project's instantiation from it.
+struct FrameModes {
+    bool strict_vs = false, ortho = false; // GSWT_OPT_STRICT_VS, GSWT_OPT_PROJECTION = 1
+    float aa_s = 0.0f;                     // GSWT_OPT_ANTIALIAS: s = 4 v / splat_scale^2 (0: off)
+    Atmo atm = {};                         // gswt_set_atmosphere's block with its derived constants (all zero: off)
+    int sty_ver = -1, shd_ver = -1;        // gswt_set_tile_styles' table, gswt_set_shadow_map's block and image: their versions in gswt_ctx::styles / shadows (-1: off)
+};
+
 struct FrameArgs {
     gswt_camera_uniforms cam;
     gswt_scene_uniforms su;
     gswt_render_config cfg;
     int width = 0, height = 0;
-    const float4* d_bg = nullptr;
-    const float* d_bgd = nullptr;
-    float4* d_out = nullptr;
-    float* d_out_depth = nullptr;          // gswt_render_depth / gswt_render_async_depth: the frame's depth image (null: none)
-    gswt_pick* d_out_pick = nullptr;       // gswt_render_pick / gswt_render_async_pick: the frame's pick image (null: none)
-    // the three options a frame keeps from its submission (the others are read at enqueue)
-    bool strict_vs = false;                // GSWT_OPT_STRICT_VS as it stood when the frame was submitted (a re-run keeps it)
-    bool ortho = false;                    // GSWT_OPT_PROJECTION likewise: k_project<.,.,true,ORTHO> (frames in flight and re-runs keep their own)
-    float aa_s = 0.0f;                     // GSWT_OPT_ANTIALIAS as it stood when the frame was submitted: s = 4 v / splat_scale^2 (a re-run keeps it)
-    Atmo atm = {};                         // gswt_set_atmosphere's block likewise, with its derived constants (all zero: off)
-    int sty_ver = -1;                      // gswt_set_tile_styles' table likewise: its version in gswt_ctx::sty_pool (-1: styles off)
-    int shd_ver = -1;                      // gswt_set_shadow_map's block and image likewise: their version in gswt_ctx::shd_pool (-1: shadows off)
+    FrameImages img;
+    FrameModes modes;
 };
 
-// One version of gswt_set_tile_styles' table: pinned staging (the host's entries, copied inside the call) and the device copy k_project
-// reads, filled by one asynchronous copy on the ctx stream.  A version is in use while it is the current one or a frame slot was last
-// submitted with it (FrameArgs::sty_ver: frames in flight and re-runs); any other one may be refilled.
+// One version of gswt_set_tile_styles' table (a VersionPool payload): pinned staging (the host's entries) and the device copy k_project reads.
 struct StyleVersion {
     HostBuf<uint2> h;
     DevBuf<uint2> d;
     uint32_t n = 0;
-    hipEvent_t ev_copied = nullptr;        // behind the copy: the staging may be refilled once it has fired
-    bool copy_pending = false;
 };
-// the frame slots' versions and the current one can all differ: one more is always free
-constexpr int kStyleVersions = kFrameSlots + 2;
 
-// One version of gswt_set_shadow_map's map, held like a StyleVersion: the validated block as the kernels read it (p.z: the device image),
-// pinned staging for an image that comes from a host pointer (a device image is copied device to device, no staging), and the copy's
-// event.  In use while it is the current one or a frame slot was last submitted with it (FrameArgs::shd_ver); any other one may be refilled.
+// One version of gswt_set_shadow_map's map, likewise: the validated block as the kernels read it (p.z: the device image) and pinned staging
+// for an image that comes from a host pointer (a device image is copied device to device, no staging).
 struct ShadowVersion {
     HostBuf<float> h;
     DevBuf<float> d;
     Shadow p = {};
-    hipEvent_t ev_copied = nullptr;        // behind the copy: the staging may be refilled once it has fired
-    bool copy_pending = false;
 };
-constexpr int kShadowVersions = kFrameSlots + 2;
 
 // A frame's events on its slot's stream.  GSWT_OPT_TIMING >= 1 records kEvStart, kEvEnd and the compositor kernel's pair, 2 also the
 // stage boundaries in between (nothing runs between kEvSorted and kEvRanges); kEvDone follows the frame's last command in any case.
@@ -271,8 +268,43 @@ struct FrameSlot {
     }
 };
 
-// gswt_set_option's values with their defaults.  strict_vs, projection and antialias (and gswt_set_atmosphere's block, gswt_ctx::atm, and
-// gswt_set_tile_styles' table version, gswt_ctx::sty_cur, and gswt_set_shadow_map's version, gswt_ctx::shd_cur) are snapshotted into FrameArgs when a frame is submitted; every other one is read when the frame (or the sort event) is enqueued.
+// A resource that frames in flight keep their own version of (gswt_set_tile_styles' table, gswt_set_shadow_map's map), filled by asynchronous
+// copies on the ctx stream.  A version is in use while it is the current one or a frame slot was last submitted with it (frames in flight and
+// re-runs; `ver`: the FrameModes member that names it).  Any other one may be refilled, and of kFrameSlots + 2 one always can: no setter waits for a frame.
+template <typename Payload>
+struct VersionPool {
+    static constexpr int kVersions = kFrameSlots + 2;
+    struct Version : Payload {
+        hipEvent_t ev_copied = nullptr;    // behind the version's copy: its staging may be refilled once it has fired ...
+        bool copy_pending = false;         // ... and until then a refill waits for it
+        ~Version() { if (ev_copied) hipEventDestroy(ev_copied); }
+    };
+    Version pool[kVersions];
+    int cur = -1;                          // the version in force (-1: off), read when a frame is submitted
+    void off() { cur = -1; }
+    const Payload* get(int v) const { return v >= 0 ? &pool[v] : nullptr; }
+    int free_version(const FrameSlot (&slots)[kFrameSlots], int FrameModes::*ver) const
+    { return gswt::free_version(kVersions, cur, slots, [ver](const FrameSlot& sl) { return sl.args.modes.*ver; }); }
+    // Before free version v is filled: only its own earlier copy (of a payload no frame ever used) can still be queued on the ctx stream.
+    hipError_t begin_fill(int v, Payload** p)
+    {
+        Version& e = pool[v];
+        *p = &e;
+        const hipError_t err = e.copy_pending ? hipEventSynchronize(e.ev_copied) : hipSuccess;
+        if (err != hipSuccess) return err;
+        e.copy_pending = false;
+        return e.ev_copied ? hipSuccess : hipEventCreateWithFlags(&e.ev_copied, hipEventDisableTiming);
+    }
+    // Behind version v's copies on the ctx stream: frames and proxy passes submitted from now on read it, and start behind that stream's queue.
+    hipError_t commit(int v, hipStream_t ctx_stream)
+    {
+        const hipError_t err = hipEventRecord(pool[v].ev_copied, ctx_stream);
+        if (err == hipSuccess) { pool[v].copy_pending = true; cur = v; }
+        return err;
+    }
+};
+
+// gswt_set_option's values with their defaults: read when the frame (or the sort event) is enqueued, but for the ones FrameModes snapshots.
 struct Options {
     int no_prefilter = 0;                  // GSWT_OPT_NO_LOD_PREFILTER
     int debug_varyings = 0;
@@ -319,12 +351,8 @@ struct gswt_ctx {
     gswt::Options opt;
     // gswt_set_atmosphere: the block in force, validated (all zero: off).  Read when a frame is submitted and when gswt_proxy_render is called.
     gswt_atmosphere atm = {};
-    // gswt_set_tile_styles: the table versions and the one in force (-1: styles off).  Read when a frame is submitted.
-    gswt::StyleVersion sty_pool[gswt::kStyleVersions];
-    int sty_cur = -1;
-    // gswt_set_shadow_map: the map versions and the one in force (-1: shadows off).  Read when a frame is submitted and when a proxy pass is called.
-    gswt::ShadowVersion shd_pool[gswt::kShadowVersions];
-    int shd_cur = -1;
+    gswt::VersionPool<gswt::StyleVersion> styles;      // gswt_set_tile_styles' table
+    gswt::VersionPool<gswt::ShadowVersion> shadows;    // gswt_set_shadow_map's map: read when a proxy pass is called, too
     // scene
     gswt::DevBuf<uint4> tex;
     size_t n_splats = 0;
@@ -398,7 +426,7 @@ struct gswt_ctx {
     hipEvent_t ev_unshard = nullptr;       // local group: this rank's re-assembly of the PREVIOUS gather has read its gather buffer
     bool unshard_pending = false;          // ... and has been recorded at least once
 
-    // Releases what the members do not release themselves (the buffers do): streams, events, the pinned counter words, graphs and the
+    // Releases what the members do not release themselves (the buffers and the version pools do): streams, events, the pinned counter words, graphs and the
     // RCCL communicator.  The caller has made the ctx's device current and nothing is in flight (gswt_api.hip).
     ~gswt_ctx();
 };
@@ -471,7 +499,7 @@ inline Atmo atmo_constants(const gswt_atmosphere& a)
 }
 
 // gswt_set_shadow_map's version v as a kernel argument (-1: off, all zero)
-inline Shadow shadow_version(const gswt_ctx* c, int v) { return v >= 0 ? c->shd_pool[v].p : Shadow{}; }
+inline Shadow shadow_version(const gswt_ctx* c, int v) { const ShadowVersion* sv = c->shadows.get(v); return sv ? sv->p : Shadow{}; }
 
 // opengl_to_wgpu * projection (gswt.wgsl:152-160, proxy.wgsl:84-91): clip z = (z + w) / 2, the other rows as they are
 inline void gl_to_wgpu_projection(const float* P, float* GP)

@@ -16,6 +16,7 @@
 #else
 #include "gswt_frame_layout.h"
 #endif
+#include "gswt_frame_modes.h"
 
 namespace gswt {
 
@@ -400,9 +401,8 @@ void launch_merge_copy(hipStream_t s, const MergeCopy* jobs, const uint2* blocks
 // (keys -> `keys`, slots -> b.vals_a; depth-ordered frames also the depth bits -> dkeys and, with krange, the frame's key range; n_launch 0:
 // over every chunk instead of the live table), k_items + the compositor over the sorted slots `vals`.
 void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_cull);
-// (the atmosphere is on when f.atm.fade_end > 0 or f.atm.fog_density > 0: strict frames only, gswt_api.hip refuses the others;
-// the tile styles are on when b.styles is set, the sun shadows when b.shadow.z is, likewise)
-void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict, bool ortho);
+// (m: the instantiation's mode bits, project_modes of gswt_frame_modes.h)
+void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, ProjectModes m);
 void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
 // b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer, the video formats
 // their planes of out_rows x f.out_w samples, both even), b.out_depth (when set) the depth image in f32, b.out_pick (when set) the pick image

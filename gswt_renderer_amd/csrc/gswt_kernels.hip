@@ -3106,25 +3106,17 @@ void launch_cull(hipStream_t s, const Frame& f, const FrameBufs& b, bool chunk_c
                 b.chunk_tab, b.n_chunks, b.boxes, chunk_cull && b.boxes ? 1u : 0u, b.live_cnt, b.live_tab, b.live_cid);
 }
 
-void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, bool strict, bool ortho)
+void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t n_launch, bool debug, ProjectModes m)
 {
     if (b.n_chunks == 0) return;
     const SuperSums ss = super_sums_of(b.n_chunks);     // (zeroed by k_cull)
     const bool full = f.surface_type == 2u || f.draw_mode != 0u;
-    // (the orthographic stage exists in its strict form only: gswt_api.hip refuses an orthographic frame with GSWT_OPT_STRICT_VS = 0)
-    // (nor has the pixel filter another: AA is a parameter of the STRICT instantiations only, and gswt_api.hip refuses a filtered v2 frame)
-    // (nor has the atmosphere: ATM likewise, and a frame with gswt_set_atmosphere's block off launches the ATM = false instantiation it always did)
-    // (nor have the tile styles: STY likewise, on when the frame was submitted with a table, b.styles)
-    const bool strict_seq = strict || ortho;
-    const bool aa = strict_seq && f.aa_s > 0.0f, atm = strict_seq && (f.atm.fade_end > 0.0f || f.atm.fog_density > 0.0f);
-    // (nor have the sun shadows: SHD likewise, on when the frame was submitted with a map, b.shadow.z)
-    const bool sty = strict_seq && b.styles != nullptr, shd = strict_seq && b.shadow.z != nullptr;
     with_variant([&](auto D, auto F, auto S, auto O, auto A, auto M, auto Y, auto Z) {
         if constexpr (S || !(O || A || M || Y || Z))
             GSWT_LAUNCH((k_project<D, F, S, O, A, M, Y, Z>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,
                         b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums,
                         b.super_sums, ss.n_super, b.dbg, b.col_f, b.styles, b.n_styles, b.shadow);
-    }, debug, full, strict_seq, ortho, aa, atm, sty, shd);
+    }, debug, full, m.strict, m.ortho, m.aa, m.atm, m.sty, m.shd);
     GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, ss.n_super, b.counters, b.super_sums + ss.prefix_word(0), b.pair_cap, b.live_cnt, n_launch / kLiveLists);
 }
 
