@@ -184,6 +184,16 @@ class ShadowParams(C.Structure):
                 ("_pad", C.c_uint32 * 3)]
 
 
+class ClipVolume(C.Structure):
+    """gswt_clip_volume: one volume of gswt_set_clip_volumes' set (64 B; clip.ClipVolume packs it)."""
+    _fields_ = [("world_to_unit", C.c_float * 12), ("shape", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+GSWT_MAX_CLIP_VOLUMES = 8
+GSWT_CLIP_BOX, GSWT_CLIP_ELLIPSOID, GSWT_CLIP_HALFSPACE = 0, 1, 2
+GSWT_CLIP_KEEP, GSWT_CLIP_GROUND = 1, 2
+
+assert C.sizeof(ClipVolume) == 64 and ClipVolume.shape.offset == 48
 assert C.sizeof(Cell) == 260 and C.sizeof(CellState) == 20
 assert C.sizeof(Pick) == 16
 assert C.sizeof(TileStyle) == 8
@@ -211,6 +221,7 @@ SYMBOLS = {
     "gswt_set_atmosphere": (C.c_int, [_P, _P]),
     "gswt_set_tile_styles": (C.c_int, [_P, _P, C.c_size_t]),
     "gswt_set_shadow_map": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "gswt_set_clip_volumes": (C.c_int, [_P, _P, C.c_size_t]),
     "gswt_upload_scene": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int]),
     "gswt_configure": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "gswt_set_draws": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_size_t]),

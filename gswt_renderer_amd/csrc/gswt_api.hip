@@ -307,6 +307,36 @@ try {
     return GSWT_OK;
 } GSWT_CATCH
 
+int gswt_set_clip_volumes(gswt_ctx* c, const gswt_clip_volume* v, size_t n)
+try {
+    if (!c) return GSWT_ERR_BAD_ARG;
+    if (!v && n > 0) return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_clip_volumes: v is NULL with n = %zu", n);
+    if (n > (size_t)GSWT_MAX_CLIP_VOLUMES)
+        return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_clip_volumes: n = %zu, more than GSWT_MAX_CLIP_VOLUMES = %d", n, GSWT_MAX_CLIP_VOLUMES);
+    const float inf = std::numeric_limits<float>::infinity();
+    ClipSet s = {};
+    for (size_t i = 0; i < n; i++) {
+        const gswt_clip_volume& e = v[i];
+        if (e.shape > GSWT_CLIP_HALFSPACE)
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_clip_volumes: v[%zu].shape = %u, not GSWT_CLIP_BOX, _ELLIPSOID or _HALFSPACE", i, e.shape);
+        if (e.flags & ~(GSWT_CLIP_KEEP | GSWT_CLIP_GROUND))
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_clip_volumes: v[%zu].flags = 0x%x has bits beyond GSWT_CLIP_KEEP | GSWT_CLIP_GROUND", i, e.flags);
+        if (e.reserved[0] | e.reserved[1])
+            return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_clip_volumes: v[%zu].reserved = (%u, %u), must be zero", i, e.reserved[0], e.reserved[1]);
+        // (a half-space reads row 2 alone: what its rows 0 and 1 hold is not looked at, and travels as zeros)
+        for (int k = e.shape == GSWT_CLIP_HALFSPACE ? 8 : 0; k < 12; k++)
+            if (!(std::fabs(e.world_to_unit[k]) < inf))
+                return fail(c, GSWT_ERR_BAD_ARG, "gswt_set_clip_volumes: v[%zu].world_to_unit[%d] = %g is not finite", i, k, e.world_to_unit[k]);
+        ClipVolume& q = s.v[i];
+        for (int k = e.shape == GSWT_CLIP_HALFSPACE ? 8 : 0; k < 12; k++) q.row[k / 4][k % 4] = e.world_to_unit[k];
+        q.shape = e.shape; q.flags = e.flags;
+        s.n_keep += (e.flags & GSWT_CLIP_KEEP) ? 1u : 0u;
+    }
+    s.n = (uint32_t)n;
+    c->clip = s;              // by value: frames already submitted keep their own copy (FrameModes), nothing to wait for
+    return GSWT_OK;
+} GSWT_CATCH
+
 int gswt_configure(gswt_ctx* c, const float* height_map, int hm_w, int hm_h)
 try {
     if (!c) return GSWT_ERR_BAD_ARG;
@@ -345,7 +375,7 @@ static float antialias_s(int value, float splat_scale) { return (4.0f * ((float)
 static FrameModes frame_modes(const gswt_ctx& c, const gswt_scene_uniforms& su)
 {
     const float aa_s = c.opt.antialias > 0 ? antialias_s(c.opt.antialias, su.splat_scale) : 0.0f;
-    return FrameModes{c.opt.strict_vs != 0, c.opt.projection == 1, aa_s, atmo_constants(c.atm), c.styles.cur, c.shadows.cur};
+    return FrameModes{c.opt.strict_vs != 0, c.opt.projection == 1, aa_s, atmo_constants(c.atm), c.styles.cur, c.shadows.cur, c.clip};
 }
 
 // The preconditions of the modes a frame submitted now would run with.  Every mode exists in the strict vertex stage only (project_modes,
@@ -370,7 +400,8 @@ static int validate_frame_modes(gswt_ctx* c, const gswt_camera_uniforms* cam, co
         {aa, "GSWT_OPT_ANTIALIAS > 0", "filtered"},
         {c->atm.fade_end > 0.0f || c->atm.fog_density > 0.0f, "gswt_set_atmosphere's fade or fog", "atmospheric"},
         {c->styles.cur >= 0, "gswt_set_tile_styles' table", "styled"},
-        {c->shadows.cur >= 0, "gswt_set_shadow_map's map", "shadowed"}};
+        {c->shadows.cur >= 0, "gswt_set_shadow_map's map", "shadowed"},
+        {c->clip.n > 0u, "gswt_set_clip_volumes' set", "clipped"}};
     for (const auto& m : modes)
         if (m.on && !c->opt.strict_vs)
             return fail(c, GSWT_ERR_BAD_ARG, "gswt_render: %s needs GSWT_OPT_STRICT_VS = 1 (the v2 sequence has no %s form)", m.who, m.form);
@@ -592,6 +623,7 @@ static int plan_frame_buffers(gswt_ctx* c, FrameSlot& sl, const DrawSet& D, cons
     const StyleVersion* const sty = c->styles.get(a.modes.sty_ver);
     b.styles = sty ? sty->d.p : nullptr; b.n_styles = sty ? sty->n : 0u;
     b.shadow = shadow_version(c, a.modes.shd_ver);
+    b.clip = a.modes.clip;
     b.bg_rgba = im.d_bg; b.bg_depth = im.d_bgd; b.out = im.d_out; b.out_depth = im.d_out_depth; b.host_counters = sl.hc_dev;
     b.out_pick = reinterpret_cast<uint4*>(im.d_out_pick);
     b.n_tiles = (uint32_t)n_tiles; b.pair_cap = cap; b.seg = seg;

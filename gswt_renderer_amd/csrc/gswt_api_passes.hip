@@ -229,8 +229,9 @@ static int proxy_draw(gswt_ctx* c, const ProxyArgs& a, const SphereProxyArgs* sp
     hipSetDevice(c->device);
     if (clear_depth) launch_fill_f32(c->stream, depth_dev, (size_t)a.width * a.height, 1.0f);
     const Shadow shd = shadow_version(c, c->shadows.cur);
-    if (sp) launch_proxy_sphere(c->stream, a, *sp, ortho, shd, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
-    else launch_proxy(c->stream, a, ortho, shd, c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
+    const ClipSet clip = clip_ground_subset(c->clip);
+    if (sp) launch_proxy_sphere(c->stream, a, *sp, ortho, shd, clip, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
+    else launch_proxy(c->stream, a, ortho, shd, clip, c->hmap.p, c->proxy_tex.p, reinterpret_cast<float4*>(rgba_dev), depth_dev);
     HIP_TRY(c, hipGetLastError());
     return GSWT_OK;
 }

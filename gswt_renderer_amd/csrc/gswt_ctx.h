@@ -110,6 +110,10 @@ static_assert(kDrawSets <= kMergeSources, "MergeSources holds one pointer pair p
 static_assert(sizeof(gswt_render_config) == 32 && offsetof(gswt_render_config, out_format) == 28, "gswt_render_config layout");
 static_assert(GSWT_OUT_RGBA32F == kOutF32 && GSWT_OUT_RGBA8_UNORM == kOutRGBA8 && GSWT_OUT_BGRA8_UNORM == kOutBGRA8, "output formats");
 static_assert(GSWT_VIDEO_NV12 == kOutNV12 && GSWT_VIDEO_I420 == kOutI420, "video output formats");
+static_assert(GSWT_MAX_CLIP_VOLUMES == kMaxClipVolumes && sizeof(gswt_clip_volume) == sizeof(ClipVolume) && sizeof(gswt_clip_volume) == 64 &&
+              offsetof(gswt_clip_volume, shape) == offsetof(ClipVolume, shape), "gswt_clip_volume is ClipVolume");
+static_assert(GSWT_CLIP_BOX == kClipBox && GSWT_CLIP_ELLIPSOID == kClipEllipsoid && GSWT_CLIP_HALFSPACE == kClipHalfspace &&
+              GSWT_CLIP_KEEP == kClipKeep && GSWT_CLIP_GROUND == kClipGround, "clip shapes and flags");
 
 struct DrawSet {
     // Everything a sort event uploads lives in ONE pinned host block mirrored by one device block of the same layout (a
@@ -176,6 +180,7 @@ struct FrameModes {
     float aa_s = 0.0f;                     // GSWT_OPT_ANTIALIAS: s = 4 v / splat_scale^2 (0: off)
     Atmo atm = {};                         // gswt_set_atmosphere's block with its derived constants (all zero: off)
     int sty_ver = -1, shd_ver = -1;        // gswt_set_tile_styles' table, gswt_set_shadow_map's block and image: their versions in gswt_ctx::styles / shadows (-1: off)
+    ClipSet clip = {};                     // gswt_set_clip_volumes' set, by value (n = 0: off): no version pool, the frame's copy is the version
 };
 
 struct FrameArgs {
@@ -353,6 +358,7 @@ struct gswt_ctx {
     gswt_atmosphere atm = {};
     gswt::VersionPool<gswt::StyleVersion> styles;      // gswt_set_tile_styles' table
     gswt::VersionPool<gswt::ShadowVersion> shadows;    // gswt_set_shadow_map's map: read when a proxy pass is called, too
+    gswt::ClipSet clip = {};                           // gswt_set_clip_volumes' set in force, validated (n = 0: off): read when a frame is submitted and when a proxy pass is called
     // scene
     gswt::DevBuf<uint4> tex;
     size_t n_splats = 0;
@@ -500,6 +506,18 @@ inline Atmo atmo_constants(const gswt_atmosphere& a)
 
 // gswt_set_shadow_map's version v as a kernel argument (-1: off, all zero)
 inline Shadow shadow_version(const gswt_ctx* c, int v) { const ShadowVersion* sv = c->shadows.get(v); return sv ? sv->p : Shadow{}; }
+
+// What the proxy passes see of gswt_set_clip_volumes' set: its volumes flagged GSWT_CLIP_GROUND, in their order (n = 0: the pass is unclipped)
+inline ClipSet clip_ground_subset(const ClipSet& s)
+{
+    ClipSet g = {};
+    for (uint32_t k = 0; k < s.n; k++)
+        if (s.v[k].flags & kClipGround) {
+            g.n_keep += (s.v[k].flags & kClipKeep) ? 1u : 0u;
+            g.v[g.n++] = s.v[k];
+        }
+    return g;
+}
 
 // opengl_to_wgpu * projection (gswt.wgsl:152-160, proxy.wgsl:84-91): clip z = (z + w) / 2, the other rows as they are
 inline void gl_to_wgpu_projection(const float* P, float* GP)

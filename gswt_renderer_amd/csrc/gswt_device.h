@@ -95,6 +95,24 @@ struct Shadow {
 };
 static_assert(sizeof(Shadow) == 88, "Shadow has no implicit padding");
 
+// gswt_set_clip_volumes' set as the kernels read it (include/gswt_hip.h): by value, a kernel argument of its own beside Frame / ProxyArgs like
+// Shadow, so that neither struct grows and the instantiations without CLIP stay the code they were.  n = 0: off.  Entries past n are zero.
+// The proxy passes get the subset flagged GSWT_CLIP_GROUND (clip_ground_subset).
+constexpr uint32_t kMaxClipVolumes = 8;
+constexpr uint32_t kClipBox = 0, kClipEllipsoid = 1, kClipHalfspace = 2;      // GSWT_CLIP_* shapes
+constexpr uint32_t kClipKeep = 1, kClipGround = 2;                            // ... and flags
+struct ClipVolume {
+    float row[3][4];                       // world_to_unit, rows 0..2
+    uint32_t shape, flags;                 // GSWT_CLIP_BOX / _ELLIPSOID / _HALFSPACE; GSWT_CLIP_KEEP | GSWT_CLIP_GROUND
+    uint32_t _pad[2];
+};
+struct ClipSet {
+    uint32_t n, n_keep;                    // volumes in force, and how many of them are keep volumes
+    uint32_t _pad[2];                      // (no implicit padding: a recorded graph node compares its argument bytes)
+    ClipVolume v[kMaxClipVolumes];
+};
+static_assert(sizeof(ClipVolume) == 64 && sizeof(ClipSet) == 16 + 64 * kMaxClipVolumes, "ClipSet has no implicit padding");
+
 // Per-frame constants (kernel argument, by value).
 struct Frame {
     float V[16];       // view
@@ -270,7 +288,7 @@ struct GraphNodeRec {
     dim3 grid, block;
     uint32_t n_args = 0, n_bytes = 0;
     uint16_t offs[40];
-    alignas(16) unsigned char args[1280];
+    alignas(16) unsigned char args[1536];      // (k_project: Frame, 19 pointers, the shadow block and the clip set are 1 320 bytes)
     template <typename T>
     void push(const T& v)
     {
@@ -347,6 +365,8 @@ struct FrameBufs {
     const uint2* styles; uint32_t n_styles;
     // gswt_set_shadow_map's block and image version as the frame was submitted with them; shadow.z null: shadows off (k_project<.., SHD = false>)
     Shadow shadow;
+    // gswt_set_clip_volumes' set as the frame was submitted with it; n = 0: off (k_project<.., CLIP = false>)
+    ClipSet clip;
     const float4* bg_rgba; const float* bg_depth; float4* out;
     float* out_depth;                          // the frame's depth image (f32, the colour's geometry); null: none (gswt_render_depth)
     uint4* out_pick;                           // the frame's pick image (gswt_pick records, the colour's geometry); null: none (gswt_render_pick)
@@ -436,11 +456,13 @@ void launch_unshard(hipStream_t s, const void* gathered, void* out, int width, i
 void launch_skybox(hipStream_t s, const float* view16, float p00, float p11, int width, int height, int face_size, int equirect,
                    const float4* faces, float4* out);
 void launch_skybox_bake(hipStream_t s, const SkyBakeArgs& a, const float4* equi, float4* faces);
-// The proxy passes, k_proxy / k_proxy_sphere<FOG, ORTHO, SHD>.  ortho: the pass reads a's ortho_* fields (gswt_proxy_render_ortho: set up in
-// the grid frame; gswt_proxy_render_sphere: with g = 0); shd.z set: it shades the ground by gswt_set_shadow_map's image.
-void launch_proxy(hipStream_t s, const ProxyArgs& a, bool ortho, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth);
-void launch_proxy_sphere(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, bool ortho, const Shadow& shd, const float4* tex, float4* rgba,
-                         float* depth);
+// The proxy passes, k_proxy / k_proxy_sphere<FOG, ORTHO, SHD, CLIP>.  ortho: the pass reads a's ortho_* fields (gswt_proxy_render_ortho: set up in
+// the grid frame; gswt_proxy_render_sphere: with g = 0); shd.z set: it shades the ground by gswt_set_shadow_map's image; clip.n > 0: it
+// discards the fragments gswt_set_clip_volumes' GROUND volumes hide (clip: clip_ground_subset of the set in force).
+void launch_proxy(hipStream_t s, const ProxyArgs& a, bool ortho, const Shadow& shd, const ClipSet& clip, const float* hm, const float4* tex,
+                  float4* rgba, float* depth);
+void launch_proxy_sphere(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, bool ortho, const Shadow& shd, const ClipSet& clip,
+                         const float4* tex, float4* rgba, float* depth);
 // One level of the proxy mip build into dst (n x n float4).  src: the staged source, a.pitch bytes per row.  ranges: 2 n int2,
 // wv / wh: the tap weights, tmp: the intermediate, part: the partial sums (sizes: proxy_mip_* above; unused on a copy level).
 void launch_proxy_mip(hipStream_t s, const ProxyMipArgs& a, const uint8_t* src, int2* ranges, float* wv, float* wh, float4* tmp,

@@ -76,6 +76,32 @@ __device__ __forceinline__ float shadow_amount(const Shadow& s, const ShadowTap&
     return s.strength * (1.0f - lit);
 }
 
+// gswt_set_clip_volumes' test (include/gswt_hip.h), shared by k_project<.., CLIP> and the proxy kernels' CLIP forms.  Every written operator
+// is one binary32 operation, the rows summed as shadow_fetch sums its own; every comparison is an ordinary IEEE compare, so a NaN coordinate
+// is not inside.  The shape is uniform: a half-space never reads rows 0 and 1.
+__device__ __forceinline__ bool clip_inside(const ClipVolume& q, float c0, float c1, float c2)
+{
+    const float u2 = ((q.row[2][0] * c0 + q.row[2][1] * c1) + q.row[2][2] * c2) + q.row[2][3];
+    if (q.shape == kClipHalfspace) return u2 <= 0.0f;
+    const float u0 = ((q.row[0][0] * c0 + q.row[0][1] * c1) + q.row[0][2] * c2) + q.row[0][3];
+    const float u1 = ((q.row[1][0] * c0 + q.row[1][1] * c1) + q.row[1][2] * c2) + q.row[1][3];
+    if (q.shape == kClipBox) return fabsf(u0) <= 1.0f && fabsf(u1) <= 1.0f && fabsf(u2) <= 1.0f;
+    return (u0 * u0 + u1 * u1) + u2 * u2 <= 1.0f;
+}
+// The visibility rule: hidden unless (no keep volume, or inside one of them) and inside no cut volume.  The trip count and everything the
+// loop reads of the set are uniform -- the set is a kernel argument, indexed by the loop counter alone -- so the rows arrive by scalar loads
+// and feed the vector multiplies as scalar operands; no lane leaves the loop early, which keeps the counter uniform.
+__device__ __forceinline__ bool clip_hidden(const ClipSet& s, float c0, float c1, float c2)
+{
+    bool in_keep = s.n_keep == 0u, in_cut = false;
+    for (uint32_t k = 0; k < s.n; k++) {
+        const bool in = clip_inside(s.v[k], c0, c1, c2);
+        if (s.v[k].flags & kClipKeep) in_keep = in_keep || in;
+        else in_cut = in_cut || in;
+    }
+    return !in_keep || in_cut;
+}
+
 // halfToFloat, gswt.wgsl:478-494: normals as IEEE; subnormals scale 2^-15 (f * 2^-25);
 // Inf/NaN -> 0.  The definition is gswt_host::half_to_float (host/gswt_math.h, the shader's arithmetic): this is the hot path's form of
 // it and must equal it on all 65536 bit patterns, signs of zero included.

@@ -957,7 +957,7 @@ __device__ __forceinline__ void fragment_setup(const Frame& f, const VertexOut& 
 
 // The kernel itself keeps the loads (launch table, list word, record: A1, A2 and the trace stamps around them) and the workgroup's sums; per
 // splat it calls, in this order, the stages above: tile_offset (A3), map_height_surface / map_sphere_surface (A4), atmosphere_fade,
-// lod_transition (A5), vertex_strict<FULL, ORTHO, AA, ATM, STY, SHD> or vertex_v2<FULL> (A6..A10; both over splat_cov3 and lod_blend_color, the
+// clip_hidden (CLIP), lod_transition (A5), vertex_strict<FULL, ORTHO, AA, ATM, STY, SHD> or vertex_v2<FULL> (A6..A10; both over splat_cov3 and lod_blend_color, the
 // strict one over shadow_fetch, tile_style_shade, sun_shadow, fog_requantise and tint_requantise) and fragment_setup (F1, F2, tile rectangle, record); with STY,
 // tile_style runs directly behind A1, in front of the record's loads.  A new per-splat feature goes into the stage it
 // belongs to; a new template flag into that stage's parameters.
@@ -986,7 +986,10 @@ __device__ __forceinline__ void fragment_setup(const Frame& f, const VertexOut& 
 // SHD (gswt_set_shadow_map with a map on, STRICT only): the sun shadow of include/gswt_hip.h, a 2 x 2 depth compare in the light's image per
 // splat that passed the frustum test.  A template parameter like STY: a frame with shadows off launches the instantiation it always did and
 // never reads `shd`, which is a kernel argument of its own so that Frame stays what it was.
-template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO, bool AA, bool ATM, bool STY, bool SHD>
+// CLIP (gswt_set_clip_volumes with a volume in force, STRICT only): the clip volumes of include/gswt_hip.h, clip_hidden (gswt_device_fn.h) on
+// A4's centre directly behind the clip_height test.  A template parameter like SHD: a frame without volumes launches the instantiation it
+// always did and never reads `clip`, the set by value as a kernel argument of its own behind `shd`.
+template <bool DEBUG, bool FULL, bool STRICT, bool ORTHO, bool AA, bool ATM, bool STY, bool SHD, bool CLIP>
 __global__ __launch_bounds__(256) void k_project(
     const Frame f, const DrawDev* __restrict__ draws, const uint2* __restrict__ chunk_tab,
     const uint32_t* __restrict__ static_list, const uint32_t* __restrict__ merged_list,
@@ -994,7 +997,8 @@ __global__ __launch_bounds__(256) void k_project(
     const float* __restrict__ hmap, const uint32_t* __restrict__ draw_culled, const uint32_t* __restrict__ cell_culled,
     const uint32_t* __restrict__ live_cnt, const uint4* __restrict__ live_tab, uint2* __restrict__ rects,
     Rec* __restrict__ recs, float* __restrict__ depths, uint32_t* __restrict__ block_sums, uint32_t* __restrict__ super_sums, uint32_t n_super,
-    Varyings* __restrict__ dbg, float4* __restrict__ col_f, const uint2* __restrict__ styles, uint32_t n_styles, const Shadow shd)
+    Varyings* __restrict__ dbg, float4* __restrict__ col_f, const uint2* __restrict__ styles, uint32_t n_styles, const Shadow shd,
+    const ClipSet clip)
 {
     __shared__ uint32_t s_wsum[4], s_wvis[4];
     // chunk_tab is in LAUNCH order, which is not slot order: workgroup b runs on XCD b % 8, and the table is laid out so
@@ -1075,6 +1079,7 @@ __global__ __launch_bounds__(256) void k_project(
             if (f.surface_type == 1u) map_height_surface(f, hmap, m);
             else if (FULL && f.surface_type == 2u) map_sphere_surface(f, d, map_id_m, m);
             if (f.use_clip == 1u && m.mapped_z < f.clip_height) break;
+            if (CLIP && clip_hidden(clip, m.c0, m.c1, m.c2)) break;
             if (ATM && !atmosphere_fade(f, m)) break;
             // A5
             if (!lod_transition<ATM>(f, d, lod_id, m)) break;
@@ -3111,12 +3116,12 @@ void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t 
     if (b.n_chunks == 0) return;
     const SuperSums ss = super_sums_of(b.n_chunks);     // (zeroed by k_cull)
     const bool full = f.surface_type == 2u || f.draw_mode != 0u;
-    with_variant([&](auto D, auto F, auto S, auto O, auto A, auto M, auto Y, auto Z) {
-        if constexpr (S || !(O || A || M || Y || Z))
-            GSWT_LAUNCH((k_project<D, F, S, O, A, M, Y, Z>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,
+    with_variant([&](auto D, auto F, auto S, auto O, auto A, auto M, auto Y, auto Z, auto C) {
+        if constexpr (S || !(O || A || M || Y || Z || C))
+            GSWT_LAUNCH((k_project<D, F, S, O, A, M, Y, Z, C>), dim3(n_launch), dim3(256), s, f, b.draws, b.chunk_tab_xcd, b.static_list, b.merged_list,
                         b.merged_map, b.tex, b.hmap, b.draw_culled, b.cell_culled, b.live_cnt, b.live_tab, b.rects, b.recs, b.depths, b.block_sums,
-                        b.super_sums, ss.n_super, b.dbg, b.col_f, b.styles, b.n_styles, b.shadow);
-    }, debug, full, m.strict, m.ortho, m.aa, m.atm, m.sty, m.shd);
+                        b.super_sums, ss.n_super, b.dbg, b.col_f, b.styles, b.n_styles, b.shadow, b.clip);
+    }, debug, full, m.strict, m.ortho, m.aa, m.atm, m.sty, m.shd, m.clip);
     GSWT_LAUNCH(k_totals, dim3(1), dim3(256), s, b.super_sums, ss.n_super, b.counters, b.super_sums + ss.prefix_word(0), b.pair_cap, b.live_cnt, n_launch / kLiveLists);
 }
 

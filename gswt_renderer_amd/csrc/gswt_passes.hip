@@ -254,10 +254,13 @@ __device__ __forceinline__ float4 proxy_colour(const ProxyArgs& a, const Shadow&
 // texturing are the same code; the rays of the right and the lower pixel differ from the pixel's own by their origin instead of their
 // direction.  Rays, vertices, a.cam and the view's translation are in the grid frame, whose lattice starts at (0, 0): far from the world
 // origin nothing here is rounded at the world coordinates' magnitude but the lattice itself (rx, ry: the reference's f32 vertices); the
-// hit point goes back to WORLD coordinates by (gx0, gy0) for the shadow map.
-template <bool FOG, bool ORTHO, bool SHD>
+// hit point goes back to WORLD coordinates by (gx0, gy0) for the shadow map and the clip volumes.
+// CLIP (gswt_set_clip_volumes with a GSWT_CLIP_GROUND volume in force when the pass is called): clip_hidden (gswt_device_fn.h) over those
+// volumes at the world hit point, in front of proxy_write: a hidden fragment is discarded, colour and depth keep what was there.  (On the
+// HeightMap surface the fragment is the walk's first hit; the walk does not go on behind a hidden one.)
+template <bool FOG, bool ORTHO, bool SHD, bool CLIP>
 __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* __restrict__ hm, const float4* __restrict__ tex,
-                                               float4* __restrict__ rgba, float* __restrict__ depth_buf, const Shadow shd)
+                                               float4* __restrict__ rgba, float* __restrict__ depth_buf, const Shadow shd, const ClipSet clip)
 {
     const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= a.width || y >= a.height) return;
@@ -322,10 +325,11 @@ __global__ __launch_bounds__(256) void k_proxy(const ProxyArgs a, const float* _
     if (!hit) return;
     const size_t pi = (size_t)y * a.width + x;
     float hw[3] = {0.0f, 0.0f, 0.0f};
-    if (SHD) {                                                   // the hit point back in WORLD coordinates
+    if (SHD || CLIP) {                                           // the hit point back in WORLD coordinates
         const float hx = o[0] + best_t * d[0], hy = o[1] + best_t * d[1], hz = o[2] + best_t * d[2];
         hw[0] = ORTHO ? hx + a.gx0 : hx; hw[1] = ORTHO ? hy + a.gy0 : hy; hw[2] = hz;
     }
+    if (CLIP && clip_hidden(clip, hw[0], hw[1], hw[2])) return;
     ShadowTap tap;                                               // (SHD only: proxy_write sets it, proxy_colour reads it)
     if (!proxy_write<SHD>(a, shd, pi, dep, hw, rgba, depth_buf, tap)) return;
     float uv[2], uvx[2], uvy[2], on[3], dn[3];
@@ -376,9 +380,12 @@ __device__ __forceinline__ float sphere_neighbour_dist(const float o[3], const f
 // FOG / ORTHO / SHD: proxy_ray, proxy_write and proxy_colour, the stages k_proxy runs; the ORTHO host set-up runs with g = 0, so origin,
 // a.cam, the view's translation and the hit are in world coordinates.  The grid fields of a (nx, ny, cs, gx0, gy0), map_proxy, width_scale,
 // surface_type and the height map are not read.  Every store goes to pixel (x, y) of the frame, inside width x height by the first test.
-template <bool FOG, bool ORTHO, bool SHD>
+// CLIP: the GROUND volumes' test joins what a candidate must pass, beside clip_height's: behind a near surface that is cut away the inside
+// of the far one shows.
+template <bool FOG, bool ORTHO, bool SHD, bool CLIP>
 __global__ __launch_bounds__(256) void k_proxy_sphere(const ProxyArgs a, const SphereProxyArgs sp, const float4* __restrict__ tex,
-                                                      float4* __restrict__ rgba, float* __restrict__ depth_buf, const Shadow shd)
+                                                      float4* __restrict__ rgba, float* __restrict__ depth_buf, const Shadow shd,
+                                                      const ClipSet clip)
 {
     const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= a.width || y >= a.height) return;
@@ -394,6 +401,7 @@ __global__ __launch_bounds__(256) void k_proxy_sphere(const ProxyArgs a, const S
         float dz;
         if (!(tk > 0.0f) || !proxy_depth(a, p, dz)) continue;
         if (a.use_clip == 1u && (p[2] / sp.r) * sp.sphere_radius < a.clip_height) continue;
+        if (CLIP && clip_hidden(clip, p[0], p[1], p[2])) continue;
         hit = true; second = k == 1; t = tk; dep = dz;
         hp[0] = p[0]; hp[1] = p[1]; hp[2] = p[2];
     }
@@ -696,28 +704,30 @@ void launch_fill_f32(hipStream_t s, float* p, size_t n, float v)
     if (n) hipLaunchKernelGGL(k_fill_f32, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, p, n, v);
 }
 
-// A proxy pass's instantiation, for both kernels: fn(FOG, ORTHO, SHD, grid), the constants in the kernels' template order <FOG, ORTHO, SHD>.
-// FOG from the fog part of a.atm, SHD from the shadow map in force (both read when the pass is called), ORTHO from the entry point.
+// A proxy pass's instantiation, for both kernels: fn(FOG, ORTHO, SHD, CLIP, grid), the constants in the kernels' template order
+// <FOG, ORTHO, SHD, CLIP>.  FOG from the fog part of a.atm, SHD from the shadow map in force, CLIP from the GROUND volumes in force (all read
+// when the pass is called), ORTHO from the entry point.
 template <typename Fn>
-static void with_proxy_variant(const ProxyArgs& a, bool ortho, const Shadow& shd, Fn&& fn)
+static void with_proxy_variant(const ProxyArgs& a, bool ortho, const Shadow& shd, const ClipSet& clip, Fn&& fn)
 {
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
     const bool fog = a.atm.fog_density > 0.0f, shade = shd.z != nullptr;
-    with_variant([&](auto FOG, auto ORTHO, auto SHD) { fn(FOG, ORTHO, SHD, grid); }, fog, ortho, shade);
+    with_variant([&](auto FOG, auto ORTHO, auto SHD, auto CLIP) { fn(FOG, ORTHO, SHD, CLIP, grid); }, fog, ortho, shade, clip.n > 0u);
 }
 
-void launch_proxy(hipStream_t s, const ProxyArgs& a, bool ortho, const Shadow& shd, const float* hm, const float4* tex, float4* rgba, float* depth)
+void launch_proxy(hipStream_t s, const ProxyArgs& a, bool ortho, const Shadow& shd, const ClipSet& clip, const float* hm, const float4* tex,
+                  float4* rgba, float* depth)
 {
-    with_proxy_variant(a, ortho, shd, [&](auto FOG, auto ORTHO, auto SHD, dim3 grid) {
-        hipLaunchKernelGGL((k_proxy<FOG, ORTHO, SHD>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd);
+    with_proxy_variant(a, ortho, shd, clip, [&](auto FOG, auto ORTHO, auto SHD, auto CLIP, dim3 grid) {
+        hipLaunchKernelGGL((k_proxy<FOG, ORTHO, SHD, CLIP>), grid, dim3(256), 0, s, a, hm, tex, rgba, depth, shd, clip);
     });
 }
 
-void launch_proxy_sphere(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, bool ortho, const Shadow& shd, const float4* tex,
-                         float4* rgba, float* depth)
+void launch_proxy_sphere(hipStream_t s, const ProxyArgs& a, const SphereProxyArgs& sp, bool ortho, const Shadow& shd, const ClipSet& clip,
+                         const float4* tex, float4* rgba, float* depth)
 {
-    with_proxy_variant(a, ortho, shd, [&](auto FOG, auto ORTHO, auto SHD, dim3 grid) {
-        hipLaunchKernelGGL((k_proxy_sphere<FOG, ORTHO, SHD>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd);
+    with_proxy_variant(a, ortho, shd, clip, [&](auto FOG, auto ORTHO, auto SHD, auto CLIP, dim3 grid) {
+        hipLaunchKernelGGL((k_proxy_sphere<FOG, ORTHO, SHD, CLIP>), grid, dim3(256), 0, s, a, sp, tex, rgba, depth, shd, clip);
     });
 }
 

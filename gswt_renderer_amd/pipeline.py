@@ -47,6 +47,10 @@ class GSWTPipeline:
         self.tile_styles = styles
         self._pack_tile_styles()
 
+    def set_clip_volumes(self, volumes):
+        """volumes: a list of clip.ClipVolume (world coordinates: nothing to repack when the map window moves) or None / [] for off."""
+        self.renderer.set_clip_volumes(volumes)
+
     def _pack_tile_styles(self):
         if not self.tile_styles:
             self.renderer.set_tile_styles(None)
@@ -81,7 +85,7 @@ class GSWTPipeline:
 
     def render(self, camera_uniforms, width, height, **kw):
         """GSWTRenderer.render with the scene uniforms of the current configuration; every other keyword (order_mode, bg_rgba, depth,
-        pick, projection, antialias, atmosphere, tile_styles, shadow, ...) is passed through."""
+        pick, projection, antialias, atmosphere, tile_styles, shadow, clip_volumes, ...) is passed through."""
         su = self.wang.scene_uniforms(splat_scale=kw.pop("splat_scale", 1.0), scene_scale=kw.pop("scene_scale", (1.0, 1.0, 1.0)),
                                       height_map_scale_v=kw.pop("height_map_scale_v", 1.0))
         # the other RenderConfig fields of SceneUniforms::from_data (renderer.rs:631-672)

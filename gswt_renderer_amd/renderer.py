@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import clip as _clip
 
 
 # one record of the pick image (gswt_pick, include/gswt_hip.h): the splat with the largest blend weight at the pixel.  entry is the list
@@ -180,6 +181,22 @@ class GSWTRenderer:
         blk = (C.c_char * 96).from_buffer_copy(bytes(m))
         self._check(self._lib.gswt_set_shadow_map(self._h, blk, C.c_void_p(m.depth_ptr()), m.width, m.height, 1 if m.on_device else 0))
 
+    def set_clip_volumes(self, volumes):
+        """gswt_set_clip_volumes: volumes is a sequence of clip.ClipVolume (at most clip.MAX_VOLUMES) or the bytes of clip.pack;
+        None or empty switches the mode off.  The set travels by value: the frames submitted and the proxy passes called afterwards
+        use it, frames in flight keep theirs, and nothing is waited for."""
+        if volumes is None:
+            self._check(self._lib.gswt_set_clip_volumes(self._h, None, 0))
+            return
+        raw = bytes(volumes) if isinstance(volumes, (bytes, bytearray, memoryview)) else _clip.pack(volumes)
+        if len(raw) % _clip.VOLUME_BYTES:
+            raise ValueError("set_clip_volumes: the array is a whole number of 64-byte gswt_clip_volume records")
+        if not raw:
+            self._check(self._lib.gswt_set_clip_volumes(self._h, None, 0))
+            return
+        buf = (C.c_char * len(raw)).from_buffer_copy(raw)
+        self._check(self._lib.gswt_set_clip_volumes(self._h, buf, len(raw) // _clip.VOLUME_BYTES))
+
     def set_stream(self, hip_stream: int):
         self._check(self._lib.gswt_set_stream(self._h, C.c_void_p(hip_stream)))
 
@@ -272,7 +289,7 @@ class GSWTRenderer:
         self._check(self._lib.gswt_debug_read_merged(self._h, _ptr(a), _ptr(b), a.shape[0], C.byref(n)))
         return a[:n.value], b[:n.value]
 
-    def _set_frame_modes(self, projection, antialias, atmosphere, tile_styles, shadow=None):
+    def _set_frame_modes(self, projection, antialias, atmosphere, tile_styles, shadow=None, clip_volumes=None):
         """The per-frame modes that render and render_async take as keywords: each one given is set on the context, in this order."""
         if projection is not None:
             self.set_option(L.GSWT_OPT_PROJECTION, int(projection))
@@ -284,6 +301,8 @@ class GSWTRenderer:
             self.set_tile_styles(tile_styles)
         if shadow is not None:
             self.set_shadow_map(shadow)
+        if clip_volumes is not None:
+            self.set_clip_volumes(clip_volumes)
 
     # -- GSWTRenderer::render (renderer.rs:407) ---------------------------------------
     def render(self, camera, scene, width: int, height: int, *, culling_dist: float = 1.0,
@@ -292,7 +311,7 @@ class GSWTRenderer:
                out_device_ptr: int | None = None, bg_on_device: bool = False, out_format: int = L.GSWT_OUT_RGBA32F,
                depth: bool = False, out_depth_device_ptr: int | None = None, pick: bool = False,
                out_pick_device_ptr: int | None = None, projection: int | None = None, antialias: float | None = None,
-               atmosphere=None, tile_styles=None, shadow=None):
+               atmosphere=None, tile_styles=None, shadow=None, clip_volumes=None):
         """camera / scene: 176 / 160-byte uniform blocks (any ctypes struct or bytes of that layout).
         Returns the image [rows, W, 4] on the host -- f32 for GSWT_OUT_RGBA32F, uint8 in the channel order of
         GSWT_OUT_RGBA8_UNORM / GSWT_OUT_BGRA8_UNORM --, or None when out_device_ptr is given.
@@ -316,8 +335,10 @@ class GSWTRenderer:
         tile_styles: when given, a table set first with set_tile_styles (b"" switches styles off); omitted, the context keeps the
         table it has.
         shadow: when given, a shadows.ShadowMap set first with set_shadow_map (shadows.OFF switches shadows off); omitted, the
-        context keeps the map it has."""
-        self._set_frame_modes(projection, antialias, atmosphere, tile_styles, shadow)
+        context keeps the map it has.
+        clip_volumes: when given, a list of clip.ClipVolume set first with set_clip_volumes ([] switches the mode off); omitted, the
+        context keeps the set it has."""
+        self._set_frame_modes(projection, antialias, atmosphere, tile_styles, shadow, clip_volumes)
         cam, sc, cfg = _frame_blocks(camera, scene, culling_dist, lod_enable_mask, order_mode, transmittance_eps, shard, out_format)
         rows, out_w = height, width
         if cfg.shard_count > 1 and cfg.shard_mode == L.GSWT_SHARD_COLUMNS:
@@ -359,13 +380,13 @@ class GSWTRenderer:
                      transmittance_eps: float = 0.0, shard=(0, 1), bg_rgba_ptr: int = 0, bg_depth_ptr: int = 0,
                      out_format: int = L.GSWT_OUT_RGBA32F, out_depth_ptr: int = 0, out_pick_ptr: int = 0,
                      projection: int | None = None, antialias: float | None = None, atmosphere=None,
-                     tile_styles=None, shadow=None) -> int:
+                     tile_styles=None, shadow=None, clip_volumes=None) -> int:
         """Queues a frame (device pointers only) and returns a ticket for render_wait.  out_device_ptr holds rows x out_w x 4
         f32, or bytes for the 8-bit out_format values, or the planes of a GSWT_VIDEO_* format (gswt_out_image_bytes(out_format,
         rows, out_w) bytes, width and height even; see video_planes); out_depth_ptr (optional) receives the depth image, rows x out_w f32
         (gswt_render_async_depth); out_pick_ptr (optional) the pick image, rows x out_w records of PICK_DTYPE (gswt_render_async_pick).
-        projection, antialias, atmosphere, tile_styles, shadow: as in render (the frame keeps the values it was submitted with, whatever is set afterwards)."""
-        self._set_frame_modes(projection, antialias, atmosphere, tile_styles, shadow)
+        projection, antialias, atmosphere, tile_styles, shadow, clip_volumes: as in render (the frame keeps the values it was submitted with, whatever is set afterwards)."""
+        self._set_frame_modes(projection, antialias, atmosphere, tile_styles, shadow, clip_volumes)
         cam, sc, cfg = _frame_blocks(camera, scene, culling_dist, lod_enable_mask, order_mode, transmittance_eps, shard, out_format)
         ticket = C.c_int(-1)
         self._check(self._lib.gswt_render_async_pick(self._h, cam, sc, C.byref(cfg), width, height,

@@ -493,6 +493,54 @@ typedef struct {
 } gswt_shadow_params;         /* 96 bytes */
 GSWT_API int gswt_set_shadow_map(gswt_ctx *ctx, const gswt_shadow_params *p, const float *depth, int width, int height, int depth_on_device);
 
+/* ---- clip volumes: cut splats and proxy ground by boxes, ellipsoids and half-spaces ------------------
+ * The reference's "Clip by Z" (use_clip / clip_height) removes everything below one horizontal plane and tile styles hide whole map
+ * cells.  A clip volume is the per-splat control between them: a cross-section along any plane, a region of interest, a hole of the
+ * host's own shape, a sun map from which the cut-away part casts no shadow.  Up to GSWT_MAX_CLIP_VOLUMES volumes are in force at a
+ * time; v == NULL or n == 0 switches them off (the default), and a frame with none launches exactly the kernels it launches without
+ * this call and is bit for bit the same frame.  The reference has no clip volumes.
+ *
+ * A volume is an affine map world_to_unit (M, rows 0..2, row-major 3 x 4) into the volume's unit frame and a shape there.  The tested
+ * point c is the surface-mapped, scene-scaled centre A6 feeds to the view matrix, the point gswt_set_shadow_map looks up.  (clip_height
+ * tests the SURFACE's height under the splat -- 0 for every splat without a surface --, these volumes the centre itself.)  Every written operator is one correctly rounded binary32 operation, nothing fused:
+ *     u_r = ((M[4r]*c0 + M[4r+1]*c1) + M[4r+2]*c2) + M[4r+3]                    r = 0, 1, 2
+ *     GSWT_CLIP_BOX        inside:  |u0| <= 1 && |u1| <= 1 && |u2| <= 1         (max(|u0|, |u1|, |u2|) <= 1)
+ *     GSWT_CLIP_ELLIPSOID  inside:  (u0*u0 + u1*u1) + u2*u2 <= 1
+ *     GSWT_CLIP_HALFSPACE  inside:  u2 <= 0                                      (rows 0 and 1 are not read and may hold anything)
+ * Every comparison is an ordinary IEEE compare: a NaN coordinate is not inside, a point on the boundary is.
+ * A splat stays exactly when (there is no GSWT_CLIP_KEEP volume, or it is inside at least one of them) and it is inside no volume
+ * without that flag (a cut volume).  The cut is by centre, like clip_height's; there is no feathered edge.  A splat that stays is bit
+ * for bit what it was -- record, depth, pair rectangle, alpha --; a hidden one counts neither in n_visible nor in n_pairs and never
+ * appears in the pick image.  M c is evaluated in binary32 at the world coordinates' magnitude, like the shadow lookup.
+ *
+ * Vertex stage.  k_project gains a ninth template flag CLIP on its strict instantiations; the test sits directly behind the clip_height
+ * test, in front of the atmosphere's fade, so that a hidden splat costs nothing more.  The set travels by value, as one kernel argument
+ * of its own: a frame keeps the set it was submitted with (frames in flight, a re-run after an overflow, GSWT_OPT_GRAPH's replay -- a
+ * node argument), setting volumes waits for no frame and allocates nothing.
+ *
+ * Proxy passes.  gswt_proxy_render, gswt_proxy_render_ortho and gswt_proxy_render_sphere read the set in force when they are called
+ * and see only its volumes flagged GSWT_CLIP_GROUND; the same rule is applied to those volumes alone at the fragment's world hit point.
+ * A hidden fragment is discarded: its colour and depth keep what was there, like a fragment under clip_height.  In the sphere pass the
+ * test joins what each of the two candidates (near, then far) must pass, so a near surface that is cut away shows the inside of the far
+ * one.  Without a GROUND volume the passes are bit for bit what they were.
+ *
+ * Refused with GSWT_ERR_BAD_ARG, the volume's index and the field named in gswt_last_error and the set in force unchanged:
+ * n > GSWT_MAX_CLIP_VOLUMES; v == NULL with n > 0; an unknown shape; an unknown flag bit; a nonzero reserved word; a non-finite entry of
+ * a row the shape reads.  With volumes set, a submit returns GSWT_ERR_BAD_ARG before anything is enqueued when GSWT_OPT_STRICT_VS = 0
+ * (sequence v2 has no clipped form).  Out of scope: soft edges, per-pixel clipping of a splat's footprint, the CPU oracle. */
+#define GSWT_MAX_CLIP_VOLUMES 8
+#define GSWT_CLIP_BOX        0u   /* inside: max(|u0|, |u1|, |u2|) <= 1          */
+#define GSWT_CLIP_ELLIPSOID  1u   /* inside: (u0*u0 + u1*u1) + u2*u2 <= 1        */
+#define GSWT_CLIP_HALFSPACE  2u   /* inside: u2 <= 0   (rows 0 and 1 are unread) */
+#define GSWT_CLIP_KEEP    1u      /* flag: a keep volume (hide what is outside); without it a cut volume (hide what is inside) */
+#define GSWT_CLIP_GROUND  2u      /* flag: the proxy passes apply this volume too */
+typedef struct gswt_clip_volume {
+    float    world_to_unit[12];   /* rows 0..2 of an affine map, row-major 3 x 4: world point -> the volume's unit frame */
+    uint32_t shape, flags;
+    uint32_t reserved[2];         /* 0 */
+} gswt_clip_volume;               /* 64 bytes */
+GSWT_API int gswt_set_clip_volumes(gswt_ctx *ctx, const gswt_clip_volume *v, size_t n);   /* NULL or n = 0: off (the default) */
+
 /* GSWTRenderer::new (renderer.rs:31-349): uploads PreloadData.tile_splats_merged.tex_data
  * (8 u32 per splat, renderer.rs:236-248) and all static base lists (renderer.rs:290-327).
  * lists is [n_lod][n_tile][n_view] row-major. */

@@ -2,7 +2,8 @@
 // versioned resource may be refilled) as a stand-alone host program, for tests/test_frame_mode_rules_cpu.py:
 //   g++ -std=c++17 -O1 -Wall -Wextra -Werror -I gswt_renderer_amd/csrc tools/frame_modes_main.cpp -o frame_modes
 // Exhaustive over both rules' inputs; prints one "FAIL ..." line per violated property (at most 20) and, last, "free_version: N states"
-// and "project_modes: N inputs, N strict outputs".  Exit status 1 when anything failed.
+// and "project_modes: N inputs, N strict outputs".  Exit status 1 when anything failed.  The clip volumes' count is held at 0 here: these are
+// the 64 inputs and 32 instantiations of a frame without volumes; tools/frame_modes_clip_main.cpp checks the rule with the count as a seventh input.
 #include <cstdio>
 
 #include "gswt_frame_modes.h"
@@ -13,6 +14,7 @@ struct Modes {
     float aa_s;
     struct { float fade_end, fog_density; } atm;
     int sty_ver, shd_ver;
+    struct { unsigned n; } clip;
 };
 
 static int n_failed = 0;
@@ -47,7 +49,7 @@ int main()
     for (int in = 0; in < 64; in++) {
         const bool strict_vs = in & 1, ortho = in & 2, aa = in & 4, atm = in & 8, sty = in & 16, shd = in & 32;
         for (int how = 1; how <= (atm ? 3 : 1); how++) {
-            Modes m = {strict_vs, ortho, aa ? 0.25f : 0.0f, {0.0f, 0.0f}, sty ? 3 : -1, shd ? 0 : -1};
+            Modes m = {strict_vs, ortho, aa ? 0.25f : 0.0f, {0.0f, 0.0f}, sty ? 3 : -1, shd ? 0 : -1, {0u}};
             if (atm && (how & 1)) m.atm.fade_end = 100.0f;
             if (atm && (how & 2)) m.atm.fog_density = 0.5f;
             const gswt::ProjectModes p = gswt::project_modes(m);
@@ -58,6 +60,7 @@ int main()
             CHECK(p.atm == (atm && strict), "project_modes input %d (atmosphere by %d)", in, how);
             CHECK(p.sty == (sty && strict), "project_modes input %d", in);
             CHECK(p.shd == (shd && strict), "project_modes input %d", in);
+            CHECK(!p.clip, "project_modes input %d", in);
             if (p.strict) reached[p.ortho | p.aa << 1 | p.atm << 2 | p.sty << 3 | p.shd << 4] = true;
         }
         n_inputs++;
