@@ -172,10 +172,11 @@ try {
         if (value < 0 || value > 4096) return fail(c, GSWT_ERR_BAD_ARG, "GSWT_OPT_ANTIALIAS: 0 (off) or 1..4096 (filter variance in 1/1024 px^2), not %d", value);
         c->opt.antialias = value; return GSWT_OK;
     case GSWT_OPT_COMPOSITE:
+        // (1: once the decoupled-waves compositor, 2: once k_composite<FOLD>; both removed, DESIGN.md sections 6 and 10.  Accepted, without effect.)
         if (value < 0 || value > 2) return fail(c, GSWT_ERR_BAD_ARG, "unknown compositor variant %d", value);
-        c->opt.composite = value; return GSWT_OK;
+        return GSWT_OK;
     case GSWT_OPT_NO_CHUNK_CULL: c->opt.no_chunk_cull = value != 0; return GSWT_OK;
-    case GSWT_OPT_ITEM_ORDER: c->opt.item_order = value != 0; return GSWT_OK;
+    case GSWT_OPT_ITEM_ORDER: return GSWT_OK;      // (once heaviest-first work items; removed.  Accepted, without effect.)
     case GSWT_OPT_DEPTH_SORT:
         if (value < 0 || value > 2) return fail(c, GSWT_ERR_BAD_ARG, "GSWT_OPT_DEPTH_SORT: 0 (auto), 1 (global passes) or 2 (tile-local)");
         c->opt.depth_sort = value; c->depth_max_tile_len = 0;
@@ -761,8 +762,8 @@ static int enqueue_frame(gswt_ctx* c, FrameSlot& sl)
     sl.sorted_vals = vals; sl.sorted_final = false;
     if (c->opt.timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvSorted], s));
     if (c->opt.timing >= 2) HIP_TRY(c, hipEventRecord(ev[kEvRanges], s));
-    launch_composite(s, f, b, vals, out_rows, c->opt.composite, depth_order && !sl.depth_local ? b.krange() : nullptr, sl.depth_passes, depth_order,
-                     c->opt.item_order != 0, c->opt.timing >= 1 ? ev[kEvCompositeBegin] : nullptr, c->opt.timing >= 1 ? ev[kEvCompositeEnd] : nullptr,
+    launch_composite(s, f, b, vals, out_rows, depth_order && !sl.depth_local ? b.krange() : nullptr, sl.depth_passes, depth_order,
+                     c->opt.timing >= 1 ? ev[kEvCompositeBegin] : nullptr, c->opt.timing >= 1 ? ev[kEvCompositeEnd] : nullptr,
                      (int)a.cfg.out_format);
     c->last_n_tiles = (uint32_t)n_tiles;
     c->last_slot = (int)(&sl - c->slots);

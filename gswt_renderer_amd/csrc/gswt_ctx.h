@@ -334,14 +334,11 @@ struct Options {
     int projection = 0;
     // GSWT_OPT_ANTIALIAS: variance of the pixel filter in 1/1024 px^2 (0 = off, 1..4096).  Read when a frame is submitted, like the projection.
     int antialias = 0;
-    // GSWT_OPT_COMPOSITE: 0 = k_composite + k_combine, 1 = k_composite_dw (decoupled waves) + k_combine, 2 = the same as 0
-    int composite = 0;
     int no_chunk_cull = 0;                 // GSWT_OPT_NO_CHUNK_CULL: k_cull keeps every chunk of a surviving draw (A/B and tests: same image)
     int no_merge_reuse = 0;                // GSWT_OPT_NO_MERGE_REUSE: every merged group is re-sorted at every sort event
     // GSWT_OPT_DEPTH_SORT: 0 / 2 = tile-local (lists of any length: the ones beyond the LDS buffer go through global memory,
     // k_tile_depth_sort_xl), 1 = the global passes.
     int depth_sort = 0;
-    int item_order = 0;                    // GSWT_OPT_ITEM_ORDER: 1 = the compositor's work items heaviest first (k_items)
 };
 
 }  // namespace gswt

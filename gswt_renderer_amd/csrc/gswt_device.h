@@ -426,9 +426,9 @@ void launch_project(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t 
 void launch_emit(hipStream_t s, const Frame& f, const FrameBufs& b, uint32_t* keys, uint32_t* dkeys, uint32_t* krange, uint32_t n_launch);
 // b.out receives the image in out_format (kOut*; the 8-bit formats store one u32 per pixel through the float4 pointer, the video formats
 // their planes of out_rows x f.out_w samples, both even), b.out_depth (when set) the depth image in f32, b.out_pick (when set) the pick image
-// (gswt_pick records; then `vals` is also what k_pick_resolve reads behind the compositors).
-void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
-                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format);
+// (gswt_pick records; then `vals` is also what k_pick_resolve reads behind the compositor).
+void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, const uint32_t* krange,
+                      uint32_t depth_passes, bool report_max, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format);
 void launch_totals(hipStream_t s, uint32_t* super_sums, SuperSums ss, FrameCounters* counters, uint32_t pair_cap);
 
 // LSD radix sort of (keys, vals) on key bits [0, key_bits), ping-pong between the a and b buffers; returns 0 if the result is in a, 1 if in b.

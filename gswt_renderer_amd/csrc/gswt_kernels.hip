@@ -9,8 +9,7 @@
 //                   the tile id as payload (depth order); k_mg_* : merged-group lists on the device
 //   k_items       : work items (tile, segment of its list: GSWT_OPT_SEGMENT pairs) from the per-tile [start, end) the last pass leaves
 //   k_composite   : front-to-back alpha compositing (fs_main gswt.wgsl:425-435 + blend/depth state
-//                   renderer.rs:118-129,179-185): LDS-staged batches, per-sub-block lists, wave ballot early termination;
-//                   k_composite_dw: the same with the four waves of an item decoupled
+//                   renderer.rs:118-129,179-185): LDS-staged batches, per-sub-block lists, wave ballot early termination
 //   k_combine     : folds the segment partials of long tile lists; k_unshard : all-gathered shards -> frame
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off.  Contraction is OFF for the
@@ -2127,7 +2126,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
 // tens of thousands): one launch instead of count + 3 scan launches.
 // GSWT_ORDER_DEPTH (krange != nullptr): also the depth sort's pass check -- depth_passes_needed = 8-bit passes this frame's depth range needs;
 // more than were launched = the pair list is not in depth order: the frame is flagged (rerun) and the host re-runs it with more passes.
-template <bool HEAVY>
 __global__ __launch_bounds__(1024) void k_items(const uint2* __restrict__ ranges, int n_tiles, uint32_t seg,
                                                 uint32_t* __restrict__ item_base, uint4* __restrict__ item_tab, uint32_t max_items,
                                                 const uint32_t* __restrict__ krange, uint32_t n_launched, FrameCounters* __restrict__ counters,
@@ -2205,87 +2203,16 @@ __global__ __launch_bounds__(1024) void k_items(const uint2* __restrict__ ranges
         if (lane == 63u) s_tot = pi;
     }
     __syncthreads();
-    if (!HEAVY) {
 #pragma unroll
-        for (int j = 0; j < kPer; j++) {
-            const int t = base + j * 1024 + (int)threadIdx.x;
-            if (t < n_tiles) {
-                const uint32_t first = carry + s_t[j * 16 + (int)w] + inc[j] - cnt[j];
-                item_base[t] = first;
-                const uint32_t multi = cnt[j] > 1u ? 1u : 0u;
-                for (uint32_t k = 0; k < cnt[j] && first + k < max_items; k++) {
-                    const uint32_t a = r[j].x + k * seg;
-                    item_tab[first + k] = make_uint4((uint32_t)t, (k << 1) | multi, a, min(r[j].y, a + seg));
-                }
-            }
-        }
-    } else {
-        // GSWT_OPT_ITEM_ORDER = 1, heaviest first: the compositor's workgroups start in table order, so the table lists the work items by
-        // falling length -- class 0: the full segments (`seg` pairs), classes 1 .. 15: the last (or only) segment of a tile by sixteenths of
-        // `seg` -- and the short ones fill the slots the long ones leave.  item_base[t] stays the tile's first PARTIAL slot (k_composite
-        // writes a segment's partial to item_base[tile] + segment, k_combine reads them from there): only the hand-out order changes.  Inside a
-        // class the order is whatever the waves' LDS atomics make it (the image does not depend on it).  A workgroup orders the items of its
-        // own 8 192 tiles (c3: the frame's; c5: a quarter's).
-        constexpr uint32_t kCls = 16u;
-        __shared__ uint32_t s_cls[kCls], s_off[kCls];
-        if (threadIdx.x < kCls) s_cls[threadIdx.x] = 0u;
-        __syncthreads();
-        uint32_t full[kPer], rcls[kPer];                 // full segments of the tile; class of its remainder item (kCls: none)
-#pragma unroll
-        for (int j = 0; j < kPer; j++) {
-            const uint32_t len = r[j].y - r[j].x;
-            full[j] = cnt[j] ? (seg_pow2 ? len >> seg_sh : len / seg) : 0u;
-            const uint32_t rem = len - full[j] * seg;
-            rcls[j] = cnt[j] > full[j] ? (rem ? (kCls - 1u) - min(kCls - 1u, ((rem - 1u) * kCls) / seg) : kCls - 1u) : kCls;
-            if (rcls[j] == 0u) rcls[j] = 1u;             // (class 0 is the full segments' alone: its slots are handed out by a scan)
-        }
-        // per-class counts: one LDS atomic per wave and class present
-#pragma unroll
-        for (int j = 0; j < kPer; j++) {
-            uint32_t fs = full[j];
-            fs = wave_sum(fs);
-            if (lane == 0u && fs) atomicAdd(&s_cls[0], fs);
-            unsigned long long left = ballot64(rcls[j] < kCls);
-            while (left) {
-                const uint32_t c = (uint32_t)__shfl((int)rcls[j], (int)__ffsll((long long)left) - 1, 64);
-                const unsigned long long m = ballot64(rcls[j] == c);
-                if (lane == 0u) atomicAdd(&s_cls[c], (uint32_t)__popcll(m));
-                left &= ~m;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0u) { uint32_t a = 0; for (uint32_t c = 0; c < kCls; c++) { s_off[c] = a; a += s_cls[c]; } }
-        __syncthreads();
-        const unsigned long long lt = (1ull << lane) - 1ull;
-#pragma unroll
-        for (int j = 0; j < kPer; j++) {
-            const int t = base + j * 1024 + (int)threadIdx.x;
+    for (int j = 0; j < kPer; j++) {
+        const int t = base + j * 1024 + (int)threadIdx.x;
+        if (t < n_tiles) {
             const uint32_t first = carry + s_t[j * 16 + (int)w] + inc[j] - cnt[j];
-            if (t < n_tiles) item_base[t] = first;
+            item_base[t] = first;
             const uint32_t multi = cnt[j] > 1u ? 1u : 0u;
-            // the full segments: a wave scan of their counts, one LDS atomic per wave for the run of slots
-            const uint32_t fi = wave_incl_scan(full[j], lane);
-            uint32_t fb = 0;
-            if (lane == 63u && fi) fb = atomicAdd(&s_off[0], fi);
-            fb = (uint32_t)__shfl((int)fb, 63, 64) + fi - full[j];
-            for (uint32_t k = 0; k < full[j]; k++) {
-                const uint32_t a = r[j].x + k * seg, pos = carry + fb + k;
-                if (pos < max_items) item_tab[pos] = make_uint4((uint32_t)t, (k << 1) | multi, a, a + seg);
-            }
-            // the remainder items, class by class
-            unsigned long long left = ballot64(rcls[j] < kCls);
-            while (left) {
-                const int src = (int)__ffsll((long long)left) - 1;
-                const uint32_t c = (uint32_t)__shfl((int)rcls[j], src, 64);
-                const unsigned long long m = ballot64(rcls[j] == c);
-                uint32_t pb = 0;
-                if (lane == (uint32_t)src) pb = atomicAdd(&s_off[c], (uint32_t)__popcll(m));
-                pb = (uint32_t)__shfl((int)pb, src, 64);
-                if (rcls[j] == c) {
-                    const uint32_t k = full[j], a = r[j].x + k * seg, pos = carry + pb + (uint32_t)__popcll(m & lt);
-                    if (pos < max_items) item_tab[pos] = make_uint4((uint32_t)t, (k << 1) | multi, a, r[j].y);
-                }
-                left &= ~m;
+            for (uint32_t k = 0; k < cnt[j] && first + k < max_items; k++) {
+                const uint32_t a = r[j].x + k * seg;
+                item_tab[first + k] = make_uint4((uint32_t)t, (k << 1) | multi, a, min(r[j].y, a + seg));
             }
         }
     }
@@ -2324,13 +2251,12 @@ constexpr uint32_t kNullRec = 256u;        // LDS record no pixel is ever inside
 // longest one -- which paces the wave -- is close to their mean: 1.98 M wave-steps against 2.28 M on the c3 frame).
 // List entries are LDS byte offsets of the records (u16), padded to an even length with the offset of a null record
 // whose r^2 is +inf: the walk needs neither a shift nor an `i < n` test nor a mid-pair exit.
-// BATCH: pairs per staged batch (256 in k_composite, 128 in k_composite_dw); the list stride and the null record's index follow it.
 // ZOUT: also blends the splats' depths (s_dep, staged as for the depth test) into az with the colour's weights (gswt_hip.h, depth output).
 // PICK: also keeps the lane's largest weight so far (wmax, strict >: the front-most of equal weights stays) and the pair that had it (wpair,
 // its index in the sorted pair list; pair_base = the index of the batch's first pair).  Inside the walk the winner is the STEP number -- uniform,
 // so the select takes it from an SGPR -- and the step's list entry is looked up once behind the loop (gswt_hip.h, pick output).
-template <bool EARLY, bool DEPTH, bool COLF, bool ZOUT, bool PICK, uint32_t BATCH>
-__device__ __forceinline__ void composite_bin_walk_pick(const Frame& f, const CompLane& g, uint32_t n, const float4* s_q0, const float4* s_q1,
+template <bool EARLY, bool DEPTH, bool COLF, bool ZOUT, bool PICK>
+__device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLane& g, uint32_t n, const float4* s_q0, const float4* s_q1,
                                                    const float4* s_q2, const uint32_t* s_bb, const float* s_dep, uint16_t* wlist,
                                                    float dbuf, float t_eps, float& T, float& ar, float& ag, float& ab, float& az, bool& wave_live,
                                                    uint32_t pair_base, float& wmax, uint32_t& wpair)
@@ -2338,15 +2264,13 @@ __device__ __forceinline__ void composite_bin_walk_pick(const Frame& f, const Co
     constexpr bool SDEP = DEPTH || ZOUT;                                       // the pairs' depths are staged in s_dep
     const uint32_t lane = g.lane, grp = g.grp;
     const float lx = g.lx, ly = g.ly;
-    constexpr uint32_t kStride = BATCH == 256u ? kListStride : BATCH + 8u;     // u16 entries per sub-block list
-    constexpr uint32_t kNull = BATCH == 256u ? kNullRec : BATCH;               // index of the null record behind the batch
-    uint16_t* const my_list = wlist + grp * kStride;
+    uint16_t* const my_list = wlist + grp * kListStride;
     // bin: append this batch's hits to the four sub-block lists (list order preserved)
     uint32_t cnt0 = 0, cnt1 = 0, cnt2 = 0, cnt3 = 0;
 #pragma unroll
-    for (int c = 0; c < (int)(BATCH / 64u); c++) {
+    for (int c = 0; c < (int)(256u / 64u); c++) {
         const uint32_t idx = (uint32_t)c * 64u + lane;
-        // the staged hit mask of the pair: this wave's strip is bits r0 .. r0 + 3 (r0 = 4 x strip).  Read unconditionally (idx < BATCH: a
+        // the staged hit mask of the pair: this wave's strip is bits r0 .. r0 + 3 (r0 = 4 x strip).  Read unconditionally (idx < 256: a
         // slot past the batch's end holds an older batch's word) and cleared by a select: predicates that come out of an `if` reach the
         // ballots as 0 / 1 registers compared once more -- eight vector instructions per 64 pairs that four v_cmp already answered
         const uint32_t hm_raw = s_bb[idx] >> (uint32_t)g.r0;
@@ -2355,7 +2279,7 @@ __device__ __forceinline__ void composite_bin_walk_pick(const Frame& f, const Co
         const unsigned long long m0 = ballot64(h0), m1 = ballot64(h1), m2 = ballot64(h2), m3 = ballot64(h3);
 #define GSWT_APPEND(H, M, CNT, G)                                                                                         \
         if (M) {                                                                                                            \
-            if (H) wlist[(G) * kStride + (CNT) + __builtin_amdgcn_mbcnt_hi((uint32_t)((M) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)(M), 0u))] = (uint16_t)(idx * 16u); \
+            if (H) wlist[(G) * kListStride + (CNT) + __builtin_amdgcn_mbcnt_hi((uint32_t)((M) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)(M), 0u))] = (uint16_t)(idx * 16u); \
             CNT += (uint32_t)__popcll(M);                                                                                   \
         }
         GSWT_APPEND(h0, m0, cnt0, 0u) GSWT_APPEND(h1, m1, cnt1, 1u) GSWT_APPEND(h2, m2, cnt2, 2u) GSWT_APPEND(h3, m3, cnt3, 3u)
@@ -2367,7 +2291,7 @@ __device__ __forceinline__ void composite_bin_walk_pick(const Frame& f, const Co
     if (n_max == 0u) return;
     // pad this group's list with the null record up to the wave's even step count (+2: the walk reads two entries ahead)
     const uint32_t n_steps = (n_max + 1u) & ~1u;
-    for (uint32_t p = n_mine + (lane & 15u); p < n_steps + 2u; p += 16u) my_list[p] = (uint16_t)(kNull * 16u);
+    for (uint32_t p = n_mine + (lane & 15u); p < n_steps + 2u; p += 16u) my_list[p] = (uint16_t)(kNullRec * 16u);
     // walk: one splat per 16-lane group per step.  Two-deep software pipeline, unrolled x2 so the two record register
     // sets (A, B) never need copying: the list entry is fetched two steps ahead, the record one step ahead.
     const char* const q0b = reinterpret_cast<const char*>(s_q0);
@@ -2437,18 +2361,6 @@ __device__ __forceinline__ void composite_bin_walk_pick(const Frame& f, const Co
     // Saturated pixels keep accumulating weights below t_eps (the oracle has no cut at all); the early-out is per wave
     // and per batch: once no pixel of the strip has T >= t_eps the wave stops binning and walking.
     if (EARLY && ballot64(T >= t_eps) == 0ull) wave_live = false;
-}
-
-// composite_bin_walk_pick without PICK: the walk of a frame without a pick output (the decoupled-waves compositor runs no other)
-template <bool EARLY, bool DEPTH, bool COLF, bool ZOUT, uint32_t BATCH = 256u>
-__device__ __forceinline__ void composite_bin_walk(const Frame& f, const CompLane& g, uint32_t n, const float4* s_q0, const float4* s_q1,
-                                                   const float4* s_q2, const uint32_t* s_bb, const float* s_dep, uint16_t* wlist,
-                                                   float dbuf, float t_eps, float& T, float& ar, float& ag, float& ab, float& az, bool& wave_live)
-{
-    float wmax = 0.0f;
-    uint32_t wpair = 0u;
-    composite_bin_walk_pick<EARLY, DEPTH, COLF, ZOUT, false, BATCH>(f, g, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, az, wave_live,
-                                                               0u, wmax, wpair);
 }
 
 // Measured and dropped in the walk (all bit-identical, c3, base 97 us):
@@ -2533,7 +2445,7 @@ __device__ __forceinline__ void store_video(float4* out, int rows, int out_w, in
     }
 }
 
-// ---- the pieces k_composite, k_composite_dw and k_combine share: one statement each, so that the three stay bit-identical ----
+// ---- the pieces k_composite and k_combine share: one statement each, so that the two stay bit-identical ----
 // Where a work item's screen tile lies: tile row tyl inside this shard's image (the rows it stores) and pixel origin (bx, by) in the frame
 // (a row-sharded ctx owns tile rows shard_index, + shard_count, ...)
 struct CompTile { int tyl, bx, by; };
@@ -2741,7 +2653,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
             slot_nxt = vals[min(base + 512u + tid, last_pair)];
         }
         if (wave_live)
-            composite_bin_walk_pick<EARLY, DEPTH, COLF, ZOUT, PICK, 256u>(f, cl, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, az, wave_live,
+            composite_bin_walk<EARLY, DEPTH, COLF, ZOUT, PICK>(f, cl, n, s_q0, s_q1, s_q2, s_bb, s_dep, wlist, dbuf, t_eps, T, ar, ag, ab, az, wave_live,
                                                                      base, wmax, wpair);
 #ifdef GSWT_TRACE
         tr_walk += GSWT_NOW() - tr_t0;
@@ -2763,8 +2675,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
     const float k255 = 1.0f / 255.0f;      // colour is continuous: sum(w * byte) / 255 vs sum(w * (byte / 255)) differ in the last bits only
     if (!COLF) { ar *= k255; ag *= k255; ab *= k255; }
     if (multi_seg) {
-        // partial (C, T) of this segment, in the slot the tile's first + the segment's number (the table position only while the table is
-        // in tile order); k_combine folds the segments front to back
+        // partial (C, T) of this segment, in the slot the tile's first + the segment's number; k_combine folds the segments front to back
         const size_t pi = (size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid;
         partials[pi] = make_float4(ar, ag, ab, T);
         if (ZOUT) partials_z[pi] = az;
@@ -2790,160 +2701,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((DEPTH || C
 // The phases of this kernel add up (round-2 ablations at c3: 15 us launch + output, 28 us record gathers, 2.5 us binning,
 // 50 us walk), but hiding the gathers behind another item's walk inside a workgroup is not what makes them overlap: the
 // dispatcher's dynamic hand-out of ~16 k short workgroups does that better than a static stride over them.
-
-// ------------------------------------------------------------------------------------
-// k_composite_dw: the compositor with DECOUPLED waves (round 4; GSWT_OPT_COMPOSITE = 1).  Same work items, same lane -> pixel map, same
-// F3 / F4 / blend order (bit-identical image), but no workgroup barrier inside an item:
-//   * batches of 128 pairs go through a ring of three LDS buffers;
-//   * batch k is staged by two waves (waves 0, 1 stage the even batches, waves 2, 3 the odd ones: 64 pairs each, the record gathered
-//     into registers two batches of its own earlier, as k_composite's staging lane does);
-//   * per buffer two monotonic LDS counters: `staged` (half batches written into it, ever) and `done` (wave walks finished on it, ever).
-//     A wave walks batch k once staged[k % 3] >= 2 (k / 3 + 1); a buffer is refilled with batch k once done[k % 3] >= 4 (k / 3), i.e.
-//     once all four waves have walked batch k - 3.  A wave stages up to two batches ahead of its own walk without waiting (and waits only
-//     for a batch it is about to walk itself), so the four waves of an item run up to two batches apart instead of meeting at two
-//     s_barriers per 256 pairs -- k_composite idles 41 % of its wave-slots there, a batch lasting as long as its longest sub-block list.
-//   Waiting = polling an LDS word with s_sleep between reads.  EARLY: a wave whose strip is saturated keeps staging and counting, skips
-//   its walks; when all four are, every wave leaves at its next poll.
-// LDS 18.4 KB (k_composite: 17.9 KB): 8 workgroups per CU.
-// ------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lds_peek(const uint32_t* p) { return *reinterpret_cast<const volatile uint32_t*>(p); }
-constexpr int kDwSleep = 1;            // s_sleep units (64 clocks) between two polls of a counter
-
-template <bool EARLY, bool DEPTH, bool COLF, int OUTF, bool ZOUT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COLF ? 6 : (DEPTH || ZOUT) ? 7 : 8, 8))) void k_composite_dw(const Frame f,
-                                                   const uint32_t* __restrict__ item_base, const uint4* __restrict__ item_tab,
-                                                   const uint32_t* __restrict__ vals, const Rec* __restrict__ recs,
-                                                   const float* __restrict__ depths, const float4* __restrict__ col_f,
-                                                   const float4* __restrict__ bg_rgba, const float* __restrict__ bg_depth,
-                                                   float4* __restrict__ out, float4* __restrict__ partials,
-                                                   int n_tiles, int out_rows, float* __restrict__ out_depth, float* __restrict__ partials_z)
-{
-    constexpr uint32_t B = 128u, NBUF = 3u, BS = B + 1u;        // pairs per batch, ring depth, records per buffer (the last one = the null record)
-    __shared__ float4 s_q0[NBUF * BS], s_q1[NBUF * BS];
-    __shared__ uint32_t s_bb[NBUF * B];
-    __shared__ float4 s_q2[COLF ? NBUF * BS : 1];
-    __shared__ float s_dep[(DEPTH || ZOUT) ? NBUF * BS : 1];
-    __shared__ uint16_t s_list[4][4][B + 8u];
-    __shared__ uint32_t s_staged[NBUF], s_done[NBUF], s_dead;
-    const uint32_t item = blockIdx.x;
-    const uint32_t n_items = item_base[n_tiles];
-    const uint4 it = item_tab[item];
-    if (item >= n_items) return;
-    const int tile = (int)it.x;
-    const bool multi_seg = (it.y & 1u) != 0u;
-    const auto [tyl, bx, by] = comp_tile(f, (uint32_t)tile);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    const uint32_t grp = lane >> 4, gi = lane & 15u;
-    const int lxi = (int)grp * 4 + (int)(gi & 3u), lyi = (int)wave * 4 + (int)(gi >> 2);
-    const int px = bx + lxi, py = by + lyi;
-    const bool inside = px < f.width && py < f.height;
-    const float lx = (float)lxi + 0.5f, ly = (float)lyi + 0.5f;
-    const float fbx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)bx)));
-    const float fby = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)by)));
-    const float hW = 0.5f * f.W, hHn = -0.5f * f.H;
-    const float c0x = hW - fbx, c0y = 0.5f * f.H - fby;
-    uint16_t* const wlist = &s_list[wave][0][0];
-    const CompLane cl = {lx, ly, (int)(wave * 4u), lane, grp};
-    const uint2 rg = make_uint2(it.z, it.w);
-    float T = (EARLY && !inside) ? 0.0f : 1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, az = 0.0f;
-    float dbuf = 1.0f;
-    if (DEPTH && inside) dbuf = bg_depth[(size_t)py * f.width + px];
-    const float t_eps = f.t_eps;
-    bool wave_live = true, counted_dead = false;
-    if (tid < NBUF) {
-        s_staged[tid] = 0u; s_done[tid] = 0u;
-        comp_null_record<DEPTH || ZOUT, COLF>(s_q0, s_q1, s_q2, s_dep, tid * BS + B);      // the null record of buffer tid
-    }
-    if (tid == 0) s_dead = 0u;
-    const uint32_t n_pairs = rg.y - rg.x;
-    const uint32_t nb = (n_pairs + B - 1u) / B;
-    const uint32_t last_pair = rg.y - 1u;
-    const uint32_t half = wave & 1u;
-    // the batch this wave stages next: ks = (wave >> 1), + 2, + 2, ...; (sb, su) = (ks % 3, ks / 3) kept incrementally
-    uint32_t ks = wave >> 1, sb = wave >> 1, su = 0u;
-    float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra, rd = ra;
-    float rbw = 0.f;
-    uint32_t slot_nxt = 0;
-#define GSWT_DW_PAIR(KB) min(rg.x + (KB) * B + half * 64u + lane, last_pair)
-#define GSWT_DW_LOAD(SLOT)                                                                           \
-        {                                                                                           \
-            const float4* rp = reinterpret_cast<const float4*>(recs + (SLOT));                      \
-            ra = rp[0];                                                                             \
-            rb = rp[1];                                                                             \
-            if (DEPTH || ZOUT) rbw = depths[(SLOT)];                                                \
-            if (COLF) rd = col_f[(SLOT)];                                                           \
-        }
-    if (n_pairs) {
-        const uint32_t slot0 = vals[GSWT_DW_PAIR(ks)];
-        GSWT_DW_LOAD(slot0)
-        slot_nxt = vals[GSWT_DW_PAIR(ks + 2u)];
-    }
-    __syncthreads();                                    // the counters and the null records are in place: the only barrier of the item
-    uint32_t kb = 0u, ku = 0u;                           // (k % 3, k / 3) of the batch this wave walks next
-    bool all_dead = false;
-    for (uint32_t k = 0; k < nb && !all_dead; k++) {
-        // ---- staging duties: everything up to two batches ahead of my walk whose buffer is free; a batch I am about to walk is waited for
-        while (ks < nb && ks <= k + 2u) {
-            const uint32_t need = 4u * su;
-            if (lds_peek(&s_done[sb]) < need) {
-                if (ks > k) break;                      // not needed yet: try again after the next walk
-                while (lds_peek(&s_done[sb]) < need) {
-                    if (EARLY && lds_peek(&s_dead) == 4u) { all_dead = true; break; }
-                    __builtin_amdgcn_s_sleep(kDwSleep);
-                }
-                if (all_dead) break;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            const uint32_t li = half * 64u + lane;      // my pair inside the batch
-            if (ks * B + li < n_pairs) comp_stage<DEPTH || ZOUT, COLF>(hW, hHn, c0x, c0y, ra, rb, rbw, rd, s_q0, s_q1, s_q2, s_dep, s_bb, sb * BS + li, sb * B + li);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (lane == 0u) atomicAdd(&s_staged[sb], 1u);
-            ks += 2u; sb += 2u; if (sb >= 3u) { sb -= 3u; su += 1u; }
-            GSWT_DW_LOAD(slot_nxt)                       // the record of my next staging batch, the slot index of the one after it
-            slot_nxt = vals[GSWT_DW_PAIR(ks + 2u)];
-        }
-        if (all_dead) break;
-        // ---- wait for batch k, walk it
-        {
-            const uint32_t target = 2u * (ku + 1u);
-            while (lds_peek(&s_staged[kb]) < target) {
-                if (EARLY && lds_peek(&s_dead) == 4u) { all_dead = true; break; }
-                __builtin_amdgcn_s_sleep(kDwSleep);
-            }
-            if (all_dead) break;
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        }
-        const uint32_t n = min(B, n_pairs - k * B);
-        if (wave_live)
-            composite_bin_walk<EARLY, DEPTH, COLF, ZOUT, B>(f, cl, n, s_q0 + kb * BS, s_q1 + kb * BS, s_q2 + (COLF ? kb * BS : 0u), s_bb + kb * B,
-                                                            s_dep + ((DEPTH || ZOUT) ? kb * BS : 0u), wlist, dbuf, t_eps, T, ar, ag, ab, az, wave_live);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0u) {
-            atomicAdd(&s_done[kb], 1u);
-            if (EARLY && !wave_live && !counted_dead) atomicAdd(&s_dead, 1u);
-        }
-        if (EARLY && !wave_live) counted_dead = true;
-        kb += 1u; if (kb >= 3u) { kb = 0u; ku += 1u; }
-        if (EARLY && lds_peek(&s_dead) == 4u) all_dead = true;
-    }
-#undef GSWT_DW_PAIR
-#undef GSWT_DW_LOAD
-    const float k255 = 1.0f / 255.0f;
-    if (!COLF) { ar *= k255; ag *= k255; ab *= k255; }
-    if (multi_seg) {
-        const size_t pi = (size_t)(item_base[tile] + (it.y >> 1)) * 256u + tid;
-        partials[pi] = make_float4(ar, ag, ab, T);
-        if (ZOUT) partials_z[pi] = az;
-        return;
-    }
-    uint32_t tid2 = threadIdx.x;                         // (k_composite: the opaque copy of the thread id)
-    asm volatile("" : "+v"(tid2));
-    const int lxi2 = (int)(((tid2 & 63u) >> 4) * 4u + (tid2 & 3u)), lyi2 = (int)((tid2 >> 6) * 4u + ((tid2 & 15u) >> 2));
-    const int px2 = bx + lxi2, py2 = by + lyi2;
-    if (px2 < f.width && py2 < f.height)
-        comp_final_pixel<OUTF, ZOUT>(f, bg_rgba, out, out_rows, px2, py2, tyl * kTile + lyi2, T, ar, ag, ab, bg_depth, out_depth, az);
-}
 
 // Folds the per-segment partials of multi-segment tiles: (C1,T1) o (C2,T2) = (C1 + T1*C2, T1*T2).
 // One workgroup per tile, same lane -> pixel map as k_composite.  ZOUT: the partial depths fold like a colour channel (Z1 + T1*Z2).
@@ -3223,11 +2980,10 @@ uint32_t tile_depth_sort_cap() { return kTileSortCap; }
 // ranges -> per-tile segment counts -> item_base (exclusive scan, item_base[n_tiles] = #items) ->
 // k_composite over an upper bound of items -> k_combine, storing the image in format OUTF.
 // ZOUT: the frame's depth image is written as well, when b.out_depth is set (gswt_render_depth).
-// PICK: its pick image, when b.out_pick is set (gswt_render_pick) -- always through k_composite (its decoupled-waves twin is a bit-identical
-// A/B switch and has no PICK instantiation) --, resolved in place by k_pick_resolve from the same `vals`.
+// PICK: its pick image, when b.out_pick is set (gswt_render_pick), resolved in place by k_pick_resolve from the same `vals`.
 // E, D, C: the compositor's <early-out, depth test, float colours> (debug draw modes: float colours from the side buffer, no early-out).
-void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, int variant, const uint32_t* krange,
-                      uint32_t depth_passes, bool report_max, bool heavy_first, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format)
+void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const uint32_t* vals, int out_rows, const uint32_t* krange,
+                      uint32_t depth_passes, bool report_max, hipEvent_t ev_begin, hipEvent_t ev_end, int out_format)
 {
     const int n_tiles = (int)b.n_tiles;
     const uint32_t seg = b.seg;
@@ -3237,21 +2993,15 @@ void launch_composite(hipStream_t s, const Frame& f, const FrameBufs& b, const u
         return;
     }
     const uint32_t max_items = (uint32_t)n_tiles + b.pair_cap / seg + 1u;
-    with_variant([&](auto HEAVY) {
-        GSWT_LAUNCH(k_items<HEAVY>, dim3((n_tiles + 8191) / 8192), dim3(1024), s, b.ranges, n_tiles, seg, b.item_base, b.item_tab, max_items, krange, depth_passes, b.counters,
-                    report_max ? 1u : 0u);
-    }, heavy_first);
+    GSWT_LAUNCH(k_items, dim3((n_tiles + 8191) / 8192), dim3(1024), s, b.ranges, n_tiles, seg, b.item_base, b.item_tab, max_items, krange, depth_passes, b.counters,
+                report_max ? 1u : 0u);
     const bool colf = f.draw_mode != 0u;
     with_variant([&](auto outf, auto pick, auto zout) {
         constexpr int OUTF = outf;          // (constants of their own: the inner lambda cannot read a captured argument at compile time)
         constexpr bool PICK = pick, ZOUT = zout;
         with_variant([&](auto C, auto E, auto D) {
-            // GSWT_OPT_COMPOSITE = 1: decoupled waves (k_composite_dw), same image bit for bit; 0 and 2: k_composite.  (The compositors carry
-            // ev_begin / ev_end themselves: GSWT_LAUNCH_TIMED.)
+            // (The compositor carries ev_begin / ev_end itself: GSWT_LAUNCH_TIMED.)
             if constexpr (C && E) return;       // (float colours have no early-out form)
-            else if (variant == 1 && !PICK)
-                GSWT_LAUNCH_TIMED((k_composite_dw<E, D, C, OUTF, ZOUT>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.item_base, b.item_tab, vals, b.recs,
-                                  b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z);
             else
                 GSWT_LAUNCH_TIMED((k_composite<E, D, C, OUTF, ZOUT, PICK>), dim3(max_items), dim3(256), s, ev_begin, ev_end, f, b.ranges, b.item_base, b.item_tab, seg, vals,
                                   b.recs, b.depths, b.col_f, b.bg_rgba, b.bg_depth, b.out, b.partials, n_tiles, out_rows, b.out_depth, b.partials_z,

@@ -234,11 +234,10 @@ enum { GSWT_OPT_NO_LOD_PREFILTER = 1, GSWT_OPT_DEBUG_VARYINGS = 2,
        GSWT_OPT_DEPTH_PASSES = 12 /* test hook: 8-bit radix passes on the depth bits the next GSWT_ORDER_DEPTH frame launches (1..4; default 3,
                                      then as many as the depth ranges of the recent frames needed); a frame whose visible depths span more
                                      bits is flagged on the device and re-run with more, like a pair-buffer overflow */,
-       GSWT_OPT_COMPOSITE = 13 /* compositor kernel: 0 (default) k_composite -- 256-pair batches staged by the whole workgroup, two barriers per
-                                  batch; 1 k_composite_dw -- the four waves of a work item decoupled (128-pair batches through a ring of three LDS
-                                  buffers, ready / consumed counters instead of barriers); 2 is accepted and runs what 0 runs (its own
-                                  compositor, which folded the segments itself instead of launching k_combine, was removed); 3 and above are
-                                  refused.  Same image bit for bit */,
+       GSWT_OPT_COMPOSITE = 13 /* no effect: there is one compositor, k_composite (256-pair batches staged by the whole workgroup, two barriers
+                                  per batch) + k_combine.  1 (once the four waves of a work item decoupled) and 2 (once a compositor that folded
+                                  the segments itself instead of launching k_combine) are accepted and run the default compositor; 3 and above
+                                  are refused */,
        GSWT_OPT_DEPTH_SORT = 14 /* how GSWT_ORDER_DEPTH orders the pairs: 0 (default) / 2 = tile passes first (depth bits as payload), then every
                                    screen tile's slice is depth-sorted by one wave / workgroup (k_tile_depth_sort: inside LDS up to 16 384 pairs,
                                    through global memory beyond); 1 = global radix passes on the depth bits in front of the tile passes.
@@ -246,8 +245,8 @@ enum { GSWT_OPT_NO_LOD_PREFILTER = 1, GSWT_OPT_DEBUG_VARYINGS = 2,
        GSWT_OPT_NO_CHUNK_CULL = 15 /* 1: the per-chunk frustum cull in front of the projection is off (every 256-entry chunk of a draw that
                                       survives the reference's tile cull is projected, as until round 3).  Same image bit for bit: the cull
                                       only leaves out chunks none of whose splats vs_main's own frustum test (gswt.wgsl:163-167) would keep */,
-       GSWT_OPT_ITEM_ORDER = 16 /* order in which the compositor's work items (screen tile, segment of its pair list) are handed out: 0 = tile
-                                  order, 1 = heaviest first (full segments, then the remainders by falling length).  Same image bit for bit */,
+       GSWT_OPT_ITEM_ORDER = 16 /* no effect: the compositor's work items (screen tile, segment of its pair list) are handed out in tile order.
+                                  1 (once heaviest first) is accepted and runs the default tile order */,
        GSWT_OPT_PROJECTION = 17 /* 0 (default): perspective, vs_main as written.  1: orthographic -- top-down maps, minimaps, sun-direction depth
                                    maps, height fields.  The vertex stage is vs_main except gswt.wgsl:213-232: the perspective Jacobian (focal / t.z,
                                    the 1.3 * htan_fov clamp, -focal t / t.z^2) is replaced by the constant affine one, J_T columns (fx, 0, 0),
@@ -344,8 +343,8 @@ GSWT_API int gswt_set_option(gswt_ctx *ctx, int key, int value);
  *     per channel  c' = c * (1.0f - F) + fog_c * F
  *     byte' = (uint32_t)rintf(fminf(fmaxf(c', 0), 1) * 255.0f)
  *     and the record's colour word becomes byte'_r | byte'_g << 8 | byte'_b << 16 | (word & 0xFF000000).
- *     Re-quantising to the record's 8-bit colour is deliberate: the projected record stays 32 bytes, the compositors are untouched and
- *     every one of their forms stays available (early-out, depth test, depth and pick outputs, GSWT_OPT_COMPOSITE = 1).  The added
+ *     Re-quantising to the record's 8-bit colour is deliberate: the projected record stays 32 bytes, the compositor is untouched and
+ *     every one of its forms stays available (early-out, depth test, depth and pick outputs).  The added
  *     error is at most half a code per splat, uncorrelated between splats.
  *   In the debug draw modes (draw_mode != 0) the colours stay the debug colours and only the fade applies.
  * gswt_debug_read_projected reports what the compositor will read: rgba[k] = (float)byte' / 255.0f for the three colours and the
@@ -689,9 +688,8 @@ GSWT_API int gswt_render_async_depth(gswt_ctx *ctx, const gswt_camera_uniforms *
  * Pointer rules are those of the depth output: out_pick is a host pointer (staged) unless out_on_device; frames in flight
  * together must write different pick buffers; a frame re-run after a pair-buffer overflow rewrites its pick.  A missing
  * out_rgba, or an out_pick equal to out_rgba or out_depth, returns GSWT_ERR_BAD_ARG before anything is enqueued.  Pick
- * frames run under GSWT_OPT_GRAPH and GSWT_OPT_TIMING as depth-output frames do.  With GSWT_OPT_COMPOSITE = 1 a pick frame
- * is composited by the default kernel, not the decoupled-waves one: the two are bit-identical A/B switches, so colour,
- * depth and pick are what either would give.  The pick image is not part of the gathers (gswt_render_gather,
+ * frames run under GSWT_OPT_GRAPH and GSWT_OPT_TIMING as depth-output frames do.  GSWT_OPT_COMPOSITE = 1 is accepted
+ * and runs the default compositor, for a pick frame as for any other.  The pick image is not part of the gathers (gswt_render_gather,
  * gswt_unshard*). */
 typedef struct {
     uint32_t map_index;  /* tile instance: TileUniforms.map_index of a static draw, the member's map id of a merged one */

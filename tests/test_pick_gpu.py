@@ -9,7 +9,7 @@ tol = 1e-4, the image contract (+ transmittance_eps with the early-out on).
 
 Then full c3 frames (1920 x 1080) against themselves: colour and depth untouched by the pick output in every out_format, sync = async
 (also replayed as a graph), short against long segments, shards, the weight bound against the colour's alpha, a re-run after a pair
-overflow, GSWT_OPT_COMPOSITE = 1, and argument errors refused before anything is enqueued."""
+overflow, and argument errors refused before anything is enqueued."""
 import ctypes as C
 
 import numpy as np
@@ -193,13 +193,12 @@ def test_shards_tile_the_pick_image(renderer, c3):
         assert not FM._raw(part[16 * len(range(r, (Hh + 15) // 16, n)):]).any()            # padding rows are zero bytes
 
 
-def test_overflow_rerun_and_composite_variant_leave_the_same_pick(renderer, c3):
+def test_overflow_rerun_leaves_the_same_pick(renderer, c3):
     W, Hh, cu, su = FO.bind_workload(renderer, c3)
     img0, p0 = FO.check_side_overflow_rerun(renderer, c3, "pick")
-    # GSWT_OPT_COMPOSITE = 1 (decoupled waves): a pick frame is composited by the default kernel, bit-identical
-    with renderer.options(COMPOSITE=1):
-        img2, z2, p2 = renderer.render(cu, su, W, Hh, depth=True, pick=True)
-        img3, z3 = renderer.render(cu, su, W, Hh, depth=True)
+    # the frames behind the re-run, with the depth image beside the pick and without the pick
+    img2, z2, p2 = renderer.render(cu, su, W, Hh, depth=True, pick=True)
+    img3, z3 = renderer.render(cu, su, W, Hh, depth=True)
     assert FM.same(p2, p0) and FM.same(img2, img0) and FM.same(img3, img0) and FM.same(z2, z3)
 
 

@@ -47,9 +47,8 @@ def _cases():
             rc["draw_mode"] = int(_RNG.integers(1, 5))
         if k % 6 == 5:
             rc["point_cloud_radius"] = 0.003
-        # round 4: the order mode (reference / global depth sort) and the compositor variant (k_composite + k_combine, decoupled waves,
-        # folded combine) rotate through the cases too
-        mode = dict(order_mode=int(k % 4 == 1), composite=(0, 1, 2)[k % 3], depth_sort=(0, 1)[(k // 4) % 2], item_order=(k // 2) % 2)
+        # round 4: the order mode (reference / depth order) and the depth sort rotate through the cases too
+        mode = dict(order_mode=int(k % 4 == 1), depth_sort=(0, 1)[(k // 4) % 2])
         out.append(pytest.param(cfg, (tuple(float(x) for x in pos), tuple(float(x) for x in tgt)), rc, bool(k % 3 == 0), mode, id=f"case{k}"))
     return out
 
@@ -58,7 +57,7 @@ def _cases():
 def test_random_sweep(renderer, cfg, cam, rc, bg, mode):
     W, Hh = (272, 176)
     t_eps = 1e-5 if cfg["surface_type"] == 0 else 0.0
-    with renderer.options(COMPOSITE=mode["composite"], DEPTH_SORT=mode["depth_sort"], ITEM_ORDER=mode["item_order"]):    # (depth-ordered cases: global passes / tile-local LDS sort)
+    with renderer.options(DEPTH_SORT=mode["depth_sort"]):    # (depth-ordered cases: global passes / tile-local LDS sort)
         with np.errstate(all="ignore"):
             img, ref, kinds, st = _run_case(renderer, cfg, cam, W, Hh, lod0=500, bg=bg, render_config=rc, t_eps=t_eps, order_mode=mode["order_mode"])
     assert H.max_abs_diff(img, ref) <= TOL + t_eps, (cfg, cam, rc, mode, kinds, st)

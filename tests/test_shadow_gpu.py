@@ -3,8 +3,8 @@ Frames are 72 x 40 (tests/ortho_ref.py) on the golden cases with the draws of th
 
 The shaded colour bytes bit for bit against tests/shadow_ref.py on the plain surface (perspective and both orthographic cameras) and
 within the derived tolerance on the HeightMap and Sphere surfaces; known answers; the light's own depth frame fed back; image, depth
-and pick against the CPU references over the GPU's own records; the same bits through graphs, frames in flight, compositor and cull
-variants, a pair-buffer overflow, output formats and shards; off leaves every output as it was; tint, shadow and fog in that order;
+and pick against the CPU references over the GPU's own records; the same bits through graphs, frames in flight, the chunk cull
+off, a pair-buffer overflow, output formats and shards; off leaves every output as it was; tint, shadow and fog in that order;
 the refusals; the proxy passes; the pipeline's keyword."""
 import ctypes as C
 import struct
@@ -295,9 +295,9 @@ def test_a_device_image_is_the_host_image(renderer, plain):
     FM.assert_frames([got], ["a"], plain, "device image")
 
 
-@pytest.mark.parametrize("opt", [L.GSWT_OPT_COMPOSITE, L.GSWT_OPT_ITEM_ORDER, L.GSWT_OPT_NO_CHUNK_CULL], ids=["composite_dw", "item_order", "no_chunk_cull"])
+@pytest.mark.parametrize("opt", [L.GSWT_OPT_NO_CHUNK_CULL], ids=["no_chunk_cull"])
 def test_compositor_and_cull_variants(renderer, plain, opt):
-    FM.check_compositor_and_cull_variant(renderer, plain, MODE, opt, ["a", "b"])
+    FM.check_with_option_on(renderer, plain, MODE, opt, ["a", "b"])
 
 
 def test_pair_buffer_overflow_rerun_keeps_the_map(renderer, plain):

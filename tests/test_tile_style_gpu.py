@@ -3,7 +3,7 @@ Frames are 72 x 40 (tests/ortho_ref.py) on the golden cases with the draws of th
 
 The styled vertex stage bit for bit against tests/tile_style_ref.py (perspective and orthographic, with and without the pixel filter,
 on the three surfaces); tint then fog against the float64 fog reference; known answers; image, depth and pick against the CPU references
-over the GPU's own styled records; the same bits through graphs, frames in flight, a pair-buffer overflow, compositor and cull variants,
+over the GPU's own styled records; the same bits through graphs, frames in flight, a pair-buffer overflow, the chunk cull off,
 output formats and shards; styles off leaves every output as it was; the refusals; the pipeline's world-keyed styles across a build
 event."""
 import ctypes as C
@@ -257,9 +257,9 @@ def test_async_frames_in_flight_keep_their_table(renderer, plain):
     FM.check_in_flight(renderer, plain, MODE, seq, waves=4, then="off", what="async, then off")
 
 
-@pytest.mark.parametrize("opt", [L.GSWT_OPT_COMPOSITE, L.GSWT_OPT_ITEM_ORDER, L.GSWT_OPT_NO_CHUNK_CULL], ids=["composite_dw", "item_order", "no_chunk_cull"])
+@pytest.mark.parametrize("opt", [L.GSWT_OPT_NO_CHUNK_CULL], ids=["no_chunk_cull"])
 def test_compositor_and_cull_variants(renderer, plain, opt):
-    FM.check_compositor_and_cull_variant(renderer, plain, MODE, opt, [MODE.on])
+    FM.check_with_option_on(renderer, plain, MODE, opt, [MODE.on])
 
 
 def test_pair_buffer_overflow_rerun_keeps_the_table(renderer, plain):

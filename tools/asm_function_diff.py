@@ -10,8 +10,8 @@ A function's text is every line from its label to its kernel descriptor (or, for
 instructions, local labels and the compiler's own comments.
 Each --rename is applied to the HEAD's symbol names and text (a new template argument in its off state, a new trailing argument type),
 after which a head function is matched with the parent function of the same name; local labels lose the function's ordinal
-(`.LBB12_3` -> `.LBB_3`).  Prints how many functions are identical, which differ (with the first differing line), which exist on one
-side only, and exits 1 when a matched function differs or a parent function has no counterpart.  The `.amdhsa_*` descriptor and the
+(`.LBB12_3` -> `.LBB_3`) and the padding in front of a comment with it (the ordinal's digits shift the comment's column).  Prints how
+many functions are identical, which differ (with the first differing line), which exist on one side only, and exits 1 when a matched function differs or a parent function has no counterpart.  The `.amdhsa_*` descriptor and the
 metadata behind the functions are not compared: a new trailing kernel argument grows the kernarg segment of every instantiation.
 """
 import argparse
@@ -33,7 +33,7 @@ def functions(path, renames):
             text = "\n".join(body)
             for pat, rep in renames:
                 name, text = pat.sub(rep, name), pat.sub(rep, text)
-            out[name] = re.sub(r"BB\d+_(?=\d)", "BB_", text).split("\n")
+            out[name] = re.sub(r"[ \t]+;", " ;", re.sub(r"BB\d+_(?=\d)", "BB_", text)).split("\n")
             name = None
             continue
         body.append(line)

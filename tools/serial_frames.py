@@ -22,12 +22,8 @@ if os.environ.get("GSWT_VS", "") == "v2":
     r.set_option(L.GSWT_OPT_STRICT_VS, 0)
 if os.environ.get("GSWT_NO_CHUNK_CULL"):
     r.set_option(L.GSWT_OPT_NO_CHUNK_CULL, 1)
-if os.environ.get("GSWT_ITEM_ORDER"):
-    r.set_option(L.GSWT_OPT_ITEM_ORDER, int(os.environ["GSWT_ITEM_ORDER"]))
 if os.environ.get("GSWT_DEPTH_SORT"):
     r.set_option(L.GSWT_OPT_DEPTH_SORT, int(os.environ["GSWT_DEPTH_SORT"]))
-if os.environ.get("GSWT_COMPOSITE"):
-    r.set_option(L.GSWT_OPT_COMPOSITE, int(os.environ["GSWT_COMPOSITE"]))
 order = L.GSWT_ORDER_DEPTH if os.environ.get("GSWT_ORDER", "") == "depth" else L.GSWT_ORDER_REFERENCE
 wang.upload_to(r)
 r.configure(wang.height_map() if int(wang.user.surface_type) == 1 else None)
