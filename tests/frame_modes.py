@@ -1,6 +1,6 @@
 """What the GPU tests of the per-frame modes share (orthographic projection, the anti-aliasing filter, the atmosphere block, the
 tile-style table, the sun shadow: tests/test_ortho_gpu.py, test_antialias_gpu.py, test_atmosphere_gpu.py, test_tile_style_gpu.py,
-test_shadow_gpu.py, and all of them stacked, test_mode_stack_gpu.py).  A mode is a
+test_shadow_gpu.py, all of them stacked, test_mode_stack_gpu.py, and under the debug draw modes, test_debug_modes_gpu.py).  A mode is a
 setting that a frame takes when it is submitted and keeps however it is run: the battery below renders a handful of named states of
 one mode synchronously (`plain_frames`) and wants the same bytes back through graphs, frames in flight, the chunk cull switched
 off, a pair-buffer overflow, output formats and shards.  Frames are 72 x 40 (tests/ortho_ref.py) on the golden cases.
@@ -43,9 +43,9 @@ def bits_equal(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
-def check_against_ref(img, z, ref_img, ref_z):
+def check_against_ref(img, z, ref_img, ref_z, tol=TOL):
     n = ref_z.size
-    bad = (np.abs(img.astype(np.float64) - ref_img.astype(np.float64)) > TOL).any(axis=-1)
+    bad = (np.abs(img.astype(np.float64) - ref_img.astype(np.float64)) > tol).any(axis=-1)
     assert bad.sum() <= 2e-3 * n, int(bad.sum())
     dz = np.abs(z.astype(np.float64) - ref_z.astype(np.float64))
     assert dz[~bad].max() <= ZTOL, float(dz[~bad].max())
@@ -162,21 +162,24 @@ def assemble_column_bands(parts_per_rank, W_, band_w):
 # ---- a mode and its plain frames -----------------------------------------------------------------------------------------------------------
 @dataclass
 class Mode:
-    states: dict                # state name -> (camera block, or None for the plain dict's "cu"; keywords of render / render_async)
+    states: dict                # state name -> (camera block, or None for the plain dict's "cu"; keywords of render / render_async[;
+                                # a scene block in the place of the plain dict's "su": a state that lives there, such as draw_mode])
     set_state: Callable         # set_state(renderer, name) puts the context (not a frame) into a state
     on: object = None           # the name of the state that the single-frame checks use
 
 
 def _submit_kw(s, mode, name):
-    cu, kw = mode.states[name]
-    return (s["cu"] if cu is None else cu), kw
+    """(camera block, keywords, scene block) of a frame of state `name`."""
+    cu, kw, *su = mode.states[name]
+    return (s["cu"] if cu is None else cu), kw, (su[0] if su else s["su"])
 
 
 def render_state(renderer, s, mode, name, **kw):
-    """The synchronous frame of state `name` over the plain dict's scene and background: (colour, depth, pick) unless `kw` says otherwise."""
-    cu, mode_kw = _submit_kw(s, mode, name)
+    """The synchronous frame of state `name` over the plain dict's scene (or the state's own) and background: (colour, depth, pick)
+    unless `kw` says otherwise."""
+    cu, mode_kw, su = _submit_kw(s, mode, name)
     kw = {"depth": True, "pick": True, **kw}
-    return renderer.render(cu, s["su"], W, Hh, **mode_kw, **s["kw"], **kw)
+    return renderer.render(cu, su, W, Hh, **mode_kw, **s["kw"], **kw)
 
 
 def plain_frames(renderer, mode, g, su, cu=None):
@@ -193,8 +196,9 @@ def plain_frames(renderer, mode, g, su, cu=None):
 
 def device_frames(renderer, s, seq, *, waves, submit_kw, then=None):
     """Submits the frames named in `seq` with render_async, `waves` at a time in flight, into buffers of their own; submit_kw(name) gives
-    a frame's camera block and keywords; then(names of the wave) runs between a wave's submits and its waits, and what it sets must
-    not reach the frames already submitted.  Returns their (colour, depth, pick) as numpy arrays."""
+    a frame's camera block and keywords, and optionally a scene block in the place of the plain dict's; then(names of the wave) runs
+    between a wave's submits and its waits, and what it sets must not reach the frames already submitted.  Returns their (colour,
+    depth, pick) as numpy arrays."""
     import torch
     bgc, bgd = torch.from_numpy(s["bgc"]).cuda(), torch.from_numpy(s["bgd"]).cuda()
     outs = [(torch.zeros((Hh, W, 4), dtype=torch.float32, device="cuda"), torch.full((Hh, W), -1.0, dtype=torch.float32, device="cuda"),
@@ -203,8 +207,8 @@ def device_frames(renderer, s, seq, *, waves, submit_kw, then=None):
     for i in range(0, len(seq), waves):
         tickets = []
         for name, (o, z, p) in zip(seq[i:i + waves], outs[i:i + waves]):
-            cu, kw = submit_kw(name)
-            tickets.append(renderer.render_async(cu, s["su"], W, Hh, o.data_ptr(), order_mode=L.GSWT_ORDER_DEPTH, bg_rgba_ptr=bgc.data_ptr(),
+            cu, kw, *su = submit_kw(name)
+            tickets.append(renderer.render_async(cu, su[0] if su else s["su"], W, Hh, o.data_ptr(), order_mode=L.GSWT_ORDER_DEPTH, bg_rgba_ptr=bgc.data_ptr(),
                                                  bg_depth_ptr=bgd.data_ptr(), out_depth_ptr=z.data_ptr(), out_pick_ptr=p.data_ptr(), **kw))
         assert len(set(tickets)) == len(tickets)
         if then is not None:
@@ -388,23 +392,28 @@ def check_v2_refused_at_submit(renderer, s, mode, names, needles, off="off"):
     assert rendered(cam, sc, cfg)
 
 
-def image_case(renderer, cam, order_mode, bg, splat_scale, mode_kw, label, min_cover=0.3, name="case_plane"):
+def image_case(renderer, cam, order_mode, bg, splat_scale, mode_kw, label, min_cover=0.3, name="case_plane", scene=None, tol=TOL,
+               transmittance_eps=0.0):
     """Image, depth and pick of case `name` (the plane case unless said otherwise) under `cam` and the mode keywords against
     tests/depth_ref.py and tests/pick_ref.py over the GPU's own projected records; the context keeps the mode from the debug-varyings
     frame on.  Returns what the caller's own checks need: timings `t`, the frame's `img` and `pick`, `again(**kw)`, the same view and
-    background rendered once more, and the debug-varyings frame's records `sp` and timings `t_debug`."""
+    background rendered once more, and the debug-varyings frame's records `sp` and timings `t_debug`.
+    scene: scene(su) gives the scene block the frames are rendered with, from the view's own (a draw mode, a point-cloud radius);
+    transmittance_eps: of the frames, with `tol` the colour tolerance that goes with it."""
     g, cu, su, proj, _ = view(name, cam, splat_scale)
+    if scene is not None:
+        su = scene(su)
     bind(renderer, g)
     sp, t_debug = varyings(renderer, cu, su, projection=proj, **mode_kw)
     bgc, bgd = DR.bg_images(W, Hh) if bg else (None, None)
     kw = dict(order_mode=order_mode, bg_rgba=bgc, bg_depth=bgd)
-    again = lambda **more: renderer.render(cu, su, W, Hh, projection=proj, **kw, **more)
+    again = lambda **more: renderer.render(cu, su, W, Hh, projection=proj, transmittance_eps=transmittance_eps, **kw, **more)
     img, z, pick = again(depth=True, pick=True)
     t = renderer.timings()
     assert z.shape == (Hh, W) and pick.shape == (Hh, W) and pick.dtype == PICK_DTYPE
     ref_img, ref_z, n_cover = DR.composite(sp, W, Hh, splat_scale=splat_scale, with_cover=True, **kw)
     assert (n_cover > 0).mean() > min_cover and ref_img[..., 3].max() > 0.5
-    dz = check_against_ref(img, z, ref_img, ref_z)
+    dz = check_against_ref(img, z, ref_img, ref_z, tol)
     ev = PR.composite(sp, W, Hh, splat_scale=splat_scale, **kw)
     mi, en = PR.identities(g["draws"])
     label = f"{label} {cam} order={order_mode} bg={bg} scale={splat_scale}"

@@ -187,9 +187,13 @@ def render_kw(pt):
 
 # ---- the base records and what the world gives ---------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def base_records(case, cam, aa, fade):
-    """The oracle's records of the case under the camera with the filter and the fade on or off, `visible` the pair rectangles'."""
+def base_records(case, cam, aa, fade, draw_mode=0, point_cloud_radius=0.0):
+    """The oracle's records of the case under the camera with the filter and the fade on or off, `visible` the pair rectangles'.
+    draw_mode, point_cloud_radius: on a copy of the view's scene block carrying them (tests/debug_modes_ref.py)."""
     g, cu, su, proj, _ = FM.view(case, cam)
+    if draw_mode or point_cloud_radius:
+        su = orc.Scene160.from_buffer_copy(bytes(su))
+        su.draw_mode, su.point_cloud_radius = int(draw_mode), float(point_cloud_radius)
     s = float(AAR.aa_s(AA_VALUE, su.splat_scale)) if aa else 0.0
     fd = None
     if fade:
@@ -313,12 +317,15 @@ def staged_codes_f64(rgb0, sty, s, p, dist, fog_p, order=ORDER, requantise_after
 
 
 # ---- the stack ----------------------------------------------------------------------------------------------------------------------------------
-def stack(pt: Point) -> dict:
+def stack(pt: Point, base=None) -> dict:
     """The expected records of the point.  `base` (geometry of the visible ones), `visible`, `alpha` (binary32, exact), `how` and with it
     `rgb` (binary32 floats, "exact") or `codes` (float64) with `bound` [n] ("bound": codes a byte may be off by) and `masked` [n]; and
-    what the population conditions read: `sty`, `sh`, `dist`, `t`, `F`, `alpha_base` (the unmoded frame's alpha)."""
+    what the population conditions read: `sty`, `sh`, `dist`, `t`, `F`, `alpha_base` (the unmoded frame's alpha).
+    base: other base records of the same instances under the point's filter and fade (tests/debug_modes_ref.py: the point cloud's); what the
+    world gives stays that of the case's own centres, which a point cloud does not move."""
     inp = inputs(pt.case)
-    base = base_records(pt.case, pt.cam, pt.aa, pt.fade)
+    if base is None:
+        base = base_records(pt.case, pt.cam, pt.aa, pt.fade)
     unf = base_records(pt.case, pt.cam, False, False)
     wd = world(pt.case, pt.cam)
     n = base.shape[0]
