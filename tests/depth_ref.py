@@ -95,9 +95,11 @@ def composite(sp, W: int, H: int, *, splat_scale: float = 1.0, order_mode: int =
     return (img, z, n_cover) if with_cover else (img, z)
 
 
-def golden_case(name: str, *, W: int | None = None, H: int | None = None):
+def golden_case(name: str, *, W: int | None = None, H: int | None = None, verts=None):
     """One of tests/golden/make_golden.py's CASES built the way that script builds it (not read from its .npz): the tile set, the
-    oracle's draws, camera and scene uniforms, and the projected instances.  W, H: another frame size for the same view."""
+    oracle's draws, camera and scene uniforms, and the projected instances.  W, H: another frame size for the same view.
+    verts: another tile set ([lod][tile] [n, 62], the case's n_lod LODs of 16 tiles) in the place of synth.make_tileset's, under the
+    same configuration, camera and sort event (tests/hostile_cases.py)."""
     import importlib.util
     import os
 
@@ -111,7 +113,9 @@ def golden_case(name: str, *, W: int | None = None, H: int | None = None):
     spec.loader.exec_module(mg)
     c = mg.CASES[name]
     W, H = W or c["W"], H or c["H"]
-    verts = synth.make_tileset(n_lod=c["n_lod"], n_tile=16, lod0_count=c["lod0"])
+    if verts is None:
+        verts = synth.make_tileset(n_lod=c["n_lod"], n_tile=16, lod0_count=c["lod0"])
+    assert len(verts) == c["n_lod"] and all(len(lod) == 16 for lod in verts)
     pp = orc.preprocess([[orc.scene_load(v) for v in lod] for lod in verts])
     ow = wo.WangTile(pp)
     ou = ow.configure(wo.UserData(**c["cfg"]))

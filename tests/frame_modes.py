@@ -43,6 +43,13 @@ def bits_equal(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
+def bits_equal_or_nan(a, b):
+    """bits_equal, but an element that is a NaN on both sides counts as equal whatever its payload (tests/test_special_splats_gpu.py's rule
+    for records outside the benign region); an Inf, a zero's sign or a finite value must still match bit for bit."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
+
+
 def check_against_ref(img, z, ref_img, ref_z, tol=TOL):
     n = ref_z.size
     bad = (np.abs(img.astype(np.float64) - ref_img.astype(np.float64)) > tol).any(axis=-1)
@@ -77,7 +84,8 @@ def bind(renderer, g):
 
 
 def ortho_cam(which, g, name="case_plane"):
-    args = OR.camera_args(which, lod_pos=g["pos"]) if name == "case_plane" else OR.surface_camera_args(name, which, lod_pos=g["pos"])
+    plane = name in ("case_plane", "case_plane_hostile")
+    args = OR.camera_args(which, lod_pos=g["pos"]) if plane else OR.surface_camera_args(name, which, lod_pos=g["pos"])
     return OR.ortho_camera_of(args)
 
 
@@ -108,8 +116,8 @@ _VIEWS = {}
 def view(name, cam, splat_scale=OR.SPLAT_SCALE):
     """(golden case, camera block, scene block, projection, reference records WITHOUT any mode but the projection) of case `name` under
     camera `cam`: "persp" (the oracle's vertex stage) or one of OR.CAMERAS (on the plane case tests/ortho_ref.py's restatement, on the
-    HeightMap and Sphere cases the oracle's own orthographic stage with the `visible` of its pair rectangles, the product's);
-    computed once."""
+    HeightMap and Sphere cases and on the hostile ones (tests/hostile_cases.py) the oracle's own orthographic stage with the `visible`
+    of its pair rectangles, the product's); computed once."""
     k = (name, cam, splat_scale)
     if k not in _VIEWS:
         g = OR.golden(name)

@@ -98,8 +98,8 @@ CAMERAS = ("top", "oblique")
 
 
 def surface_camera_args(name: str, which: str, lod_pos=None):
-    """The two cameras over the HeightMap / Sphere golden cases (vertex-stage comparisons only)."""
-    if name == "case_hmap":
+    """The two cameras over the HeightMap / Sphere golden cases (vertex-stage comparisons only); a hostile case's are its benign one's."""
+    if name in ("case_hmap", "case_hmap_hostile"):
         if which == "top":
             return dict(kind="top_down", center_xy=(2.0, 2.0), half_extent=6.0, z_top=4.0, z_bottom=-2.0, lod_pos=lod_pos)
         el = math.radians(35.0)
@@ -113,10 +113,12 @@ _CACHE = {}
 
 
 def golden(name="case_plane"):
-    """tests/depth_ref.py's golden case: the scene, and the draws of the case's own perspective sort event."""
+    """tests/depth_ref.py's golden case: the scene, and the draws of the case's own perspective sort event.  case_plane_hostile and
+    case_hmap_hostile: the same case over a hostile tile set (tests/hostile_cases.py)."""
     from tests import depth_ref as DR
+    from tests import hostile_cases as HC
     if name not in _CACHE:
-        _CACHE[name] = DR.golden_case(name)
+        _CACHE[name] = HC.build(name) if HC.is_hostile(name) else DR.golden_case(name)
     return _CACHE[name]
 
 
